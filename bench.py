@@ -8,6 +8,11 @@
 One step = one pass of the hot path over one per-GPU batch of synthetic 640x640 frames already resident in
 HBM: Model.forward through the HIP engine, lp_nms, and (N > 1) the RCCL all-gather of the padded detections.
 Rank 0 prints ONE JSON line.  Workload at N=1: BASELINE.json configs[1] (yololps 640x640 bs=32 fp16).
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, step_ms, config).  --full adds what takes runs of its own: the same K steps with one batch in flight
+(value_inflight1, step_ms_inflight1), the per-op device times and the roofline of the 3x3 layers (roofline, --detail) and
+the CPU baseline (cpu_baseline).  --dump-outputs DIR writes the detections of the last timed step as DIR/*.npy.
 """
 import argparse
 import json
@@ -60,7 +65,16 @@ def parse():
                          '(default: profiles/r04_pmc_traffic[_<workload>].json)')
     ap.add_argument('--profile-inner', type=int, default=4, help='back-to-back launches of each op per event pair in the per-op '
                     'timing (amortises the cost of the event pair itself)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='also measure what the headline figure does not need: the same steps with '
+                    'one batch in flight, per-op device times and the roofline (and --detail), the CPU baseline')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='after the timed steps, write what the last timed step '
+                    'computed (the detections its caller receives) to DIR/<name>.npy')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.detail and not args.full:
+        ap.error('--detail is part of the per-op timing: it needs --full')
+    return args
 
 
 def host_cores():
@@ -104,6 +118,33 @@ def cpu_baseline(model_name, sigma, size, conf, iou, max_det, budget_s):
     return {'value': round(n * B / el, 3), 'unit': 'images/s', 'cores': cores, 'kind': 'port',
             'sample': '%d steps of %d images %dx%d, %s fp32, oracle/lp_oracle.py forward + oracle/lp_post_ref.c NMS, '
                       '%d torch threads' % (n, B, size, size, model_name, cores)}
+
+
+DUMP_BYTES = 64 << 20      # cap of --dump-outputs
+
+
+def dump_outputs(dirname, det, count):
+    """The last timed step's result as its caller receives it: det [B, max_det, 28] fp32 and count [B].  Rows past count[b]
+    are padding the kernels leave unwritten: zeroed, so that two builds compare element for element.  Above DUMP_BYTES a
+    fixed, seeded sample of images is written, with their indices (image_index.npy)."""
+    import numpy as np
+    det = det.float().cpu().numpy()
+    count = count.cpu().numpy().astype(np.int64)
+    out = {}
+    per_image = det[0].nbytes if len(det) else 0
+    if per_image and det.nbytes > DUMP_BYTES:
+        keep = max(1, DUMP_BYTES // per_image - 1)
+        idx = np.sort(np.random.default_rng(0).choice(len(det), keep, replace=False))
+        det, count = det[idx], count[idx]
+        out['image_index'] = idx.astype(np.float64)
+    det = det.copy()
+    for b, n in enumerate(count):
+        det[b, n:] = 0.0
+    out['detections'] = det.astype(np.float32)
+    out['counts'] = count.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def main():
@@ -258,9 +299,11 @@ def main():
     with torch.no_grad():
         elapsed, t_issue, dev_ms, out = timed(pipe, depth)
         stats = step_stats()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, *out)
         # the same K steps with ONE batch in flight (a single engine; the NMS of a step still runs on the post stream under
         # the next forward): what a caller gets who hands over one batch at a time
-        if depth > 1:
+        if args.full and depth > 1:
             elapsed1, _, _, _ = timed(None, 1)
             stats1 = step_stats()
         else:
@@ -271,8 +314,8 @@ def main():
     elapsed, elapsed1 = float(el[0].item()), float(el[1].item())
     counts = out[1].float().mean().item()
 
-    result = None
-    if rank == 0:
+    def roofline_figures():
+        """--full: per-op device times of one forward (--detail writes them), the NMS's, and the roofline built on them."""
         # per-op device time (hipEvent pairs on torch's current stream, inside lp_engine_profile)
         ops = eng.profile(x, reps=5, inner=max(1, args.profile_inner))
         t_nms = []
@@ -385,13 +428,21 @@ def main():
                                                 % (os.path.relpath(args.roofline_file, ROOT), rf_ok['steps'])})
             if tf_ok is not None and tf_ok.get('forward_hbm_bytes_per_step'):
                 roofline['traffic'] = tf_ok['forward_hbm_bytes_per_step']
+        return roofline
+
+    result = None
+    if rank == 0:
         result = {
             'metric': METRIC, 'value': round(world * B * args.steps / elapsed, 2), 'unit': 'images/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': round(elapsed / args.steps * 1e3, 4), 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
-            'value_inflight1': round(world * B * args.steps / elapsed1, 2),
-            'step_ms': stats, 'step_ms_inflight1': stats1,
+            'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic'}
+        if args.full:
+            result['value_inflight1'] = round(world * B * args.steps / elapsed1, 2)
+        result['step_ms'] = stats
+        if args.full:
+            result['step_ms_inflight1'] = stats1
+        result.update({
             'config': {'workload': '%s %dx%d bs=%d/GPU %s, synthetic frames resident in HBM, seeded random-init weights '
                                    '(sigma %.2f), conf %.2f iou %.2f max_det %d'
                                    % (args.model, args.size, args.size, B, args.dtype, sigma, args.conf, args.iou, args.max_det),
@@ -402,12 +453,12 @@ def main():
                                    if depth > 1 else 'forward || NMS(+gather) of the previous step') if overlap else 'single stream',
                        'mean_detections_per_image': round(counts, 1),
                        'host_enqueue_ms_per_step': round(t_issue / args.steps * 1e3, 3),
-                       'device_ms_per_step': round(dev_ms / args.steps, 3)},
-            'roofline': roofline,
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            result['cpu_baseline'] = cpu_baseline(args.model, sigma, args.size, args.conf, args.iou, args.max_det,
-                                                  args.cpu_seconds)
+                       'device_ms_per_step': round(dev_ms / args.steps, 3)}})
+        if args.full:
+            result['roofline'] = roofline_figures()
+            if world == 1 and not args.no_cpu_baseline:
+                result['cpu_baseline'] = cpu_baseline(args.model, sigma, args.size, args.conf, args.iou, args.max_det,
+                                                      args.cpu_seconds)
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()

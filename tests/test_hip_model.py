@@ -891,7 +891,7 @@ def test_bench_under_the_distributed_launcher():
     port = 29700 + os.getpid() % 200
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
-           '--no-cpu-baseline']
+           '--full', '--no-cpu-baseline']
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     r = subprocess.run(cmd, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
@@ -901,6 +901,32 @@ def test_bench_under_the_distributed_launcher():
     assert d['n_gpus'] == 1 and d['config']['parallelism'].startswith('dp1') and d['steps'] == 3
     assert np.isfinite(d['value']) and d['value'] > 0 and d['unit'] == 'images/s' and d['scaling'] == 'weak'
     assert 'roofline' in d and d['roofline']['bound'] in ('mfma', 'hbm')
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain ``bench.py`` run (no --full) times exactly --steps steps, prints the headline fields only, and --dump-outputs
+    writes the detections of the last timed step: det [B, max_det, 28] fp32 with zeroed padding rows, counts [B]."""
+    import json
+    import subprocess
+    import sys
+    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '4',
+           '--dump-outputs', str(tmp_path)]
+    r = subprocess.run(cmd, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout.decode()[-2000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['dtype'] == 'f16' and d['unit'] == 'images/s' and d['higher_is_better'] is True
+    assert np.isfinite(d['value']) and d['value'] > 0 and d['ms_per_step'] > 0
+    assert abs(d['value'] - 4 * 1e3 / d['ms_per_step']) <= 0.01 * d['value']
+    for k in ('roofline', 'cpu_baseline', 'value_inflight1', 'step_ms_inflight1'):
+        assert k not in d, k
+    det, cnt = np.load(tmp_path / 'detections.npy'), np.load(tmp_path / 'counts.npy')
+    assert det.dtype == np.float32 and det.shape == (4, 1000, 28) and cnt.dtype == np.float64 and cnt.shape == (4,)
+    assert np.all(np.isfinite(det)) and np.all((cnt >= 0) & (cnt <= 1000)) and cnt.sum() > 0
+    for b, n in enumerate(cnt.astype(int)):
+        assert not det[b, n:].any() and det[b, :n].any(axis=1).all()
+    assert abs(cnt.mean() - d['config']['mean_detections_per_image']) <= 0.051
 
 
 def test_gather_detections_rccl_on_side_stream():

@@ -243,3 +243,26 @@ def test_pmc_traffic_arithmetic(tmp_path):
     assert r['fetch_bytes_per_launch'] == round(1500 / 2 * 1024 * 2) and r['write_bytes_per_launch'] == round(750 / 2 * 1024)
     assert r['hbm_bytes_per_launch'] == r['fetch_bytes_per_launch'] + r['write_bytes_per_launch']
     assert r['forward_hbm_bytes_per_step'] == round(1700 * 1024 * 2 + 850 * 1024)
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on CPU tensors: det / counts as float32 / float64 .npy with the unwritten padding rows zeroed;
+    above the size cap a fixed, seeded sample of images, the same on every call, with its indices."""
+    import bench
+    g = torch.Generator().manual_seed(5)
+    det = torch.rand(6, 10, 28, generator=g) + 0.5
+    count = torch.tensor([0, 3, 10, 5, 1, 7], dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / 'all'), det, count)
+    d, c = np.load(tmp_path / 'all' / 'detections.npy'), np.load(tmp_path / 'all' / 'counts.npy')
+    assert sorted(os.listdir(tmp_path / 'all')) == ['counts.npy', 'detections.npy']
+    assert d.dtype == np.float32 and d.shape == (6, 10, 28) and c.dtype == np.float64 and c.tolist() == [0, 3, 10, 5, 1, 7]
+    for b, n in enumerate(count.tolist()):
+        assert np.array_equal(d[b, :n], det[b, :n].numpy()) and not d[b, n:].any()
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 3 * 10 * 28 * 4)
+    for sub in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / sub), det, count)
+    idx = np.load(tmp_path / 's1' / 'image_index.npy')
+    assert np.array_equal(idx, np.load(tmp_path / 's2' / 'image_index.npy')) and len(idx) == 2 and np.all(np.diff(idx) > 0)
+    s = np.load(tmp_path / 's1' / 'detections.npy')
+    assert s.shape == (2, 10, 28) and np.array_equal(s, d[idx.astype(int)])
+    assert np.array_equal(np.load(tmp_path / 's1' / 'counts.npy'), c[idx.astype(int)])

@@ -7,7 +7,7 @@ try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
     print('$1', 'value', d['value'], 'inflight1', d['value_inflight1'], 'fwd_dev_ms', r['forward_device_ms'], '3x3', r['achieved'], 'step', d['step_ms'], 'step1', d['step_ms_inflight1'])
 except Exception as e: print('$1', 'FAILED', e)"; }
-run() { tag=$1; shift; echo "== $tag"; timeout -k 10 240 env "$@" python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline 2>$out/$tag.err | tee $out/$tag.json | line "$tag" | tee -a $out/summary.txt; }
+run() { tag=$1; shift; echo "== $tag"; timeout -k 10 240 env "$@" python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline 2>$out/$tag.err | tee $out/$tag.json | line "$tag" | tee -a $out/summary.txt; }
 run base A=1
 run nopipe LP_NO_PIPE=1
 run hwq8 GPU_MAX_HW_QUEUES=8

@@ -14,15 +14,15 @@ print('$1', 'value', d['value'], 'inflight1', d.get('value_inflight1'), 'ms_per_
 {
 for rep in 1 2 3; do
   unset LP_NO_BOX_SPARSE
-  timeout -k 10 300 python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | one "sparse lps"
+  timeout -k 10 300 python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | one "sparse lps"
   export LP_NO_BOX_SPARSE=1
-  timeout -k 10 300 python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | one "dense  lps"
+  timeout -k 10 300 python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | one "dense  lps"
 done
 for rep in 1 2; do
   unset LP_NO_BOX_SPARSE
-  timeout -k 10 300 python3 bench.py --model yololpn --batch 128 --steps 30 --warmup 3 --no-cpu-baseline 2>/dev/null | one "sparse lpn"
+  timeout -k 10 300 python3 bench.py --full --model yololpn --batch 128 --steps 30 --warmup 3 --no-cpu-baseline 2>/dev/null | one "sparse lpn"
   export LP_NO_BOX_SPARSE=1
-  timeout -k 10 300 python3 bench.py --model yololpn --batch 128 --steps 30 --warmup 3 --no-cpu-baseline 2>/dev/null | one "dense  lpn"
+  timeout -k 10 300 python3 bench.py --full --model yololpn --batch 128 --steps 30 --warmup 3 --no-cpu-baseline 2>/dev/null | one "dense  lpn"
 done
 } > gpurun_out/r4_box_ab.txt 2>&1
 cat gpurun_out/r4_box_ab.txt

@@ -4,8 +4,8 @@
 tag=${1:-r04}
 cd "$GRAFT_REPO_ROOT" || exit 1
 out=gpurun_out/prof_$tag; mkdir -p $out
-timeout -k 10 300 python3 bench.py --model yololpn --batch 128 --steps 30 --warmup 3 --no-cpu-baseline --detail $out/per_op_yololpn_bs128.txt > $out/bench_yololpn_bs128.json 2>/dev/null || exit 1
-timeout -k 10 400 python3 bench.py --model yolov6m --batch 8 --size 1280 --dtype bf16 --steps 20 --warmup 3 --no-cpu-baseline --detail $out/per_op_yolov6m_1280.txt > $out/bench_yolov6m_1280.json 2>/dev/null || exit 1
+timeout -k 10 300 python3 bench.py --full --model yololpn --batch 128 --steps 30 --warmup 3 --no-cpu-baseline --detail $out/per_op_yololpn_bs128.txt > $out/bench_yololpn_bs128.json 2>/dev/null || exit 1
+timeout -k 10 400 python3 bench.py --full --model yolov6m --batch 8 --size 1280 --dtype bf16 --steps 20 --warmup 3 --no-cpu-baseline --detail $out/per_op_yolov6m_1280.txt > $out/bench_yolov6m_1280.json 2>/dev/null || exit 1
 python3 - $out <<'P'
 import json, sys
 out = sys.argv[1]

@@ -11,9 +11,9 @@ A="--model yolov6m --batch 8 --size 1280 --dtype bf16 --steps 30 --warmup 3 --no
 for rep in 1 2 3; do
   unset LP_NO_MFMA16
   timeout -k 10 300 python3 _r03/bench.py $A 2>/dev/null | one r03
-  timeout -k 10 300 python3 bench.py $A 2>/dev/null | one r04
+  timeout -k 10 300 python3 bench.py --full $A 2>/dev/null | one r04
   export LP_NO_MFMA16=1
-  timeout -k 10 300 python3 bench.py $A 2>/dev/null | one r04_nomfma16
+  timeout -k 10 300 python3 bench.py --full $A 2>/dev/null | one r04_nomfma16
 done
 } > gpurun_out/r4_v6m_ab.txt 2>&1
 cat gpurun_out/r4_v6m_ab.txt

@@ -11,13 +11,13 @@ mkdir -p gpurun_out
 {
 for rep in 1 2 3; do
   timeout -k 10 300 python3 $REF/bench.py --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | sec "$LA yololps_bs32"
-  timeout -k 10 300 python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | sec "$LB yololps_bs32"
+  timeout -k 10 300 python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | sec "$LB yololps_bs32"
 done
 for rep in 1 2; do
   timeout -k 10 300 python3 $REF/bench.py --model yolov6m --batch 8 --size 1280 --dtype bf16 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | sec "$LA yolov6m_1280_bs8"
-  timeout -k 10 300 python3 bench.py --model yolov6m --batch 8 --size 1280 --dtype bf16 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | sec "$LB yolov6m_1280_bs8"
+  timeout -k 10 300 python3 bench.py --full --model yolov6m --batch 8 --size 1280 --dtype bf16 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | sec "$LB yolov6m_1280_bs8"
   timeout -k 10 300 python3 $REF/bench.py --model yololpn --batch 128 --steps 30 --warmup 3 --no-cpu-baseline 2>/dev/null | sec "$LA yololpn_bs128"
-  timeout -k 10 300 python3 bench.py --model yololpn --batch 128 --steps 30 --warmup 3 --no-cpu-baseline 2>/dev/null | sec "$LB yololpn_bs128"
+  timeout -k 10 300 python3 bench.py --full --model yololpn --batch 128 --steps 30 --warmup 3 --no-cpu-baseline 2>/dev/null | sec "$LB yololpn_bs128"
 done
 } > gpurun_out/round_ab_$LB.txt 2>&1
 cat gpurun_out/round_ab_$LB.txt

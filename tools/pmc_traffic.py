@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Per-launch HBM traffic of the dominant kernel (3x3 conv_mfma_kernel launches) from two rocprofv3 --pmc passes.
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    python tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write --steps 3 --launches 47 > profiles/r02_pmc_traffic.json
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d pmc_fetch -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d pmc_write -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > bench.json
+    python tools/pmc_traffic.py pmc_fetch pmc_write --steps 3 --bench bench.json > profiles/r02_pmc_traffic.json
 
 Counters are taken from the LAST steps*launches matching dispatches (the timed steps; earlier ones belong to warm-up
 and to the autotuner).  Corrections per MI355X_MICROARCH.md (HBM section): FETCH_SIZE / WRITE_SIZE are in KiB;

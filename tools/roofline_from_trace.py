@@ -3,8 +3,8 @@
 algorithmic FLOPs of the 3x3 convolution layers of a step / the summed kernel-trace duration of their dispatches in the
 TIMED steps (the last steps x launches_per_step matching dispatches; everything before belongs to warm-up and the tuner).
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/kt1 -- python3 bench.py --steps 50 --warmup 5 --inflight 1 --no-cpu-baseline > bench.json
-    python tools/roofline_from_trace.py gpurun_out/kt1 bench.json --steps 50 > profiles/r03_roofline.json
+    rocprofv3 --kernel-trace --output-format csv -d kt1 -- python3 bench.py --full --steps 50 --warmup 5 --inflight 1 --no-cpu-baseline > bench.json
+    python tools/roofline_from_trace.py kt1 bench.json --steps 50 > profiles/r03_roofline.json
 
 (one batch in flight, one execution lane: kernels do not overlap, so a dispatch's duration is its own).  The file records the hash of
 the kernel sources; bench.py reports the figure as roofline.frac only when that hash is the running build's.
@@ -39,7 +39,7 @@ def main():
     for f in glob.glob(a.trace_dir + '/**/*kernel_trace.csv', recursive=True):
         rows += [(int(x['Start_Timestamp']), int(x['End_Timestamp']), x['Kernel_Name']) for x in csv.DictReader(open(f))]
     rows.sort()
-    # the timed steps: bench.py ends with five forward + lp_nms timings (five greedy_kernel dispatches) behind the K timed steps;
+    # the timed steps: bench.py --full ends with five forward + lp_nms timings (five greedy_kernel dispatches) behind the K timed steps;
     # a step's NMS runs under the next forward, so the window between the greedy dispatches of steps i0 and i0 + K holds K forwards
     g = [i for i, (s_, e_, n) in enumerate(rows) if 'greedy_kernel' in n]
     if len(g) < a.steps + 6:
