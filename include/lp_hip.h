@@ -262,6 +262,27 @@ int lp_preprocess_letterbox(const unsigned char* img, int h0, int w0, void* out,
                             int top, int left, void* stream);
 int lp_rescale_round(float* det, int n, double ratio, double padx, double pady, int img_w, int img_h, void* stream);
 
+/* Batched forms of the two entry points above for B frames of any source sizes (the same restatement of inferer.py:191-228
+ * and data_augment.py:30-61, one launch per LP_FRAMES_PER_LAUNCH frames; descriptors travel as kernel arguments, so neither
+ * call uploads anything and both may be captured in a graph).
+ *
+ * lp_preprocess_letterbox_batch: out [B,3,H,W] of out_dtype.  Slot b < n_frames is bit-identical to lp_preprocess_letterbox
+ * with desc[b] into [3,H,W]; slots n_frames <= b < B are padding (114/255 everywhere).  desc is a HOST array of n_frames
+ * entries; every entry is checked with the single-frame rules before anything is launched (LP_ERR_ARG names the frame).
+ *
+ * lp_rescale_round_batch: det [B,max_det,28] in place; for image b, rows r < min(count[b], max_det) (count: DEVICE int32 [B],
+ * read by the kernel: no host sync) are rescaled exactly as lp_rescale_round(det[b], n, desc[b]...) would.  Rows at or beyond
+ * the count and columns 12..27 are left untouched.  desc is a HOST array of B entries. */
+#define LP_FRAMES_PER_LAUNCH 64
+typedef struct lp_frame_desc {
+    const unsigned char* img;   /* device uint8 [h0,w0,3] BGR, any alignment */
+    int h0, w0, rh, rw, top, left;
+} lp_frame_desc;
+typedef struct lp_rescale_desc { double ratio, padx, pady; int img_w, img_h; } lp_rescale_desc;
+int lp_preprocess_letterbox_batch(const lp_frame_desc* desc, int n_frames, int B, void* out, int out_dtype, int H, int W,
+                                  void* stream);
+int lp_rescale_round_batch(float* det, const int32_t* count, int B, int max_det, const lp_rescale_desc* desc, void* stream);
+
 /* lp_eval_counts: the matching loops of Evaler.eval (yolov6/core/evaler.py:153-243, box_iou general.py:93-115) for a
  * batch of images, one workgroup per image.
  *   det [B,max_det,28] fp32 + det_count [B]: detections as lp_nms returns them (xyxy, 8 corner coords, 8 confs, 8 ids)

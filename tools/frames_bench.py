@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""Frames benchmark: rescaled detections from host frames, end to end, per frame and batched.
+
+    python tools/frames_bench.py [--model yololps] [--size 640] [--dtype f16] [--frame 1080 1920] [--batches 8 32 64]
+
+Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
+  - frames/s of the per-frame path (upload, lp_preprocess_letterbox, detect at B=1 with hipGraph replay, lp_rescale_round,
+    host read: what Inferer.infer does per frame) and of FrameBatcher + detect_frames at each batch size;
+  - the device time of each stage of one batch from events (H2D from pinned memory, letterbox, detect, rescale) and the
+    stage that bounds the batched path;
+  - the letterbox kernel's GB/s over the bytes it must move: the source rows it samples plus its output.
+The model is the synthetic recipe of bench.py (same weights scale), prepared as Inferer prepares it.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+SIGMA = {'yololps': 0.25, 'yololpn': 0.6}
+
+
+def parse():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--model', default='yololps', choices=list(SIGMA))
+    ap.add_argument('--size', type=int, default=640)
+    ap.add_argument('--dtype', default='f16', choices=['f16', 'f32'])
+    ap.add_argument('--frame', nargs=2, type=int, default=[1080, 1920], metavar=('H', 'W'))
+    ap.add_argument('--batches', nargs='+', type=int, default=[8, 32, 64])
+    ap.add_argument('--frames', type=int, default=256, help='frames per timed run of the batched path')
+    ap.add_argument('--single-frames', type=int, default=128, help='frames per timed run of the per-frame path')
+    ap.add_argument('--distinct', type=int, default=16, help='distinct seeded frames, cycled')
+    ap.add_argument('--reps', type=int, default=5, help='event-timed repetitions of each stage')
+    ap.add_argument('--conf', type=float, default=0.4)
+    ap.add_argument('--iou', type=float, default=0.45)
+    ap.add_argument('--max-det', type=int, default=1000)
+    return ap.parse_args()
+
+
+def sampled_rows(h0, rh):
+    """Distinct source rows the bilinear resize reads for rh output rows (the y0 / y1 of resize_coef, lp_internal.h)."""
+    if rh == h0:
+        return h0
+    d = np.arange(rh, dtype=np.float64)
+    f = ((d + 0.5) * (h0 / rh) - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int64)
+    s = np.clip(s, 0, h0 - 1)
+    return len(np.union1d(s, np.minimum(s + 1, h0 - 1)))
+
+
+def main():
+    args = parse()
+    import torch
+    from yolov6.utils.synth import build_synthetic
+    from yolov6.utils.torch_utils import fuse_model
+    from yolov6.layers.common import RepVGGBlock
+    from yolov6.hip import runtime
+    from yolov6.core.frames import FrameBatcher, letterbox_hw
+    from yolov6.data.data_augment import letterbox_geometry
+    if not torch.cuda.is_available():
+        raise SystemExit('frames_bench.py measures the GPU path: no GPU')
+    dev = torch.device('cuda', 0)
+    tdt = {'f16': torch.float16, 'f32': torch.float32}[args.dtype]
+    model = fuse_model(build_synthetic(os.path.join(ROOT, 'configs', args.model + '.py'), sigma=SIGMA[args.model])).eval()
+    for layer in model.modules():
+        if isinstance(layer, RepVGGBlock):
+            layer.switch_to_deploy()
+    model = model.to(dev).to(tdt)
+    model.lp_graph = True                   # as Inferer sets it
+    size, stride = [args.size, args.size], int(model.stride.max())
+    h0, w0 = args.frame
+    rng = np.random.default_rng(0)
+    pool = [rng.integers(0, 256, (h0, w0, 3), dtype=np.uint8) for _ in range(args.distinct)]
+    H, W = letterbox_hw((h0, w0), size, stride)
+    conf, iou, max_det = args.conf, args.iou, args.max_det
+    sync = torch.cuda.synchronize
+    out = dict(metric='frames/s end to end (host frames in, rescaled detections out)', model=args.model, dtype=args.dtype,
+               frame=[h0, w0], net=[H, W])
+
+    # ---- per-frame path (Inferer.infer at batch_size 1) --------------------------------------------------------------
+    def one(f):
+        frame = torch.from_numpy(f).to(dev)
+        img = runtime.preprocess_letterbox(frame, size, stride, tdt)
+        det = runtime.detect(model, img[None], conf, iou, max_det)[0]
+        if len(det):
+            runtime.rescale_round(img.shape[1:], det, f.shape)
+        return det.cpu()
+
+    with torch.no_grad():
+        runtime.prepare_for(model, (1, 3, H, W), tdt)
+        for i in range(8):
+            one(pool[i % len(pool)])
+        sync()
+        t0 = time.perf_counter()
+        for i in range(args.single_frames):
+            one(pool[i % len(pool)])
+        sync()
+        out['per_frame_fps'] = round(args.single_frames / (time.perf_counter() - t0), 1)
+
+        # ---- batched path: FrameBatcher + detect_frames ---------------------------------------------------------------
+        batched, stages = {}, {}
+        for B in args.batches:
+            runtime.prepare_for(model, (B, 3, H, W), tdt)
+            batcher = FrameBatcher(dev)
+            x = torch.empty(B, 3, H, W, dtype=tdt, device=dev)
+            def run(k):
+                fr = [pool[(k * B + j) % len(pool)] for j in range(B)]
+                return runtime.detect_frames(model, batcher.put(fr), size, conf, iou, max_det, batch=B, out=x)
+            for k in range(2):
+                run(k)
+            sync()
+            nb = max(2, args.frames // B)
+            t0 = time.perf_counter()
+            for k in range(nb):
+                run(k)
+            sync()
+            batched[str(B)] = round(nb * B / (time.perf_counter() - t0), 1)
+
+            # device time per stage of one batch, from events on one stream
+            fr = [pool[j % len(pool)] for j in range(B)]
+            nbytes = sum(f.nbytes for f in fr)
+            host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            hv = host.numpy()
+            for j, f in enumerate(fr):
+                hv[j * f.nbytes:(j + 1) * f.nbytes] = f.reshape(-1)
+            dbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            views = [dbuf[j * f.nbytes:(j + 1) * f.nbytes].view(f.shape) for j, f in enumerate(fr)]
+            times = {k: [] for k in ('h2d', 'letterbox', 'detect', 'rescale')}
+            for _ in range(args.reps + 1):
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+                ev[0].record()
+                dbuf.copy_(host, non_blocking=True)
+                ev[1].record()
+                xx, _ = runtime.preprocess_frames(views, size, stride, tdt, batch=B, out=x)
+                ev[2].record()
+                det, count, _ = runtime.detect_padded(model, xx, conf, iou, max_det)
+                ev[3].record()
+                runtime.rescale_round_batch(det, count, (H, W), [f.shape for f in fr])
+                ev[4].record()
+                sync()
+                for i, k in enumerate(times):
+                    times[k].append(ev[i].elapsed_time(ev[i + 1]))
+            med = {k: float(np.median(v[1:])) for k, v in times.items()}
+            stages[str(B)] = {k: round(v, 4) for k, v in med.items()}
+            e2e_ms = B * 1000.0 / batched[str(B)]
+            stages[str(B)]['host_other'] = round(max(0.0, e2e_ms - sum(med.values())), 4)
+            stages[str(B)]['bound_by'] = max(('h2d', 'letterbox', 'detect', 'rescale', 'host_other'), key=lambda k: stages[str(B)][k])
+            _, (rw, rh), _, _ = letterbox_geometry((h0, w0), size, stride=stride)
+            moved = B * (sampled_rows(h0, rh) * w0 * 3 + 3 * H * W * x.element_size())
+            stages[str(B)]['letterbox_MB'] = round(moved / 1e6, 2)
+            stages[str(B)]['letterbox_GBps'] = round(moved / (med['letterbox'] * 1e-3) / 1e9, 1)
+            del host, dbuf, views
+    out['batched_fps'] = batched
+    out['stage_ms'] = stages
+    out['speedup_vs_per_frame'] = {b: round(v / out['per_frame_fps'], 1) for b, v in batched.items()}
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()

@@ -41,6 +41,21 @@ template <typename K> inline int set_max_lds_once(K kernel, int bytes, std::atom
     return LP_OK;
 }
 
+// Per-axis coefficients of the OpenCV INTER_LINEAR fixed-point resize (lp_prepost.hip, lp_frames.hip): source index and the
+// two 11-bit weights of destination index d at scale src/dst.
+__device__ __forceinline__ void resize_coef(int d, double scale, int src, int* s0, int* a0, int* a1) {
+    // cv::resize: fx = (dx + 0.5) * scale - 0.5 ; sx = floor(fx) ; fx -= sx ; clamps at the borders
+    float f = (float)((d + 0.5) * scale - 0.5);
+    int s = (int)floorf(f);
+    f -= (float)s;
+    if (s < 0) { f = 0.f; s = 0; }
+    if (s >= src - 1) { f = 0.f; s = src - 1; }
+    *s0 = s;
+    const float c0 = (1.f - f) * 2048.f, c1 = f * 2048.f;
+    *a0 = (int)rintf(c0);   // saturate_cast<short>(cvRound(v * INTER_RESIZE_COEF_SCALE))
+    *a1 = (int)rintf(c1);
+}
+
 inline size_t dtype_size(int dt) { return dt == LP_F32 ? 4 : 2; }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }

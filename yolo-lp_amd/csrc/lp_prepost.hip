@@ -12,19 +12,6 @@
 
 namespace lp {
 
-__device__ __forceinline__ void resize_coef(int d, double scale, int src, int* s0, int* a0, int* a1) {
-    // cv::resize: fx = (dx + 0.5) * scale - 0.5 ; sx = floor(fx) ; fx -= sx ; clamps at the borders
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { f = 0.f; s = 0; }
-    if (s >= src - 1) { f = 0.f; s = src - 1; }
-    *s0 = s;
-    const float c0 = (1.f - f) * 2048.f, c1 = f * 2048.f;
-    *a0 = (int)rintf(c0);   // saturate_cast<short>(cvRound(v * INTER_RESIZE_COEF_SCALE))
-    *a1 = (int)rintf(c1);
-}
-
 template <typename TO>
 __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __restrict__ img, int h0, int w0, TO* __restrict__ out,
                                                         int H, int W, int rh, int rw, int top, int left, double sy, double sx,

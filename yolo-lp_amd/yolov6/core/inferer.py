@@ -26,8 +26,13 @@ from yolov6.utils.nms import non_max_suppression
 
 
 class Inferer:
-    def __init__(self, source, weights, device, yaml, img_size, half):
+    def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True):
+        """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_infer_batched``);
+        ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple)."""
         self.__dict__.update(locals())
+        if int(batch_size) < 1:
+            raise ValueError('batch_size must be >= 1')
+        self.batch_size = int(batch_size)
         self.device = device
         self.img_size = img_size
         cuda = self.device != 'cpu' and torch.cuda.is_available()
@@ -64,6 +69,8 @@ class Inferer:
     def infer(self, conf_thres, iou_thres, classes, agnostic_nms, max_det, save_dir, save_txt, save_img, hide_labels,
               hide_conf, view_img=True):
         """Run every source image through model + NMS; returns the list of rescaled ``[n, 28]`` detections."""
+        if self.device.type != 'cpu' and self.batch_size > 1:
+            return self._infer_batched(conf_thres, iou_thres, max_det, save_dir, save_txt, save_img)
         fps = CalcFPS()
         results = []
         for img_src, img_path, _ in self.files:
@@ -71,9 +78,9 @@ class Inferer:
                 from yolov6.hip import runtime
                 frame = torch.from_numpy(np.ascontiguousarray(img_src)).to(self.device)
                 img = runtime.preprocess_letterbox(frame, self.img_size, self.stride,
-                                                   torch.float16 if self.half else torch.float32)
+                                                   torch.float16 if self.half else torch.float32, auto=self.auto)
             else:
-                img, img_src = self.precess_image(img_src, self.img_size, self.stride, self.half)
+                img, img_src = self.precess_image(img_src, self.img_size, self.stride, self.half, auto=self.auto)
                 img = img.to(self.device)
             if len(img.shape) == 3:
                 img = img[None]
@@ -91,34 +98,93 @@ class Inferer:
             t2 = time.time()
             fps.update(1.0 / max(t2 - t1, 1e-9))
 
-            rel_path = osp.relpath(osp.dirname(img_path), osp.dirname(self.source))
-            save_path = osp.join(save_dir, rel_path, osp.basename(img_path))
-            txt_path = osp.join(save_dir, rel_path, osp.splitext(osp.basename(img_path))[0])
-            if save_txt or save_img:
-                os.makedirs(osp.join(save_dir, rel_path), exist_ok=True)
-            gn = torch.tensor(img_src.shape)[[1, 0, 1, 0]]
-            gn_cor = torch.tensor(img_src.shape)[[1, 0, 1, 0, 1, 0, 1, 0]]
             if len(det):
                 if det.is_cuda:
                     from yolov6.hip import runtime
                     runtime.rescale_round(img.shape[2:], det, img_src.shape)
                 else:
                     det[:, :12] = self.rescale(img.shape[2:], det[:, :12], img_src.shape).round()
-                rows = det.detach().float().cpu()
-                if save_txt:
-                    with open(txt_path + '.txt', 'a') as f:
-                        for output in rows:
-                            xywh = (self.box_convert(output[:4].view(1, 4)) / gn).view(-1).tolist()
-                            corners_gn = (output[4:12] / gn_cor).tolist()
-                            line = (*output[20:].tolist(), *xywh, *corners_gn)
-                            f.write(('%g ' * len(line)).rstrip() % line + '\n')
-                if save_img:
-                    self.save_annotated(img_src, rows, save_path)
-            elif save_img:
-                self.save_annotated(img_src, [], save_path)
+            self.save_outputs(img_src, img_path, det, save_dir, save_txt, save_img)
             results.append(det)
         LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
         return results
+
+    def _infer_batched(self, conf_thres, iou_thres, max_det, save_dir, save_txt, save_img):
+        """``infer`` with ``batch_size`` frames per forward: consecutive frames of one letterboxed shape (``plan_batches``) go
+        through ``runtime.detect_frames`` together.  Image files are decoded on a small thread pool ahead of the GPU, each
+        batch is uploaded with one copy from pinned memory (``FrameBatcher``), and a short group is padded to the bound batch
+        size so that the engine is never set up for a new one.  Writes and returns per frame, in source order, exactly
+        what the per-frame loop does; the FPS figure is per frame (batch time / frames in the batch)."""
+        from yolov6.hip import runtime
+        from yolov6.core.frames import FrameBatcher, letterbox_hw, plan_batches, prefetch_frames
+        from yolov6.data.datasets import imread_bgr
+        B, dtype = self.batch_size, (torch.float16 if self.half else torch.float32)
+        batcher = FrameBatcher(self.device)
+        inputs = {}                     # (H, W) -> persistent [B,3,H,W] input buffer
+        fps = CalcFPS()
+        results = []
+        frames = self._frames_ahead(prefetch_frames, imread_bgr)
+        window = deque()
+        while True:
+            while len(window) < B:
+                nxt = next(frames, None)
+                if nxt is None:
+                    break
+                window.append(nxt)
+            if not window:
+                break
+            group = plan_batches([f.shape for f, _ in window], self.img_size, self.stride, B, self.auto)[0]
+            items = [window.popleft() for _ in group]
+            H, W = letterbox_hw(items[0][0].shape, self.img_size, self.stride, self.auto)
+            x = inputs.get((H, W))
+            if x is None:
+                x = inputs[(H, W)] = torch.empty(B, 3, H, W, dtype=dtype, device=self.device)
+            runtime.prepare_for(self.model.model, x.shape, dtype)      # a new shape tunes once: outside the FPS window
+            t1 = time.time()
+            dev_frames = batcher.put([f for f, _ in items])
+            dets = runtime.detect_frames(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det,
+                                         auto=self.auto, batch=B, out=x)
+            t2 = time.time()
+            for _ in items:
+                fps.update(len(items) / max(t2 - t1, 1e-9))
+            for (img_src, img_path), det in zip(items, dets):
+                self.save_outputs(img_src, img_path, det, save_dir, save_txt, save_img)
+                results.append(det)
+        LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
+        return results
+
+    def _frames_ahead(self, prefetch_frames, imread_bgr):
+        """(frame, path) of every source in LoadData's order: image files decoded ahead on the pool, videos read in turn."""
+        files = self.files.files
+        images = [p for p in files if self.files.checkext(p) == 'image']
+        yield from prefetch_frames(images, imread_bgr, threads=min(self.batch_size, 8), depth=2 * self.batch_size)
+        for p in files:
+            if self.files.checkext(p) != 'image':
+                for frame in self.files._frames_of(p):
+                    yield frame, p
+
+    def save_outputs(self, img_src, img_path, det, save_dir, save_txt, save_img):
+        """The label lines and the annotated image of one frame's rescaled, rounded detections (reference :100-120)."""
+        rel_path = osp.relpath(osp.dirname(img_path), osp.dirname(self.source))
+        save_path = osp.join(save_dir, rel_path, osp.basename(img_path))
+        txt_path = osp.join(save_dir, rel_path, osp.splitext(osp.basename(img_path))[0])
+        if save_txt or save_img:
+            os.makedirs(osp.join(save_dir, rel_path), exist_ok=True)
+        gn = torch.tensor(img_src.shape)[[1, 0, 1, 0]]
+        gn_cor = torch.tensor(img_src.shape)[[1, 0, 1, 0, 1, 0, 1, 0]]
+        if len(det):
+            rows = det.detach().float().cpu()
+            if save_txt:
+                with open(txt_path + '.txt', 'a') as f:
+                    for output in rows:
+                        xywh = (self.box_convert(output[:4].view(1, 4)) / gn).view(-1).tolist()
+                        corners_gn = (output[4:12] / gn_cor).tolist()
+                        line = (*output[20:].tolist(), *xywh, *corners_gn)
+                        f.write(('%g ' * len(line)).rstrip() % line + '\n')
+            if save_img:
+                self.save_annotated(img_src, rows, save_path)
+        elif save_img:
+            self.save_annotated(img_src, [], save_path)
 
     @staticmethod
     def save_annotated(img_bgr, rows, save_path):
@@ -132,9 +198,9 @@ class Inferer:
         im.save(save_path)
 
     @staticmethod
-    def precess_image(img_src, img_size, stride, half):
+    def precess_image(img_src, img_size, stride, half, auto=True):
         """letterbox -> CHW RGB -> fp16/fp32 in [0, 1] (reference :191-201)."""
-        image = letterbox(img_src, img_size, stride=stride)[0]
+        image = letterbox(img_src, img_size, stride=stride, auto=auto)[0]
         image = image.transpose((2, 0, 1))[::-1]
         image = torch.from_numpy(np.ascontiguousarray(image))
         image = image.half() if half else image.float()

@@ -770,15 +770,16 @@ def non_max_suppression(prediction, conf_thres, iou_thres, max_det):
 
 
 # ---------------------------------------------------------------------------------------------------
-def preprocess_letterbox(frame_bgr_u8, img_size, stride, dtype):
+def preprocess_letterbox(frame_bgr_u8, img_size, stride, dtype, auto=True):
     """GPU form of Inferer.precess_image: device uint8 [h,w,3] BGR frame -> [3,H,W] RGB /255 tensor of ``dtype``.
-    Geometry (ratio, resized size, padding) is the reference's letterbox arithmetic, done on the host."""
+    Geometry (ratio, resized size, padding) is the reference's letterbox arithmetic, done on the host; ``auto=False``
+    pads to exactly ``img_size`` instead of the next stride multiple."""
     from yolov6.data.data_augment import letterbox_geometry
     if not (frame_bgr_u8.is_cuda and frame_bgr_u8.dtype == torch.uint8 and frame_bgr_u8.dim() == 3 and
             frame_bgr_u8.shape[2] == 3 and frame_bgr_u8.is_contiguous()):
         raise ValueError('frame must be a contiguous uint8 CUDA tensor [h, w, 3]')
     h0, w0 = frame_bgr_u8.shape[:2]
-    _, (rw, rh), (top, bottom, left, right), _ = letterbox_geometry((h0, w0), img_size, stride=stride)
+    _, (rw, rh), (top, bottom, left, right), _ = letterbox_geometry((h0, w0), img_size, auto=auto, stride=stride)
     H, W = rh + top + bottom, rw + left + right
     out = torch.empty(3, H, W, dtype=dtype, device=frame_bgr_u8.device)
     with torch.cuda.device(out.device):
@@ -787,6 +788,48 @@ def preprocess_letterbox(frame_bgr_u8, img_size, stride, dtype):
                                                      ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)),
                   'lp_preprocess_letterbox')
     return out
+
+
+def preprocess_frames(frames, img_size, stride, dtype, auto=True, batch=None, out=None):
+    """Batched ``preprocess_letterbox`` (lp_preprocess_letterbox_batch, one launch per 64 frames): a list of contiguous
+    uint8 CUDA [h,w,3] BGR frames of any sizes -> (x[B,3,H,W] of ``dtype``, geoms).  ``geoms[i]`` is frame i's
+    (rh, rw, top, left) from the host letterbox arithmetic.  With ``auto=True`` every frame must letterbox to the same
+    (H, W); ``auto=False`` letterboxes each to exactly ``img_size``.  ``batch`` (>= len(frames)) sets B: slots past the
+    frames are padding (114/255).  ``out``: a persistent [B,3,H,W] input buffer to write (graphs are keyed on the
+    input pointer)."""
+    from yolov6.data.data_augment import letterbox_geometry
+    if dtype not in _DT:
+        raise TypeError('unsupported input dtype %s' % dtype)
+    if not frames:
+        raise ValueError('preprocess_frames needs at least one frame')
+    dev = frames[0].device
+    for f in frames:
+        if not (f.is_cuda and f.device == dev and f.dtype == torch.uint8 and f.dim() == 3 and f.shape[2] == 3 and f.is_contiguous()):
+            raise ValueError('frames must be contiguous uint8 CUDA tensors [h, w, 3] on one device')
+    B = len(frames) if batch is None else int(batch)
+    if B < len(frames):
+        raise ValueError('batch %d < %d frames' % (B, len(frames)))
+    geoms, hws = [], []
+    for f in frames:
+        _, (rw, rh), (top, bottom, left, right), _ = letterbox_geometry(tuple(f.shape[:2]), img_size, auto=auto, stride=stride)
+        geoms.append((rh, rw, top, left))
+        hws.append((rh + top + bottom, rw + left + right))
+    if len(set(hws)) != 1:
+        raise ValueError('frames letterbox to different shapes %s (source shapes %s): batch them separately or use auto=False'
+                         % (sorted(set(hws)), [tuple(f.shape[:2]) for f in frames]))
+    H, W = hws[0]
+    if out is None:
+        out = torch.empty(B, 3, H, W, dtype=dtype, device=dev)
+    elif not (out.shape == (B, 3, H, W) and out.dtype == dtype and out.device == dev and out.is_contiguous()):
+        raise ValueError('out must be a contiguous %s tensor [%d,3,%d,%d] on %s' % (dtype, B, H, W, dev))
+    desc = (abi.FrameDesc * len(frames))()
+    for d, f, (rh, rw, top, left) in zip(desc, frames, geoms):
+        d.img, d.h0, d.w0, d.rh, d.rw, d.top, d.left = f.data_ptr(), f.shape[0], f.shape[1], rh, rw, top, left
+    with torch.cuda.device(dev):
+        abi.check(abi.load().lp_preprocess_letterbox_batch(desc, len(frames), B, ctypes.c_void_p(out.data_ptr()), _DT[dtype], H, W,
+                                                           ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                  'lp_preprocess_letterbox_batch')
+    return out, geoms
 
 
 def rescale_round(ori_shape, det, target_shape):
@@ -802,6 +845,45 @@ def rescale_round(ori_shape, det, target_shape):
                                               ctypes.c_void_p(torch.cuda.current_stream(det.device).cuda_stream)),
                   'lp_rescale_round')
     return det
+
+
+def rescale_round_batch(det, count, net_hw, src_shapes):
+    """Batched ``rescale_round`` (lp_rescale_round_batch), in place on det [B,max_det,28]: rows r < count[b] of image
+    b < len(src_shapes) are mapped back to source image b of shape (h, w[, c]) from the network input size ``net_hw``
+    (Inferer.rescale's ratio and padding) and rounded.  ``count`` (int32 [B], CUDA) is read on the device: no host sync."""
+    if not (det.is_cuda and det.dtype == torch.float32 and det.dim() == 3 and det.shape[2] == abi.LP_DET_COLS and det.is_contiguous()):
+        raise ValueError('det must be a contiguous CUDA fp32 [B, max_det, 28] tensor')
+    if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.numel() == det.shape[0]
+            and count.device == det.device):
+        raise ValueError('count must be a contiguous CUDA int32 [B] tensor on det\'s device')
+    n = len(src_shapes)
+    if n > det.shape[0]:
+        raise ValueError('%d source shapes for a batch of %d' % (n, det.shape[0]))
+    desc = (abi.RescaleDesc * max(n, 1))()
+    for d, s in zip(desc, src_shapes):
+        ratio = min(net_hw[0] / s[0], net_hw[1] / s[1])
+        d.ratio, d.padx, d.pady = ratio, (net_hw[1] - s[1] * ratio) / 2, (net_hw[0] - s[0] * ratio) / 2
+        d.img_w, d.img_h = int(s[1]), int(s[0])
+    with torch.cuda.device(det.device):
+        abi.check(abi.load().lp_rescale_round_batch(ctypes.c_void_p(det.data_ptr()), ctypes.c_void_p(count.data_ptr()), n,
+                                                    det.shape[1], desc,
+                                                    ctypes.c_void_p(torch.cuda.current_stream(det.device).cuda_stream)),
+                  'lp_rescale_round_batch')
+    return det
+
+
+def detect_frames(model, frames, img_size, conf_thres, iou_thres, max_det, auto=True, batch=None, out=None):
+    """Detections of a batch of raw frames (contiguous uint8 CUDA [h,w,3] BGR, any sizes that letterbox to one shape, or any
+    sizes with ``auto=False``): ``preprocess_frames`` -> ``detect_padded`` -> ``rescale_round_batch``, then one host read of
+    the counts.  Returns a list of [n_i, 28] tensors in source-image pixels, rounded: per frame what Inferer.infer returns,
+    bit for bit.  The input dtype is the model's parameter dtype (Inferer's fp16 / fp32 input); ``batch`` / ``out`` as in
+    ``preprocess_frames`` (padding slots let a short tail reuse a bound batch size)."""
+    dtype = next(model.parameters()).dtype
+    x, _ = preprocess_frames(frames, img_size, int(model.stride.max()), dtype, auto=auto, batch=batch, out=out)   # DetectBackend's stride
+    det, count, _ = detect_padded(model, x, conf_thres, iou_thres, max_det)
+    rescale_round_batch(det, count, x.shape[2:], [tuple(f.shape[:2]) for f in frames])
+    counts = count.cpu().tolist()
+    return [det[b, :counts[b]] for b in range(len(frames))]
 
 
 def eval_counts(det, det_count, tgt, tgt_count, counts=None):
