@@ -1,5 +1,5 @@
 /* lp_hip.h -- C ABI of libyololp_hip.so: the MI355X (gfx950) implementation of YOLO-LP's detection
- * forward + decode + NMS hot path.
+ * forward + decode + NMS hot path, with the frame pre- and post-processing around it (letterbox, rescale, plate crops).
  *
  * The reference (KyleHuang9/YOLO-LP) is pure Python/PyTorch and has no FFI of its own; its boundary for this
  * path is the Python module API.  This header is the C-ABI a binding for that API
@@ -282,6 +282,34 @@ typedef struct lp_rescale_desc { double ratio, padx, pady; int img_w, img_h; } l
 int lp_preprocess_letterbox_batch(const lp_frame_desc* desc, int n_frames, int B, void* out, int out_dtype, int H, int W,
                                   void* stream);
 int lp_rescale_round_batch(float* det, const int32_t* count, int B, int max_det, const lp_rescale_desc* desc, void* stream);
+
+/* lp_plate_crops_batch: perspective-rectified plate crops of B frames' detections (the inverse of the warp of the reference's
+ * plate generator, yolov6/data/generate/generate.py:566-586), one launch per LP_FRAMES_PER_LAUNCH frames; descriptors travel
+ * as kernel arguments, so nothing is uploaded and the call may be captured in a graph.
+ *   det [n_frames,max_det,28] fp32 in source-frame pixels (as lp_rescale_round_batch leaves it); count: DEVICE int32
+ *   [n_frames], read by the kernel (no host sync).  Frame b crops its rows r < n_b = clamp(count[b], 0, min(max_det,
+ *   max_crops_b)) into slot out_slot_b + r of out [n_slots,crop_h,crop_w,3] uint8 BGR (the frames' pixel format), and writes
+ *   status[out_slot_b + r] for every r < max_crops_b: 1 = cropped along the corners, 2 = along the box, 3 = neither is
+ *   usable (crop filled with 0), 0 = not cropped (r >= n_b; those crop pixels are left untouched).  Nothing outside the
+ *   frames' slot ranges is written.
+ *   Quad: corners TL (c4,c5), TR (c10,c11), BR (c8,c9), BL (c6,c7) if all finite, strictly convex in label orientation (the
+ *   cross products of consecutive edges along TL->BL->BR->TR all < 0, y down) and of area >= 1; else the box (x1,y1)-(x2,y2)
+ *   if finite with x2-x1 >= 1 and y2-y1 >= 1.  Map: the fp64 square-to-quad projective map (Heckbert), (0,0)->TL, (1,0)->TR,
+ *   (1,1)->BR, (0,1)->BL.  Output pixel (i,j) samples the map at ((j+0.5)/crop_w, (i+0.5)/crop_h), source point
+ *   clamp(X-0.5, 0, w0-1), clamp(Y-0.5, 0, h0-1) (edge replicated), fp32 bilinear blend, rounded half to even: what
+ *   grid_sample(bilinear, border, align_corners=False) gives at the mapped points.  yolov6/utils/plate_crop.py restates it
+ *   bit for bit.
+ *   desc is a HOST array of n_frames entries; every entry (img, h0, w0 >= 1, max_crops, out_slot >= 0, out_slot + max_crops <=
+ *   n_slots, no two frames' slot ranges overlapping) and 1 <= crop_h, crop_w <= 1024 are checked before anything is launched
+ *   (LP_ERR_ARG names the frame); the pointers must be non-null when any frame has max_crops > 0.  Nothing to do: LP_OK. */
+typedef struct lp_crop_desc {
+    const unsigned char* img;   /* device uint8 [h0,w0,3] BGR, any alignment (as lp_frame_desc) */
+    int h0, w0;
+    int max_crops;              /* slots reserved for this frame */
+    int out_slot;               /* first output slot of this frame */
+} lp_crop_desc;
+int lp_plate_crops_batch(const lp_crop_desc* desc, int n_frames, const float* det, const int32_t* count, int max_det,
+                         unsigned char* out, int32_t* status, int n_slots, int crop_h, int crop_w, void* stream);
 
 /* lp_eval_counts: the matching loops of Evaler.eval (yolov6/core/evaler.py:153-243, box_iou general.py:93-115) for a
  * batch of images, one workgroup per image.

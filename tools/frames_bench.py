@@ -2,13 +2,17 @@
 """Frames benchmark: rescaled detections from host frames, end to end, per frame and batched.
 
     python tools/frames_bench.py [--model yololps] [--size 640] [--dtype f16] [--frame 1080 1920] [--batches 8 32 64]
+                                 [--crops N]
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
   - frames/s of the per-frame path (upload, lp_preprocess_letterbox, detect at B=1 with hipGraph replay, lp_rescale_round,
     host read: what Inferer.infer does per frame) and of FrameBatcher + detect_frames at each batch size;
   - the device time of each stage of one batch from events (H2D from pinned memory, letterbox, detect, rescale) and the
     stage that bounds the batched path;
-  - the letterbox kernel's GB/s over the bytes it must move: the source rows it samples plus its output.
+  - the letterbox kernel's GB/s over the bytes it must move: the source rows it samples plus its output;
+  - with ``--crops N``, the device time of the plate-crop stage (runtime.plate_crops, 64x192 crops) on N seeded synthetic
+    quads per frame (rotated and perspective plates, and one in four with unusable corners that falls back to its box),
+    timed in the same event chain right behind rescale, and its share of the detect stage.
 The model is the synthetic recipe of bench.py (same weights scale), prepared as Inferer prepares it.
 """
 import argparse
@@ -40,7 +44,33 @@ def parse():
     ap.add_argument('--conf', type=float, default=0.4)
     ap.add_argument('--iou', type=float, default=0.45)
     ap.add_argument('--max-det', type=int, default=1000)
+    ap.add_argument('--crops', type=int, default=0, help='plate crops per frame to time (0: no crop stage)')
     return ap.parse_args()
+
+
+def synthetic_quads(n_frames, n, h0, w0, seed=0):
+    """[n_frames, n, 28] fp32 detection rows: plates of 120..400 px x 1/3.1 of that, turned by up to 30 degrees; row r % 4 == 1
+    also has each corner moved by up to 10 % (perspective), r % 4 == 3 has its BL and TR swapped (a bow-tie: the box is used)."""
+    rng = np.random.default_rng(seed)
+    rows = np.zeros((n_frames, n, 28), np.float32)
+    for b in range(n_frames):
+        for r in range(n):
+            w = rng.uniform(120, 400)
+            h = w / 3.1
+            cx, cy = rng.uniform(w / 2, w0 - w / 2), rng.uniform(h / 2, h0 - h / 2)
+            t = np.radians(rng.uniform(-30, 30))
+            c, s = np.cos(t), np.sin(t)
+            pts = []
+            for px, py in ((-w / 2, -h / 2), (-w / 2, h / 2), (w / 2, h / 2), (w / 2, -h / 2)):    # TL, BL, BR, TR
+                if r % 4 == 1:
+                    px, py = px + rng.uniform(-0.1, 0.1) * w, py + rng.uniform(-0.1, 0.1) * h
+                pts.append((cx + c * px - s * py, cy + s * px + c * py))
+            xs, ys = [p[0] for p in pts], [p[1] for p in pts]
+            rows[b, r, :4] = [min(xs), min(ys), max(xs), max(ys)]
+            if r % 4 == 3:
+                pts = [pts[0], pts[3], pts[2], pts[1]]
+            rows[b, r, 4:12] = [v for p in pts for v in p]
+    return rows
 
 
 def sampled_rows(h0, rh):
@@ -131,9 +161,15 @@ def main():
                 hv[j * f.nbytes:(j + 1) * f.nbytes] = f.reshape(-1)
             dbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             views = [dbuf[j * f.nbytes:(j + 1) * f.nbytes].view(f.shape) for j, f in enumerate(fr)]
-            times = {k: [] for k in ('h2d', 'letterbox', 'detect', 'rescale')}
+            times = {k: [] for k in ('h2d', 'letterbox', 'detect', 'rescale') + (('crops',) if args.crops else ())}
+            if args.crops:
+                crop_hw = (64, 192)
+                cdet = torch.from_numpy(synthetic_quads(B, args.crops, h0, w0, seed=B)).to(dev)
+                ccount = torch.full((B,), args.crops, dtype=torch.int32, device=dev)
+                cout = torch.empty(B, args.crops, *crop_hw, 3, dtype=torch.uint8, device=dev)
+                cst = torch.empty(B, args.crops, dtype=torch.int32, device=dev)
             for _ in range(args.reps + 1):
-                ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(times) + 1)]
                 ev[0].record()
                 dbuf.copy_(host, non_blocking=True)
                 ev[1].record()
@@ -143,18 +179,27 @@ def main():
                 ev[3].record()
                 runtime.rescale_round_batch(det, count, (H, W), [f.shape for f in fr])
                 ev[4].record()
+                if args.crops:      # enqueued while detect still runs: the event pair brackets the kernel alone
+                    runtime.plate_crops(views, cdet, ccount, crop_hw, max_crops=args.crops, out=cout, status=cst)
+                    ev[5].record()
                 sync()
                 for i, k in enumerate(times):
                     times[k].append(ev[i].elapsed_time(ev[i + 1]))
             med = {k: float(np.median(v[1:])) for k, v in times.items()}
             stages[str(B)] = {k: round(v, 4) for k, v in med.items()}
             e2e_ms = B * 1000.0 / batched[str(B)]
-            stages[str(B)]['host_other'] = round(max(0.0, e2e_ms - sum(med.values())), 4)
+            stages[str(B)]['host_other'] = round(max(0.0, e2e_ms - sum(med[k] for k in ('h2d', 'letterbox', 'detect', 'rescale'))), 4)
             stages[str(B)]['bound_by'] = max(('h2d', 'letterbox', 'detect', 'rescale', 'host_other'), key=lambda k: stages[str(B)][k])
             _, (rw, rh), _, _ = letterbox_geometry((h0, w0), size, stride=stride)
             moved = B * (sampled_rows(h0, rh) * w0 * 3 + 3 * H * W * x.element_size())
             stages[str(B)]['letterbox_MB'] = round(moved / 1e6, 2)
             stages[str(B)]['letterbox_GBps'] = round(moved / (med['letterbox'] * 1e-3) / 1e9, 1)
+            if args.crops:
+                stages[str(B)]['crops_per_frame'] = args.crops
+                stages[str(B)]['crops_status_counts'] = np.bincount(cst.cpu().numpy().reshape(-1), minlength=4).tolist()
+                stages[str(B)]['crops_out_MB'] = round(cout.numel() / 1e6, 2)
+                stages[str(B)]['crops_pct_of_detect'] = round(100.0 * med['crops'] / med['detect'], 2)
+                del cdet, ccount, cout, cst
             del host, dbuf, views
     out['batched_fps'] = batched
     out['stage_ms'] = stages

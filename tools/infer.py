@@ -2,7 +2,7 @@
 """Inference entry point: the flags and the ``run`` keyword arguments of reference tools/infer.py:19-107.
 
     python tools/infer.py --weights weights/yololps.pt --source data/images --yaml data/dataset.yaml [--half]
-                          [--batch-size 32] [--fixed-shape]
+                          [--batch-size 32] [--fixed-shape] [--save-crops [--crop-size 64 192]]
 """
 import argparse
 import os
@@ -41,6 +41,8 @@ _FLAGS = [
     ('--half', dict(action='store_true', help='fp16 engine')),
     ('--batch-size', dict(type=int, default=1, help='frames per forward on a GPU (consecutive frames of one letterboxed shape)')),
     ('--fixed-shape', dict(action='store_true', help='letterbox every frame to exactly --img-size (no stride-multiple trim)')),
+    ('--save-crops', dict(action='store_true', help='write every plate, rectified along its four corners, as crops/<stem>_<k>.png')),
+    ('--crop-size', dict(nargs=2, type=int, default=[64, 192], metavar=('H', 'W'), help='size of the plate crops, h w')),
 ]
 
 
@@ -57,18 +59,19 @@ def get_args_parser(add_help=True):
 def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images'), yaml=None, img_size=640,
         conf_thres=0.4, iou_thres=0.45, max_det=1000, device='', save_txt=False, not_save_img=False, save_dir=None,
         view_img=True, classes=None, agnostic_nms=False, project=osp.join(ROOT, 'runs/inference'), name='exp',
-        hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False):
+        hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False, save_crops=False, crop_size=(64, 192)):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
-    if (save_img or save_txt) and not osp.exists(out_dir):
+    if (save_img or save_txt or save_crops) and not osp.exists(out_dir):
         os.makedirs(out_dir)
     else:
         LOGGER.warning('Save directory already existed')
     if save_txt:
         os.makedirs(osp.join(out_dir, 'labels'), exist_ok=True)
     results = Inferer(source, weights, device, yaml, img_size, half, batch_size=batch_size, auto=not fixed_shape).infer(
-        conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img)
-    if save_txt or save_img:
+        conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
+        save_crops=save_crops, crop_size=tuple(crop_size))
+    if save_txt or save_img or save_crops:
         LOGGER.info(f"Results saved to {out_dir}")
     return results
 

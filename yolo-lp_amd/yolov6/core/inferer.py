@@ -8,6 +8,8 @@ reference's order: checkpoint -> float -> fuse_model -> eval -> switch_to_deploy
 label lines ``cls*8 xywh(normalised) corners(normalised)`` (reference :100-120).
 Drawing / video writing are cv2 GUI plumbing outside the hot-path scope: boxes and
 corner polygons are drawn with PIL when images are saved, labels are not rendered.
+With ``save_crops`` every detection's plate is also cut out along its four corners as
+an upright image (``runtime.plate_crops`` on a GPU, ``plate_crops_np`` on the CPU).
 """
 import math
 import os
@@ -67,10 +69,12 @@ class Inferer:
         LOGGER.info("Switch model to deploy modality.")
 
     def infer(self, conf_thres, iou_thres, classes, agnostic_nms, max_det, save_dir, save_txt, save_img, hide_labels,
-              hide_conf, view_img=True):
-        """Run every source image through model + NMS; returns the list of rescaled ``[n, 28]`` detections."""
+              hide_conf, view_img=True, save_crops=False, crop_size=(64, 192)):
+        """Run every source image through model + NMS; returns the list of rescaled ``[n, 28]`` detections.  ``save_crops``:
+        also write the plate crop (``crop_size`` = (h, w)) of detection k of an image as ``<save_dir>/<rel>/crops/<stem>_<k>.png``
+        (RGB; k is the line of the detection in ``<stem>.txt``)."""
         if self.device.type != 'cpu' and self.batch_size > 1:
-            return self._infer_batched(conf_thres, iou_thres, max_det, save_dir, save_txt, save_img)
+            return self._infer_batched(conf_thres, iou_thres, max_det, save_dir, save_txt, save_img, save_crops, crop_size)
         fps = CalcFPS()
         results = []
         for img_src, img_path, _ in self.files:
@@ -105,11 +109,20 @@ class Inferer:
                 else:
                     det[:, :12] = self.rescale(img.shape[2:], det[:, :12], img_src.shape).round()
             self.save_outputs(img_src, img_path, det, save_dir, save_txt, save_img)
+            if save_crops and len(det):
+                if det.is_cuda:     # the uploaded frame and its detections are on the device: crop there
+                    count = torch.tensor([len(det)], dtype=torch.int32, device=self.device)
+                    crops, _ = runtime.plate_crops([frame], det[None], count, crop_size, max_crops=len(det))
+                    crops = crops[0].cpu().numpy()
+                else:
+                    from yolov6.utils.plate_crop import plate_crops_np
+                    crops, _ = plate_crops_np(img_src, det.detach().float().cpu().numpy(), crop_size)
+                self.write_crops(img_path, crops, save_dir)
             results.append(det)
         LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
         return results
 
-    def _infer_batched(self, conf_thres, iou_thres, max_det, save_dir, save_txt, save_img):
+    def _infer_batched(self, conf_thres, iou_thres, max_det, save_dir, save_txt, save_img, save_crops=False, crop_size=(64, 192)):
         """``infer`` with ``batch_size`` frames per forward: consecutive frames of one letterboxed shape (``plan_batches``) go
         through ``runtime.detect_frames`` together.  Image files are decoded on a small thread pool ahead of the GPU, each
         batch is uploaded with one copy from pinned memory (``FrameBatcher``), and a short group is padded to the bound batch
@@ -142,13 +155,19 @@ class Inferer:
             runtime.prepare_for(self.model.model, x.shape, dtype)      # a new shape tunes once: outside the FPS window
             t1 = time.time()
             dev_frames = batcher.put([f for f, _ in items])
-            dets = runtime.detect_frames(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det,
-                                         auto=self.auto, batch=B, out=x)
+            if save_crops:      # crops of every detection, enqueued before the next put reuses the frames' buffer
+                dets, crops, _ = runtime.detect_frames_with_crops(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres,
+                                                                  max_det, crop_size, auto=self.auto, batch=B, out=x)
+            else:
+                dets = runtime.detect_frames(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det,
+                                             auto=self.auto, batch=B, out=x)
             t2 = time.time()
             for _ in items:
                 fps.update(len(items) / max(t2 - t1, 1e-9))
-            for (img_src, img_path), det in zip(items, dets):
+            for k, ((img_src, img_path), det) in enumerate(zip(items, dets)):
                 self.save_outputs(img_src, img_path, det, save_dir, save_txt, save_img)
+                if save_crops and len(det):
+                    self.write_crops(img_path, crops[k].cpu().numpy(), save_dir)
                 results.append(det)
         LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
         return results
@@ -185,6 +204,15 @@ class Inferer:
                 self.save_annotated(img_src, rows, save_path)
         elif save_img:
             self.save_annotated(img_src, [], save_path)
+
+    def write_crops(self, img_path, crops_bgr, save_dir):
+        """Plate crops of one image (uint8 [n, h, w, 3] BGR) as ``<save_dir>/<rel>/crops/<stem>_<k>.png``, RGB."""
+        from PIL import Image
+        crop_dir = osp.join(save_dir, osp.relpath(osp.dirname(img_path), osp.dirname(self.source)), 'crops')
+        os.makedirs(crop_dir, exist_ok=True)
+        stem = osp.splitext(osp.basename(img_path))[0]
+        for k, crop in enumerate(crops_bgr):
+            Image.fromarray(np.ascontiguousarray(crop[:, :, ::-1])).save(osp.join(crop_dir, '%s_%d.png' % (stem, k)))
 
     @staticmethod
     def save_annotated(img_bgr, rows, save_path):

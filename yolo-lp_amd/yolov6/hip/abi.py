@@ -20,7 +20,7 @@ LP_VARIANT_BOX_SPARSE, LP_VARIANT_BOX_DENSE = 46, 47                            
 LP_VARIANT_FUSED_PW_S2 = 38                                                                      # a 1x1 layer + the 3x3 stride-2 layer behind it as one kernel
 LP_VARIANT_FUSED_STEM2 = 37                                                                      # input op + stem + the layer behind it as one kernel
 LP_VARIANT_PIPE_P = 36                                                                           # the stem reading the NCHW frame itself
-LP_FRAMES_PER_LAUNCH = 64   # lp_preprocess_letterbox_batch / lp_rescale_round_batch: frames per launch
+LP_FRAMES_PER_LAUNCH = 64   # lp_preprocess_letterbox_batch / lp_rescale_round_batch / lp_plate_crops_batch: frames per launch
 LP_EVAL_NCOUNTS = 43   # lp_eval_counts: length of the counts vector (include/lp_hip.h)
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # .../yolo-lp_amd
@@ -36,6 +36,11 @@ class FrameDesc(ctypes.Structure):
 class RescaleDesc(ctypes.Structure):
     """lp_rescale_desc"""
     _fields_ = [('ratio', c_double), ('padx', c_double), ('pady', c_double), ('img_w', c_int), ('img_h', c_int)]
+
+
+class CropDesc(ctypes.Structure):
+    """lp_crop_desc"""
+    _fields_ = [('img', c_void_p), ('h0', c_int), ('w0', c_int), ('max_crops', c_int), ('out_slot', c_int)]
 
 
 class ConvDesc(ctypes.Structure):
@@ -89,6 +94,8 @@ SYMBOLS = {
     'lp_rescale_round': (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_int, c_int, c_void_p]),
     'lp_preprocess_letterbox_batch': (c_int, [POINTER(FrameDesc), c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     'lp_rescale_round_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(RescaleDesc), c_void_p]),
+    'lp_plate_crops_batch': (c_int, [POINTER(CropDesc), c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                     c_void_p]),
     'lp_eval_counts': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'lp_check_sigmoid_monotone': (c_int, [c_void_p, c_void_p]),
     'lp_debug_poison_lds': (c_int, [c_void_p]),

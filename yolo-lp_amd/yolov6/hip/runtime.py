@@ -790,6 +790,15 @@ def preprocess_letterbox(frame_bgr_u8, img_size, stride, dtype, auto=True):
     return out
 
 
+def _frames_device(frames):
+    """The one device of a non-empty list of contiguous uint8 CUDA [h,w,3] frames (ValueError otherwise)."""
+    dev = frames[0].device
+    for f in frames:
+        if not (f.is_cuda and f.device == dev and f.dtype == torch.uint8 and f.dim() == 3 and f.shape[2] == 3 and f.is_contiguous()):
+            raise ValueError('frames must be contiguous uint8 CUDA tensors [h, w, 3] on one device')
+    return dev
+
+
 def preprocess_frames(frames, img_size, stride, dtype, auto=True, batch=None, out=None):
     """Batched ``preprocess_letterbox`` (lp_preprocess_letterbox_batch, one launch per 64 frames): a list of contiguous
     uint8 CUDA [h,w,3] BGR frames of any sizes -> (x[B,3,H,W] of ``dtype``, geoms).  ``geoms[i]`` is frame i's
@@ -802,10 +811,7 @@ def preprocess_frames(frames, img_size, stride, dtype, auto=True, batch=None, ou
         raise TypeError('unsupported input dtype %s' % dtype)
     if not frames:
         raise ValueError('preprocess_frames needs at least one frame')
-    dev = frames[0].device
-    for f in frames:
-        if not (f.is_cuda and f.device == dev and f.dtype == torch.uint8 and f.dim() == 3 and f.shape[2] == 3 and f.is_contiguous()):
-            raise ValueError('frames must be contiguous uint8 CUDA tensors [h, w, 3] on one device')
+    dev = _frames_device(frames)
     B = len(frames) if batch is None else int(batch)
     if B < len(frames):
         raise ValueError('batch %d < %d frames' % (B, len(frames)))
@@ -878,12 +884,91 @@ def detect_frames(model, frames, img_size, conf_thres, iou_thres, max_det, auto=
     the counts.  Returns a list of [n_i, 28] tensors in source-image pixels, rounded: per frame what Inferer.infer returns,
     bit for bit.  The input dtype is the model's parameter dtype (Inferer's fp16 / fp32 input); ``batch`` / ``out`` as in
     ``preprocess_frames`` (padding slots let a short tail reuse a bound batch size)."""
+    det, _, counts = _detect_frames_padded(model, frames, img_size, conf_thres, iou_thres, max_det, auto, batch, out)
+    return [det[b, :counts[b]] for b in range(len(frames))]
+
+
+def _detect_frames_padded(model, frames, img_size, conf_thres, iou_thres, max_det, auto, batch, out):
+    """The device work of ``detect_frames`` and its one host read: (det [B,max_det,28], count [B] on the device, counts as a
+    host list)."""
     dtype = next(model.parameters()).dtype
     x, _ = preprocess_frames(frames, img_size, int(model.stride.max()), dtype, auto=auto, batch=batch, out=out)   # DetectBackend's stride
     det, count, _ = detect_padded(model, x, conf_thres, iou_thres, max_det)
     rescale_round_batch(det, count, x.shape[2:], [tuple(f.shape[:2]) for f in frames])
-    counts = count.cpu().tolist()
-    return [det[b, :counts[b]] for b in range(len(frames))]
+    return det, count, count.cpu().tolist()
+
+
+def _crop_size(crop_hw):
+    Hc, Wc = (int(v) for v in crop_hw)
+    if not (1 <= Hc <= 1024 and 1 <= Wc <= 1024):
+        raise ValueError('crop size %dx%d: need 1..1024 on each side' % (Hc, Wc))
+    return Hc, Wc
+
+
+def _plate_crops_launch(frames, det, count, slots, out, status, crop_hw):
+    """lp_plate_crops_batch on frames with ``slots[b]`` = (max_crops, out_slot): out [n_slots,Hc,Wc,3], status [n_slots]."""
+    if not (det.is_cuda and det.dtype == torch.float32 and det.dim() == 3 and det.shape[2] == abi.LP_DET_COLS and
+            det.is_contiguous() and det.shape[0] >= len(frames) and det.device == out.device):
+        raise ValueError('det must be a contiguous CUDA fp32 [B >= %d frames, max_det, 28] tensor on the frames\' device'
+                         % len(frames))
+    if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.numel() == det.shape[0]
+            and count.device == det.device):
+        raise ValueError('count must be a contiguous CUDA int32 [B] tensor on det\'s device')
+    desc = (abi.CropDesc * len(frames))()
+    for d, f, (m, o) in zip(desc, frames, slots):
+        d.img, d.h0, d.w0, d.max_crops, d.out_slot = f.data_ptr(), f.shape[0], f.shape[1], m, o
+    with torch.cuda.device(det.device):
+        abi.check(abi.load().lp_plate_crops_batch(desc, len(frames), ctypes.c_void_p(det.data_ptr()),
+                                                  ctypes.c_void_p(count.data_ptr()), det.shape[1], ctypes.c_void_p(out.data_ptr()),
+                                                  ctypes.c_void_p(status.data_ptr()), status.numel(), crop_hw[0], crop_hw[1],
+                                                  ctypes.c_void_p(torch.cuda.current_stream(det.device).cuda_stream)),
+                  'lp_plate_crops_batch')
+
+
+def plate_crops(frames, det, count, crop_hw=(64, 192), max_crops=None, out=None, status=None):
+    """Perspective-rectified plate crops (lp_plate_crops_batch, one launch per 64 frames) of the detections of B frames:
+    frame b (contiguous uint8 CUDA [h,w,3] BGR) is cut along its rows r < min(count[b], max_det, max_crops) of det
+    [B,max_det,28] (fp32, source-frame pixels, as ``rescale_round_batch`` leaves them; count int32 [B] on the device, read by
+    the kernel: no host sync).  Returns (crops [B,max_crops,Hc,Wc,3] uint8 BGR, status [B,max_crops] int32): 1 = cut along
+    the four corners, 2 = along the box (the corners are not a convex quad of area >= 1), 3 = neither is usable (zeros),
+    0 = no such detection (the crop's bytes are left as they were).  ``max_crops`` defaults to 16 (each slot is Hc*Wc*3
+    bytes); ``out`` / ``status``: persistent buffers of those shapes.  yolov6.utils.plate_crop.plate_crops_np is the same
+    computation on the CPU, bit for bit."""
+    if not frames:
+        raise ValueError('plate_crops needs at least one frame')
+    dev = _frames_device(frames)
+    Hc, Wc = _crop_size(crop_hw)
+    n, m = len(frames), 16 if max_crops is None else int(max_crops)
+    if m < 0:
+        raise ValueError('max_crops must be >= 0')
+    if out is None:
+        out = torch.empty(n, m, Hc, Wc, 3, dtype=torch.uint8, device=dev)
+    elif not (out.shape == (n, m, Hc, Wc, 3) and out.dtype == torch.uint8 and out.device == dev and out.is_contiguous()):
+        raise ValueError('out must be a contiguous uint8 tensor [%d,%d,%d,%d,3] on %s' % (n, m, Hc, Wc, dev))
+    if status is None:
+        status = torch.empty(n, m, dtype=torch.int32, device=dev)
+    elif not (status.shape == (n, m) and status.dtype == torch.int32 and status.device == dev and status.is_contiguous()):
+        raise ValueError('status must be a contiguous int32 tensor [%d,%d] on %s' % (n, m, dev))
+    _plate_crops_launch(frames, det, count, [(m, b * m) for b in range(n)], out, status, (Hc, Wc))
+    return out, status
+
+
+def detect_frames_with_crops(model, frames, img_size, conf_thres, iou_thres, max_det, crop_hw=(64, 192), auto=True, batch=None,
+                             out=None):
+    """``detect_frames`` plus the plate crop of every detection: (dets, crops, status).  ``dets`` is bit for bit what
+    ``detect_frames`` returns; after its one host read of the counts the crops are packed, frame b's n_b crops right behind
+    frame b-1's in one [sum n_b,Hc,Wc,3] uint8 tensor: ``crops[b]`` is an [n_b,Hc,Wc,3] view of it and ``status[b]`` an
+    [n_b] int32 view (codes as in ``plate_crops``).  The crops are enqueued here, before the next ``FrameBatcher.put`` may
+    reuse the frames' buffer."""
+    Hc, Wc = _crop_size(crop_hw)
+    det, count, counts = _detect_frames_padded(model, frames, img_size, conf_thres, iou_thres, max_det, auto, batch, out)
+    ns = [max(0, min(int(c), det.shape[1])) for c in counts[:len(frames)]]
+    offs = np.concatenate([[0], np.cumsum(ns)]).astype(int).tolist()
+    crops = torch.empty(offs[-1], Hc, Wc, 3, dtype=torch.uint8, device=det.device)
+    status = torch.empty(offs[-1], dtype=torch.int32, device=det.device)
+    _plate_crops_launch(frames, det, count, list(zip(ns, offs)), crops, status, (Hc, Wc))
+    return ([det[b, :counts[b]] for b in range(len(frames))], [crops[o:o + k] for o, k in zip(offs, ns)],
+            [status[o:o + k] for o, k in zip(offs, ns)])
 
 
 def eval_counts(det, det_count, tgt, tgt_count, counts=None):
