@@ -283,6 +283,56 @@ int lp_preprocess_letterbox_batch(const lp_frame_desc* desc, int n_frames, int B
                                   void* stream);
 int lp_rescale_round_batch(float* det, const int32_t* count, int B, int max_det, const lp_rescale_desc* desc, void* stream);
 
+/* Tiled detection of large frames: a 3840x2160 frame letterboxed to one 640x640 input is shrunk 6x and its plates with it.  The
+ * reference has nothing here (Inferer shrinks every frame, inferer.py:191-201); these two entry points put the work around
+ * the forward on the device: cutting letterboxed tiles out of device frames, and merging the per-tile detections per frame.
+ *
+ * lp_preprocess_tiles_batch extends lp_preprocess_letterbox_batch (same kernel, same conventions: descriptors by value in the
+ * kernel arguments, one launch per LP_FRAMES_PER_LAUNCH tiles, nothing uploaded, no host sync): slot b < n_tiles of out
+ * [B,3,H,W] is bit-identical to what lp_preprocess_letterbox_batch writes for a CONTIGUOUS COPY of the region
+ * frame[y0:y0+th, x0:x0+tw] with the same (rh, rw, top, left) -- the bilinear taps clamp at the region's edges, not the
+ * frame's; slots n_tiles <= b < B are padding (114/255).  The region is read in place: its first pixel and the frame's row
+ * pitch of w0*3 bytes.  desc is a HOST array of n_tiles entries, all checked before the first launch (LP_ERR_ARG names the
+ * tile): img, h0, w0 >= 1, region inside the frame with th, tw >= 1, geometry inside H x W. */
+typedef struct lp_tile_desc {
+    const unsigned char* img;   /* the device frame, uint8 [h0,w0,3] BGR, any alignment */
+    int h0, w0;
+    int y0, x0, th, tw;         /* the region of it */
+    int rh, rw, top, left;      /* letterbox geometry of a (th, tw) image */
+} lp_tile_desc;
+int lp_preprocess_tiles_batch(const lp_tile_desc* desc, int n_tiles, int B, void* out, int out_dtype, int H, int W, void* stream);
+
+/* lp_merge_tiles: per-frame merge of per-tile detections; one workgroup per frame, at most 64 tiles (whole frames) per launch,
+ * the tile table travels as kernel arguments: nothing is uploaded, no host sync.
+ *   det_t [n_tiles,max_det_t,28] fp32 + count_t [n_tiles] int32 (DEVICE): the tiles' detections as lp_nms leaves them, in
+ *   tile-local source pixels, rounded, i.e. after lp_rescale_round_batch with each tile's (th, tw) as its source image.
+ *   tiles: HOST array, tile t belongs to frame tiles[t].frame and covers (y0, x0, th, tw) of it; the tiles of a frame are
+ *   contiguous, frames ascending.  frame_hw: HOST int [n_frames][2] = (h, w).
+ *   det [n_frames,max_det,28], count [n_frames], src [n_frames,max_det] int32 (tile index x max_det_t + row of every kept row,
+ *   tiles counted from 0 over the whole call; -1 past the count).  Rows at or past count[f] are zero, as lp_nms leaves them.
+ * Per frame, in this order (yolov6/utils/tiles.py::merge_tiles_np restates it bit for bit):
+ *   1. candidates: rows r < min(max(count_t[t], 0), max_det_t) of the frame's tiles, in (tile, row) order;
+ *   2. cut-plate filter (border >= 0; negative: off): with the tile-local box (x1,y1,x2,y2) = columns 0..3 a row is dropped if
+ *      x0 > 0 && x1 <= border, or y0 > 0 && y1 <= border, or x0 + tw < w && x2 >= tw - border, or y0 + th < h && y2 >= th - border
+ *      (a box touching a tile side that is not a frame side is a plate cut by the slicing; the neighbouring tile sees it whole);
+ *   3. shift: columns 0,2,..,10 += (float)x0, columns 1,3,..,11 += (float)y0; columns 12..27 are copied;
+ *   4. score = (c12 + c13 + ... + c19) / 8.0f, summed left to right in fp32 (nms.py:120); order: descending score (-0 = +0; NaNs
+ *      by their bit pattern, as the keys of lp_nms order them), ties in candidate order;
+ *   5. greedy suppression ACROSS tiles only: in that order a candidate is kept unless an already kept candidate of ANOTHER tile
+ *      overlaps it by more than thres.  metric 0 (IoU): torchvision's predicate as lp_nms evaluates it (fp32 op by op, the
+ *      quotient compared against the double threshold); metric 1 (IoS): inter / min(area_i, area_j) > thres, the same fp32 ops
+ *      with that denominator (IEEE division: a zero area gives NaN = not suppressed, or +inf = suppressed);
+ *   6. the first max_det kept rows, in order.
+ * A frame covered by one tile therefore comes out as that tile's rows, unchanged and in order.
+ * Limits (LP_ERR_ARG, with the numbers in the message): at most 64 tiles per frame, and tiles_of_frame * max_det_t <= 16384
+ * candidate slots per frame (they are sorted in LDS).  workspace: DEVICE, 16-byte aligned, lp_merge_tiles_workspace_bytes
+ * bytes (kept lists that outgrow LDS).  Every argument is checked before the first launch. */
+typedef struct lp_tile_ref { int frame, y0, x0, th, tw; } lp_tile_ref;
+size_t lp_merge_tiles_workspace_bytes(int n_frames, int max_det);
+int lp_merge_tiles(const float* det_t, const int32_t* count_t, const lp_tile_ref* tiles, int n_tiles, int max_det_t,
+                   const int* frame_hw, int n_frames, double thres, int metric /* 0 IoU, 1 IoS */, int border, int max_det,
+                   float* det, int32_t* count, int32_t* src, void* workspace, size_t workspace_bytes, void* stream);
+
 /* lp_plate_crops_batch: perspective-rectified plate crops of B frames' detections (the inverse of the warp of the reference's
  * plate generator, yolov6/data/generate/generate.py:566-586), one launch per LP_FRAMES_PER_LAUNCH frames; descriptors travel
  * as kernel arguments, so nothing is uploaded and the call may be captured in a graph.

@@ -3,6 +3,8 @@
 
     python tools/frames_bench.py [--model yololps] [--size 640] [--dtype f16] [--frame 1080 1920] [--batches 8 32 64]
                                  [--crops N]
+    python tools/frames_bench.py --tile [--tile-baseline] [--tile-frame 2160 3840] [--tile-size 640] [--tile-overlap 128]
+                                 [--tile-frames 4] [--tile-batch 32] [--runs 3]
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
   - frames/s of the per-frame path (upload, lp_preprocess_letterbox, detect at B=1 with hipGraph replay, lp_rescale_round,
@@ -13,6 +15,13 @@ Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by defa
   - with ``--crops N``, the device time of the plate-crop stage (runtime.plate_crops, 64x192 crops) on N seeded synthetic
     quads per frame (rotated and perspective plates, and one in four with unusable corners that falls back to its box),
     timed in the same event chain right behind rescale, and its share of the detect stage.
+With ``--tile`` the tool measures tiled detection of large frames instead (its other modes are unchanged): seeded frames
+of ``--tile-frame`` (3840x2160 by default) already on the device, ``runtime.detect_tiled_with_crops`` on ``--tile-frames`` of
+them per call -- frames/s over ``--runs`` timed runs, and the device time of each stage from events: tile letterbox
+(lp_preprocess_tiles_batch), detect, rescale, merge (lp_merge_tiles), crops.  ``--tile-baseline`` also times, in the same
+run, the same job done with the entry points that existed before tiling: region copies made contiguous on the device,
+``detect_frames(auto=False)`` per ``--tile-batch`` tiles, the detections read to the host and merged there by
+``merge_tiles_np``.
 The model is the synthetic recipe of bench.py (same weights scale), prepared as Inferer prepares it.
 """
 import argparse
@@ -45,7 +54,115 @@ def parse():
     ap.add_argument('--iou', type=float, default=0.45)
     ap.add_argument('--max-det', type=int, default=1000)
     ap.add_argument('--crops', type=int, default=0, help='plate crops per frame to time (0: no crop stage)')
+    ap.add_argument('--tile', action='store_true', help='measure tiled detection of large frames (detect_tiled) instead')
+    ap.add_argument('--tile-baseline', action='store_true', help='with --tile: also time region copies + detect_frames + host merge')
+    ap.add_argument('--tile-frame', nargs=2, type=int, default=[2160, 3840], metavar=('H', 'W'))
+    ap.add_argument('--tile-size', type=int, default=None, help='tile side (default: --size)')
+    ap.add_argument('--tile-overlap', type=int, default=128, help='tile overlap in pixels')
+    ap.add_argument('--tile-frames', type=int, default=4, help='frames per detect_tiled call')
+    ap.add_argument('--tile-batch', type=int, default=32, help='tiles per forward')
+    ap.add_argument('--runs', type=int, default=3, help='timed runs of the frames/s figures (the spread is reported)')
     return ap.parse_args()
+
+
+def tile_mode(args, model, dev, tdt):
+    """--tile: frames/s of detect_tiled_with_crops (and of the baseline) and the device time of every stage."""
+    import torch
+    from yolov6.hip import runtime
+    from yolov6.utils.tiles import merge_tiles_np
+    size, stride = [args.size, args.size], int(model.stride.max())
+    h0, w0 = args.tile_frame
+    tile = args.tile_size or args.size
+    F, B = args.tile_frames, args.tile_batch
+    conf, iou, max_det = args.conf, args.iou, args.max_det
+    rng = np.random.default_rng(0)
+    frames = [torch.from_numpy(rng.integers(0, 256, (h0, w0, 3), dtype=np.uint8)).to(dev) for _ in range(F)]
+    shapes = [(h0, w0)] * F
+    tiles, tmd = runtime.plan_tiled(shapes, size, max_det, (tile, tile), args.tile_overlap, True)
+    kw = dict(tile_hw=(tile, tile), overlap=args.tile_overlap, batch=B)
+    sync = torch.cuda.synchronize
+    out = dict(metric='frames/s of tiled detection (device frames in, merged detections + crops out)', model=args.model,
+               dtype=args.dtype, frame=[h0, w0], tile=tile, overlap=args.tile_overlap, tiles_per_frame=len(tiles) // F,
+               frames_per_call=F, tiles_per_forward=B, tile_max_det=tmd, runs=args.runs)
+
+    def timed(fn, calls):
+        fn()
+        sync()
+        fps = []
+        for _ in range(args.runs):
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                fn()
+            sync()
+            fps.append(round(calls * F / (time.perf_counter() - t0), 2))
+        return fps
+
+    def tiled():
+        return runtime.detect_tiled_with_crops(model, frames, size, conf, iou, max_det, **kw)
+
+    def baseline():         # what the entry points before tiling can do for the same job
+        dets, counts = [], []
+        for c0 in range(0, len(tiles), B):
+            copies = [frames[f][y0:y0 + th, x0:x0 + tw].contiguous() for f, y0, x0, th, tw in tiles[c0:c0 + B]]
+            det, count, _ = runtime._detect_frames_padded(model, copies, size, conf, iou, tmd, False, B, None)
+            dets.append(det[:len(copies)].cpu().numpy())
+            counts.append(count[:len(copies)].cpu().numpy())
+        det, count, _ = merge_tiles_np(np.concatenate(dets), np.concatenate(counts), tiles, shapes, iou, max_det)
+        d_det, d_count = torch.from_numpy(det).to(dev), torch.from_numpy(count).to(dev)
+        ns = [int(c) for c in count]
+        return det, runtime.plate_crops(frames, d_det, d_count, max_crops=max(ns + [1]))
+
+    with torch.no_grad():
+        runtime.prepare_for(model, (B, 3, *size), tdt)
+        dets, _, _ = tiled()
+        out['detections_per_frame'] = [len(d) for d in dets]
+        calls = max(2, args.frames // (F * 8))
+        out['tiled_fps_runs'] = timed(tiled, calls)
+        out['tiled_fps'] = float(np.median(out['tiled_fps_runs']))
+        if args.tile_baseline:
+            bdet, _ = baseline()
+            out['baseline_equal'] = all(np.array_equal(bdet[f, :len(dets[f])], dets[f].cpu().numpy()) for f in range(F))
+            out['baseline_fps_runs'] = timed(baseline, calls)
+            out['baseline_fps'] = float(np.median(out['baseline_fps_runs']))
+            out['tiled_over_baseline'] = round(out['tiled_fps'] / out['baseline_fps'], 3)
+
+        # device time per stage of one call, from events on one stream
+        x = torch.empty(B, 3, *size, dtype=tdt, device=dev)
+        names = ('tile_letterbox', 'detect', 'rescale', 'merge', 'crops')
+        times = {k: [] for k in names}
+        for _ in range(args.reps + 1):
+            acc = dict.fromkeys(names, 0.0)
+            pairs = []
+
+            def mark(name, fn):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                r = fn()
+                b.record()
+                pairs.append((name, a, b))
+                return r
+
+            dl, cl = [], []
+            for c0 in range(0, len(tiles), B):
+                mark('tile_letterbox', lambda: runtime.preprocess_tiles(frames, tiles[c0:c0 + B], size, stride, tdt, batch=B, out=x))
+                det, count, _ = mark('detect', lambda: runtime.detect_padded(model, x, conf, iou, tmd))
+                dl.append(det)
+                cl.append(count)
+            det_t, count_t = torch.cat(dl), torch.cat(cl)
+            mark('rescale', lambda: runtime.rescale_round_batch(det_t, count_t, size, [(t[3], t[4]) for t in tiles]))
+            det, count, _ = mark('merge', lambda: runtime.merge_tiles(det_t, count_t, tiles, shapes, iou, max_det))
+            mark('crops', lambda: runtime.plate_crops(frames, det, count, max_crops=16))
+            sync()
+            for name, a, b in pairs:
+                acc[name] += a.elapsed_time(b)
+            for k in names:
+                times[k].append(acc[k])
+        med = {k: float(np.median(v[1:])) for k, v in times.items()}
+        out['stage_ms_per_call'] = {k: round(v, 4) for k, v in med.items()}
+        out['stage_pct_of_detect'] = {k: round(100.0 * med[k] / med['detect'], 2) for k in names if k != 'detect'}
+        out['merged_counts'] = count.cpu().tolist()
+        out['candidates_per_frame'] = [int(count_t[f * (len(tiles) // F):(f + 1) * (len(tiles) // F)].clamp(0, tmd).sum()) for f in range(F)]
+    print(json.dumps(out))
 
 
 def synthetic_quads(n_frames, n, h0, w0, seed=0):
@@ -103,6 +220,8 @@ def main():
             layer.switch_to_deploy()
     model = model.to(dev).to(tdt)
     model.lp_graph = True                   # as Inferer sets it
+    if args.tile:
+        return tile_mode(args, model, dev, tdt)
     size, stride = [args.size, args.size], int(model.stride.max())
     h0, w0 = args.frame
     rng = np.random.default_rng(0)

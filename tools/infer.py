@@ -3,6 +3,7 @@
 
     python tools/infer.py --weights weights/yololps.pt --source data/images --yaml data/dataset.yaml [--half]
                           [--batch-size 32] [--fixed-shape] [--save-crops [--crop-size 64 192]]
+                          [--tile 640 640 [--tile-overlap 0.2] [--no-tile-overview] [--merge-metric iou|ios]]
 """
 import argparse
 import os
@@ -43,6 +44,12 @@ _FLAGS = [
     ('--fixed-shape', dict(action='store_true', help='letterbox every frame to exactly --img-size (no stride-multiple trim)')),
     ('--save-crops', dict(action='store_true', help='write every plate, rectified along its four corners, as crops/<stem>_<k>.png')),
     ('--crop-size', dict(nargs=2, type=int, default=[64, 192], metavar=('H', 'W'), help='size of the plate crops, h w')),
+    ('--tile', dict(nargs=2, type=int, default=None, metavar=('H', 'W'),
+                    help='detect large frames by overlapping tiles of this size (plus the whole frame), merged per frame; '
+                         '--batch-size is then tiles per forward')),
+    ('--tile-overlap', dict(type=float, default=0.2, help='overlap of neighbouring tiles: pixels, or a fraction of the tile below 1')),
+    ('--no-tile-overview', dict(action='store_true', help='do not add the whole frame as one more tile')),
+    ('--merge-metric', dict(default='iou', choices=['iou', 'ios'], help='overlap measure of the cross-tile merge')),
 ]
 
 
@@ -59,7 +66,8 @@ def get_args_parser(add_help=True):
 def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images'), yaml=None, img_size=640,
         conf_thres=0.4, iou_thres=0.45, max_det=1000, device='', save_txt=False, not_save_img=False, save_dir=None,
         view_img=True, classes=None, agnostic_nms=False, project=osp.join(ROOT, 'runs/inference'), name='exp',
-        hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False, save_crops=False, crop_size=(64, 192)):
+        hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False, save_crops=False, crop_size=(64, 192),
+        tile=None, tile_overlap=0.2, no_tile_overview=False, merge_metric='iou'):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops) and not osp.exists(out_dir):
@@ -68,7 +76,10 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         LOGGER.warning('Save directory already existed')
     if save_txt:
         os.makedirs(osp.join(out_dir, 'labels'), exist_ok=True)
-    results = Inferer(source, weights, device, yaml, img_size, half, batch_size=batch_size, auto=not fixed_shape).infer(
+    if tile is not None and tile_overlap >= 1:
+        tile_overlap = int(tile_overlap)        # pixels
+    results = Inferer(source, weights, device, yaml, img_size, half, batch_size=batch_size, auto=not fixed_shape, tile=tile,
+                      tile_overlap=tile_overlap, tile_overview=not no_tile_overview, merge_metric=merge_metric).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

@@ -1,4 +1,5 @@
-// Batched callers either side of the hot path: lp_preprocess_letterbox_batch and lp_rescale_round_batch (include/lp_hip.h).
+// Batched callers either side of the hot path: lp_preprocess_letterbox_batch, lp_preprocess_tiles_batch and lp_rescale_round_batch
+// (include/lp_hip.h).
 // They restate, for B frames of any source sizes in one launch per LP_FRAMES_PER_LAUNCH frames, what lp_prepost.hip does for
 // one frame: Inferer.precess_image + letterbox (reference yolov6/core/inferer.py:191-201, yolov6/data/data_augment.py:30-61)
 // and Inferer.rescale + .round() (inferer.py:203-228, :100).  Every output element is computed by the same expressions in the
@@ -7,6 +8,7 @@
 // Descriptors are passed by value as a kernel-argument table (at most 64 entries, < 4 KiB of kernarg): nothing is uploaded,
 // and the calls are safe under graph capture.
 #include "lp_internal.h"
+#include <vector>
 
 namespace lp {
 
@@ -18,7 +20,7 @@ constexpr int LB_ROWS = 16;             // output rows of one workgroup (4 waves
 struct LbEntry {
     const unsigned char* img;
     int h0, w0, rh, rw, top, left;      // rh = rw = 0: a padding slot
-    int resize, pad_;
+    int resize, pitch;                  // pitch: bytes between source rows (w0 * 3 for a whole frame; the frame's for a region of it)
     double sy, sx;                      // h0 / rh, w0 / rw: divided on the host, as lp_preprocess_letterbox does
 };
 struct LbTable { LbEntry f[LP_FRAMES_PER_LAUNCH]; };
@@ -67,10 +69,10 @@ __global__ __launch_bounds__(256) void letterbox_batch_kernel(const LbTable tab,
                 int y0;
                 resize_coef(ry, f.sy, f.h0, &y0, &b0, &b1);
                 const int y1 = y0 + 1 < f.h0 ? y0 + 1 : f.h0 - 1;
-                r0 = f.img + (long long)y0 * f.w0 * 3;
-                r1 = f.img + (long long)y1 * f.w0 * 3;
+                r0 = f.img + (long long)y0 * f.pitch;
+                r1 = f.img + (long long)y1 * f.pitch;
             } else {
-                r0 = f.img + (long long)ry * f.w0 * 3;
+                r0 = f.img + (long long)ry * f.pitch;
             }
         }
         TO v[3][4];
@@ -149,30 +151,23 @@ int launch_letterbox(const LbTable& tab, int nf, void* out, int H, int W, bool v
 
 using namespace lp;
 
-extern "C" int lp_preprocess_letterbox_batch(const lp_frame_desc* desc, int n_frames, int B, void* out, int out_dtype, int H, int W,
-                                             void* stream) {
-    const char* fn = "lp_preprocess_letterbox_batch: ";
-    if (out_dtype != LP_F16 && out_dtype != LP_BF16 && out_dtype != LP_F32) return fail(LP_ERR_ARG, std::string(fn) + "dtype");
-    if (!out || B < 1 || n_frames < 0 || n_frames > B || (n_frames > 0 && !desc) || H < 1 || W < 1 ||
-        (long long)ceil_div(H, LB_ROWS) * ceil_div(W, LB_COLS) > 0x7fffffffLL)
-        return fail(LP_ERR_ARG, std::string(fn) + "bad arguments (need out, 0 <= n_frames <= B, B >= 1, H, W >= 1)");
-    for (int b = 0; b < n_frames; ++b) {       // the rules of lp_preprocess_letterbox, all checked before any launch
-        const lp_frame_desc& d = desc[b];
-        if (!d.img || d.h0 < 1 || d.w0 < 1 || d.rh < 1 || d.rw < 1 || d.top < 0 || d.left < 0 || d.top + d.rh > H ||
-            d.left + d.rw > W)
-            return fail(LP_ERR_ARG, std::string(fn) + "bad geometry of frame " + std::to_string(b));
-    }
+// One source image of a letterbox launch: a whole frame (pitch = w0 * 3) or a region of one (img = the region's first pixel,
+// h0 x w0 = the region's size, pitch = the frame's).  The bilinear taps clamp at h0 / w0, i.e. at the region's edges.
+struct LbSrc { const unsigned char* img; int h0, w0, pitch, rh, rw, top, left; };
+
+// The launches of both entry points: slots [0, n) from `src`, slots [n, B) padding, LP_FRAMES_PER_LAUNCH slots per launch.
+static int letterbox_run(const LbSrc* src, int n, int B, void* out, int out_dtype, int H, int W, hipStream_t st) {
     const size_t esz = dtype_size(out_dtype);
     const bool vec = W % 4 == 0 && ((uintptr_t)out & 15) == 0;
-    hipStream_t st = (hipStream_t)stream;
     for (int b0 = 0; b0 < B; b0 += LP_FRAMES_PER_LAUNCH) {
         const int nf = B - b0 < LP_FRAMES_PER_LAUNCH ? B - b0 : LP_FRAMES_PER_LAUNCH;
         LbTable tab = {};
         for (int j = 0; j < nf; ++j) {
             LbEntry& e = tab.f[j];
-            if (b0 + j < n_frames) {
-                const lp_frame_desc& d = desc[b0 + j];
+            if (b0 + j < n) {
+                const LbSrc& d = src[b0 + j];
                 e.img = d.img; e.h0 = d.h0; e.w0 = d.w0; e.rh = d.rh; e.rw = d.rw; e.top = d.top; e.left = d.left;
+                e.pitch = d.pitch;
                 e.resize = !(d.rh == d.h0 && d.rw == d.w0);
                 e.sy = (double)d.h0 / d.rh;
                 e.sx = (double)d.w0 / d.rw;
@@ -188,6 +183,45 @@ extern "C" int lp_preprocess_letterbox_batch(const lp_frame_desc* desc, int n_fr
         if (rc != LP_OK) return rc;
     }
     return LP_OK;
+}
+
+extern "C" int lp_preprocess_letterbox_batch(const lp_frame_desc* desc, int n_frames, int B, void* out, int out_dtype, int H, int W,
+                                             void* stream) {
+    const char* fn = "lp_preprocess_letterbox_batch: ";
+    if (out_dtype != LP_F16 && out_dtype != LP_BF16 && out_dtype != LP_F32) return fail(LP_ERR_ARG, std::string(fn) + "dtype");
+    if (!out || B < 1 || n_frames < 0 || n_frames > B || (n_frames > 0 && !desc) || H < 1 || W < 1 ||
+        (long long)ceil_div(H, LB_ROWS) * ceil_div(W, LB_COLS) > 0x7fffffffLL)
+        return fail(LP_ERR_ARG, std::string(fn) + "bad arguments (need out, 0 <= n_frames <= B, B >= 1, H, W >= 1)");
+    std::vector<LbSrc> src((size_t)n_frames);
+    for (int b = 0; b < n_frames; ++b) {       // the rules of lp_preprocess_letterbox, all checked before any launch
+        const lp_frame_desc& d = desc[b];
+        if (!d.img || d.h0 < 1 || d.w0 < 1 || d.rh < 1 || d.rw < 1 || d.top < 0 || d.left < 0 || d.top + d.rh > H ||
+            d.left + d.rw > W || d.w0 > 0x7fffffff / 3)
+            return fail(LP_ERR_ARG, std::string(fn) + "bad geometry of frame " + std::to_string(b));
+        src[b] = {d.img, d.h0, d.w0, d.w0 * 3, d.rh, d.rw, d.top, d.left};
+    }
+    return letterbox_run(src.data(), n_frames, B, out, out_dtype, H, W, (hipStream_t)stream);
+}
+
+extern "C" int lp_preprocess_tiles_batch(const lp_tile_desc* desc, int n_tiles, int B, void* out, int out_dtype, int H, int W,
+                                         void* stream) {
+    const char* fn = "lp_preprocess_tiles_batch: ";
+    if (out_dtype != LP_F16 && out_dtype != LP_BF16 && out_dtype != LP_F32) return fail(LP_ERR_ARG, std::string(fn) + "dtype");
+    if (!out || B < 1 || n_tiles < 0 || n_tiles > B || (n_tiles > 0 && !desc) || H < 1 || W < 1 ||
+        (long long)ceil_div(H, LB_ROWS) * ceil_div(W, LB_COLS) > 0x7fffffffLL)
+        return fail(LP_ERR_ARG, std::string(fn) + "bad arguments (need out, 0 <= n_tiles <= B, B >= 1, H, W >= 1)");
+    std::vector<LbSrc> src((size_t)n_tiles);
+    for (int b = 0; b < n_tiles; ++b) {        // every tile is checked before any launch
+        const lp_tile_desc& d = desc[b];
+        if (!d.img || d.h0 < 1 || d.w0 < 1 || d.w0 > 0x7fffffff / 3 || d.y0 < 0 || d.x0 < 0 || d.th < 1 || d.tw < 1 ||
+            d.th > d.h0 - d.y0 || d.tw > d.w0 - d.x0)
+            return fail(LP_ERR_ARG, std::string(fn) + "region of tile " + std::to_string(b) + " is not inside its frame");
+        if (d.rh < 1 || d.rw < 1 || d.top < 0 || d.left < 0 || d.top + d.rh > H || d.left + d.rw > W)
+            return fail(LP_ERR_ARG, std::string(fn) + "bad geometry of tile " + std::to_string(b));
+        // the region as a view of the frame: its first pixel, its own size, the frame's row pitch
+        src[b] = {d.img + ((long long)d.y0 * d.w0 + d.x0) * 3, d.th, d.tw, d.w0 * 3, d.rh, d.rw, d.top, d.left};
+    }
+    return letterbox_run(src.data(), n_tiles, B, out, out_dtype, H, W, (hipStream_t)stream);
 }
 
 extern "C" int lp_rescale_round_batch(float* det, const int32_t* count, int B, int max_det, const lp_rescale_desc* desc, void* stream) {

@@ -10,6 +10,9 @@ Drawing / video writing are cv2 GUI plumbing outside the hot-path scope: boxes a
 corner polygons are drawn with PIL when images are saved, labels are not rendered.
 With ``save_crops`` every detection's plate is also cut out along its four corners as
 an upright image (``runtime.plate_crops`` on a GPU, ``plate_crops_np`` on the CPU).
+With ``tile`` every frame is detected by overlapping tiles of that size plus an overview of the whole frame, merged per
+frame (``runtime.detect_tiled`` on a GPU; per-tile inference and ``merge_tiles_np`` on the CPU): for frames much larger
+than the network input, whose plates a single letterbox would shrink away.
 """
 import math
 import os
@@ -28,10 +31,17 @@ from yolov6.utils.nms import non_max_suppression
 
 
 class Inferer:
-    def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True):
+    def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True, tile=None, tile_overlap=0.2,
+                 tile_overview=True, merge_metric='iou'):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_infer_batched``);
-        ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple)."""
+        ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
+        ``tile`` = (h, w): tiled detection (``_infer_tiled``) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
+        the whole frame as one more tile with ``tile_overview``, and the cross-tile merge by ``merge_metric`` ('iou' / 'ios');
+        ``batch_size`` is then the number of tiles per forward."""
         self.__dict__.update(locals())
+        if merge_metric not in ('iou', 'ios'):
+            raise ValueError("merge_metric must be 'iou' or 'ios'")
+        self.tile = None if tile is None else ((int(tile), int(tile)) if isinstance(tile, int) else (int(tile[0]), int(tile[-1])))
         if int(batch_size) < 1:
             raise ValueError('batch_size must be >= 1')
         self.batch_size = int(batch_size)
@@ -73,6 +83,9 @@ class Inferer:
         """Run every source image through model + NMS; returns the list of rescaled ``[n, 28]`` detections.  ``save_crops``:
         also write the plate crop (``crop_size`` = (h, w)) of detection k of an image as ``<save_dir>/<rel>/crops/<stem>_<k>.png``
         (RGB; k is the line of the detection in ``<stem>.txt``)."""
+        if self.tile is not None:
+            return self._infer_tiled(conf_thres, iou_thres, classes, agnostic_nms, max_det, save_dir, save_txt, save_img, save_crops,
+                                     crop_size)
         if self.device.type != 'cpu' and self.batch_size > 1:
             return self._infer_batched(conf_thres, iou_thres, max_det, save_dir, save_txt, save_img, save_crops, crop_size)
         fps = CalcFPS()
@@ -171,6 +184,86 @@ class Inferer:
                 results.append(det)
         LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
         return results
+
+    def _infer_tiled(self, conf_thres, iou_thres, classes, agnostic_nms, max_det, save_dir, save_txt, save_img, save_crops=False,
+                     crop_size=(64, 192)):
+        """``infer`` by tiles.  On a GPU consecutive frames are grouped until their tiles fill a forward of ``batch_size`` tiles
+        (at least one frame per group), uploaded with one copy and run through ``runtime.detect_tiled`` (``..._with_crops``);
+        on the CPU every tile goes through the torch model and ``merge_tiles_np`` merges them (``tiled_rows_cpu``).  Writes and
+        returns per frame what the other paths do, in source order."""
+        from yolov6.core.tiles import plan_tiles
+        results = []
+        fps = CalcFPS()
+        if self.device.type == 'cpu':
+            for img_src, img_path, _ in self.files:
+                t1 = time.time()
+                det = self.tiled_rows_cpu(img_src, conf_thres, iou_thres, classes, agnostic_nms, max_det)
+                fps.update(1.0 / max(time.time() - t1, 1e-9))
+                self.save_outputs(img_src, img_path, det, save_dir, save_txt, save_img)
+                if save_crops and len(det):
+                    from yolov6.utils.plate_crop import plate_crops_np
+                    self.write_crops(img_path, plate_crops_np(img_src, det.numpy(), crop_size)[0], save_dir)
+                results.append(det)
+            LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
+            return results
+        from yolov6.hip import runtime
+        from yolov6.core.frames import FrameBatcher, prefetch_frames
+        from yolov6.data.datasets import imread_bgr
+        B = self.batch_size
+        batcher = FrameBatcher(self.device)
+        frames = self._frames_ahead(prefetch_frames, imread_bgr)
+        runtime.prepare_for(self.model.model, (B, 3, *self.img_size), torch.float16 if self.half else torch.float32)
+        kw = dict(tile_hw=self.tile, overlap=self.tile_overlap, overview=self.tile_overview, metric=self.merge_metric, batch=B)
+        pending = next(frames, None)
+        while pending is not None:
+            items, n_tiles = [], 0
+            while pending is not None:
+                k = len(plan_tiles(pending[0].shape, self.tile, self.tile_overlap, self.tile_overview))
+                if items and n_tiles + k > B:
+                    break
+                items.append(pending)
+                n_tiles += k
+                pending = next(frames, None)
+            t1 = time.time()
+            dev_frames = batcher.put([f for f, _ in items])
+            if save_crops:      # enqueued before the next put reuses the frames' buffer
+                dets, crops, _ = runtime.detect_tiled_with_crops(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres,
+                                                                 max_det, crop_size, **kw)
+            else:
+                dets = runtime.detect_tiled(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det, **kw)
+            t2 = time.time()
+            for _ in items:
+                fps.update(len(items) / max(t2 - t1, 1e-9))
+            for k, ((img_src, img_path), det) in enumerate(zip(items, dets)):
+                self.save_outputs(img_src, img_path, det, save_dir, save_txt, save_img)
+                if save_crops and len(det):
+                    self.write_crops(img_path, crops[k].cpu().numpy(), save_dir)
+                results.append(det)
+        LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
+        return results
+
+    def tiled_rows_cpu(self, img_src, conf_thres, iou_thres, classes, agnostic_nms, max_det, border=1):
+        """Tiled detection of one BGR frame on the CPU: [n, 28] fp32 tensor in frame pixels.  Every tile of the plan is
+        letterboxed to exactly ``img_size``, run through the model and the NMS, rescaled to tile pixels and rounded; then
+        ``merge_tiles_np`` (threshold ``iou_thres``)."""
+        from yolov6.core.tiles import plan_tiles
+        from yolov6.utils.tiles import MAX_CANDIDATES, merge_tiles_np
+        tiles = plan_tiles(img_src.shape, self.tile, self.tile_overlap, self.tile_overview)
+        tmd = max(1, min(int(max_det), MAX_CANDIDATES // len(tiles)))
+        det_t = np.zeros((len(tiles), tmd, 28), np.float32)
+        count_t = np.zeros(len(tiles), np.int32)
+        for t, (y0, x0, th, tw) in enumerate(tiles):
+            region = np.ascontiguousarray(img_src[y0:y0 + th, x0:x0 + tw])
+            img, _ = self.precess_image(region, self.img_size, self.stride, self.half, auto=False)
+            img = img.to(self.device)[None]
+            det = non_max_suppression(self.model(img), conf_thres, iou_thres, classes, agnostic_nms, max_det=tmd)[0]
+            if len(det):
+                det[:, :12] = self.rescale(img.shape[2:], det[:, :12], region.shape).round()
+                det_t[t, :len(det)] = det.detach().float().cpu().numpy()
+            count_t[t] = len(det)
+        det, count, _ = merge_tiles_np(det_t, count_t, [(0,) + t for t in tiles], [img_src.shape], iou_thres, max_det,
+                                       self.merge_metric, border)
+        return torch.from_numpy(det[0, :int(count[0])].copy())
 
     def _frames_ahead(self, prefetch_frames, imread_bgr):
         """(frame, path) of every source in LoadData's order: image files decoded ahead on the pool, videos read in turn."""

@@ -21,6 +21,7 @@ LP_VARIANT_FUSED_PW_S2 = 38                                                     
 LP_VARIANT_FUSED_STEM2 = 37                                                                      # input op + stem + the layer behind it as one kernel
 LP_VARIANT_PIPE_P = 36                                                                           # the stem reading the NCHW frame itself
 LP_FRAMES_PER_LAUNCH = 64   # lp_preprocess_letterbox_batch / lp_rescale_round_batch / lp_plate_crops_batch: frames per launch
+LP_MERGE_MAX_TILES, LP_MERGE_MAX_CANDIDATES = 64, 16384   # lp_merge_tiles: tiles per frame, tiles_of_frame * max_det_t
 LP_EVAL_NCOUNTS = 43   # lp_eval_counts: length of the counts vector (include/lp_hip.h)
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # .../yolo-lp_amd
@@ -41,6 +42,17 @@ class RescaleDesc(ctypes.Structure):
 class CropDesc(ctypes.Structure):
     """lp_crop_desc"""
     _fields_ = [('img', c_void_p), ('h0', c_int), ('w0', c_int), ('max_crops', c_int), ('out_slot', c_int)]
+
+
+class TileDesc(ctypes.Structure):
+    """lp_tile_desc"""
+    _fields_ = [('img', c_void_p), ('h0', c_int), ('w0', c_int), ('y0', c_int), ('x0', c_int), ('th', c_int), ('tw', c_int),
+                ('rh', c_int), ('rw', c_int), ('top', c_int), ('left', c_int)]
+
+
+class TileRef(ctypes.Structure):
+    """lp_tile_ref"""
+    _fields_ = [('frame', c_int), ('y0', c_int), ('x0', c_int), ('th', c_int), ('tw', c_int)]
 
 
 class ConvDesc(ctypes.Structure):
@@ -94,6 +106,10 @@ SYMBOLS = {
     'lp_rescale_round': (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_int, c_int, c_void_p]),
     'lp_preprocess_letterbox_batch': (c_int, [POINTER(FrameDesc), c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     'lp_rescale_round_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(RescaleDesc), c_void_p]),
+    'lp_preprocess_tiles_batch': (c_int, [POINTER(TileDesc), c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'lp_merge_tiles_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'lp_merge_tiles': (c_int, [c_void_p, c_void_p, POINTER(TileRef), c_int, c_int, POINTER(c_int), c_int, c_double, c_int, c_int, c_int,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'lp_plate_crops_batch': (c_int, [POINTER(CropDesc), c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                      c_void_p]),
     'lp_eval_counts': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -971,6 +971,181 @@ def detect_frames_with_crops(model, frames, img_size, conf_thres, iou_thres, max
             [status[o:o + k] for o, k in zip(offs, ns)])
 
 
+# ---------------------------------------------------------------------------------------------------
+# Tiled detection of large frames (yolov6/core/tiles.py plans the tiles; lp_preprocess_tiles_batch / lp_merge_tiles)
+def _net_hw(img_size):
+    if isinstance(img_size, (list, tuple)):
+        return (int(img_size[0]), int(img_size[0])) if len(img_size) == 1 else (int(img_size[0]), int(img_size[1]))
+    return int(img_size), int(img_size)
+
+
+def preprocess_tiles(frames, plans, img_size, stride, dtype, batch=None, out=None):
+    """Letterboxed regions of device frames (lp_preprocess_tiles_batch, one launch per 64 tiles): ``plans`` is a list of
+    (frame index, y0, x0, th, tw); tile k is read in place from ``frames[frame]`` (contiguous uint8 CUDA [h,w,3] BGR) and
+    letterboxed to exactly ``img_size`` (the reference arithmetic of a (th, tw) image, ``auto=False``) into slot k of
+    x [B,3,H,W] of ``dtype``: bit for bit what ``preprocess_frames(auto=False)`` gives for a contiguous copy of the region.
+    Returns (x, geoms) with ``geoms[k]`` = (rh, rw, top, left).  ``batch`` (>= len(plans)) sets B, the slots past the tiles
+    are padding (114/255); ``out``: a persistent [B,3,H,W] buffer to write."""
+    from yolov6.data.data_augment import letterbox_geometry
+    if dtype not in _DT:
+        raise TypeError('unsupported input dtype %s' % dtype)
+    if not frames:
+        raise ValueError('preprocess_tiles needs at least one frame')
+    dev = _frames_device(frames)
+    B = len(plans) if batch is None else int(batch)
+    if B < len(plans) or B < 1:
+        raise ValueError('batch %d < %d tiles (or < 1)' % (B, len(plans)))
+    H, W = _net_hw(img_size)
+    if out is None:
+        out = torch.empty(B, 3, H, W, dtype=dtype, device=dev)
+    elif not (out.shape == (B, 3, H, W) and out.dtype == dtype and out.device == dev and out.is_contiguous()):
+        raise ValueError('out must be a contiguous %s tensor [%d,3,%d,%d] on %s' % (dtype, B, H, W, dev))
+    desc = (abi.TileDesc * max(len(plans), 1))()
+    geoms = []
+    for d, (f, y0, x0, th, tw) in zip(desc, plans):
+        if not 0 <= f < len(frames):
+            raise ValueError('tile of frame %d: %d frames' % (f, len(frames)))
+        _, (rw, rh), (top, _, left, _), _ = letterbox_geometry((th, tw), [H, W], auto=False, stride=stride)
+        geoms.append((rh, rw, top, left))
+        fr = frames[f]
+        d.img, d.h0, d.w0 = fr.data_ptr(), fr.shape[0], fr.shape[1]
+        d.y0, d.x0, d.th, d.tw, d.rh, d.rw, d.top, d.left = y0, x0, th, tw, rh, rw, top, left
+    with torch.cuda.device(dev):
+        abi.check(abi.load().lp_preprocess_tiles_batch(desc, len(plans), B, ctypes.c_void_p(out.data_ptr()), _DT[dtype], H, W,
+                                                       ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                  'lp_preprocess_tiles_batch')
+    return out, geoms
+
+
+_METRICS = {'iou': 0, 'ios': 1}
+
+
+def merge_tiles(det_t, count_t, tiles, frame_shapes, thres, max_det, metric='iou', border=1):
+    """Per-frame merge of per-tile detections on the device (lp_merge_tiles; no host sync): det_t [T',max_det_t,28] fp32 and
+    count_t [T'] int32 hold the detections of tiles 0..len(tiles)-1 (T' >= len(tiles)) in tile-local source pixels, rounded;
+    ``tiles[t]`` = (frame, y0, x0, th, tw) with a frame's tiles contiguous and frames ascending; ``frame_shapes[f]`` =
+    (h, w[, c]).  Returns (det [F,max_det,28], count [F] int32, src [F,max_det] int32) in frame pixels -- the layout
+    ``plate_crops`` takes.  Highest-scoring view wins; rows of one tile never suppress each other.
+    ``yolov6.utils.tiles.merge_tiles_np`` is the same computation on the CPU, bit for bit, and states the rules."""
+    if not (det_t.is_cuda and det_t.dtype == torch.float32 and det_t.dim() == 3 and det_t.shape[2] == abi.LP_DET_COLS
+            and det_t.is_contiguous() and det_t.shape[0] >= len(tiles)):
+        raise ValueError('det_t must be a contiguous CUDA fp32 [T >= %d tiles, max_det_t, 28] tensor' % len(tiles))
+    if not (count_t.is_cuda and count_t.dtype == torch.int32 and count_t.is_contiguous() and count_t.numel() == det_t.shape[0]
+            and count_t.device == det_t.device):
+        raise ValueError('count_t must be a contiguous CUDA int32 [T] tensor on det_t\'s device')
+    if metric not in _METRICS:
+        raise ValueError('metric must be one of %s' % sorted(_METRICS))
+    dev, F, max_det = det_t.device, len(frame_shapes), int(max_det)
+    if max_det < 1:
+        raise ValueError('max_det must be >= 1')
+    ref = (abi.TileRef * max(len(tiles), 1))()
+    for r, (f, y0, x0, th, tw) in zip(ref, tiles):
+        r.frame, r.y0, r.x0, r.th, r.tw = f, y0, x0, th, tw
+    hw = (ctypes.c_int * max(2 * F, 1))(*[int(v) for s in frame_shapes for v in s[:2]])
+    lib = abi.load()
+    with torch.cuda.device(dev):
+        det = torch.empty(F, max_det, abi.LP_DET_COLS, dtype=torch.float32, device=dev)
+        count = torch.empty(F, dtype=torch.int32, device=dev)
+        src = torch.empty(F, max_det, dtype=torch.int32, device=dev)
+        need = lib.lp_merge_tiles_workspace_bytes(F, max_det)
+        ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
+        abi.check(lib.lp_merge_tiles(ctypes.c_void_p(det_t.data_ptr()), ctypes.c_void_p(count_t.data_ptr()), ref, len(tiles),
+                                     det_t.shape[1], hw, F, float(thres), _METRICS[metric], int(border), max_det,
+                                     ctypes.c_void_p(det.data_ptr()), ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(src.data_ptr()),
+                                     ctypes.c_void_p((ws.data_ptr() + 15) // 16 * 16), need,
+                                     ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'lp_merge_tiles')
+    return det, count, src
+
+
+_tile_inputs = {}      # (device, stream, dtype, B, H, W) -> persistent network input of the tile batches (graphs are keyed on the input pointer)
+
+
+def plan_tiled(frame_shapes, img_size, max_det, tile_hw=None, overlap=0.2, overview=True, tile_max_det=None):
+    """(tiles, tile_max_det) of ``detect_tiled`` for frames of ``frame_shapes``: the flat tile table (frame, y0, x0, th, tw)
+    and the detections kept per tile, min(max_det, 16384 // most tiles of any frame) by default."""
+    from yolov6.core.tiles import plan_frames, tiles_per_frame
+    tiles = plan_frames(frame_shapes, _net_hw(img_size) if tile_hw is None else tile_hw, overlap, overview)
+    most = max(tiles_per_frame(tiles, len(frame_shapes)))
+    if most > abi.LP_MERGE_MAX_TILES:
+        raise ValueError('%d tiles for one frame (at most %d): use larger tiles or a smaller overlap' % (most, abi.LP_MERGE_MAX_TILES))
+    tmd = min(int(max_det), abi.LP_MERGE_MAX_CANDIDATES // most) if tile_max_det is None else int(tile_max_det)
+    if tmd < 1:
+        raise ValueError('tile_max_det must be >= 1')
+    return tiles, tmd
+
+
+def detect_tiles_padded(model, frames, tiles, img_size, conf_thres, iou_thres, tile_max_det, batch=32):
+    """The per-tile half of ``detect_tiled``: the tiles (frame, y0, x0, th, tw) of ``frames`` in chunks of ``batch`` (the tail
+    padded, so the engine is bound once) through ``preprocess_tiles`` -> ``detect_padded``, then one ``rescale_round_batch``
+    over all tiles with each tile's (th, tw) as its source image.  Returns (det_t [T',tile_max_det,28], count_t [T']) on the
+    device, T' = len(tiles) rounded up to a multiple of ``batch``; no host sync."""
+    dev = _frames_device(frames)
+    dtype = next(model.parameters()).dtype
+    H, W = _net_hw(img_size)
+    B = int(batch)
+    if B < 1:
+        raise ValueError('batch must be >= 1')
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream, dtype, B, H, W)
+    x = _tile_inputs.get(key)
+    if x is None:
+        x = _tile_inputs[key] = torch.empty(B, 3, H, W, dtype=dtype, device=dev)
+    stride = int(model.stride.max())
+    dets, counts = [], []
+    for c0 in range(0, len(tiles), B):
+        preprocess_tiles(frames, tiles[c0:c0 + B], [H, W], stride, dtype, batch=B, out=x)
+        det, count, _ = detect_padded(model, x, conf_thres, iou_thres, tile_max_det)
+        dets.append(det)
+        counts.append(count)
+    det_t = dets[0] if len(dets) == 1 else torch.cat(dets)
+    count_t = counts[0] if len(counts) == 1 else torch.cat(counts)
+    rescale_round_batch(det_t, count_t, (H, W), [(t[3], t[4]) for t in tiles])
+    return det_t, count_t
+
+
+def _detect_tiled_padded(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw, overlap, overview, metric, border, batch,
+                         tile_max_det):
+    """The device work of ``detect_tiled`` and its one host read: (det [F,max_det,28], count [F] on the device, counts as a
+    host list)."""
+    if not frames:
+        raise ValueError('detect_tiled needs at least one frame')
+    shapes = [tuple(f.shape[:2]) for f in frames]
+    tiles, tmd = plan_tiled(shapes, img_size, max_det, tile_hw, overlap, overview, tile_max_det)
+    det_t, count_t = detect_tiles_padded(model, frames, tiles, img_size, conf_thres, iou_thres, tmd, batch)
+    det, count, _ = merge_tiles(det_t, count_t, tiles, shapes, iou_thres, max_det, metric, border)
+    return det, count, count.cpu().tolist()
+
+
+def detect_tiled(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw=None, overlap=0.2, overview=True, metric='iou',
+                 border=1, batch=32, tile_max_det=None):
+    """Detections of large frames (contiguous uint8 CUDA [h,w,3] BGR, any sizes) by tiles: every frame is sliced into
+    overlapping ``tile_hw`` tiles (default: the network input size, so a tile maps 1:1 to network pixels) plus, with
+    ``overview``, the whole frame (``yolov6.core.tiles.plan_tiles``); the tiles of all frames run through the engine ``batch``
+    at a time; the per-tile detections are rescaled to tile pixels, shifted and merged per frame on the device
+    (``merge_tiles``: threshold ``iou_thres``, ``metric`` 'iou' or 'ios', cut-plate ``border``), then ONE host read of the
+    per-frame counts.  Returns a list of [n_f, 28] tensors in frame pixels.  ``tile_max_det``: detections kept per tile
+    (default min(max_det, 16384 // most tiles of any frame)).  With ``tile_hw`` >= the frame this is
+    ``detect_frames(auto=False)``, bit for bit."""
+    det, _, counts = _detect_tiled_padded(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw, overlap, overview, metric,
+                                          border, batch, tile_max_det)
+    return [det[f, :counts[f]] for f in range(len(frames))]
+
+
+def detect_tiled_with_crops(model, frames, img_size, conf_thres, iou_thres, max_det, crop_hw=(64, 192), tile_hw=None, overlap=0.2,
+                            overview=True, metric='iou', border=1, batch=32, tile_max_det=None):
+    """``detect_tiled`` plus the plate crop of every merged detection, cut from the full-resolution frame: (dets, crops, status)
+    packed as ``detect_frames_with_crops`` packs them (``plate_crops`` on the merged det / count, which have its layout)."""
+    Hc, Wc = _crop_size(crop_hw)
+    det, count, counts = _detect_tiled_padded(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw, overlap, overview,
+                                              metric, border, batch, tile_max_det)
+    ns = [max(0, min(int(c), det.shape[1])) for c in counts]
+    offs = np.concatenate([[0], np.cumsum(ns)]).astype(int).tolist()
+    crops = torch.empty(offs[-1], Hc, Wc, 3, dtype=torch.uint8, device=det.device)
+    status = torch.empty(offs[-1], dtype=torch.int32, device=det.device)
+    _plate_crops_launch(frames, det, count, list(zip(ns, offs)), crops, status, (Hc, Wc))
+    return ([det[f, :counts[f]] for f in range(len(frames))], [crops[o:o + k] for o, k in zip(offs, ns)],
+            [status[o:o + k] for o, k in zip(offs, ns)])
+
+
 def eval_counts(det, det_count, tgt, tgt_count, counts=None):
     """Counters of the LP accuracy metric for one batch (``lp_eval_counts``): det [B,max_det,28] fp32 + det_count [B]
     int32 as ``nms_padded`` returns them, tgt [B,max_t,20] fp32 + tgt_count [B] int32; ``counts`` (int64 [43], CUDA) is
