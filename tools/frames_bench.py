@@ -104,7 +104,7 @@ def tile_mode(args, model, dev, tdt):
         dets, counts = [], []
         for c0 in range(0, len(tiles), B):
             copies = [frames[f][y0:y0 + th, x0:x0 + tw].contiguous() for f, y0, x0, th, tw in tiles[c0:c0 + B]]
-            det, count, _ = runtime._detect_frames_padded(model, copies, size, conf, iou, tmd, False, B, None)
+            det, count = runtime.detect_frames_padded(model, copies, size, conf, iou, tmd, auto=False, batch=B)
             dets.append(det[:len(copies)].cpu().numpy())
             counts.append(count[:len(copies)].cpu().numpy())
         det, count, _ = merge_tiles_np(np.concatenate(dets), np.concatenate(counts), tiles, shapes, iou, max_det)

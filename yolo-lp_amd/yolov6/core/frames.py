@@ -17,10 +17,16 @@ from yolov6.data.data_augment import letterbox_geometry
 MAX_DECODE_THREADS = 8
 
 
-def letterbox_hw(shape, img_size, stride, auto=True):
-    """(H, W) of the network input that a frame of ``shape`` (h, w[, c]) letterboxes to (reference letterbox arithmetic)."""
+def letterbox_placement(shape, img_size, stride, auto=True):
+    """(rh, rw, top, left, H, W): where a frame of ``shape`` (h, w[, c]) lands in its network input -- resized to (rh, rw),
+    at (top, left) of the (H, W) it letterboxes to (reference letterbox arithmetic)."""
     _, (rw, rh), (top, bottom, left, right), _ = letterbox_geometry(tuple(shape[:2]), img_size, auto=auto, stride=stride)
-    return rh + top + bottom, rw + left + right
+    return rh, rw, top, left, rh + top + bottom, rw + left + right
+
+
+def letterbox_hw(shape, img_size, stride, auto=True):
+    """(H, W) of the network input that a frame of ``shape`` (h, w[, c]) letterboxes to."""
+    return letterbox_placement(shape, img_size, stride, auto)[4:]
 
 
 def plan_batches(shapes, img_size, stride, batch, auto=True):

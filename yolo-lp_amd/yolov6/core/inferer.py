@@ -33,9 +33,9 @@ from yolov6.utils.nms import non_max_suppression
 class Inferer:
     def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True, tile=None, tile_overlap=0.2,
                  tile_overview=True, merge_metric='iou'):
-        """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_infer_batched``);
+        """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
-        ``tile`` = (h, w): tiled detection (``_infer_tiled``) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
+        ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
         the whole frame as one more tile with ``tile_overview``, and the cross-tile merge by ``merge_metric`` ('iou' / 'ios');
         ``batch_size`` is then the number of tiles per forward."""
         self.__dict__.update(locals())
@@ -82,165 +82,132 @@ class Inferer:
               hide_conf, view_img=True, save_crops=False, crop_size=(64, 192)):
         """Run every source image through model + NMS; returns the list of rescaled ``[n, 28]`` detections.  ``save_crops``:
         also write the plate crop (``crop_size`` = (h, w)) of detection k of an image as ``<save_dir>/<rel>/crops/<stem>_<k>.png``
-        (RGB; k is the line of the detection in ``<stem>.txt``)."""
-        if self.tile is not None:
-            return self._infer_tiled(conf_thres, iou_thres, classes, agnostic_nms, max_det, save_dir, save_txt, save_img, save_crops,
-                                     crop_size)
-        if self.device.type != 'cpu' and self.batch_size > 1:
-            return self._infer_batched(conf_thres, iou_thres, max_det, save_dir, save_txt, save_img, save_crops, crop_size)
+        (RGB; k is the line of the detection in ``<stem>.txt``).
+
+        The frames come in groups of ``(items, dets, crops or None, seconds)`` -- ``items`` = [(frame, path)], ``seconds`` the
+        timed model + NMS window of the group -- from ``_per_image`` (groups of one) or, on a GPU with ``tile`` or
+        ``batch_size > 1``, from ``_gpu_groups``; every path writes and returns per frame, in source order, the same things."""
+        if self.device.type != 'cpu' and (self.tile is not None or self.batch_size > 1):
+            groups = self._gpu_groups(conf_thres, iou_thres, max_det, save_crops, crop_size)
+        else:
+            groups = self._per_image(conf_thres, iou_thres, classes, agnostic_nms, max_det, save_crops, crop_size)
         fps = CalcFPS()
         results = []
+        for items, dets, crops, seconds in groups:
+            for _ in items:     # the FPS figure is per frame (group time / frames in the group)
+                fps.update(len(items) / max(seconds, 1e-9))
+            for k, ((img_src, img_path), det) in enumerate(zip(items, dets)):
+                self.save_outputs(img_src, img_path, det, save_dir, save_txt, save_img)
+                if save_crops and len(det):
+                    self.write_crops(img_path, crops[k], save_dir)
+                results.append(det)
+        LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
+        return results
+
+    def _per_image(self, conf_thres, iou_thres, classes, agnostic_nms, max_det, save_crops, crop_size):
+        """One frame per group: the reference's loop (on a GPU through the HIP letterbox / detect / rescale kernels), or with
+        ``tile`` on the CPU every tile through the torch model and ``merge_tiles_np`` (``tiled_rows_cpu``).  The timed window
+        is model + NMS alone, not the letterbox or the rescale."""
+        gpu = self.device.type != 'cpu'
+        if gpu:
+            from yolov6.hip import runtime
         for img_src, img_path, _ in self.files:
-            if self.device.type != 'cpu':      # letterbox + BGR->RGB + /255 in one HIP kernel on the uploaded frame
-                from yolov6.hip import runtime
+            if gpu:      # letterbox + BGR->RGB + /255 in one HIP kernel on the uploaded frame
                 frame = torch.from_numpy(np.ascontiguousarray(img_src)).to(self.device)
                 img = runtime.preprocess_letterbox(frame, self.img_size, self.stride,
-                                                   torch.float16 if self.half else torch.float32, auto=self.auto)
-            else:
+                                                   torch.float16 if self.half else torch.float32, auto=self.auto)[None]
+                runtime.prepare_for(self.model.model, img.shape, img.dtype)   # a new frame shape runs the kernel-variant tuner once: outside the FPS window
+            elif self.tile is None:
                 img, img_src = self.precess_image(img_src, self.img_size, self.stride, self.half, auto=self.auto)
-                img = img.to(self.device)
-            if len(img.shape) == 3:
-                img = img[None]
-            if img.is_cuda:      # a new frame shape runs the kernel-variant tuner once: outside the FPS window
-                from yolov6.hip import runtime
-                runtime.prepare_for(self.model.model, img.shape, img.dtype)
+                img = img.to(self.device)[None]
             t1 = time.time()
-            if img.is_cuda:
+            if gpu:
                 # model(img) -> non_max_suppression (reference :80-83) as one call: the detections-only forward, or forward +
                 # lp_nms when most anchors pass the mask (runtime.Engine.detect) -- the same detections bit for bit either way
                 det = runtime.detect(self.model.model, img, conf_thres, iou_thres, max_det)[0]
+            elif self.tile is None:
+                det = non_max_suppression(self.model(img), conf_thres, iou_thres, classes, agnostic_nms, max_det=max_det)[0]
             else:
-                pred_results = self.model(img)
-                det = non_max_suppression(pred_results, conf_thres, iou_thres, classes, agnostic_nms, max_det=max_det)[0]
-            t2 = time.time()
-            fps.update(1.0 / max(t2 - t1, 1e-9))
-
-            if len(det):
-                if det.is_cuda:
-                    from yolov6.hip import runtime
-                    runtime.rescale_round(img.shape[2:], det, img_src.shape)
-                else:
-                    det[:, :12] = self.rescale(img.shape[2:], det[:, :12], img_src.shape).round()
-            self.save_outputs(img_src, img_path, det, save_dir, save_txt, save_img)
+                det = self.tiled_rows_cpu(img_src, conf_thres, iou_thres, classes, agnostic_nms, max_det)
+            seconds = time.time() - t1
+            if len(det) and gpu:
+                runtime.rescale_round(img.shape[2:], det, img_src.shape)
+            elif len(det) and self.tile is None:      # (tiled_rows_cpu returns frame pixels)
+                det[:, :12] = self.rescale(img.shape[2:], det[:, :12], img_src.shape).round()
+            crops = None
             if save_crops and len(det):
-                if det.is_cuda:     # the uploaded frame and its detections are on the device: crop there
+                if gpu:     # the uploaded frame and its detections are on the device: crop there
                     count = torch.tensor([len(det)], dtype=torch.int32, device=self.device)
                     crops, _ = runtime.plate_crops([frame], det[None], count, crop_size, max_crops=len(det))
-                    crops = crops[0].cpu().numpy()
                 else:
                     from yolov6.utils.plate_crop import plate_crops_np
-                    crops, _ = plate_crops_np(img_src, det.detach().float().cpu().numpy(), crop_size)
-                self.write_crops(img_path, crops, save_dir)
-            results.append(det)
-        LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
-        return results
+                    crops = [plate_crops_np(img_src, det.detach().float().cpu().numpy(), crop_size)[0]]
+            yield [(img_src, img_path)], [det], crops, seconds
 
-    def _infer_batched(self, conf_thres, iou_thres, max_det, save_dir, save_txt, save_img, save_crops=False, crop_size=(64, 192)):
-        """``infer`` with ``batch_size`` frames per forward: consecutive frames of one letterboxed shape (``plan_batches``) go
-        through ``runtime.detect_frames`` together.  Image files are decoded on a small thread pool ahead of the GPU, each
-        batch is uploaded with one copy from pinned memory (``FrameBatcher``), and a short group is padded to the bound batch
-        size so that the engine is never set up for a new one.  Writes and returns per frame, in source order, exactly
-        what the per-frame loop does; the FPS figure is per frame (batch time / frames in the batch)."""
+    def _gpu_groups(self, conf_thres, iou_thres, max_det, save_crops, crop_size):
+        """Several frames per group on a GPU.  Image files are decoded on a small thread pool ahead of the GPU and each group
+        is uploaded with one copy from pinned memory (``FrameBatcher``).  Without ``tile``: consecutive frames of one
+        letterboxed shape (``plan_batches``) go through ``runtime.detect_frames`` together, a short group padded to the bound
+        batch size so that the engine is never set up for a new one.  With ``tile``: consecutive frames are grouped until
+        their tiles fill a forward of ``batch_size`` tiles (at least one frame per group) and run through
+        ``runtime.detect_tiled``.  The timed window is the upload through the runtime call (``..._with_crops`` with
+        ``save_crops``: the crops of every detection are enqueued before the next put reuses the frames' buffer)."""
         from yolov6.hip import runtime
         from yolov6.core.frames import FrameBatcher, letterbox_hw, plan_batches, prefetch_frames
+        from yolov6.core.tiles import plan_tiles
         from yolov6.data.datasets import imread_bgr
         B, dtype = self.batch_size, (torch.float16 if self.half else torch.float32)
-        batcher = FrameBatcher(self.device)
-        inputs = {}                     # (H, W) -> persistent [B,3,H,W] input buffer
-        fps = CalcFPS()
-        results = []
         frames = self._frames_ahead(prefetch_frames, imread_bgr)
-        window = deque()
-        while True:
-            while len(window) < B:
-                nxt = next(frames, None)
-                if nxt is None:
-                    break
-                window.append(nxt)
-            if not window:
-                break
-            group = plan_batches([f.shape for f, _ in window], self.img_size, self.stride, B, self.auto)[0]
-            items = [window.popleft() for _ in group]
-            H, W = letterbox_hw(items[0][0].shape, self.img_size, self.stride, self.auto)
-            x = inputs.get((H, W))
-            if x is None:
-                x = inputs[(H, W)] = torch.empty(B, 3, H, W, dtype=dtype, device=self.device)
-            runtime.prepare_for(self.model.model, x.shape, dtype)      # a new shape tunes once: outside the FPS window
-            t1 = time.time()
-            dev_frames = batcher.put([f for f, _ in items])
-            if save_crops:      # crops of every detection, enqueued before the next put reuses the frames' buffer
-                dets, crops, _ = runtime.detect_frames_with_crops(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres,
-                                                                  max_det, crop_size, auto=self.auto, batch=B, out=x)
-            else:
-                dets = runtime.detect_frames(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det,
-                                             auto=self.auto, batch=B, out=x)
-            t2 = time.time()
-            for _ in items:
-                fps.update(len(items) / max(t2 - t1, 1e-9))
-            for k, ((img_src, img_path), det) in enumerate(zip(items, dets)):
-                self.save_outputs(img_src, img_path, det, save_dir, save_txt, save_img)
-                if save_crops and len(det):
-                    self.write_crops(img_path, crops[k].cpu().numpy(), save_dir)
-                results.append(det)
-        LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
-        return results
 
-    def _infer_tiled(self, conf_thres, iou_thres, classes, agnostic_nms, max_det, save_dir, save_txt, save_img, save_crops=False,
-                     crop_size=(64, 192)):
-        """``infer`` by tiles.  On a GPU consecutive frames are grouped until their tiles fill a forward of ``batch_size`` tiles
-        (at least one frame per group), uploaded with one copy and run through ``runtime.detect_tiled`` (``..._with_crops``);
-        on the CPU every tile goes through the torch model and ``merge_tiles_np`` merges them (``tiled_rows_cpu``).  Writes and
-        returns per frame what the other paths do, in source order."""
-        from yolov6.core.tiles import plan_tiles
-        results = []
-        fps = CalcFPS()
-        if self.device.type == 'cpu':
-            for img_src, img_path, _ in self.files:
-                t1 = time.time()
-                det = self.tiled_rows_cpu(img_src, conf_thres, iou_thres, classes, agnostic_nms, max_det)
-                fps.update(1.0 / max(time.time() - t1, 1e-9))
-                self.save_outputs(img_src, img_path, det, save_dir, save_txt, save_img)
-                if save_crops and len(det):
-                    from yolov6.utils.plate_crop import plate_crops_np
-                    self.write_crops(img_path, plate_crops_np(img_src, det.numpy(), crop_size)[0], save_dir)
-                results.append(det)
-            LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
-            return results
-        from yolov6.hip import runtime
-        from yolov6.core.frames import FrameBatcher, prefetch_frames
-        from yolov6.data.datasets import imread_bgr
-        B = self.batch_size
-        batcher = FrameBatcher(self.device)
-        frames = self._frames_ahead(prefetch_frames, imread_bgr)
-        runtime.prepare_for(self.model.model, (B, 3, *self.img_size), torch.float16 if self.half else torch.float32)
-        kw = dict(tile_hw=self.tile, overlap=self.tile_overlap, overview=self.tile_overview, metric=self.merge_metric, batch=B)
-        pending = next(frames, None)
-        while pending is not None:
-            items, n_tiles = [], 0
+        def frame_groups():
+            inputs = {}                     # (H, W) -> persistent [B,3,H,W] input buffer
+            window = deque()
+            while True:
+                while len(window) < B:
+                    nxt = next(frames, None)
+                    if nxt is None:
+                        break
+                    window.append(nxt)
+                if not window:
+                    return
+                group = plan_batches([f.shape for f, _ in window], self.img_size, self.stride, B, self.auto)[0]
+                items = [window.popleft() for _ in group]
+                H, W = letterbox_hw(items[0][0].shape, self.img_size, self.stride, self.auto)
+                x = inputs.get((H, W))
+                if x is None:
+                    x = inputs[(H, W)] = torch.empty(B, 3, H, W, dtype=dtype, device=self.device)
+                runtime.prepare_for(self.model.model, x.shape, dtype)      # a new shape tunes once: outside the FPS window
+                yield items, dict(auto=self.auto, batch=B, out=x)
+
+        def tile_groups():
+            runtime.prepare_for(self.model.model, (B, 3, *self.img_size), dtype)
+            kw = dict(tile_hw=self.tile, overlap=self.tile_overlap, overview=self.tile_overview, metric=self.merge_metric, batch=B)
+            pending = next(frames, None)
             while pending is not None:
-                k = len(plan_tiles(pending[0].shape, self.tile, self.tile_overlap, self.tile_overview))
-                if items and n_tiles + k > B:
-                    break
-                items.append(pending)
-                n_tiles += k
-                pending = next(frames, None)
+                items, n_tiles = [], 0
+                while pending is not None:
+                    k = len(plan_tiles(pending[0].shape, self.tile, self.tile_overlap, self.tile_overview))
+                    if items and n_tiles + k > B:
+                        break
+                    items.append(pending)
+                    n_tiles += k
+                    pending = next(frames, None)
+                yield items, kw
+
+        if self.tile is None:
+            groups, detect, detect_with_crops = frame_groups(), runtime.detect_frames, runtime.detect_frames_with_crops
+        else:
+            groups, detect, detect_with_crops = tile_groups(), runtime.detect_tiled, runtime.detect_tiled_with_crops
+        batcher = FrameBatcher(self.device)
+        for items, kw in groups:
             t1 = time.time()
             dev_frames = batcher.put([f for f, _ in items])
-            if save_crops:      # enqueued before the next put reuses the frames' buffer
-                dets, crops, _ = runtime.detect_tiled_with_crops(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres,
-                                                                 max_det, crop_size, **kw)
+            if save_crops:
+                dets, crops, _ = detect_with_crops(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det,
+                                                   crop_size, **kw)
             else:
-                dets = runtime.detect_tiled(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det, **kw)
-            t2 = time.time()
-            for _ in items:
-                fps.update(len(items) / max(t2 - t1, 1e-9))
-            for k, ((img_src, img_path), det) in enumerate(zip(items, dets)):
-                self.save_outputs(img_src, img_path, det, save_dir, save_txt, save_img)
-                if save_crops and len(det):
-                    self.write_crops(img_path, crops[k].cpu().numpy(), save_dir)
-                results.append(det)
-        LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
-        return results
+                dets, crops = detect(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det, **kw), None
+            yield items, dets, crops, time.time() - t1
 
     def tiled_rows_cpu(self, img_src, conf_thres, iou_thres, classes, agnostic_nms, max_det, border=1):
         """Tiled detection of one BGR frame on the CPU: [n, 28] fp32 tensor in frame pixels.  Every tile of the plan is
@@ -299,8 +266,10 @@ class Inferer:
             self.save_annotated(img_src, [], save_path)
 
     def write_crops(self, img_path, crops_bgr, save_dir):
-        """Plate crops of one image (uint8 [n, h, w, 3] BGR) as ``<save_dir>/<rel>/crops/<stem>_<k>.png``, RGB."""
+        """Plate crops of one image (uint8 [n, h, w, 3] BGR, a tensor or an array) as ``<save_dir>/<rel>/crops/<stem>_<k>.png``, RGB."""
         from PIL import Image
+        if torch.is_tensor(crops_bgr):
+            crops_bgr = crops_bgr.cpu().numpy()
         crop_dir = osp.join(save_dir, osp.relpath(osp.dirname(img_path), osp.dirname(self.source)), 'crops')
         os.makedirs(crop_dir, exist_ok=True)
         stem = osp.splitext(osp.basename(img_path))[0]

@@ -34,22 +34,28 @@ class InflightForward:
         self._ws = [None] * self.depth          # detections-only path: one NMS workspace per engine ...
         self._ws_free = [None] * self.depth     # ... and the event after which its previous candidates are no longer needed
 
+    def _next_slot(self, x, fresh):
+        """Rotate to the next slot and make it ready for batch ``x``: (k, engine, stream, (B, H, W))."""
+        k = self._next
+        self._next = (k + 1) % self.depth
+        s = self.streams[k]
+        eng = self.engines[k]
+        shape = (x.shape[0], x.shape[2], x.shape[3])
+        if k and shape not in eng.tuned and shape in self.engines[0].tuned:
+            eng.copy_tuning(self.engines[0])      # tune once (engine 0), not once per engine
+        eng.set_single_lane(self.single_lane)     # (engine 0 is shared with the model's one-at-a-time callers)
+        if fresh:
+            s.wait_stream(torch.cuda.current_stream(self.device))
+        return k, eng, s, shape
+
     def submit(self, x, fresh=True):
         """Enqueue the forward of batch ``x`` on the next engine; returns (pred, event): ``pred`` [B,N,290] fp32 is
         complete once ``event`` has fired (make the consumer's stream wait for it and call ``pred.record_stream``).
         ``fresh``: ``x`` was just produced on the caller's current stream, so the engine's stream must wait for that stream;
         pass False for inputs that have long been resident."""
-        k = self._next
-        self._next = (k + 1) % self.depth
-        s = self.streams[k]
-        shape = (x.shape[0], x.shape[2], x.shape[3])
-        if k and shape not in self.engines[k].tuned and shape in self.engines[0].tuned:
-            self.engines[k].copy_tuning(self.engines[0])      # tune once (engine 0), not once per engine
-        self.engines[k].set_single_lane(self.single_lane)     # (engine 0 is shared with the model's one-at-a-time callers)
-        if fresh:
-            s.wait_stream(torch.cuda.current_stream(self.device))
+        _, eng, s, _ = self._next_slot(x, fresh)
         with torch.cuda.stream(s):
-            pred = self.engines[k].forward(x)
+            pred = eng.forward(x)
             done = torch.cuda.Event()
             done.record(s)
         x.record_stream(s)
@@ -59,16 +65,7 @@ class InflightForward:
         """Detections-only form of ``submit``: the forward of batch ``x`` writes NMS candidates (``Engine.forward_det``) into the
         slot's own workspace; returns (handle, event, release): run ``runtime.nms_candidates(handle, ...)`` on a stream that
         waits for ``event``, then call ``release(stream)`` so that the slot's next forward waits for that NMS."""
-        k = self._next
-        self._next = (k + 1) % self.depth
-        s = self.streams[k]
-        eng = self.engines[k]
-        shape = (x.shape[0], x.shape[2], x.shape[3])
-        if k and shape not in eng.tuned and shape in self.engines[0].tuned:
-            eng.copy_tuning(self.engines[0])
-        eng.set_single_lane(self.single_lane)
-        if fresh:
-            s.wait_stream(torch.cuda.current_stream(self.device))
+        k, eng, s, shape = self._next_slot(x, fresh)
         with torch.cuda.stream(s):
             if self._ws_free[k] is not None:
                 s.wait_event(self._ws_free[k])          # the NMS of this slot's previous batch has read its candidates

@@ -8,7 +8,8 @@ frames through the engine in batches and merges the per-tile detections per fram
 """
 
 
-def _pair(v):
+def hw_pair(v):
+    """(h, w) of a size given as one number, [n] or [h, w] (``img_size`` / ``tile_hw``)."""
     if isinstance(v, (list, tuple)):
         return (int(v[0]), int(v[0])) if len(v) == 1 else (int(v[0]), int(v[1]))
     return int(v), int(v)
@@ -36,7 +37,7 @@ def plan_tiles(shape, tile_hw, overlap=0.2, overview=True):
     gives one tile [0, n); else origins 0, t-ov, 2(t-ov), ... while origin + t < n, then a last origin n - t.  With
     ``overview`` and more than one tile the whole frame (0, 0, h, w) is appended as the last tile."""
     h, w = int(shape[0]), int(shape[1])
-    th, tw = _pair(tile_hw)
+    th, tw = hw_pair(tile_hw)
     if h < 1 or w < 1 or th < 1 or tw < 1:
         raise ValueError('frame %dx%d, tile %dx%d: sizes must be >= 1' % (h, w, th, tw))
     tiles = [(y0, x0, lh, lw) for y0, lh in _axis(h, th, overlap) for x0, lw in _axis(w, tw, overlap)]

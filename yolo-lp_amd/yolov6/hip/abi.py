@@ -20,6 +20,14 @@ LP_VARIANT_BOX_SPARSE, LP_VARIANT_BOX_DENSE = 46, 47                            
 LP_VARIANT_FUSED_PW_S2 = 38                                                                      # a 1x1 layer + the 3x3 stride-2 layer behind it as one kernel
 LP_VARIANT_FUSED_STEM2 = 37                                                                      # input op + stem + the layer behind it as one kernel
 LP_VARIANT_PIPE_P = 36                                                                           # the stem reading the NCHW frame itself
+#: short names of the variant codes above in ``Engine.profile`` (the plain tiles 0..7 print as 'A'..'H')
+VARIANT_SHORT = {
+    LP_VARIANT_STREAM64: 'S', LP_VARIANT_STREAM128: 'W', LP_VARIANT_ROWS: 'R',
+    LP_VARIANT_PIPE_D: 'Pd', LP_VARIANT_PIPE_B: 'Pb', LP_VARIANT_PIPE_F: 'Pf', LP_VARIANT_PIPE_C: 'Pc', LP_VARIANT_PIPE_P: 'Pp',
+    LP_VARIANT_FUSED_STEM2: 'Fz', LP_VARIANT_FUSED_PW_S2: 'Fp', LP_VARIANT_FUSED_BIFUSION: 'Fb',
+    LP_VARIANT_PIPE16_D: 'Md', LP_VARIANT_PIPE16_F: 'Mf', LP_VARIANT_PIPE16_V0: 'V0', LP_VARIANT_PIPE16_V1: 'V1',
+    LP_VARIANT_PIPE16_S2A: 'Xa', LP_VARIANT_PIPE16_S2B: 'Xb',
+}
 LP_FRAMES_PER_LAUNCH = 64   # lp_preprocess_letterbox_batch / lp_rescale_round_batch / lp_plate_crops_batch: frames per launch
 LP_MERGE_MAX_TILES, LP_MERGE_MAX_CANDIDATES = 64, 16384   # lp_merge_tiles: tiles per frame, tiles_of_frame * max_det_t
 LP_EVAL_NCOUNTS = 43   # lp_eval_counts: length of the counts vector (include/lp_hip.h)

@@ -18,6 +18,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from yolov6.core.frames import letterbox_placement
+from yolov6.core.tiles import hw_pair, plan_frames, tiles_per_frame
 from yolov6.hip import abi
 from yolov6.layers import common as L
 
@@ -25,6 +27,22 @@ DET_CROSSOVER = 0.5   # candidate density (candidates / anchors) above which for
 _DT = {torch.float16: abi.LP_F16, torch.bfloat16: abi.LP_BF16, torch.float32: abi.LP_F32}
 _TORCH_DT = {v: k for k, v in _DT.items()}
 CLS_HEADS = ('pro', 'alp', 'ad0', 'ad1', 'ad2', 'ad3', 'ad4', 'ad5')
+OP_KINDS = ('input', 'conv', 'deconv', 'pool', 'head_cls', 'head_box', 'stem')   # lp_engine_op_info's kind codes
+
+
+def _dptr(t):
+    """Device pointer of a tensor for the C ABI (None stays a null pointer)."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _aligned(buf):
+    """256-byte aligned base address inside ``buf``: arenas and workspaces are allocated 256 bytes larger than needed."""
+    return (buf.data_ptr() + 255) // 256 * 256
+
+
+def _stream_ptr(device):
+    """torch's current stream on ``device`` as the hipStream_t every launch of the library goes to."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _act_of(module):
@@ -87,7 +105,6 @@ class Engine:
         self.max_tuned_shapes = 32   # a directory of oddly sized frames must not pay the tuner for every new shape
         self.graph = False         # hipGraph replay of the forward (set_graph); pred is then a persistent buffer
         self.single_lane = True    # set_single_lane (the library's default; LP_LANES=1: execution lanes on)
-        self.fuse_siblings = os.environ.get('LP_NO_SIBLINGS') is None   # sibling layers on one input as one launch (conv_pair)
         self._last_stream = None   # stream of the last forward: a forward on ANOTHER stream waits for it (one arena)
         self._graph_pred = None
         self._graph_x = None       # graph mode: persistent staging copy of the input (fixed address)
@@ -115,7 +132,7 @@ class Engine:
         if self.device.type == 'cuda':
             with torch.cuda.device(self.device):
                 self.weights = torch.empty(self.weight_bytes + 256, dtype=torch.uint8, device=self.device)
-                abi.check(self.lib.lp_engine_upload(self.h, self._aligned(self.weights), self._stream()),
+                abi.check(self.lib.lp_engine_upload(self.h, _aligned(self.weights), _stream_ptr(self.device)),
                           'lp_engine_upload')
         return self
 
@@ -132,13 +149,6 @@ class Engine:
             pass
 
     # -- helpers -------------------------------------------------------------
-    @staticmethod
-    def _aligned(buf):
-        return ctypes.c_void_p((buf.data_ptr() + 255) // 256 * 256)
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _ptr(self, arr):
         self._keep.append(arr)
         return arr.ctypes.data_as(ctypes.c_void_p)
@@ -154,6 +164,11 @@ class Engine:
         """act(conv(cat(srcs))+b) [+ alpha*res] -> new tensor id; ``sl`` is the sources' log2 stride."""
         w, b = _f32(weight), _f32(bias)
         dst = self.tensor(w.shape[0], sl + (1 if s == 2 else 0))
+        self._add_conv(srcs, w, b, k, s, act, dst, res=res, alpha=alpha)
+        return dst
+
+    def _add_conv(self, srcs, w, b, k, s, act, dst, dst2=-1, res=None, alpha=0.0):
+        """One conv op (lp_conv_desc) on fp32 numpy weights: ``dst2`` >= 0 makes it a two-destination launch."""
         d = abi.ConvDesc()
         d.n_src = len(srcs)
         for i in range(abi.LP_MAX_SRC):
@@ -162,29 +177,20 @@ class Engine:
         d.res = -1 if res is None else res
         d.res_alpha = float(alpha)
         d.weight, d.bias = self._ptr(w), self._ptr(b)
-        d.dst2 = -1
+        d.dst2 = dst2
         abi.check(self.lib.lp_engine_add_conv(self.h, ctypes.byref(d)), 'lp_engine_add_conv')
-        return dst
 
     def conv_pair(self, srcs, wb1, wb2, k, s, act, sl):
         """Two sibling layers on the same input (same kernel size, stride, activation) as ONE launch with two destination
         tensors (lp_conv_desc.dst2): their weight rows stacked.  The sums of every output channel are those of the two
         separate layers (a cout tile never mixes rows), so the results are the same bits.  Returns (dst1, dst2)."""
         (w1, b1), (w2, b2) = [(_f32(w), _f32(b)) for w, b in (wb1, wb2)]
-        if w1.shape[0] % 8 != 0 or not self.fuse_siblings:
+        if w1.shape[0] % 8 != 0:                           # lp_conv_desc.dst2 wants the first layer's channels a multiple of 8
             return (self.conv(srcs, w1, b1, k, s, act, sl), self.conv(srcs, w2, b2, k, s, act, sl))
         w, b = np.ascontiguousarray(np.concatenate([w1, w2], 0)), np.ascontiguousarray(np.concatenate([b1, b2], 0))
         sl_out = sl + (1 if s == 2 else 0)
         dst1, dst2 = self.tensor(w1.shape[0], sl_out), self.tensor(w2.shape[0], sl_out)
-        d = abi.ConvDesc()
-        d.n_src = len(srcs)
-        for i in range(abi.LP_MAX_SRC):
-            d.src[i] = srcs[i] if i < len(srcs) else -1
-        d.dst, d.ksize, d.stride, d.act = dst1, k, s, act
-        d.res, d.res_alpha = -1, 0.0
-        d.weight, d.bias = self._ptr(w), self._ptr(b)
-        d.dst2 = dst2
-        abi.check(self.lib.lp_engine_add_conv(self.h, ctypes.byref(d)), 'lp_engine_add_conv')
+        self._add_conv(srcs, w, b, k, s, act, dst1, dst2)
         return dst1, dst2
 
     def cba_pair(self, m1, m2, srcs, sl):
@@ -332,24 +338,18 @@ class Engine:
                 t = [self.upsample(getattr(nk, 'upsample%d' % k), f, sl), feats[-2 - k]]
             sl -= 1
             x = self.stage(getattr(nk, names_p[k]), t, sl)
-        # The heads run behind the neck, level i's two towers on lanes i % 3 and (i + 1) % 3.  (Experiment, LP_HEADS_EARLY=1: each
-        # level's head issued right behind the neck layer that feeds it, on lanes 3 / 4 of its own, to run UNDER the rest of the
-        # bottom-up path.  Measured same-box: one batch in flight 2.46 ms either way, six in flight 13.8 -> 13.2 k images/s -- the
-        # neck's persistent 3x3 kernels hold every CU's LDS, so the head kernels interleave with them instead of filling gaps.)
-        heads_last = not os.environ.get('LP_HEADS_EARLY')
         self.neck_ids = [x]
-        if not heads_last:
-            self._head(det, 0, x, (0, 1) if nlev == 1 else (3, 4))
         for k in range(nlev - 1):                                  # bottom-up
             d = self.cba(getattr(nk, downs[k]), [x], sl)
             sl += 1
             x = self.stage(getattr(nk, names_n[k]), [d, fpn[-1 - k]], sl)
             self.neck_ids.append(x)
-            if not heads_last:
-                self._head(det, k + 1, x, (0, 1) if k + 2 == nlev else (3, 4))
-        if heads_last:
-            for i, f in enumerate(self.neck_ids):
-                self._head(det, i, f, (i % 3, (i + 1) % 3))
+        # The heads run behind the neck, level i's two towers on lanes i % 3 and (i + 1) % 3.  (Issuing each level's head right
+        # behind the neck layer that feeds it, on lanes of its own, was measured: equal with one batch in flight, slower with six --
+        # the neck's persistent 3x3 kernels hold every CU's LDS, so the head kernels interleave with them instead of filling gaps;
+        # DESIGN 6.3.)
+        for i, f in enumerate(self.neck_ids):
+            self._head(det, i, f, (i % 3, (i + 1) % 3))
         self.lane(0)
 
     def _head(self, det, i, f, lanes):
@@ -375,7 +375,6 @@ class Engine:
         abi.check(self.lib.lp_engine_add_head_box(self.h, r, i, bins, self._ptr(wb), self._ptr(bbias), proj),
                   'lp_engine_add_head_box')
         self.lane(0)
-        self.lane(0)
 
     # -- execution ---------------------------------------------------------------
     def bind(self, B, H, W):
@@ -391,7 +390,7 @@ class Engine:
         if self.arena is None or self.arena.numel() < need + 256:
             self.arena = None
             self.arena = torch.zeros(need + 256, dtype=torch.uint8, device=self.device)
-        abi.check(self.lib.lp_engine_bind(self.h, self._aligned(self.arena), need, B, H, W), 'lp_engine_bind')
+        abi.check(self.lib.lp_engine_bind(self.h, _aligned(self.arena), need, B, H, W), 'lp_engine_bind')
         self.bound = (B, H, W)
         self.n_anchors = self.lib.lp_engine_num_anchors(self.h)
 
@@ -438,7 +437,7 @@ class Engine:
                                                  ctypes.byref(h), ctypes.byref(w)), 'lp_engine_tensor_info')
         B = self.bound[0]
         esz = torch.empty(0, dtype=self.dtype).element_size()
-        base = (self.arena.data_ptr() + 255) // 256 * 256 - self.arena.data_ptr() + off.value
+        base = _aligned(self.arena) - self.arena.data_ptr() + off.value
         n = B * h.value * w.value * cs.value
         flat = self.arena[base:base + n * esz].view(self.dtype)
         return flat.view(B, h.value, w.value, cs.value)[..., :c.value].permute(0, 3, 1, 2)
@@ -450,8 +449,7 @@ class Engine:
         ``forward`` re-binds such a shape by itself, which is cheap.  No hipGraph is captured here: graphs are keyed on the
         input pointer (lp_engine_forward), so one captured for the dummy tensor could never be replayed; the caller's first
         forward captures its own."""
-        shape = (B, H, W)
-        if not self.autotune or shape in self.tuned or len(self.tuned) >= self.max_tuned_shapes:
+        if not self._untuned((B, H, W)):
             return
         x = torch.zeros(B, 3, H, W, dtype=x_dtype or self.dtype, device=self.device)
         graph = self.graph
@@ -464,31 +462,41 @@ class Engine:
             if graph:
                 self.set_graph(True)
 
-    def forward(self, x):
+    @staticmethod
+    def _check_input(x):
+        """The contiguous form of a network input [B,3,H,W] and its (B, H, W)."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError('expected [B,3,H,W], got %s' % (tuple(x.shape),))
         if x.dtype not in _DT:
             raise TypeError('unsupported input dtype %s' % x.dtype)
-        x = x.contiguous()
-        B, _, H, W = x.shape
+        return x.contiguous(), (x.shape[0], x.shape[2], x.shape[3])
+
+    def _new_pred(self, B):
+        return torch.empty(B, self.n_anchors, abi.LP_PRED_COLS, dtype=torch.float32, device=self.device)
+
+    def _untuned(self, shape):
+        """First batch of this (B, H, W) with the tuner on: its kernel variants are still to be timed."""
+        return self.autotune and shape not in self.tuned and len(self.tuned) < self.max_tuned_shapes
+
+    def forward(self, x):
+        x, shape = self._check_input(x)
         with torch.cuda.device(self.device):
             cur = self._stream_enter()
-            self.bind(B, H, W)
+            self.bind(*shape)
             if self.graph:      # fixed input and output addresses: one captured graph per shape, never re-captured
-                if self._graph_pred is None or self._graph_pred.shape != (B, self.n_anchors, abi.LP_PRED_COLS):
-                    self._graph_pred = torch.empty(B, self.n_anchors, abi.LP_PRED_COLS, dtype=torch.float32, device=self.device)
+                if self._graph_pred is None or self._graph_pred.shape != (shape[0], self.n_anchors, abi.LP_PRED_COLS):
+                    self._graph_pred = self._new_pred(shape[0])
                 pred = self._graph_pred
                 x = self._stage_for_graph(x)
             else:
-                pred = torch.empty(B, self.n_anchors, abi.LP_PRED_COLS, dtype=torch.float32, device=self.device)
-            if self.autotune and self.bound not in self.tuned and len(self.tuned) < self.max_tuned_shapes:
+                pred = self._new_pred(shape[0])
+            if self._untuned(shape):
                 # first batch of this shape: time the kernel variants of every conv layer in place, keep the best
-                abi.check(self.lib.lp_engine_autotune(self.h, ctypes.c_void_p(x.data_ptr()), _DT[x.dtype],
-                                                      ctypes.c_void_p(pred.data_ptr()), self._stream(), 5),
+                abi.check(self.lib.lp_engine_autotune(self.h, _dptr(x), _DT[x.dtype], _dptr(pred), _stream_ptr(self.device), 5),
                           'lp_engine_autotune')
-                self.tuned.add(self.bound)
-            abi.check(self.lib.lp_engine_forward(self.h, ctypes.c_void_p(x.data_ptr()), _DT[x.dtype],
-                                                 ctypes.c_void_p(pred.data_ptr()), self._stream()), 'lp_engine_forward')
+                self.tuned.add(shape)
+            abi.check(self.lib.lp_engine_forward(self.h, _dptr(x), _DT[x.dtype], _dptr(pred), _stream_ptr(self.device)),
+                      'lp_engine_forward')
             self._stream_leave(cur)
         return pred
 
@@ -506,33 +514,24 @@ class Engine:
         workspace instead of the [B,N,290] prediction tensor.  Returns the handle ``nms_candidates`` takes: (workspace tensor,
         B, N).  ``ws``: a workspace to reuse (the caller orders its previous use before this call); by default the
         workspace of the current (device, stream)."""
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError('expected [B,3,H,W], got %s' % (tuple(x.shape),))
-        if x.dtype not in _DT:
-            raise TypeError('unsupported input dtype %s' % x.dtype)
+        x, shape = self._check_input(x)
         if not 0.0 <= conf_thres <= 1.0:
             raise ValueError('conf_thres must be in [0, 1]')
-        x = x.contiguous()
-        B, _, H, W = x.shape
         with torch.cuda.device(self.device):
-            if self.autotune and (B, H, W) not in self.tuned and len(self.tuned) < self.max_tuned_shapes:
+            if self._untuned(shape):
                 self.forward(x)                                 # first batch of this shape: bind + tune through the plain forward
             cur = self._stream_enter()
-            self.bind(B, H, W)
-            N = self.n_anchors
+            self.bind(*shape)
+            B, N = shape[0], self.n_anchors
             need = self.lib.lp_nms_workspace_bytes(B, N)
             if ws is None:
-                key = (self.device, torch.cuda.current_stream(self.device).cuda_stream)
-                ws = _nms_ws.get(key)
-                if ws is None or ws.numel() < need + 256:
-                    ws = _nms_ws[key] = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                ws = _nms_workspace(self.device, need)
             elif ws.numel() < need + 256:
                 raise ValueError('workspace too small: %d bytes needed' % (need + 256))
-            wsp = ctypes.c_void_p((ws.data_ptr() + 255) // 256 * 256)
             if self.graph:
                 x = self._stage_for_graph(x)
-            abi.check(self.lib.lp_engine_forward_det(self.h, ctypes.c_void_p(x.data_ptr()), _DT[x.dtype], float(conf_thres), wsp, need,
-                                                     self._stream()), 'lp_engine_forward_det')
+            abi.check(self.lib.lp_engine_forward_det(self.h, _dptr(x), _DT[x.dtype], float(conf_thres), _aligned(ws), need,
+                                                     _stream_ptr(self.device)), 'lp_engine_forward_det')
             self._stream_leave(cur)
         return ws, B, N
 
@@ -558,8 +557,7 @@ class Engine:
         if route == 'pred':
             pred = self.forward(x)
             out = nms_padded(pred, conf_thres, iou_thres, max_det, want_keep)
-            ws = _nms_ws[(self.device, torch.cuda.current_stream(self.device).cuda_stream)]
-            self._probe_pass_rate(ws, pred.shape[0], pred.shape[1])
+            self._probe_pass_rate(_nms_workspace(self.device, 0), pred.shape[0], pred.shape[1])   # the one nms_padded just filled
             return out
         handle = self.forward_det(x, conf_thres)
         out = nms_candidates(handle, iou_thres, max_det, want_keep)
@@ -569,8 +567,7 @@ class Engine:
     def _probe_pass_rate(self, ws, B, N):
         """Queue a copy of the workspace's per-image candidate counts to pinned host memory behind the work just enqueued."""
         with torch.cuda.device(self.device):
-            base = (ws.data_ptr() + 255) // 256 * 256
-            ptr = self.lib.lp_nms_candidate_counts(ctypes.c_void_p(base), B, N)
+            ptr = self.lib.lp_nms_candidate_counts(_aligned(ws), B, N)
             off = ptr - ws.data_ptr()
             pr = self._pass_probe
             if pr is None or pr[0].numel() != B:
@@ -587,14 +584,15 @@ class Engine:
     def op_kinds(self):
         """Kind name of every op of the frozen graph, in op order ('input', 'conv', 'deconv', 'pool', 'head_cls', 'head_box'); needs a
         bound arena (``bind`` / a forward)."""
-        out = []
-        for i in range(self.lib.lp_engine_num_ops(self.h)):
-            kind, ks, cin, cout = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-            fl, by = ctypes.c_double(), ctypes.c_double()
-            abi.check(self.lib.lp_engine_op_info(self.h, i, ctypes.byref(kind), ctypes.byref(ks), ctypes.byref(cin),
-                                                 ctypes.byref(cout), ctypes.byref(fl), ctypes.byref(by)), 'lp_engine_op_info')
-            out.append(('input', 'conv', 'deconv', 'pool', 'head_cls', 'head_box', 'stem')[kind.value])
-        return out
+        return [self._op_info(i)['kind'] for i in range(self.lib.lp_engine_num_ops(self.h))]
+
+    def _op_info(self, i):
+        """lp_engine_op_info of op ``i``: its kind name, kernel size, channels and algorithmic FLOPs / bytes."""
+        kind, ks, cin, cout = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        fl, by = ctypes.c_double(), ctypes.c_double()
+        abi.check(self.lib.lp_engine_op_info(self.h, i, ctypes.byref(kind), ctypes.byref(ks), ctypes.byref(cin),
+                                             ctypes.byref(cout), ctypes.byref(fl), ctypes.byref(by)), 'lp_engine_op_info')
+        return dict(kind=OP_KINDS[kind.value], ksize=ks.value, cin=cin.value, cout=cout.value, flops=fl.value, bytes=by.value)
 
     def profile(self, x, reps=3, inner=1):
         """Per-op device milliseconds (hipEvent pairs around ``inner`` back-to-back launches of each op) + op descriptions,
@@ -603,23 +601,17 @@ class Engine:
         B, _, H, W = x.shape
         with torch.cuda.device(self.device):
             self.bind(B, H, W)
-            pred = torch.empty(B, self.n_anchors, abi.LP_PRED_COLS, dtype=torch.float32, device=self.device)
+            pred = self._new_pred(B)
             n = self.lib.lp_engine_num_ops(self.h)
             ms = (ctypes.c_float * n)()
-            abi.check(self.lib.lp_engine_profile_ops(self.h, ctypes.c_void_p(x.data_ptr()), _DT[x.dtype],
-                                                     ctypes.c_void_p(pred.data_ptr()), self._stream(), ms, reps, inner),
-                      'lp_engine_profile_ops')
+            abi.check(self.lib.lp_engine_profile_ops(self.h, _dptr(x), _DT[x.dtype], _dptr(pred), _stream_ptr(self.device), ms, reps,
+                                                     inner), 'lp_engine_profile_ops')
         ops = []
         for i in range(n):
-            kind, ks, cin, cout = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-            fl, by = ctypes.c_double(), ctypes.c_double()
-            abi.check(self.lib.lp_engine_op_info(self.h, i, ctypes.byref(kind), ctypes.byref(ks), ctypes.byref(cin),
-                                                 ctypes.byref(cout), ctypes.byref(fl), ctypes.byref(by)), 'lp_engine_op_info')
             cfg, nb = ctypes.c_int(), ctypes.c_int()
             self.lib.lp_engine_op_variant(self.h, i, ctypes.byref(cfg), ctypes.byref(nb))
-            ops.append(dict(kind=('input', 'conv', 'deconv', 'pool', 'head_cls', 'head_box', 'stem')[kind.value], ksize=ks.value,
-                            cin=cin.value, cout=cout.value, flops=fl.value, bytes=by.value, ms=float(ms[i]),
-                            variant='%s%d' % ({16: 'S', 17: 'W', 18: 'R', 32: 'Pd', 33: 'Pb', 34: 'Pf', 35: 'Pc', 36: 'Pp', 37: 'Fz', 38: 'Fp', 45: 'Fb', 39: 'Md', 41: 'Mf', 42: 'V0', 43: 'V1', 48: 'Xa', 49: 'Xb'}.get(cfg.value) or 'ABCDEFGH'[cfg.value], nb.value)))
+            ops.append(dict(self._op_info(i), ms=float(ms[i]),
+                            variant='%s%d' % (abi.VARIANT_SHORT.get(cfg.value) or 'ABCDEFGH'[cfg.value], nb.value)))
         # Ops that launch nothing because a fused kernel carries them (the input op and the stem inside stem2_fused_kernel or behind
         # stem_planar_kernel, the 1x1 layer inside pw_s2_fused_kernel) are folded into their carrier's row: their FLOPs and bytes
         # are work of that kernel, and their own row keeps only the note (an empty event pair -- 1.4 us -- is not a 4 000 TFLOP/s launch).
@@ -667,23 +659,33 @@ def engine_for(model, dtype=None):
     return cached[1]
 
 
-def prepare_for(model, shape, x_dtype=None):
-    """Untimed set-up (the one-off kernel-variant tuner) of ``model``'s engine for input shape [B,3,H,W]."""
+def _engine(model):
+    """``engine_for(model)`` in the model's graph mode: model.lp_graph = True (set by Inferer) switches the engine to
+    hipGraph replay."""
     eng = engine_for(model)
     if bool(getattr(model, 'lp_graph', False)) != eng.graph:
         eng.set_graph(getattr(model, 'lp_graph', False))
-    eng.prepare(int(shape[0]), int(shape[2]), int(shape[3]), x_dtype)
+    return eng
+
+
+def prepare_for(model, shape, x_dtype=None):
+    """Untimed set-up (the one-off kernel-variant tuner) of ``model``'s engine for input shape [B,3,H,W]."""
+    _engine(model).prepare(int(shape[0]), int(shape[2]), int(shape[3]), x_dtype)
 
 
 def model_forward(model, x):
-    # model.lp_graph = True (set by Inferer) switches the engine to hipGraph replay
     """``Model.forward`` on a GPU: [pred[B,N,290] fp32, [f_s8, f_s16, f_s32]].  The feature maps are
     zero-copy channels_last views of the engine's arena (valid until the next forward of this model)."""
-    eng = engine_for(model)
-    if bool(getattr(model, 'lp_graph', False)) != eng.graph:
-        eng.set_graph(getattr(model, 'lp_graph', False))
+    eng = _engine(model)
     pred = eng.forward(x)
     return [pred, [eng.tensor_view(t) for t in eng.neck_ids]]
+
+
+def _det_buffers(B, max_det, device, index=True):
+    """Outputs of an NMS / merge launch: (det [B,max_det,28] fp32, count [B] int32, index [B,max_det] int32 or None)."""
+    return (torch.empty(B, max_det, abi.LP_DET_COLS, dtype=torch.float32, device=device),
+            torch.empty(B, dtype=torch.int32, device=device),
+            torch.empty(B, max_det, dtype=torch.int32, device=device) if index else None)
 
 
 def nms_candidates(handle, iou_thres, max_det, want_keep=False):
@@ -696,33 +698,43 @@ def nms_candidates(handle, iou_thres, max_det, want_keep=False):
     dev = ws.device
     with torch.cuda.device(dev):
         need = lib.lp_nms_workspace_bytes(B, N)
-        det = torch.empty(B, max_det, abi.LP_DET_COLS, dtype=torch.float32, device=dev)
-        count = torch.empty(B, dtype=torch.int32, device=dev)
-        keep = torch.empty(B, max_det, dtype=torch.int32, device=dev) if want_keep else None
-        abi.check(lib.lp_nms_candidates(B, N, float(iou_thres), int(max_det), ctypes.c_void_p(det.data_ptr()),
-                                        ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(keep.data_ptr()) if want_keep else None,
-                                        ctypes.c_void_p((ws.data_ptr() + 255) // 256 * 256), need,
-                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'lp_nms_candidates')
+        det, count, keep = _det_buffers(B, max_det, dev, want_keep)
+        abi.check(lib.lp_nms_candidates(B, N, float(iou_thres), int(max_det), _dptr(det), _dptr(count), _dptr(keep), _aligned(ws),
+                                        need, _stream_ptr(dev)), 'lp_nms_candidates')
     return det, count, keep
 
 
 def detect_padded(model, x, conf_thres, iou_thres, max_det, want_keep=False, route=None):
     """``Model.forward`` + ``non_max_suppression`` of a GPU model as one call: (det[B,max_det,28], count[B], keep or None);
     see ``Engine.detect`` for the two forms it chooses between.  For callers that only want detections (Inferer, serving)."""
-    eng = engine_for(model)
-    if bool(getattr(model, 'lp_graph', False)) != eng.graph:
-        eng.set_graph(getattr(model, 'lp_graph', False))
-    return eng.detect(x, conf_thres, iou_thres, max_det, want_keep, route)
+    return _engine(model).detect(x, conf_thres, iou_thres, max_det, want_keep, route)
+
+
+def _unpad(det, counts, n=None):
+    """The reference-shaped list of a padded result: det[b, :counts[b]] of the first ``n`` images (default: all), ``counts``
+    being the host copy of the count tensor -- reading it is the caller's one host sync."""
+    return [det[b, :counts[b]] for b in range(len(counts) if n is None else n)]
 
 
 def detect(model, x, conf_thres, iou_thres, max_det, route=None):
     """Reference-shaped result of ``non_max_suppression(model(x)[0], ...)``: list (len B) of [n_i, 28] tensors."""
     det, count, _ = detect_padded(model, x, conf_thres, iou_thres, max_det, route=route)
-    return [det[b, :n] for b, n in enumerate(count.cpu().tolist())]
+    return _unpad(det, count.cpu().tolist())
 
 
 # ---------------------------------------------------------------------------------------------------
 _nms_ws = {}
+
+
+def _nms_workspace(device, need):
+    """The NMS workspace of ``device``'s current stream, grown to ``need`` bytes (+ 256 for ``_aligned``)."""
+    # one workspace per (device, stream): lp_nms memsets and fills it on the current stream, so two streams must never
+    # share one; a regrown buffer is released through the caching allocator, which orders its reuse on this stream
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _nms_ws.get(key)
+    if ws is None or ws.numel() < need + 256:
+        ws = _nms_ws[key] = torch.empty(need + 256, dtype=torch.uint8, device=device)
+    return ws
 
 
 def nms_padded(prediction, conf_thres, iou_thres, max_det, want_keep=False):
@@ -736,20 +748,10 @@ def nms_padded(prediction, conf_thres, iou_thres, max_det, want_keep=False):
     dev = prediction.device
     with torch.cuda.device(dev):
         need = lib.lp_nms_workspace_bytes(B, N)
-        # one workspace per (device, stream): lp_nms memsets and fills it on the current stream, so two streams must never
-        # share one; a regrown buffer is released through the caching allocator, which orders its reuse on this stream
-        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-        ws = _nms_ws.get(key)
-        if ws is None or ws.numel() < need + 256:
-            ws = _nms_ws[key] = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-        det = torch.empty(B, max_det, abi.LP_DET_COLS, dtype=torch.float32, device=dev)
-        count = torch.empty(B, dtype=torch.int32, device=dev)
-        keep = torch.empty(B, max_det, dtype=torch.int32, device=dev) if want_keep else None
-        abi.check(lib.lp_nms(ctypes.c_void_p(prediction.data_ptr()), B, N, float(conf_thres), float(iou_thres),
-                             int(max_det), ctypes.c_void_p(det.data_ptr()), ctypes.c_void_p(count.data_ptr()),
-                             ctypes.c_void_p(keep.data_ptr()) if want_keep else None,
-                             ctypes.c_void_p((ws.data_ptr() + 255) // 256 * 256), need,
-                             ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'lp_nms')
+        ws = _nms_workspace(dev, need)
+        det, count, keep = _det_buffers(B, max_det, dev, want_keep)
+        abi.check(lib.lp_nms(_dptr(prediction), B, N, float(conf_thres), float(iou_thres), int(max_det), _dptr(det), _dptr(count),
+                             _dptr(keep), _aligned(ws), need, _stream_ptr(dev)), 'lp_nms')
     return det, count, keep
 
 
@@ -765,31 +767,10 @@ def non_max_suppression(prediction, conf_thres, iou_thres, max_det):
     det, count, _ = nms_padded(work, conf_thres, iou_thres, max_det)
     if work is not src:
         src.copy_(work)          # keep the reference's in-place obj*cls side effect on the caller's tensor
-    counts = count.cpu().tolist()
-    return [det[b, :n] for b, n in enumerate(counts)]
+    return _unpad(det, count.cpu().tolist())
 
 
 # ---------------------------------------------------------------------------------------------------
-def preprocess_letterbox(frame_bgr_u8, img_size, stride, dtype, auto=True):
-    """GPU form of Inferer.precess_image: device uint8 [h,w,3] BGR frame -> [3,H,W] RGB /255 tensor of ``dtype``.
-    Geometry (ratio, resized size, padding) is the reference's letterbox arithmetic, done on the host; ``auto=False``
-    pads to exactly ``img_size`` instead of the next stride multiple."""
-    from yolov6.data.data_augment import letterbox_geometry
-    if not (frame_bgr_u8.is_cuda and frame_bgr_u8.dtype == torch.uint8 and frame_bgr_u8.dim() == 3 and
-            frame_bgr_u8.shape[2] == 3 and frame_bgr_u8.is_contiguous()):
-        raise ValueError('frame must be a contiguous uint8 CUDA tensor [h, w, 3]')
-    h0, w0 = frame_bgr_u8.shape[:2]
-    _, (rw, rh), (top, bottom, left, right), _ = letterbox_geometry((h0, w0), img_size, auto=auto, stride=stride)
-    H, W = rh + top + bottom, rw + left + right
-    out = torch.empty(3, H, W, dtype=dtype, device=frame_bgr_u8.device)
-    with torch.cuda.device(out.device):
-        abi.check(abi.load().lp_preprocess_letterbox(ctypes.c_void_p(frame_bgr_u8.data_ptr()), h0, w0,
-                                                     ctypes.c_void_p(out.data_ptr()), _DT[dtype], H, W, rh, rw, top, left,
-                                                     ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)),
-                  'lp_preprocess_letterbox')
-    return out
-
-
 def _frames_device(frames):
     """The one device of a non-empty list of contiguous uint8 CUDA [h,w,3] frames (ValueError otherwise)."""
     dev = frames[0].device
@@ -799,6 +780,55 @@ def _frames_device(frames):
     return dev
 
 
+def _buffer(buf, shape, dtype, device, what='out'):
+    """A caller's persistent output buffer, checked; a new tensor of that ``shape`` / ``dtype`` on ``device`` when it is None."""
+    if buf is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not (buf.shape == shape and buf.dtype == dtype and buf.device == device and buf.is_contiguous()):
+        raise ValueError('%s must be a contiguous %s tensor %s on %s' % (what, dtype, list(shape), device))
+    return buf
+
+
+def _batch_on(frames, n, dtype, batch, what):
+    """Argument checks of a batched preprocess of ``n`` images cut from ``frames``: (device, B), where ``batch`` (>= n, >= 1)
+    sets B and the slots past n are padding."""
+    if dtype not in _DT:
+        raise TypeError('unsupported input dtype %s' % dtype)
+    if not frames:
+        raise ValueError('%s needs at least one frame' % what)
+    dev = _frames_device(frames)
+    B = n if batch is None else int(batch)
+    if B < n or B < 1:
+        raise ValueError('batch %d < %d images (or < 1)' % (B, n))
+    return dev, B
+
+
+def _check_det_count(det, count, what='det', min_batch=0):
+    """det [B >= min_batch, max_det, 28] fp32 and count [B] int32 as ``nms_padded`` returns them: contiguous, on one GPU."""
+    if not (det.is_cuda and det.dtype == torch.float32 and det.dim() == 3 and det.shape[2] == abi.LP_DET_COLS
+            and det.is_contiguous() and det.shape[0] >= min_batch):
+        raise ValueError('%s must be a contiguous CUDA fp32 [B >= %d, max_det, 28] tensor' % (what, min_batch))
+    if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.numel() == det.shape[0]
+            and count.device == det.device):
+        raise ValueError('the count of %s must be a contiguous CUDA int32 [B] tensor on its device' % what)
+
+
+def preprocess_letterbox(frame_bgr_u8, img_size, stride, dtype, auto=True):
+    """GPU form of Inferer.precess_image: device uint8 [h,w,3] BGR frame -> [3,H,W] RGB /255 tensor of ``dtype``.
+    Geometry (ratio, resized size, padding) is the reference's letterbox arithmetic, done on the host; ``auto=False``
+    pads to exactly ``img_size`` instead of the next stride multiple."""
+    if not (frame_bgr_u8.is_cuda and frame_bgr_u8.dtype == torch.uint8 and frame_bgr_u8.dim() == 3 and
+            frame_bgr_u8.shape[2] == 3 and frame_bgr_u8.is_contiguous()):
+        raise ValueError('frame must be a contiguous uint8 CUDA tensor [h, w, 3]')
+    h0, w0 = frame_bgr_u8.shape[:2]
+    rh, rw, top, left, H, W = letterbox_placement((h0, w0), img_size, stride, auto)
+    out = torch.empty(3, H, W, dtype=dtype, device=frame_bgr_u8.device)
+    with torch.cuda.device(out.device):
+        abi.check(abi.load().lp_preprocess_letterbox(_dptr(frame_bgr_u8), h0, w0, _dptr(out), _DT[dtype], H, W, rh, rw, top, left,
+                                                     _stream_ptr(out.device)), 'lp_preprocess_letterbox')
+    return out
+
+
 def preprocess_frames(frames, img_size, stride, dtype, auto=True, batch=None, out=None):
     """Batched ``preprocess_letterbox`` (lp_preprocess_letterbox_batch, one launch per 64 frames): a list of contiguous
     uint8 CUDA [h,w,3] BGR frames of any sizes -> (x[B,3,H,W] of ``dtype``, geoms).  ``geoms[i]`` is frame i's
@@ -806,36 +836,27 @@ def preprocess_frames(frames, img_size, stride, dtype, auto=True, batch=None, ou
     (H, W); ``auto=False`` letterboxes each to exactly ``img_size``.  ``batch`` (>= len(frames)) sets B: slots past the
     frames are padding (114/255).  ``out``: a persistent [B,3,H,W] input buffer to write (graphs are keyed on the
     input pointer)."""
-    from yolov6.data.data_augment import letterbox_geometry
-    if dtype not in _DT:
-        raise TypeError('unsupported input dtype %s' % dtype)
-    if not frames:
-        raise ValueError('preprocess_frames needs at least one frame')
-    dev = _frames_device(frames)
-    B = len(frames) if batch is None else int(batch)
-    if B < len(frames):
-        raise ValueError('batch %d < %d frames' % (B, len(frames)))
-    geoms, hws = [], []
-    for f in frames:
-        _, (rw, rh), (top, bottom, left, right), _ = letterbox_geometry(tuple(f.shape[:2]), img_size, auto=auto, stride=stride)
-        geoms.append((rh, rw, top, left))
-        hws.append((rh + top + bottom, rw + left + right))
-    if len(set(hws)) != 1:
+    dev, B = _batch_on(frames, len(frames), dtype, batch, 'preprocess_frames')
+    places = [letterbox_placement(f.shape, img_size, stride, auto) for f in frames]
+    geoms, hws = [p[:4] for p in places], set(p[4:] for p in places)
+    if len(hws) != 1:
         raise ValueError('frames letterbox to different shapes %s (source shapes %s): batch them separately or use auto=False'
-                         % (sorted(set(hws)), [tuple(f.shape[:2]) for f in frames]))
-    H, W = hws[0]
-    if out is None:
-        out = torch.empty(B, 3, H, W, dtype=dtype, device=dev)
-    elif not (out.shape == (B, 3, H, W) and out.dtype == dtype and out.device == dev and out.is_contiguous()):
-        raise ValueError('out must be a contiguous %s tensor [%d,3,%d,%d] on %s' % (dtype, B, H, W, dev))
+                         % (sorted(hws), [tuple(f.shape[:2]) for f in frames]))
+    H, W = hws.pop()
+    out = _buffer(out, (B, 3, H, W), dtype, dev)
     desc = (abi.FrameDesc * len(frames))()
     for d, f, (rh, rw, top, left) in zip(desc, frames, geoms):
         d.img, d.h0, d.w0, d.rh, d.rw, d.top, d.left = f.data_ptr(), f.shape[0], f.shape[1], rh, rw, top, left
     with torch.cuda.device(dev):
-        abi.check(abi.load().lp_preprocess_letterbox_batch(desc, len(frames), B, ctypes.c_void_p(out.data_ptr()), _DT[dtype], H, W,
-                                                           ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+        abi.check(abi.load().lp_preprocess_letterbox_batch(desc, len(frames), B, _dptr(out), _DT[dtype], H, W, _stream_ptr(dev)),
                   'lp_preprocess_letterbox_batch')
     return out, geoms
+
+
+def _rescale_terms(ori_shape, target_shape):
+    """Inferer.rescale's (ratio, padx, pady) from the network input (h, w) back to a source image of (h, w[, c])."""
+    ratio = min(ori_shape[0] / target_shape[0], ori_shape[1] / target_shape[1])
+    return ratio, (ori_shape[1] - target_shape[1] * ratio) / 2, (ori_shape[0] - target_shape[0] * ratio) / 2
 
 
 def rescale_round(ori_shape, det, target_shape):
@@ -843,12 +864,10 @@ def rescale_round(ori_shape, det, target_shape):
     if not (det.is_cuda and det.dtype == torch.float32 and det.dim() == 2 and det.shape[1] == abi.LP_DET_COLS and
             det.stride(1) == 1 and det.stride(0) == abi.LP_DET_COLS):
         raise ValueError('det must be a CUDA fp32 [n, 28] tensor with contiguous rows')
-    ratio = min(ori_shape[0] / target_shape[0], ori_shape[1] / target_shape[1])
-    padx, pady = (ori_shape[1] - target_shape[1] * ratio) / 2, (ori_shape[0] - target_shape[0] * ratio) / 2
+    ratio, padx, pady = _rescale_terms(ori_shape, target_shape)
     with torch.cuda.device(det.device):
-        abi.check(abi.load().lp_rescale_round(ctypes.c_void_p(det.data_ptr()), det.shape[0], float(ratio), float(padx),
-                                              float(pady), int(target_shape[1]), int(target_shape[0]),
-                                              ctypes.c_void_p(torch.cuda.current_stream(det.device).cuda_stream)),
+        abi.check(abi.load().lp_rescale_round(_dptr(det), det.shape[0], float(ratio), float(padx), float(pady),
+                                              int(target_shape[1]), int(target_shape[0]), _stream_ptr(det.device)),
                   'lp_rescale_round')
     return det
 
@@ -857,25 +876,28 @@ def rescale_round_batch(det, count, net_hw, src_shapes):
     """Batched ``rescale_round`` (lp_rescale_round_batch), in place on det [B,max_det,28]: rows r < count[b] of image
     b < len(src_shapes) are mapped back to source image b of shape (h, w[, c]) from the network input size ``net_hw``
     (Inferer.rescale's ratio and padding) and rounded.  ``count`` (int32 [B], CUDA) is read on the device: no host sync."""
-    if not (det.is_cuda and det.dtype == torch.float32 and det.dim() == 3 and det.shape[2] == abi.LP_DET_COLS and det.is_contiguous()):
-        raise ValueError('det must be a contiguous CUDA fp32 [B, max_det, 28] tensor')
-    if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.numel() == det.shape[0]
-            and count.device == det.device):
-        raise ValueError('count must be a contiguous CUDA int32 [B] tensor on det\'s device')
+    _check_det_count(det, count)
     n = len(src_shapes)
     if n > det.shape[0]:
         raise ValueError('%d source shapes for a batch of %d' % (n, det.shape[0]))
     desc = (abi.RescaleDesc * max(n, 1))()
     for d, s in zip(desc, src_shapes):
-        ratio = min(net_hw[0] / s[0], net_hw[1] / s[1])
-        d.ratio, d.padx, d.pady = ratio, (net_hw[1] - s[1] * ratio) / 2, (net_hw[0] - s[0] * ratio) / 2
+        d.ratio, d.padx, d.pady = _rescale_terms(net_hw, s)
         d.img_w, d.img_h = int(s[1]), int(s[0])
     with torch.cuda.device(det.device):
-        abi.check(abi.load().lp_rescale_round_batch(ctypes.c_void_p(det.data_ptr()), ctypes.c_void_p(count.data_ptr()), n,
-                                                    det.shape[1], desc,
-                                                    ctypes.c_void_p(torch.cuda.current_stream(det.device).cuda_stream)),
+        abi.check(abi.load().lp_rescale_round_batch(_dptr(det), _dptr(count), n, det.shape[1], desc, _stream_ptr(det.device)),
                   'lp_rescale_round_batch')
     return det
+
+
+def detect_frames_padded(model, frames, img_size, conf_thres, iou_thres, max_det, auto=True, batch=None, out=None):
+    """The device work of ``detect_frames`` without its host read: (det [B,max_det,28], count [B] int32) on the device, rows
+    r < count[b] of frame b < len(frames) in source-image pixels, rounded."""
+    dtype = next(model.parameters()).dtype
+    x, _ = preprocess_frames(frames, img_size, int(model.stride.max()), dtype, auto=auto, batch=batch, out=out)   # DetectBackend's stride
+    det, count, _ = detect_padded(model, x, conf_thres, iou_thres, max_det)
+    rescale_round_batch(det, count, x.shape[2:], [tuple(f.shape[:2]) for f in frames])
+    return det, count
 
 
 def detect_frames(model, frames, img_size, conf_thres, iou_thres, max_det, auto=True, batch=None, out=None):
@@ -884,18 +906,8 @@ def detect_frames(model, frames, img_size, conf_thres, iou_thres, max_det, auto=
     the counts.  Returns a list of [n_i, 28] tensors in source-image pixels, rounded: per frame what Inferer.infer returns,
     bit for bit.  The input dtype is the model's parameter dtype (Inferer's fp16 / fp32 input); ``batch`` / ``out`` as in
     ``preprocess_frames`` (padding slots let a short tail reuse a bound batch size)."""
-    det, _, counts = _detect_frames_padded(model, frames, img_size, conf_thres, iou_thres, max_det, auto, batch, out)
-    return [det[b, :counts[b]] for b in range(len(frames))]
-
-
-def _detect_frames_padded(model, frames, img_size, conf_thres, iou_thres, max_det, auto, batch, out):
-    """The device work of ``detect_frames`` and its one host read: (det [B,max_det,28], count [B] on the device, counts as a
-    host list)."""
-    dtype = next(model.parameters()).dtype
-    x, _ = preprocess_frames(frames, img_size, int(model.stride.max()), dtype, auto=auto, batch=batch, out=out)   # DetectBackend's stride
-    det, count, _ = detect_padded(model, x, conf_thres, iou_thres, max_det)
-    rescale_round_batch(det, count, x.shape[2:], [tuple(f.shape[:2]) for f in frames])
-    return det, count, count.cpu().tolist()
+    det, count = detect_frames_padded(model, frames, img_size, conf_thres, iou_thres, max_det, auto, batch, out)
+    return _unpad(det, count.cpu().tolist(), len(frames))
 
 
 def _crop_size(crop_hw):
@@ -907,21 +919,15 @@ def _crop_size(crop_hw):
 
 def _plate_crops_launch(frames, det, count, slots, out, status, crop_hw):
     """lp_plate_crops_batch on frames with ``slots[b]`` = (max_crops, out_slot): out [n_slots,Hc,Wc,3], status [n_slots]."""
-    if not (det.is_cuda and det.dtype == torch.float32 and det.dim() == 3 and det.shape[2] == abi.LP_DET_COLS and
-            det.is_contiguous() and det.shape[0] >= len(frames) and det.device == out.device):
-        raise ValueError('det must be a contiguous CUDA fp32 [B >= %d frames, max_det, 28] tensor on the frames\' device'
-                         % len(frames))
-    if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.numel() == det.shape[0]
-            and count.device == det.device):
-        raise ValueError('count must be a contiguous CUDA int32 [B] tensor on det\'s device')
+    _check_det_count(det, count, min_batch=len(frames))
+    if det.device != out.device:
+        raise ValueError('det must be on the frames\' device')
     desc = (abi.CropDesc * len(frames))()
     for d, f, (m, o) in zip(desc, frames, slots):
         d.img, d.h0, d.w0, d.max_crops, d.out_slot = f.data_ptr(), f.shape[0], f.shape[1], m, o
     with torch.cuda.device(det.device):
-        abi.check(abi.load().lp_plate_crops_batch(desc, len(frames), ctypes.c_void_p(det.data_ptr()),
-                                                  ctypes.c_void_p(count.data_ptr()), det.shape[1], ctypes.c_void_p(out.data_ptr()),
-                                                  ctypes.c_void_p(status.data_ptr()), status.numel(), crop_hw[0], crop_hw[1],
-                                                  ctypes.c_void_p(torch.cuda.current_stream(det.device).cuda_stream)),
+        abi.check(abi.load().lp_plate_crops_batch(desc, len(frames), _dptr(det), _dptr(count), det.shape[1], _dptr(out),
+                                                  _dptr(status), status.numel(), crop_hw[0], crop_hw[1], _stream_ptr(det.device)),
                   'lp_plate_crops_batch')
 
 
@@ -941,16 +947,23 @@ def plate_crops(frames, det, count, crop_hw=(64, 192), max_crops=None, out=None,
     n, m = len(frames), 16 if max_crops is None else int(max_crops)
     if m < 0:
         raise ValueError('max_crops must be >= 0')
-    if out is None:
-        out = torch.empty(n, m, Hc, Wc, 3, dtype=torch.uint8, device=dev)
-    elif not (out.shape == (n, m, Hc, Wc, 3) and out.dtype == torch.uint8 and out.device == dev and out.is_contiguous()):
-        raise ValueError('out must be a contiguous uint8 tensor [%d,%d,%d,%d,3] on %s' % (n, m, Hc, Wc, dev))
-    if status is None:
-        status = torch.empty(n, m, dtype=torch.int32, device=dev)
-    elif not (status.shape == (n, m) and status.dtype == torch.int32 and status.device == dev and status.is_contiguous()):
-        raise ValueError('status must be a contiguous int32 tensor [%d,%d] on %s' % (n, m, dev))
+    out = _buffer(out, (n, m, Hc, Wc, 3), torch.uint8, dev)
+    status = _buffer(status, (n, m), torch.int32, dev, 'status')
     _plate_crops_launch(frames, det, count, [(m, b * m) for b in range(n)], out, status, (Hc, Wc))
     return out, status
+
+
+def _unpad_with_crops(frames, det, count, crop_hw):
+    """(dets, crops, status) of the ``*_with_crops`` entry points from a padded result in frame pixels: the one host read of
+    the counts, then the crops packed, frame b's n_b right behind frame b-1's (``crop_hw``: checked by ``_crop_size``)."""
+    counts = count.cpu().tolist()
+    ns = [max(0, min(int(c), det.shape[1])) for c in counts[:len(frames)]]
+    offs = np.concatenate([[0], np.cumsum(ns)]).astype(int).tolist()
+    crops = torch.empty(offs[-1], *crop_hw, 3, dtype=torch.uint8, device=det.device)
+    status = torch.empty(offs[-1], dtype=torch.int32, device=det.device)
+    _plate_crops_launch(frames, det, count, list(zip(ns, offs)), crops, status, crop_hw)
+    return (_unpad(det, counts, len(frames)), [crops[o:o + k] for o, k in zip(offs, ns)],
+            [status[o:o + k] for o, k in zip(offs, ns)])
 
 
 def detect_frames_with_crops(model, frames, img_size, conf_thres, iou_thres, max_det, crop_hw=(64, 192), auto=True, batch=None,
@@ -960,25 +973,13 @@ def detect_frames_with_crops(model, frames, img_size, conf_thres, iou_thres, max
     frame b-1's in one [sum n_b,Hc,Wc,3] uint8 tensor: ``crops[b]`` is an [n_b,Hc,Wc,3] view of it and ``status[b]`` an
     [n_b] int32 view (codes as in ``plate_crops``).  The crops are enqueued here, before the next ``FrameBatcher.put`` may
     reuse the frames' buffer."""
-    Hc, Wc = _crop_size(crop_hw)
-    det, count, counts = _detect_frames_padded(model, frames, img_size, conf_thres, iou_thres, max_det, auto, batch, out)
-    ns = [max(0, min(int(c), det.shape[1])) for c in counts[:len(frames)]]
-    offs = np.concatenate([[0], np.cumsum(ns)]).astype(int).tolist()
-    crops = torch.empty(offs[-1], Hc, Wc, 3, dtype=torch.uint8, device=det.device)
-    status = torch.empty(offs[-1], dtype=torch.int32, device=det.device)
-    _plate_crops_launch(frames, det, count, list(zip(ns, offs)), crops, status, (Hc, Wc))
-    return ([det[b, :counts[b]] for b in range(len(frames))], [crops[o:o + k] for o, k in zip(offs, ns)],
-            [status[o:o + k] for o, k in zip(offs, ns)])
+    crop_hw = _crop_size(crop_hw)
+    det, count = detect_frames_padded(model, frames, img_size, conf_thres, iou_thres, max_det, auto, batch, out)
+    return _unpad_with_crops(frames, det, count, crop_hw)
 
 
 # ---------------------------------------------------------------------------------------------------
 # Tiled detection of large frames (yolov6/core/tiles.py plans the tiles; lp_preprocess_tiles_batch / lp_merge_tiles)
-def _net_hw(img_size):
-    if isinstance(img_size, (list, tuple)):
-        return (int(img_size[0]), int(img_size[0])) if len(img_size) == 1 else (int(img_size[0]), int(img_size[1]))
-    return int(img_size), int(img_size)
-
-
 def preprocess_tiles(frames, plans, img_size, stride, dtype, batch=None, out=None):
     """Letterboxed regions of device frames (lp_preprocess_tiles_batch, one launch per 64 tiles): ``plans`` is a list of
     (frame index, y0, x0, th, tw); tile k is read in place from ``frames[frame]`` (contiguous uint8 CUDA [h,w,3] BGR) and
@@ -986,33 +987,21 @@ def preprocess_tiles(frames, plans, img_size, stride, dtype, batch=None, out=Non
     x [B,3,H,W] of ``dtype``: bit for bit what ``preprocess_frames(auto=False)`` gives for a contiguous copy of the region.
     Returns (x, geoms) with ``geoms[k]`` = (rh, rw, top, left).  ``batch`` (>= len(plans)) sets B, the slots past the tiles
     are padding (114/255); ``out``: a persistent [B,3,H,W] buffer to write."""
-    from yolov6.data.data_augment import letterbox_geometry
-    if dtype not in _DT:
-        raise TypeError('unsupported input dtype %s' % dtype)
-    if not frames:
-        raise ValueError('preprocess_tiles needs at least one frame')
-    dev = _frames_device(frames)
-    B = len(plans) if batch is None else int(batch)
-    if B < len(plans) or B < 1:
-        raise ValueError('batch %d < %d tiles (or < 1)' % (B, len(plans)))
-    H, W = _net_hw(img_size)
-    if out is None:
-        out = torch.empty(B, 3, H, W, dtype=dtype, device=dev)
-    elif not (out.shape == (B, 3, H, W) and out.dtype == dtype and out.device == dev and out.is_contiguous()):
-        raise ValueError('out must be a contiguous %s tensor [%d,3,%d,%d] on %s' % (dtype, B, H, W, dev))
+    dev, B = _batch_on(frames, len(plans), dtype, batch, 'preprocess_tiles')
+    H, W = hw_pair(img_size)
+    out = _buffer(out, (B, 3, H, W), dtype, dev)
     desc = (abi.TileDesc * max(len(plans), 1))()
     geoms = []
     for d, (f, y0, x0, th, tw) in zip(desc, plans):
         if not 0 <= f < len(frames):
             raise ValueError('tile of frame %d: %d frames' % (f, len(frames)))
-        _, (rw, rh), (top, _, left, _), _ = letterbox_geometry((th, tw), [H, W], auto=False, stride=stride)
-        geoms.append((rh, rw, top, left))
+        rh, rw, top, left = geom = letterbox_placement((th, tw), [H, W], stride, auto=False)[:4]
+        geoms.append(geom)
         fr = frames[f]
         d.img, d.h0, d.w0 = fr.data_ptr(), fr.shape[0], fr.shape[1]
         d.y0, d.x0, d.th, d.tw, d.rh, d.rw, d.top, d.left = y0, x0, th, tw, rh, rw, top, left
     with torch.cuda.device(dev):
-        abi.check(abi.load().lp_preprocess_tiles_batch(desc, len(plans), B, ctypes.c_void_p(out.data_ptr()), _DT[dtype], H, W,
-                                                       ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+        abi.check(abi.load().lp_preprocess_tiles_batch(desc, len(plans), B, _dptr(out), _DT[dtype], H, W, _stream_ptr(dev)),
                   'lp_preprocess_tiles_batch')
     return out, geoms
 
@@ -1027,12 +1016,7 @@ def merge_tiles(det_t, count_t, tiles, frame_shapes, thres, max_det, metric='iou
     (h, w[, c]).  Returns (det [F,max_det,28], count [F] int32, src [F,max_det] int32) in frame pixels -- the layout
     ``plate_crops`` takes.  Highest-scoring view wins; rows of one tile never suppress each other.
     ``yolov6.utils.tiles.merge_tiles_np`` is the same computation on the CPU, bit for bit, and states the rules."""
-    if not (det_t.is_cuda and det_t.dtype == torch.float32 and det_t.dim() == 3 and det_t.shape[2] == abi.LP_DET_COLS
-            and det_t.is_contiguous() and det_t.shape[0] >= len(tiles)):
-        raise ValueError('det_t must be a contiguous CUDA fp32 [T >= %d tiles, max_det_t, 28] tensor' % len(tiles))
-    if not (count_t.is_cuda and count_t.dtype == torch.int32 and count_t.is_contiguous() and count_t.numel() == det_t.shape[0]
-            and count_t.device == det_t.device):
-        raise ValueError('count_t must be a contiguous CUDA int32 [T] tensor on det_t\'s device')
+    _check_det_count(det_t, count_t, 'det_t', min_batch=len(tiles))
     if metric not in _METRICS:
         raise ValueError('metric must be one of %s' % sorted(_METRICS))
     dev, F, max_det = det_t.device, len(frame_shapes), int(max_det)
@@ -1044,16 +1028,12 @@ def merge_tiles(det_t, count_t, tiles, frame_shapes, thres, max_det, metric='iou
     hw = (ctypes.c_int * max(2 * F, 1))(*[int(v) for s in frame_shapes for v in s[:2]])
     lib = abi.load()
     with torch.cuda.device(dev):
-        det = torch.empty(F, max_det, abi.LP_DET_COLS, dtype=torch.float32, device=dev)
-        count = torch.empty(F, dtype=torch.int32, device=dev)
-        src = torch.empty(F, max_det, dtype=torch.int32, device=dev)
+        det, count, src = _det_buffers(F, max_det, dev)
         need = lib.lp_merge_tiles_workspace_bytes(F, max_det)
         ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
-        abi.check(lib.lp_merge_tiles(ctypes.c_void_p(det_t.data_ptr()), ctypes.c_void_p(count_t.data_ptr()), ref, len(tiles),
-                                     det_t.shape[1], hw, F, float(thres), _METRICS[metric], int(border), max_det,
-                                     ctypes.c_void_p(det.data_ptr()), ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(src.data_ptr()),
-                                     ctypes.c_void_p((ws.data_ptr() + 15) // 16 * 16), need,
-                                     ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'lp_merge_tiles')
+        abi.check(lib.lp_merge_tiles(_dptr(det_t), _dptr(count_t), ref, len(tiles), det_t.shape[1], hw, F, float(thres),
+                                     _METRICS[metric], int(border), max_det, _dptr(det), _dptr(count), _dptr(src),
+                                     (ws.data_ptr() + 15) // 16 * 16, need, _stream_ptr(dev)), 'lp_merge_tiles')
     return det, count, src
 
 
@@ -1063,8 +1043,7 @@ _tile_inputs = {}      # (device, stream, dtype, B, H, W) -> persistent network 
 def plan_tiled(frame_shapes, img_size, max_det, tile_hw=None, overlap=0.2, overview=True, tile_max_det=None):
     """(tiles, tile_max_det) of ``detect_tiled`` for frames of ``frame_shapes``: the flat tile table (frame, y0, x0, th, tw)
     and the detections kept per tile, min(max_det, 16384 // most tiles of any frame) by default."""
-    from yolov6.core.tiles import plan_frames, tiles_per_frame
-    tiles = plan_frames(frame_shapes, _net_hw(img_size) if tile_hw is None else tile_hw, overlap, overview)
+    tiles = plan_frames(frame_shapes, hw_pair(img_size) if tile_hw is None else tile_hw, overlap, overview)
     most = max(tiles_per_frame(tiles, len(frame_shapes)))
     if most > abi.LP_MERGE_MAX_TILES:
         raise ValueError('%d tiles for one frame (at most %d): use larger tiles or a smaller overlap' % (most, abi.LP_MERGE_MAX_TILES))
@@ -1081,7 +1060,7 @@ def detect_tiles_padded(model, frames, tiles, img_size, conf_thres, iou_thres, t
     device, T' = len(tiles) rounded up to a multiple of ``batch``; no host sync."""
     dev = _frames_device(frames)
     dtype = next(model.parameters()).dtype
-    H, W = _net_hw(img_size)
+    H, W = hw_pair(img_size)
     B = int(batch)
     if B < 1:
         raise ValueError('batch must be >= 1')
@@ -1102,17 +1081,17 @@ def detect_tiles_padded(model, frames, tiles, img_size, conf_thres, iou_thres, t
     return det_t, count_t
 
 
-def _detect_tiled_padded(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw, overlap, overview, metric, border, batch,
-                         tile_max_det):
-    """The device work of ``detect_tiled`` and its one host read: (det [F,max_det,28], count [F] on the device, counts as a
-    host list)."""
+def detect_tiled_padded(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw=None, overlap=0.2, overview=True,
+                        metric='iou', border=1, batch=32, tile_max_det=None):
+    """The device work of ``detect_tiled`` without its host read: (det [F,max_det,28], count [F] int32) on the device, in
+    frame pixels."""
     if not frames:
         raise ValueError('detect_tiled needs at least one frame')
     shapes = [tuple(f.shape[:2]) for f in frames]
     tiles, tmd = plan_tiled(shapes, img_size, max_det, tile_hw, overlap, overview, tile_max_det)
     det_t, count_t = detect_tiles_padded(model, frames, tiles, img_size, conf_thres, iou_thres, tmd, batch)
     det, count, _ = merge_tiles(det_t, count_t, tiles, shapes, iou_thres, max_det, metric, border)
-    return det, count, count.cpu().tolist()
+    return det, count
 
 
 def detect_tiled(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw=None, overlap=0.2, overview=True, metric='iou',
@@ -1125,25 +1104,19 @@ def detect_tiled(model, frames, img_size, conf_thres, iou_thres, max_det, tile_h
     per-frame counts.  Returns a list of [n_f, 28] tensors in frame pixels.  ``tile_max_det``: detections kept per tile
     (default min(max_det, 16384 // most tiles of any frame)).  With ``tile_hw`` >= the frame this is
     ``detect_frames(auto=False)``, bit for bit."""
-    det, _, counts = _detect_tiled_padded(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw, overlap, overview, metric,
-                                          border, batch, tile_max_det)
-    return [det[f, :counts[f]] for f in range(len(frames))]
+    det, count = detect_tiled_padded(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw, overlap, overview, metric,
+                                     border, batch, tile_max_det)
+    return _unpad(det, count.cpu().tolist())
 
 
 def detect_tiled_with_crops(model, frames, img_size, conf_thres, iou_thres, max_det, crop_hw=(64, 192), tile_hw=None, overlap=0.2,
                             overview=True, metric='iou', border=1, batch=32, tile_max_det=None):
     """``detect_tiled`` plus the plate crop of every merged detection, cut from the full-resolution frame: (dets, crops, status)
     packed as ``detect_frames_with_crops`` packs them (``plate_crops`` on the merged det / count, which have its layout)."""
-    Hc, Wc = _crop_size(crop_hw)
-    det, count, counts = _detect_tiled_padded(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw, overlap, overview,
-                                              metric, border, batch, tile_max_det)
-    ns = [max(0, min(int(c), det.shape[1])) for c in counts]
-    offs = np.concatenate([[0], np.cumsum(ns)]).astype(int).tolist()
-    crops = torch.empty(offs[-1], Hc, Wc, 3, dtype=torch.uint8, device=det.device)
-    status = torch.empty(offs[-1], dtype=torch.int32, device=det.device)
-    _plate_crops_launch(frames, det, count, list(zip(ns, offs)), crops, status, (Hc, Wc))
-    return ([det[f, :counts[f]] for f in range(len(frames))], [crops[o:o + k] for o, k in zip(offs, ns)],
-            [status[o:o + k] for o, k in zip(offs, ns)])
+    crop_hw = _crop_size(crop_hw)
+    det, count = detect_tiled_padded(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw, overlap, overview, metric,
+                                     border, batch, tile_max_det)
+    return _unpad_with_crops(frames, det, count, crop_hw)
 
 
 def eval_counts(det, det_count, tgt, tgt_count, counts=None):
@@ -1151,20 +1124,16 @@ def eval_counts(det, det_count, tgt, tgt_count, counts=None):
     int32 as ``nms_padded`` returns them, tgt [B,max_t,20] fp32 + tgt_count [B] int32; ``counts`` (int64 [43], CUDA) is
     accumulated into and returned (allocated zeroed when None)."""
     dev = det.device
-    ok = (det.is_cuda and det.dtype == torch.float32 and det.dim() == 3 and det.shape[2] == abi.LP_DET_COLS and det.is_contiguous()
-          and tgt.dtype == torch.float32 and tgt.dim() == 3 and tgt.shape[2] == 20 and tgt.is_contiguous() and tgt.device == dev
-          and det_count.dtype == torch.int32 and tgt_count.dtype == torch.int32 and det_count.is_contiguous() and tgt_count.is_contiguous()
-          and det_count.device == dev and tgt_count.device == dev
-          and det.shape[0] == tgt.shape[0] == det_count.numel() == tgt_count.numel())
-    if not ok:
-        raise ValueError('eval_counts: expected contiguous CUDA det [B,D,28] / tgt [B,T,20] fp32 and int32 counts [B] on one device')
+    _check_det_count(det, det_count)
+    if not (tgt.dtype == torch.float32 and tgt.dim() == 3 and tgt.shape[2] == 20 and tgt.is_contiguous() and tgt.device == dev
+            and tgt_count.dtype == torch.int32 and tgt_count.is_contiguous() and tgt_count.device == dev
+            and det.shape[0] == tgt.shape[0] == tgt_count.numel()):
+        raise ValueError('eval_counts: expected contiguous CUDA tgt [B,T,20] fp32 and int32 tgt_count [B] on det\'s device')
     if counts is None:
         counts = torch.zeros(abi.LP_EVAL_NCOUNTS, dtype=torch.int64, device=dev)
     elif not (counts.dtype == torch.int64 and counts.numel() == abi.LP_EVAL_NCOUNTS and counts.device == dev and counts.is_contiguous()):
         raise ValueError('eval_counts: counts must be a contiguous CUDA int64 [%d] tensor' % abi.LP_EVAL_NCOUNTS)
     with torch.cuda.device(dev):
-        abi.check(abi.load().lp_eval_counts(ctypes.c_void_p(det.data_ptr()), ctypes.c_void_p(det_count.data_ptr()), det.shape[1],
-                                            ctypes.c_void_p(tgt.data_ptr()), ctypes.c_void_p(tgt_count.data_ptr()), tgt.shape[1],
-                                            det.shape[0], ctypes.c_void_p(counts.data_ptr()),
-                                            ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'lp_eval_counts')
+        abi.check(abi.load().lp_eval_counts(_dptr(det), _dptr(det_count), det.shape[1], _dptr(tgt), _dptr(tgt_count), tgt.shape[1],
+                                            det.shape[0], _dptr(counts), _stream_ptr(dev)), 'lp_eval_counts')
     return counts
