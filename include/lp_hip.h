@@ -218,6 +218,14 @@ int lp_engine_op_carrier(const lp_engine* e, int op, int frame_direct);
 int lp_engine_autotune(lp_engine* e, const void* x, int x_dtype, float* pred, void* stream, int reps);
 int lp_engine_op_variant(const lp_engine* e, int op, int* cfg, int* nbuf);
 int lp_engine_set_op_variant(lp_engine* e, int op, int cfg, int nbuf);
+/* Test hook: the output-tile choice (0 = the planner's best, 1, 2, ... = the next candidates; the autotuner times 0..2) of whatever
+ * variant the op currently has -- the implicit-GEMM, pipelined and block-tiled kernels, and the planar stem, the fused stem and the
+ * fused 1x1 + 3x3 stride-2 form while one of those is switched on.  Invalidates what lp_engine_set_op_variant invalidates.  A choice
+ * past the last candidate repeats the last one (conv kernels) or is LP_ERR_UNSUPPORTED and changes nothing (stem / fused forms).
+ * lp_engine_op_tile reports the choice and the TH x TW output tile prepared for the bound shape.  LP_ERR_UNSUPPORTED: the op's
+ * kernel has no output tiles (input, pooling, head ops, the streaming 1x1 kernel, the fused BiFusion kernel). */
+int lp_engine_set_op_tile(lp_engine* e, int op, int choice);
+int lp_engine_op_tile(const lp_engine* e, int op, int* choice, int* TH, int* TW);
 /* Copy the tuned choices (all shapes) of an engine built from the same graph and dtype, e.g. to the other engines of a
  * several-batches-in-flight pipeline, instead of tuning each. */
 int lp_engine_copy_tuning(lp_engine* dst, const lp_engine* src);

@@ -86,3 +86,267 @@ def synth_metric_batch(seed, B, max_pred, max_tgt, hw=640.0):
         pb.append(pred.float())
         tb.append(tgt.float())
     return pb, tb
+
+
+# ---- exact-arithmetic helpers (tests/test_exact_cpu.py, tests/test_exact_gpu.py) ---------------------------------------
+# Grid data: every tensor holds multiples of a power of two.  Products x*w are multiples of step_x*step_w (the "grid unit"),
+# and as long as sum|x||w| + |b| stays below 2^24 units every product and every partial sum, in ANY order, is an integer
+# number of units below 2^24, i.e. exact in fp32.  The result of a convolution then does not depend on the summation order
+# and its bits are known: the float64 sum, converted to float32 (exact) and rounded ONCE to the storage type.
+SIG_BITS = {torch.float16: 11, torch.bfloat16: 8, torch.float32: 24}
+MIN_EXP = {torch.float16: -14, torch.bfloat16: -126, torch.float32: -126}
+INT_VIEW = {torch.float16: torch.int16, torch.bfloat16: torch.int16, torch.float32: torch.int32}
+RES_ALPHA = 0.75                 # residual weight of the exact tests: a multiple of 1/4, so alpha * res stays on the grid
+# value ranges of the grid data per storage type: (|x|, |w| bound, |bias| bound, |residual| bound).  x, w and the residual are
+# multiples of 1/4 that the 16-bit type holds exactly; the bias (fp32 in the engine) is a multiple of 1/16 and sets the scale of
+# the outputs so that they need rounding: outputs are multiples of 1/16, fp16 cannot hold those from |v| >= 128, bf16 from 16.
+GRID_RANGE = {torch.float16: (4.0, 1024.0, 256.0), torch.bfloat16: (4.0, 128.0, 32.0), torch.float32: (4.0, 1024.0, 256.0)}
+
+
+def grid_rand(shape, seed, lo=-4.0, hi=4.0, step=0.25, device='cpu'):
+    """Seeded float64 tensor of multiples of ``step`` (a power of two) drawn uniformly from [lo, hi] (``device``: where it is
+    drawn and kept; the sequence of a seed differs between devices, each is reproducible)."""
+    m, _ = np.frexp(step)
+    assert m == 0.5 and lo <= hi, 'step must be a power of two'
+    g = torch.Generator(device).manual_seed(seed)
+    return torch.randint(int(round(lo / step)), int(round(hi / step)) + 1, tuple(shape), generator=g, device=device).double() * step
+
+
+def grid_inputs(cins, cout, k, B, h, w, dtype, res_hw=None, seed=0, wshape=None, device='cpu'):
+    """Grid-valued activations (one per source), weights, bias and residual (or None) of one layer for storage type ``dtype``."""
+    xw, bb, rb = GRID_RANGE[dtype]
+    xs = [grid_rand((B, c, h, w), seed + 10 + i, -xw, xw, device=device) for i, c in enumerate(cins)]
+    wt = grid_rand(wshape or (cout, sum(cins), k, k), seed + 1, -xw, xw)
+    bias = grid_rand((cout,), seed + 2, -bb / 4, bb, 1.0 / 16)       # mostly positive: ReLU leaves four outputs of five
+    res = grid_rand((B, cout) + tuple(res_hw), seed + 20, -rb, rb, device=device) if res_hw else None
+    return xs, wt, bias, res
+
+
+def assert_grid_exact(xs, wt, bias, dtype, unit=1.0 / 16, fan_in=None):
+    """The conditions ON THE INPUTS under which the result is independent of the summation order: everything on its grid and
+    held exactly by the storage type, and fan_in * max|x| * max|w| + max|b| (an upper bound of sum|x||w| + |b|) below 2^24
+    grid units."""
+    for t in list(xs) + [wt]:
+        assert torch.equal(t.to(dtype).double(), t), 'the storage type does not hold the grid values'
+    assert torch.equal(bias.float().double(), bias)
+    fan_in = fan_in or wt[0].numel()
+    bound = fan_in * max(float(x.abs().max()) for x in xs) * float(wt.abs().max()) + float(bias.abs().max())
+    assert bound < 2 ** 24 * unit, bound
+    for t in list(xs) + [wt]:
+        assert torch.equal(torch.round(t * 4) / 4, t)              # x * w: multiples of 1/16
+    assert unit <= 1.0 / 16 and torch.equal(torch.round(bias / unit) * unit, bias)
+
+
+def to_exact_f32(t64):
+    """float64 -> float32, asserting that nothing is rounded (the value was an exact fp32 sum)."""
+    t32 = t64.float()
+    assert torch.equal(t32.double(), t64), 'the float64 reference is not an fp32 value: the data left the exact regime'
+    return t32
+
+
+def exact_epilogue(pre64, act, dtype, res64=None, alpha=RES_ALPHA):
+    """Expected bits for a pre-activation float64 sum on grid data: activation (none / relu), ONE round-to-nearest-even step
+    to the storage type, then the residual epilogue from_f32<T>(to_f32(T(act)) + alpha * to_f32(res)) -- an exact fp32 sum
+    of grid values rounded once more."""
+    assert act in ('none', 'relu')
+    v = torch.where(pre64 > 0, pre64, torch.zeros_like(pre64)) if act == 'relu' else pre64
+    y = to_exact_f32(v).to(dtype)
+    if res64 is not None:
+        assert torch.equal(res64.to(dtype).double(), res64)
+        y = to_exact_f32(y.double() + alpha * res64).to(dtype)
+    return y
+
+
+def exact_conv(xs, wt, bias, k, s, act, dtype, res64=None, alpha=RES_ALPHA):
+    """(expected tensor in ``dtype``, float64 values before the activation and the rounding) of a grid-valued conv layer."""
+    pre = torch.nn.functional.conv2d(torch.cat(xs, 1), wt, bias, stride=s, padding=k // 2)
+    return exact_epilogue(pre, act, dtype, res64, alpha), pre
+
+
+def rounding_stats(pre64, act, dtype):
+    """Fractions of the pre-rounding outputs (after the activation) that the storage type cannot hold, and that are exact ties."""
+    v = (torch.relu(pre64) if act == 'relu' else pre64)
+    r = v.float().to(dtype).double()
+    inexact = r != v
+    u = ulp(v, dtype)
+    tie = inexact & ((r - v).abs() * 2 == u)
+    return float(inexact.double().mean()), float(tie.double().mean())
+
+
+def ulp(v64, dtype):
+    """Spacing of the storage type at |v| (float64 tensor): 2^(max(floor(log2|v|), emin) - (p - 1))."""
+    _, e = torch.frexp(v64.abs())
+    e = torch.where(v64 == 0, torch.full_like(e, -10000), e) - 1
+    e = e.clamp(min=MIN_EXP[dtype], max=15 if dtype == torch.float16 else 127)
+    return torch.ldexp(torch.ones_like(v64), e - (SIG_BITS[dtype] - 1))
+
+
+def bit_mismatch_count(got, want):
+    """0-d integer tensor (on the device of ``got``): number of elements whose bit patterns differ.  Zeros of either sign compare
+    equal (the sign of zero has its own test); a NaN is equal only to the identical NaN pattern."""
+    assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
+    iv = INT_VIEW[got.dtype]
+    g, w = got.contiguous(), want.to(got.device).contiguous()
+    same = (g.view(iv) == w.view(iv)) | ((g == 0) & (w == 0))
+    return (~same).sum()
+
+
+def bit_mismatches(got, want):
+    return int(bit_mismatch_count(got, want))
+
+
+def assert_bits(got, want, what=''):
+    n = bit_mismatches(got, want)
+    if n:
+        g, w = got.cpu().double(), want.cpu().double()
+        bad = torch.nonzero((g != w) | torch.isnan(g))[:4].tolist()
+        raise AssertionError('%s: %d of %d elements differ from the exact reference, max |diff| %g, first at %s'
+                             % (what, n, got.numel(), float((g - w).abs().nan_to_num(float('inf')).max()), bad))
+
+
+def elementwise_excess(got, ref64, mag64, K, dtype, transcendental=False, slack64=None):
+    """max over elements of |got - ref64| / bound, bound = ulp_T(ref64) + 1.1 K 2^-24 mag64 (+ 4 * 2^-23 |ref64|):
+    one ulp of the storage type (half an ulp of rounding + a boundary flip), the standard bound K u sum|x||w| of an fp32
+    accumulation of K terms in any order (u = 2^-24) times the Lipschitz constant 1.1 of SiLU (1 for none / ReLU: covered), and
+    for an epilogue with v_exp_f32, v_rcp_f32 (1 ulp each) and a multiply, 4 * 2^-23 relative.  ``slack64``: a further derived
+    absolute term (the residual epilogue rounds the activation to the storage type BEFORE the add: one more ulp_T of it)."""
+    g, r, m = got.cpu().double(), ref64.double(), mag64.double()
+    bound = ulp(r, dtype) + 1.1 * K * 2.0 ** -24 * m
+    if transcendental:
+        bound = bound + 4 * 2.0 ** -23 * r.abs()
+    if slack64 is not None:
+        bound = bound + slack64.double()
+    ratio = (g - r).abs() / bound
+    ratio = torch.where(torch.isfinite(g), ratio, torch.full_like(ratio, float('inf')))
+    return float(ratio.max()), ratio
+
+
+def assert_elementwise(got, ref64, mag64, K, dtype, transcendental=False, slack64=None):
+    assert got.shape == ref64.shape == mag64.shape, (got.shape, ref64.shape, mag64.shape)
+    worst, ratio = elementwise_excess(got, ref64, mag64, K, dtype, transcendental, slack64)
+    if not worst <= 1.0:
+        i = int(ratio.flatten().argmax())
+        idx = np.unravel_index(i, tuple(ratio.shape))
+        raise AssertionError('element %s: got %r, reference %r, error / bound = %g (%d of %d elements over the bound)'
+                             % (idx, float(got.cpu().double().flatten()[i]), float(ref64.flatten()[i]), worst,
+                                int((ratio > 1).sum()), ratio.numel()))
+
+
+def _trim(B, h, w, cin, cout, k, budget=0.5e9):
+    """Batch size of the exact test for a case of the parity tests: as many images as keep the float64 CPU reference under
+    ``budget`` multiply-adds (the tile geometry of the block-tiled kernels depends on B: it gets a sweep of its own)."""
+    per_image = h * w * cin * cout * k * k
+    return max(1, min(B, int(budget // per_image)))
+
+
+def exact_conv_cases():
+    """(id, cins, cout, k, s, h, w, B) of the exact tests: the shapes of the parity tests (CONV_ / PIPE_ / PIPE16_ /
+    S2P16_ / RING_CASES of test_hip_kernels.py; the epilogue is the exact tests' own) with the batch trimmed."""
+    import test_hip_kernels as T
+    out, seen = [], set()
+
+    def add(cins, cout, k, s, res, h, w, B):
+        B = _trim(B, h // s, w // s, sum(cins), cout, k)
+        key = (tuple(cins), cout, k, s, h, w, B)
+        if key not in seen:
+            seen.add(key)
+            out.append(('%s-%d-k%ds%d-%dx%dx%d' % ('+'.join(map(str, cins)), cout, k, s, B, h, w),) + key)
+    for cins, cout, k, s, act, res, h, w, B in T.CONV_CASES:
+        add(cins, cout, k, s, res, h, w, B)
+    for cins, cout, act, res, h, w, B in T.PIPE_CASES + T.PIPE16_CASES:
+        add(cins, cout, 3, 1, res, h, w, B)
+    for cins, cout, act, h, w, B in T.S2P16_CASES:
+        add(cins, cout, 3, 2, False, h, w, B)
+    for cin, cout, h, w, B in T.RING_CASES:
+        add([cin], cout, 3, 1, False, h, w, B)
+    return out
+
+
+MODEL_CONFIGS = (('yololpn', 640), ('yololps', 640), ('yolov6m', 1280))     # the benchmark's configurations
+
+
+def model_layer_signatures(name, size):
+    """Distinct conv layers of a model as the engine lowers them (deploy form), found by walking its modules with the engine's
+    own graph builder on the CPU: (cins, cout or (cout1, cout2) for a two-destination launch, k, stride, residual, h, w of the
+    layer's INPUT map, log2 stride of that map).  The network input's own reader (the stem) is left to the stem tests."""
+    import os
+    from yolov6.hip import runtime
+    from yolov6.utils.synth import build_synthetic
+
+    class Recorder(runtime.Engine):
+        def __init__(self):
+            self.chan, self.sigs = {}, []
+            super().__init__(torch.float16, 'cpu')
+
+        def tensor(self, channels, sl):
+            tid = super().tensor(channels, sl)
+            self.chan[tid] = int(channels)
+            return tid
+
+        def _add_conv(self, srcs, w, b, k, s, act, dst, dst2=-1, res=None, alpha=0.0):
+            if srcs != [self.input_id]:
+                cout = (self.chan[dst], self.chan[dst2]) if dst2 >= 0 else self.chan[dst]
+                sig = (tuple(self.chan[t] for t in srcs), cout, k, s, res is not None, size >> self._sl, size >> self._sl, self._sl)
+                if sig not in self.sigs:
+                    self.sigs.append(sig)
+            super()._add_conv(srcs, w, b, k, s, act, dst, dst2, res, alpha)
+
+        def conv(self, srcs, weight, bias, k, s, act, sl, res=None, alpha=0.0):
+            self._sl = sl
+            return super().conv(srcs, weight, bias, k, s, act, sl, res, alpha)
+
+        def conv_pair(self, srcs, wb1, wb2, k, s, act, sl):
+            self._sl = sl
+            return super().conv_pair(srcs, wb1, wb2, k, s, act, sl)
+
+    m = build_synthetic(os.path.join(REPO, 'configs', name + '.py'))
+    rec = Recorder()
+    with torch.no_grad():
+        rec._build(m)
+    return rec.sigs
+
+
+def ref_images(B, most=3):
+    """Images of a batch the float64 reference of the elementwise check is computed for: all of a small batch, else the first,
+    the middle and the last one (the kernels still run the whole batch; the max-norm check beside it covers every image)."""
+    return list(range(B)) if B <= most else [0, B // 2, B - 1]
+
+
+def conv_ref64(xs, wt, bias, dtype, stride=1, padding=0, act='none', res=None, alpha=0.0, transposed=False):
+    """(ref64, mag64, K, slack64) for assert_elementwise: the layer in float64 on the values the engine stores (activations and
+    weights rounded to ``dtype``, fp32 bias), the same operation on absolute values, the number of summed terms, and -- residual
+    epilogue, which rounds the activation to the storage type before the add -- that rounding applied to the reference plus one
+    ulp of it as slack (a boundary flip of the first rounding)."""
+    import torch.nn.functional as F
+    q = lambda t: t.to(dtype).double()
+    x, w, b = torch.cat([q(t) for t in xs], 1), q(wt), bias.float().double()
+    if transposed:
+        op, K = (lambda a, c, d: F.conv_transpose2d(a, c, d, stride=stride)), w.shape[0] + 1
+    else:
+        op, K = (lambda a, c, d: F.conv2d(a, c, d, stride=stride, padding=padding)), w[0].numel() + 1
+    pre, mag = op(x, w, b), op(x.abs(), w.abs(), b.abs())
+    ref = {'none': lambda v: v, 'relu': torch.relu, 'silu': lambda v: v * torch.sigmoid(v), 'sigmoid': torch.sigmoid}[act](pre)
+    slack = None
+    if res is not None:
+        y1 = ref.float().to(dtype).double()
+        slack, ref, mag = ulp(y1, dtype), y1 + alpha * q(res), mag + abs(alpha) * q(res).abs()
+    return ref, mag, K, slack
+
+
+def log_dir():
+    """Folder the GPU tests append their logs to (the parity log, the tile log of the exact tests): LP_TEST_LOG_DIR if set, else the
+    output folder the repository's .gitignore keeps out of git (its first ``<name>_out/`` entry), else ``test_out`` in the tree."""
+    import re
+    d = os.environ.get('LP_TEST_LOG_DIR')
+    if not d:
+        d = os.path.join(REPO, 'test_out')
+        try:
+            with open(os.path.join(REPO, '.gitignore')) as f:
+                for line in f:
+                    if re.fullmatch(r'/?\w+_out/', line.strip()):
+                        d = os.path.join(REPO, line.strip().strip('/'))
+                        break
+        except OSError:
+            pass
+    os.makedirs(d, exist_ok=True)
+    return d

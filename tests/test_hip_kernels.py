@@ -5,7 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from lp_testing import rel_err
+from lp_testing import assert_elementwise, conv_ref64, ref_images, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -94,6 +94,9 @@ def test_conv(case, dtype):
     assert got.shape == ref.shape
     assert rel_err(got, ref) <= TOL[dtype], rel_err(got, ref)
     assert torch.isfinite(got).all()
+    # on top of the max-norm: every element within one ulp of the storage type + the fp32 accumulation bound of the float64 reference
+    ref64, mag64, K, slack = conv_ref64(xs, wt, bias, dtype, s, k // 2, act, res, 0.75)
+    assert_elementwise(got, ref64, mag64, K, dtype, transcendental=act == 'silu', slack64=slack)
 
 
 STREAM_CASES = [
@@ -204,6 +207,8 @@ def test_deconv2x2(cin, cout, h, w, dtype):
     q = lambda t: t.to(dtype).float()
     ref = F.conv_transpose2d(q(x), q(wt), bias, stride=2)
     assert rel_err(got, ref) <= TOL[dtype]
+    ref64, mag64, K, _ = conv_ref64([x], wt, bias, dtype, 2, transposed=True)
+    assert_elementwise(got, ref64, mag64, K, dtype)
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
@@ -280,6 +285,10 @@ def test_head(dtype, bins):
     assert torch.equal(pred[..., 4], torch.ones_like(pred[..., 4]))
     tol = TOL[dtype]
     assert float((pred[..., 13:] - ref[..., 13:]).abs().max()) <= tol * 2            # probabilities
+    # ... and elementwise: fp32 outputs of v_exp_f32 + v_rcp_f32 on an fp32 sum of C + 1 terms
+    cls64 = [conv_ref64([x], wc[..., None, None], bc, dtype, act='sigmoid') for (wc, bc, _, _, _), x in zip(ws, xs)]
+    cat64 = lambda k: torch.cat([c[k].reshape(B, 277, -1) for c in cls64], -1).permute(0, 2, 1)
+    assert_elementwise(pred[..., 13:], cat64(0), cat64(1), cls64[0][2], torch.float32, transcendental=True)
     scale = float(ref[..., :13].abs().max())
     assert float((pred[..., :13] - ref[..., :13]).abs().max()) <= tol * scale * (4 if bins > 1 else 2)
 
@@ -302,6 +311,8 @@ def test_fused_stem(dtype, xdtype, cout, H, W):
     ref = F.relu(F.conv2d(q(x), q(wt), bias, stride=2, padding=1))
     assert got.shape == ref.shape
     assert rel_err(got, ref) <= TOL[dtype]
+    ref64, mag64, K, _ = conv_ref64([x.float()], wt, bias, dtype, 2, 1, 'relu')
+    assert_elementwise(got, ref64, mag64, K, dtype)
 
 
 # ---- LP accuracy metric (lp_eval_counts) -----------------------------------------------------------------------
@@ -609,6 +620,11 @@ def test_conv3x3_pipe16(case, dtype):
                 assert float(d.max()) <= TOL[dtype] * float(ref.abs().max()) and float((d > 0).float().mean()) < 0.25
             assert torch.equal(out, base16), (cfg, rep, int((out != base16).sum()), int(torch.isnan(out.float()).sum()))
     assert base16 is not None
+    # both families elementwise against the float64 reference (of up to three images of the batch)
+    im = ref_images(B)
+    ref64, mag64, K, slack = conv_ref64([x[im] for x in xs], wt, bias, dtype, 1, 1, act, res[im] if use_res else None, 0.75)
+    for fam in (base32, base16):
+        assert_elementwise(fam[im], ref64, mag64, K, dtype, transcendental=act == 'silu', slack64=slack)
 
 
 S2P16_CASES = [
@@ -669,6 +685,10 @@ def test_conv3x3_s2p16(case, dtype):
                 d = (base16.float() - base32.float()).abs()
                 assert float(d.max()) <= TOL[dtype] * float(ref.abs().max()) and float((d > 0).float().mean()) < 0.25
             assert torch.equal(out, base16), (cfg, rep, int((out != base16).sum()), int(torch.isnan(out.float()).sum()))
+    im = ref_images(B)
+    ref64, mag64, K, _ = conv_ref64([x[im] for x in xs], wt, bias, dtype, 2, 1, act)
+    for fam in (base32, base16):
+        assert_elementwise(fam[im], ref64, mag64, K, dtype, transcendental=act == 'silu')
 
 
 RING_CASES = [

@@ -1654,6 +1654,52 @@ extern "C" int lp_engine_set_op_variant(lp_engine* e, int op_idx, int cfg, int n
     return LP_OK;
 }
 
+// Where the tile choice of an op's current form lives and which launch holds its prepared geometry: the fused / planar forms keep
+// choice + 1 in their own field (0 = form off), everything else uses op.tile.  nullptr: the op's current kernel has no output tiles.
+static int* op_tile_slot(lp_engine* e, int op_idx, int* bias, const Launch** L) {
+    Op& op = e->ops[(size_t)op_idx];
+    if (op.kind == OP_INPUT || op.kind == OP_POOL || op.mode != MODE_ACT || op.fused_bf) return nullptr;
+    const bool bound = e->arena && op_idx < (int)e->launches.size();
+    *bias = 1;
+    if (op.fused_pw) { *L = bound ? &e->pw_fused[op_idx] : nullptr; return &op.fused_pw; }
+    if (op.fused) { *L = bound ? &e->stem2_fused : nullptr; return &op.fused; }
+    if (op.planar) { *L = bound ? &e->stem_planar : nullptr; return &op.planar; }
+    if (op.stream_wc && !op.pipe) return nullptr;      // the streaming 1x1 kernel walks pixels, not tiles
+    *bias = 0;
+    *L = bound ? &e->launches[(size_t)op_idx] : nullptr;
+    return &op.tile;
+}
+
+extern "C" int lp_engine_set_op_tile(lp_engine* e, int op_idx, int choice) {
+    if (!e || !e->finalized || op_idx < 0 || op_idx >= (int)e->ops.size() || choice < 0) return fail(LP_ERR_ARG, "lp_engine_set_op_tile: op index or choice");
+    int bias = 0;
+    const Launch* L = nullptr;
+    int* slot = op_tile_slot(e, op_idx, &bias, &L);
+    if (!slot) return fail(LP_ERR_UNSUPPORTED, "lp_engine_set_op_tile: the op's kernel has no output tiles");
+    const int before = *slot;
+    *slot = choice + bias;
+    e->tuned.erase({e->B, e->H, e->W});
+    if (e->arena && op_idx < (int)e->launches.size()) {
+        const int rc = prepare_op(e, (size_t)op_idx);
+        if (rc) { *slot = before; prepare_op(e, (size_t)op_idx); }      // (the fused / planar forms have a finite list of tiles)
+        return rc;
+    }
+    return LP_OK;
+}
+
+extern "C" int lp_engine_op_tile(const lp_engine* e, int op_idx, int* choice, int* TH, int* TW) {
+    if (!e || !e->finalized || op_idx < 0 || op_idx >= (int)e->ops.size()) return fail(LP_ERR_ARG, "lp_engine_op_tile: op index");
+    int bias = 0;
+    const Launch* L = nullptr;
+    const int* slot = op_tile_slot(const_cast<lp_engine*>(e), op_idx, &bias, &L);
+    if (!slot) return fail(LP_ERR_UNSUPPORTED, "lp_engine_op_tile: the op's kernel has no output tiles");
+    if (!L) return fail(LP_ERR_STATE, "lp_engine_op_tile: no shape bound");
+    if (choice) *choice = *slot - bias;
+    if (TH) *TH = L->a.TH;
+    if (TW) *TW = L->a.TW;
+    return LP_OK;
+}
+
 extern "C" int lp_engine_op_carrier(const lp_engine* e, int op, int frame_direct_) {
     if (!e || op < 0 || op >= (int)e->ops.size()) return -1;
     const Op& o = e->ops[(size_t)op];

@@ -106,6 +106,8 @@ SYMBOLS = {
     'lp_engine_autotune': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]),
     'lp_engine_op_variant': (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int)]),
     'lp_engine_set_op_variant': (c_int, [c_void_p, c_int, c_int, c_int]),
+    'lp_engine_set_op_tile': (c_int, [c_void_p, c_int, c_int]),
+    'lp_engine_op_tile': (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     'lp_engine_copy_tuning': (c_int, [c_void_p, c_void_p]),
     'lp_nms_workspace_bytes': (c_size_t, [c_int, c_int]),
     'lp_nms_candidate_counts': (c_void_p, [c_void_p, c_int, c_int]),

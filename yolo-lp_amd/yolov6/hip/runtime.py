@@ -430,6 +430,17 @@ class Engine:
         self.autotune = False
         abi.check(self.lib.lp_engine_set_op_variant(self.h, op, cfg, nbuf), 'lp_engine_set_op_variant')
 
+    def set_tile(self, op, choice):
+        """Force the output-tile choice of op ``op``'s current variant (see lp_engine_set_op_tile; tests); switches the autotuner off."""
+        self.autotune = False
+        abi.check(self.lib.lp_engine_set_op_tile(self.h, op, choice), 'lp_engine_set_op_tile')
+
+    def tile(self, op):
+        """(choice, TH, TW) of op ``op``'s current variant for the bound shape (lp_engine_op_tile)."""
+        c, th, tw = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        abi.check(self.lib.lp_engine_op_tile(self.h, op, ctypes.byref(c), ctypes.byref(th), ctypes.byref(tw)), 'lp_engine_op_tile')
+        return c.value, th.value, tw.value
+
     def tensor_view(self, tid):
         """Zero-copy [B,C,h,w] view (channels_last strides) of an arena tensor."""
         off, c, cs, h, w = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
