@@ -341,6 +341,63 @@ int lp_merge_tiles(const float* det_t, const int32_t* count_t, const lp_tile_ref
                    const int* frame_hw, int n_frames, double thres, int metric /* 0 IoU, 1 IoS */, int border, int max_det,
                    float* det, int32_t* count, int32_t* src, void* workspace, size_t workspace_bytes, void* stream);
 
+/* lp_track_update: plate tracking across video frames with a per-track vote over the eight character heads; a small
+ * device-resident tracker per stream, one workgroup per stream, at most LP_FRAMES_PER_LAUNCH frames per launch (a longer call is
+ * several launches on `stream`, a stream's frames may span them); the frame table travels as kernel arguments: nothing is
+ * uploaded, no host sync, so the call can be enqueued behind lp_rescale_round_batch.  The reference has nothing here (Inferer
+ * treats video frames independently, inferer.py); yolov6/utils/track.py::PlateTrackerNp restates the rules below bit for bit.
+ *   state: DEVICE, 16-byte aligned, lp_track_state_bytes(n_streams, max_tracks) bytes, all zero = no tracks (the caller zeroes
+ *   it once; zeroing a stream's lp_track_state_bytes(1, max_tracks) bytes resets that stream).  max_tracks: 1..LP_TRACK_MAX_TRACKS.
+ *   det [B,max_det,28] fp32 + count [B] int32 (DEVICE): the frames' detections as lp_nms / lp_rescale_round_batch leave them;
+ *   only the first n = min(max(count, 0), max_det, LP_TRACK_MAX_DETS) rows of a frame take part.
+ *   stream_of: HOST int [B], the stream of frame b, or -1: the frame is not tracked (padding slots of a batch).  The frames of a
+ *   stream are taken in ascending b; streams need not be contiguous.  flush: HOST [n_streams] or NULL; after its frames (there
+ *   may be none) a stream with flush[s] != 0 ends all its live tracks in slot order.
+ *   det_out [B,max_det,28] (may not alias det), tid [B,max_det] int32; ended_i / ended_f [n_streams,max_ended,12], ended_count
+ *   [n_streams] int32: per stream the first max_ended records of the tracks that ended in this call, in the order they ended
+ *   (records past them are zero), and the number that ended (it may exceed max_ended).  ended_i = id, first, last, hits,
+ *   best_0..7; ended_f = share_0..7, x1, y1, x2, y2 (the last matched box).
+ * Per frame of a stream, fp32 op by op (no fused multiply-add), every live slot holding id, first, last (frame index of the last
+ * match), hits, misses, the box and corners of the last matched row, a velocity (vx, vy), votes[8][LP_TRACK_MAX_CLS] and total[8]:
+ *   1. predict: the box shifted by (vx * k, vy * k), k = (float)(misses + 1); the product is rounded, then the add;
+ *   2. expand, for the predicted box and every row's box: e = (float)expand * (x2 - x1), x1 -= e, x2 += e; the same in y;
+ *   3. pairs: the IoU of every (slot, row) on the expanded boxes, inter / (area_i + area_j - inter) with the fp32 ops of lp_nms's
+ *      IoU predicate (torchvision's, the quotient computed: it is the sort key); the pair exists iff (double)iou > match_thres
+ *      (not for NaN).  Order: descending IoU, ties by slot, then row; in that order a pair is taken iff its slot and its row are
+ *      both still free (global greedy matching);
+ *   4. a matched slot: vx = (cx_new - cx_old) / k with cx = (x1 + x2) * 0.5f on the stored, unexpanded box, vy likewise; box and
+ *      corners = the row's columns 0..11; hits += 1, misses = 0, last = frame; it votes (7);
+ *   5. an unmatched live slot: misses += 1; misses > max_age ends the track (record appended, slot zeroed), in slot order;
+ *   6. unmatched rows in row order: score = (c12 + ... + c19) / 8.0f summed left to right (nms.py:120); iff (double)score >=
+ *      new_thres (not for NaN) the lowest free slot -- those freed in 5 included -- becomes a new track: id = next_id++, first =
+ *      last = frame, hits = 1, misses = 0, zero velocity, zero votes, then it votes.  With no free slot the row stays untracked
+ *      and the stream's `dropped` counter goes up;
+ *   7. vote, per head p: v = c[20+p], conf = c[12+p]; iff conf > 0 && 0 <= v < ncls[p] (float compares, false for NaN):
+ *      votes[p][(int)v] += conf, total[p] += conf;
+ *   8. read of a track: best_p = the first index of the largest votes[p][0..ncls[p]) (strict >: 0 for an all-zero head),
+ *      share_p = total[p] > 0 ? votes[p][best_p] / total[p] : 0.0f;
+ *   9. tid[r] = the id of a matched or new row's track, -1 for every other r < max_det; det_out[r] = the row with columns
+ *      12..19 replaced by the track's shares and 20..27 by (float)best_p, read after this frame's vote: the layout everything
+ *      downstream takes (lp_plate_crops_batch).  Other rows r < min(max(count, 0), max_det) are copied unchanged (so are all
+ *      such rows of a frame with stream_of -1, whose tid is -1), rows at or past it are zero;
+ *  10. the stream's frame counter goes up.  Frame counter and next_id start at 0.
+ * `dropped` (int32, rows that found no free slot since the state was zeroed) is read from the state itself: it lives
+ * lp_track_dropped_offset(max_tracks, s) bytes into it.
+ * Every argument is checked before the first launch (LP_ERR_ARG names the offending frame or head; nothing is launched):
+ * match_thres in [0, 1], |new_thres| <= 3e38, expand in [0, 1e6], max_age >= 0, ncls[p] in 1..LP_TRACK_MAX_CLS (the model's
+ * npro, nalp, nads x 6), B >= 0, max_det >= 1, max_ended >= 0, stream_of[b] in -1..n_streams-1. */
+#define LP_TRACK_MAX_TRACKS 128
+#define LP_TRACK_MAX_DETS 128   /* 128 x 128 pair keys are sorted in LDS: the budget of lp_merge_tiles */
+#define LP_TRACK_MAX_CLS 64
+typedef struct lp_track_params { double match_thres, new_thres, expand; int max_age; int ncls[8]; } lp_track_params;
+size_t lp_track_state_bytes(int n_streams, int max_tracks);   /* 0: bad arguments */
+size_t lp_track_dropped_offset(int max_tracks, int stream_index);
+int lp_track_update(void* state, int n_streams, int max_tracks, const lp_track_params* p,
+                    const float* det, const int32_t* count, int B, int max_det,
+                    const int* stream_of /* HOST [B] */, const unsigned char* flush /* HOST [n_streams] or NULL */,
+                    float* det_out, int32_t* tid, int32_t* ended_i, float* ended_f, int32_t* ended_count,
+                    int max_ended, void* stream);
+
 /* lp_plate_crops_batch: perspective-rectified plate crops of B frames' detections (the inverse of the warp of the reference's
  * plate generator, yolov6/data/generate/generate.py:566-586), one launch per LP_FRAMES_PER_LAUNCH frames; descriptors travel
  * as kernel arguments, so nothing is uploaded and the call may be captured in a graph.

@@ -5,6 +5,7 @@
                                  [--crops N]
     python tools/frames_bench.py --tile [--tile-baseline] [--tile-frame 2160 3840] [--tile-size 640] [--tile-overlap 128]
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
+    python tools/frames_bench.py --track [--track-batch 32] [--runs 3]
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
   - frames/s of the per-frame path (upload, lp_preprocess_letterbox, detect at B=1 with hipGraph replay, lp_rescale_round,
@@ -22,6 +23,11 @@ them per call -- frames/s over ``--runs`` timed runs, and the device time of eac
 run, the same job done with the entry points that existed before tiling: region copies made contiguous on the device,
 ``detect_frames(auto=False)`` per ``--tile-batch`` tiles, the detections read to the host and merged there by
 ``merge_tiles_np``.
+With ``--track`` the tool measures plate tracking instead: ``--track-batch`` camera streams, one frame each per step --
+frames/s of FrameBatcher + ``detect_frames`` alone and of ``detect_frames_padded`` + ``PlateTracker.update`` + the host read
+of the voted rows and track ids, ``--runs`` timed runs each in the same process, alternating; the device time of the update
+from events (median of ``--reps``) next to the detect stage of the same chain, at the bench's own detection density; and the
+update alone on a full frame per stream (128 live tracks x 128 rows, every pair above the threshold: 16384 sorted keys).
 The model is the synthetic recipe of bench.py (same weights scale), prepared as Inferer prepares it.
 """
 import argparse
@@ -61,6 +67,8 @@ def parse():
     ap.add_argument('--tile-overlap', type=int, default=128, help='tile overlap in pixels')
     ap.add_argument('--tile-frames', type=int, default=4, help='frames per detect_tiled call')
     ap.add_argument('--tile-batch', type=int, default=32, help='tiles per forward')
+    ap.add_argument('--track', action='store_true', help='measure plate tracking (PlateTracker.update behind detect_frames) instead')
+    ap.add_argument('--track-batch', type=int, default=32, help='with --track: camera streams = frames per step')
     ap.add_argument('--runs', type=int, default=3, help='timed runs of the frames/s figures (the spread is reported)')
     return ap.parse_args()
 
@@ -165,6 +173,96 @@ def tile_mode(args, model, dev, tdt):
     print(json.dumps(out))
 
 
+def track_mode(args, model, dev, tdt):
+    """--track: frames/s with and without PlateTracker.update behind detect_frames, and the device time of the update."""
+    import torch
+    from yolov6.hip import runtime
+    from yolov6.core.frames import FrameBatcher, letterbox_hw
+    size, stride = [args.size, args.size], int(model.stride.max())
+    h0, w0 = args.frame
+    B, conf, iou, max_det = args.track_batch, args.conf, args.iou, args.max_det
+    rng = np.random.default_rng(0)
+    pool = [rng.integers(0, 256, (h0, w0, 3), dtype=np.uint8) for _ in range(args.distinct)]
+    H, W = letterbox_hw((h0, w0), size, stride)
+    sync = torch.cuda.synchronize
+    out = dict(metric='frames/s end to end with and without plate tracking (host frames in, rows out)', model=args.model,
+               dtype=args.dtype, frame=[h0, w0], net=[H, W], streams=B, runs=args.runs)
+    with torch.no_grad():
+        runtime.prepare_for(model, (B, 3, H, W), tdt)
+        batcher = FrameBatcher(dev)
+        x = torch.empty(B, 3, H, W, dtype=tdt, device=dev)
+        trk = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
+        batch_of = lambda k: batcher.put([pool[(k * B + j) % len(pool)] for j in range(B)])   # noqa: E731
+
+        def plain(k):
+            return runtime.detect_frames(model, batch_of(k), size, conf, iou, max_det, batch=B, out=x)
+
+        def tracked(k):
+            det, count = runtime.detect_frames_padded(model, batch_of(k), size, conf, iou, max_det, batch=B, out=x)
+            det_out, tid = trk.update(det, count)[:2]
+            return runtime._unpad(det_out, count.cpu().tolist()), tid.cpu()
+
+        nb = max(2, args.frames // B)
+        fps = dict(plain=[], tracked=[])
+        for fn in (plain, tracked):
+            for k in range(2):
+                fn(k)
+        sync()
+        for _ in range(args.runs):
+            for name, fn in (('plain', plain), ('tracked', tracked)):
+                t0 = time.perf_counter()
+                for k in range(nb):
+                    fn(k)
+                sync()
+                fps[name].append(round(nb * B / (time.perf_counter() - t0), 1))
+        out['fps_runs'] = fps
+        out['fps'] = {k: float(np.median(v)) for k, v in fps.items()}
+        out['tracked_over_plain'] = round(out['fps']['tracked'] / out['fps']['plain'], 4)
+
+        # device time of detect and of the update behind it, from events on one stream
+        frames = batch_of(0)
+        times = dict(detect=[], track=[])
+        for _ in range(args.reps + 1):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            xx, _ = runtime.preprocess_frames(frames, size, stride, tdt, batch=B, out=x)
+            ev[0].record()
+            det, count, _ = runtime.detect_padded(model, xx, conf, iou, max_det)
+            runtime.rescale_round_batch(det, count, (H, W), [f.shape for f in frames])
+            ev[1].record()
+            trk.update(det, count)
+            ev[2].record()
+            sync()
+            times['detect'].append(ev[0].elapsed_time(ev[1]))
+            times['track'].append(ev[1].elapsed_time(ev[2]))
+        med = {k: float(np.median(v[1:])) for k, v in times.items()}
+        out['stage_ms'] = {k: round(v, 4) for k, v in med.items()}
+        out['track_pct_of_detect'] = round(100.0 * med['track'] / med['detect'], 2)
+        out['detections_per_frame'] = count.clamp(0, max_det).cpu().tolist()
+        out['live_tracks_per_stream'] = (trk.state.view(B, -1)[:, 16:].view(B, 128, -1)[:, :, 3] > 0).sum(1).cpu().tolist()
+
+        # the full case: 128 live tracks x 128 rows per stream, every pair above the threshold
+        full = runtime.PlateTracker(B, max_tracks=128, max_age=0, ncls=model, device=dev)
+        rows = np.zeros((B, 128, 28), np.float32)
+        for k in range(128):
+            rows[:, k, 0:4] = (k % 7, k % 5, 1000 + k, 1000 + k % 11)
+        rows[:, :, 12:20] = 0.5
+        rows[:, :, 20:28] = rng.integers(0, 24, (B, 128, 8))
+        fdet = torch.from_numpy(rows).to(dev)
+        fcount = torch.full((B,), 128, dtype=torch.int32, device=dev)
+        full.update(fdet, fcount)                 # 128 new tracks per stream
+        ms = []
+        for _ in range(args.reps + 1):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            tid = full.update(fdet, fcount)[1]
+            b.record()
+            sync()
+            ms.append(a.elapsed_time(b))
+        out['full_128x128_ms'] = round(float(np.median(ms[1:])), 4)
+        out['full_128x128_matched'] = int((tid >= 0).sum())
+    print(json.dumps(out))
+
+
 def synthetic_quads(n_frames, n, h0, w0, seed=0):
     """[n_frames, n, 28] fp32 detection rows: plates of 120..400 px x 1/3.1 of that, turned by up to 30 degrees; row r % 4 == 1
     also has each corner moved by up to 10 % (perspective), r % 4 == 3 has its BL and TR swapped (a bow-tie: the box is used)."""
@@ -222,6 +320,8 @@ def main():
     model.lp_graph = True                   # as Inferer sets it
     if args.tile:
         return tile_mode(args, model, dev, tdt)
+    if args.track:
+        return track_mode(args, model, dev, tdt)
     size, stride = [args.size, args.size], int(model.stride.max())
     h0, w0 = args.frame
     rng = np.random.default_rng(0)

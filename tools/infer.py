@@ -4,6 +4,7 @@
     python tools/infer.py --weights weights/yololps.pt --source data/images --yaml data/dataset.yaml [--half]
                           [--batch-size 32] [--fixed-shape] [--save-crops [--crop-size 64 192]]
                           [--tile 640 640 [--tile-overlap 0.2] [--no-tile-overview] [--merge-metric iou|ios]]
+                          [--track [--track-max-age 5] [--track-iou 0.3] [--track-expand 0.5]]
 """
 import argparse
 import os
@@ -50,6 +51,11 @@ _FLAGS = [
     ('--tile-overlap', dict(type=float, default=0.2, help='overlap of neighbouring tiles: pixels, or a fraction of the tile below 1')),
     ('--no-tile-overview', dict(action='store_true', help='do not add the whole frame as one more tile')),
     ('--merge-metric', dict(default='iou', choices=['iou', 'ios'], help='overlap measure of the cross-tile merge')),
+    ('--track', dict(action='store_true', help='track plates across the frames of a video (or of the image files, in order) and vote '
+                                               'their characters per track: saves the voted rows, tracks.txt and plates.txt')),
+    ('--track-max-age', dict(type=int, default=5, help='frames a track survives unseen')),
+    ('--track-iou', dict(type=float, default=0.3, help='IoU (of the expanded boxes) above which a detection continues a track')),
+    ('--track-expand', dict(type=float, default=0.5, help='boxes are grown by this fraction of their size on every side before the IoU')),
 ]
 
 
@@ -67,10 +73,11 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         conf_thres=0.4, iou_thres=0.45, max_det=1000, device='', save_txt=False, not_save_img=False, save_dir=None,
         view_img=True, classes=None, agnostic_nms=False, project=osp.join(ROOT, 'runs/inference'), name='exp',
         hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False, save_crops=False, crop_size=(64, 192),
-        tile=None, tile_overlap=0.2, no_tile_overview=False, merge_metric='iou'):
+        tile=None, tile_overlap=0.2, no_tile_overview=False, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3,
+        track_expand=0.5):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
-    if (save_img or save_txt or save_crops) and not osp.exists(out_dir):
+    if (save_img or save_txt or save_crops or track) and not osp.exists(out_dir):
         os.makedirs(out_dir)
     else:
         LOGGER.warning('Save directory already existed')
@@ -79,7 +86,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
     if tile is not None and tile_overlap >= 1:
         tile_overlap = int(tile_overlap)        # pixels
     results = Inferer(source, weights, device, yaml, img_size, half, batch_size=batch_size, auto=not fixed_shape, tile=tile,
-                      tile_overlap=tile_overlap, tile_overview=not no_tile_overview, merge_metric=merge_metric).infer(
+                      tile_overlap=tile_overlap, tile_overview=not no_tile_overview, merge_metric=merge_metric, track=track, track_max_age=track_max_age,
+                      track_iou=track_iou, track_expand=track_expand).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

@@ -13,6 +13,9 @@ an upright image (``runtime.plate_crops`` on a GPU, ``plate_crops_np`` on the CP
 With ``tile`` every frame is detected by overlapping tiles of that size plus an overview of the whole frame, merged per
 frame (``runtime.detect_tiled`` on a GPU; per-tile inference and ``merge_tiles_np`` on the CPU): for frames much larger
 than the network input, whose plates a single letterbox would shrink away.
+With ``track`` the detections of consecutive frames are associated into plate tracks and every track votes its eight
+characters over its frames (``runtime.PlateTracker`` on a GPU, ``PlateTrackerNp`` on the CPU): ``infer`` returns and saves the
+voted rows and writes ``tracks.txt`` (one line per frame row) and ``plates.txt`` (one line per track).
 """
 import math
 import os
@@ -32,12 +35,16 @@ from yolov6.utils.nms import non_max_suppression
 
 class Inferer:
     def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True, tile=None, tile_overlap=0.2,
-                 tile_overview=True, merge_metric='iou'):
+                 tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
         the whole frame as one more tile with ``tile_overview``, and the cross-tile merge by ``merge_metric`` ('iou' / 'ios');
-        ``batch_size`` is then the number of tiles per forward."""
+        ``batch_size`` is then the number of tiles per forward.
+        ``track``: plate tracking with a per-track character vote (``yolov6.utils.track`` states the rules): every video file is
+        one stream, all image files of the source, in ``LoadData``'s order, are one more; a row continues the track whose
+        predicted box (grown by ``track_expand`` of its size) it overlaps by more than ``track_iou``, a track unseen for more
+        than ``track_max_age`` frames ends."""
         self.__dict__.update(locals())
         if merge_metric not in ('iou', 'ios'):
             raise ValueError("merge_metric must be 'iou' or 'ios'")
@@ -86,7 +93,15 @@ class Inferer:
 
         The frames come in groups of ``(items, dets, crops or None, seconds)`` -- ``items`` = [(frame, path)], ``seconds`` the
         timed model + NMS window of the group -- from ``_per_image`` (groups of one) or, on a GPU with ``tile`` or
-        ``batch_size > 1``, from ``_gpu_groups``; every path writes and returns per frame, in source order, the same things."""
+        ``batch_size > 1``, from ``_gpu_groups``; every path writes and returns per frame, in source order, the same things.
+
+        With ``track`` the rows returned and saved are the voted ones (the class columns of a tracked row replaced by its
+        track's read: columns 12..19 the vote shares, 20..27 the voted ids; the geometry is unchanged), and two files are
+        written: ``<save_dir>/tracks.txt``, one line ``path row track_id`` per frame row (-1: untracked), and
+        ``<save_dir>/plates.txt``, one line ``id first last hits text share_0..7`` per ended track (all streams are flushed
+        at the end; ids count per stream)."""
+        if self.track:
+            self._track_begin()
         if self.device.type != 'cpu' and (self.tile is not None or self.batch_size > 1):
             groups = self._gpu_groups(conf_thres, iou_thres, max_det, save_crops, crop_size)
         else:
@@ -101,6 +116,10 @@ class Inferer:
                 if save_crops and len(det):
                     self.write_crops(img_path, crops[k], save_dir)
                 results.append(det)
+                if self.track:
+                    self._track_lines += ['%s %d %d' % (img_path, r, t) for r, t in enumerate(self._track_tids.popleft().tolist())]
+        if self.track:
+            self._track_finish(save_dir)
         LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
         return results
 
@@ -134,6 +153,8 @@ class Inferer:
                 runtime.rescale_round(img.shape[2:], det, img_src.shape)
             elif len(det) and self.tile is None:      # (tiled_rows_cpu returns frame pixels)
                 det[:, :12] = self.rescale(img.shape[2:], det[:, :12], img_src.shape).round()
+            if self.track:
+                det = self._track_frame(det, img_path, max_det)
             crops = None
             if save_crops and len(det):
                 if gpu:     # the uploaded frame and its detections are on the device: crop there
@@ -202,7 +223,16 @@ class Inferer:
         for items, kw in groups:
             t1 = time.time()
             dev_frames = batcher.put([f for f, _ in items])
-            if save_crops:
+            if self.track:      # detect -> track -> (crops) enqueued back to back on the device, then the host reads
+                padded = runtime.detect_frames_padded if self.tile is None else runtime.detect_tiled_padded
+                det, count = padded(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det, **kw)
+                det, tid = self._track_update(det, count, [p for _, p in items])
+                if save_crops:
+                    dets, crops, _ = runtime._unpad_with_crops(dev_frames, det, count, runtime._crop_size(crop_size))
+                else:
+                    dets, crops = runtime._unpad(det, count.cpu().tolist(), len(items)), None
+                self._track_tids.extend(tid[k, :len(d)].cpu().numpy() for k, d in enumerate(dets))
+            elif save_crops:
                 dets, crops, _ = detect_with_crops(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det,
                                                    crop_size, **kw)
             else:
@@ -231,6 +261,73 @@ class Inferer:
         det, count, _ = merge_tiles_np(det_t, count_t, [(0,) + t for t in tiles], [img_src.shape], iou_thres, max_det,
                                        self.merge_metric, border)
         return torch.from_numpy(det[0, :int(count[0])].copy())
+
+    # ---- tracking (``track=True``) ---------------------------------------------------------------------------------------
+    TRACK_SLOTS = 64        # tracks alive at once per stream
+
+    def _track_begin(self):
+        """A fresh tracker: stream 0 = the image files of the source, stream 1 + k = its k-th video file."""
+        from yolov6.utils.track import PlateTrackerNp
+        videos = [p for p in self.files.files if self.files.checkext(p) != 'image']
+        self._track_streams = {p: 1 + k for k, p in enumerate(videos)}
+        kw = dict(max_tracks=self.TRACK_SLOTS, match_thres=self.track_iou, new_thres=0.0, expand=self.track_expand,
+                  max_age=self.track_max_age, ncls=self.model.model)
+        if self.device.type != 'cpu':
+            from yolov6.hip import runtime
+            self._tracker = runtime.PlateTracker(1 + len(videos), device=self.device, **kw)
+        else:
+            self._tracker = PlateTrackerNp(1 + len(videos), **kw)
+        self._track_tids, self._track_lines, self._track_ended = deque(), [], []
+
+    def _track_collect(self, ended_i, ended_f, ended_count):
+        """Keep the ended records of one update (the host read of a GPU update)."""
+        if torch.is_tensor(ended_count):
+            ended_i, ended_f, ended_count = ended_i.cpu().numpy(), ended_f.cpu().numpy(), ended_count.cpu().numpy()
+        for s, c in enumerate(ended_count.tolist()):
+            if c > ended_i.shape[1]:
+                LOGGER.warning('stream %d: %d tracks ended in one step, %d recorded' % (s, c, ended_i.shape[1]))
+            for k in range(min(c, ended_i.shape[1])):
+                self._track_ended.append((ended_i[s, k].copy(), ended_f[s, k].copy()))
+
+    def _track_update(self, det, count, paths):
+        """One tracker update of a padded group: det [B,max_det,28] + count [B] (numpy on the CPU, device tensors on a GPU) of
+        the frames ``paths`` (consecutive frames; slots past them are padding): (voted det, tid [B,max_det]), copies."""
+        B = det.shape[0]
+        streams = [self._track_streams.get(p, 0) for p in paths] + [-1] * (B - len(paths))
+        # a slot's track lives at least max_age + 1 frames: so many records at most can end in B frames
+        max_ended = self._tracker.max_tracks * (B // (self.track_max_age + 1) + 1)
+        det_out, tid, ended_i, ended_f, ended_count = self._tracker.update(det, count, streams, max_ended=max_ended)
+        self._track_collect(ended_i, ended_f, ended_count)
+        if torch.is_tensor(det_out):
+            det_out, tid = det_out.clone(), tid.clone()     # the tracker's buffers are persistent
+        return det_out, tid
+
+    def _track_frame(self, det, img_path, max_det):
+        """The voted rows of one frame's rescaled detections ([n, 28] tensor); its track ids are queued for ``infer``."""
+        n, max_det = len(det), max(int(max_det), len(det), 1)
+        if self.device.type != 'cpu':
+            pad = torch.zeros(1, max_det, 28, dtype=torch.float32, device=self.device)
+            pad[0, :n] = det
+            out, tid = self._track_update(pad, torch.full((1,), n, dtype=torch.int32, device=self.device), [img_path])
+            self._track_tids.append(tid[0, :n].cpu().numpy())
+            return out[0, :n]
+        pad = np.zeros((1, max_det, 28), np.float32)
+        pad[0, :n] = det.detach().float().cpu().numpy()
+        out, tid = self._track_update(pad, np.array([n], np.int32), [img_path])
+        self._track_tids.append(tid[0, :n])
+        return torch.from_numpy(out[0, :n].copy())
+
+    def _track_finish(self, save_dir):
+        """Flush every stream and write tracks.txt / plates.txt."""
+        from yolov6.utils.track import plate_text
+        self._track_collect(*self._tracker.flush_all()[2:])
+        os.makedirs(save_dir, exist_ok=True)
+        with open(osp.join(save_dir, 'tracks.txt'), 'w') as f:
+            f.writelines(line + '\n' for line in self._track_lines)
+        with open(osp.join(save_dir, 'plates.txt'), 'w') as f:
+            for ri, rf in self._track_ended:
+                text = plate_text(ri[4:12], self.pro_names, self.alp_names, self.ads_names)
+                f.write('%d %d %d %d %s %s\n' % (ri[0], ri[1], ri[2], ri[3], text, ' '.join('%g' % v for v in rf[:8])))
 
     def _frames_ahead(self, prefetch_frames, imread_bgr):
         """(frame, path) of every source in LoadData's order: image files decoded ahead on the pool, videos read in turn."""

@@ -30,7 +30,8 @@ VARIANT_SHORT = {
 }
 LP_FRAMES_PER_LAUNCH = 64   # lp_preprocess_letterbox_batch / lp_rescale_round_batch / lp_plate_crops_batch: frames per launch
 LP_MERGE_MAX_TILES, LP_MERGE_MAX_CANDIDATES = 64, 16384   # lp_merge_tiles: tiles per frame, tiles_of_frame * max_det_t
-LP_EVAL_NCOUNTS = 43   # lp_eval_counts: length of the counts vector (include/lp_hip.h)
+LP_TRACK_MAX_TRACKS, LP_TRACK_MAX_DETS, LP_TRACK_MAX_CLS = 128, 128, 64   # lp_track_update: slots per stream, rows per frame, classes per head
+LP_EVAL_NCOUNTS = 43  # lp_eval_counts: length of the counts vector (include/lp_hip.h)
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # .../yolo-lp_amd
 LIB_PATH = os.environ.get('LP_HIP_LIB') or os.path.join(_PKG_ROOT, 'libyololp_hip.so')   # LP_HIP_LIB: debug builds
@@ -61,6 +62,11 @@ class TileDesc(ctypes.Structure):
 class TileRef(ctypes.Structure):
     """lp_tile_ref"""
     _fields_ = [('frame', c_int), ('y0', c_int), ('x0', c_int), ('th', c_int), ('tw', c_int)]
+
+
+class TrackParams(ctypes.Structure):
+    """lp_track_params"""
+    _fields_ = [('match_thres', c_double), ('new_thres', c_double), ('expand', c_double), ('max_age', c_int), ('ncls', c_int * 8)]
 
 
 class ConvDesc(ctypes.Structure):
@@ -120,6 +126,10 @@ SYMBOLS = {
     'lp_merge_tiles_workspace_bytes': (c_size_t, [c_int, c_int]),
     'lp_merge_tiles': (c_int, [c_void_p, c_void_p, POINTER(TileRef), c_int, c_int, POINTER(c_int), c_int, c_double, c_int, c_int, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'lp_track_state_bytes': (c_size_t, [c_int, c_int]),
+    'lp_track_dropped_offset': (c_size_t, [c_int, c_int]),
+    'lp_track_update': (c_int, [c_void_p, c_int, c_int, POINTER(TrackParams), c_void_p, c_void_p, c_int, c_int, POINTER(c_int),
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'lp_plate_crops_batch': (c_int, [POINTER(CropDesc), c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                      c_void_p]),
     'lp_eval_counts': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

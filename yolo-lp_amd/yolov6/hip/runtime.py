@@ -1130,6 +1130,93 @@ def detect_tiled_with_crops(model, frames, img_size, conf_thres, iou_thres, max_
     return _unpad_with_crops(frames, det, count, crop_hw)
 
 
+# ---------------------------------------------------------------------------------------------------
+# Plate tracking across video frames (lp_track_update; yolov6/utils/track.py states the rules)
+class PlateTracker:
+    """``n_streams`` independent device-resident plate trackers of ``max_tracks`` slots each (lp_track_update, one workgroup per
+    stream): detections of consecutive frames are associated by the IoU of expanded, velocity-predicted boxes
+    (``match_thres``, ``expand``), a row that matches nothing and scores at least ``new_thres`` starts a track, a track unseen
+    for more than ``max_age`` frames ends, and every track votes its eight character heads over its frames, weighted by
+    confidence.  ``ncls``: the eight head widths, a model, or None for the shipped configs' (31, 24, 37 x 6).  The object owns
+    the zeroed state tensor and persistent output buffers (one set per (B, max_det, max_ended): a later ``update`` of the same
+    shape overwrites what the earlier one returned).  ``yolov6.utils.track.PlateTrackerNp`` is the same computation on the
+    CPU, bit for bit."""
+
+    def __init__(self, n_streams, max_tracks=64, match_thres=0.3, new_thres=0.0, expand=0.5, max_age=5, ncls=None, device=None):
+        from yolov6.utils import track
+        track.check_params(n_streams, max_tracks, match_thres, new_thres, expand, max_age)
+        self.n_streams, self.max_tracks, self.max_age = int(n_streams), int(max_tracks), int(max_age)
+        self.ncls = track.ncls_of(ncls)
+        dev = torch.device('cuda' if device is None else device)
+        if dev.type != 'cuda':
+            raise ValueError('PlateTracker runs on a GPU (PlateTrackerNp is the CPU form)')
+        self.device = torch.device('cuda', torch.cuda.current_device() if dev.index is None else dev.index)
+        self._params = abi.TrackParams(float(match_thres), float(new_thres), float(expand), self.max_age, (ctypes.c_int * 8)(*self.ncls))
+        lib = abi.load()
+        self._words = lib.lp_track_state_bytes(1, self.max_tracks) // 4
+        self.state = torch.zeros(self.n_streams * self._words, dtype=torch.int32, device=self.device)
+        self._drop_word = lib.lp_track_dropped_offset(self.max_tracks, 0) // 4
+        self._out = {}
+
+    def reset(self, streams=None):
+        """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0."""
+        if streams is None:
+            self.state.zero_()
+        else:
+            for s in streams:
+                self.state.view(self.n_streams, self._words)[int(s)].zero_()
+
+    @property
+    def dropped(self):
+        """int32 [n_streams] view of the state: rows that found no free slot since the last reset (on the device)."""
+        return self.state.view(self.n_streams, self._words)[:, self._drop_word]
+
+    def update(self, det, count, stream_of=None, flush=None, max_ended=None):
+        """``B`` frames: det [B,max_det,28] fp32 + count [B] int32 on the device (``detect_frames_padded`` /
+        ``detect_tiled_padded`` / ``nms_padded`` layout); ``stream_of[b]`` (host ints, default ``range(B)``: one frame from
+        each of B cameras) names the stream of frame b or is -1 for a frame that is not tracked; ``flush[s]`` ends the live
+        tracks of stream s after its frames.  Returns (det_out [B,max_det,28], tid [B,max_det] int32, ended_i
+        [S,max_ended,12] int32, ended_f [S,max_ended,12] fp32, ended_count [S] int32), all on the device, no host read: det_out
+        is det with the class columns of every tracked row replaced by its track's voted read (columns 12..19 the vote
+        shares, 20..27 the voted ids), tid the track id per row (-1: untracked), ended_* the tracks that ended in this call
+        (id, first, last, hits, ids | shares, last box), ``max_ended`` per stream (default ``max_tracks``)."""
+        from yolov6.utils import track
+        _check_det_count(det, count)
+        if det.device != self.device:
+            raise ValueError('det must be on the tracker\'s device %s' % self.device)
+        B, max_det, S = det.shape[0], det.shape[1], self.n_streams
+        stream_of, flush, max_ended = track.check_call(S, B, stream_of, flush, self.max_tracks if max_ended is None else max_ended)
+        out = self.buffers(B, max_det, max_ended)
+        det_out, tid, ended_i, ended_f, ended_count = out
+        so = (ctypes.c_int * max(B, 1))(*stream_of)
+        fl = (ctypes.c_ubyte * S)(*flush)
+        with torch.cuda.device(self.device):
+            abi.check(abi.load().lp_track_update(_dptr(self.state), S, self.max_tracks, ctypes.byref(self._params), _dptr(det), _dptr(count),
+                                                 B, max_det, so, ctypes.cast(fl, ctypes.c_void_p), _dptr(det_out), _dptr(tid),
+                                                 _dptr(ended_i), _dptr(ended_f), _dptr(ended_count), max_ended,
+                                                 _stream_ptr(self.device)), 'lp_track_update')
+        return out
+
+    def buffers(self, B, max_det, max_ended=None):
+        """The persistent outputs of an ``update`` of B frames of max_det rows: (det_out, tid, ended_i, ended_f, ended_count)."""
+        S, dev = self.n_streams, self.device
+        key = (int(B), int(max_det), self.max_tracks if max_ended is None else int(max_ended))
+        out = self._out.get(key)
+        if out is None:
+            out = self._out[key] = (torch.empty(key[0], key[1], abi.LP_DET_COLS, dtype=torch.float32, device=dev),
+                                    torch.empty(key[0], key[1], dtype=torch.int32, device=dev),
+                                    torch.empty(S, key[2], 12, dtype=torch.int32, device=dev),
+                                    torch.empty(S, key[2], 12, dtype=torch.float32, device=dev),
+                                    torch.empty(S, dtype=torch.int32, device=dev))
+        return out
+
+    def flush_all(self, max_det=1, max_ended=None):
+        """End every live track of every stream: ``update`` of zero frames with every flush flag set."""
+        det = torch.empty(0, int(max_det), abi.LP_DET_COLS, dtype=torch.float32, device=self.device)
+        count = torch.empty(0, dtype=torch.int32, device=self.device)
+        return self.update(det, count, stream_of=[], flush=[1] * self.n_streams, max_ended=max_ended)
+
+
 def eval_counts(det, det_count, tgt, tgt_count, counts=None):
     """Counters of the LP accuracy metric for one batch (``lp_eval_counts``): det [B,max_det,28] fp32 + det_count [B]
     int32 as ``nms_padded`` returns them, tgt [B,max_t,20] fp32 + tgt_count [B] int32; ``counts`` (int64 [43], CUDA) is

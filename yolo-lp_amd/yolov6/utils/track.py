@@ -1,0 +1,324 @@
+"""Plate tracking across video frames with a per-track vote over the eight character heads, on the CPU:
+``PlateTrackerNp`` is the written-down specification of ``lp_track_update`` (include/lp_hip.h, csrc/lp_track.hip), which
+matches it bit for bit, and the CPU path of ``Inferer(track=True)``.  Everything is fp32, evaluated op by op in the kernel's
+order (no fused multiply-add).
+
+The reference has nothing here: its Inferer treats video frames independently (yolov6/core/inferer.py).
+
+Rules, per frame of one stream (``det`` [max_det, 28] and ``count`` as lp_nms / lp_rescale_round_batch leave them; only the first
+n = min(max(count, 0), max_det, MAX_DETS) rows take part):
+  1. predict: every live slot's box is shifted by (vx * k, vy * k), k = (float)(misses + 1); product rounded, then the add;
+  2. expand: the predicted box and every detection box grow by e = (float)expand * w on both sides in x, likewise in y;
+  3. pairs: IoU of every (live slot, row) on the expanded boxes with the fp32 ops of ``yolov6.utils.tiles.overlaps`` ('iou');
+     a pair exists iff (double)iou > match_thres.  The pairs are ordered by ``tiles._sort_keys(iou, slot * 128 + row)``
+     (descending IoU, ties by slot, then row) and taken greedily while slot and row are both free;
+  4. a matched slot: vx = (cx_new - cx_old) / k with cx = (x1 + x2) * 0.5f on the stored (unexpanded) box, vy likewise; box and
+     corners become the row's columns 0..11; hits += 1, misses = 0, last = frame; it votes (7);
+  5. an unmatched live slot: misses += 1; misses > max_age ends the track (its record is appended to the stream's ended list,
+     the slot is freed: all-zero), in ascending slot order;
+  6. unmatched rows in row order: score = (c12 + ... + c19) / 8.0f summed left to right (nms.py:120); with
+     (double)score >= new_thres the lowest free slot (those freed in 5 included) becomes a new track: id = next_id++,
+     first = last = frame, hits = 1, misses = 0, zero velocity, zero votes, then it votes.  No free slot: the row stays
+     untracked and the stream's ``dropped`` counter goes up;
+  7. vote, per head p: v = c[20 + p], conf = c[12 + p]; iff conf > 0 and 0 <= v < ncls[p] (float compares: false for NaN):
+     votes[p][(int)v] += conf, total[p] += conf;
+  8. read of a track: best_p = first index of the largest votes[p][0 .. ncls[p]) (0 for an all-zero head),
+     share_p = votes[p][best_p] / total[p] if total[p] > 0 else 0;
+  9. outputs: tid[r] = the track id of a matched or new row, -1 for every other r < max_det; det_out[r] = the row with columns
+     12..19 replaced by the track's shares and 20..27 by (float)best_p, read after this frame's vote; other rows below
+     min(max(count, 0), max_det) are copied, rows at or past it are zero;
+ 10. the stream's frame counter goes up.
+"""
+import numpy as np
+
+from yolov6.utils.tiles import _sort_keys
+
+DET_COLS = 28
+MAX_TRACKS = 128          # LP_TRACK_MAX_TRACKS: slots per stream
+MAX_DETS = 128            # LP_TRACK_MAX_DETS: rows of a frame that take part (128 x 128 pair keys are sorted in LDS)
+MAX_CLS = 64              # LP_TRACK_MAX_CLS: classes per head
+HEADS = 8
+ENDED_COLS = 12           # ended_i: id, first, last, hits, best_0..7; ended_f: share_0..7, x1, y1, x2, y2
+DEFAULT_NCLS = (31, 24, 37, 37, 37, 37, 37, 37)
+f32 = np.float32
+
+
+def ncls_of(model=None):
+    """The eight head widths (npro, nalp, nads x 6): of a model (its ``detect`` head), a sequence of eight, or the shipped
+    configs' (31, 24, 37, ...) for None."""
+    if model is None:
+        return DEFAULT_NCLS
+    if isinstance(model, (tuple, list, np.ndarray)):
+        out = tuple(int(v) for v in model)
+    else:
+        head = getattr(model, 'detect', None)
+        if head is None:
+            head = getattr(getattr(model, 'model', None), 'detect', None)
+        if head is None:
+            raise ValueError('ncls: expected eight widths or a model with a detect head')
+        out = (int(head.npro), int(head.nalp)) + (int(head.nads),) * 6
+    if len(out) != HEADS or not all(1 <= v <= MAX_CLS for v in out):
+        raise ValueError('ncls must be eight widths in 1..%d' % MAX_CLS)
+    return out
+
+
+def check_params(n_streams, max_tracks, match_thres, new_thres, expand, max_age):
+    """The argument rules of lp_track_update's parameters (ValueError)."""
+    if int(n_streams) < 1:
+        raise ValueError('n_streams must be >= 1')
+    if not 1 <= int(max_tracks) <= MAX_TRACKS:
+        raise ValueError('max_tracks must be in 1..%d' % MAX_TRACKS)
+    if not 0.0 <= match_thres <= 1.0:
+        raise ValueError('match_thres must be in [0, 1]')
+    if not abs(new_thres) <= 3.0e38:
+        raise ValueError('new_thres must be finite (|new_thres| <= 3e38)')
+    if not 0.0 <= expand <= 1.0e6:
+        raise ValueError('expand must be in [0, 1e6]')
+    if int(max_age) < 0:
+        raise ValueError('max_age must be >= 0')
+
+
+def check_call(n_streams, B, stream_of, flush, max_ended):
+    """(stream_of list [B], flush list [n_streams], max_ended) of one update call, checked."""
+    stream_of = list(range(B)) if stream_of is None else [int(v) for v in stream_of]
+    if len(stream_of) != B:
+        raise ValueError('stream_of must name the stream of each of the %d frames' % B)
+    for b, s in enumerate(stream_of):
+        if not -1 <= s < n_streams:
+            raise ValueError('stream %d of frame %d: need -1 (skip) or 0..%d' % (s, b, n_streams - 1))
+    flush = [0] * n_streams if flush is None else [int(bool(v)) for v in flush]
+    if len(flush) != n_streams:
+        raise ValueError('flush must have one entry per stream')
+    if int(max_ended) < 0:
+        raise ValueError('max_ended must be >= 0')
+    return stream_of, flush, int(max_ended)
+
+
+def expand_boxes(box, e):
+    """Boxes [..., 4] fp32 grown by e * width on both sides in x and e * height in y (``e`` fp32)."""
+    box = np.asarray(box, f32)
+    with np.errstate(all='ignore'):
+        ex = e * (box[..., 2] - box[..., 0])
+        ey = e * (box[..., 3] - box[..., 1])
+        out = np.stack([box[..., 0] - ex, box[..., 1] - ey, box[..., 2] + ex, box[..., 3] + ey], -1)
+    assert out.dtype == f32
+    return out
+
+
+def iou_matrix(a, b):
+    """fp32 [K, N]: inter / (area_i + area_j - inter) of boxes a [K,4] (i) and b [N,4] (j), the ops of ``tiles.overlaps``
+    ('iou') in its order; the quotient itself, which is a sort key here."""
+    a, b = np.asarray(a, f32).reshape(-1, 4), np.asarray(b, f32).reshape(-1, 4)
+    ix1, iy1, ix2, iy2 = (a[:, k][:, None] for k in range(4))
+    jx1, jy1, jx2, jy2 = (b[:, k][None, :] for k in range(4))
+    with np.errstate(all='ignore'):
+        xx1 = np.where(ix1 > jx1, ix1, jx1)
+        yy1 = np.where(iy1 > jy1, iy1, jy1)
+        xx2 = np.where(ix2 < jx2, ix2, jx2)
+        yy2 = np.where(iy2 < jy2, iy2, jy2)
+        w = xx2 - xx1
+        w = np.where(w > 0, w, f32(0))
+        h = yy2 - yy1
+        h = np.where(h > 0, h, f32(0))
+        inter = w * h
+        iarea = (ix2 - ix1) * (iy2 - iy1)
+        jarea = (jx2 - jx1) * (jy2 - jy1)
+        ovr = inter / (iarea + jarea - inter)
+    assert ovr.dtype == f32
+    return ovr
+
+
+def plate_text(ids, pro_names=None, alp_names=None, ads_names=None):
+    """The plate string of eight head ids (province, alphabet, six characters) with the three name lists of a data yaml
+    (``names`` / ``alps`` / ``ads``); without names, or for an id outside its list, the ids joined by spaces."""
+    ids = [int(v) for v in ids]
+    if len(ids) != HEADS:
+        raise ValueError('plate_text needs eight ids')
+    if pro_names and alp_names and ads_names:
+        lists = [pro_names, alp_names] + [ads_names] * 6
+        if all(0 <= i < len(names) for i, names in zip(ids, lists)):
+            return ''.join(str(names[i]) for i, names in zip(ids, lists))
+    return ' '.join(str(i) for i in ids)
+
+
+class PlateTrackerNp:
+    """``n_streams`` independent trackers of ``max_tracks`` slots each (the module docstring states the rules).  Same
+    constructor and ``update`` as ``yolov6.hip.runtime.PlateTracker``, on numpy arrays; ``device`` is ignored."""
+
+    def __init__(self, n_streams, max_tracks=64, match_thres=0.3, new_thres=0.0, expand=0.5, max_age=5, ncls=None, device=None):
+        check_params(n_streams, max_tracks, match_thres, new_thres, expand, max_age)
+        self.n_streams, self.max_tracks, self.max_age = int(n_streams), int(max_tracks), int(max_age)
+        self.match_thres, self.new_thres, self.expand = float(match_thres), float(new_thres), float(expand)
+        self.ncls = ncls_of(ncls)
+        S, T = self.n_streams, self.max_tracks
+        self.frame = np.zeros(S, np.int32)
+        self.next_id = np.zeros(S, np.int32)
+        self.dropped = np.zeros(S, np.int32)            # rows that found no free slot, since the last reset
+        self.id, self.first, self.last, self.hits, self.misses = (np.zeros((S, T), np.int32) for _ in range(5))
+        self.box = np.zeros((S, T, 4), f32)
+        self.cor = np.zeros((S, T, 8), f32)
+        self.vel = np.zeros((S, T, 2), f32)
+        self.votes = np.zeros((S, T, HEADS, MAX_CLS), f32)
+        self.total = np.zeros((S, T, HEADS), f32)
+        #: counters for tests and diagnostics (no part of the state): pairs above the threshold, pairs sharing their IoU
+        #: with another pair of the frame, pairs taken, tracks ended
+        self.stats = dict(pairs=0, ties=0, matched=0, ended=0)
+
+    _SLOT_ARRAYS = ('id', 'first', 'last', 'hits', 'misses', 'box', 'cor', 'vel', 'votes', 'total')
+
+    def reset(self, streams=None):
+        """Zero the state of ``streams`` (all streams for None): no tracks, frame counter, next id and dropped at 0."""
+        for s in (range(self.n_streams) if streams is None else streams):
+            for name in self._SLOT_ARRAYS + ('frame', 'next_id', 'dropped'):
+                getattr(self, name)[s] = 0
+
+    def live(self, s):
+        """bool [max_tracks]: the live slots of stream ``s``."""
+        return self.hits[s] > 0
+
+    def read(self, s, t):
+        """(best int32 [8], share fp32 [8]) of slot ``t`` of stream ``s`` (rule 8)."""
+        best, share = np.zeros(HEADS, np.int32), np.zeros(HEADS, f32)
+        for p in range(HEADS):
+            v = self.votes[s, t, p, :self.ncls[p]]
+            best[p] = int(np.argmax(v))              # first index of the largest (the votes are never NaN)
+            tot = self.total[s, t, p]
+            with np.errstate(all='ignore'):
+                share[p] = v[best[p]] / tot if tot > 0 else f32(0)
+        return best, share
+
+    def _vote(self, s, t, row):
+        for p in range(HEADS):
+            v, conf = row[20 + p], row[12 + p]
+            if conf > 0 and v >= 0 and v < f32(self.ncls[p]):
+                with np.errstate(all='ignore'):
+                    self.votes[s, t, p, int(v)] = self.votes[s, t, p, int(v)] + conf
+                    self.total[s, t, p] = self.total[s, t, p] + conf
+
+    def _end(self, s, t, ended):
+        best, share = self.read(s, t)
+        self.stats['ended'] += 1
+        ended.append((np.concatenate([[self.id[s, t], self.first[s, t], self.last[s, t], self.hits[s, t]], best]).astype(np.int32),
+                      np.concatenate([share, self.box[s, t]]).astype(f32)))
+        for name in self._SLOT_ARRAYS:
+            getattr(self, name)[s, t] = 0
+
+    def _frame(self, s, rows, count, ended):
+        """One frame of stream ``s``: (det_out [max_det, 28], tid [max_det])."""
+        T, max_det = self.max_tracks, rows.shape[0]
+        nc = min(max(int(count), 0), max_det)
+        n = min(nc, MAX_DETS)
+        frame = int(self.frame[s])
+        e = f32(self.expand)
+        live = self.live(s)
+        slot_row = np.full(T, -1, np.int64)
+        row_slot = np.full(n, -1, np.int64)
+        kf = (self.misses[s] + 1).astype(f32)
+        if n and live.any():
+            with np.errstate(all='ignore'):
+                dx, dy = self.vel[s, :, 0] * kf, self.vel[s, :, 1] * kf
+                b = self.box[s]
+                pred = np.stack([b[:, 0] + dx, b[:, 1] + dy, b[:, 2] + dx, b[:, 3] + dy], -1)
+            iou = iou_matrix(expand_boxes(pred, e), expand_boxes(rows[:n, :4], e))
+            pair = live[:, None] & (iou.astype(np.float64) > self.match_thres)
+            sl, rw = np.nonzero(pair)
+            self.stats['pairs'] += len(sl)
+            self.stats['ties'] += len(sl) - len(np.unique(iou[sl, rw]))
+            for i in np.argsort(_sort_keys(iou[sl, rw], sl * MAX_DETS + rw), kind='stable'):
+                if slot_row[sl[i]] < 0 and row_slot[rw[i]] < 0:
+                    slot_row[sl[i]], row_slot[rw[i]] = rw[i], sl[i]
+                    self.stats['matched'] += 1
+        for t in np.nonzero(live)[0]:
+            r = slot_row[t]
+            if r >= 0:
+                row, b = rows[r], self.box[s, t]
+                with np.errstate(all='ignore'):
+                    self.vel[s, t, 0] = ((row[0] + row[2]) * f32(0.5) - (b[0] + b[2]) * f32(0.5)) / kf[t]
+                    self.vel[s, t, 1] = ((row[1] + row[3]) * f32(0.5) - (b[1] + b[3]) * f32(0.5)) / kf[t]
+                self.box[s, t], self.cor[s, t] = row[0:4], row[4:12]
+                self.hits[s, t] += 1
+                self.misses[s, t] = 0
+                self.last[s, t] = frame
+                self._vote(s, t, row)
+            else:
+                self.misses[s, t] += 1
+                if self.misses[s, t] > self.max_age:
+                    self._end(s, t, ended)
+        for r in range(n):
+            if row_slot[r] >= 0:
+                continue
+            row = rows[r]
+            with np.errstate(all='ignore'):
+                score = row[12] + row[13]
+                for c in range(14, 20):
+                    score = score + row[c]
+                score = score / f32(8.0)
+            if not np.float64(score) >= self.new_thres:
+                continue
+            free = np.nonzero(~self.live(s))[0]
+            if not len(free):
+                self.dropped[s] += 1
+                continue
+            t = free[0]
+            for name in self._SLOT_ARRAYS:
+                getattr(self, name)[s, t] = 0
+            self.id[s, t] = self.next_id[s]
+            self.next_id[s] += 1
+            self.first[s, t] = self.last[s, t] = frame
+            self.hits[s, t] = 1
+            self.box[s, t], self.cor[s, t] = row[0:4], row[4:12]
+            self._vote(s, t, row)
+            row_slot[r] = t
+        det_out = np.zeros_like(rows)
+        det_out[:nc] = rows[:nc]
+        tid = np.full(max_det, -1, np.int32)
+        for r in range(n):
+            t = row_slot[r]
+            if t >= 0:
+                best, share = self.read(s, t)
+                det_out[r, 12:20], det_out[r, 20:28], tid[r] = share, best.astype(f32), self.id[s, t]
+        self.frame[s] += 1
+        return det_out, tid
+
+    def flush_all(self, max_det=1, max_ended=None):
+        """End every live track of every stream: ``update`` of zero frames with every flush flag set."""
+        return self.update(np.zeros((0, int(max_det), DET_COLS), f32), np.zeros(0, np.int32), stream_of=[], flush=[1] * self.n_streams,
+                           max_ended=max_ended)
+
+    def update(self, det, count, stream_of=None, flush=None, max_ended=None):
+        """``B`` frames: det [B, max_det, 28] fp32 and count [B]; ``stream_of[b]`` names the stream of frame b (default
+        ``range(B)``; -1: the frame is not tracked, its rows below the count are copied and its tid is -1); the frames of a
+        stream are taken in ascending b.  After its frames a stream with ``flush[s]`` ends all its live tracks in slot order.
+        Returns (det_out [B,max_det,28], tid [B,max_det] int32, ended_i [S,max_ended,12] int32, ended_f [S,max_ended,12] fp32,
+        ended_count [S] int32): per stream the first ``max_ended`` (default ``max_tracks``) records that ended in this call,
+        records past them zero; ``ended_count`` is the number that ended and may exceed ``max_ended``."""
+        det = np.ascontiguousarray(det, dtype=f32)
+        if det.ndim != 3 or det.shape[2] != DET_COLS or det.shape[1] < 1:
+            raise ValueError('det must be [B, max_det >= 1, 28]')
+        B, max_det = det.shape[:2]
+        count = np.asarray(count).astype(np.int64).reshape(-1)
+        if len(count) != B:
+            raise ValueError('count must be [B]')
+        S = self.n_streams
+        stream_of, flush, max_ended = check_call(S, B, stream_of, flush, self.max_tracks if max_ended is None else max_ended)
+        det_out = np.zeros_like(det)
+        tid = np.full((B, max_det), -1, np.int32)
+        ended = [[] for _ in range(S)]
+        for b, s in enumerate(stream_of):
+            if s < 0:
+                nc = min(max(int(count[b]), 0), max_det)
+                det_out[b, :nc] = det[b, :nc]
+            else:
+                det_out[b], tid[b] = self._frame(s, det[b], count[b], ended[s])
+        for s in range(S):
+            if flush[s]:
+                for t in np.nonzero(self.live(s))[0]:
+                    self._end(s, t, ended[s])
+        ended_i = np.zeros((S, max_ended, ENDED_COLS), np.int32)
+        ended_f = np.zeros((S, max_ended, ENDED_COLS), f32)
+        ended_count = np.zeros(S, np.int32)
+        for s in range(S):
+            ended_count[s] = len(ended[s])
+            for k, (ri, rf) in enumerate(ended[s][:max_ended]):
+                ended_i[s, k], ended_f[s, k] = ri, rf
+        return det_out, tid, ended_i, ended_f, ended_count
