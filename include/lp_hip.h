@@ -397,6 +397,14 @@ int lp_track_update(void* state, int n_streams, int max_tracks, const lp_track_p
                     const int* stream_of /* HOST [B] */, const unsigned char* flush /* HOST [n_streams] or NULL */,
                     float* det_out, int32_t* tid, int32_t* ended_i, float* ended_f, int32_t* ended_count,
                     int max_ended, void* stream);
+/* lp_track_update_slots: lp_track_update (which is this call with slot = NULL) that also reports where each row's track lives:
+ * slot [B,max_det] int32 (DEVICE, may be NULL), slot[r] = the tracker slot (0..max_tracks-1) of a matched or new row's track, -1
+ * wherever tid[r] is -1.  A slot holds one track at a time, so it indexes per-track side tables (lp_best_shot_update). */
+int lp_track_update_slots(void* state, int n_streams, int max_tracks, const lp_track_params* p,
+                          const float* det, const int32_t* count, int B, int max_det,
+                          const int* stream_of /* HOST [B] */, const unsigned char* flush /* HOST [n_streams] or NULL */,
+                          float* det_out, int32_t* tid, int32_t* slot, int32_t* ended_i, float* ended_f, int32_t* ended_count,
+                          int max_ended, void* stream);
 
 /* lp_plate_crops_batch: perspective-rectified plate crops of B frames' detections (the inverse of the warp of the reference's
  * plate generator, yolov6/data/generate/generate.py:566-586), one launch per LP_FRAMES_PER_LAUNCH frames; descriptors travel
@@ -425,6 +433,62 @@ typedef struct lp_crop_desc {
 } lp_crop_desc;
 int lp_plate_crops_batch(const lp_crop_desc* desc, int n_frames, const float* det, const int32_t* count, int max_det,
                          unsigned char* out, int32_t* status, int n_slots, int crop_h, int crop_w, void* stream);
+
+/* lp_crop_sharpness: the Laplacian energy of plate crops, an integer per crop that ranks the frames of one track by focus.
+ *   crops [n_slots,crop_h,crop_w,3] uint8 BGR + status [n_slots] int32 as lp_plate_crops_batch leaves them (DEVICE); sharp
+ *   [n_slots] unsigned 64-bit (DEVICE, 8-byte aligned).  For a slot with status 1 or 2:
+ *     g = (29 * B + 150 * G + 77 * R + 128) >> 8 per pixel;
+ *     L = 4 g(i,j) - g(i-1,j) - g(i+1,j) - g(i,j-1) - g(i,j+1) on the interior 1 <= i <= crop_h-2, 1 <= j <= crop_w-2;
+ *     sharp = the sum of L * L (|L| <= 1020: a 64 x 192 checkerboard of 0 / 255 gives 12255912000 > 2^32).
+ *   sharp = 0 for status 0 or 3, or when a side is shorter than 3.  One workgroup per slot, no atomics; all integer, so the
+ *   result does not depend on the order of the sum.  yolov6/utils/best_shot.py::crop_sharpness_np restates it.
+ *   Sensor noise raises the measure as focus does: it ranks the frames of one track and is not comparable across cameras. */
+int lp_crop_sharpness(const unsigned char* crops, const int32_t* status, int n_slots, int crop_h, int crop_w,
+                      unsigned long long* sharp, void* stream);
+
+/* lp_best_shot_update: the sharpest rectified crop of every live plate track, kept on the device and handed out next to the
+ * track's record when the track ends.  Called right behind lp_track_update_slots, lp_plate_crops_batch and lp_crop_sharpness
+ * of the same frames; the frame table travels as kernel arguments (one launch per LP_FRAMES_PER_LAUNCH frames, one workgroup per
+ * stream, plus one closing launch): nothing is uploaded, no host sync, capturable in a graph.  The reference has nothing here;
+ * yolov6/utils/best_shot.py::BestShotNp restates the rules below bit for bit.
+ *   state: DEVICE, 16-byte aligned, lp_best_shot_state_bytes(n_streams, max_tracks, crop_h, crop_w) bytes, all zero = empty (the
+ *   caller zeroes it once; zeroing a stream's lp_best_shot_state_bytes(1, ...) bytes resets that stream).  Per stream: its own
+ *   frame counter and max_tracks entries indexed by the tracker's slot, each id + 1 (0 = empty), a has-shot flag, a 64-bit key,
+ *   the frame, row and status of the shot, its det row and the crop bytes (16-byte aligned).
+ *   det [B,max_det,28] + count [B]: the rows GIVEN to the tracker (their raw per-frame confidences); tid, slot [B,max_det] as
+ *   lp_track_update_slots wrote them; crops [B,max_crops,crop_h,crop_w,3], status [B,max_crops], sharp [B,max_crops] as
+ *   lp_plate_crops_batch (frame b's slots at b * max_crops) and lp_crop_sharpness wrote them; stream_of: HOST int [B], as given to
+ *   the tracker; ended_i [n_streams,max_ended,12] + ended_count [n_streams] as that tracker call wrote them (all DEVICE).
+ *   Outputs (DEVICE): shot_crops [n_streams,max_ended,crop_h,crop_w,3] uint8, shot_i [n_streams,max_ended,4] int32 = frame, row,
+ *   status, valid; shot_q [n_streams,max_ended] unsigned 64-bit = the shot's sharpness; shot_det [n_streams,max_ended,28] fp32 =
+ *   its det row.  The call first zeroes shot_i, shot_q and shot_det; the crop bytes of a record without a shot are left as
+ *   they were (the convention of lp_plate_crops_batch's status 0).
+ * Per stream the frames are taken in ascending b (stream_of -1: skipped):
+ *   1. rows r < min(max(count, 0), max_det, max_crops, LP_TRACK_MAX_DETS) with tid[r] >= 0 take part, g = slot[r] (a row whose
+ *      slot is outside 0..max_tracks-1 is skipped);
+ *   2. if entry g holds another id it is retired (5); an entry that does not hold id becomes {id + 1, no shot};
+ *   3. the row is eligible iff status[r] is 1 or 2 and (double)score >= min_score, score = (c12 + ... + c19) / 8.0f summed left
+ *      to right in fp32 as lp_track_update's rule 6 (false for NaN);
+ *   4. key = ((status == 1) << 63) | sharp[r]: a crop cut along the corners beats one cut along the box.  The row becomes the
+ *      entry's shot iff the entry has none or key > the entry's key (strict: the earlier frame keeps a tie); that copies the crop,
+ *      the det row, the stream's frame counter, r, status and key into the entry;
+ *   5. retire entry g: e = the first index < min(ended_count[s], max_ended) with ended_i[s][e][0] == the entry's id; if there is
+ *      one and the entry has a shot: shot_crops[s][e] = its crop, shot_i[s][e] = (frame, row, status, 1), shot_q[s][e] = the key
+ *      without its top bit, shot_det[s][e] = its det row.  Either way the entry becomes empty (an occupant whose record was cut
+ *      off by max_ended is dropped silently);
+ *   6. the stream's frame counter goes up.  After the stream's last frame (also for a stream without frames in the call) every
+ *      non-empty entry whose id is among the call's records is retired, in slot order.  Live tracks stay.
+ * Every argument is checked before the first launch (LP_ERR_ARG): n_streams >= 1, max_tracks in 1..LP_TRACK_MAX_TRACKS, crop
+ * sides in 1..1024, B >= 0, max_det >= 1, max_crops >= 0, max_ended >= 0, |min_score| <= 3e38, stream_of[b] in -1..n_streams-1,
+ * the alignment of state, sharp and shot_q, and the pointers (crops, status, sharp may be NULL when B == 0 or max_crops == 0; the
+ * record arrays when max_ended == 0). */
+size_t lp_best_shot_state_bytes(int n_streams, int max_tracks, int crop_h, int crop_w);   /* 0: bad arguments */
+int lp_best_shot_update(void* state, int n_streams, int max_tracks, int crop_h, int crop_w,
+                        const float* det, const int32_t* count, int B, int max_det, const int32_t* tid, const int32_t* slot,
+                        const unsigned char* crops, const int32_t* status, const unsigned long long* sharp, int max_crops,
+                        const int* stream_of /* HOST [B] */, const int32_t* ended_i, const int32_t* ended_count, int max_ended,
+                        double min_score, unsigned char* shot_crops, int32_t* shot_i, unsigned long long* shot_q, float* shot_det,
+                        void* stream);
 
 /* lp_eval_counts: the matching loops of Evaler.eval (yolov6/core/evaler.py:153-243, box_iou general.py:93-115) for a
  * batch of images, one workgroup per image.

@@ -5,7 +5,7 @@
                                  [--crops N]
     python tools/frames_bench.py --tile [--tile-baseline] [--tile-frame 2160 3840] [--tile-size 640] [--tile-overlap 128]
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
-    python tools/frames_bench.py --track [--track-batch 32] [--runs 3]
+    python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot]
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
   - frames/s of the per-frame path (upload, lp_preprocess_letterbox, detect at B=1 with hipGraph replay, lp_rescale_round,
@@ -28,6 +28,10 @@ frames/s of FrameBatcher + ``detect_frames`` alone and of ``detect_frames_padded
 of the voted rows and track ids, ``--runs`` timed runs each in the same process, alternating; the device time of the update
 from events (median of ``--reps``) next to the detect stage of the same chain, at the bench's own detection density; and the
 update alone on a full frame per stream (128 live tracks x 128 rows, every pair above the threshold: 16384 sorted keys).
+``--best-shot`` adds the best-shot stages of ``PlateTracker.update_with_shots`` to that event chain, right behind the update:
+plate crops (16 slots of 64x192 per frame), lp_crop_sharpness and lp_best_shot_update, each from events, at the bench's own
+detection density; and a worst case on 16 constant rows per stream whose sharpness is made to grow with every call, so that
+every row of every frame replaces its shot (16 x 36 KB copied per stream by one workgroup).
 The model is the synthetic recipe of bench.py (same weights scale), prepared as Inferer prepares it.
 """
 import argparse
@@ -69,6 +73,7 @@ def parse():
     ap.add_argument('--tile-batch', type=int, default=32, help='tiles per forward')
     ap.add_argument('--track', action='store_true', help='measure plate tracking (PlateTracker.update behind detect_frames) instead')
     ap.add_argument('--track-batch', type=int, default=32, help='with --track: camera streams = frames per step')
+    ap.add_argument('--best-shot', action='store_true', help='with --track: also time crops + sharpness + gallery behind the update')
     ap.add_argument('--runs', type=int, default=3, help='timed runs of the frames/s figures (the spread is reported)')
     return ap.parse_args()
 
@@ -240,6 +245,9 @@ def track_mode(args, model, dev, tdt):
         out['detections_per_frame'] = count.clamp(0, max_det).cpu().tolist()
         out['live_tracks_per_stream'] = (trk.state.view(B, -1)[:, 16:].view(B, 128, -1)[:, :, 3] > 0).sum(1).cpu().tolist()
 
+        if args.best_shot:
+            out['best_shot'] = best_shot_stages(args, model, dev, tdt, frames, x, (H, W))
+
         # the full case: 128 live tracks x 128 rows per stream, every pair above the threshold
         full = runtime.PlateTracker(B, max_tracks=128, max_age=0, ncls=model, device=dev)
         rows = np.zeros((B, 128, 28), np.float32)
@@ -261,6 +269,73 @@ def track_mode(args, model, dev, tdt):
         out['full_128x128_ms'] = round(float(np.median(ms[1:])), 4)
         out['full_128x128_matched'] = int((tid >= 0).sum())
     print(json.dumps(out))
+
+
+def best_shot_stages(args, model, dev, tdt, frames, x, net_hw):
+    """--track --best-shot: device time of tracker, crops, sharpness and gallery behind detect, from events on one stream."""
+    import torch
+    from yolov6.hip import runtime
+    size, stride = [args.size, args.size], int(model.stride.max())
+    B, conf, iou, max_det = args.track_batch, args.conf, args.iou, args.max_det
+    h0, w0 = args.frame
+    so = list(range(B))
+    names = ('detect', 'track', 'crops', 'sharpness', 'gallery')
+
+    def chain(trk, det_count=None, grow=None):
+        """One pass; ``det_count``: fixed rows instead of the detector's; ``grow``: overwrite the sharpness by this value."""
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        xx, _ = runtime.preprocess_frames(frames, size, stride, tdt, batch=B, out=x)
+        ev[0].record()
+        det, count, _ = runtime.detect_padded(model, xx, conf, iou, max_det)
+        runtime.rescale_round_batch(det, count, net_hw, [f.shape for f in frames])
+        ev[1].record()
+        if det_count is not None:
+            det, count = det_count
+        trk.update(det, count)
+        ev[2].record()
+        crops, status, sharp = trk._shot_crops(frames, det, count, so, trk.max_tracks)
+        ev[3].record()
+        runtime.crop_sharpness(crops, status, out=sharp)
+        if grow is not None:
+            sharp.fill_(grow)
+        ev[4].record()
+        shot_i = trk._shot_gallery(det, count, so, trk.max_tracks)[1]
+        ev[5].record()
+        torch.cuda.synchronize()
+        return [ev[k].elapsed_time(ev[k + 1]) for k in range(5)], count
+
+    def summary(runs):
+        a = np.array(runs[1:])
+        return {n: dict(median=round(float(np.median(a[:, k])), 4), min=round(float(a[:, k].min()), 4), max=round(float(a[:, k].max()), 4))
+                for k, n in enumerate(names)}
+
+    res = {}
+    trk = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
+    trk.enable_best_shot((64, 192), max_crops=16)
+    runs = []
+    for _ in range(args.reps + 1):
+        ms, count = chain(trk)
+        runs.append(ms)
+    res['stage_ms'] = summary(runs)
+    res['rows_cropped_per_frame'] = count.clamp(0, 16).cpu().tolist()
+    med = {n: v['median'] for n, v in res['stage_ms'].items()}
+    res['shot_stages_pct_of_detect'] = round(100.0 * (med['crops'] + med['sharpness'] + med['gallery']) / med['detect'], 2)
+    # worst case: 16 constant rows per stream (tracks 0..15 matched in every call), every one replaces its shot in every call
+    worst = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
+    worst.enable_best_shot((64, 192), max_crops=16)
+    rows = synthetic_quads(B, 16, h0, w0, seed=1)
+    rows[:, :, 12:20] = 0.5
+    wdet = torch.from_numpy(rows).to(dev)
+    wcount = torch.full((B,), 16, dtype=torch.int32, device=dev)
+    runs = []
+    for k in range(args.reps + 1):
+        ms, _ = chain(worst, (wdet, wcount), grow=k + 1)
+        runs.append(ms)
+    res['worst_stage_ms'] = summary(runs)
+    res['worst_bytes_copied_per_stream'] = 16 * 64 * 192 * 3
+    state = worst._shots['state'].view(B, -1)[:, 16:].view(B, 128, -1)[:, :16, :32].contiguous().view(torch.int32)
+    res['worst_shots_replaced_last_call'] = int((state[:, :, 4] == args.reps).sum())      # frame index of the shot = the last call
+    return res
 
 
 def synthetic_quads(n_frames, n, h0, w0, seed=0):

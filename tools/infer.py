@@ -4,7 +4,7 @@
     python tools/infer.py --weights weights/yololps.pt --source data/images --yaml data/dataset.yaml [--half]
                           [--batch-size 32] [--fixed-shape] [--save-crops [--crop-size 64 192]]
                           [--tile 640 640 [--tile-overlap 0.2] [--no-tile-overview] [--merge-metric iou|ios]]
-                          [--track [--track-max-age 5] [--track-iou 0.3] [--track-expand 0.5]]
+                          [--track [--track-max-age 5] [--track-iou 0.3] [--track-expand 0.5] [--best-shots [--crop-size 64 192]]]
 """
 import argparse
 import os
@@ -56,6 +56,8 @@ _FLAGS = [
     ('--track-max-age', dict(type=int, default=5, help='frames a track survives unseen')),
     ('--track-iou', dict(type=float, default=0.3, help='IoU (of the expanded boxes) above which a detection continues a track')),
     ('--track-expand', dict(type=float, default=0.5, help='boxes are grown by this fraction of their size on every side before the IoU')),
+    ('--best-shots', dict(action='store_true', help='with --track: keep the sharpest rectified crop (--crop-size) of every track and write '
+                                                    'shots/<line>_<id>.png and shots.txt, line-parallel to plates.txt')),
 ]
 
 
@@ -74,7 +76,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         view_img=True, classes=None, agnostic_nms=False, project=osp.join(ROOT, 'runs/inference'), name='exp',
         hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False, save_crops=False, crop_size=(64, 192),
         tile=None, tile_overlap=0.2, no_tile_overview=False, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3,
-        track_expand=0.5):
+        track_expand=0.5, best_shots=False):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track) and not osp.exists(out_dir):
@@ -87,7 +89,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         tile_overlap = int(tile_overlap)        # pixels
     results = Inferer(source, weights, device, yaml, img_size, half, batch_size=batch_size, auto=not fixed_shape, tile=tile,
                       tile_overlap=tile_overlap, tile_overview=not no_tile_overview, merge_metric=merge_metric, track=track, track_max_age=track_max_age,
-                      track_iou=track_iou, track_expand=track_expand).infer(
+                      track_iou=track_iou, track_expand=track_expand, best_shots=best_shots).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

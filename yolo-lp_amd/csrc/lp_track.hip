@@ -82,11 +82,12 @@ __global__ void track_clear_kernel(int32_t* ended_count, int n_streams, int32_t*
 }
 
 // grid (workgroups of this launch), block (1024), dynamic LDS = n_max keys (8 B), n_max >= max_tracks * min(max_det, 128).
-//   det / count / det_out / tid_out: the launch's first frame; state, ended_*: the whole call's.
+//   det / count / det_out / tid_out / slot_out (may be null): the launch's first frame; state, ended_*: the whole call's.
 __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const TkParams prm, int* __restrict__ state, int T, long long sstride,
                                                     const float* __restrict__ det, const int32_t* __restrict__ count, int max_det,
-                                                    float* __restrict__ det_out, int32_t* __restrict__ tid_out, int32_t* __restrict__ ended_i,
-                                                    float* __restrict__ ended_f, int32_t* __restrict__ ended_count, int max_ended) {
+                                                    float* __restrict__ det_out, int32_t* __restrict__ tid_out, int32_t* __restrict__ slot_out,
+                                                    int32_t* __restrict__ ended_i, float* __restrict__ ended_f, int32_t* __restrict__ ended_count,
+                                                    int max_ended) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long skeys[];
     __shared__ __attribute__((aligned(16))) box4 s_pbox[TK_SLOTS];     // predicted, expanded boxes of the live slots
     __shared__ __attribute__((aligned(16))) box4 s_dbox[TK_ROWS];      // expanded boxes of the rows
@@ -347,12 +348,13 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
             dout[i] = v;
         }
         for (int r = tid; r < max_det; r += TK_T) {
-            int v = -1;
+            int v = -1, slot = -1;
             if (r < n) {
-                const int slot = s_row_slot[r];
+                slot = s_row_slot[r];
                 if (slot >= 0) v = s_id[slot];
             }
             tid_out[(long long)j * max_det + r] = v;
+            if (slot_out) slot_out[(long long)j * max_det + r] = slot;
         }
         __syncthreads();                                               // the next frame reuses the LDS tables and reads the state
     }
@@ -388,6 +390,14 @@ extern "C" size_t lp_track_dropped_offset(int max_tracks, int stream_index) {
 extern "C" int lp_track_update(void* state, int n_streams, int max_tracks, const lp_track_params* p, const float* det, const int32_t* count,
                                int B, int max_det, const int* stream_of, const unsigned char* flush, float* det_out, int32_t* tid,
                                int32_t* ended_i, float* ended_f, int32_t* ended_count, int max_ended, void* stream) {
+    return lp_track_update_slots(state, n_streams, max_tracks, p, det, count, B, max_det, stream_of, flush, det_out, tid, nullptr, ended_i,
+                                 ended_f, ended_count, max_ended, stream);
+}
+
+extern "C" int lp_track_update_slots(void* state, int n_streams, int max_tracks, const lp_track_params* p, const float* det,
+                                     const int32_t* count, int B, int max_det, const int* stream_of, const unsigned char* flush, float* det_out,
+                                     int32_t* tid, int32_t* slot, int32_t* ended_i, float* ended_f, int32_t* ended_count, int max_ended,
+                                     void* stream) {
     const std::string fn = "lp_track_update: ";
     if (n_streams < 1 || max_tracks < 1 || max_tracks > LP_TRACK_MAX_TRACKS)
         return fail(LP_ERR_ARG, fn + "need n_streams >= 1 and max_tracks in 1.." + std::to_string(LP_TRACK_MAX_TRACKS));
@@ -440,8 +450,8 @@ extern "C" int lp_track_update(void* state, int n_streams, int max_tracks, const
     auto launch = [&](const TkTable& tab, int nblk, int b0) -> int {
         hipLaunchKernelGGL(track_kernel, dim3((unsigned)nblk), dim3(TK_T), lds, st, tab, prm, (int*)state, max_tracks, sstride,
                            det ? det + (size_t)b0 * max_det * LP_DET_COLS : nullptr, count ? count + b0 : nullptr, max_det,
-                           det_out ? det_out + (size_t)b0 * max_det * LP_DET_COLS : nullptr, tid ? tid + (size_t)b0 * max_det : nullptr, ended_i,
-                           ended_f, ended_count, max_ended);
+                           det_out ? det_out + (size_t)b0 * max_det * LP_DET_COLS : nullptr, tid ? tid + (size_t)b0 * max_det : nullptr,
+                           slot ? slot + (size_t)b0 * max_det : nullptr, ended_i, ended_f, ended_count, max_ended);
         LP_HIP_CHECK(hipGetLastError());
         return LP_OK;
     };

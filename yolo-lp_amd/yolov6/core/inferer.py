@@ -16,6 +16,8 @@ than the network input, whose plates a single letterbox would shrink away.
 With ``track`` the detections of consecutive frames are associated into plate tracks and every track votes its eight
 characters over its frames (``runtime.PlateTracker`` on a GPU, ``PlateTrackerNp`` on the CPU): ``infer`` returns and saves the
 voted rows and writes ``tracks.txt`` (one line per frame row) and ``plates.txt`` (one line per track).
+With ``best_shots`` every track also keeps the sharpest rectified crop it has shown (``PlateTracker.update_with_shots`` on a GPU,
+``BestShotNp`` on the CPU): ``shots/<line>_<id>.png`` and ``shots.txt``, line-parallel to ``plates.txt``.
 """
 import math
 import os
@@ -35,7 +37,7 @@ from yolov6.utils.nms import non_max_suppression
 
 class Inferer:
     def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True, tile=None, tile_overlap=0.2,
-                 tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5):
+                 tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5, best_shots=False):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -44,8 +46,12 @@ class Inferer:
         ``track``: plate tracking with a per-track character vote (``yolov6.utils.track`` states the rules): every video file is
         one stream, all image files of the source, in ``LoadData``'s order, are one more; a row continues the track whose
         predicted box (grown by ``track_expand`` of its size) it overlaps by more than ``track_iou``, a track unseen for more
-        than ``track_max_age`` frames ends."""
+        than ``track_max_age`` frames ends.
+        ``best_shots`` (with ``track``): every track keeps the sharpest plate crop among the first ``SHOT_ROWS`` rows of its
+        frames (``yolov6.utils.best_shot`` states the rules); ``infer`` writes one image per ended track that has one."""
         self.__dict__.update(locals())
+        if best_shots and not track:
+            raise ValueError('best_shots needs track=True')
         if merge_metric not in ('iou', 'ios'):
             raise ValueError("merge_metric must be 'iou' or 'ios'")
         self.tile = None if tile is None else ((int(tile), int(tile)) if isinstance(tile, int) else (int(tile[0]), int(tile[-1])))
@@ -99,9 +105,14 @@ class Inferer:
         track's read: columns 12..19 the vote shares, 20..27 the voted ids; the geometry is unchanged), and two files are
         written: ``<save_dir>/tracks.txt``, one line ``path row track_id`` per frame row (-1: untracked), and
         ``<save_dir>/plates.txt``, one line ``id first last hits text share_0..7`` per ended track (all streams are flushed
-        at the end; ids count per stream)."""
+        at the end; ids count per stream).
+
+        With ``best_shots`` the sharpest crop (``crop_size``) of line k of ``plates.txt`` is written as
+        ``<save_dir>/shots/<k>_<id>.png`` (RGB), and ``<save_dir>/shots.txt`` has one line ``id frame row status sharpness file``
+        per line of ``plates.txt``: the stream's frame index and the row the shot was cut from, the crop's status (1 corners,
+        2 box) and its Laplacian energy; a track without a shot has ``id 0 0 0 0 -``."""
         if self.track:
-            self._track_begin()
+            self._track_begin(crop_size)
         if self.device.type != 'cpu' and (self.tile is not None or self.batch_size > 1):
             groups = self._gpu_groups(conf_thres, iou_thres, max_det, save_crops, crop_size)
         else:
@@ -154,7 +165,7 @@ class Inferer:
             elif len(det) and self.tile is None:      # (tiled_rows_cpu returns frame pixels)
                 det[:, :12] = self.rescale(img.shape[2:], det[:, :12], img_src.shape).round()
             if self.track:
-                det = self._track_frame(det, img_path, max_det)
+                det = self._track_frame(det, img_path, max_det, frame if gpu else img_src)
             crops = None
             if save_crops and len(det):
                 if gpu:     # the uploaded frame and its detections are on the device: crop there
@@ -226,7 +237,7 @@ class Inferer:
             if self.track:      # detect -> track -> (crops) enqueued back to back on the device, then the host reads
                 padded = runtime.detect_frames_padded if self.tile is None else runtime.detect_tiled_padded
                 det, count = padded(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det, **kw)
-                det, tid = self._track_update(det, count, [p for _, p in items])
+                det, tid = self._track_update(det, count, [p for _, p in items], dev_frames)
                 if save_crops:
                     dets, crops, _ = runtime._unpad_with_crops(dev_frames, det, count, runtime._crop_size(crop_size))
                 else:
@@ -264,8 +275,9 @@ class Inferer:
 
     # ---- tracking (``track=True``) ---------------------------------------------------------------------------------------
     TRACK_SLOTS = 64        # tracks alive at once per stream
+    SHOT_ROWS = 16          # with best_shots: the first rows of a frame (the NMS's order) whose crops compete
 
-    def _track_begin(self):
+    def _track_begin(self, crop_size=(64, 192)):
         """A fresh tracker: stream 0 = the image files of the source, stream 1 + k = its k-th video file."""
         from yolov6.utils.track import PlateTrackerNp
         videos = [p for p in self.files.files if self.files.checkext(p) != 'image']
@@ -277,50 +289,81 @@ class Inferer:
             self._tracker = runtime.PlateTracker(1 + len(videos), device=self.device, **kw)
         else:
             self._tracker = PlateTrackerNp(1 + len(videos), **kw)
-        self._track_tids, self._track_lines, self._track_ended = deque(), [], []
+        self._track_tids, self._track_lines, self._track_ended, self._track_shots = deque(), [], [], []
+        if self.best_shots:
+            if self.device.type != 'cpu':
+                self._tracker.enable_best_shot(crop_size, max_crops=self.SHOT_ROWS)
+            else:
+                from yolov6.utils.best_shot import BestShotNp
+                self._gallery = BestShotNp(1 + len(videos), self.TRACK_SLOTS, crop_size)
 
-    def _track_collect(self, ended_i, ended_f, ended_count):
-        """Keep the ended records of one update (the host read of a GPU update)."""
+    def _track_collect(self, ended_i, ended_f, ended_count, shot_crops=None, shot_i=None, shot_q=None, shot_det=None):
+        """Keep the ended records of one update and, with ``best_shots``, their shots (the host read of a GPU update; of the
+        crops only those of records with a shot are read)."""
         if torch.is_tensor(ended_count):
             ended_i, ended_f, ended_count = ended_i.cpu().numpy(), ended_f.cpu().numpy(), ended_count.cpu().numpy()
+        if torch.is_tensor(shot_i):
+            shot_i, shot_q = shot_i.cpu().numpy(), shot_q.cpu().numpy().view(np.uint64)
         for s, c in enumerate(ended_count.tolist()):
             if c > ended_i.shape[1]:
                 LOGGER.warning('stream %d: %d tracks ended in one step, %d recorded' % (s, c, ended_i.shape[1]))
             for k in range(min(c, ended_i.shape[1])):
                 self._track_ended.append((ended_i[s, k].copy(), ended_f[s, k].copy()))
+                if shot_i is not None:
+                    crop = shot_crops[s, k] if shot_i[s, k, 3] else None
+                    crop = crop.cpu().numpy() if torch.is_tensor(crop) else (None if crop is None else crop.copy())
+                    self._track_shots.append((shot_i[s, k].copy(), int(shot_q[s, k]), crop))
 
-    def _track_update(self, det, count, paths):
+    def _track_update(self, det, count, paths, frames=None):
         """One tracker update of a padded group: det [B,max_det,28] + count [B] (numpy on the CPU, device tensors on a GPU) of
-        the frames ``paths`` (consecutive frames; slots past them are padding): (voted det, tid [B,max_det]), copies."""
+        the frames ``paths`` (consecutive frames; slots past them are padding): (voted det, tid [B,max_det]), copies.
+        ``frames``: the frames themselves, for ``best_shots`` (device tensors on a GPU, BGR arrays on the CPU)."""
         B = det.shape[0]
         streams = [self._track_streams.get(p, 0) for p in paths] + [-1] * (B - len(paths))
         # a slot's track lives at least max_age + 1 frames: so many records at most can end in B frames
         max_ended = self._tracker.max_tracks * (B // (self.track_max_age + 1) + 1)
-        det_out, tid, ended_i, ended_f, ended_count = self._tracker.update(det, count, streams, max_ended=max_ended)
-        self._track_collect(ended_i, ended_f, ended_count)
+        if not self.best_shots:
+            det_out, tid, ended_i, ended_f, ended_count = self._tracker.update(det, count, streams, max_ended=max_ended)
+            self._track_collect(ended_i, ended_f, ended_count)
+        elif torch.is_tensor(det):
+            det_out, tid, *rest = self._tracker.update_with_shots(list(frames), det, count, streams, max_ended=max_ended)
+            self._track_collect(*rest)
+        else:
+            det_out, tid, ended_i, ended_f, ended_count = self._tracker.update(det, count, streams, max_ended=max_ended)
+            shots = self._gallery.update_from_frames(frames, det, count, tid, self._tracker.last_slot, streams, ended_i, ended_count,
+                                                     self.SHOT_ROWS)
+            self._track_collect(ended_i, ended_f, ended_count, *shots)
         if torch.is_tensor(det_out):
             det_out, tid = det_out.clone(), tid.clone()     # the tracker's buffers are persistent
         return det_out, tid
 
-    def _track_frame(self, det, img_path, max_det):
+    def _track_frame(self, det, img_path, max_det, frame=None):
         """The voted rows of one frame's rescaled detections ([n, 28] tensor); its track ids are queued for ``infer``."""
         n, max_det = len(det), max(int(max_det), len(det), 1)
         if self.device.type != 'cpu':
             pad = torch.zeros(1, max_det, 28, dtype=torch.float32, device=self.device)
             pad[0, :n] = det
-            out, tid = self._track_update(pad, torch.full((1,), n, dtype=torch.int32, device=self.device), [img_path])
+            out, tid = self._track_update(pad, torch.full((1,), n, dtype=torch.int32, device=self.device), [img_path], [frame])
             self._track_tids.append(tid[0, :n].cpu().numpy())
             return out[0, :n]
         pad = np.zeros((1, max_det, 28), np.float32)
         pad[0, :n] = det.detach().float().cpu().numpy()
-        out, tid = self._track_update(pad, np.array([n], np.int32), [img_path])
+        out, tid = self._track_update(pad, np.array([n], np.int32), [img_path], [frame])
         self._track_tids.append(tid[0, :n])
         return torch.from_numpy(out[0, :n].copy())
 
     def _track_finish(self, save_dir):
         """Flush every stream and write tracks.txt / plates.txt."""
         from yolov6.utils.track import plate_text
-        self._track_collect(*self._tracker.flush_all()[2:])
+        if not self.best_shots:
+            self._track_collect(*self._tracker.flush_all()[2:])
+        elif self.device.type != 'cpu':
+            self._track_collect(*self._tracker.flush_all_with_shots()[2:])
+        else:
+            _, tid, ended_i, ended_f, ended_count = self._tracker.flush_all()
+            shots = self._gallery.update_from_frames([], np.zeros((0, 1, 28), np.float32), [], tid, self._tracker.last_slot, [], ended_i,
+                                                     ended_count, self.SHOT_ROWS)
+            self._track_collect(ended_i, ended_f, ended_count, *shots)
         os.makedirs(save_dir, exist_ok=True)
         with open(osp.join(save_dir, 'tracks.txt'), 'w') as f:
             f.writelines(line + '\n' for line in self._track_lines)
@@ -328,6 +371,16 @@ class Inferer:
             for ri, rf in self._track_ended:
                 text = plate_text(ri[4:12], self.pro_names, self.alp_names, self.ads_names)
                 f.write('%d %d %d %d %s %s\n' % (ri[0], ri[1], ri[2], ri[3], text, ' '.join('%g' % v for v in rf[:8])))
+        if self.best_shots:
+            from PIL import Image
+            os.makedirs(osp.join(save_dir, 'shots'), exist_ok=True)
+            with open(osp.join(save_dir, 'shots.txt'), 'w') as f:
+                for k, ((ri, _), (si, q, crop)) in enumerate(zip(self._track_ended, self._track_shots)):
+                    name = '-'
+                    if crop is not None:
+                        name = osp.join('shots', '%d_%d.png' % (k, ri[0]))
+                        Image.fromarray(np.ascontiguousarray(crop[:, :, ::-1])).save(osp.join(save_dir, name))
+                    f.write('%d %d %d %d %d %s\n' % (ri[0], si[0], si[1], si[2], q, name))
 
     def _frames_ahead(self, prefetch_frames, imread_bgr):
         """(frame, path) of every source in LoadData's order: image files decoded ahead on the pool, videos read in turn."""

@@ -130,8 +130,15 @@ SYMBOLS = {
     'lp_track_dropped_offset': (c_size_t, [c_int, c_int]),
     'lp_track_update': (c_int, [c_void_p, c_int, c_int, POINTER(TrackParams), c_void_p, c_void_p, c_int, c_int, POINTER(c_int),
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'lp_track_update_slots': (c_int, [c_void_p, c_int, c_int, POINTER(TrackParams), c_void_p, c_void_p, c_int, c_int, POINTER(c_int),
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'lp_plate_crops_batch': (c_int, [POINTER(CropDesc), c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                      c_void_p]),
+    'lp_crop_sharpness': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'lp_best_shot_state_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'lp_best_shot_update': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_int, POINTER(c_int), c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
     'lp_eval_counts': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'lp_check_sigmoid_monotone': (c_int, [c_void_p, c_void_p]),
     'lp_debug_poison_lds': (c_int, [c_void_p]),

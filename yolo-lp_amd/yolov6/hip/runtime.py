@@ -964,6 +964,24 @@ def plate_crops(frames, det, count, crop_hw=(64, 192), max_crops=None, out=None,
     return out, status
 
 
+def crop_sharpness(crops, status, out=None):
+    """Laplacian energy of plate crops (lp_crop_sharpness, one workgroup per crop): crops [..., Hc, Wc, 3] uint8 + status [...]
+    int32 as ``plate_crops`` returns them -> int64 [...] on the device holding the unsigned 64-bit sums (view the host copy as
+    uint64); 0 for status 0 or 3 or a side shorter than 3.  ``out``: a persistent buffer of that shape.
+    yolov6.utils.best_shot.crop_sharpness_np is the same computation on the CPU, bit for bit."""
+    if not (crops.is_cuda and crops.dtype == torch.uint8 and crops.dim() >= 3 and crops.shape[-1] == 3 and crops.is_contiguous()):
+        raise ValueError('crops must be a contiguous uint8 CUDA tensor [..., Hc, Wc, 3]')
+    lead = crops.shape[:-3]
+    Hc, Wc = _crop_size(crops.shape[-3:-1])
+    if not (status.dtype == torch.int32 and status.shape == lead and status.device == crops.device and status.is_contiguous()):
+        raise ValueError('status must be a contiguous int32 tensor %s on the crops\' device' % list(lead))
+    out = _buffer(out, lead, torch.int64, crops.device, 'sharp')
+    with torch.cuda.device(crops.device):
+        abi.check(abi.load().lp_crop_sharpness(_dptr(crops), _dptr(status), status.numel(), Hc, Wc, _dptr(out), _stream_ptr(crops.device)),
+                  'lp_crop_sharpness')
+    return out
+
+
 def _unpad_with_crops(frames, det, count, crop_hw):
     """(dets, crops, status) of the ``*_with_crops`` entry points from a padded result in frame pixels: the one host read of
     the counts, then the crops packed, frame b's n_b right behind frame b-1's (``crop_hw``: checked by ``_crop_size``)."""
@@ -1157,14 +1175,21 @@ class PlateTracker:
         self.state = torch.zeros(self.n_streams * self._words, dtype=torch.int32, device=self.device)
         self._drop_word = lib.lp_track_dropped_offset(self.max_tracks, 0) // 4
         self._out = {}
+        self._slot = {}
+        self._shots = None
 
     def reset(self, streams=None):
-        """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0."""
-        if streams is None:
-            self.state.zero_()
-        else:
-            for s in streams:
-                self.state.view(self.n_streams, self._words)[int(s)].zero_()
+        """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0; their best-shot
+        galleries (``enable_best_shot``) are emptied with them."""
+        states = [self.state.view(self.n_streams, self._words)]
+        if self._shots is not None:
+            states.append(self._shots['state'].view(self.n_streams, -1))
+        for st in states:
+            if streams is None:
+                st.zero_()
+            else:
+                for s in streams:
+                    st[int(s)].zero_()
 
     @property
     def dropped(self):
@@ -1191,11 +1216,20 @@ class PlateTracker:
         so = (ctypes.c_int * max(B, 1))(*stream_of)
         fl = (ctypes.c_ubyte * S)(*flush)
         with torch.cuda.device(self.device):
-            abi.check(abi.load().lp_track_update(_dptr(self.state), S, self.max_tracks, ctypes.byref(self._params), _dptr(det), _dptr(count),
-                                                 B, max_det, so, ctypes.cast(fl, ctypes.c_void_p), _dptr(det_out), _dptr(tid),
-                                                 _dptr(ended_i), _dptr(ended_f), _dptr(ended_count), max_ended,
-                                                 _stream_ptr(self.device)), 'lp_track_update')
+            abi.check(abi.load().lp_track_update_slots(_dptr(self.state), S, self.max_tracks, ctypes.byref(self._params), _dptr(det),
+                                                       _dptr(count), B, max_det, so, ctypes.cast(fl, ctypes.c_void_p), _dptr(det_out),
+                                                       _dptr(tid), _dptr(self.slot_buffer(B, max_det)), _dptr(ended_i), _dptr(ended_f),
+                                                       _dptr(ended_count), max_ended, _stream_ptr(self.device)), 'lp_track_update_slots')
         return out
+
+    def slot_buffer(self, B, max_det):
+        """The persistent int32 [B,max_det] tensor an ``update`` of that shape fills beside its returns: the tracker slot of each
+        matched or new row's track, -1 wherever tid is -1 (``PlateTrackerNp.last_slot``)."""
+        key = (int(B), int(max_det))
+        buf = self._slot.get(key)
+        if buf is None:
+            buf = self._slot[key] = torch.empty(key, dtype=torch.int32, device=self.device)
+        return buf
 
     def buffers(self, B, max_det, max_ended=None):
         """The persistent outputs of an ``update`` of B frames of max_det rows: (det_out, tid, ended_i, ended_f, ended_count)."""
@@ -1215,6 +1249,102 @@ class PlateTracker:
         det = torch.empty(0, int(max_det), abi.LP_DET_COLS, dtype=torch.float32, device=self.device)
         count = torch.empty(0, dtype=torch.int32, device=self.device)
         return self.update(det, count, stream_of=[], flush=[1] * self.n_streams, max_ended=max_ended)
+
+    # ---- the best shot of every track (lp_crop_sharpness, lp_best_shot_update; yolov6/utils/best_shot.py states the rules) ----
+    def enable_best_shot(self, crop_hw=(64, 192), max_crops=16, min_score=0.0):
+        """Allocate the zeroed gallery: per slot the sharpest ``crop_hw`` crop its track has shown (``update_with_shots``).  The
+        first ``max_crops`` rows of a frame compete; a row needs a mean confidence of at least ``min_score``."""
+        Hc, Wc = _crop_size(crop_hw)
+        if int(max_crops) < 1:
+            raise ValueError('max_crops must be >= 1')
+        if not abs(float(min_score)) <= 3.0e38:
+            raise ValueError('min_score must be finite (|min_score| <= 3e38)')
+        nbytes = abi.load().lp_best_shot_state_bytes(self.n_streams, self.max_tracks, Hc, Wc)
+        self._shots = dict(crop_hw=(Hc, Wc), max_crops=int(max_crops), min_score=float(min_score), out={},
+                           state=torch.zeros(nbytes, dtype=torch.uint8, device=self.device),
+                           blank=torch.zeros(1, 1, 3, dtype=torch.uint8, device=self.device))
+
+    def shot_buffers(self, B, max_ended=None):
+        """The persistent buffers of an ``update_with_shots`` of B frames: (crops [B,max_crops,Hc,Wc,3] uint8, status
+        [B,max_crops] int32, sharp [B,max_crops] int64, shot_crops [S,max_ended,Hc,Wc,3] uint8, shot_i [S,max_ended,4] int32,
+        shot_q [S,max_ended] int64, shot_det [S,max_ended,28] fp32)."""
+        if self._shots is None:
+            raise RuntimeError('call enable_best_shot() first')
+        sh, S, dev = self._shots, self.n_streams, self.device
+        (Hc, Wc), m = sh['crop_hw'], sh['max_crops']
+        key = (int(B), self.max_tracks if max_ended is None else int(max_ended))
+        out = sh['out'].get(key)
+        if out is None:
+            out = sh['out'][key] = (torch.zeros(key[0], m, Hc, Wc, 3, dtype=torch.uint8, device=dev),
+                                    torch.zeros(key[0], m, dtype=torch.int32, device=dev),
+                                    torch.zeros(key[0], m, dtype=torch.int64, device=dev),
+                                    torch.zeros(S, key[1], Hc, Wc, 3, dtype=torch.uint8, device=dev),
+                                    torch.empty(S, key[1], 4, dtype=torch.int32, device=dev),
+                                    torch.empty(S, key[1], dtype=torch.int64, device=dev),
+                                    torch.empty(S, key[1], abi.LP_DET_COLS, dtype=torch.float32, device=dev))
+        return out
+
+    def update_with_shots(self, frames, det, count, stream_of=None, flush=None, max_ended=None):
+        """``update`` plus the best shot of every track that ends in it, enqueued back to back with no host read: the tracker,
+        ``plate_crops`` of ``frames`` (contiguous uint8 CUDA [h,w,3] BGR, frame b of ``det``; shorter than B or None where
+        ``stream_of`` is -1) along the rows of ``det`` as given, ``crop_sharpness``, then lp_best_shot_update.  Returns the five
+        tensors of ``update`` followed by (shot_crops [S,max_ended,Hc,Wc,3] uint8, shot_i [S,max_ended,4] int32 = frame, row,
+        status, valid; shot_q [S,max_ended] int64 holding the unsigned sharpness; shot_det [S,max_ended,28] fp32 = the shot's
+        row with its per-frame confidences), line-parallel to ended_i / ended_f; persistent buffers per shape.  The crop of a
+        record without a shot (valid 0) is left as it was.  yolov6.utils.best_shot.BestShotNp is the same computation on the
+        CPU, bit for bit."""
+        from yolov6.utils import track
+        if self._shots is None:
+            raise RuntimeError('call enable_best_shot() first')
+        S, B = self.n_streams, det.shape[0]
+        stream_of, _, max_ended = track.check_call(S, B, stream_of, flush, self.max_tracks if max_ended is None else max_ended)
+        frames = list(frames) + [None] * (B - len(frames))
+        if len(frames) != B:
+            raise ValueError('%d frames for a batch of %d' % (len(frames), B))
+        for b, f in enumerate(frames):
+            if f is None and stream_of[b] >= 0:
+                raise ValueError('frame %d of stream %d is missing' % (b, stream_of[b]))
+        live = [f for f in frames if f is not None]
+        if live and _frames_device(live) != self.device:
+            raise ValueError('frames must be on the tracker\'s device %s' % self.device)
+        out = self.update(det, count, stream_of, flush, max_ended)
+        crops, status, sharp = self._shot_crops(frames, det, count, stream_of, max_ended)
+        if B:
+            crop_sharpness(crops, status, out=sharp)
+        return out + self._shot_gallery(det, count, stream_of, max_ended)
+
+    def _shot_crops(self, frames, det, count, stream_of, max_ended):
+        """The crop stage of ``update_with_shots``: (crops, status, sharp) of ``shot_buffers``, the first two written."""
+        sh, B = self._shots, det.shape[0]
+        crops, status, sharp = self.shot_buffers(B, max_ended)[:3]
+        m = sh['max_crops']
+        if B:
+            # a frame that is not tracked takes no slots: its status keeps what an earlier call left, and nothing reads it
+            off = [f is None or stream_of[b] < 0 for b, f in enumerate(frames)]
+            _plate_crops_launch([sh['blank'] if o else f for o, f in zip(off, frames)], det, count,
+                                [(0 if o else m, b * m) for b, o in enumerate(off)], crops, status, sh['crop_hw'])
+        return crops, status, sharp
+
+    def _shot_gallery(self, det, count, stream_of, max_ended):
+        """The gallery stage of ``update_with_shots`` behind ``update`` of the same arguments: (shot_crops, shot_i, shot_q,
+        shot_det)."""
+        sh, S, (B, max_det) = self._shots, self.n_streams, det.shape[:2]
+        crops, status, sharp, shot_crops, shot_i, shot_q, shot_det = self.shot_buffers(B, max_ended)
+        _, tid, ended_i, _, ended_count = self.buffers(B, max_det, max_ended)
+        so = (ctypes.c_int * max(B, 1))(*stream_of)
+        with torch.cuda.device(self.device):
+            abi.check(abi.load().lp_best_shot_update(_dptr(sh['state']), S, self.max_tracks, sh['crop_hw'][0], sh['crop_hw'][1], _dptr(det),
+                                                     _dptr(count), B, max_det, _dptr(tid), _dptr(self.slot_buffer(B, max_det)), _dptr(crops),
+                                                     _dptr(status), _dptr(sharp), sh['max_crops'], so, _dptr(ended_i), _dptr(ended_count),
+                                                     max_ended, sh['min_score'], _dptr(shot_crops), _dptr(shot_i), _dptr(shot_q),
+                                                     _dptr(shot_det), _stream_ptr(self.device)), 'lp_best_shot_update')
+        return shot_crops, shot_i, shot_q, shot_det
+
+    def flush_all_with_shots(self, max_det=1, max_ended=None):
+        """``flush_all`` with the best shots of the tracks it ends: ``update_with_shots`` of zero frames."""
+        det = torch.empty(0, int(max_det), abi.LP_DET_COLS, dtype=torch.float32, device=self.device)
+        count = torch.empty(0, dtype=torch.int32, device=self.device)
+        return self.update_with_shots([], det, count, stream_of=[], flush=[1] * self.n_streams, max_ended=max_ended)
 
 
 def eval_counts(det, det_count, tgt, tgt_count, counts=None):

@@ -163,6 +163,9 @@ class PlateTrackerNp:
         #: counters for tests and diagnostics (no part of the state): pairs above the threshold, pairs sharing their IoU
         #: with another pair of the frame, pairs taken, tracks ended
         self.stats = dict(pairs=0, ties=0, matched=0, ended=0)
+        #: int32 [B, max_det] of the last ``update``: the slot of each matched or new row's track, -1 wherever its tid is -1
+        #: (the ``slot`` output of lp_track_update_slots)
+        self.last_slot = np.zeros((0, 1), np.int32)
 
     _SLOT_ARRAYS = ('id', 'first', 'last', 'hits', 'misses', 'box', 'cor', 'vel', 'votes', 'total')
 
@@ -278,6 +281,7 @@ class PlateTrackerNp:
                 best, share = self.read(s, t)
                 det_out[r, 12:20], det_out[r, 20:28], tid[r] = share, best.astype(f32), self.id[s, t]
         self.frame[s] += 1
+        self._row_slot = row_slot
         return det_out, tid
 
     def flush_all(self, max_det=1, max_ended=None):
@@ -303,6 +307,7 @@ class PlateTrackerNp:
         stream_of, flush, max_ended = check_call(S, B, stream_of, flush, self.max_tracks if max_ended is None else max_ended)
         det_out = np.zeros_like(det)
         tid = np.full((B, max_det), -1, np.int32)
+        slot = self.last_slot = np.full((B, max_det), -1, np.int32)
         ended = [[] for _ in range(S)]
         for b, s in enumerate(stream_of):
             if s < 0:
@@ -310,6 +315,7 @@ class PlateTrackerNp:
                 det_out[b, :nc] = det[b, :nc]
             else:
                 det_out[b], tid[b] = self._frame(s, det[b], count[b], ended[s])
+                slot[b, :len(self._row_slot)] = self._row_slot
         for s in range(S):
             if flush[s]:
                 for t in np.nonzero(self.live(s))[0]:
