@@ -310,6 +310,52 @@ typedef struct lp_tile_desc {
 } lp_tile_desc;
 int lp_preprocess_tiles_batch(const lp_tile_desc* desc, int n_tiles, int B, void* out, int out_dtype, int H, int W, void* stream);
 
+/* NV12 video frames.  Decoders deliver NV12, not BGR: an h0 x w0 frame (both even) is a luma plane y, uint8 [h0][w0] with rows
+ * pitch_y >= w0 bytes apart, and a half-resolution chroma plane uv, uint8 [h0/2][w0/2][2] (U first) with rows pitch_uv >= w0 bytes
+ * apart, pitch_uv even, base 2-byte aligned.  The reference has nothing here; yolov6/utils/nv12.py states the rule and restates
+ * both entry points in numpy, bit for bit.  For pixel (i, j): Y = y[i][j], U = uv[i>>1][j>>1][0], V = uv[i>>1][j>>1][1] (chroma
+ * is replicated, not interpolated), and in int32 with arithmetic right shifts
+ *     c = max(Y - yoff, 0) * CY;  d = U - 128;  e = V - 128;  half = 1 << 19
+ *     R = clamp255((c + half + CVR*e) >> 20);  G = clamp255((c + half + CVG*e + CUG*d) >> 20);  B = clamp255((c + half + CUB*d) >> 20)
+ * with (yoff, CY, CUB, CUG, CVG, CVR) of `matrix`:
+ *     0 bt601  (limited range; the table of OpenCV's COLOR_YUV2BGR_NV12)  16, 1220542, 2116026, -409993, -852492, 1673527
+ *     1 bt709  (limited range)                                            16, 1220945, 2215014, -223607, -558796, 1879825
+ *     2 bt601f (full range)                                                0, 1048576, 1858077, -360853, -748826, 1470104
+ *     3 bt709f (full range)                                                0, 1048576, 1945738, -196424, -490864, 1651297
+ *
+ * lp_preprocess_nv12_batch: the letterbox of lp_preprocess_tiles_batch with the conversion fused in; no BGR frame exists on the
+ * device.  Slot b < n of out [B,3,H,W] is bit-identical to what lp_preprocess_tiles_batch writes for the region (y0, x0, th, tw)
+ * and the geometry (rh, rw, top, left) of the BGR frame the rule gives for the WHOLE frame: the bilinear taps clamp at the region's
+ * edges, chroma is indexed by the absolute frame coordinate (odd y0, x0 are legal), rh == th && rw == tw means no resize; a whole
+ * frame is the region (0, 0, h0, w0).  Slots n <= b < B are padding (114/255).  Descriptors travel by value in the kernel
+ * arguments, one launch per LP_NV12_PER_LAUNCH slots: nothing is uploaded, no host sync, capturable in a graph.  desc is a HOST
+ * array of n entries, all checked before the first launch; LP_ERR_ARG names the entry for: a null plane, odd (or < 2) h0 or w0,
+ * pitch_y < w0, pitch_uv < w0 or odd, uv not 2-byte aligned, an unknown matrix, a region outside the frame, geometry outside H x W.
+ *
+ * lp_nv12_to_bgr_batch: the frame itself for the callers that need it (plate crops, the best-shot gallery, saving images):
+ * out = uint8 [h0,w0,3] BGR, contiguous, any alignment, by the rule above; one launch per LP_FRAMES_PER_LAUNCH frames, the
+ * table in the kernel arguments.  The same plane checks, and a null out, are LP_ERR_ARG naming the entry before any launch. */
+#define LP_NV12_PER_LAUNCH 32
+typedef struct lp_nv12_desc {
+    const unsigned char* y;     /* device luma plane */
+    const unsigned char* uv;    /* device chroma plane */
+    int pitch_y, pitch_uv;
+    int h0, w0;
+    int y0, x0, th, tw;         /* the region of the frame */
+    int rh, rw, top, left;      /* letterbox geometry of a (th, tw) image */
+    int matrix;
+} lp_nv12_desc;
+typedef struct lp_nv12_bgr_desc {
+    const unsigned char* y;
+    const unsigned char* uv;
+    int pitch_y, pitch_uv;
+    int h0, w0;
+    int matrix;
+    unsigned char* out;         /* device uint8 [h0,w0,3] */
+} lp_nv12_bgr_desc;
+int lp_preprocess_nv12_batch(const lp_nv12_desc* desc, int n, int B, void* out, int out_dtype, int H, int W, void* stream);
+int lp_nv12_to_bgr_batch(const lp_nv12_bgr_desc* desc, int n, void* stream);
+
 /* lp_merge_tiles: per-frame merge of per-tile detections; one workgroup per frame, at most 64 tiles (whole frames) per launch,
  * the tile table travels as kernel arguments: nothing is uploaded, no host sync.
  *   det_t [n_tiles,max_det_t,28] fp32 + count_t [n_tiles] int32 (DEVICE): the tiles' detections as lp_nms leaves them, in

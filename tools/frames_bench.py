@@ -6,6 +6,7 @@
     python tools/frames_bench.py --tile [--tile-baseline] [--tile-frame 2160 3840] [--tile-size 640] [--tile-overlap 128]
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot]
+    python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
   - frames/s of the per-frame path (upload, lp_preprocess_letterbox, detect at B=1 with hipGraph replay, lp_rescale_round,
@@ -32,6 +33,12 @@ update alone on a full frame per stream (128 live tracks x 128 rows, every pair 
 plate crops (16 slots of 64x192 per frame), lp_crop_sharpness and lp_best_shot_update, each from events, at the bench's own
 detection density; and a worst case on 16 constant rows per stream whose sharpness is made to grow with every call, so that
 every row of every frame replaces its shot (16 x 36 KB copied per stream by one workgroup).
+With ``--nv12 [MATRIX]`` the same seeded frames are sent as BGR and as NV12 (encoded on the host before any clock starts, as a
+decoder would deliver them), alternating, ``--runs`` timed runs each: frames/s of FrameBatcher + ``detect_frames``; the stages of
+one batch from events for both kinds (H2D, letterbox -- lp_preprocess_letterbox_batch on the BGR frames against
+lp_preprocess_nv12_batch on the NV12 frames, in the same run --, detect, rescale), the NV12 convert stage (lp_nv12_to_bgr_batch,
+with its GB/s over 1.5 B read + 3 B written per pixel) and, with ``--crops N``, the crop stage behind it.  With ``--tile`` the
+same for tiled detection: frames/s of ``detect_tiled_with_crops`` for both kinds and the stage times of each.
 The model is the synthetic recipe of bench.py (same weights scale), prepared as Inferer prepares it.
 """
 import argparse
@@ -74,6 +81,8 @@ def parse():
     ap.add_argument('--track', action='store_true', help='measure plate tracking (PlateTracker.update behind detect_frames) instead')
     ap.add_argument('--track-batch', type=int, default=32, help='with --track: camera streams = frames per step')
     ap.add_argument('--best-shot', action='store_true', help='with --track: also time crops + sharpness + gallery behind the update')
+    ap.add_argument('--nv12', nargs='?', const='bt709', default=None, choices=['bt601', 'bt709', 'bt601f', 'bt709f'], metavar='MATRIX',
+                    help='also send the same seeded frames as NV12 with this matrix and compare (default matrix: bt709)')
     ap.add_argument('--runs', type=int, default=3, help='timed runs of the frames/s figures (the spread is reported)')
     return ap.parse_args()
 
@@ -89,7 +98,12 @@ def tile_mode(args, model, dev, tdt):
     F, B = args.tile_frames, args.tile_batch
     conf, iou, max_det = args.conf, args.iou, args.max_det
     rng = np.random.default_rng(0)
-    frames = [torch.from_numpy(rng.integers(0, 256, (h0, w0, 3), dtype=np.uint8)).to(dev) for _ in range(F)]
+    host_frames = [rng.integers(0, 256, (h0, w0, 3), dtype=np.uint8) for _ in range(F)]
+    frames = [torch.from_numpy(f).to(dev) for f in host_frames]
+    nv_frames = None
+    if args.nv12:
+        from yolov6.utils.nv12 import bgr_to_nv12_np
+        nv_frames = [bgr_to_nv12_np(f, args.nv12).to(dev) for f in host_frames]
     shapes = [(h0, w0)] * F
     tiles, tmd = runtime.plan_tiled(shapes, size, max_det, (tile, tile), args.tile_overlap, True)
     kw = dict(tile_hw=(tile, tile), overlap=args.tile_overlap, batch=B)
@@ -110,8 +124,8 @@ def tile_mode(args, model, dev, tdt):
             fps.append(round(calls * F / (time.perf_counter() - t0), 2))
         return fps
 
-    def tiled():
-        return runtime.detect_tiled_with_crops(model, frames, size, conf, iou, max_det, **kw)
+    def tiled(fr=None):
+        return runtime.detect_tiled_with_crops(model, frames if fr is None else fr, size, conf, iou, max_det, **kw)
 
     def baseline():         # what the entry points before tiling can do for the same job
         dets, counts = [], []
@@ -130,7 +144,21 @@ def tile_mode(args, model, dev, tdt):
         dets, _, _ = tiled()
         out['detections_per_frame'] = [len(d) for d in dets]
         calls = max(2, args.frames // (F * 8))
-        out['tiled_fps_runs'] = timed(tiled, calls)
+        if nv_frames is None:
+            out['tiled_fps_runs'] = timed(tiled, calls)
+        else:                              # BGR and NV12 device frames, alternating
+            tiled(nv_frames)
+            sync()
+            both = dict(bgr=[], nv12=[])
+            for _ in range(args.runs):
+                for kind, fr in (('bgr', frames), ('nv12', nv_frames)):
+                    t0 = time.perf_counter()
+                    for _ in range(calls):
+                        tiled(fr)
+                    sync()
+                    both[kind].append(round(calls * F / (time.perf_counter() - t0), 2))
+            out['tiled_fps_runs'] = both['bgr']
+            out['nv12'] = dict(matrix=args.nv12, tiled_fps_runs=both['nv12'], tiled_fps=float(np.median(both['nv12'])))
         out['tiled_fps'] = float(np.median(out['tiled_fps_runs']))
         if args.tile_baseline:
             bdet, _ = baseline()
@@ -142,6 +170,40 @@ def tile_mode(args, model, dev, tdt):
         # device time per stage of one call, from events on one stream
         x = torch.empty(B, 3, *size, dtype=tdt, device=dev)
         names = ('tile_letterbox', 'detect', 'rescale', 'merge', 'crops')
+        if nv_frames is not None:          # the NV12 chain first: tile letterbox from the planes, one conversion before the crops
+            bgr_out = [torch.empty(h0, w0, 3, dtype=torch.uint8, device=dev) for _ in range(F)]
+            nv_names = ('tile_letterbox', 'detect', 'rescale', 'merge', 'convert', 'crops')
+            nv_times = {k: [] for k in nv_names}
+            for _ in range(args.reps + 1):
+                acc = dict.fromkeys(nv_names, 0.0)
+                pairs = []
+
+                def mark(name, fn):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    r = fn()
+                    b.record()
+                    pairs.append((name, a, b))
+                    return r
+
+                dl, cl = [], []
+                for c0 in range(0, len(tiles), B):
+                    mark('tile_letterbox', lambda: runtime.preprocess_tiles(nv_frames, tiles[c0:c0 + B], size, stride, tdt, batch=B, out=x))
+                    det, count, _ = mark('detect', lambda: runtime.detect_padded(model, x, conf, iou, tmd))
+                    dl.append(det)
+                    cl.append(count)
+                det_t, count_t = torch.cat(dl), torch.cat(cl)
+                mark('rescale', lambda: runtime.rescale_round_batch(det_t, count_t, size, [(t[3], t[4]) for t in tiles]))
+                det, count, _ = mark('merge', lambda: runtime.merge_tiles(det_t, count_t, tiles, shapes, iou, max_det))
+                conv = mark('convert', lambda: runtime.nv12_to_bgr(nv_frames, out=bgr_out))
+                mark('crops', lambda: runtime.plate_crops(conv, det, count, max_crops=16))
+                sync()
+                for name, a, b in pairs:
+                    acc[name] += a.elapsed_time(b)
+                for k in nv_names:
+                    nv_times[k].append(acc[k])
+            out['nv12']['stage_ms_per_call'] = {k: round(float(np.median(v[1:])), 4) for k, v in nv_times.items()}
+            out['nv12']['tile_letterbox_runs'] = [round(v, 4) for v in nv_times['tile_letterbox'][1:]]
         times = {k: [] for k in names}
         for _ in range(args.reps + 1):
             acc = dict.fromkeys(names, 0.0)
@@ -172,6 +234,7 @@ def tile_mode(args, model, dev, tdt):
                 times[k].append(acc[k])
         med = {k: float(np.median(v[1:])) for k, v in times.items()}
         out['stage_ms_per_call'] = {k: round(v, 4) for k, v in med.items()}
+        out['tile_letterbox_runs'] = [round(v, 4) for v in times['tile_letterbox'][1:]]
         out['stage_pct_of_detect'] = {k: round(100.0 * med[k] / med['detect'], 2) for k in names if k != 'detect'}
         out['merged_counts'] = count.cpu().tolist()
         out['candidates_per_frame'] = [int(count_t[f * (len(tiles) // F):(f + 1) * (len(tiles) // F)].clamp(0, tmd).sum()) for f in range(F)]
@@ -338,6 +401,116 @@ def best_shot_stages(args, model, dev, tdt, frames, x, net_hw):
     return res
 
 
+def nv12_mode(args, model, dev, tdt):
+    """--nv12: the same seeded frames as BGR and as NV12, alternating -- frames/s, and the stages of one batch of each kind."""
+    import torch
+    from yolov6.hip import runtime
+    from yolov6.core.frames import FrameBatcher, letterbox_hw
+    from yolov6.utils.nv12 import Nv12Frame, bgr_to_nv12_np
+    size, stride = [args.size, args.size], int(model.stride.max())
+    h0, w0 = args.frame
+    conf, iou, max_det = args.conf, args.iou, args.max_det
+    rng = np.random.default_rng(0)
+    pool = [rng.integers(0, 256, (h0, w0, 3), dtype=np.uint8) for _ in range(args.distinct)]
+    nv_pool = [bgr_to_nv12_np(f, args.nv12) for f in pool]          # what a decoder delivers: encoded before any clock starts
+    H, W = letterbox_hw((h0, w0), size, stride)
+    sync = torch.cuda.synchronize
+    out = dict(metric='frames/s end to end, the same frames as BGR and as NV12 (host frames in, rescaled detections out)',
+               model=args.model, dtype=args.dtype, frame=[h0, w0], net=[H, W], matrix=args.nv12, runs=args.runs)
+    res = {}
+    with torch.no_grad():
+        for B in args.batches:
+            runtime.prepare_for(model, (B, 3, H, W), tdt)
+            batchers = dict(bgr=FrameBatcher(dev), nv12=FrameBatcher(dev))
+            pools = dict(bgr=pool, nv12=nv_pool)
+            x = torch.empty(B, 3, H, W, dtype=tdt, device=dev)
+
+            def run(kind, k):
+                fr = [pools[kind][(k * B + j) % len(pool)] for j in range(B)]
+                return runtime.detect_frames(model, batchers[kind].put(fr), size, conf, iou, max_det, batch=B, out=x)
+
+            for kind in pools:
+                for k in range(2):
+                    run(kind, k)
+            sync()
+            nb = max(2, args.frames // B)
+            fps = dict(bgr=[], nv12=[])
+            for _ in range(args.runs):
+                for kind in pools:
+                    t0 = time.perf_counter()
+                    for k in range(nb):
+                        run(kind, k)
+                    sync()
+                    fps[kind].append(round(nb * B / (time.perf_counter() - t0), 1))
+            r = dict(fps_runs=fps, fps={k: float(np.median(v)) for k, v in fps.items()})
+            r['nv12_over_bgr'] = round(r['fps']['nv12'] / r['fps']['bgr'], 4)
+
+            # device time per stage of one batch of each kind, from events on one stream, alternating
+            n_bgr, n_nv = h0 * w0 * 3, h0 * w0 * 3 // 2
+            host = dict(bgr=torch.empty(B * n_bgr, dtype=torch.uint8, pin_memory=True), nv12=torch.empty(B * n_nv, dtype=torch.uint8, pin_memory=True))
+            for j in range(B):
+                host['bgr'].numpy()[j * n_bgr:(j + 1) * n_bgr] = pool[j % len(pool)].reshape(-1)
+                host['nv12'].numpy()[j * n_nv:(j + 1) * n_nv] = nv_pool[j % len(pool)].packed().reshape(-1)
+            dbuf = {k: torch.empty(v.numel(), dtype=torch.uint8, device=dev) for k, v in host.items()}
+            views = dict(bgr=[dbuf['bgr'][j * n_bgr:(j + 1) * n_bgr].view(h0, w0, 3) for j in range(B)],
+                         nv12=[Nv12Frame.from_packed(dbuf['nv12'][j * n_nv:(j + 1) * n_nv], h0, w0, args.nv12) for j in range(B)])
+            conv_out = [torch.empty(h0, w0, 3, dtype=torch.uint8, device=dev) for _ in range(B)]
+            names = dict(bgr=['h2d', 'letterbox', 'detect', 'rescale'], nv12=['h2d', 'letterbox', 'detect', 'rescale', 'convert'])
+            if args.crops:
+                crop_hw = (64, 192)
+                cdet = torch.from_numpy(synthetic_quads(B, args.crops, h0, w0, seed=B)).to(dev)
+                ccount = torch.full((B,), args.crops, dtype=torch.int32, device=dev)
+                cout = torch.empty(B, args.crops, *crop_hw, 3, dtype=torch.uint8, device=dev)
+                cst = torch.empty(B, args.crops, dtype=torch.int32, device=dev)
+                for v in names.values():
+                    v.append('crops')
+            times = {kind: {k: [] for k in v} for kind, v in names.items()}
+            for _ in range(args.reps + 1):
+                for kind in ('bgr', 'nv12'):
+                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names[kind]) + 1)]
+                    ev[0].record()
+                    dbuf[kind].copy_(host[kind], non_blocking=True)
+                    ev[1].record()
+                    xx, _ = runtime.preprocess_frames(views[kind], size, stride, tdt, batch=B, out=x)
+                    ev[2].record()
+                    det, count, _ = runtime.detect_padded(model, xx, conf, iou, max_det)
+                    ev[3].record()
+                    runtime.rescale_round_batch(det, count, (H, W), [(h0, w0)] * B)
+                    ev[4].record()
+                    i, fr = 4, views[kind]
+                    if kind == 'nv12':
+                        fr = runtime.nv12_to_bgr(views['nv12'], out=conv_out)
+                        i += 1
+                        ev[i].record()
+                    if args.crops:
+                        runtime.plate_crops(fr, cdet, ccount, crop_hw, max_crops=args.crops, out=cout, status=cst)
+                        ev[i + 1].record()
+                    sync()
+                    for i, k in enumerate(names[kind]):
+                        times[kind][k].append(ev[i].elapsed_time(ev[i + 1]))
+            for kind in ('bgr', 'nv12'):
+                med = {k: float(np.median(v[1:])) for k, v in times[kind].items()}
+                st = {k: round(v, 4) for k, v in med.items()}
+                st['letterbox_runs'] = [round(v, 4) for v in times[kind]['letterbox'][1:]]
+                st['h2d_MB'] = round(host[kind].numel() / 1e6, 2)
+                st['host_other'] = round(max(0.0, B * 1000.0 / r['fps'][kind] - sum(med[k] for k in ('h2d', 'letterbox', 'detect', 'rescale'))), 4)
+                if kind == 'nv12':
+                    moved = B * h0 * w0 * 4.5
+                    st['convert_runs'] = [round(v, 4) for v in times[kind]['convert'][1:]]
+                    st['convert_MB'] = round(moved / 1e6, 2)
+                    st['convert_GBps'] = round(moved / (med['convert'] * 1e-3) / 1e9, 1)
+                    if args.crops:
+                        st['convert_pct_of_detect'] = round(100.0 * med['convert'] / med['detect'], 2)
+                r['stage_ms_' + kind] = st
+            sp = times['bgr']['letterbox'][1:]
+            r['letterbox_nv12_over_bgr'] = round(r['stage_ms_nv12']['letterbox'] / r['stage_ms_bgr']['letterbox'], 4)
+            r['bgr_letterbox_spread_ms'] = round(max(sp) - min(sp), 4)
+            res[str(B)] = r
+            del host, dbuf, views, conv_out
+    out['batches'] = res
+    print(json.dumps(out))
+
+
 def synthetic_quads(n_frames, n, h0, w0, seed=0):
     """[n_frames, n, 28] fp32 detection rows: plates of 120..400 px x 1/3.1 of that, turned by up to 30 degrees; row r % 4 == 1
     also has each corner moved by up to 10 % (perspective), r % 4 == 3 has its BL and TR swapped (a bow-tie: the box is used)."""
@@ -397,6 +570,8 @@ def main():
         return tile_mode(args, model, dev, tdt)
     if args.track:
         return track_mode(args, model, dev, tdt)
+    if args.nv12:
+        return nv12_mode(args, model, dev, tdt)
     size, stride = [args.size, args.size], int(model.stride.max())
     h0, w0 = args.frame
     rng = np.random.default_rng(0)

@@ -5,6 +5,7 @@
                           [--batch-size 32] [--fixed-shape] [--save-crops [--crop-size 64 192]]
                           [--tile 640 640 [--tile-overlap 0.2] [--no-tile-overview] [--merge-metric iou|ios]]
                           [--track [--track-max-age 5] [--track-iou 0.3] [--track-expand 0.5] [--best-shots [--crop-size 64 192]]]
+                          [--nv12 bt601|bt709|bt601f|bt709f [--nv12-size W H]]
 """
 import argparse
 import os
@@ -58,6 +59,10 @@ _FLAGS = [
     ('--track-expand', dict(type=float, default=0.5, help='boxes are grown by this fraction of their size on every side before the IoU')),
     ('--best-shots', dict(action='store_true', help='with --track: keep the sharpest rectified crop (--crop-size) of every track and write '
                                                     'shots/<line>_<id>.png and shots.txt, line-parallel to plates.txt')),
+    ('--nv12', dict(default=None, choices=['bt601', 'bt709', 'bt601f', 'bt709f'], metavar='MATRIX',
+                    help='send frames as NV12 with this matrix (bt601, bt709: limited range; bt601f, bt709f: full range): decoded images '
+                         'are encoded on the host as a stand-in for a decoder; a source ending in .nv12 is a raw stream of packed frames')),
+    ('--nv12-size', dict(nargs=2, type=int, default=None, metavar=('W', 'H'), help='frame size of .nv12 sources')),
 ]
 
 
@@ -76,7 +81,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         view_img=True, classes=None, agnostic_nms=False, project=osp.join(ROOT, 'runs/inference'), name='exp',
         hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False, save_crops=False, crop_size=(64, 192),
         tile=None, tile_overlap=0.2, no_tile_overview=False, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3,
-        track_expand=0.5, best_shots=False):
+        track_expand=0.5, best_shots=False, nv12=None, nv12_size=None):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track) and not osp.exists(out_dir):
@@ -89,7 +94,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         tile_overlap = int(tile_overlap)        # pixels
     results = Inferer(source, weights, device, yaml, img_size, half, batch_size=batch_size, auto=not fixed_shape, tile=tile,
                       tile_overlap=tile_overlap, tile_overview=not no_tile_overview, merge_metric=merge_metric, track=track, track_max_age=track_max_age,
-                      track_iou=track_iou, track_expand=track_expand, best_shots=best_shots).infer(
+                      track_iou=track_iou, track_expand=track_expand, best_shots=best_shots, nv12=nv12, nv12_size=nv12_size).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

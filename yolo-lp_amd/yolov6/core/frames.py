@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from yolov6.data.data_augment import letterbox_geometry
+from yolov6.utils.nv12 import Nv12Frame, is_nv12_list
 
 MAX_DECODE_THREADS = 8
 
@@ -49,7 +50,8 @@ def plan_batches(shapes, img_size, stride, batch, auto=True):
 
 
 class FrameBatcher:
-    """Uploads a batch of host frames (uint8 [h,w,3] arrays) with one H2D copy and returns device views of them.
+    """Uploads a batch of host frames (uint8 [h,w,3] BGR arrays, or host ``Nv12Frame``s: half the bytes) with one H2D copy and
+    returns device views of them (tensors, or device ``Nv12Frame``s whose planes are views: Y, then UV right behind it).
 
     Two slots alternate; each has a pinned staging buffer and a device buffer.  A batch is packed into its slot's staging
     buffer (after waiting for that buffer's previous copy to finish), copied on the batcher's copy stream once the compute
@@ -65,10 +67,17 @@ class FrameBatcher:
         self.last = None
 
     def put(self, frames):
-        frames = [np.ascontiguousarray(f) for f in frames]
-        for f in frames:
-            if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
-                raise ValueError('frames must be uint8 [h, w, 3] arrays, got %s %s' % (f.dtype, f.shape))
+        nv12 = is_nv12_list(frames, 'FrameBatcher.put')
+        if nv12:
+            if any(f.is_tensor for f in frames):
+                raise ValueError('FrameBatcher.put takes host Nv12Frames (numpy planes)')
+            sizes = [f.nbytes for f in frames]
+        else:
+            frames = [np.ascontiguousarray(f) for f in frames]
+            for f in frames:
+                if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+                    raise ValueError('frames must be uint8 [h, w, 3] arrays, got %s %s' % (f.dtype, f.shape))
+            sizes = [f.nbytes for f in frames]
         compute = torch.cuda.current_stream(self.device)
         if self.last is not None:          # the work enqueued since the last put is the consumer of that slot's device buffer
             ev = torch.cuda.Event()
@@ -77,16 +86,21 @@ class FrameBatcher:
         slot = self.slots[self.k]
         self.k ^= 1
         offs, n = [], 0
-        for f in frames:
+        for nb in sizes:
             offs.append(n)
-            n += (f.nbytes + 255) // 256 * 256          # 256-byte aligned frame bases
+            n += (nb + 255) // 256 * 256                # 256-byte aligned frame bases
         if slot['copied'] is not None:
             slot['copied'].synchronize()                # the staging buffer's previous copy has left it
         if slot['host'] is None or slot['host'].numel() < n:
             slot['host'] = torch.empty(max(n, 1), dtype=torch.uint8, pin_memory=True)
         host = slot['host'].numpy()
         for f, o in zip(frames, offs):
-            host[o:o + f.nbytes] = f.reshape(-1)
+            if nv12:                                    # Y rows, then UV rows, packed (a source pitch is dropped here)
+                hw = f.h * f.w
+                host[o:o + hw].reshape(f.h, f.w)[:] = f.y
+                host[o + hw:o + f.nbytes].reshape(f.h // 2, f.w // 2, 2)[:] = f.uv
+            else:
+                host[o:o + f.nbytes] = f.reshape(-1)
         with torch.cuda.device(self.device):
             if slot['dev'] is None or slot['dev'].numel() < n:
                 slot['dev'] = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)   # owned by the compute stream
@@ -101,6 +115,8 @@ class FrameBatcher:
             slot['copied'] = ev
             compute.wait_event(ev)
         self.last = slot
+        if nv12:
+            return [Nv12Frame.from_packed(dev[o:o + f.nbytes], f.h, f.w, f.matrix) for f, o in zip(frames, offs)]
         return [dev[o:o + f.nbytes].view(f.shape) for f, o in zip(frames, offs)]
 
 

@@ -18,6 +18,10 @@ characters over its frames (``runtime.PlateTracker`` on a GPU, ``PlateTrackerNp`
 voted rows and writes ``tracks.txt`` (one line per frame row) and ``plates.txt`` (one line per track).
 With ``best_shots`` every track also keeps the sharpest rectified crop it has shown (``PlateTracker.update_with_shots`` on a GPU,
 ``BestShotNp`` on the CPU): ``shots/<line>_<id>.png`` and ``shots.txt``, line-parallel to ``plates.txt``.
+With ``nv12`` the frames travel as NV12 (``yolov6.utils.nv12``): decoded images are encoded on the host as a stand-in for a
+video decoder, ``.nv12`` sources are raw streams of packed frames; on a GPU the planes are uploaded (half the bytes of BGR) and
+read by the fused letterbox, a BGR frame exists on the device only where crops are cut; on the CPU every frame goes through
+``nv12_to_bgr_np`` into the existing path.
 """
 import math
 import os
@@ -33,11 +37,13 @@ from yolov6.layers.common import DetectBackend
 from yolov6.data.data_augment import letterbox
 from yolov6.data.datasets import LoadData
 from yolov6.utils.nms import non_max_suppression
+from yolov6.utils.nv12 import MATRICES, Nv12Frame, bgr_to_nv12_np, nv12_to_bgr_np
 
 
 class Inferer:
     def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True, tile=None, tile_overlap=0.2,
-                 tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5, best_shots=False):
+                 tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5, best_shots=False,
+                 nv12=None, nv12_size=None):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -48,12 +54,18 @@ class Inferer:
         predicted box (grown by ``track_expand`` of its size) it overlaps by more than ``track_iou``, a track unseen for more
         than ``track_max_age`` frames ends.
         ``best_shots`` (with ``track``): every track keeps the sharpest plate crop among the first ``SHOT_ROWS`` rows of its
-        frames (``yolov6.utils.best_shot`` states the rules); ``infer`` writes one image per ended track that has one."""
+        frames (``yolov6.utils.best_shot`` states the rules); ``infer`` writes one image per ended track that has one.
+        ``nv12`` = 'bt601' | 'bt709' | 'bt601f' | 'bt709f': send every frame as NV12 with that matrix (decoded images are encoded
+        with ``bgr_to_nv12_np``, an odd last row or column cut off as a decoder would never deliver one); ``nv12_size`` = (w, h)
+        of the frames of ``.nv12`` sources, which need ``nv12``."""
         self.__dict__.update(locals())
         if best_shots and not track:
             raise ValueError('best_shots needs track=True')
         if merge_metric not in ('iou', 'ios'):
             raise ValueError("merge_metric must be 'iou' or 'ios'")
+        if nv12 is not None and nv12 not in MATRICES:
+            raise ValueError('nv12 must be one of %s' % ', '.join(sorted(MATRICES)))
+        self.nv12_size = None if nv12_size is None else (int(nv12_size[0]), int(nv12_size[1]))
         self.tile = None if tile is None else ((int(tile), int(tile)) if isinstance(tile, int) else (int(tile[0]), int(tile[-1])))
         if int(batch_size) < 1:
             raise ValueError('batch_size must be >= 1')
@@ -80,7 +92,9 @@ class Inferer:
         if self.device.type != 'cpu':   # warm-up: builds the engine and tunes it for this shape
             self.model.model.lp_graph = True      # per-image loop = launch-bound: replay the forward as one hipGraph
             self.model(torch.zeros(1, 3, *self.img_size).to(self.device).type_as(next(self.model.model.parameters())))
-        self.files = LoadData(source)
+        self.files = LoadData(source, nv12_size=self.nv12_size, nv12_matrix=nv12, nv12_chunk=self.batch_size)
+        if nv12 is None and any(p.lower().endswith('.nv12') for p in self.files.files):
+            raise ValueError('.nv12 sources need nv12=MATRIX (--nv12 MATRIX) and their frame size')
         self.source = source
 
     def model_switch(self, model, img_size):
@@ -113,7 +127,7 @@ class Inferer:
         2 box) and its Laplacian energy; a track without a shot has ``id 0 0 0 0 -``."""
         if self.track:
             self._track_begin(crop_size)
-        if self.device.type != 'cpu' and (self.tile is not None or self.batch_size > 1):
+        if self.device.type != 'cpu' and (self.tile is not None or self.batch_size > 1 or self.nv12 is not None):
             groups = self._gpu_groups(conf_thres, iou_thres, max_det, save_crops, crop_size)
         else:
             groups = self._per_image(conf_thres, iou_thres, classes, agnostic_nms, max_det, save_crops, crop_size)
@@ -142,6 +156,8 @@ class Inferer:
         if gpu:
             from yolov6.hip import runtime
         for img_src, img_path, _ in self.files:
+            if self.nv12 is not None:       # (CPU only: a GPU takes NV12 through _gpu_groups) NV12 in, nv12_to_bgr_np, the existing path
+                img_src = nv12_to_bgr_np(self._as_nv12(img_src))
             if gpu:      # letterbox + BGR->RGB + /255 in one HIP kernel on the uploaded frame
                 frame = torch.from_numpy(np.ascontiguousarray(img_src)).to(self.device)
                 img = runtime.preprocess_letterbox(frame, self.img_size, self.stride,
@@ -189,7 +205,8 @@ class Inferer:
         from yolov6.core.tiles import plan_tiles
         from yolov6.data.datasets import imread_bgr
         B, dtype = self.batch_size, (torch.float16 if self.half else torch.float32)
-        frames = self._frames_ahead(prefetch_frames, imread_bgr)
+        decode = imread_bgr if self.nv12 is None else (lambda p: self._as_nv12(imread_bgr(p)))     # the encoder runs on the pool too
+        frames = ((self._as_nv12(f) if self.nv12 is not None else f, p) for f, p in self._frames_ahead(prefetch_frames, decode))
 
         def frame_groups():
             inputs = {}                     # (H, W) -> persistent [B,3,H,W] input buffer
@@ -392,8 +409,19 @@ class Inferer:
                 for frame in self.files._frames_of(p):
                     yield frame, p
 
+    def _as_nv12(self, frame):
+        """A frame as the host ``Nv12Frame`` the source would have delivered: a BGR array is encoded (``bgr_to_nv12_np``, an odd
+        last row / column cut off first), an ``Nv12Frame`` is passed on."""
+        if isinstance(frame, Nv12Frame):
+            return frame
+        h, w = frame.shape[0] & ~1, frame.shape[1] & ~1
+        return bgr_to_nv12_np(np.ascontiguousarray(frame[:h, :w]), self.nv12)
+
     def save_outputs(self, img_src, img_path, det, save_dir, save_txt, save_img):
-        """The label lines and the annotated image of one frame's rescaled, rounded detections (reference :100-120)."""
+        """The label lines and the annotated image of one frame's rescaled, rounded detections (reference :100-120).  An
+        ``Nv12Frame`` is converted on the host only when the image is saved."""
+        if save_img and isinstance(img_src, Nv12Frame):
+            img_src = nv12_to_bgr_np(img_src)
         rel_path = osp.relpath(osp.dirname(img_path), osp.dirname(self.source))
         save_path = osp.join(save_dir, rel_path, osp.basename(img_path))
         txt_path = osp.join(save_dir, rel_path, osp.splitext(osp.basename(img_path))[0])

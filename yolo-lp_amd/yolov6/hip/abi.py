@@ -29,6 +29,7 @@ VARIANT_SHORT = {
     LP_VARIANT_PIPE16_S2A: 'Xa', LP_VARIANT_PIPE16_S2B: 'Xb',
 }
 LP_FRAMES_PER_LAUNCH = 64   # lp_preprocess_letterbox_batch / lp_rescale_round_batch / lp_plate_crops_batch: frames per launch
+LP_NV12_PER_LAUNCH = 32     # lp_preprocess_nv12_batch: slots per launch (its table entries are larger)
 LP_MERGE_MAX_TILES, LP_MERGE_MAX_CANDIDATES = 64, 16384   # lp_merge_tiles: tiles per frame, tiles_of_frame * max_det_t
 LP_TRACK_MAX_TRACKS, LP_TRACK_MAX_DETS, LP_TRACK_MAX_CLS = 128, 128, 64   # lp_track_update: slots per stream, rows per frame, classes per head
 LP_EVAL_NCOUNTS = 43  # lp_eval_counts: length of the counts vector (include/lp_hip.h)
@@ -57,6 +58,19 @@ class TileDesc(ctypes.Structure):
     """lp_tile_desc"""
     _fields_ = [('img', c_void_p), ('h0', c_int), ('w0', c_int), ('y0', c_int), ('x0', c_int), ('th', c_int), ('tw', c_int),
                 ('rh', c_int), ('rw', c_int), ('top', c_int), ('left', c_int)]
+
+
+class Nv12Desc(ctypes.Structure):
+    """lp_nv12_desc"""
+    _fields_ = [('y', c_void_p), ('uv', c_void_p), ('pitch_y', c_int), ('pitch_uv', c_int), ('h0', c_int), ('w0', c_int),
+                ('y0', c_int), ('x0', c_int), ('th', c_int), ('tw', c_int), ('rh', c_int), ('rw', c_int), ('top', c_int),
+                ('left', c_int), ('matrix', c_int)]
+
+
+class Nv12BgrDesc(ctypes.Structure):
+    """lp_nv12_bgr_desc"""
+    _fields_ = [('y', c_void_p), ('uv', c_void_p), ('pitch_y', c_int), ('pitch_uv', c_int), ('h0', c_int), ('w0', c_int),
+                ('matrix', c_int), ('out', c_void_p)]
 
 
 class TileRef(ctypes.Structure):
@@ -123,6 +137,8 @@ SYMBOLS = {
     'lp_preprocess_letterbox_batch': (c_int, [POINTER(FrameDesc), c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     'lp_rescale_round_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(RescaleDesc), c_void_p]),
     'lp_preprocess_tiles_batch': (c_int, [POINTER(TileDesc), c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'lp_preprocess_nv12_batch': (c_int, [POINTER(Nv12Desc), c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'lp_nv12_to_bgr_batch': (c_int, [POINTER(Nv12BgrDesc), c_int, c_void_p]),
     'lp_merge_tiles_workspace_bytes': (c_size_t, [c_int, c_int]),
     'lp_merge_tiles': (c_int, [c_void_p, c_void_p, POINTER(TileRef), c_int, c_int, POINTER(c_int), c_int, c_double, c_int, c_int, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -22,6 +22,7 @@ from yolov6.core.frames import letterbox_placement
 from yolov6.core.tiles import hw_pair, plan_frames, tiles_per_frame
 from yolov6.hip import abi
 from yolov6.layers import common as L
+from yolov6.utils.nv12 import Nv12Frame, is_nv12_list
 
 DET_CROSSOVER = 0.5   # candidate density (candidates / anchors) above which forward + lp_nms beats the detections-only forward
 _DT = {torch.float16: abi.LP_F16, torch.bfloat16: abi.LP_BF16, torch.float32: abi.LP_F32}
@@ -791,6 +792,23 @@ def _frames_device(frames):
     return dev
 
 
+def _nv12_device(frames):
+    """The one device of a non-empty list of ``Nv12Frame`` whose planes are CUDA tensors (ValueError otherwise)."""
+    dev = frames[0].device
+    for f in frames:
+        if not (isinstance(f, Nv12Frame) and f.is_cuda and f.device == dev):
+            raise ValueError('NV12 frames must be Nv12Frame objects with CUDA planes on one device')
+    return dev
+
+
+def _frames_on(frames, what='frames'):
+    """(device, is_nv12) of a non-empty list of frames of ONE kind: contiguous uint8 CUDA [h,w,3] BGR tensors, or ``Nv12Frame``
+    objects with CUDA planes (a mixed list is a ValueError)."""
+    if is_nv12_list(frames, what):
+        return _nv12_device(frames), True
+    return _frames_device(frames), False
+
+
 def _buffer(buf, shape, dtype, device, what='out'):
     """A caller's persistent output buffer, checked; a new tensor of that ``shape`` / ``dtype`` on ``device`` when it is None."""
     if buf is None:
@@ -807,7 +825,7 @@ def _batch_on(frames, n, dtype, batch, what):
         raise TypeError('unsupported input dtype %s' % dtype)
     if not frames:
         raise ValueError('%s needs at least one frame' % what)
-    dev = _frames_device(frames)
+    dev, _ = _frames_on(frames, what)
     B = n if batch is None else int(batch)
     if B < n or B < 1:
         raise ValueError('batch %d < %d images (or < 1)' % (B, n))
@@ -822,6 +840,59 @@ def _check_det_count(det, count, what='det', min_batch=0):
     if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.numel() == det.shape[0]
             and count.device == det.device):
         raise ValueError('the count of %s must be a contiguous CUDA int32 [B] tensor on its device' % what)
+
+
+def nv12_to_bgr(frames, out=None):
+    """BGR device frames of a list of ``Nv12Frame`` with CUDA planes on one device (lp_nv12_to_bgr_batch, one launch per 64
+    frames, on the current stream): a list of contiguous uint8 [h,w,3] tensors, bit for bit ``nv12_to_bgr_np`` of each frame.
+    For the callers that need the frame itself -- plate crops, the best-shot gallery, saving images; detection reads NV12
+    directly.  ``out``: a list of persistent [h,w,3] uint8 buffers to write (any alignment); by default the frames are views
+    of one new buffer, at 256-byte aligned bases."""
+    if not frames:
+        return []
+    dev = _nv12_device(frames)
+    if out is None:
+        offs, n = [], 0
+        for f in frames:
+            offs.append(n)
+            n += (f.h * f.w * 3 + 255) // 256 * 256
+        buf = torch.empty(n, dtype=torch.uint8, device=dev)
+        out = [buf[o:o + f.h * f.w * 3].view(f.h, f.w, 3) for f, o in zip(frames, offs)]
+    else:
+        out = list(out)
+        if len(out) != len(frames):
+            raise ValueError('%d output buffers for %d frames' % (len(out), len(frames)))
+        out = [_buffer(o, (f.h, f.w, 3), torch.uint8, dev, 'out[%d]' % k) for k, (o, f) in enumerate(zip(out, frames))]
+    desc = (abi.Nv12BgrDesc * len(frames))()
+    for d, f, o in zip(desc, frames, out):
+        d.y, d.uv, d.pitch_y, d.pitch_uv, d.h0, d.w0 = f.y.data_ptr(), f.uv.data_ptr(), f.pitch_y, f.pitch_uv, f.h, f.w
+        d.matrix, d.out = f.matrix_id, o.data_ptr()
+    with torch.cuda.device(dev):
+        abi.check(abi.load().lp_nv12_to_bgr_batch(desc, len(frames), _stream_ptr(dev)), 'lp_nv12_to_bgr_batch')
+    return out
+
+
+def _bgr_frames(frames):
+    """``frames`` as BGR device frames: an NV12 list converted once (``nv12_to_bgr``), a BGR list as it is; None entries stay."""
+    live = [f for f in frames if f is not None]
+    if not live or not is_nv12_list(live):
+        return frames
+    it = iter(nv12_to_bgr(live))
+    return [None if f is None else next(it) for f in frames]
+
+
+def _preprocess_nv12(frames, plans, geoms, B, H, W, dtype, out, dev):
+    """lp_preprocess_nv12_batch: region ``plans[k]`` = (frame index, y0, x0, th, tw) of the NV12 ``frames`` with the letterbox
+    geometry ``geoms[k]`` into slot k of ``out`` [B,3,H,W]; no BGR frame is created."""
+    desc = (abi.Nv12Desc * max(len(plans), 1))()
+    for d, (k, y0, x0, th, tw), (rh, rw, top, left) in zip(desc, plans, geoms):
+        f = frames[k]
+        d.y, d.uv, d.pitch_y, d.pitch_uv, d.h0, d.w0 = f.y.data_ptr(), f.uv.data_ptr(), f.pitch_y, f.pitch_uv, f.h, f.w
+        d.y0, d.x0, d.th, d.tw, d.rh, d.rw, d.top, d.left, d.matrix = y0, x0, th, tw, rh, rw, top, left, f.matrix_id
+    with torch.cuda.device(dev):
+        abi.check(abi.load().lp_preprocess_nv12_batch(desc, len(plans), B, _dptr(out), _DT[dtype], H, W, _stream_ptr(dev)),
+                  'lp_preprocess_nv12_batch')
+    return out
 
 
 def preprocess_letterbox(frame_bgr_u8, img_size, stride, dtype, auto=True):
@@ -846,7 +917,8 @@ def preprocess_frames(frames, img_size, stride, dtype, auto=True, batch=None, ou
     (rh, rw, top, left) from the host letterbox arithmetic.  With ``auto=True`` every frame must letterbox to the same
     (H, W); ``auto=False`` letterboxes each to exactly ``img_size``.  ``batch`` (>= len(frames)) sets B: slots past the
     frames are padding (114/255).  ``out``: a persistent [B,3,H,W] input buffer to write (graphs are keyed on the
-    input pointer)."""
+    input pointer).  A list of ``Nv12Frame`` (CUDA planes) is taken instead of BGR tensors: the conversion is fused into the
+    letterbox (lp_preprocess_nv12_batch) and x equals, bit for bit, that of the frames ``nv12_to_bgr`` gives."""
     dev, B = _batch_on(frames, len(frames), dtype, batch, 'preprocess_frames')
     places = [letterbox_placement(f.shape, img_size, stride, auto) for f in frames]
     geoms, hws = [p[:4] for p in places], set(p[4:] for p in places)
@@ -855,6 +927,8 @@ def preprocess_frames(frames, img_size, stride, dtype, auto=True, batch=None, ou
                          % (sorted(hws), [tuple(f.shape[:2]) for f in frames]))
     H, W = hws.pop()
     out = _buffer(out, (B, 3, H, W), dtype, dev)
+    if isinstance(frames[0], Nv12Frame):
+        return _preprocess_nv12(frames, [(k, 0, 0, f.h, f.w) for k, f in enumerate(frames)], geoms, B, H, W, dtype, out, dev), geoms
     desc = (abi.FrameDesc * len(frames))()
     for d, f, (rh, rw, top, left) in zip(desc, frames, geoms):
         d.img, d.h0, d.w0, d.rh, d.rw, d.top, d.left = f.data_ptr(), f.shape[0], f.shape[1], rh, rw, top, left
@@ -916,7 +990,9 @@ def detect_frames(model, frames, img_size, conf_thres, iou_thres, max_det, auto=
     sizes with ``auto=False``): ``preprocess_frames`` -> ``detect_padded`` -> ``rescale_round_batch``, then one host read of
     the counts.  Returns a list of [n_i, 28] tensors in source-image pixels, rounded: per frame what Inferer.infer returns,
     bit for bit.  The input dtype is the model's parameter dtype (Inferer's fp16 / fp32 input); ``batch`` / ``out`` as in
-    ``preprocess_frames`` (padding slots let a short tail reuse a bound batch size)."""
+    ``preprocess_frames`` (padding slots let a short tail reuse a bound batch size).  ``frames`` may be a list of ``Nv12Frame``
+    instead (the conversion is fused into the letterbox; no BGR frame is created): the result is, bit for bit, that of the frames
+    ``nv12_to_bgr`` gives."""
     det, count = detect_frames_padded(model, frames, img_size, conf_thres, iou_thres, max_det, auto, batch, out)
     return _unpad(det, count.cpu().tolist(), len(frames))
 
@@ -950,9 +1026,10 @@ def plate_crops(frames, det, count, crop_hw=(64, 192), max_crops=None, out=None,
     the four corners, 2 = along the box (the corners are not a convex quad of area >= 1), 3 = neither is usable (zeros),
     0 = no such detection (the crop's bytes are left as they were).  ``max_crops`` defaults to 16 (each slot is Hc*Wc*3
     bytes); ``out`` / ``status``: persistent buffers of those shapes.  yolov6.utils.plate_crop.plate_crops_np is the same
-    computation on the CPU, bit for bit."""
+    computation on the CPU, bit for bit.  A list of ``Nv12Frame`` is converted with ``nv12_to_bgr`` first."""
     if not frames:
         raise ValueError('plate_crops needs at least one frame')
+    frames = _bgr_frames(frames)            # an NV12 list is converted once, on this stream
     dev = _frames_device(frames)
     Hc, Wc = _crop_size(crop_hw)
     n, m = len(frames), 16 if max_crops is None else int(max_crops)
@@ -985,6 +1062,7 @@ def crop_sharpness(crops, status, out=None):
 def _unpad_with_crops(frames, det, count, crop_hw):
     """(dets, crops, status) of the ``*_with_crops`` entry points from a padded result in frame pixels: the one host read of
     the counts, then the crops packed, frame b's n_b right behind frame b-1's (``crop_hw``: checked by ``_crop_size``)."""
+    frames = _bgr_frames(frames)            # an NV12 list is converted once, on this stream, before the host read
     counts = count.cpu().tolist()
     ns = [max(0, min(int(c), det.shape[1])) for c in counts[:len(frames)]]
     offs = np.concatenate([[0], np.cumsum(ns)]).astype(int).tolist()
@@ -1019,6 +1097,12 @@ def preprocess_tiles(frames, plans, img_size, stride, dtype, batch=None, out=Non
     dev, B = _batch_on(frames, len(plans), dtype, batch, 'preprocess_tiles')
     H, W = hw_pair(img_size)
     out = _buffer(out, (B, 3, H, W), dtype, dev)
+    if isinstance(frames[0], Nv12Frame):    # the same regions and geometry through the fused kernel
+        for f, *_ in plans:
+            if not 0 <= f < len(frames):
+                raise ValueError('tile of frame %d: %d frames' % (f, len(frames)))
+        geoms = [letterbox_placement((th, tw), [H, W], stride, auto=False)[:4] for _, _, _, th, tw in plans]
+        return _preprocess_nv12(frames, plans, geoms, B, H, W, dtype, out, dev), geoms
     desc = (abi.TileDesc * max(len(plans), 1))()
     geoms = []
     for d, (f, y0, x0, th, tw) in zip(desc, plans):
@@ -1087,7 +1171,7 @@ def detect_tiles_padded(model, frames, tiles, img_size, conf_thres, iou_thres, t
     padded, so the engine is bound once) through ``preprocess_tiles`` -> ``detect_padded``, then one ``rescale_round_batch``
     over all tiles with each tile's (th, tw) as its source image.  Returns (det_t [T',tile_max_det,28], count_t [T']) on the
     device, T' = len(tiles) rounded up to a multiple of ``batch``; no host sync."""
-    dev = _frames_device(frames)
+    dev, _ = _frames_on(frames, 'detect_tiled')
     dtype = next(model.parameters()).dtype
     H, W = hw_pair(img_size)
     B = int(batch)
@@ -1132,7 +1216,8 @@ def detect_tiled(model, frames, img_size, conf_thres, iou_thres, max_det, tile_h
     (``merge_tiles``: threshold ``iou_thres``, ``metric`` 'iou' or 'ios', cut-plate ``border``), then ONE host read of the
     per-frame counts.  Returns a list of [n_f, 28] tensors in frame pixels.  ``tile_max_det``: detections kept per tile
     (default min(max_det, 16384 // most tiles of any frame)).  With ``tile_hw`` >= the frame this is
-    ``detect_frames(auto=False)``, bit for bit."""
+    ``detect_frames(auto=False)``, bit for bit.  ``frames`` may be a list of ``Nv12Frame`` instead: the tiles are cut from the planes
+    (lp_preprocess_nv12_batch) and the result equals that of the converted frames."""
     det, count = detect_tiled_padded(model, frames, img_size, conf_thres, iou_thres, max_det, tile_hw, overlap, overview, metric,
                                      border, batch, tile_max_det)
     return _unpad(det, count.cpu().tolist())
@@ -1292,7 +1377,7 @@ class PlateTracker:
         status, valid; shot_q [S,max_ended] int64 holding the unsigned sharpness; shot_det [S,max_ended,28] fp32 = the shot's
         row with its per-frame confidences), line-parallel to ended_i / ended_f; persistent buffers per shape.  The crop of a
         record without a shot (valid 0) is left as it was.  yolov6.utils.best_shot.BestShotNp is the same computation on the
-        CPU, bit for bit."""
+        CPU, bit for bit.  ``frames`` may be ``Nv12Frame``s instead: they are converted once (``nv12_to_bgr``) on this stream."""
         from yolov6.utils import track
         if self._shots is None:
             raise RuntimeError('call enable_best_shot() first')
@@ -1305,8 +1390,9 @@ class PlateTracker:
             if f is None and stream_of[b] >= 0:
                 raise ValueError('frame %d of stream %d is missing' % (b, stream_of[b]))
         live = [f for f in frames if f is not None]
-        if live and _frames_device(live) != self.device:
+        if live and _frames_on(live, 'update_with_shots')[0] != self.device:
             raise ValueError('frames must be on the tracker\'s device %s' % self.device)
+        frames = _bgr_frames(frames)        # an NV12 list is converted once, on this stream
         out = self.update(det, count, stream_of, flush, max_ended)
         crops, status, sharp = self._shot_crops(frames, det, count, stream_of, max_ended)
         if B:
