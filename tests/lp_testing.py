@@ -306,6 +306,40 @@ def model_layer_signatures(name, size):
     return rec.sigs
 
 
+# Layers at the edges of the kernel selection rules (pick_cfg, conv_pipe_fits, op_fam16): 3x3 layers as (id, sources, cout, stride,
+# families that take the op besides the generic kernel, family of the default the rule picks at finalize with the production
+# settings).  The LDS tables of the kernels decide them: PIPE / PIPE16 hold 1024 biases and 64 K-chunks of 16 stored channels
+# (PIPE_MAXC, PIPE_MAXCHUNKS), PIPE16_V 512 and 32, S2P16 512 and 64; PIPE16 wants the 128-row packing and K-chunks a multiple of four.
+RULE_ROWS = [
+    ('576-128-s1', [576], 128, 1, {'PIPE', 'PIPE16'}, 'PIPE16'),               # 36 chunks: past PIPE16_V's table
+    ('1024-128-s1', [1024], 128, 1, {'PIPE', 'PIPE16'}, 'PIPE16'),             # 64 chunks: the chunk table exactly full
+    ('512+512-128-s1', [512, 512], 128, 1, {'PIPE', 'PIPE16'}, 'PIPE16'),
+    ('1088-128-s1', [1088], 128, 1, set(), 'generic'),                         # 68 chunks: past every chunk table
+    ('64-640-s1', [64], 640, 1, {'PIPE', 'PIPE16'}, 'PIPE16'),                 # 5 cout tiles of 128: past PIPE16_V's bias table
+    ('64-1024-s1', [64], 1024, 1, {'PIPE', 'PIPE16'}, 'PIPE16'),               # 8 tiles: the bias table exactly full
+    ('64-1152-s1', [64], 1152, 1, set(), 'generic'),                           # 9 tiles
+    ('64-960-s1', [64], 960, 1, {'PIPE'}, 'generic'),                          # 64-row packing, 15 tiles: PIPE_B only
+    ('64-1088-s1', [64], 1088, 1, set(), 'generic'),                           # 64-row packing, 17 tiles
+    ('1024-128-s2', [1024], 128, 2, {'S2P16'}, 'generic'),                     # 64 chunks (the stride-2 family is opt-in: not the default)
+    ('1088-128-s2', [1088], 128, 2, set(), 'generic'),
+    ('64-640-s2', [64], 640, 2, set(), 'generic'),                             # 5 tiles: past S2P16's bias table
+]
+CONV3_FAMILIES = {'generic', 'PIPE', 'PIPE16', 'PIPE16_V', 'S2P16'}             # kernel families with 3x3 variants a test can ask for
+
+
+def det_workspace_views(ws, B, N):
+    """The detections-only workspace as lp_nms.hip carves it (256-byte aligned pieces): views of the candidate counts [B] int32, the
+    sort keys [B][NP] int64 (NP = N rounded up to a power of two, at least 64) and the candidate rows [B][N][28] fp32."""
+    off = (ws.data_ptr() + 255) // 256 * 256 - ws.data_ptr()
+    cnt = ws[off:][:4 * B].view(torch.int32)
+    NP = 1 << max(6, (N - 1).bit_length())
+    keys_off = off + (4 * B + 255) // 256 * 256
+    keys = ws[keys_off:][:8 * B * NP].view(torch.int64).view(B, NP)
+    rows_off = keys_off + (8 * B * NP + 255) // 256 * 256
+    rows = ws[rows_off:][:4 * B * N * 28].view(torch.float32).view(B, N, 28)
+    return cnt, keys, rows
+
+
 def ref_images(B, most=3):
     """Images of a batch the float64 reference of the elementwise check is computed for: all of a small batch, else the first,
     the middle and the last one (the kernels still run the whole batch; the max-norm check beside it covers every image)."""

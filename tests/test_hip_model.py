@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from conftest import load_golden, REPO
-from lp_testing import synth_pred, rel_err
+from lp_testing import det_workspace_views, synth_pred, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -545,14 +545,7 @@ def test_box_predictors_for_candidates_only_write_the_same_rows(name, kw, B, H, 
             ws.fill_(0xFF)                                       # NaN rows: what the kernels do not write stays recognisable
             _, _, N = eng.forward_det(x, conf, ws=ws)
             torch.cuda.synchronize()
-            # the workspace as lp_nms.hip carves it (256-byte aligned pieces): counts [B], keys [B][NP], candidate rows [B][N][28], ...
-            off = (ws.data_ptr() + 255) // 256 * 256 - ws.data_ptr()
-            cnt = ws[off:][:4 * B].view(torch.int32).clone()
-            NP = 1 << max(6, (N - 1).bit_length())
-            keys_off = off + (4 * B + 255) // 256 * 256
-            keys = ws[keys_off:][:8 * B * NP].view(torch.int64).view(B, NP).clone()
-            rows_off = keys_off + (8 * B * NP + 255) // 256 * 256
-            rows = ws[rows_off:][:4 * B * N * 28].view(torch.float32).view(B, N, 28).clone()
+            cnt, keys, rows = [t.clone() for t in det_workspace_views(ws, B, N)]     # counts [B], keys [B][NP], candidate rows [B][N][28]
             det = runtime.nms_candidates((ws, B, N), 0.45, 300, want_keep=True)
             torch.cuda.synchronize()
             got[mode] = (cnt, keys, rows, det)

@@ -265,7 +265,7 @@ bool conv_pipe_fits(int dtype, int pcfg, int cb_pack, int ksize, int stride, int
     if (dtype == LP_F32 || pcfg < 0 || (pcfg >= PIPE_COUNT && !pipe_is_16(pcfg)) || ksize != 3 || stride != 1 || mode != MODE_ACT || nphase != 1) return false;
     const ConvShape s = conv_pipe_shape(pcfg);
     if (pipe_is_16v(pcfg) && (nct * s.CB > 512 || nchunks > 32)) return false;   // PIPE16V_MAXC / PIPE16V_MAXCHUNKS (its LDS tables)
-    return s.CB == cb_pack && nct * s.CB <= 1024;   // 1024 = PIPE_MAXC (bias table in LDS)
+    return s.CB == cb_pack && nct * s.CB <= 1024 && nchunks <= 64;   // PIPE_MAXC (bias table in LDS), PIPE_MAXCHUNKS (chunk table in LDS)
 }
 
 static int g_ncu[16] = {0};
@@ -359,6 +359,7 @@ int conv_pipe_launch(int dtype, int pcfg, const ConvArgs& a, hipStream_t st) {
         if (a.out2 && a.out2_pix_stride > stride) stride = a.out2_pix_stride;
         if (((long long)a.TH * a.Wo + a.TW) * stride + 2048 >= (1ll << 31)) return fail(LP_ERR_ARG, "conv3x3 pipe16v: a tile's rows span more than 2^31 elements");
     }
+    if (a.chunk_begin[a.nsrc] > 64) return fail(LP_ERR_ARG, "conv3x3 pipe: more K-chunks than the kernel's LDS chunk table holds");   // PIPE_MAXCHUNKS
     if (a.nsrc < 1 || a.nsrc > LP_MAX_SRC || a.nct < 1 || a.nct * s.CB > 1024 || a.nphase != 1 || a.out_scale != 1 || a.Ho != a.H || a.Wo != a.W)
         return fail(LP_ERR_ARG, "conv3x3 pipe: not a 3x3 stride-1 layer this kernel runs");
     switch (dtype) {

@@ -1002,18 +1002,25 @@ static int run_head_det(lp_engine* e, size_t idx, const DetCtx& dc, hipStream_t 
         a.out_img_stride = (long long)N * LP_DET_COLS;
         static const bool no_box_stream = getenv("LP_NO_BOX_STREAM") != nullptr;     // (A/B switch: the generic decode kernel)
         static const bool no_box_sparse = getenv("LP_NO_BOX_SPARSE") != nullptr;     // (A/B switch: boxes of every anchor)
-        if (!no_box_stream && head_box_det_fits(a, L.cb_pack, L.ks, L.st)) {
-            // one lane: the class kernel of this level has appended its candidates in front of this launch, nobody else in between
-            if (!no_box_sparse && op.box_sparse && e->box_sparse_ok && (e->n_lanes <= 1 || e->single_lane) && e->box_ord[idx] >= 0 && N >= 8) {
+        // one lane: the class kernel of this level has appended its candidates in front of this launch, nobody else in between
+        const bool snap_ok = !no_box_sparse && e->box_sparse_ok && (e->n_lanes <= 1 || e->single_lane) && e->box_ord[idx] >= 0 && N >= 8;
+        // whether box op j runs the streaming kernel here (either form of it leaves the level's snapshot when snap_ok; the generic kernel never does)
+        auto streams = [&](size_t j) { const Launch& Lj = e->launches[j]; return !no_box_stream && head_box_det_fits(Lj.a, Lj.cb_pack, Lj.ks, Lj.st); };
+        if (streams(idx)) {
+            if (snap_ok) {
                 const int k = e->box_ord[idx];
                 int* const snaps = dc.w.kept;           // [4][B] ints of the NMS's `kept` array, which lp_nms_candidates only writes later
-                a.det_keys = dc.w.keys;
                 a.det_cnt = dc.w.cnt;
                 a.det_np = dc.w.NP;
-                a.det_n = N;
-                a.det_anchor0 = anchor0;
-                a.det_prev = k > 0 ? snaps + (size_t)(k - 1) * e->B : nullptr;
-                a.det_snap = snaps + (size_t)k * e->B;
+                a.det_snap = snaps + (size_t)k * e->B;  // written by the dense form as well: the level behind may run sparse
+                bool prev_snap = k == 0;                // the sparse form needs the snapshot of the level before: only a streaming launch leaves it
+                for (size_t j = 0; j < idx && !prev_snap; ++j) prev_snap = e->box_ord[j] == k - 1 && streams(j);
+                if (op.box_sparse && prev_snap) {
+                    a.det_keys = dc.w.keys;
+                    a.det_n = N;
+                    a.det_anchor0 = anchor0;
+                    a.det_prev = k > 0 ? snaps + (size_t)(k - 1) * e->B : nullptr;
+                }
             }
             return head_box_det_launch(dt, a, L.cb_pack, st);
         }

@@ -42,12 +42,15 @@ __global__ __launch_bounds__(256) void head_box_det_kernel(const ConvArgs a, con
         int hi = a.det_cnt[sb];
         hi = hi > a.det_np ? a.det_np : hi;                       // (keys beyond the list's capacity were dropped by the class kernel)
         slo = a.det_prev ? a.det_prev[sb] : 0;
-        slo = slo > hi ? hi : slo;
+        slo = slo < 0 ? 0 : (slo > hi ? hi : slo);
         sn = hi - slo;
         if (gi == 0 && threadIdx.x == 0) a.det_snap[sb] = hi;     // where the next level's entries begin
         ntiles = (sn + 31) / 32;
         t0 = (long long)gi * 4 + wave;
         tstride = (long long)gpi * 4;
+    } else if (a.det_snap) {                                      // dense form in front of a level that may run sparse: the same snapshot, one thread per image
+        const int b = blockIdx.x * 256 + threadIdx.x;
+        if (b < a.B) { const int c = a.det_cnt[b]; a.det_snap[b] = c > a.det_np ? a.det_np : c; }
     }
     if (t0 >= ntiles) return;
 
