@@ -323,8 +323,8 @@ int lp_preprocess_tiles_batch(const lp_tile_desc* desc, int n_tiles, int B, void
  *     2 bt601f (full range)                                                0, 1048576, 1858077, -360853, -748826, 1470104
  *     3 bt709f (full range)                                                0, 1048576, 1945738, -196424, -490864, 1651297
  *
- * lp_preprocess_nv12_batch: the letterbox of lp_preprocess_tiles_batch with the conversion fused in; no BGR frame exists on the
- * device.  Slot b < n of out [B,3,H,W] is bit-identical to what lp_preprocess_tiles_batch writes for the region (y0, x0, th, tw)
+ * lp_preprocess_nv12_batch: the letterbox of lp_preprocess_tiles_batch (same kernel, reading NV12 planes through another pixel
+ * source) with the conversion fused in; no BGR frame exists on the device.  Slot b < n of out [B,3,H,W] is bit-identical to what lp_preprocess_tiles_batch writes for the region (y0, x0, th, tw)
  * and the geometry (rh, rw, top, left) of the BGR frame the rule gives for the WHOLE frame: the bilinear taps clamp at the region's
  * edges, chroma is indexed by the absolute frame coordinate (odd y0, x0 are legal), rh == th && rw == tw means no resize; a whole
  * frame is the region (0, 0, h0, w0).  Slots n <= b < B are padding (114/255).  Descriptors travel by value in the kernel

@@ -42,7 +42,7 @@ def test_table_is_the_specification():
         assert nv12.MATRICES[name] == (mid, *coef)
     for _, name, _, *ints in TABLE[1:]:                 # rows 1..3: round(x * 2^20) of the float matrix
         assert list(ints) == [int(round(v * 2 ** 20)) for v in FLOAT[name][1:]], name
-    src = open(os.path.join(REPO, 'yolo-lp_amd', 'csrc', 'lp_nv12.hip')).read()
+    src = open(os.path.join(REPO, 'yolo-lp_amd', 'csrc', 'lp_nv12_color.inc')).read()
     for _, _, *coef in TABLE:                           # the kernels' table is the same one
         assert '{%s}' % ', '.join(str(c) for c in coef) in src
 

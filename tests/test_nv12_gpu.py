@@ -196,6 +196,45 @@ def test_regions_equal_region_copies_of_the_converted_frame(dtype):
         assert _bits_equal(got, spec.to(dtype).cuda())
 
 
+@functools.lru_cache(maxsize=1)
+def _one_region_list():
+    """(host frames, 33 regions of them, their numpy definition [34,3,32,32] fp32): two 64 x 96 frames into 32 x 32.  33 slots
+    cross the 32-slot split of the NV12 table and stay inside the 64-slot one of the BGR table; the special regions sit on both
+    sides of the split."""
+    from yolov6.utils.nv12 import region_nv12_np
+    hosts = [_host_frame(64, 96, 31, 'bt709'), _host_frame(64, 96, 32, 'bt601')]
+    rng = np.random.default_rng(33)
+    plans = [(1, 5, 7, 1, 1),                   # a single pixel: every tap clamps onto it
+             (0, 11, 95, 40, 1),                # one pixel wide, at the frame's right edge
+             (1, 3, 9, 32, 20),                 # ratio 1: unresized (th, tw == rh, rw), odd origin, padded left and right
+             (0, 0, 0, 64, 96)]                 # the whole frame
+    while len(plans) < 31:
+        th, tw = int(rng.integers(2, 65)), int(rng.integers(2, 97))      # >= 2: every region letterboxes to rh, rw >= 1
+        plans.append((len(plans) % 2, int(rng.integers(0, 65 - th)), int(rng.integers(0, 97 - tw)), th, tw))
+    plans += [(0, 62, 1, 2, 95),                # slot 31: two rows at the bottom edge, resized to one
+              (1, 31, 63, 32, 32)]              # slot 32, past the split: unresized, odd (y0, x0), touching the bottom-right corner
+    spec = torch.full((34, 3, 32, 32), 114.0) / 255
+    for k, (f, y0, x0, th, tw) in enumerate(plans):
+        spec[k] = torch.from_numpy(region_nv12_np(hosts[f], y0, x0, th, tw, [32, 32], 32))
+    return hosts, plans, spec
+
+
+@pytest.mark.parametrize('dtype', [torch.float16, torch.float32])
+def test_one_region_list_through_both_sources_of_the_letterbox_kernel(dtype):
+    """The same regions through ``preprocess_tiles`` on the BGR frames and on their NV12 form: equal bytes, and the BGR result
+    equals ``region_nv12_np`` -- the numpy specification is the anchor, not the other source of the kernel."""
+    from yolov6.hip import runtime
+    hosts, plans, spec = _one_region_list()
+    assert len(plans) == 33 and any((th, tw) == (32, 32) for *_, th, tw in plans)
+    B = 34                                                                            # one padding slot
+    bgr, g1 = runtime.preprocess_tiles([_bgr_dev(f) for f in hosts], plans, [32, 32], 32, dtype, batch=B, out=_nan_out(B, 32, 32, dtype))
+    nv, g2 = runtime.preprocess_tiles([_place(f, extra_y=3, extra_uv=2) for f in hosts], plans, [32, 32], 32, dtype, batch=B,
+                                      out=_nan_out(B, 32, 32, dtype))
+    assert g1 == g2 and g1[2] == (32, 20, 0, 6) and g1[32] == (32, 32, 0, 0)             # the unresized regions are unresized
+    assert _bits_equal(bgr, spec.to(dtype).cuda())
+    assert _bits_equal(nv, bgr)
+
+
 # ---- 5. the runtime entry points --------------------------------------------------------------------------------------------------
 def _tiny(dtype):
     from yolov6.utils.synth import build_synthetic

@@ -35,7 +35,7 @@ detection density; and a worst case on 16 constant rows per stream whose sharpne
 every row of every frame replaces its shot (16 x 36 KB copied per stream by one workgroup).
 With ``--nv12 [MATRIX]`` the same seeded frames are sent as BGR and as NV12 (encoded on the host before any clock starts, as a
 decoder would deliver them), alternating, ``--runs`` timed runs each: frames/s of FrameBatcher + ``detect_frames``; the stages of
-one batch from events for both kinds (H2D, letterbox -- lp_preprocess_letterbox_batch on the BGR frames against
+one batch from events for both kinds (H2D, letterbox -- lp_preprocess_tiles_batch on the BGR frames against
 lp_preprocess_nv12_batch on the NV12 frames, in the same run --, detect, rescale), the NV12 convert stage (lp_nv12_to_bgr_batch,
 with its GB/s over 1.5 B read + 3 B written per pixel) and, with ``--crops N``, the crop stage behind it.  With ``--tile`` the
 same for tiled detection: frames/s of ``detect_tiled_with_crops`` for both kinds and the stage times of each.

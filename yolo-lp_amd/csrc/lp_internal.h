@@ -41,7 +41,7 @@ template <typename K> inline int set_max_lds_once(K kernel, int bytes, std::atom
     return LP_OK;
 }
 
-// Per-axis coefficients of the OpenCV INTER_LINEAR fixed-point resize (lp_prepost.hip, lp_frames.hip): source index and the
+// Per-axis coefficients of the OpenCV INTER_LINEAR fixed-point resize (preprocess_kernel, letterbox_kernel): source index and the
 // two 11-bit weights of destination index d at scale src/dst.
 __device__ __forceinline__ void resize_coef(int d, double scale, int src, int* s0, int* a0, int* a1) {
     // cv::resize: fx = (dx + 0.5) * scale - 0.5 ; sx = floor(fx) ; fx -= sx ; clamps at the borders
@@ -55,6 +55,17 @@ __device__ __forceinline__ void resize_coef(int d, double scale, int src, int* s
     *a0 = (int)rintf(c0);   // saturate_cast<short>(cvRound(v * INTER_RESIZE_COEF_SCALE))
     *a1 = (int)rintf(c1);
 }
+// One channel of that resize: the taps t00, t01 of source row y0 and t10, t11 of row y1 at columns x0, x1, blended with the
+// column weights (a0, a1) and the row weights (b0, b1) of resize_coef.
+__device__ __forceinline__ int resize_blend(int t00, int t01, int t10, int t11, int a0, int a1, int b0, int b1) {
+    const int h0v = t00 * a0 + t01 * a1;   // HResizeLinear (scaled by 2048)
+    const int h1v = t10 * a0 + t11 * a1;
+    return (((b0 * (h0v >> 4)) >> 16) + ((b1 * (h1v >> 4)) >> 16) + 2) >> 2;   // VResizeLinear
+}
+constexpr int LETTERBOX_PAD = 114;      // the letterbox's border colour, all three channels (letterbox() of data_augment.py)
+
+// The plane rules of an NV12 frame shared by lp_preprocess_nv12_batch and lp_nv12_to_bgr_batch (lp_nv12.hip); an empty string: fine.
+std::string plane_fault(const unsigned char* y, const unsigned char* uv, int pitch_y, int pitch_uv, int h0, int w0, int matrix);
 
 inline size_t dtype_size(int dt) { return dt == LP_F32 ? 4 : 2; }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int y = (int)(i / W), x = (int)(i - (long long)y * W);
         const int ry = y - top, rx = x - left;
-        int bgr[3] = {114, 114, 114};
+        int bgr[3] = {LETTERBOX_PAD, LETTERBOX_PAD, LETTERBOX_PAD};
         if (ry >= 0 && ry < rh && rx >= 0 && rx < rw) {
             if (!resize) {
                 const unsigned char* p = img + ((long long)ry * w0 + rx) * 3;
@@ -33,11 +33,8 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __
                 const unsigned char* r0 = img + (long long)y0 * w0 * 3;
                 const unsigned char* r1 = img + (long long)y1 * w0 * 3;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int h0v = r0[x0 * 3 + c] * a0 + r0[x1 * 3 + c] * a1;   // HResizeLinear (scaled by 2048)
-                    const int h1v = r1[x0 * 3 + c] * a0 + r1[x1 * 3 + c] * a1;
-                    bgr[c] = (((b0 * (h0v >> 4)) >> 16) + ((b1 * (h1v >> 4)) >> 16) + 2) >> 2;   // VResizeLinear
-                }
+                for (int c = 0; c < 3; ++c)
+                    bgr[c] = resize_blend(r0[x0 * 3 + c], r0[x1 * 3 + c], r1[x0 * 3 + c], r1[x1 * 3 + c], a0, a1, b0, b1);
             }
         }
         // HWC BGR -> CHW RGB, uint8 -> float / 255 (inferer.py:195-199); the division is done in the output dtype's

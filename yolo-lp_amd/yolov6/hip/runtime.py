@@ -881,17 +881,25 @@ def _bgr_frames(frames):
     return [None if f is None else next(it) for f in frames]
 
 
-def _preprocess_nv12(frames, plans, geoms, B, H, W, dtype, out, dev):
-    """lp_preprocess_nv12_batch: region ``plans[k]`` = (frame index, y0, x0, th, tw) of the NV12 ``frames`` with the letterbox
-    geometry ``geoms[k]`` into slot k of ``out`` [B,3,H,W]; no BGR frame is created."""
-    desc = (abi.Nv12Desc * max(len(plans), 1))()
+def _letterbox_regions(frames, plans, geoms, B, H, W, dtype, out, dev):
+    """One letterbox call: region ``plans[k]`` = (frame index, y0, x0, th, tw) of ``frames`` with the letterbox geometry ``geoms[k]``
+    = (rh, rw, top, left) into slot k of ``out`` [B,3,H,W].  BGR tensors go through lp_preprocess_tiles_batch; ``Nv12Frame``s through
+    lp_preprocess_nv12_batch (the same kernel reading the planes: no BGR frame is created)."""
+    for k, *_ in plans:
+        if not 0 <= k < len(frames):
+            raise ValueError('tile of frame %d: %d frames' % (k, len(frames)))
+    nv12 = isinstance(frames[0], Nv12Frame)
+    desc = ((abi.Nv12Desc if nv12 else abi.TileDesc) * max(len(plans), 1))()
     for d, (k, y0, x0, th, tw), (rh, rw, top, left) in zip(desc, plans, geoms):
         f = frames[k]
-        d.y, d.uv, d.pitch_y, d.pitch_uv, d.h0, d.w0 = f.y.data_ptr(), f.uv.data_ptr(), f.pitch_y, f.pitch_uv, f.h, f.w
-        d.y0, d.x0, d.th, d.tw, d.rh, d.rw, d.top, d.left, d.matrix = y0, x0, th, tw, rh, rw, top, left, f.matrix_id
+        if nv12:
+            d.y, d.uv, d.pitch_y, d.pitch_uv, d.matrix = f.y.data_ptr(), f.uv.data_ptr(), f.pitch_y, f.pitch_uv, f.matrix_id
+        else:
+            d.img = f.data_ptr()
+        d.h0, d.w0, d.y0, d.x0, d.th, d.tw, d.rh, d.rw, d.top, d.left = f.shape[0], f.shape[1], y0, x0, th, tw, rh, rw, top, left
+    name = 'lp_preprocess_nv12_batch' if nv12 else 'lp_preprocess_tiles_batch'
     with torch.cuda.device(dev):
-        abi.check(abi.load().lp_preprocess_nv12_batch(desc, len(plans), B, _dptr(out), _DT[dtype], H, W, _stream_ptr(dev)),
-                  'lp_preprocess_nv12_batch')
+        abi.check(getattr(abi.load(), name)(desc, len(plans), B, _dptr(out), _DT[dtype], H, W, _stream_ptr(dev)), name)
     return out
 
 
@@ -912,7 +920,8 @@ def preprocess_letterbox(frame_bgr_u8, img_size, stride, dtype, auto=True):
 
 
 def preprocess_frames(frames, img_size, stride, dtype, auto=True, batch=None, out=None):
-    """Batched ``preprocess_letterbox`` (lp_preprocess_letterbox_batch, one launch per 64 frames): a list of contiguous
+    """Batched ``preprocess_letterbox`` (each frame as the region (0, 0, h, w) of lp_preprocess_tiles_batch, which is
+    lp_preprocess_letterbox_batch on whole frames; one launch per 64 frames): a list of contiguous
     uint8 CUDA [h,w,3] BGR frames of any sizes -> (x[B,3,H,W] of ``dtype``, geoms).  ``geoms[i]`` is frame i's
     (rh, rw, top, left) from the host letterbox arithmetic.  With ``auto=True`` every frame must letterbox to the same
     (H, W); ``auto=False`` letterboxes each to exactly ``img_size``.  ``batch`` (>= len(frames)) sets B: slots past the
@@ -927,15 +936,8 @@ def preprocess_frames(frames, img_size, stride, dtype, auto=True, batch=None, ou
                          % (sorted(hws), [tuple(f.shape[:2]) for f in frames]))
     H, W = hws.pop()
     out = _buffer(out, (B, 3, H, W), dtype, dev)
-    if isinstance(frames[0], Nv12Frame):
-        return _preprocess_nv12(frames, [(k, 0, 0, f.h, f.w) for k, f in enumerate(frames)], geoms, B, H, W, dtype, out, dev), geoms
-    desc = (abi.FrameDesc * len(frames))()
-    for d, f, (rh, rw, top, left) in zip(desc, frames, geoms):
-        d.img, d.h0, d.w0, d.rh, d.rw, d.top, d.left = f.data_ptr(), f.shape[0], f.shape[1], rh, rw, top, left
-    with torch.cuda.device(dev):
-        abi.check(abi.load().lp_preprocess_letterbox_batch(desc, len(frames), B, _dptr(out), _DT[dtype], H, W, _stream_ptr(dev)),
-                  'lp_preprocess_letterbox_batch')
-    return out, geoms
+    plans = [(k, 0, 0) + tuple(f.shape[:2]) for k, f in enumerate(frames)]      # a whole frame: the region (0, 0, h, w)
+    return _letterbox_regions(frames, plans, geoms, B, H, W, dtype, out, dev), geoms
 
 
 def _rescale_terms(ori_shape, target_shape):
@@ -1097,26 +1099,8 @@ def preprocess_tiles(frames, plans, img_size, stride, dtype, batch=None, out=Non
     dev, B = _batch_on(frames, len(plans), dtype, batch, 'preprocess_tiles')
     H, W = hw_pair(img_size)
     out = _buffer(out, (B, 3, H, W), dtype, dev)
-    if isinstance(frames[0], Nv12Frame):    # the same regions and geometry through the fused kernel
-        for f, *_ in plans:
-            if not 0 <= f < len(frames):
-                raise ValueError('tile of frame %d: %d frames' % (f, len(frames)))
-        geoms = [letterbox_placement((th, tw), [H, W], stride, auto=False)[:4] for _, _, _, th, tw in plans]
-        return _preprocess_nv12(frames, plans, geoms, B, H, W, dtype, out, dev), geoms
-    desc = (abi.TileDesc * max(len(plans), 1))()
-    geoms = []
-    for d, (f, y0, x0, th, tw) in zip(desc, plans):
-        if not 0 <= f < len(frames):
-            raise ValueError('tile of frame %d: %d frames' % (f, len(frames)))
-        rh, rw, top, left = geom = letterbox_placement((th, tw), [H, W], stride, auto=False)[:4]
-        geoms.append(geom)
-        fr = frames[f]
-        d.img, d.h0, d.w0 = fr.data_ptr(), fr.shape[0], fr.shape[1]
-        d.y0, d.x0, d.th, d.tw, d.rh, d.rw, d.top, d.left = y0, x0, th, tw, rh, rw, top, left
-    with torch.cuda.device(dev):
-        abi.check(abi.load().lp_preprocess_tiles_batch(desc, len(plans), B, _dptr(out), _DT[dtype], H, W, _stream_ptr(dev)),
-                  'lp_preprocess_tiles_batch')
-    return out, geoms
+    geoms = [letterbox_placement((th, tw), [H, W], stride, auto=False)[:4] for _, _, _, th, tw in plans]
+    return _letterbox_regions(frames, plans, geoms, B, H, W, dtype, out, dev), geoms
 
 
 _METRICS = {'iou': 0, 'ios': 1}
