@@ -536,6 +536,59 @@ int lp_best_shot_update(void* state, int n_streams, int max_tracks, int crop_h, 
                         double min_score, unsigned char* shot_crops, int32_t* shot_i, unsigned long long* shot_q, float* shot_det,
                         void* stream);
 
+/* lp_redact_plates_batch: make the plates of B frames unreadable IN PLACE, by a mosaic or a fill, in BGR frames or in the planes of
+ * NV12 frames; at most LP_FRAMES_PER_LAUNCH frames per launch, descriptors by value in the kernel arguments: nothing is uploaded,
+ * no host sync, capturable in a graph, so the call can be enqueued behind lp_rescale_round_batch.  It goes LAST: whatever reads the
+ * frames (lp_plate_crops_batch, the best-shot gallery) must be enqueued before it.  The reference has nothing here;
+ * yolov6/utils/redact.py::redact_plates_np restates the rules below bit for bit.
+ *   det [n_frames,max_det,28] fp32 in frame pixels + count [n_frames] int32 (DEVICE, read by the kernels).  For frame b every row
+ *   r < n_b = clamp(count[b], 0, max_det) is redacted: there is no cap on the plates of a frame.
+ *   Quad of a row: the rule of lp_plate_crops_batch (corners if finite, strictly convex and of area >= 1, else the box if finite
+ *   and >= 1 px on each side).  status [n_frames,max_det] int32: 1 corners, 2 box, 3 neither (nothing is written for the row),
+ *   0 for r >= n_b.
+ *   Expanded quad, fp64 op by op (no fused multiply-add): cx = 0.25 * (((x0 + x1) + x2) + x3), cy likewise, s = 1.0 + margin,
+ *   x'_k = cx + s * (x_k - cx), y'_k = cy + s * (y_k - cy).
+ *   Pixel (i, j) belongs to the row iff j in [clamp(floor(min x'), 0, w0), clamp(ceil(max x'), 0, w0)), i likewise in y and h0
+ *   (clamped in double, then converted), and its centre P = (j + 0.5, i + 0.5) satisfies ex * (P.y - a.y) - ey * (P.x - a.x) <= 0,
+ *   e = b - a, for the four edges a -> b along p0 -> p3 -> p2 -> p1 -> p0 (the label orientation; an edge belongs to the quad).
+ *   A quad partly or wholly outside the frame redacts what is inside.
+ *   Mosaic: the cell grid is anchored to the frame, cell (I, J) = rows [I * cell, min((I + 1) * cell, h0)) x the same in columns;
+ *   its value per channel is (2 * sum + n) / (2 * n) in integers over its n pixels (the mean, rounded half up) OF THE FRAME AS IT
+ *   WAS BEFORE THE CALL; a pixel that belongs to any row is replaced by its cell's value.  So the result does not depend on the
+ *   order of the rows, overlapping plates store the same bytes, and a second call with the same rows changes only bytes the first changed.
+ *   NV12: the luma plane takes the same cells on Y; the chroma plane cells of cell/2 x cell/2 samples, U and V averaged
+ *   separately by the same formula; chroma sample (ci, cj) is replaced iff any of its four luma pixels (2ci..2ci+1, 2cj..2cj+1)
+ *   belongs to a row.  The matrix plays no part (the result is not the BGR result of the converted frame).
+ *   Fill: the same pixels and chroma samples get fill[0..2], bytes in the frame's own format.
+ *   No other byte changes: pitch padding, pixels of no row, rows at or past n_b, frames whose count is <= 0.
+ * Two kernels: the first reads the frames and writes, for every cell that the bounding rectangle of a row touches, one packed
+ * entry (c0, c1, c2, 0) into the workspace (per frame a table of ceil(h0 / cell) x ceil(w0 / cell) 4-byte entries, each table at
+ * a 16-byte multiple); the second reads det, count and those entries and writes the frames.  The second looks up only entries the
+ * first wrote in the same call, so the workspace may hold anything on entry.  Fill is the second kernel alone (workspace unused).
+ * Every argument is checked before the first launch (LP_ERR_ARG names the frame; nothing is launched): null desc, p or status,
+ * null det or count with n_frames > 0, format, p0 null, p1 null (NV12) or non-null (BGR), the NV12 plane rules of lp_nv12_desc,
+ * pitch0 < 3 * w0 (BGR), h0 or w0 < 1, mode, cell odd or outside 2..LP_REDACT_MAX_CELL (mosaic), margin outside [0, 4] or NaN,
+ * max_det < 1, and in mosaic mode a workspace that is null, not 16-byte aligned or smaller than lp_redact_workspace_bytes.
+ * n_frames == 0: LP_OK. */
+#define LP_REDACT_MAX_CELL 64
+typedef struct lp_redact_desc {
+    unsigned char* p0;      /* BGR: the frame, uint8 [h0][w0][3], rows pitch0 >= 3*w0 bytes apart, any alignment.  NV12: the luma plane */
+    unsigned char* p1;      /* BGR: NULL.  NV12: the chroma plane (2-byte aligned, U first) */
+    int pitch0, pitch1;     /* NV12: pitch0 >= w0, pitch1 >= w0 and even (the plane rules of lp_nv12_desc) */
+    int h0, w0;             /* NV12: both even, >= 2 */
+    int format;             /* 0 BGR, 1 NV12 */
+} lp_redact_desc;
+typedef struct lp_redact_params {
+    int mode;               /* 0 mosaic, 1 fill */
+    int cell;               /* mosaic: side of a cell in pixels, even, 2..LP_REDACT_MAX_CELL (64) */
+    double margin;          /* the quad is scaled by 1 + margin about its centre; 0 <= margin <= 4 */
+    unsigned char fill[3];  /* fill: the bytes written, in the frame's own format: (B,G,R), or (Y,U,V) */
+} lp_redact_params;
+size_t lp_redact_workspace_bytes(const lp_redact_desc* desc, int n_frames, const lp_redact_params* p);  /* 0 for fill (and for bad arguments) */
+int lp_redact_plates_batch(const lp_redact_desc* desc, int n_frames, const float* det, const int32_t* count, int max_det,
+                           const lp_redact_params* p, int32_t* status /* [n_frames,max_det] */,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* lp_eval_counts: the matching loops of Evaler.eval (yolov6/core/evaler.py:153-243, box_iou general.py:93-115) for a
  * batch of images, one workgroup per image.
  *   det [B,max_det,28] fp32 + det_count [B]: detections as lp_nms returns them (xyxy, 8 corner coords, 8 confs, 8 ids)

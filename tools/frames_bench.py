@@ -2,7 +2,7 @@
 """Frames benchmark: rescaled detections from host frames, end to end, per frame and batched.
 
     python tools/frames_bench.py [--model yololps] [--size 640] [--dtype f16] [--frame 1080 1920] [--batches 8 32 64]
-                                 [--crops N]
+                                 [--crops N] [--redact [--redact-cell 16]]
     python tools/frames_bench.py --tile [--tile-baseline] [--tile-frame 2160 3840] [--tile-size 640] [--tile-overlap 128]
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot]
@@ -39,6 +39,11 @@ one batch from events for both kinds (H2D, letterbox -- lp_preprocess_tiles_batc
 lp_preprocess_nv12_batch on the NV12 frames, in the same run --, detect, rescale), the NV12 convert stage (lp_nv12_to_bgr_batch,
 with its GB/s over 1.5 B read + 3 B written per pixel) and, with ``--crops N``, the crop stage behind it.  With ``--tile`` the
 same for tiled detection: frames/s of ``detect_tiled_with_crops`` for both kinds and the stage times of each.
+With ``--redact`` (also with ``--nv12``) the plate-redaction stage (runtime.redact_plates, in place on the device frames) is timed
+at the end of the same event chain, on the ``--crops`` quads of each frame (4 when ``--crops`` is not given): ``redact`` = the mosaic
+(lp_redact_plates_batch's two kernels, cell means + write), ``redact_fill`` = the fill (the write kernel alone), so their
+difference is what the cell means cost; and the mosaic's share of the detect stage.  With ``--nv12`` the NV12 planes themselves are
+redacted.
 The model is the synthetic recipe of bench.py (same weights scale), prepared as Inferer prepares it.
 """
 import argparse
@@ -71,6 +76,8 @@ def parse():
     ap.add_argument('--iou', type=float, default=0.45)
     ap.add_argument('--max-det', type=int, default=1000)
     ap.add_argument('--crops', type=int, default=0, help='plate crops per frame to time (0: no crop stage)')
+    ap.add_argument('--redact', action='store_true', help='also time the plate-redaction stage (mosaic, and fill) on the quads of --crops (4 without it)')
+    ap.add_argument('--redact-cell', type=int, default=16, help='with --redact: side of a mosaic cell')
     ap.add_argument('--tile', action='store_true', help='measure tiled detection of large frames (detect_tiled) instead')
     ap.add_argument('--tile-baseline', action='store_true', help='with --tile: also time region copies + detect_frames + host merge')
     ap.add_argument('--tile-frame', nargs=2, type=int, default=[2160, 3840], metavar=('H', 'W'))
@@ -464,6 +471,13 @@ def nv12_mode(args, model, dev, tdt):
                 cst = torch.empty(B, args.crops, dtype=torch.int32, device=dev)
                 for v in names.values():
                     v.append('crops')
+            if args.redact:
+                rn = args.crops or 4
+                rdet = torch.from_numpy(synthetic_quads(B, rn, h0, w0, seed=B)).to(dev)
+                rcount = torch.full((B,), rn, dtype=torch.int32, device=dev)
+                rst = torch.empty(B, rn, dtype=torch.int32, device=dev)
+                for v in names.values():
+                    v.extend(['redact', 'redact_fill'])
             times = {kind: {k: [] for k in v} for kind, v in names.items()}
             for _ in range(args.reps + 1):
                 for kind in ('bgr', 'nv12'):
@@ -484,7 +498,13 @@ def nv12_mode(args, model, dev, tdt):
                         ev[i].record()
                     if args.crops:
                         runtime.plate_crops(fr, cdet, ccount, crop_hw, max_crops=args.crops, out=cout, status=cst)
+                        i += 1
+                        ev[i].record()
+                    if args.redact:     # last: it writes the frames (the next repetition's copy restores them)
+                        runtime.redact_plates(views[kind], rdet, rcount, 'mosaic', args.redact_cell, status=rst)
                         ev[i + 1].record()
+                        runtime.redact_plates(views[kind], rdet, rcount, 'fill', status=rst)
+                        ev[i + 2].record()
                     sync()
                     for i, k in enumerate(names[kind]):
                         times[kind][k].append(ev[i].elapsed_time(ev[i + 1]))
@@ -501,6 +521,9 @@ def nv12_mode(args, model, dev, tdt):
                     st['convert_GBps'] = round(moved / (med['convert'] * 1e-3) / 1e9, 1)
                     if args.crops:
                         st['convert_pct_of_detect'] = round(100.0 * med['convert'] / med['detect'], 2)
+                if args.redact:
+                    st['redact_rows_per_frame'], st['redact_cell'] = rn, args.redact_cell
+                    st['redact_pct_of_detect'] = round(100.0 * med['redact'] / med['detect'], 2)
                 r['stage_ms_' + kind] = st
             sp = times['bgr']['letterbox'][1:]
             r['letterbox_nv12_over_bgr'] = round(r['stage_ms_nv12']['letterbox'] / r['stage_ms_bgr']['letterbox'], 4)
@@ -630,7 +653,13 @@ def main():
                 hv[j * f.nbytes:(j + 1) * f.nbytes] = f.reshape(-1)
             dbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             views = [dbuf[j * f.nbytes:(j + 1) * f.nbytes].view(f.shape) for j, f in enumerate(fr)]
-            times = {k: [] for k in ('h2d', 'letterbox', 'detect', 'rescale') + (('crops',) if args.crops else ())}
+            times = {k: [] for k in ('h2d', 'letterbox', 'detect', 'rescale') + (('crops',) if args.crops else ())
+                     + (('redact', 'redact_fill') if args.redact else ())}
+            if args.redact:
+                rn = args.crops or 4
+                rdet = torch.from_numpy(synthetic_quads(B, rn, h0, w0, seed=B)).to(dev)
+                rcount = torch.full((B,), rn, dtype=torch.int32, device=dev)
+                rst = torch.empty(B, rn, dtype=torch.int32, device=dev)
             if args.crops:
                 crop_hw = (64, 192)
                 cdet = torch.from_numpy(synthetic_quads(B, args.crops, h0, w0, seed=B)).to(dev)
@@ -651,6 +680,12 @@ def main():
                 if args.crops:      # enqueued while detect still runs: the event pair brackets the kernel alone
                     runtime.plate_crops(views, cdet, ccount, crop_hw, max_crops=args.crops, out=cout, status=cst)
                     ev[5].record()
+                if args.redact:         # last: it writes the frames (the next repetition's copy restores them)
+                    i = 5 if args.crops else 4
+                    runtime.redact_plates(views, rdet, rcount, 'mosaic', args.redact_cell, status=rst)
+                    ev[i + 1].record()
+                    runtime.redact_plates(views, rdet, rcount, 'fill', status=rst)
+                    ev[i + 2].record()
                 sync()
                 for i, k in enumerate(times):
                     times[k].append(ev[i].elapsed_time(ev[i + 1]))
@@ -669,6 +704,9 @@ def main():
                 stages[str(B)]['crops_out_MB'] = round(cout.numel() / 1e6, 2)
                 stages[str(B)]['crops_pct_of_detect'] = round(100.0 * med['crops'] / med['detect'], 2)
                 del cdet, ccount, cout, cst
+            if args.redact:
+                stages[str(B)]['redact_rows_per_frame'], stages[str(B)]['redact_cell'] = rn, args.redact_cell
+                stages[str(B)]['redact_pct_of_detect'] = round(100.0 * med['redact'] / med['detect'], 2)
             del host, dbuf, views
     out['batched_fps'] = batched
     out['stage_ms'] = stages

@@ -6,6 +6,7 @@
                           [--tile 640 640 [--tile-overlap 0.2] [--no-tile-overview] [--merge-metric iou|ios]]
                           [--track [--track-max-age 5] [--track-iou 0.3] [--track-expand 0.5] [--best-shots [--crop-size 64 192]]]
                           [--nv12 bt601|bt709|bt601f|bt709f [--nv12-size W H]]
+                          [--redact mosaic|fill [--redact-cell 16] [--redact-margin 0.1]]
 """
 import argparse
 import os
@@ -63,6 +64,10 @@ _FLAGS = [
                     help='send frames as NV12 with this matrix (bt601, bt709: limited range; bt601f, bt709f: full range): decoded images '
                          'are encoded on the host as a stand-in for a decoder; a source ending in .nv12 is a raw stream of packed frames')),
     ('--nv12-size', dict(nargs=2, type=int, default=None, metavar=('W', 'H'), help='frame size of .nv12 sources')),
+    ('--redact', dict(default=None, choices=['mosaic', 'fill'], metavar='MODE',
+                      help='also write every frame with its detected plates made unreadable (mosaic, or a black fill) to redacted/')),
+    ('--redact-cell', dict(type=int, default=16, help='with --redact mosaic: side of a mosaic cell in pixels (even, 2..64)')),
+    ('--redact-margin', dict(type=float, default=0.1, help='with --redact: grow every plate by this fraction of its size (0..4)')),
 ]
 
 
@@ -81,10 +86,11 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         view_img=True, classes=None, agnostic_nms=False, project=osp.join(ROOT, 'runs/inference'), name='exp',
         hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False, save_crops=False, crop_size=(64, 192),
         tile=None, tile_overlap=0.2, no_tile_overview=False, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3,
-        track_expand=0.5, best_shots=False, nv12=None, nv12_size=None):
+        track_expand=0.5, best_shots=False, nv12=None, nv12_size=None, redact=None, redact_cell=16,
+        redact_margin=0.1):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
-    if (save_img or save_txt or save_crops or track) and not osp.exists(out_dir):
+    if (save_img or save_txt or save_crops or track or redact) and not osp.exists(out_dir):
         os.makedirs(out_dir)
     else:
         LOGGER.warning('Save directory already existed')
@@ -94,7 +100,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         tile_overlap = int(tile_overlap)        # pixels
     results = Inferer(source, weights, device, yaml, img_size, half, batch_size=batch_size, auto=not fixed_shape, tile=tile,
                       tile_overlap=tile_overlap, tile_overview=not no_tile_overview, merge_metric=merge_metric, track=track, track_max_age=track_max_age,
-                      track_iou=track_iou, track_expand=track_expand, best_shots=best_shots, nv12=nv12, nv12_size=nv12_size).infer(
+                      track_iou=track_iou, track_expand=track_expand, best_shots=best_shots, nv12=nv12, nv12_size=nv12_size,
+                      redact=redact, redact_cell=redact_cell, redact_margin=redact_margin).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

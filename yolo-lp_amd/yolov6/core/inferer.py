@@ -22,6 +22,9 @@ With ``nv12`` the frames travel as NV12 (``yolov6.utils.nv12``): decoded images 
 video decoder, ``.nv12`` sources are raw streams of packed frames; on a GPU the planes are uploaded (half the bytes of BGR) and
 read by the fused letterbox, a BGR frame exists on the device only where crops are cut; on the CPU every frame goes through
 ``nv12_to_bgr_np`` into the existing path.
+With ``redact`` every detection's plate is made unreadable in the frame itself, by a mosaic or a fill (``runtime.redact_plates`` on a
+GPU, in place on the device frames and behind everything that reads them; ``redact_plates_np`` on the CPU), and the frame is
+written to ``<save_dir>/redacted/``.  NV12 frames are redacted as NV12 and converted only to be saved.
 """
 import math
 import os
@@ -43,7 +46,7 @@ from yolov6.utils.nv12 import MATRICES, Nv12Frame, bgr_to_nv12_np, nv12_to_bgr_n
 class Inferer:
     def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True, tile=None, tile_overlap=0.2,
                  tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5, best_shots=False,
-                 nv12=None, nv12_size=None):
+                 nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -57,8 +60,14 @@ class Inferer:
         frames (``yolov6.utils.best_shot`` states the rules); ``infer`` writes one image per ended track that has one.
         ``nv12`` = 'bt601' | 'bt709' | 'bt601f' | 'bt709f': send every frame as NV12 with that matrix (decoded images are encoded
         with ``bgr_to_nv12_np``, an odd last row or column cut off as a decoder would never deliver one); ``nv12_size`` = (w, h)
-        of the frames of ``.nv12`` sources, which need ``nv12``."""
+        of the frames of ``.nv12`` sources, which need ``nv12``.
+        ``redact`` = 'mosaic' | 'fill' (black): ``infer`` also writes every frame with the plates of its detections made unreadable
+        (``yolov6.utils.redact`` states the rules): the quad of every row, grown by ``redact_margin`` of its size about its centre,
+        in cells of ``redact_cell`` pixels (mosaic)."""
         self.__dict__.update(locals())
+        if redact is not None:
+            from yolov6.utils.redact import check_params
+            check_params(redact, redact_cell, redact_margin)
         if best_shots and not track:
             raise ValueError('best_shots needs track=True')
         if merge_metric not in ('iou', 'ios'):
@@ -124,7 +133,11 @@ class Inferer:
         With ``best_shots`` the sharpest crop (``crop_size``) of line k of ``plates.txt`` is written as
         ``<save_dir>/shots/<k>_<id>.png`` (RGB), and ``<save_dir>/shots.txt`` has one line ``id frame row status sharpness file``
         per line of ``plates.txt``: the stream's frame index and the row the shot was cut from, the crop's status (1 corners,
-        2 box) and its Laplacian energy; a track without a shot has ``id 0 0 0 0 -``."""
+        2 box) and its Laplacian energy; a track without a shot has ``id 0 0 0 0 -``.
+
+        With ``redact`` every frame is also written, its plates redacted along the rows returned, as
+        ``<save_dir>/redacted/<image name>`` (``.png`` for a frame of a video or a raw stream)."""
+        self._redacted = deque()
         if self.track:
             self._track_begin(crop_size)
         if self.device.type != 'cpu' and (self.tile is not None or self.batch_size > 1 or self.nv12 is not None):
@@ -141,6 +154,8 @@ class Inferer:
                 if save_crops and len(det):
                     self.write_crops(img_path, crops[k], save_dir)
                 results.append(det)
+                if self.redact is not None:
+                    self.write_redacted(img_path, self._redacted.popleft(), save_dir)
                 if self.track:
                     self._track_lines += ['%s %d %d' % (img_path, r, t) for r, t in enumerate(self._track_tids.popleft().tolist())]
         if self.track:
@@ -156,8 +171,10 @@ class Inferer:
         if gpu:
             from yolov6.hip import runtime
         for img_src, img_path, _ in self.files:
+            img_nv12 = None
             if self.nv12 is not None:       # (CPU only: a GPU takes NV12 through _gpu_groups) NV12 in, nv12_to_bgr_np, the existing path
-                img_src = nv12_to_bgr_np(self._as_nv12(img_src))
+                img_nv12 = self._as_nv12(img_src)
+                img_src = nv12_to_bgr_np(img_nv12)
             if gpu:      # letterbox + BGR->RGB + /255 in one HIP kernel on the uploaded frame
                 frame = torch.from_numpy(np.ascontiguousarray(img_src)).to(self.device)
                 img = runtime.preprocess_letterbox(frame, self.img_size, self.stride,
@@ -190,6 +207,7 @@ class Inferer:
                 else:
                     from yolov6.utils.plate_crop import plate_crops_np
                     crops = [plate_crops_np(img_src, det.detach().float().cpu().numpy(), crop_size)[0]]
+            self._redact_group([img_src if img_nv12 is None else img_nv12], [det], [frame] if gpu else None)     # last: it writes the frame
             yield [(img_src, img_path)], [det], crops, seconds
 
     def _gpu_groups(self, conf_thres, iou_thres, max_det, save_crops, crop_size):
@@ -265,6 +283,7 @@ class Inferer:
                                                    crop_size, **kw)
             else:
                 dets, crops = detect(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det, **kw), None
+            self._redact_group([f for f, _ in items], dets, dev_frames)     # behind the crops and the shots, before the next put
             yield items, dets, crops, time.time() - t1
 
     def tiled_rows_cpu(self, img_src, conf_thres, iou_thres, classes, agnostic_nms, max_det, border=1):
@@ -442,6 +461,44 @@ class Inferer:
                 self.save_annotated(img_src, rows, save_path)
         elif save_img:
             self.save_annotated(img_src, [], save_path)
+
+    def _redact_group(self, frames, dets, dev_frames=None):
+        """With ``redact``: queue for ``infer`` the frames of one group with the plates of their final rows ``dets`` redacted, host
+        BGR arrays or host ``Nv12Frame``s.  On a GPU ``dev_frames`` (the group's device frames) are redacted in place
+        (``runtime.redact_plates``: whatever reads them has been enqueued before) and read back; on the CPU ``frames`` are
+        copied (``redact_plates_np``)."""
+        if self.redact is None:
+            return
+        n, m = len(frames), max([len(d) for d in dets] + [1])
+        if dev_frames is not None:
+            from yolov6.hip import runtime
+            det = torch.zeros(n, m, 28, dtype=torch.float32, device=self.device)
+            for k, d in enumerate(dets):
+                det[k, :len(d)] = d
+            count = torch.tensor([len(d) for d in dets], dtype=torch.int32).to(self.device)
+            dev_frames = list(dev_frames)[:n]
+            runtime.redact_plates(dev_frames, det, count, self.redact, self.redact_cell, self.redact_margin)
+            self._redacted.extend(Nv12Frame(f.y.cpu().numpy(), f.uv.cpu().numpy(), f.matrix) if isinstance(f, Nv12Frame)
+                                  else f.cpu().numpy() for f in dev_frames)
+        else:
+            from yolov6.utils.redact import redact_plates_np
+            det = np.zeros((n, m, 28), np.float32)
+            for k, d in enumerate(dets):
+                det[k, :len(d)] = d.detach().float().cpu().numpy()
+            self._redacted.extend(redact_plates_np(list(frames), det, [len(d) for d in dets], self.redact, self.redact_cell,
+                                                   self.redact_margin)[0])
+
+    def write_redacted(self, img_path, frame, save_dir):
+        """One redacted frame (BGR array or host ``Nv12Frame``) as ``<save_dir>/redacted/<image name>``, by the writer of
+        ``save_annotated``; a frame that is no image file (video, raw stream) is named ``<stem>.png``."""
+        from PIL import Image
+        if isinstance(frame, Nv12Frame):
+            frame = nv12_to_bgr_np(frame)
+        name = osp.basename(img_path)
+        if self.files.checkext(img_path) != 'image':
+            name = osp.splitext(name)[0] + '.png'
+        os.makedirs(osp.join(save_dir, 'redacted'), exist_ok=True)
+        Image.fromarray(np.ascontiguousarray(frame[:, :, ::-1])).save(osp.join(save_dir, 'redacted', name))
 
     def write_crops(self, img_path, crops_bgr, save_dir):
         """Plate crops of one image (uint8 [n, h, w, 3] BGR, a tensor or an array) as ``<save_dir>/<rel>/crops/<stem>_<k>.png``, RGB."""

@@ -32,6 +32,7 @@ LP_FRAMES_PER_LAUNCH = 64   # lp_preprocess_letterbox_batch / lp_rescale_round_b
 LP_NV12_PER_LAUNCH = 32     # lp_preprocess_nv12_batch: slots per launch (its table entries are larger)
 LP_MERGE_MAX_TILES, LP_MERGE_MAX_CANDIDATES = 64, 16384   # lp_merge_tiles: tiles per frame, tiles_of_frame * max_det_t
 LP_TRACK_MAX_TRACKS, LP_TRACK_MAX_DETS, LP_TRACK_MAX_CLS = 128, 128, 64   # lp_track_update: slots per stream, rows per frame, classes per head
+LP_REDACT_MAX_CELL = 64    # lp_redact_plates_batch: largest mosaic cell
 LP_EVAL_NCOUNTS = 43  # lp_eval_counts: length of the counts vector (include/lp_hip.h)
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # .../yolo-lp_amd
@@ -71,6 +72,17 @@ class Nv12BgrDesc(ctypes.Structure):
     """lp_nv12_bgr_desc"""
     _fields_ = [('y', c_void_p), ('uv', c_void_p), ('pitch_y', c_int), ('pitch_uv', c_int), ('h0', c_int), ('w0', c_int),
                 ('matrix', c_int), ('out', c_void_p)]
+
+
+class RedactDesc(ctypes.Structure):
+    """lp_redact_desc"""
+    _fields_ = [('p0', c_void_p), ('p1', c_void_p), ('pitch0', c_int), ('pitch1', c_int), ('h0', c_int), ('w0', c_int),
+                ('format', c_int)]
+
+
+class RedactParams(ctypes.Structure):
+    """lp_redact_params"""
+    _fields_ = [('mode', c_int), ('cell', c_int), ('margin', c_double), ('fill', ctypes.c_ubyte * 3)]
 
 
 class TileRef(ctypes.Structure):
@@ -155,6 +167,9 @@ SYMBOLS = {
     'lp_best_shot_update': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, POINTER(c_int), c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p]),
+    'lp_redact_workspace_bytes': (c_size_t, [POINTER(RedactDesc), c_int, POINTER(RedactParams)]),
+    'lp_redact_plates_batch': (c_int, [POINTER(RedactDesc), c_int, c_void_p, c_void_p, c_int, POINTER(RedactParams), c_void_p, c_void_p,
+                                       c_size_t, c_void_p]),
     'lp_eval_counts': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'lp_check_sigmoid_monotone': (c_int, [c_void_p, c_void_p]),
     'lp_debug_poison_lds': (c_int, [c_void_p]),

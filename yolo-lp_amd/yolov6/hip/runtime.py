@@ -1087,6 +1087,69 @@ def detect_frames_with_crops(model, frames, img_size, conf_thres, iou_thres, max
     return _unpad_with_crops(frames, det, count, crop_hw)
 
 
+_redact_ws = {}
+
+
+def _redact_workspace(device, need):
+    """The cell table of ``redact_plates`` on ``device``'s current stream, grown to ``need`` bytes (+ 256 for ``_aligned``); one per
+    (device, stream), as ``_nms_workspace``.  It needs no zeroing: a call reads only entries it has written itself."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _redact_ws.get(key)
+    if ws is None or ws.numel() < need + 256:
+        ws = _redact_ws[key] = torch.empty(need + 256, dtype=torch.uint8, device=device)
+    return ws
+
+
+def redact_plates(frames, det, count, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0), status=None):
+    """Make the plates of B device frames unreadable IN PLACE (lp_redact_plates_batch, two launches per 64 frames on the current
+    stream, no host read): ``frames`` is a list of contiguous uint8 CUDA [h,w,3] BGR tensors or of ``Nv12Frame`` with CUDA planes
+    (one kind; NV12 is redacted in its own planes, no BGR copy exists), ``det`` [>= B,max_det,28] + ``count`` int32 on the device
+    as ``detect_frames_padded``, ``detect_tiled_padded`` or ``PlateTracker.update`` (det_out) return them.  EVERY row
+    r < min(max(count[b], 0), max_det) of frame b is redacted -- there is no cap -- along its corners, or its box when the
+    corners are no convex quad of area >= 1, scaled by ``1 + margin`` about the centre.  ``mode`` 'mosaic': a pixel takes the mean of
+    its ``cell`` x ``cell`` cell (even, 2..64; the grid is anchored to the frame, the means are of the frame before the call, so
+    overlapping plates and the order of the rows do not matter); 'fill': ``fill`` = (B, G, R), converted with the frame's matrix
+    for NV12.  Writes into the caller's tensors and returns status [B,max_det] int32: 1 = corners, 2 = box, 3 = neither usable
+    (nothing written), 0 = no such row.  yolov6.utils.redact.redact_plates_np is the same computation on the CPU, bit for bit.
+
+    REDACTION GOES LAST: ``plate_crops``, ``PlateTracker.update_with_shots`` and the best-shot gallery must read the frames
+    BEFORE this call on the same stream, or they cut mosaics."""
+    from yolov6.utils.redact import check_params, fill_bytes
+    if not frames:
+        raise ValueError('redact_plates needs at least one frame')
+    dev, nv12 = _frames_on(frames, 'redact_plates')
+    _check_det_count(det, count, min_batch=len(frames))
+    if det.device != dev or det.shape[1] < 1:
+        raise ValueError('det must be on the frames\' device with max_det >= 1')
+    m, cell, margin = check_params(mode, cell, margin)
+    n, max_det = len(frames), det.shape[1]
+    status = _buffer(status, (n, max_det), torch.int32, dev, 'status')
+    desc = (abi.RedactDesc * n)()
+    for d, f in zip(desc, frames):
+        if nv12:
+            d.p0, d.p1, d.pitch0, d.pitch1, d.format = f.y.data_ptr(), f.uv.data_ptr(), f.pitch_y, f.pitch_uv, 1
+        else:
+            d.p0, d.p1, d.pitch0, d.format = f.data_ptr(), None, 3 * f.shape[1], 0
+        d.h0, d.w0 = f.shape[0], f.shape[1]
+    # one call per run of frames that share the fill's bytes: a BGR list or a mosaic is one run, an NV12 fill one per matrix
+    fills = [fill_bytes(fill, f.matrix if nv12 and m == 1 else None) for f in frames]
+    lib, b0 = abi.load(), 0
+    with torch.cuda.device(dev):
+        while b0 < n:
+            b1 = b0 + 1
+            while b1 < n and fills[b1] == fills[b0]:
+                b1 += 1
+            params = abi.RedactParams(m, cell, margin, (ctypes.c_ubyte * 3)(*fills[b0]))
+            run = ctypes.cast(ctypes.byref(desc, b0 * ctypes.sizeof(abi.RedactDesc)), ctypes.POINTER(abi.RedactDesc))
+            need = lib.lp_redact_workspace_bytes(run, b1 - b0, ctypes.byref(params))
+            ws = _redact_workspace(dev, need) if m == 0 else None
+            abi.check(lib.lp_redact_plates_batch(run, b1 - b0, _dptr(det[b0:b1]), _dptr(count[b0:b1]), max_det, ctypes.byref(params),
+                                                 _dptr(status[b0:b1]), None if ws is None else _aligned(ws), need, _stream_ptr(dev)),
+                      'lp_redact_plates_batch')
+            b0 = b1
+    return status
+
+
 # ---------------------------------------------------------------------------------------------------
 # Tiled detection of large frames (yolov6/core/tiles.py plans the tiles; lp_preprocess_tiles_batch / lp_merge_tiles)
 def preprocess_tiles(frames, plans, img_size, stride, dtype, batch=None, out=None):
