@@ -451,6 +451,33 @@ int lp_track_update_slots(void* state, int n_streams, int max_tracks, const lp_t
                           const int* stream_of /* HOST [B] */, const unsigned char* flush /* HOST [n_streams] or NULL */,
                           float* det_out, int32_t* tid, int32_t* slot, int32_t* ended_i, float* ended_f, int32_t* ended_count,
                           int max_ended, void* stream);
+/* lp_track_update_hold: lp_track_update_slots (which is this call with hp = NULL: the hold outputs are then ignored) that also
+ * emits, per frame, the rows redaction has to cover: the frame's own rows followed by one predicted row for every track the
+ * frame missed, so that a plate the detector loses for a frame is not stored readable (lp_redact_plates_batch takes det_hold,
+ * count_hold as they are).  The hold reads the state and never writes it: det_out, tid, slot, the ended records, `dropped` and
+ * every state byte are what they are without it.
+ *  11. hold: in a tracked frame, after step 5, a slot is held iff it was live at the start of the frame, was not matched, did
+ *      not end in this frame, has hits >= min_hits and, after the increment of 5, misses <= max_misses (values above max_age
+ *      behave as max_age: the track ends first).  A slot that ended in this frame and was re-used by a new track is not held.
+ *      The held row of a slot, fp32 op by op: k = (float)misses, dx = vx * k, dy = vy * k (the k and the rounded products of
+ *      step 1 of this frame); columns 0..3 = the stored box + (dx, dy, dx, dy), bit for bit the box step 1 predicted before the
+ *      expansion; columns 4..11 = the stored corners, x columns (4, 6, 8, 10) + dx, y columns (5, 7, 9, 11) + dy; columns
+ *      12..19 the track's shares and 20..27 its voted ids (8; the slot cast no vote in this frame).
+ *   Per frame b, nc = min(max(count[b], 0), max_det): det_hold [B, max_det + max_tracks, 28] = rows 0..nc-1 of det_out[b] (all of
+ *   them, those past LP_TRACK_MAX_DETS included), then the held rows in slot order, every later row zero; count_hold [B] = nc +
+ *   the number of held rows (never capped: max_tracks extra rows always fit); tid_hold [B, max_det + max_tracks] int32 = tid
+ *   for the first nc rows, the track id for held rows, -1 elsewhere.  A frame with stream_of -1 gets its copied rows,
+ *   count_hold = nc and no held row.  Flushing happens after the frames and changes nothing here.  The hold does not grow the
+ *   box with the track's age, has no model beyond the constant velocity of step 1 and holds nothing past max_age.
+ * Also checked before the first launch with hp != NULL: min_hits >= 1, max_misses >= 0, the three hold pointers non-null (B > 0),
+ * det_hold overlapping neither det nor det_out, (max_det + max_tracks) * 28 below 2^31. */
+typedef struct lp_track_hold_params { int min_hits, max_misses; } lp_track_hold_params;
+int lp_track_update_hold(void* state, int n_streams, int max_tracks, const lp_track_params* p,
+                         const float* det, const int32_t* count, int B, int max_det,
+                         const int* stream_of /* HOST [B] */, const unsigned char* flush /* HOST [n_streams] or NULL */,
+                         float* det_out, int32_t* tid, int32_t* slot, int32_t* ended_i, float* ended_f, int32_t* ended_count,
+                         int max_ended, const lp_track_hold_params* hp, float* det_hold, int32_t* count_hold, int32_t* tid_hold,
+                         void* stream);
 
 /* lp_plate_crops_batch: perspective-rectified plate crops of B frames' detections (the inverse of the warp of the reference's
  * plate generator, yolov6/data/generate/generate.py:566-586), one launch per LP_FRAMES_PER_LAUNCH frames; descriptors travel

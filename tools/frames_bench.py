@@ -5,7 +5,7 @@
                                  [--crops N] [--redact [--redact-cell 16]]
     python tools/frames_bench.py --tile [--tile-baseline] [--tile-frame 2160 3840] [--tile-size 640] [--tile-overlap 128]
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
-    python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot]
+    python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot] [--redact [--hold]] [--nv12]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
@@ -44,6 +44,10 @@ at the end of the same event chain, on the ``--crops`` quads of each frame (4 wh
 (lp_redact_plates_batch's two kernels, cell means + write), ``redact_fill`` = the fill (the write kernel alone), so their
 difference is what the cell means cost; and the mosaic's share of the detect stage.  With ``--nv12`` the NV12 planes themselves are
 redacted.
+With ``--track --redact [--hold]`` (also with ``--nv12``: the streams' frames are then NV12) the update and the mosaic behind it
+are timed from events on the tracker's own rows, every stream seeing another frame in every step so that tracks are missed;
+``--hold`` runs a second tracker with ``enable_hold`` on the same frames, alternating, and redacts along its ``last_hold``:
+``update_ms`` / ``update_hold_ms``, ``redact_ms`` / ``redact_hold_ms`` and the rows per frame each mosaic covered.
 The model is the synthetic recipe of bench.py (same weights scale), prepared as Inferer prepares it.
 """
 import argparse
@@ -88,6 +92,8 @@ def parse():
     ap.add_argument('--track', action='store_true', help='measure plate tracking (PlateTracker.update behind detect_frames) instead')
     ap.add_argument('--track-batch', type=int, default=32, help='with --track: camera streams = frames per step')
     ap.add_argument('--best-shot', action='store_true', help='with --track: also time crops + sharpness + gallery behind the update')
+    ap.add_argument('--hold', action='store_true', help='with --track --redact: also time the update with the redaction hold (enable_hold) '
+                                                        'and the redaction along its rows')
     ap.add_argument('--nv12', nargs='?', const='bt709', default=None, choices=['bt601', 'bt709', 'bt601f', 'bt709f'], metavar='MATRIX',
                     help='also send the same seeded frames as NV12 with this matrix and compare (default matrix: bt709)')
     ap.add_argument('--runs', type=int, default=3, help='timed runs of the frames/s figures (the spread is reported)')
@@ -258,10 +264,15 @@ def track_mode(args, model, dev, tdt):
     B, conf, iou, max_det = args.track_batch, args.conf, args.iou, args.max_det
     rng = np.random.default_rng(0)
     pool = [rng.integers(0, 256, (h0, w0, 3), dtype=np.uint8) for _ in range(args.distinct)]
+    if args.nv12:
+        from yolov6.utils.nv12 import bgr_to_nv12_np
+        pool = [bgr_to_nv12_np(f, args.nv12) for f in pool]         # what a decoder delivers: encoded before any clock starts
+    if args.hold and not args.redact:
+        raise SystemExit('--hold needs --track --redact')
     H, W = letterbox_hw((h0, w0), size, stride)
     sync = torch.cuda.synchronize
     out = dict(metric='frames/s end to end with and without plate tracking (host frames in, rows out)', model=args.model,
-               dtype=args.dtype, frame=[h0, w0], net=[H, W], streams=B, runs=args.runs)
+               dtype=args.dtype, frame=[h0, w0], net=[H, W], streams=B, runs=args.runs, conf=conf, matrix=args.nv12)
     with torch.no_grad():
         runtime.prepare_for(model, (B, 3, H, W), tdt)
         batcher = FrameBatcher(dev)
@@ -317,6 +328,8 @@ def track_mode(args, model, dev, tdt):
 
         if args.best_shot:
             out['best_shot'] = best_shot_stages(args, model, dev, tdt, frames, x, (H, W))
+        if args.redact:
+            out['redact'] = redact_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
 
         # the full case: 128 live tracks x 128 rows per stream, every pair above the threshold
         full = runtime.PlateTracker(B, max_tracks=128, max_age=0, ncls=model, device=dev)
@@ -339,6 +352,48 @@ def track_mode(args, model, dev, tdt):
         out['full_128x128_ms'] = round(float(np.median(ms[1:])), 4)
         out['full_128x128_matched'] = int((tid >= 0).sum())
     print(json.dumps(out))
+
+
+def redact_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
+    """--track --redact [--hold]: device time of the update and of the mosaic behind it, from events on one stream; with --hold a
+    second tracker with ``enable_hold`` takes the same frames, alternating, and the mosaic runs along its ``last_hold``.  Every
+    stream sees another frame of the pool in every step, so tracks are missed (and end) all the time."""
+    import torch
+    from yolov6.hip import runtime
+    size, stride = [args.size, args.size], int(model.stride.max())
+    B, conf, iou, max_det = args.track_batch, args.conf, args.iou, args.max_det
+    trackers = dict(plain=runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev))
+    if args.hold:
+        trackers['hold'] = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
+        trackers['hold'].enable_hold()
+    times = {name: dict(update=[], redact=[]) for name in trackers}
+    rows = {name: [] for name in trackers}
+    warm = 3
+    for k in range(warm + args.reps + 1):
+        for name, trk in trackers.items():
+            frames = batcher.put([pool[(j + k) % len(pool)] for j in range(B)])      # (the put restores what the last mosaic wrote)
+            xx, _ = runtime.preprocess_frames(frames, size, stride, tdt, batch=B, out=x)
+            det, count, _ = runtime.detect_padded(model, xx, conf, iou, max_det)
+            runtime.rescale_round_batch(det, count, net_hw, [f.shape for f in frames])
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record()
+            det_out = trk.update(det, count)[0]
+            ev[1].record()
+            rdet, rcount = (det_out, count) if name == 'plain' else trk.last_hold[:2]
+            runtime.redact_plates(frames, rdet, rcount, 'mosaic', args.redact_cell)
+            ev[2].record()
+            torch.cuda.synchronize()
+            if k > warm:
+                times[name]['update'].append(ev[0].elapsed_time(ev[1]))
+                times[name]['redact'].append(ev[1].elapsed_time(ev[2]))
+                rows[name].append(float(rcount.clamp(0, rdet.shape[1]).float().mean()))
+    r = dict(redact_cell=args.redact_cell, reps=args.reps)
+    for name in trackers:
+        sfx = '' if name == 'plain' else '_hold'
+        r['update%s_ms' % sfx] = round(float(np.median(times[name]['update'])), 4)
+        r['redact%s_ms' % sfx] = round(float(np.median(times[name]['redact'])), 4)
+        r['redact%s_rows_per_frame' % sfx] = round(float(np.mean(rows[name])), 2)
+    return r
 
 
 def best_shot_stages(args, model, dev, tdt, frames, x, net_hw):

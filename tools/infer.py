@@ -6,7 +6,8 @@
                           [--tile 640 640 [--tile-overlap 0.2] [--no-tile-overview] [--merge-metric iou|ios]]
                           [--track [--track-max-age 5] [--track-iou 0.3] [--track-expand 0.5] [--best-shots [--crop-size 64 192]]]
                           [--nv12 bt601|bt709|bt601f|bt709f [--nv12-size W H]]
-                          [--redact mosaic|fill [--redact-cell 16] [--redact-margin 0.1]]
+                          [--redact mosaic|fill [--redact-cell 16] [--redact-margin 0.1]
+                           [--redact-hold [--redact-hold-min-hits 1]]]
 """
 import argparse
 import os
@@ -68,6 +69,9 @@ _FLAGS = [
                       help='also write every frame with its detected plates made unreadable (mosaic, or a black fill) to redacted/')),
     ('--redact-cell', dict(type=int, default=16, help='with --redact mosaic: side of a mosaic cell in pixels (even, 2..64)')),
     ('--redact-margin', dict(type=float, default=0.1, help='with --redact: grow every plate by this fraction of its size (0..4)')),
+    ('--redact-hold', dict(action='store_true', help='with --track and --redact: keep a tracked plate redacted, where its track predicts '
+                                                     'it, in the frames in which the detector misses it (until the track ends)')),
+    ('--redact-hold-min-hits', dict(type=int, default=1, help='with --redact-hold: detections a track needs before it is held')),
 ]
 
 
@@ -87,7 +91,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False, save_crops=False, crop_size=(64, 192),
         tile=None, tile_overlap=0.2, no_tile_overview=False, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3,
         track_expand=0.5, best_shots=False, nv12=None, nv12_size=None, redact=None, redact_cell=16,
-        redact_margin=0.1):
+        redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track or redact) and not osp.exists(out_dir):
@@ -101,7 +105,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
     results = Inferer(source, weights, device, yaml, img_size, half, batch_size=batch_size, auto=not fixed_shape, tile=tile,
                       tile_overlap=tile_overlap, tile_overview=not no_tile_overview, merge_metric=merge_metric, track=track, track_max_age=track_max_age,
                       track_iou=track_iou, track_expand=track_expand, best_shots=best_shots, nv12=nv12, nv12_size=nv12_size,
-                      redact=redact, redact_cell=redact_cell, redact_margin=redact_margin).infer(
+                      redact=redact, redact_cell=redact_cell, redact_margin=redact_margin, redact_hold=redact_hold,
+                      redact_hold_min_hits=redact_hold_min_hits).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

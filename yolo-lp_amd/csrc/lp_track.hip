@@ -16,6 +16,11 @@
 //   6. wave 0 hands the free slots, in order, to the unmatched rows that pass new_thres, in order;
 //   7. one thread per (slot, head) casts the vote of a matched or new slot and reads the head (best, share) into LDS;
 //   8. all threads write the frame's output rows and track ids.
+// lp_track_update_hold runs the <true> instantiation (rule 11, read-only on the state): step 5 also marks the missed slots that
+// pass the two gates ST_HELD and numbers them in slot order (ballot and prefix count over the two waves of 128 slots, as end_marked
+// numbers the ending tracks); step 7 reads their heads into the same two tables; step 8 also writes det_hold / count_hold /
+// tid_hold: the frame's rows, then one predicted row per held slot.  Every other caller runs <false>, whose code is the kernel
+// without all this (profiles/hold_codegen.txt).
 // State of a stream (int32 / fp32 words, all zero = empty): 16 header words (frame counter, next id, dropped), then per slot
 // 544 words: id, first, last, hits, misses, 3 unused; box[4]; corners[8]; vx, vy, 2 unused; total[8]; votes[8][64].  A slot is
 // live iff hits > 0.
@@ -40,7 +45,7 @@ constexpr int TK_FRAMES = LP_FRAMES_PER_LAUNCH; // frames (and streams) per laun
 static_assert(TK_W_COR == TK_W_BOX + 4 && TK_W_VEL == TK_W_COR + 8, "box and corners are the row's columns 0..11, contiguous");
 static_assert(TK_SLOTS * TK_ROWS == SORT_LDS_KEYS && TK_T / TK_HEADS == TK_SLOTS && TK_ROWS == 128, "track kernel geometry");
 
-enum { ST_EMPTY = 0, ST_LIVE = 1, ST_MATCHED = 2, ST_ENDING = 3, ST_NEW = 4, ST_MISSED = 5 };
+enum { ST_EMPTY = 0, ST_LIVE = 1, ST_MATCHED = 2, ST_ENDING = 3, ST_NEW = 4, ST_MISSED = 5, ST_HELD = 6 };   // ST_HELD: missed and held
 
 struct TkTable {                                // 584 bytes of kernel arguments
     int nfr;                                    // frames of this launch
@@ -50,6 +55,12 @@ struct TkTable {                                // 584 bytes of kernel arguments
     unsigned char blk_flush[TK_FRAMES];         // workgroup k ends all live tracks after its frames
 };
 struct TkParams { float thr_f, new_f, expand_f; int max_age; int ncls[TK_HEADS]; };
+struct TkHold {                                 // rule 11 (read by the <true> instantiation only)
+    int min_hits, max_misses;
+    float* det;                                 // [frames, max_det + T, 28], the launch's first frame (as det_out)
+    int32_t* count;                             // [frames]
+    int32_t* tid;                               // [frames, max_det + T]
+};
 
 typedef float box4 __attribute__((ext_vector_type(4)));
 
@@ -83,11 +94,12 @@ __global__ void track_clear_kernel(int32_t* ended_count, int n_streams, int32_t*
 
 // grid (workgroups of this launch), block (1024), dynamic LDS = n_max keys (8 B), n_max >= max_tracks * min(max_det, 128).
 //   det / count / det_out / tid_out / slot_out (may be null): the launch's first frame; state, ended_*: the whole call's.
+template <bool HOLD>
 __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const TkParams prm, int* __restrict__ state, int T, long long sstride,
                                                     const float* __restrict__ det, const int32_t* __restrict__ count, int max_det,
                                                     float* __restrict__ det_out, int32_t* __restrict__ tid_out, int32_t* __restrict__ slot_out,
                                                     int32_t* __restrict__ ended_i, float* __restrict__ ended_f, int32_t* __restrict__ ended_count,
-                                                    int max_ended) {
+                                                    int max_ended, const TkHold hold) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long skeys[];
     __shared__ __attribute__((aligned(16))) box4 s_pbox[TK_SLOTS];     // predicted, expanded boxes of the live slots
     __shared__ __attribute__((aligned(16))) box4 s_dbox[TK_ROWS];      // expanded boxes of the rows
@@ -96,6 +108,7 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
     __shared__ int s_best[TK_SLOTS * TK_HEADS];
     __shared__ int s_ncls[TK_HEADS];
     __shared__ int s_nkeys, s_wcnt[2], s_nfree, s_made, s_drop;
+    __shared__ int s_hslot[HOLD ? TK_SLOTS : 1], s_hcnt[2];           // HOLD: the held slots in slot order, their number per wave
     const int blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int strm = tab.blk_stream[blk];
     int* const sst = state + (strm >= 0 ? (long long)strm * sstride : 0);
@@ -236,7 +249,7 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
             }
             __syncthreads();
             // ---- 5. matched and unmatched slots ------------------------------------------------------------------------------
-            bool ending = false;
+            bool ending = false, held = false;
             if (tid < T && s_status[tid] == ST_LIVE) {
                 int* sl = sst + TK_HDR_WORDS + tid * TK_SLOT_WORDS;
                 const int r = s_slot_row[tid];
@@ -260,10 +273,17 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
                     const int m = sl[4] + 1;
                     sl[4] = m;
                     ending = m > prm.max_age;
-                    s_status[tid] = ending ? ST_ENDING : ST_MISSED;
+                    if (HOLD) held = !ending && sl[3] >= hold.min_hits && m <= hold.max_misses;
+                    s_status[tid] = ending ? ST_ENDING : (held ? ST_HELD : ST_MISSED);
                 }
             }
+            unsigned long long hm = 0;
+            if (HOLD) {                                                // (made visible by the barriers of end_marked)
+                hm = __ballot(held);
+                if (tid < TK_SLOTS && lane == 0) s_hcnt[wave] = __popcll(hm);
+            }
             end_marked(ending);
+            if (HOLD && held) s_hslot[(wave == 1 ? s_hcnt[0] : 0) + __popcll(hm & lt)] = tid;   // (read behind the barriers of step 6)
             // ---- 6. new tracks: the free slots, in order, to the unmatched rows that pass new_thres, in order ---------------
             if (wave == 0) {
                 const bool f0 = lane < T && (s_status[lane] == ST_EMPTY || s_status[lane] == ST_ENDING);
@@ -328,6 +348,12 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
                     read_head(hsl, head, &best, &share);
                     s_best[tid] = best;
                     s_share[tid] = share;
+                } else if (HOLD && st == ST_HELD) {                    // a held slot casts no vote: its read as it stands
+                    int best;
+                    float share;
+                    read_head(hsl, head, &best, &share);
+                    s_best[tid] = best;
+                    s_share[tid] = share;
                 }
             }
             __syncthreads();
@@ -346,6 +372,7 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
                 }
             }
             dout[i] = v;
+            if (HOLD && r < nc) hold.det[(long long)j * (max_det + T) * LP_DET_COLS + i] = v;
         }
         for (int r = tid; r < max_det; r += TK_T) {
             int v = -1, slot = -1;
@@ -355,6 +382,29 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
             }
             tid_out[(long long)j * max_det + r] = v;
             if (slot_out) slot_out[(long long)j * max_det + r] = slot;
+            if (HOLD && r < nc) hold.tid[(long long)j * (max_det + T) + r] = v;
+        }
+        if (HOLD) {                                                    // rule 11: the held rows behind the frame's nc, then zero rows
+            const int hrows = max_det + T, nheld = skip ? 0 : s_hcnt[0] + s_hcnt[1];
+            float* dh = hold.det + (long long)j * hrows * LP_DET_COLS;
+            for (int i = nc * LP_DET_COLS + tid; i < hrows * LP_DET_COLS; i += TK_T) {
+                const int r = i / LP_DET_COLS, col = i - r * LP_DET_COLS;
+                float v = 0.f;
+                if (r - nc < nheld) {
+                    const int slot = s_hslot[r - nc];
+                    const int* sl = sst + TK_HDR_WORDS + slot * TK_SLOT_WORDS;
+                    if (col < 12) {                                    // the products of step 1 of this frame: k = (float)misses
+                        const float d = __int_as_float(sl[TK_W_VEL + (col & 1)]) * (float)sl[4];
+                        v = __int_as_float(sl[TK_W_BOX + col]) + d;
+                    } else {
+                        v = col < 20 ? s_share[slot * TK_HEADS + col - 12] : (float)s_best[slot * TK_HEADS + col - 20];
+                    }
+                }
+                dh[i] = v;
+            }
+            for (int r = nc + tid; r < hrows; r += TK_T)
+                hold.tid[(long long)j * hrows + r] = r - nc < nheld ? sst[TK_HDR_WORDS + s_hslot[r - nc] * TK_SLOT_WORDS] : -1;
+            if (tid == 0) hold.count[j] = nc + nheld;
         }
         __syncthreads();                                               // the next frame reuses the LDS tables and reads the state
     }
@@ -398,11 +448,21 @@ extern "C" int lp_track_update_slots(void* state, int n_streams, int max_tracks,
                                      const int32_t* count, int B, int max_det, const int* stream_of, const unsigned char* flush, float* det_out,
                                      int32_t* tid, int32_t* slot, int32_t* ended_i, float* ended_f, int32_t* ended_count, int max_ended,
                                      void* stream) {
+    return lp_track_update_hold(state, n_streams, max_tracks, p, det, count, B, max_det, stream_of, flush, det_out, tid, slot, ended_i,
+                                ended_f, ended_count, max_ended, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int lp_track_update_hold(void* state, int n_streams, int max_tracks, const lp_track_params* p, const float* det,
+                                    const int32_t* count, int B, int max_det, const int* stream_of, const unsigned char* flush, float* det_out,
+                                    int32_t* tid, int32_t* slot, int32_t* ended_i, float* ended_f, int32_t* ended_count, int max_ended,
+                                    const lp_track_hold_params* hp, float* det_hold, int32_t* count_hold, int32_t* tid_hold, void* stream) {
     const std::string fn = "lp_track_update: ";
     if (n_streams < 1 || max_tracks < 1 || max_tracks > LP_TRACK_MAX_TRACKS)
         return fail(LP_ERR_ARG, fn + "need n_streams >= 1 and max_tracks in 1.." + std::to_string(LP_TRACK_MAX_TRACKS));
     if (B < 0 || max_det < 1 || max_det > 0x7fffffff / LP_DET_COLS || max_ended < 0)
         return fail(LP_ERR_ARG, fn + "need B >= 0, max_det >= 1 and max_ended >= 0");
+    if (hp && (hp->min_hits < 1 || hp->max_misses < 0)) return fail(LP_ERR_ARG, fn + "hold needs min_hits >= 1 and max_misses >= 0");
+    if (hp && max_det > 0x7fffffff / LP_DET_COLS - max_tracks) return fail(LP_ERR_ARG, fn + "hold: max_det + max_tracks rows overflow");
     if (!p) return fail(LP_ERR_ARG, fn + "null pointer (params)");
     if (!(p->match_thres >= 0.0 && p->match_thres <= 1.0)) return fail(LP_ERR_ARG, fn + "match_thres must be in [0, 1]");
     if (!(std::fabs(p->new_thres) <= 3.0e38)) return fail(LP_ERR_ARG, fn + "new_thres must be finite (|new_thres| <= 3e38)");
@@ -419,12 +479,23 @@ extern "C" int lp_track_update_slots(void* state, int n_streams, int max_tracks,
         const size_t bytes = (size_t)B * max_det * LP_DET_COLS * sizeof(float);
         if (a < b + bytes && b < a + bytes) return fail(LP_ERR_ARG, fn + "det_out may not alias det");
     }
+    if (hp) {
+        if (B > 0 && (!det_hold || !count_hold || !tid_hold)) return fail(LP_ERR_ARG, fn + "null pointer (hold)");
+        if (B > 0) {
+            const uintptr_t h = (uintptr_t)det_hold, a = (uintptr_t)det, b = (uintptr_t)det_out;
+            const size_t bytes = (size_t)B * max_det * LP_DET_COLS * sizeof(float);
+            const size_t hbytes = (size_t)B * ((size_t)max_det + max_tracks) * LP_DET_COLS * sizeof(float);
+            if ((h < a + bytes && a < h + hbytes) || (h < b + bytes && b < h + hbytes))
+                return fail(LP_ERR_ARG, fn + "det_hold may not alias det or det_out");
+        }
+    }
     for (int b = 0; b < B; ++b)
         if (stream_of[b] < -1 || stream_of[b] >= n_streams)
             return fail(LP_ERR_ARG, fn + "stream " + std::to_string(stream_of[b]) + " of frame " + std::to_string(b) + " (need -1 or 0.." +
                                         std::to_string(n_streams - 1) + ")");
-    static std::atomic<unsigned long long> attr{0};
-    if (int rc = set_max_lds_once(track_kernel, SORT_LDS_KEYS * 8, attr, "track")) return rc;
+    static std::atomic<unsigned long long> attr{0}, attr_hold{0};
+    if (int rc = hp ? set_max_lds_once(track_kernel<true>, SORT_LDS_KEYS * 8, attr_hold, "track hold")
+                    : set_max_lds_once(track_kernel<false>, SORT_LDS_KEYS * 8, attr, "track")) return rc;
 
     TkParams prm;
     prm.thr_f = (float)p->match_thres;                          // largest fp32 not above the double threshold
@@ -447,11 +518,15 @@ extern "C" int lp_track_update_slots(void* state, int n_streams, int max_tracks,
     while (n_max < max_tracks * rows_cap) n_max <<= 1;
     const size_t lds = (size_t)n_max * 8;
     const long long sstride = (long long)stream_words(max_tracks);
+    const size_t hrows = (size_t)max_det + max_tracks;
     auto launch = [&](const TkTable& tab, int nblk, int b0) -> int {
-        hipLaunchKernelGGL(track_kernel, dim3((unsigned)nblk), dim3(TK_T), lds, st, tab, prm, (int*)state, max_tracks, sstride,
-                           det ? det + (size_t)b0 * max_det * LP_DET_COLS : nullptr, count ? count + b0 : nullptr, max_det,
+        TkHold hold = {};
+        if (hp && B > 0) hold = TkHold{hp->min_hits, hp->max_misses, det_hold + (size_t)b0 * hrows * LP_DET_COLS, count_hold + b0,
+                                       tid_hold + (size_t)b0 * hrows};
+        hipLaunchKernelGGL(hp ? track_kernel<true> : track_kernel<false>, dim3((unsigned)nblk), dim3(TK_T), lds, st, tab, prm, (int*)state,
+                           max_tracks, sstride, det ? det + (size_t)b0 * max_det * LP_DET_COLS : nullptr, count ? count + b0 : nullptr, max_det,
                            det_out ? det_out + (size_t)b0 * max_det * LP_DET_COLS : nullptr, tid ? tid + (size_t)b0 * max_det : nullptr,
-                           slot ? slot + (size_t)b0 * max_det : nullptr, ended_i, ended_f, ended_count, max_ended);
+                           slot ? slot + (size_t)b0 * max_det : nullptr, ended_i, ended_f, ended_count, max_ended, hold);
         LP_HIP_CHECK(hipGetLastError());
         return LP_OK;
     };

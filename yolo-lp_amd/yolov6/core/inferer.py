@@ -46,7 +46,7 @@ from yolov6.utils.nv12 import MATRICES, Nv12Frame, bgr_to_nv12_np, nv12_to_bgr_n
 class Inferer:
     def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True, tile=None, tile_overlap=0.2,
                  tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5, best_shots=False,
-                 nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1):
+                 nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -63,11 +63,19 @@ class Inferer:
         of the frames of ``.nv12`` sources, which need ``nv12``.
         ``redact`` = 'mosaic' | 'fill' (black): ``infer`` also writes every frame with the plates of its detections made unreadable
         (``yolov6.utils.redact`` states the rules): the quad of every row, grown by ``redact_margin`` of its size about its centre,
-        in cells of ``redact_cell`` pixels (mosaic)."""
+        in cells of ``redact_cell`` pixels (mosaic).
+        ``redact_hold`` (with ``track`` and ``redact``): a plate that is being tracked stays redacted in the frames in which
+        the detector misses it, at the box and corners its track predicts, until the track ends (rule 11 of
+        ``yolov6.utils.track``); a track needs ``redact_hold_min_hits`` detections before it is held.  The rows returned and
+        saved, the crops, ``tracks.txt`` and ``plates.txt`` are what they are without it."""
         self.__dict__.update(locals())
         if redact is not None:
             from yolov6.utils.redact import check_params
             check_params(redact, redact_cell, redact_margin)
+        if redact_hold and not (track and redact is not None):
+            raise ValueError('redact_hold needs track=True and redact=MODE')
+        if redact_hold and int(redact_hold_min_hits) < 1:
+            raise ValueError('redact_hold_min_hits must be >= 1')
         if best_shots and not track:
             raise ValueError('best_shots needs track=True')
         if merge_metric not in ('iou', 'ios'):
@@ -326,6 +334,8 @@ class Inferer:
         else:
             self._tracker = PlateTrackerNp(1 + len(videos), **kw)
         self._track_tids, self._track_lines, self._track_ended, self._track_shots = deque(), [], [], []
+        if self.redact_hold:
+            self._tracker.enable_hold(min_hits=self.redact_hold_min_hits)
         if self.best_shots:
             if self.device.type != 'cpu':
                 self._tracker.enable_best_shot(crop_size, max_crops=self.SHOT_ROWS)
@@ -466,27 +476,34 @@ class Inferer:
         """With ``redact``: queue for ``infer`` the frames of one group with the plates of their final rows ``dets`` redacted, host
         BGR arrays or host ``Nv12Frame``s.  On a GPU ``dev_frames`` (the group's device frames) are redacted in place
         (``runtime.redact_plates``: whatever reads them has been enqueued before) and read back; on the CPU ``frames`` are
-        copied (``redact_plates_np``)."""
+        copied (``redact_plates_np``).  With ``redact_hold`` the rows are those the group's tracker update left in
+        ``last_hold`` -- the same rows followed by the predicted rows of the tracks each frame missed -- taken where they lie."""
         if self.redact is None:
             return
         n, m = len(frames), max([len(d) for d in dets] + [1])
+        hold = self._tracker.last_hold if self.redact_hold else None
         if dev_frames is not None:
             from yolov6.hip import runtime
-            det = torch.zeros(n, m, 28, dtype=torch.float32, device=self.device)
-            for k, d in enumerate(dets):
-                det[k, :len(d)] = d
-            count = torch.tensor([len(d) for d in dets], dtype=torch.int32).to(self.device)
+            if hold is not None:
+                det, count = hold[0], hold[1]       # [>= n, max_det + slots, 28] on the device: no host read, no copy
+            else:
+                det = torch.zeros(n, m, 28, dtype=torch.float32, device=self.device)
+                for k, d in enumerate(dets):
+                    det[k, :len(d)] = d
+                count = torch.tensor([len(d) for d in dets], dtype=torch.int32).to(self.device)
             dev_frames = list(dev_frames)[:n]
             runtime.redact_plates(dev_frames, det, count, self.redact, self.redact_cell, self.redact_margin)
             self._redacted.extend(Nv12Frame(f.y.cpu().numpy(), f.uv.cpu().numpy(), f.matrix) if isinstance(f, Nv12Frame)
                                   else f.cpu().numpy() for f in dev_frames)
         else:
             from yolov6.utils.redact import redact_plates_np
-            det = np.zeros((n, m, 28), np.float32)
-            for k, d in enumerate(dets):
-                det[k, :len(d)] = d.detach().float().cpu().numpy()
-            self._redacted.extend(redact_plates_np(list(frames), det, [len(d) for d in dets], self.redact, self.redact_cell,
-                                                   self.redact_margin)[0])
+            if hold is not None:
+                det, count = hold[0], hold[1]
+            else:
+                det, count = np.zeros((n, m, 28), np.float32), [len(d) for d in dets]
+                for k, d in enumerate(dets):
+                    det[k, :len(d)] = d.detach().float().cpu().numpy()
+            self._redacted.extend(redact_plates_np(list(frames), det, count, self.redact, self.redact_cell, self.redact_margin)[0])
 
     def write_redacted(self, img_path, frame, save_dir):
         """One redacted frame (BGR array or host ``Nv12Frame``) as ``<save_dir>/redacted/<image name>``, by the writer of

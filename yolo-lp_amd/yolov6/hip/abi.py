@@ -95,6 +95,11 @@ class TrackParams(ctypes.Structure):
     _fields_ = [('match_thres', c_double), ('new_thres', c_double), ('expand', c_double), ('max_age', c_int), ('ncls', c_int * 8)]
 
 
+class TrackHoldParams(ctypes.Structure):
+    """lp_track_hold_params"""
+    _fields_ = [('min_hits', c_int), ('max_misses', c_int)]
+
+
 class ConvDesc(ctypes.Structure):
     """lp_conv_desc"""
     _fields_ = [('n_src', c_int), ('src', c_int * LP_MAX_SRC), ('dst', c_int), ('ksize', c_int), ('stride', c_int),
@@ -160,6 +165,9 @@ SYMBOLS = {
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'lp_track_update_slots': (c_int, [c_void_p, c_int, c_int, POINTER(TrackParams), c_void_p, c_void_p, c_int, c_int, POINTER(c_int),
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'lp_track_update_hold': (c_int, [c_void_p, c_int, c_int, POINTER(TrackParams), c_void_p, c_void_p, c_int, c_int, POINTER(c_int),
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                     POINTER(TrackHoldParams), c_void_p, c_void_p, c_void_p, c_void_p]),
     'lp_plate_crops_batch': (c_int, [POINTER(CropDesc), c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                      c_void_p]),
     'lp_crop_sharpness': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -1309,6 +1309,9 @@ class PlateTracker:
         self._out = {}
         self._slot = {}
         self._shots = None
+        self._hold = None
+        #: (det_hold, count_hold, tid_hold) of the last ``update`` after ``enable_hold``, else None
+        self.last_hold = None
 
     def reset(self, streams=None):
         """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0; their best-shot
@@ -1347,11 +1350,42 @@ class PlateTracker:
         det_out, tid, ended_i, ended_f, ended_count = out
         so = (ctypes.c_int * max(B, 1))(*stream_of)
         fl = (ctypes.c_ubyte * S)(*flush)
+        hp, hold = None, (None, None, None)
+        if self._hold is not None:
+            hp, hold = ctypes.byref(self._hold['params']), self.hold_buffers(B, max_det)
+            self.last_hold = hold
         with torch.cuda.device(self.device):
-            abi.check(abi.load().lp_track_update_slots(_dptr(self.state), S, self.max_tracks, ctypes.byref(self._params), _dptr(det),
-                                                       _dptr(count), B, max_det, so, ctypes.cast(fl, ctypes.c_void_p), _dptr(det_out),
-                                                       _dptr(tid), _dptr(self.slot_buffer(B, max_det)), _dptr(ended_i), _dptr(ended_f),
-                                                       _dptr(ended_count), max_ended, _stream_ptr(self.device)), 'lp_track_update_slots')
+            abi.check(abi.load().lp_track_update_hold(_dptr(self.state), S, self.max_tracks, ctypes.byref(self._params), _dptr(det),
+                                                      _dptr(count), B, max_det, so, ctypes.cast(fl, ctypes.c_void_p), _dptr(det_out),
+                                                      _dptr(tid), _dptr(self.slot_buffer(B, max_det)), _dptr(ended_i), _dptr(ended_f),
+                                                      _dptr(ended_count), max_ended, hp, _dptr(hold[0]), _dptr(hold[1]), _dptr(hold[2]),
+                                                      _stream_ptr(self.device)), 'lp_track_update_hold')
+        return out
+
+    # ---- redaction held over missed frames (lp_track_update_hold; rule 11 of yolov6/utils/track.py) -----------------------------
+    def enable_hold(self, min_hits=1, max_misses=None):
+        """From now on every ``update`` / ``update_with_shots`` also fills ``hold_buffers`` (``last_hold``): the frame's rows
+        followed by a predicted row for every track of at least ``min_hits`` hits that the frame missed, for at most
+        ``max_misses`` frames in a row (None, or anything above ``max_age``: ``max_age``, where the track ends).  That is the
+        (det, count) to hand ``redact_plates``, so that a plate the detector loses for a frame is still covered.  Returns,
+        state and every other buffer are what they are without it."""
+        min_hits, max_misses = int(min_hits), self.max_age if max_misses is None else int(max_misses)
+        if min_hits < 1 or max_misses < 0:
+            raise ValueError('hold needs min_hits >= 1 and max_misses >= 0')
+        self._hold = dict(params=abi.TrackHoldParams(min_hits, max_misses), out={})
+
+    def hold_buffers(self, B, max_det):
+        """The persistent (det_hold [B,max_det+max_tracks,28] fp32, count_hold [B] int32, tid_hold [B,max_det+max_tracks] int32)
+        an ``update`` of that shape fills after ``enable_hold`` (``PlateTrackerNp.hold_buffers``)."""
+        if self._hold is None:
+            raise RuntimeError('call enable_hold() first')
+        key = (int(B), int(max_det))
+        out = self._hold['out'].get(key)
+        if out is None:
+            rows, dev = key[1] + self.max_tracks, self.device
+            out = self._hold['out'][key] = (torch.empty(key[0], rows, abi.LP_DET_COLS, dtype=torch.float32, device=dev),
+                                            torch.empty(key[0], dtype=torch.int32, device=dev),
+                                            torch.empty(key[0], rows, dtype=torch.int32, device=dev))
         return out
 
     def slot_buffer(self, B, max_det):

@@ -28,6 +28,15 @@ n = min(max(count, 0), max_det, MAX_DETS) rows take part):
      12..19 replaced by the track's shares and 20..27 by (float)best_p, read after this frame's vote; other rows below
      min(max(count, 0), max_det) are copied, rows at or past it are zero;
  10. the stream's frame counter goes up.
+ 11. hold (``enable_hold(min_hits, max_misses)``, lp_track_update_hold; read-only on the state, for redaction): a slot is held in
+     a frame iff it was live at the start of the frame, was not matched, did not end in it, has hits >= min_hits and, after
+     the increment of 5, misses <= max_misses.  Its held row: k = (float)misses, dx = vx * k, dy = vy * k (the k and the
+     products of step 1 of this frame); columns 0..3 = the stored box + (dx, dy, dx, dy): the box step 1 predicted before the
+     expansion; columns 4..11 = the stored corners, x columns + dx and y columns + dy; columns 12..19 the track's shares and
+     20..27 its voted ids (8).  Per frame, with nc = min(max(count, 0), max_det): det_hold [max_det + max_tracks, 28] = the nc
+     rows of det_out, then the held rows in slot order, then zero rows; count_hold = nc + the number of held rows; tid_hold
+     [max_det + max_tracks] = tid for the first nc rows, the track id for held rows, -1 elsewhere.  A frame that is not tracked
+     has no held row.  (det_hold, count_hold) is the layout ``redact_plates`` takes.
 """
 import numpy as np
 
@@ -166,6 +175,9 @@ class PlateTrackerNp:
         #: int32 [B, max_det] of the last ``update``: the slot of each matched or new row's track, -1 wherever its tid is -1
         #: (the ``slot`` output of lp_track_update_slots)
         self.last_slot = np.zeros((0, 1), np.int32)
+        self._hold = None
+        #: (det_hold, count_hold, tid_hold) of the last ``update`` after ``enable_hold`` (rule 11), else None
+        self.last_hold = None
 
     _SLOT_ARRAYS = ('id', 'first', 'last', 'hits', 'misses', 'box', 'cor', 'vel', 'votes', 'total')
 
@@ -174,6 +186,46 @@ class PlateTrackerNp:
         for s in (range(self.n_streams) if streams is None else streams):
             for name in self._SLOT_ARRAYS + ('frame', 'next_id', 'dropped'):
                 getattr(self, name)[s] = 0
+
+    def enable_hold(self, min_hits=1, max_misses=None):
+        """From now on every ``update`` also fills ``hold_buffers`` (rule 11): the frame's rows followed by a predicted row for
+        every track of at least ``min_hits`` hits that the frame missed, for at most ``max_misses`` frames in a row (None, or
+        anything above ``max_age``: ``max_age``, where the track ends).  The state and every other output stay what they are."""
+        min_hits, max_misses = int(min_hits), self.max_age if max_misses is None else int(max_misses)
+        if min_hits < 1 or max_misses < 0:
+            raise ValueError('hold needs min_hits >= 1 and max_misses >= 0')
+        self._hold = dict(min_hits=min_hits, max_misses=max_misses, out={})
+
+    def hold_buffers(self, B, max_det):
+        """The persistent (det_hold [B,max_det+max_tracks,28] fp32, count_hold [B] int32, tid_hold [B,max_det+max_tracks] int32)
+        an ``update`` of that shape fills after ``enable_hold``."""
+        if self._hold is None:
+            raise RuntimeError('call enable_hold() first')
+        key = (int(B), int(max_det))
+        out = self._hold['out'].get(key)
+        if out is None:
+            rows = key[1] + self.max_tracks
+            out = self._hold['out'][key] = (np.zeros((key[0], rows, DET_COLS), f32), np.zeros(key[0], np.int32),
+                                            np.full((key[0], rows), -1, np.int32))
+        return out
+
+    def _held_rows(self, s, was_live, slot_row):
+        """Rule 11 behind step 5 of a frame: [(row [28], track id)] of the held slots of stream ``s``, in slot order."""
+        hp, out = self._hold, []
+        for t in np.nonzero(was_live)[0]:
+            if slot_row[t] >= 0 or self.hits[s, t] < hp['min_hits'] or self.misses[s, t] > hp['max_misses']:
+                continue                                  # matched; ended (hits is 0 again); too young; missed for too long
+            row = np.zeros(DET_COLS, f32)
+            with np.errstate(all='ignore'):
+                k = f32(self.misses[s, t])
+                dx, dy = self.vel[s, t, 0] * k, self.vel[s, t, 1] * k
+                d = np.array([dx, dy], f32)
+                row[0:4] = self.box[s, t] + np.tile(d, 2)
+                row[4:12] = self.cor[s, t] + np.tile(d, 4)
+            best, share = self.read(s, t)
+            row[12:20], row[20:28] = share, best.astype(f32)
+            out.append((row, int(self.id[s, t])))
+        return out
 
     def live(self, s):
         """bool [max_tracks]: the live slots of stream ``s``."""
@@ -247,6 +299,7 @@ class PlateTrackerNp:
                 self.misses[s, t] += 1
                 if self.misses[s, t] > self.max_age:
                     self._end(s, t, ended)
+        self._held = self._held_rows(s, live, slot_row) if self._hold is not None else []
         for r in range(n):
             if row_slot[r] >= 0:
                 continue
@@ -309,6 +362,7 @@ class PlateTrackerNp:
         tid = np.full((B, max_det), -1, np.int32)
         slot = self.last_slot = np.full((B, max_det), -1, np.int32)
         ended = [[] for _ in range(S)]
+        held = [[] for _ in range(B)]
         for b, s in enumerate(stream_of):
             if s < 0:
                 nc = min(max(int(count[b]), 0), max_det)
@@ -316,6 +370,16 @@ class PlateTrackerNp:
             else:
                 det_out[b], tid[b] = self._frame(s, det[b], count[b], ended[s])
                 slot[b, :len(self._row_slot)] = self._row_slot
+                held[b] = self._held
+        if self._hold is not None:
+            det_hold, count_hold, tid_hold = self.last_hold = self.hold_buffers(B, max_det)
+            det_hold[:], tid_hold[:] = 0, -1
+            for b in range(B):
+                nc = min(max(int(count[b]), 0), max_det)
+                det_hold[b, :nc], tid_hold[b, :nc] = det_out[b, :nc], tid[b, :nc]
+                for k, (row, track_id) in enumerate(held[b]):
+                    det_hold[b, nc + k], tid_hold[b, nc + k] = row, track_id
+                count_hold[b] = nc + len(held[b])
         for s in range(S):
             if flush[s]:
                 for t in np.nonzero(self.live(s))[0]:
