@@ -616,6 +616,72 @@ int lp_redact_plates_batch(const lp_redact_desc* desc, int n_frames, const float
                            const lp_redact_params* p, int32_t* status /* [n_frames,max_det] */,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* lp_lookback_update: the look-back delay of redaction.  lp_track_update_hold covers a tracked plate from its first detection on; a
+ * plate enters the picture small or blurred and is detected a few frames later, and those first frames would be stored readable.
+ * A small device-resident delay line keeps, per stream, the redaction rows of the last `depth` frames, adds rows to those past
+ * frames once a new track's second detection has fixed its velocity, and hands the rows of a frame out `depth` frames later, when
+ * the frame itself is redacted (lp_redact_plates_batch takes rel_det, rel_count as they are; its result does not depend on the
+ * order of the rows).  Called right behind lp_track_update_hold of the same frames; the frame table travels as kernel arguments (one
+ * launch per LP_FRAMES_PER_LAUNCH frames, one workgroup per stream, plus one closing launch per 64 streams): nothing is uploaded, no
+ * host sync, capturable in a graph.  The reference has nothing here; yolov6/utils/lookback.py::LookbackNp restates the rules
+ * below bit for bit.
+ *   Parameters: depth D in 1..LP_LOOKBACK_MAX_DEPTH; max_back >= 0: the frames before a track's first detection that are covered;
+ *   back_cap >= 0: the back rows a stored frame can take.  hold_rows = max_det + max_tracks as lp_track_update_hold lays det_hold
+ *   out (any hold_rows >= max_det is taken), rows = hold_rows + back_cap: every stored entry is [rows,28] fp32 plus a count.
+ *   state: DEVICE, 16-byte aligned, lp_lookback_state_bytes(n_streams, max_tracks, depth, rows) bytes, all zero = empty (the caller
+ *   zeroes it once; zeroing a stream's lp_lookback_state_bytes(1, ...) bytes resets that stream, together with the tracker's).
+ *   Per stream, in 4-byte words: f (the counter of tracked frames), base (every frame below it has been released), dropped (the
+ *   back rows that found no room), one unused; per tracker slot 16 words: id + 1 (0 = empty), seen (0, 1 or 2), first (the stream
+ *   frame of the first detection), one unused, the twelve geometry words of that detection; the D counts of the ring padded to a
+ *   multiple of 4 words; the ring of D entries of rows * 28 floats, frame g living in entry g % D.  D * rows * 112 bytes plus
+ *   16 + 64 * max_tracks + 4 * D (rounded up to 16) of tables.
+ *   Inputs (DEVICE) are what lp_track_update_hold of the same frames left: det_hold [B,hold_rows,28] (16-byte aligned), count_hold
+ *   [B], tid [B,max_det], slot [B,max_det] (a slot names at most one row of a frame); stream_of and flush: HOST, as given to the
+ *   tracker.  Outputs (DEVICE): rel_det [B,rows,28] fp32 (16-byte aligned), rel_count [B], rel_frame [B] int32; tail_det
+ *   [n_streams,D,rows,28] fp32 (16-byte aligned), tail_count [n_streams,D], tail_frame [n_streams,D] int32.  Every element of
+ *   rel_* and tail_* is written exactly once per call, so the buffers need no clearing.
+ * The frames of a stream are taken in ascending b.  Per tracked frame, its stream counter at f:
+ *   A. follow: every row r < min(max_det, LP_TRACK_MAX_DETS) with slot[b][r] = t in 0..max_tracks-1 and tid[b][r] = id >= 0, in
+ *      ascending r; the row is det_hold[b][r], which is det_out[b][r] (rule 11).  The entry of t holds another id, or is empty:
+ *      it becomes {id + 1, seen = 1, first = f, geometry = columns 0..11}.  It holds id with seen == 1: the row CONFIRMS the
+ *      track (B) and seen = 2.  seen == 2: nothing happens.
+ *   B. back rows of a confirming row, fp32 op by op, no fused multiply-add: k = (float)(f - first),
+ *      vx = ((x1' + x2') * 0.5f - (x1 + x2) * 0.5f) / k and vy likewise (step 4 of lp_track_update; primes mark the confirming
+ *      row, the unprimed values are the stored first geometry).  Targets: every frame g with
+ *      max(base, f - D, first - max_back, 0) <= g < f and g != first, in ascending g.  The back row for g: m = (float)(g - first)
+ *      (negative before the first detection, positive in the gap between the two), dx = vx * m, dy = vy * m (rounded products);
+ *      columns 0..3 = the first box + (dx, dy, dx, dy); columns 4..11 = the first corners, x columns (4, 6, 8, 10) + dx, y
+ *      columns (5, 7, 9, 11) + dy; columns 12..27 those of the confirming row (the track's shares and voted ids after this
+ *      frame's vote).  The row is appended to the ring entry of g behind the rows already there; within one frame the appended
+ *      rows come in ascending r.  An entry that already holds `rows` rows does not take the row and dropped goes up.  A track
+ *      with only one detection gets no back rows.
+ *   C. release: if f - D >= base: rel_det[b] = the entry of frame f - D (its rows, then zero rows), rel_count[b] its count,
+ *      rel_frame[b] = f - D, then base = f - D + 1.  Otherwise rel_det[b] is all zero, rel_count[b] = 0, rel_frame[b] = -1.
+ *   D. store: the entry f % D becomes the first min(max(count_hold[b], 0), hold_rows) rows of det_hold[b] followed by zero
+ *      rows, with that count.  Then f goes up.
+ * A frame with stream_of -1 is released at once: rel_det[b] = its own det_hold rows below the clamped count, then zero rows,
+ * rel_count[b] that count, rel_frame[b] = -2; it touches no state.
+ * After a stream's frames, with flush[s]: every frame still in the ring, base .. f - 1, goes to tail_det[s], tail_count[s] and
+ * tail_frame[s] in ascending frame order; the remaining tail entries are zero rows, count 0, frame -1; then base = f.  The slot
+ * entries stay: the tracker has ended those tracks, and new ids replace them by rule A.  A stream without a flush gets an
+ * all-empty tail.  B == 0 with a flush is valid and gives tails only.
+ * What it does not do: the model is constant velocity from two detections only; a plate visible for more than depth frames before
+ * its confirmation is covered for depth of them; a track that is never confirmed adds nothing; the delay is depth frames of
+ * latency, and depth frames that the caller's frame memory stays occupied.
+ * Every argument is checked before the first launch (LP_ERR_ARG, nothing launched): depth in 1..LP_LOOKBACK_MAX_DEPTH, max_back >= 0,
+ * back_cap >= 0, n_streams >= 1, max_tracks in 1..LP_TRACK_MAX_TRACKS, B >= 0, max_det >= 1, hold_rows >= max_det, rows * 28 below
+ * 2^31, stream_of[b] in -1..n_streams-1, the alignment of state, det_hold, rel_det and tail_det, the pointers (the per-frame ones
+ * may be NULL when B == 0; flush may be NULL: no stream is flushed), and that no output (rel_*, tail_*) overlaps the state, an
+ * input or another output.  Not checked: that a slot names at most one row of a frame (the tracker's outputs do). */
+#define LP_LOOKBACK_MAX_DEPTH 32
+size_t lp_lookback_state_bytes(int n_streams, int max_tracks, int depth, int rows);   /* 0: bad arguments */
+int lp_lookback_update(void* state, int n_streams, int max_tracks, int depth, int max_back, int back_cap,
+                       const float* det_hold, const int32_t* count_hold, const int32_t* tid, const int32_t* slot,
+                       int B, int max_det, int hold_rows,
+                       const int* stream_of /* HOST [B] */, const unsigned char* flush /* HOST [n_streams] or NULL */,
+                       float* rel_det, int32_t* rel_count, int32_t* rel_frame,
+                       float* tail_det, int32_t* tail_count, int32_t* tail_frame, void* stream);
+
 /* lp_eval_counts: the matching loops of Evaler.eval (yolov6/core/evaler.py:153-243, box_iou general.py:93-115) for a
  * batch of images, one workgroup per image.
  *   det [B,max_det,28] fp32 + det_count [B]: detections as lp_nms returns them (xyxy, 8 corner coords, 8 confs, 8 ids)

@@ -5,7 +5,7 @@
                                  [--crops N] [--redact [--redact-cell 16]]
     python tools/frames_bench.py --tile [--tile-baseline] [--tile-frame 2160 3840] [--tile-size 640] [--tile-overlap 128]
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
-    python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot] [--redact [--hold]] [--nv12]
+    python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot] [--redact [--hold [--lookback D]]] [--nv12]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
@@ -48,6 +48,9 @@ With ``--track --redact [--hold]`` (also with ``--nv12``: the streams' frames ar
 are timed from events on the tracker's own rows, every stream seeing another frame in every step so that tracks are missed;
 ``--hold`` runs a second tracker with ``enable_hold`` on the same frames, alternating, and redacts along its ``last_hold``:
 ``update_ms`` / ``update_hold_ms``, ``redact_ms`` / ``redact_hold_ms`` and the rows per frame each mosaic covered.
+``--lookback D`` adds a third tracker with the hold and a ``LookbackRedactor`` of that depth behind it: ``update_lookback_ms`` (the
+same update), ``lookback_ms`` (lp_lookback_update) and ``redact_lookback_ms`` (the mosaic on the frames that leave the delay, along
+the rows released for them).
 The model is the synthetic recipe of bench.py (same weights scale), prepared as Inferer prepares it.
 """
 import argparse
@@ -94,6 +97,8 @@ def parse():
     ap.add_argument('--best-shot', action='store_true', help='with --track: also time crops + sharpness + gallery behind the update')
     ap.add_argument('--hold', action='store_true', help='with --track --redact: also time the update with the redaction hold (enable_hold) '
                                                         'and the redaction along its rows')
+    ap.add_argument('--lookback', type=int, default=0, metavar='D', help='with --track --redact --hold: also time the look-back delay of '
+                                                                         'that depth (LookbackRedactor) behind the update with the hold')
     ap.add_argument('--nv12', nargs='?', const='bt709', default=None, choices=['bt601', 'bt709', 'bt601f', 'bt709f'], metavar='MATRIX',
                     help='also send the same seeded frames as NV12 with this matrix and compare (default matrix: bt709)')
     ap.add_argument('--runs', type=int, default=3, help='timed runs of the frames/s figures (the spread is reported)')
@@ -269,6 +274,8 @@ def track_mode(args, model, dev, tdt):
         pool = [bgr_to_nv12_np(f, args.nv12) for f in pool]         # what a decoder delivers: encoded before any clock starts
     if args.hold and not args.redact:
         raise SystemExit('--hold needs --track --redact')
+    if args.lookback and not args.hold:
+        raise SystemExit('--lookback needs --track --redact --hold')
     H, W = letterbox_hw((h0, w0), size, stride)
     sync = torch.cuda.synchronize
     out = dict(metric='frames/s end to end with and without plate tracking (host frames in, rows out)', model=args.model,
@@ -366,30 +373,54 @@ def redact_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
     if args.hold:
         trackers['hold'] = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
         trackers['hold'].enable_hold()
-    times = {name: dict(update=[], redact=[]) for name in trackers}
+    lb, mid = None, [None]
+    if args.lookback:
+        from yolov6.utils.nv12 import Nv12Frame
+        trackers['lookback'] = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
+        trackers['lookback'].enable_hold()
+        lb = runtime.LookbackRedactor(trackers['lookback'], args.lookback, mode='mosaic', cell=args.redact_cell)
+
+        def mark():      # the event between lp_lookback_update and the mosaic of one push
+            mid[0] = torch.cuda.Event(enable_timing=True)
+            mid[0].record()
+    times = {name: dict(update=[], redact=[], lookback=[]) for name in trackers}
     rows = {name: [] for name in trackers}
-    warm = 3
+    warm = max(3, args.lookback + 1)
     for k in range(warm + args.reps + 1):
         for name, trk in trackers.items():
             frames = batcher.put([pool[(j + k) % len(pool)] for j in range(B)])      # (the put restores what the last mosaic wrote)
             xx, _ = runtime.preprocess_frames(frames, size, stride, tdt, batch=B, out=x)
             det, count, _ = runtime.detect_padded(model, xx, conf, iou, max_det)
             runtime.rescale_round_batch(det, count, net_hw, [f.shape for f in frames])
+            if name == 'lookback':      # the delay keeps references and the uploader reuses its buffer: copies, before the clock
+                frames = [Nv12Frame(f.y.clone(), f.uv.clone(), f.matrix) if isinstance(f, Nv12Frame) else f.clone() for f in frames]
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record()
             det_out = trk.update(det, count)[0]
             ev[1].record()
-            rdet, rcount = (det_out, count) if name == 'plain' else trk.last_hold[:2]
-            runtime.redact_plates(frames, rdet, rcount, 'mosaic', args.redact_cell)
+            if name == 'lookback':
+                lb.push(frames, between=mark)
+                rdet, rcount = lb.buffers(B, lb.entry_rows)[:2]
+            else:
+                rdet, rcount = (det_out, count) if name == 'plain' else trk.last_hold[:2]
+                runtime.redact_plates(frames, rdet, rcount, 'mosaic', args.redact_cell)
             ev[2].record()
             torch.cuda.synchronize()
             if k > warm:
                 times[name]['update'].append(ev[0].elapsed_time(ev[1]))
-                times[name]['redact'].append(ev[1].elapsed_time(ev[2]))
+                if name == 'lookback':
+                    times[name]['lookback'].append(ev[1].elapsed_time(mid[0]))
+                    times[name]['redact'].append(mid[0].elapsed_time(ev[2]))
+                else:
+                    times[name]['redact'].append(ev[1].elapsed_time(ev[2]))
                 rows[name].append(float(rcount.clamp(0, rdet.shape[1]).float().mean()))
     r = dict(redact_cell=args.redact_cell, reps=args.reps)
     for name in trackers:
-        sfx = '' if name == 'plain' else '_hold'
+        sfx = '' if name == 'plain' else '_' + name
+        if name == 'lookback':
+            r['lookback_depth'] = args.lookback
+            r['lookback_ms'] = round(float(np.median(times[name]['lookback'])), 4)
+            r['lookback_state_mib'] = round(lb.state.numel() * 4 / 2 ** 20, 2)
         r['update%s_ms' % sfx] = round(float(np.median(times[name]['update'])), 4)
         r['redact%s_ms' % sfx] = round(float(np.median(times[name]['redact'])), 4)
         r['redact%s_rows_per_frame' % sfx] = round(float(np.mean(rows[name])), 2)

@@ -7,7 +7,7 @@
                           [--track [--track-max-age 5] [--track-iou 0.3] [--track-expand 0.5] [--best-shots [--crop-size 64 192]]]
                           [--nv12 bt601|bt709|bt601f|bt709f [--nv12-size W H]]
                           [--redact mosaic|fill [--redact-cell 16] [--redact-margin 0.1]
-                           [--redact-hold [--redact-hold-min-hits 1]]]
+                           [--redact-hold [--redact-hold-min-hits 1] [--redact-lookback D [--redact-lookback-max-back N]]]]
 """
 import argparse
 import os
@@ -72,6 +72,11 @@ _FLAGS = [
     ('--redact-hold', dict(action='store_true', help='with --track and --redact: keep a tracked plate redacted, where its track predicts '
                                                      'it, in the frames in which the detector misses it (until the track ends)')),
     ('--redact-hold-min-hits', dict(type=int, default=1, help='with --redact-hold: detections a track needs before it is held')),
+    ('--redact-lookback', dict(type=int, default=None, metavar='D',
+                               help='with --redact-hold: redact every frame D frames late (1..32), so that the frames before a '
+                                    'plate\'s first detection are covered too, where its first two detections extrapolate it')),
+    ('--redact-lookback-max-back', dict(type=int, default=None, metavar='N',
+                                        help='with --redact-lookback: frames before the first detection that are covered (default D)')),
 ]
 
 
@@ -91,7 +96,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False, save_crops=False, crop_size=(64, 192),
         tile=None, tile_overlap=0.2, no_tile_overview=False, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3,
         track_expand=0.5, best_shots=False, nv12=None, nv12_size=None, redact=None, redact_cell=16,
-        redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1):
+        redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1, redact_lookback=None, redact_lookback_max_back=None):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track or redact) and not osp.exists(out_dir):
@@ -106,7 +111,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
                       tile_overlap=tile_overlap, tile_overview=not no_tile_overview, merge_metric=merge_metric, track=track, track_max_age=track_max_age,
                       track_iou=track_iou, track_expand=track_expand, best_shots=best_shots, nv12=nv12, nv12_size=nv12_size,
                       redact=redact, redact_cell=redact_cell, redact_margin=redact_margin, redact_hold=redact_hold,
-                      redact_hold_min_hits=redact_hold_min_hits).infer(
+                      redact_hold_min_hits=redact_hold_min_hits, redact_lookback=redact_lookback,
+                      redact_lookback_max_back=redact_lookback_max_back).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

@@ -25,6 +25,8 @@ read by the fused letterbox, a BGR frame exists on the device only where crops a
 With ``redact`` every detection's plate is made unreadable in the frame itself, by a mosaic or a fill (``runtime.redact_plates`` on a
 GPU, in place on the device frames and behind everything that reads them; ``redact_plates_np`` on the CPU), and the frame is
 written to ``<save_dir>/redacted/``.  NV12 frames are redacted as NV12 and converted only to be saved.
+With ``redact_lookback`` = D every frame is redacted D frames late, so that the frames before a plate's first detection are
+covered too (``runtime.LookbackRedactor`` on a GPU, ``LookbackNp`` on the CPU; ``yolov6.utils.lookback`` states the rule).
 """
 import math
 import os
@@ -46,7 +48,8 @@ from yolov6.utils.nv12 import MATRICES, Nv12Frame, bgr_to_nv12_np, nv12_to_bgr_n
 class Inferer:
     def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True, tile=None, tile_overlap=0.2,
                  tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5, best_shots=False,
-                 nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1):
+                 nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1,
+                 redact_lookback=None, redact_lookback_max_back=None):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -67,13 +70,23 @@ class Inferer:
         ``redact_hold`` (with ``track`` and ``redact``): a plate that is being tracked stays redacted in the frames in which
         the detector misses it, at the box and corners its track predicts, until the track ends (rule 11 of
         ``yolov6.utils.track``); a track needs ``redact_hold_min_hits`` detections before it is held.  The rows returned and
-        saved, the crops, ``tracks.txt`` and ``plates.txt`` are what they are without it."""
+        saved, the crops, ``tracks.txt`` and ``plates.txt`` are what they are without it.
+        ``redact_lookback`` = D in 1..32 (with ``track``, ``redact`` and ``redact_hold``): redaction is delayed by D frames per
+        stream, and once a new track's second detection has fixed its velocity the frames still inside the delay also get a row
+        for it, at most ``redact_lookback_max_back`` (default D) frames before its first detection (``yolov6.utils.lookback``).
+        ``redacted/<image name>`` is written when the frame leaves the delay, the rest at the end of the source; every other
+        output is what it is without it."""
         self.__dict__.update(locals())
         if redact is not None:
             from yolov6.utils.redact import check_params
             check_params(redact, redact_cell, redact_margin)
         if redact_hold and not (track and redact is not None):
             raise ValueError('redact_hold needs track=True and redact=MODE')
+        if redact_lookback is not None:
+            from yolov6.utils.lookback import check_lookback
+            if not (track and redact is not None and redact_hold):
+                raise ValueError('redact_lookback needs track=True, redact=MODE and redact_hold=True')
+            check_lookback(self.TRACK_SLOTS, redact_lookback, redact_lookback_max_back, None)
         if redact_hold and int(redact_hold_min_hits) < 1:
             raise ValueError('redact_hold_min_hits must be >= 1')
         if best_shots and not track:
@@ -162,12 +175,16 @@ class Inferer:
                 if save_crops and len(det):
                     self.write_crops(img_path, crops[k], save_dir)
                 results.append(det)
-                if self.redact is not None:
+                if self.redact is not None and self.redact_lookback is None:
                     self.write_redacted(img_path, self._redacted.popleft(), save_dir)
                 if self.track:
                     self._track_lines += ['%s %d %d' % (img_path, r, t) for r, t in enumerate(self._track_tids.popleft().tolist())]
+            self._write_delayed(save_dir)
         if self.track:
             self._track_finish(save_dir)
+            if self.redact_lookback is not None:        # right behind the tracker's flush: the frames still inside the delay
+                self._lookback_collect(self._lookback.flush_all())
+                self._write_delayed(save_dir)
         LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
         return results
 
@@ -336,6 +353,14 @@ class Inferer:
         self._track_tids, self._track_lines, self._track_ended, self._track_shots = deque(), [], [], []
         if self.redact_hold:
             self._tracker.enable_hold(min_hits=self.redact_hold_min_hits)
+        if self.redact_lookback is not None:
+            kw = dict(max_back=self.redact_lookback_max_back, mode=self.redact, cell=self.redact_cell, margin=self.redact_margin)
+            if self.device.type != 'cpu':
+                self._lookback = runtime.LookbackRedactor(self._tracker, self.redact_lookback, **kw)
+            else:
+                from yolov6.utils.lookback import LookbackNp
+                self._lookback = LookbackNp(self._tracker, self.redact_lookback, **kw)
+            self._lookback_paths = [deque() for _ in range(1 + len(videos))]     # per stream: the paths of the frames inside the delay
         if self.best_shots:
             if self.device.type != 'cpu':
                 self._tracker.enable_best_shot(crop_size, max_crops=self.SHOT_ROWS)
@@ -365,7 +390,8 @@ class Inferer:
         the frames ``paths`` (consecutive frames; slots past them are padding): (voted det, tid [B,max_det]), copies.
         ``frames``: the frames themselves, for ``best_shots`` (device tensors on a GPU, BGR arrays on the CPU)."""
         B = det.shape[0]
-        streams = [self._track_streams.get(p, 0) for p in paths] + [-1] * (B - len(paths))
+        streams = self._track_last_streams = [self._track_streams.get(p, 0) for p in paths] + [-1] * (B - len(paths))
+        self._track_last_paths = list(paths)
         # a slot's track lives at least max_age + 1 frames: so many records at most can end in B frames
         max_ended = self._tracker.max_tracks * (B // (self.track_max_age + 1) + 1)
         if not self.best_shots:
@@ -480,6 +506,9 @@ class Inferer:
         ``last_hold`` -- the same rows followed by the predicted rows of the tracks each frame missed -- taken where they lie."""
         if self.redact is None:
             return
+        if self.redact_lookback is not None:
+            self._redact_delayed(frames, dev_frames)
+            return
         n, m = len(frames), max([len(d) for d in dets] + [1])
         hold = self._tracker.last_hold if self.redact_hold else None
         if dev_frames is not None:
@@ -504,6 +533,33 @@ class Inferer:
                 for k, d in enumerate(dets):
                     det[k, :len(d)] = d.detach().float().cpu().numpy()
             self._redacted.extend(redact_plates_np(list(frames), det, count, self.redact, self.redact_cell, self.redact_margin)[0])
+
+    def _redact_delayed(self, frames, dev_frames=None):
+        """With ``redact_lookback``: hand the group's frames to the delay line behind the group's tracker update and queue, with
+        their paths, the frames that leave it (host BGR arrays or host ``Nv12Frame``s).  On a GPU the device frames are copied
+        first -- the delay line keeps references, and the uploader reuses its buffer for the next group."""
+        streams = self._track_last_streams
+        for path, s in zip(self._track_last_paths, streams):
+            self._lookback_paths[s].append(path)
+        if dev_frames is not None:
+            held = [Nv12Frame(f.y.clone(), f.uv.clone(), f.matrix) if isinstance(f, Nv12Frame) else f.clone()
+                    for f in list(dev_frames)[:len(frames)]]
+        else:
+            held = list(frames)
+        self._lookback_collect(self._lookback.push(held, streams))
+
+    def _lookback_collect(self, done):
+        for s, _, f in done:
+            if isinstance(f, Nv12Frame) and f.is_tensor:
+                f = Nv12Frame(f.y.cpu().numpy(), f.uv.cpu().numpy(), f.matrix)
+            elif torch.is_tensor(f):
+                f = f.cpu().numpy()
+            self._redacted.append((self._lookback_paths[s].popleft(), f))
+
+    def _write_delayed(self, save_dir):
+        """With ``redact_lookback``: write the frames that have left the delay so far."""
+        while self.redact_lookback is not None and self._redacted:
+            self.write_redacted(*self._redacted.popleft(), save_dir)
 
     def write_redacted(self, img_path, frame, save_dir):
         """One redacted frame (BGR array or host ``Nv12Frame``) as ``<save_dir>/redacted/<image name>``, by the writer of

@@ -33,6 +33,7 @@ LP_NV12_PER_LAUNCH = 32     # lp_preprocess_nv12_batch: slots per launch (its ta
 LP_MERGE_MAX_TILES, LP_MERGE_MAX_CANDIDATES = 64, 16384   # lp_merge_tiles: tiles per frame, tiles_of_frame * max_det_t
 LP_TRACK_MAX_TRACKS, LP_TRACK_MAX_DETS, LP_TRACK_MAX_CLS = 128, 128, 64   # lp_track_update: slots per stream, rows per frame, classes per head
 LP_REDACT_MAX_CELL = 64    # lp_redact_plates_batch: largest mosaic cell
+LP_LOOKBACK_MAX_DEPTH = 32    # lp_lookback_update: frames of delay
 LP_EVAL_NCOUNTS = 43  # lp_eval_counts: length of the counts vector (include/lp_hip.h)
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # .../yolo-lp_amd
@@ -178,6 +179,9 @@ SYMBOLS = {
     'lp_redact_workspace_bytes': (c_size_t, [POINTER(RedactDesc), c_int, POINTER(RedactParams)]),
     'lp_redact_plates_batch': (c_int, [POINTER(RedactDesc), c_int, c_void_p, c_void_p, c_int, POINTER(RedactParams), c_void_p, c_void_p,
                                        c_size_t, c_void_p]),
+    'lp_lookback_state_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'lp_lookback_update': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'lp_eval_counts': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'lp_check_sigmoid_monotone': (c_int, [c_void_p, c_void_p]),
     'lp_debug_poison_lds': (c_int, [c_void_p]),

@@ -22,6 +22,7 @@ from yolov6.core.frames import letterbox_placement
 from yolov6.core.tiles import hw_pair, plan_frames, tiles_per_frame
 from yolov6.hip import abi
 from yolov6.layers import common as L
+from yolov6.utils.lookback import LookbackHost
 from yolov6.utils.nv12 import Nv12Frame, is_nv12_list
 
 DET_CROSSOVER = 0.5   # candidate density (candidates / anchors) above which forward + lp_nms beats the detections-only forward
@@ -1312,6 +1313,8 @@ class PlateTracker:
         self._hold = None
         #: (det_hold, count_hold, tid_hold) of the last ``update`` after ``enable_hold``, else None
         self.last_hold = None
+        #: the tid buffer [B,max_det] the last ``update`` filled (what ``LookbackRedactor.push`` reads), else None
+        self.last_tid = None
 
     def reset(self, streams=None):
         """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0; their best-shot
@@ -1348,6 +1351,7 @@ class PlateTracker:
         stream_of, flush, max_ended = track.check_call(S, B, stream_of, flush, self.max_tracks if max_ended is None else max_ended)
         out = self.buffers(B, max_det, max_ended)
         det_out, tid, ended_i, ended_f, ended_count = out
+        self.last_tid = tid
         so = (ctypes.c_int * max(B, 1))(*stream_of)
         fl = (ctypes.c_ubyte * S)(*flush)
         hp, hold = None, (None, None, None)
@@ -1512,6 +1516,146 @@ class PlateTracker:
         det = torch.empty(0, int(max_det), abi.LP_DET_COLS, dtype=torch.float32, device=self.device)
         count = torch.empty(0, dtype=torch.int32, device=self.device)
         return self.update_with_shots([], det, count, stream_of=[], flush=[1] * self.n_streams, max_ended=max_ended)
+
+
+class LookbackRedactor(LookbackHost):
+    """Redaction delayed by ``depth`` frames, so that the frames BEFORE a plate's first detection are covered too
+    (lp_lookback_update; ``yolov6.utils.lookback`` states the rule, and ``LookbackNp`` there is the same object on numpy).  It
+    needs a ``PlateTracker`` with ``enable_hold`` called (RuntimeError otherwise).  ``max_back``: frames before the first detection
+    that are covered (default ``depth``); ``back_cap``: back rows a stored frame can take (default ``max_tracks``); ``mode``,
+    ``cell``, ``margin``, ``fill``: as ``redact_plates``.
+
+    ``push(frames, stream_of, flush)`` right after ``tracker.update(...)`` / ``update_with_shots(...)`` of the same frames
+    enqueues lp_lookback_update on ``tracker.last_hold``, ``last_tid`` and ``slot_buffer`` and keeps REFERENCES to the frames per
+    stream (BGR device tensors or ``Nv12Frame``s; no copy: the caller hands them over and must not write them until they come
+    back), then redacts every frame that leaves the delay in this call with the rows released for it, one ``redact_plates`` call
+    per push (plus one per flushed stream), and returns them as [(stream, frame_number, frame), ...] in release order; an
+    untracked frame comes back at once as (-1, -2, frame).  Which frame leaves at which b follows from the host's own
+    per-stream counters: no host read, and no allocation in the steady state (persistent buffers per update shape).
+    ``flush`` / ``flush_all()`` hand the tail frames back the same way.
+
+    Crops and best shots read the frames at update time, before any redaction of them is enqueued, so the order rule
+    "redaction goes last" holds by construction."""
+
+    def __init__(self, tracker, depth, max_back=None, back_cap=None, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0)):
+        if not isinstance(tracker, PlateTracker):
+            raise TypeError('LookbackRedactor needs a PlateTracker (LookbackNp is the CPU form)')
+        self._init_host(tracker, depth, max_back, back_cap, mode, cell, margin, fill)
+        self.device = tracker.device
+        self.state = None          # allocated by the first push: the entries' rows follow max_det
+        self._rows = None
+        self._out, self._status, self._blank = {}, {}, {}
+
+    def _slots(self):
+        B, hold_rows = self.tracker.last_hold[0].shape[:2]
+        return self.tracker.slot_buffer(B, hold_rows - self.max_tracks)
+
+    def _allocated(self):
+        return self.state is not None
+
+    @property
+    def entry_rows(self):
+        """Rows of a stored entry (max_det + max_tracks + back_cap); None before the first push with frames."""
+        return self._rows
+
+    def _state_for(self, rows):
+        if self.state is None:
+            nbytes = abi.load().lp_lookback_state_bytes(self.n_streams, self.max_tracks, self.depth, rows)
+            if nbytes == 0:
+                raise ValueError('lookback: entries of %d rows do not fit (rows * 28 must stay below 2^31)' % rows)
+            self._rows = rows
+            self.state = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.device)
+        elif rows != self._rows:
+            raise ValueError('this delay line holds entries of %d rows, the update has %d' % (self._rows, rows))
+        return self.state
+
+    def buffers(self, B, rows):
+        """The persistent outputs of a push behind an update of B frames: (rel_det [B,rows,28], rel_count [B], rel_frame [B],
+        tail_det [S,D,rows,28], tail_count [S,D], tail_frame [S,D])."""
+        key, S, D, dev = (int(B), int(rows)), self.n_streams, self.depth, self.device
+        out = self._out.get(key)
+        if out is None:
+            tails = next(iter(self._out.values()))[3:] if self._out else (
+                torch.empty(S, D, key[1], abi.LP_DET_COLS, dtype=torch.float32, device=dev),
+                torch.empty(S, D, dtype=torch.int32, device=dev), torch.empty(S, D, dtype=torch.int32, device=dev))
+            out = self._out[key] = (torch.empty(key[0], key[1], abi.LP_DET_COLS, dtype=torch.float32, device=dev),
+                                    torch.empty(key[0], dtype=torch.int32, device=dev),
+                                    torch.empty(key[0], dtype=torch.int32, device=dev)) + tuple(tails)
+        return out
+
+    def reset(self, streams=None):
+        """Zero the state of ``streams`` (all for None) and forget their frames; use it together with ``PlateTracker.reset``."""
+        if self.state is not None:
+            st = self.state.view(self.n_streams, -1)
+            if streams is None:
+                st.zero_()
+            else:
+                for s in streams:
+                    st[int(s)].zero_()
+        self._reset_host(streams)
+
+    @property
+    def dropped(self):
+        """int32 [n_streams] on the host: the back rows that found no room since the last reset (a host read, outside the hot
+        path)."""
+        if self.state is None:
+            return np.zeros(self.n_streams, np.int32)
+        return self.state.view(self.n_streams, -1)[:, 2].cpu().numpy()
+
+    def _update(self, det_hold, count_hold, tid, slot, stream_of, flush):
+        B, hold_rows, max_det, S = det_hold.shape[0], det_hold.shape[1], tid.shape[1], self.n_streams
+        if B == 0 and self.state is not None:
+            hold_rows, max_det = self._rows - self.back_cap, 1      # a call without frames (a flush) takes the entries as they are
+        rows = hold_rows + self.back_cap
+        state = self._state_for(rows)
+        out = self.buffers(B, rows)
+        so = (ctypes.c_int * max(B, 1))(*stream_of)
+        fl = (ctypes.c_ubyte * S)(*flush)
+        with torch.cuda.device(self.device):
+            abi.check(abi.load().lp_lookback_update(_dptr(state), S, self.max_tracks, self.depth, self.max_back, self.back_cap,
+                                                    _dptr(det_hold), _dptr(count_hold), _dptr(tid), _dptr(slot), B, max_det, hold_rows,
+                                                    so, ctypes.cast(fl, ctypes.c_void_p), _dptr(out[0]), _dptr(out[1]), _dptr(out[2]),
+                                                    _dptr(out[3]), _dptr(out[4]), _dptr(out[5]), _stream_ptr(self.device)),
+                      'lp_lookback_update')
+        return out
+
+    def _blank_like(self, frame):
+        """A scratch frame of the kind of ``frame`` for a slot of the redact call that has no frame (its count is 0)."""
+        key = frame.matrix if isinstance(frame, Nv12Frame) else None
+        blank = self._blank.get(key)
+        if blank is None:
+            if key is None:
+                blank = torch.zeros(1, 1, 3, dtype=torch.uint8, device=self.device)
+            else:
+                blank = Nv12Frame.from_packed(torch.zeros(6, dtype=torch.uint8, device=self.device), 2, 2, key)
+            self._blank[key] = blank
+        return blank
+
+    def _status_for(self, n, rows):
+        st = self._status.get((n, rows))
+        if st is None:
+            st = self._status[(n, rows)] = torch.empty(n, rows, dtype=torch.int32, device=self.device)
+        return st
+
+    def _redact(self, frames, rel, tails, out):
+        kw = dict(mode=self.mode, cell=self.cell, margin=self.margin, fill=self.fill)
+        rel_det, rel_count, _, tail_det, tail_count, _ = out
+        B, rows = rel_det.shape[:2]
+        if rel:
+            # one call over all B slots: slot b takes the frame that leaves at b; a slot that releases nothing has rel_count 0
+            # and takes frame b itself (no byte changes), or a scratch frame where there is none
+            # (a frame that enters and leaves within this push is in the list twice, at its own b with count 0 and at the b
+            # that releases it: redact_plates reads and writes a frame only along its rows, so the count-0 entry touches nothing)
+            leaving = {b: fr for b, _, _, fr in rel}
+            lst = [leaving.get(b, frames[b]) for b in range(B)]
+            lst = [self._blank_like(rel[0][3]) if fr is None else fr for fr in lst]
+            redact_plates(lst, rel_det, rel_count, status=self._status_for(B, rows), **kw)
+        done = [(s, g, fr) for _, s, g, fr in rel]
+        for s, items in tails:
+            if items:
+                redact_plates([fr for _, fr in items], tail_det[s], tail_count[s], status=self._status_for(len(items), rows), **kw)
+                done += [(s, g, fr) for g, fr in items]
+        return done
 
 
 def eval_counts(det, det_count, tgt, tgt_count, counts=None):

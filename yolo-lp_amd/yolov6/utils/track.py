@@ -175,6 +175,8 @@ class PlateTrackerNp:
         #: int32 [B, max_det] of the last ``update``: the slot of each matched or new row's track, -1 wherever its tid is -1
         #: (the ``slot`` output of lp_track_update_slots)
         self.last_slot = np.zeros((0, 1), np.int32)
+        #: int32 [B, max_det] of the last ``update``: the tid it returned (what ``LookbackNp.push`` reads), else None
+        self.last_tid = None
         self._hold = None
         #: (det_hold, count_hold, tid_hold) of the last ``update`` after ``enable_hold`` (rule 11), else None
         self.last_hold = None
@@ -359,7 +361,7 @@ class PlateTrackerNp:
         S = self.n_streams
         stream_of, flush, max_ended = check_call(S, B, stream_of, flush, self.max_tracks if max_ended is None else max_ended)
         det_out = np.zeros_like(det)
-        tid = np.full((B, max_det), -1, np.int32)
+        tid = self.last_tid = np.full((B, max_det), -1, np.int32)
         slot = self.last_slot = np.full((B, max_det), -1, np.int32)
         ended = [[] for _ in range(S)]
         held = [[] for _ in range(B)]
