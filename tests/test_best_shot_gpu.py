@@ -14,6 +14,7 @@ import torch
 from conftest import REPO
 import test_track_cpu as C
 import test_best_shot_cpu as S
+import test_streams_cpu as U
 from test_track_gpu import CASES, CFG, _assert_call_equal, video_dir   # noqa: F401  (video_dir: the fixture)
 
 pytestmark = pytest.mark.gpu
@@ -108,12 +109,9 @@ def _dev(a):
     return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).cuda()
 
 
-@pytest.mark.parametrize('case', S.SHOT_CASES, ids=S.SHOT_IDS)
-def test_best_shot_update_equals_numpy_spec(case):
+def _run_shot_calls(calls, n_streams, T, max_det, crop_hw, max_crops, max_ended, min_score):
+    """The calls of ``shot_case`` through lp_best_shot_update, every output bit for bit; returns the device state."""
     from yolov6.hip import abi, runtime
-    seed, n_streams, T, max_det, Bs, crop_hw, max_crops, max_ended, kw = case
-    gal, calls = S.shot_case(seed, n_streams, T, max_det, Bs, crop_hw, max_crops, max_ended, **kw)
-    S.check_shot_case(case, gal, calls)                     # what the case is there for happened
     lib, dev = abi.load(), torch.device('cuda', torch.cuda.current_device())
     state = torch.zeros(lib.lp_best_shot_state_bytes(n_streams, T, *crop_hw), dtype=torch.uint8, device=dev)
     out = (torch.empty((n_streams, max_ended) + crop_hw + (3,), dtype=torch.uint8, device=dev),
@@ -129,13 +127,40 @@ def test_best_shot_update_equals_numpy_spec(case):
             abi.check(lib.lp_best_shot_update(state.data_ptr(), n_streams, T, crop_hw[0], crop_hw[1], t['det'].data_ptr(), t['count'].data_ptr(),
                                               B, max_det, t['tid'].data_ptr(), t['slot'].data_ptr(), t['crops'].data_ptr(),
                                               t['status'].data_ptr(), t['sharp'].data_ptr(), max_crops, so, t['ended_i'].data_ptr(),
-                                              t['ended_count'].data_ptr(), max_ended, gal.min_score, *(o.data_ptr() for o in out),
+                                              t['ended_count'].data_ptr(), max_ended, min_score, *(o.data_ptr() for o in out),
                                               runtime._stream_ptr(dev)), 'lp_best_shot_update')
         _assert_shots_equal(out, want, 'call %d' % k)       # (want's crops of records without a shot hold the poison 0xAB)
+    return state
+
+
+@pytest.mark.parametrize('case', S.SHOT_CASES, ids=S.SHOT_IDS)
+def test_best_shot_update_equals_numpy_spec(case):
+    seed, n_streams, T, max_det, Bs, crop_hw, max_crops, max_ended, kw = case
+    gal, calls = S.shot_case(seed, n_streams, T, max_det, Bs, crop_hw, max_crops, max_ended, **kw)
+    S.check_shot_case(case, gal, calls)                     # what the case is there for happened
+    state = _run_shot_calls(calls, n_streams, T, max_det, crop_hw, max_crops, max_ended, gal.min_score)
     # the last call flushes every stream and nothing was cut off in it, or what is left are entries whose records were cut off:
     # either way the numpy gallery and the device state agree on which entries are occupied
     words = state.view(n_streams, -1)[:, 16:].view(n_streams, T, -1)[:, :, :4].contiguous().view(torch.int32)[:, :, 0].cpu().numpy()
     assert np.array_equal(words, gal.idp1)
+
+
+def test_a_launch_of_untracked_frames_only_launches_nothing_for_it():
+    """The first launch of call 1 holds untracked frames only and call 2 nothing else: no workgroup; the track that call 2's flush
+    ends is retired by the closing kernel.  The state is compared field by field (the crop and the det row of an entry with a
+    shot; a retired entry keeps what it held)."""
+    crop_hw, max_ended = (5, 7), 4
+    n_streams, T, max_det = U.UL['n_streams'], U.UL['max_tracks'], U.UL['max_det']
+    gal, calls = U.untracked_launch_shots(crop_hw, max_ended)
+    state = _run_shot_calls(calls, n_streams, T, max_det, crop_hw, max_det, max_ended, gal.min_score).cpu().view(n_streams, -1)
+    assert np.array_equal(state[:, :4].contiguous().view(torch.int32)[:, 0].numpy(), gal.frame) and gal.frame.tolist() == [1, 1]
+    entries = state[:, 16:].view(n_streams, T, -1)
+    head = entries[:, :, :144].contiguous().view(torch.int32).numpy()
+    assert np.array_equal(head[:, :, 0], gal.idp1) and np.array_equal(head[:, :, 1], gal.has) and gal.has.sum() == 1
+    for s, g in np.argwhere(gal.has):
+        assert np.array_equal(head[s, g, 2:4].view(np.uint64)[0], gal.key[s, g]) and np.array_equal(head[s, g, 4:7], gal.meta[s, g])
+        assert np.array_equal(head[s, g, 8:36], gal.det[s, g].view(np.int32))
+        assert np.array_equal(entries[s, g, 144:144 + gal.crop[s, g].size].numpy(), gal.crop[s, g].reshape(-1))
 
 
 # ---- PlateTracker.update_with_shots ---------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ import torch
 from conftest import REPO
 import test_track_cpu as C
 import test_hold_cpu as H
+import test_streams_cpu as U
 from test_track_gpu import CASES, CFG, _assert_call_equal
 
 pytestmark = pytest.mark.gpu
@@ -55,9 +56,9 @@ def _assert_hold_equal(got, want, guards, what):
         assert bool((guard == 12345).all()), (what, name, 'guard words overwritten')
 
 
-def _run_both(calls, n_streams, max_ended, min_hits=1, max_misses=None, **kw):
+def _run_both(calls, n_streams, max_ended, min_hits=1, max_misses=None, whole_state=False, **kw):
     """The calls through runtime.PlateTracker and PlateTrackerNp, both with the hold: all eight outputs and the slots bit for
-    bit, the state's ``dropped``.  Returns (the numpy tracker, held rows seen)."""
+    bit, the state's ``dropped`` (``whole_state``: every word of it).  Returns (the numpy tracker, held rows seen)."""
     from yolov6.hip import runtime
     ref = H.tracker(True, n_streams, min_hits, max_misses, **kw)
     trk = runtime.PlateTracker(n_streams, device='cuda', **kw)
@@ -75,7 +76,17 @@ def _run_both(calls, n_streams, max_ended, min_hits=1, max_misses=None, **kw):
         _assert_hold_equal(trk.last_hold, ref.last_hold, guards, 'call %d' % k)
         held += int((ref.last_hold[1] - np.clip(count, 0, max_det)).sum())
     assert np.array_equal(trk.dropped.cpu().numpy(), ref.dropped)
+    if whole_state:
+        assert np.array_equal(trk.state.view(n_streams, -1).cpu().numpy(), U.track_state_words(ref))
     return ref, held
+
+
+def test_a_launch_of_untracked_frames_only_and_a_flushed_stream_without_a_frame():
+    """The first launch of call 1 holds untracked frames only (one workgroup of no stream copies them all); call 2 flushes a
+    stream that has no frame in it (a workgroup of its own behind the frames' launch)."""
+    ref, held = _run_both(U.untracked_launch_calls(), U.UL['n_streams'], 4, whole_state=True, max_tracks=U.UL['max_tracks'],
+                          max_age=U.UL['max_age'])
+    assert ref.stats['ended'] == 1 and ref.live(1).sum() == 1 and not ref.live(0).any() and ref.frame.tolist() == [1, 1]
 
 
 @pytest.mark.parametrize('case', CASES, ids=lambda c: 's%d-t%d-d%d' % c[1:4])

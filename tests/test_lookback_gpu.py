@@ -16,6 +16,7 @@ import torch
 from conftest import REPO
 import test_track_cpu as C
 import test_lookback_cpu as L
+import test_streams_cpu as U
 from test_track_gpu import CFG
 
 pytestmark = pytest.mark.gpu
@@ -121,6 +122,14 @@ def test_calls_that_split_into_several_launches():
     assert sum(so.count(-1) for _, _, so, _ in calls) >= 10 and all(len(set(so[:64])) >= 30 for _, _, so, _ in calls if len(so) > 64)
     lb = _run_kernel_against_spec(calls, 2, None, None, n_streams=66, max_tracks=2, match_thres=0.3, new_thres=0.2, expand=0.5, max_age=2)
     assert lb.stats['confirmed'] > 0 and lb.stats['back_rows'] > 0 and lb.f.max() >= 5
+
+
+def test_a_launch_of_untracked_frames_only_and_a_flushed_stream_without_a_frame():
+    """The first launch of call 1 holds untracked frames only: one workgroup of no stream releases them all at once; call 2 has no
+    tracked frame and hands out the tail of a flushed stream."""
+    lb = _run_kernel_against_spec(U.untracked_launch_calls(), 2, None, None, n_streams=U.UL['n_streams'], max_tracks=U.UL['max_tracks'],
+                                  max_age=U.UL['max_age'])
+    assert lb.f.tolist() == [1, 1] and lb.base.tolist() == [1, 0]
 
 
 def test_full_entry_overflows_into_dropped():

@@ -18,7 +18,8 @@
 // geometry[12]; the D counts of the ring, padded to a multiple of 4; the D entries of rows * 28 floats.  Every part starts at a
 // multiple of 16 bytes.  All zero = empty.
 #include "lp_internal.h"
-#include <vector>
+#include "lp_streams.h"
+#include <cstring>
 
 namespace lp {
 
@@ -222,13 +223,7 @@ __global__ __launch_bounds__(LB_T) void lookback_tail_kernel(const LbTail tab, c
 }
 
 bool lookback_dims_ok(int n_streams, int max_tracks, int depth, long long rows) {
-    return n_streams >= 1 && max_tracks >= 1 && max_tracks <= LP_TRACK_MAX_TRACKS && depth >= 1 && depth <= LB_DEPTH && rows >= 1 &&
-           rows * LP_DET_COLS < 0x80000000ll;
-}
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return na > 0 && nb > 0 && x < y + nb && y < x + na;
+    return stream_dims_fault(n_streams, max_tracks).empty() && depth >= 1 && depth <= LB_DEPTH && rows >= 1 && rows * LP_DET_COLS < 0x80000000ll;
 }
 
 }  // namespace
@@ -249,8 +244,8 @@ extern "C" int lp_lookback_update(void* state, int n_streams, int max_tracks, in
     const std::string fn = "lp_lookback_update: ";
     if (depth < 1 || depth > LB_DEPTH || max_back < 0 || back_cap < 0)
         return fail(LP_ERR_ARG, fn + "need depth in 1.." + std::to_string(LB_DEPTH) + ", max_back >= 0 and back_cap >= 0");
-    if (n_streams < 1 || max_tracks < 1 || max_tracks > LP_TRACK_MAX_TRACKS)
-        return fail(LP_ERR_ARG, fn + "need n_streams >= 1 and max_tracks in 1.." + std::to_string(LP_TRACK_MAX_TRACKS));
+    std::string why = stream_dims_fault(n_streams, max_tracks);
+    if (!why.empty()) return fail(LP_ERR_ARG, fn + why);
     const long long rows = (long long)hold_rows + back_cap;
     if (B < 0 || max_det < 1 || hold_rows < max_det || rows * LP_DET_COLS >= 0x80000000ll)
         return fail(LP_ERR_ARG, fn + "need B >= 0, max_det >= 1, hold_rows >= max_det and (hold_rows + back_cap) * 28 < 2^31");
@@ -259,23 +254,17 @@ extern "C" int lp_lookback_update(void* state, int n_streams, int max_tracks, in
         return fail(LP_ERR_ARG, fn + "null pointer");
     if ((((uintptr_t)state | (uintptr_t)det_hold | (uintptr_t)rel_det | (uintptr_t)tail_det) & 15) != 0)
         return fail(LP_ERR_ARG, fn + "state, det_hold, rel_det and tail_det must be 16-byte aligned");
-    for (int b = 0; b < B; ++b)
-        if (stream_of[b] < -1 || stream_of[b] >= n_streams)
-            return fail(LP_ERR_ARG, fn + "stream " + std::to_string(stream_of[b]) + " of frame " + std::to_string(b) + " (need -1 or 0.." +
-                                        std::to_string(n_streams - 1) + ")");
+    why = stream_of_fault(stream_of, B, n_streams);
+    if (!why.empty()) return fail(LP_ERR_ARG, fn + why);
     {   // no output may overlap the state, an input or another output
         const size_t row_bytes = LP_DET_COLS * sizeof(float), nb = (size_t)B, nt = (size_t)n_streams * depth;
-        struct Region { const void* p; size_t bytes; bool out; };
         const Region reg[] = {{state, (size_t)n_streams * (size_t)stream_words(max_tracks, depth, rows) * 4, false},
                               {det_hold, nb * hold_rows * row_bytes, false}, {count_hold, nb * 4, false},
                               {tid, nb * max_det * 4, false}, {slot, nb * max_det * 4, false},
                               {rel_det, nb * (size_t)rows * row_bytes, true}, {rel_count, nb * 4, true}, {rel_frame, nb * 4, true},
                               {tail_det, nt * (size_t)rows * row_bytes, true}, {tail_count, nt * 4, true}, {tail_frame, nt * 4, true}};
-        const int nreg = (int)(sizeof(reg) / sizeof(reg[0]));
-        for (int i = 0; i < nreg; ++i)
-            for (int j = i + 1; j < nreg; ++j)
-                if ((reg[i].out || reg[j].out) && overlap(reg[i].p, reg[i].bytes, reg[j].p, reg[j].bytes))
-                    return fail(LP_ERR_ARG, fn + "the outputs (rel_*, tail_*) may overlap neither the state, an input nor each other");
+        if (regions_clash(reg, (int)(sizeof(reg) / sizeof(reg[0]))))
+            return fail(LP_ERR_ARG, fn + "the outputs (rel_*, tail_*) may overlap neither the state, an input nor each other");
     }
 
     hipStream_t st = (hipStream_t)stream;
@@ -286,25 +275,12 @@ extern "C" int lp_lookback_update(void* state, int n_streams, int max_tracks, in
     std::vector<int> blk_of((size_t)n_streams, -1);
     for (int b0 = 0; b0 < B; b0 += LB_FRAMES) {
         LbTable tab = {};
-        const int nf = B - b0 < LB_FRAMES ? B - b0 : LB_FRAMES;
-        int nblk = 0;
-        for (int j = 0; j < nf; ++j) {
-            const int s = stream_of[b0 + j];
-            if (s < 0) continue;
-            if (blk_of[(size_t)s] < 0) {
-                blk_of[(size_t)s] = nblk;
-                tab.blk_stream[nblk++] = s;
-            }
-            tab.fr_blk[j] = (short)blk_of[(size_t)s];
-        }
-        if (nblk == 0) { tab.blk_stream[0] = -1; nblk = 1; }
-        for (int j = 0; j < nf; ++j) {
-            const int s = stream_of[b0 + j];
-            if (s < 0) { tab.fr_skip[j] = 1; tab.fr_blk[j] = (short)(j % nblk); }
-            else blk_of[(size_t)s] = -1;
-        }
-        tab.nfr = nf;
-        hipLaunchKernelGGL(lookback_kernel, dim3((unsigned)nblk), dim3(LB_T), 0, st, tab, dm, (int*)state,
+        tab.nfr = B - b0 < LB_FRAMES ? B - b0 : LB_FRAMES;
+        const StreamPlan pl = plan_streams(stream_of + b0, tab.nfr, blk_of, UNTRACKED_DEAL);
+        memcpy(tab.blk_stream, pl.blk_stream, sizeof(tab.blk_stream));
+        memcpy(tab.fr_blk, pl.fr_blk, sizeof(tab.fr_blk));
+        memcpy(tab.fr_skip, pl.fr_skip, sizeof(tab.fr_skip));
+        hipLaunchKernelGGL(lookback_kernel, dim3((unsigned)pl.nblk), dim3(LB_T), 0, st, tab, dm, (int*)state,
                            (const float4*)(det_hold + (size_t)b0 * hold_rows * LP_DET_COLS), count_hold + b0, tid + (size_t)b0 * max_det,
                            slot + (size_t)b0 * max_det, (float4*)rel_det + (size_t)b0 * evec, rel_count + b0, rel_frame + b0);
         LP_HIP_CHECK(hipGetLastError());

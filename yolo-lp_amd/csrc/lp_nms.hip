@@ -13,6 +13,7 @@
 //   order: descending score, ties by ascending anchor index (stable sort); at most 30000 candidates
 //   greedy: keep i, suppress later j with inter/(area_i+area_j-inter) > iou (double compare), until max_det
 #include "lp_internal.h"
+#include "lp_streams.h"
 #include "lp_score.inc"
 #include "lp_nms_shared.inc"
 
@@ -452,8 +453,7 @@ extern "C" const int32_t* lp_nms_candidate_counts(const void* workspace, int B, 
 extern "C" int lp_check_iou_predicate(const float* dev_pairs, long long n, double iou_thres, unsigned char* dev_out, void* stream) {
     if (!dev_pairs || !dev_out || n < 1) return fail(LP_ERR_ARG, "lp_check_iou_predicate: bad argument");
     if (!(iou_thres >= 0.0 && iou_thres <= 1.0)) return fail(LP_ERR_ARG, "lp_check_iou_predicate: threshold must be in [0, 1]");
-    float thr_f = (float)iou_thres;
-    if ((double)thr_f > iou_thres) thr_f = nextafterf(thr_f, -INFINITY);
+    const float thr_f = f32_not_above(iou_thres);
     long long blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(iou_predicate_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dev_pairs, n, thr_f, dev_out);
@@ -487,8 +487,7 @@ extern "C" int lp_nms(float* pred, int B, int N, double conf_thres, double iou_t
     if (workspace_bytes < w.bytes) return fail(LP_ERR_ARG, "lp_nms: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const float conf_f = (float)conf_thres;
-    float thr_f = (float)iou_thres;                       // largest fp32 not above the double threshold
-    if ((double)thr_f > iou_thres) thr_f = nextafterf(thr_f, -INFINITY);
+    const float thr_f = f32_not_above(iou_thres);
 
     if (int rc = zero_counts_launch(w.cnt, B, st)) return rc;
     if (int rc = nms_score_launch(pred, B, N, 0, N, conf_f, w, true, st)) return rc;
@@ -505,7 +504,6 @@ extern "C" int lp_nms_candidates(int B, int N, double iou_thres, int max_det, fl
     NmsWs w = nms_carve(workspace, B, N);
     if (workspace_bytes < w.bytes) return fail(LP_ERR_ARG, "lp_nms_candidates: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    float thr_f = (float)iou_thres;                       // largest fp32 not above the double threshold
-    if ((double)thr_f > iou_thres) thr_f = nextafterf(thr_f, -INFINITY);
+    const float thr_f = f32_not_above(iou_thres);
     return sort_greedy_launch(w, B, N, thr_f, max_det, det, count, keep, st);
 }

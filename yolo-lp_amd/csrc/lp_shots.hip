@@ -18,8 +18,8 @@
 // State of a stream: 16 bytes (the frame counter, 12 unused), then per slot an entry of 144 bytes + the crop rounded up to 16:
 // id + 1, has-shot, key (64 bits), frame, row, status, one unused word, det[28], crop.  All zero = empty.
 #include "lp_internal.h"
-#include <cmath>
-#include <vector>
+#include "lp_streams.h"
+#include <cstring>
 
 namespace lp {
 
@@ -254,10 +254,8 @@ __global__ __launch_bounds__(BS_T) void best_shot_final_kernel(unsigned char* __
     run_jobs(s_retire, s_nretire, crop_bytes, tid >> 6, tid & 63);
 }
 
-bool shot_dims_ok(int n_streams, int max_tracks, int crop_h, int crop_w) {
-    return n_streams >= 1 && max_tracks >= 1 && max_tracks <= BS_SLOTS && crop_h >= 1 && crop_w >= 1 && crop_h <= BS_MAX_SIDE &&
-           crop_w <= BS_MAX_SIDE;
-}
+static_assert(BS_SLOTS == LP_TRACK_MAX_TRACKS, "stream_dims_fault states the rule of max_tracks");
+bool crop_dims_ok(int crop_h, int crop_w) { return crop_h >= 1 && crop_w >= 1 && crop_h <= BS_MAX_SIDE && crop_w <= BS_MAX_SIDE; }
 size_t entry_bytes(int crop_h, int crop_w) { return (size_t)BS_ENTRY_WORDS * 4 + (((size_t)crop_h * crop_w * 3 + 15) & ~(size_t)15); }
 size_t shot_stream_bytes(int max_tracks, int crop_h, int crop_w) { return BS_HDR_BYTES + (size_t)max_tracks * entry_bytes(crop_h, crop_w); }
 
@@ -285,7 +283,7 @@ extern "C" int lp_crop_sharpness(const unsigned char* crops, const int32_t* stat
 }
 
 extern "C" size_t lp_best_shot_state_bytes(int n_streams, int max_tracks, int crop_h, int crop_w) {
-    if (!shot_dims_ok(n_streams, max_tracks, crop_h, crop_w)) return 0;
+    if (!stream_dims_fault(n_streams, max_tracks).empty() || !crop_dims_ok(crop_h, crop_w)) return 0;
     return (size_t)n_streams * shot_stream_bytes(max_tracks, crop_h, crop_w);
 }
 
@@ -295,8 +293,9 @@ extern "C" int lp_best_shot_update(void* state, int n_streams, int max_tracks, i
                                    const int32_t* ended_i, const int32_t* ended_count, int max_ended, double min_score,
                                    unsigned char* shot_crops, int32_t* shot_i, unsigned long long* shot_q, float* shot_det, void* stream) {
     const std::string fn = "lp_best_shot_update: ";
-    if (!shot_dims_ok(n_streams, max_tracks, crop_h, crop_w))
-        return fail(LP_ERR_ARG, fn + "need n_streams >= 1, max_tracks in 1.." + std::to_string(BS_SLOTS) + " and a crop size of 1..1024 on each side");
+    std::string why = stream_dims_fault(n_streams, max_tracks);
+    if (!why.empty()) return fail(LP_ERR_ARG, fn + why);
+    if (!crop_dims_ok(crop_h, crop_w)) return fail(LP_ERR_ARG, fn + "need a crop size of 1..1024 on each side");
     if (B < 0 || max_det < 1 || max_det > 0x7fffffff / LP_DET_COLS || max_ended < 0 || max_crops < 0)
         return fail(LP_ERR_ARG, fn + "need B >= 0, max_det >= 1, max_ended >= 0 and max_crops >= 0");
     if (!(std::fabs(min_score) <= 3.0e38)) return fail(LP_ERR_ARG, fn + "min_score must be finite (|min_score| <= 3e38)");
@@ -305,12 +304,9 @@ extern "C" int lp_best_shot_update(void* state, int n_streams, int max_tracks, i
         return fail(LP_ERR_ARG, fn + "null pointer");
     if (((uintptr_t)state & 15) != 0) return fail(LP_ERR_ARG, fn + "state must be 16-byte aligned");
     if (((uintptr_t)sharp & 7) != 0 || ((uintptr_t)shot_q & 7) != 0) return fail(LP_ERR_ARG, fn + "sharp and shot_q must be 8-byte aligned");
-    for (int b = 0; b < B; ++b)
-        if (stream_of[b] < -1 || stream_of[b] >= n_streams)
-            return fail(LP_ERR_ARG, fn + "stream " + std::to_string(stream_of[b]) + " of frame " + std::to_string(b) + " (need -1 or 0.." +
-                                        std::to_string(n_streams - 1) + ")");
-    float min_f = (float)min_score;                             // smallest fp32 not below the double threshold
-    if ((double)min_f < min_score) min_f = nextafterf(min_f, INFINITY);
+    why = stream_of_fault(stream_of, B, n_streams);
+    if (!why.empty()) return fail(LP_ERR_ARG, fn + why);
+    const float min_f = f32_not_below(min_score);
 
     hipStream_t st = (hipStream_t)stream;
     const int crop_bytes = crop_h * crop_w * 3;
@@ -325,22 +321,12 @@ extern "C" int lp_best_shot_update(void* state, int n_streams, int max_tracks, i
     std::vector<int> blk_of((size_t)n_streams, -1);
     for (int b0 = 0; b0 < B; b0 += BS_FRAMES) {
         BsTable tab = {};
-        const int nf = B - b0 < BS_FRAMES ? B - b0 : BS_FRAMES;
-        int nblk = 0;
-        for (int j = 0; j < nf; ++j) {
-            const int s = stream_of[b0 + j];
-            tab.fr_blk[j] = -1;
-            if (s < 0) continue;
-            if (blk_of[(size_t)s] < 0) {
-                blk_of[(size_t)s] = nblk;
-                tab.blk_stream[nblk++] = s;
-            }
-            tab.fr_blk[j] = (short)blk_of[(size_t)s];
-        }
-        for (int k = 0; k < nblk; ++k) blk_of[(size_t)tab.blk_stream[k]] = -1;
-        tab.nfr = nf;
-        if (nblk == 0) continue;
-        hipLaunchKernelGGL(best_shot_kernel, dim3((unsigned)nblk), dim3(BS_T), 0, st, tab, (unsigned char*)state, max_tracks, sstride, estride,
+        tab.nfr = B - b0 < BS_FRAMES ? B - b0 : BS_FRAMES;
+        const StreamPlan pl = plan_streams(stream_of + b0, tab.nfr, blk_of, UNTRACKED_LEAVE_OUT);
+        if (pl.nblk == 0) continue;
+        memcpy(tab.blk_stream, pl.blk_stream, sizeof(tab.blk_stream));
+        memcpy(tab.fr_blk, pl.fr_blk, sizeof(tab.fr_blk));
+        hipLaunchKernelGGL(best_shot_kernel, dim3((unsigned)pl.nblk), dim3(BS_T), 0, st, tab, (unsigned char*)state, max_tracks, sstride, estride,
                            det + (size_t)b0 * max_det * LP_DET_COLS, count + b0, max_det, tid + (size_t)b0 * max_det,
                            slot + (size_t)b0 * max_det, crops ? crops + (size_t)b0 * max_crops * crop_bytes : nullptr,
                            status ? status + (size_t)b0 * max_crops : nullptr, sharp ? sharp + (size_t)b0 * max_crops : nullptr, max_crops,

@@ -16,6 +16,7 @@
 //      of OTHER tiles: rows of one tile have been through that tile's own NMS.
 //   4. the first max_det kept rows are gathered from det_t, columns 0..11 shifted by the tile's origin; rows past the count are zero.
 #include "lp_internal.h"
+#include "lp_streams.h"
 #include "lp_score.inc"
 #include "lp_nms_shared.inc"
 #include <vector>
@@ -275,8 +276,7 @@ extern "C" int lp_merge_tiles(const float* det_t, const int32_t* count_t, const 
     }
     static std::atomic<unsigned long long> attr{0};
     if (int rc = set_max_lds_once(merge_tiles_kernel, MT_LDS_BUDGET, attr, "merge tiles")) return rc;
-    float thr_f = (float)thres;                               // largest fp32 not above the double threshold
-    if ((double)thr_f > thres) thr_f = nextafterf(thr_f, -INFINITY);
+    const float thr_f = f32_not_above(thres);
     hipStream_t st = (hipStream_t)stream;
     const size_t spf = spill_bytes_per_frame(max_det);
     for (int f0 = 0; f0 < n_frames;) {                          // whole frames per launch: <= 64 tiles and <= 64 frames

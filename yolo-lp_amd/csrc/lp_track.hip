@@ -25,10 +25,10 @@
 // 544 words: id, first, last, hits, misses, 3 unused; box[4]; corners[8]; vx, vy, 2 unused; total[8]; votes[8][64].  A slot is
 // live iff hits > 0.
 #include "lp_internal.h"
+#include "lp_streams.h"
 #include "lp_score.inc"
 #include "lp_nms_shared.inc"
-#include <cmath>
-#include <vector>
+#include <cstring>
 
 namespace lp {
 
@@ -457,8 +457,8 @@ extern "C" int lp_track_update_hold(void* state, int n_streams, int max_tracks, 
                                     int32_t* tid, int32_t* slot, int32_t* ended_i, float* ended_f, int32_t* ended_count, int max_ended,
                                     const lp_track_hold_params* hp, float* det_hold, int32_t* count_hold, int32_t* tid_hold, void* stream) {
     const std::string fn = "lp_track_update: ";
-    if (n_streams < 1 || max_tracks < 1 || max_tracks > LP_TRACK_MAX_TRACKS)
-        return fail(LP_ERR_ARG, fn + "need n_streams >= 1 and max_tracks in 1.." + std::to_string(LP_TRACK_MAX_TRACKS));
+    std::string why = stream_dims_fault(n_streams, max_tracks);
+    if (!why.empty()) return fail(LP_ERR_ARG, fn + why);
     if (B < 0 || max_det < 1 || max_det > 0x7fffffff / LP_DET_COLS || max_ended < 0)
         return fail(LP_ERR_ARG, fn + "need B >= 0, max_det >= 1 and max_ended >= 0");
     if (hp && (hp->min_hits < 1 || hp->max_misses < 0)) return fail(LP_ERR_ARG, fn + "hold needs min_hits >= 1 and max_misses >= 0");
@@ -474,34 +474,24 @@ extern "C" int lp_track_update_hold(void* state, int n_streams, int max_tracks, 
     if (!state || !ended_count || (max_ended > 0 && (!ended_i || !ended_f)) || (B > 0 && (!det || !count || !stream_of || !det_out || !tid)))
         return fail(LP_ERR_ARG, fn + "null pointer");
     if (((uintptr_t)state & 15) != 0) return fail(LP_ERR_ARG, fn + "state must be 16-byte aligned");
-    if (B > 0) {
-        const uintptr_t a = (uintptr_t)det, b = (uintptr_t)det_out;
-        const size_t bytes = (size_t)B * max_det * LP_DET_COLS * sizeof(float);
-        if (a < b + bytes && b < a + bytes) return fail(LP_ERR_ARG, fn + "det_out may not alias det");
-    }
+    const size_t hrows = (size_t)max_det + max_tracks;
+    const size_t bytes = (size_t)B * max_det * LP_DET_COLS * sizeof(float), hbytes = (size_t)B * hrows * LP_DET_COLS * sizeof(float);
+    const Region io[] = {{det, bytes, false}, {det_out, bytes, true}};
+    if (regions_clash(io, 2)) return fail(LP_ERR_ARG, fn + "det_out may not alias det");
     if (hp) {
         if (B > 0 && (!det_hold || !count_hold || !tid_hold)) return fail(LP_ERR_ARG, fn + "null pointer (hold)");
-        if (B > 0) {
-            const uintptr_t h = (uintptr_t)det_hold, a = (uintptr_t)det, b = (uintptr_t)det_out;
-            const size_t bytes = (size_t)B * max_det * LP_DET_COLS * sizeof(float);
-            const size_t hbytes = (size_t)B * ((size_t)max_det + max_tracks) * LP_DET_COLS * sizeof(float);
-            if ((h < a + bytes && a < h + hbytes) || (h < b + bytes && b < h + hbytes))
-                return fail(LP_ERR_ARG, fn + "det_hold may not alias det or det_out");
-        }
+        const Region held[] = {{det, bytes, false}, {det_out, bytes, false}, {det_hold, hbytes, true}};   // (det / det_out: checked above)
+        if (regions_clash(held, 3)) return fail(LP_ERR_ARG, fn + "det_hold may not alias det or det_out");
     }
-    for (int b = 0; b < B; ++b)
-        if (stream_of[b] < -1 || stream_of[b] >= n_streams)
-            return fail(LP_ERR_ARG, fn + "stream " + std::to_string(stream_of[b]) + " of frame " + std::to_string(b) + " (need -1 or 0.." +
-                                        std::to_string(n_streams - 1) + ")");
+    why = stream_of_fault(stream_of, B, n_streams);
+    if (!why.empty()) return fail(LP_ERR_ARG, fn + why);
     static std::atomic<unsigned long long> attr{0}, attr_hold{0};
     if (int rc = hp ? set_max_lds_once(track_kernel<true>, SORT_LDS_KEYS * 8, attr_hold, "track hold")
                     : set_max_lds_once(track_kernel<false>, SORT_LDS_KEYS * 8, attr, "track")) return rc;
 
     TkParams prm;
-    prm.thr_f = (float)p->match_thres;                          // largest fp32 not above the double threshold
-    if ((double)prm.thr_f > p->match_thres) prm.thr_f = nextafterf(prm.thr_f, -INFINITY);
-    prm.new_f = (float)p->new_thres;                            // smallest fp32 not below the double threshold
-    if ((double)prm.new_f < p->new_thres) prm.new_f = nextafterf(prm.new_f, INFINITY);
+    prm.thr_f = f32_not_above(p->match_thres);
+    prm.new_f = f32_not_below(p->new_thres);
     prm.expand_f = (float)p->expand;
     prm.max_age = p->max_age;
     for (int h = 0; h < TK_HEADS; ++h) prm.ncls[h] = p->ncls[h];
@@ -518,7 +508,6 @@ extern "C" int lp_track_update_hold(void* state, int n_streams, int max_tracks, 
     while (n_max < max_tracks * rows_cap) n_max <<= 1;
     const size_t lds = (size_t)n_max * 8;
     const long long sstride = (long long)stream_words(max_tracks);
-    const size_t hrows = (size_t)max_det + max_tracks;
     auto launch = [&](const TkTable& tab, int nblk, int b0) -> int {
         TkHold hold = {};
         if (hp && B > 0) hold = TkHold{hp->min_hits, hp->max_misses, det_hold + (size_t)b0 * hrows * LP_DET_COLS, count_hold + b0,
@@ -536,27 +525,16 @@ extern "C" int lp_track_update_hold(void* state, int n_streams, int max_tracks, 
         if (stream_of[b] >= 0) last_chunk[(size_t)stream_of[b]] = b / TK_FRAMES;
     for (int b0 = 0, c = 0; b0 < B; b0 += TK_FRAMES, ++c) {
         TkTable tab = {};
-        const int nf = B - b0 < TK_FRAMES ? B - b0 : TK_FRAMES;
-        int nblk = 0;
-        for (int j = 0; j < nf; ++j) {
-            const int s = stream_of[b0 + j];
-            if (s < 0) continue;
-            if (blk_of[(size_t)s] < 0) {
-                blk_of[(size_t)s] = nblk;
-                tab.blk_stream[nblk] = s;
-                tab.blk_flush[nblk] = (flush && flush[s] && last_chunk[(size_t)s] == c) ? 1 : 0;
-                ++nblk;
-            }
-            tab.fr_blk[j] = (short)blk_of[(size_t)s];
+        tab.nfr = B - b0 < TK_FRAMES ? B - b0 : TK_FRAMES;
+        const StreamPlan pl = plan_streams(stream_of + b0, tab.nfr, blk_of, UNTRACKED_DEAL);
+        memcpy(tab.blk_stream, pl.blk_stream, sizeof(tab.blk_stream));
+        memcpy(tab.fr_blk, pl.fr_blk, sizeof(tab.fr_blk));
+        memcpy(tab.fr_skip, pl.fr_skip, sizeof(tab.fr_skip));
+        for (int k = 0; k < pl.nblk; ++k) {
+            const int s = pl.blk_stream[k];
+            tab.blk_flush[k] = (s >= 0 && flush && flush[s] && last_chunk[(size_t)s] == c) ? 1 : 0;
         }
-        if (nblk == 0) { tab.blk_stream[0] = -1; nblk = 1; }
-        for (int j = 0; j < nf; ++j) {
-            const int s = stream_of[b0 + j];
-            if (s < 0) { tab.fr_skip[j] = 1; tab.fr_blk[j] = (short)(j % nblk); }
-            else blk_of[(size_t)s] = -1;
-        }
-        tab.nfr = nf;
-        if (int rc = launch(tab, nblk, b0)) return rc;
+        if (int rc = launch(tab, pl.nblk, b0)) return rc;
     }
     if (flush) {
         TkTable tab = {};

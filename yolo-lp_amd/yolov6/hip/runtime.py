@@ -736,18 +736,23 @@ def detect(model, x, conf_thres, iou_thres, max_det, route=None):
 
 
 # ---------------------------------------------------------------------------------------------------
-_nms_ws = {}
+_nms_ws, _redact_ws = {}, {}
+
+
+def _stream_workspace(cache, device, need):
+    """``cache``'s workspace of ``device``'s current stream, grown to ``need`` bytes (+ 256 for ``_aligned``), never zeroed."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = cache.get(key)
+    if ws is None or ws.numel() < need + 256:
+        ws = cache[key] = torch.empty(need + 256, dtype=torch.uint8, device=device)
+    return ws
 
 
 def _nms_workspace(device, need):
     """The NMS workspace of ``device``'s current stream, grown to ``need`` bytes (+ 256 for ``_aligned``)."""
     # one workspace per (device, stream): lp_nms memsets and fills it on the current stream, so two streams must never
     # share one; a regrown buffer is released through the caching allocator, which orders its reuse on this stream
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _nms_ws.get(key)
-    if ws is None or ws.numel() < need + 256:
-        ws = _nms_ws[key] = torch.empty(need + 256, dtype=torch.uint8, device=device)
-    return ws
+    return _stream_workspace(_nms_ws, device, need)
 
 
 def nms_padded(prediction, conf_thres, iou_thres, max_det, want_keep=False):
@@ -1088,17 +1093,10 @@ def detect_frames_with_crops(model, frames, img_size, conf_thres, iou_thres, max
     return _unpad_with_crops(frames, det, count, crop_hw)
 
 
-_redact_ws = {}
-
-
 def _redact_workspace(device, need):
     """The cell table of ``redact_plates`` on ``device``'s current stream, grown to ``need`` bytes (+ 256 for ``_aligned``); one per
     (device, stream), as ``_nms_workspace``.  It needs no zeroing: a call reads only entries it has written itself."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _redact_ws.get(key)
-    if ws is None or ws.numel() < need + 256:
-        ws = _redact_ws[key] = torch.empty(need + 256, dtype=torch.uint8, device=device)
-    return ws
+    return _stream_workspace(_redact_ws, device, need)
 
 
 def redact_plates(frames, det, count, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0), status=None):
@@ -1283,6 +1281,31 @@ def detect_tiled_with_crops(model, frames, img_size, conf_thres, iou_thres, max_
 
 # ---------------------------------------------------------------------------------------------------
 # Plate tracking across video frames (lp_track_update; yolov6/utils/track.py states the rules)
+def _host_lists(stream_of, B, flush=None):
+    """The host lists of a per-stream call as the C ABI takes them: (stream_of as int [max(B, 1)], flush as a pointer to one byte
+    per stream, or None)."""
+    so = (ctypes.c_int * max(B, 1))(*stream_of)
+    return so, None if flush is None else ctypes.cast((ctypes.c_ubyte * len(flush))(*flush), ctypes.c_void_p)
+
+
+def _zero_streams(state, n_streams, streams):
+    """Zero the part of ``streams`` (all for None) in a state tensor of ``n_streams`` equal parts."""
+    st = state.view(n_streams, -1)
+    if streams is None:
+        st.zero_()
+    else:
+        for s in streams:
+            st[int(s)].zero_()
+
+
+def _persistent(cache, key, make):
+    """``cache[key]``, from ``make()`` at the first use of the key: the persistent buffers of one call shape."""
+    buf = cache.get(key)
+    if buf is None:
+        buf = cache[key] = make()
+    return buf
+
+
 class PlateTracker:
     """``n_streams`` independent device-resident plate trackers of ``max_tracks`` slots each (lp_track_update, one workgroup per
     stream): detections of consecutive frames are associated by the IoU of expanded, velocity-predicted boxes
@@ -1319,15 +1342,9 @@ class PlateTracker:
     def reset(self, streams=None):
         """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0; their best-shot
         galleries (``enable_best_shot``) are emptied with them."""
-        states = [self.state.view(self.n_streams, self._words)]
+        _zero_streams(self.state, self.n_streams, streams)
         if self._shots is not None:
-            states.append(self._shots['state'].view(self.n_streams, -1))
-        for st in states:
-            if streams is None:
-                st.zero_()
-            else:
-                for s in streams:
-                    st[int(s)].zero_()
+            _zero_streams(self._shots['state'], self.n_streams, streams)
 
     @property
     def dropped(self):
@@ -1352,15 +1369,14 @@ class PlateTracker:
         out = self.buffers(B, max_det, max_ended)
         det_out, tid, ended_i, ended_f, ended_count = out
         self.last_tid = tid
-        so = (ctypes.c_int * max(B, 1))(*stream_of)
-        fl = (ctypes.c_ubyte * S)(*flush)
+        so, fl = _host_lists(stream_of, B, flush)
         hp, hold = None, (None, None, None)
         if self._hold is not None:
             hp, hold = ctypes.byref(self._hold['params']), self.hold_buffers(B, max_det)
             self.last_hold = hold
         with torch.cuda.device(self.device):
             abi.check(abi.load().lp_track_update_hold(_dptr(self.state), S, self.max_tracks, ctypes.byref(self._params), _dptr(det),
-                                                      _dptr(count), B, max_det, so, ctypes.cast(fl, ctypes.c_void_p), _dptr(det_out),
+                                                      _dptr(count), B, max_det, so, fl, _dptr(det_out),
                                                       _dptr(tid), _dptr(self.slot_buffer(B, max_det)), _dptr(ended_i), _dptr(ended_f),
                                                       _dptr(ended_count), max_ended, hp, _dptr(hold[0]), _dptr(hold[1]), _dptr(hold[2]),
                                                       _stream_ptr(self.device)), 'lp_track_update_hold')
@@ -1383,36 +1399,25 @@ class PlateTracker:
         an ``update`` of that shape fills after ``enable_hold`` (``PlateTrackerNp.hold_buffers``)."""
         if self._hold is None:
             raise RuntimeError('call enable_hold() first')
-        key = (int(B), int(max_det))
-        out = self._hold['out'].get(key)
-        if out is None:
-            rows, dev = key[1] + self.max_tracks, self.device
-            out = self._hold['out'][key] = (torch.empty(key[0], rows, abi.LP_DET_COLS, dtype=torch.float32, device=dev),
-                                            torch.empty(key[0], dtype=torch.int32, device=dev),
-                                            torch.empty(key[0], rows, dtype=torch.int32, device=dev))
-        return out
+        B, rows, dev = int(B), int(max_det) + self.max_tracks, self.device
+        return _persistent(self._hold['out'], (B, int(max_det)), lambda: (
+            torch.empty(B, rows, abi.LP_DET_COLS, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+            torch.empty(B, rows, dtype=torch.int32, device=dev)))
 
     def slot_buffer(self, B, max_det):
         """The persistent int32 [B,max_det] tensor an ``update`` of that shape fills beside its returns: the tracker slot of each
         matched or new row's track, -1 wherever tid is -1 (``PlateTrackerNp.last_slot``)."""
         key = (int(B), int(max_det))
-        buf = self._slot.get(key)
-        if buf is None:
-            buf = self._slot[key] = torch.empty(key, dtype=torch.int32, device=self.device)
-        return buf
+        return _persistent(self._slot, key, lambda: torch.empty(key, dtype=torch.int32, device=self.device))
 
     def buffers(self, B, max_det, max_ended=None):
         """The persistent outputs of an ``update`` of B frames of max_det rows: (det_out, tid, ended_i, ended_f, ended_count)."""
         S, dev = self.n_streams, self.device
         key = (int(B), int(max_det), self.max_tracks if max_ended is None else int(max_ended))
-        out = self._out.get(key)
-        if out is None:
-            out = self._out[key] = (torch.empty(key[0], key[1], abi.LP_DET_COLS, dtype=torch.float32, device=dev),
-                                    torch.empty(key[0], key[1], dtype=torch.int32, device=dev),
-                                    torch.empty(S, key[2], 12, dtype=torch.int32, device=dev),
-                                    torch.empty(S, key[2], 12, dtype=torch.float32, device=dev),
-                                    torch.empty(S, dtype=torch.int32, device=dev))
-        return out
+        return _persistent(self._out, key, lambda: (
+            torch.empty(key[0], key[1], abi.LP_DET_COLS, dtype=torch.float32, device=dev),
+            torch.empty(key[0], key[1], dtype=torch.int32, device=dev), torch.empty(S, key[2], 12, dtype=torch.int32, device=dev),
+            torch.empty(S, key[2], 12, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.int32, device=dev)))
 
     def flush_all(self, max_det=1, max_ended=None):
         """End every live track of every stream: ``update`` of zero frames with every flush flag set."""
@@ -1443,16 +1448,11 @@ class PlateTracker:
         sh, S, dev = self._shots, self.n_streams, self.device
         (Hc, Wc), m = sh['crop_hw'], sh['max_crops']
         key = (int(B), self.max_tracks if max_ended is None else int(max_ended))
-        out = sh['out'].get(key)
-        if out is None:
-            out = sh['out'][key] = (torch.zeros(key[0], m, Hc, Wc, 3, dtype=torch.uint8, device=dev),
-                                    torch.zeros(key[0], m, dtype=torch.int32, device=dev),
-                                    torch.zeros(key[0], m, dtype=torch.int64, device=dev),
-                                    torch.zeros(S, key[1], Hc, Wc, 3, dtype=torch.uint8, device=dev),
-                                    torch.empty(S, key[1], 4, dtype=torch.int32, device=dev),
-                                    torch.empty(S, key[1], dtype=torch.int64, device=dev),
-                                    torch.empty(S, key[1], abi.LP_DET_COLS, dtype=torch.float32, device=dev))
-        return out
+        return _persistent(sh['out'], key, lambda: (
+            torch.zeros(key[0], m, Hc, Wc, 3, dtype=torch.uint8, device=dev), torch.zeros(key[0], m, dtype=torch.int32, device=dev),
+            torch.zeros(key[0], m, dtype=torch.int64, device=dev), torch.zeros(S, key[1], Hc, Wc, 3, dtype=torch.uint8, device=dev),
+            torch.empty(S, key[1], 4, dtype=torch.int32, device=dev), torch.empty(S, key[1], dtype=torch.int64, device=dev),
+            torch.empty(S, key[1], abi.LP_DET_COLS, dtype=torch.float32, device=dev)))
 
     def update_with_shots(self, frames, det, count, stream_of=None, flush=None, max_ended=None):
         """``update`` plus the best shot of every track that ends in it, enqueued back to back with no host read: the tracker,
@@ -1502,7 +1502,7 @@ class PlateTracker:
         sh, S, (B, max_det) = self._shots, self.n_streams, det.shape[:2]
         crops, status, sharp, shot_crops, shot_i, shot_q, shot_det = self.shot_buffers(B, max_ended)
         _, tid, ended_i, _, ended_count = self.buffers(B, max_det, max_ended)
-        so = (ctypes.c_int * max(B, 1))(*stream_of)
+        so, _ = _host_lists(stream_of, B)
         with torch.cuda.device(self.device):
             abi.check(abi.load().lp_best_shot_update(_dptr(sh['state']), S, self.max_tracks, sh['crop_hw'][0], sh['crop_hw'][1], _dptr(det),
                                                      _dptr(count), B, max_det, _dptr(tid), _dptr(self.slot_buffer(B, max_det)), _dptr(crops),
@@ -1573,25 +1573,19 @@ class LookbackRedactor(LookbackHost):
         """The persistent outputs of a push behind an update of B frames: (rel_det [B,rows,28], rel_count [B], rel_frame [B],
         tail_det [S,D,rows,28], tail_count [S,D], tail_frame [S,D])."""
         key, S, D, dev = (int(B), int(rows)), self.n_streams, self.depth, self.device
-        out = self._out.get(key)
-        if out is None:
+
+        def make():                             # the tails do not depend on B: every shape shares the first one's
             tails = next(iter(self._out.values()))[3:] if self._out else (
                 torch.empty(S, D, key[1], abi.LP_DET_COLS, dtype=torch.float32, device=dev),
                 torch.empty(S, D, dtype=torch.int32, device=dev), torch.empty(S, D, dtype=torch.int32, device=dev))
-            out = self._out[key] = (torch.empty(key[0], key[1], abi.LP_DET_COLS, dtype=torch.float32, device=dev),
-                                    torch.empty(key[0], dtype=torch.int32, device=dev),
-                                    torch.empty(key[0], dtype=torch.int32, device=dev)) + tuple(tails)
-        return out
+            return (torch.empty(key[0], key[1], abi.LP_DET_COLS, dtype=torch.float32, device=dev),
+                    torch.empty(key[0], dtype=torch.int32, device=dev), torch.empty(key[0], dtype=torch.int32, device=dev)) + tuple(tails)
+        return _persistent(self._out, key, make)
 
     def reset(self, streams=None):
         """Zero the state of ``streams`` (all for None) and forget their frames; use it together with ``PlateTracker.reset``."""
         if self.state is not None:
-            st = self.state.view(self.n_streams, -1)
-            if streams is None:
-                st.zero_()
-            else:
-                for s in streams:
-                    st[int(s)].zero_()
+            _zero_streams(self.state, self.n_streams, streams)
         self._reset_host(streams)
 
     @property
@@ -1609,12 +1603,11 @@ class LookbackRedactor(LookbackHost):
         rows = hold_rows + self.back_cap
         state = self._state_for(rows)
         out = self.buffers(B, rows)
-        so = (ctypes.c_int * max(B, 1))(*stream_of)
-        fl = (ctypes.c_ubyte * S)(*flush)
+        so, fl = _host_lists(stream_of, B, flush)
         with torch.cuda.device(self.device):
             abi.check(abi.load().lp_lookback_update(_dptr(state), S, self.max_tracks, self.depth, self.max_back, self.back_cap,
                                                     _dptr(det_hold), _dptr(count_hold), _dptr(tid), _dptr(slot), B, max_det, hold_rows,
-                                                    so, ctypes.cast(fl, ctypes.c_void_p), _dptr(out[0]), _dptr(out[1]), _dptr(out[2]),
+                                                    so, fl, _dptr(out[0]), _dptr(out[1]), _dptr(out[2]),
                                                     _dptr(out[3]), _dptr(out[4]), _dptr(out[5]), _stream_ptr(self.device)),
                       'lp_lookback_update')
         return out
@@ -1632,10 +1625,7 @@ class LookbackRedactor(LookbackHost):
         return blank
 
     def _status_for(self, n, rows):
-        st = self._status.get((n, rows))
-        if st is None:
-            st = self._status[(n, rows)] = torch.empty(n, rows, dtype=torch.int32, device=self.device)
-        return st
+        return _persistent(self._status, (n, rows), lambda: torch.empty(n, rows, dtype=torch.int32, device=self.device))
 
     def _redact(self, frames, rel, tails, out):
         kw = dict(mode=self.mode, cell=self.cell, margin=self.margin, fill=self.fill)
