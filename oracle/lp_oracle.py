@@ -1,6 +1,6 @@
 """ORACLE (test infrastructure, not product code) -- CPU restatement of the
 YOLO-LP detection forward pass: BN fold / RepVGG re-parameterisation, backbone,
-BiFPAN neck, decoupled LP head and anchor-free decode, as plain fp32 torch
+BiFPAN neck, decoupled LP head and anchor-free decode, as plain fp32 (or, on request, fp64) torch
 functional ops over a *state_dict* (no nn.Module classes of the product are
 used).  Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s
 ``cpu_baseline`` leg may import this file; the product path never does.
@@ -32,11 +32,18 @@ BN_EPS = 1e-3   # yolov6/utils/torch_utils.py:44 (initialize_weights sets every 
 # of exp / reciprocal in SiLU, each of which can move an activation by one 16-bit ulp when its fp32 value sits at a
 # rounding boundary.  None = the plain fp32 restatement.
 _RND = None
+# Working precision (``forward(..., precision=torch.float32 / torch.float64)``): the type that carries the state dict, the fold,
+# the input, the anchors and strides and every layer output.  float64 is the high-precision yardstick of the whole-model parity
+# tests: the same operations in the same order with rounding errors ~2^-29 times smaller, so that the fp32 oracle's OWN error
+# (fp32 - fp64) can be measured and an engine's error stated relative to it.  With ``round_to`` the 16-bit roundings stay where
+# they are and everything between them is done in ``precision``.
+_PREC = torch.float32
 
 
 def _r(t):
-    """Round to the 16-bit activation type of the rounding-aware mode (identity in fp32 mode)."""
-    return t if _RND is None else t.to(_RND).float()
+    """Round to the 16-bit activation type of the rounding-aware mode and widen back to the working precision (identity without
+    ``round_to``)."""
+    return t if _RND is None else t.to(_RND).to(_PREC)
 
 
 class Arch:
@@ -96,7 +103,7 @@ def fold_conv_bn(sd, p):
     g, beta, mu, var = _bn(sd, p + '.bn')
     scale = g / torch.sqrt(BN_EPS + var)
     w2 = torch.mm(torch.diag(scale), w.reshape(w.shape[0], -1)).reshape(w.shape)
-    b_conv = sd.get(p + '.conv.bias', torch.zeros(w.shape[0]))
+    b_conv = sd.get(p + '.conv.bias', torch.zeros(w.shape[0], dtype=w.dtype))
     b2 = torch.mm(torch.diag(scale), b_conv.reshape(-1, 1)).reshape(-1) + (beta - g * mu / torch.sqrt(var + BN_EPS))
     return w2, b2
 
@@ -117,7 +124,7 @@ def fold_repvgg(sd, p):
     w, b = w3 + F.pad(w1, [1, 1, 1, 1]), b3 + b1
     if p + '.rbr_identity.weight' in sd:
         c = w3.shape[1]
-        eye = torch.zeros(c, c, 3, 3)
+        eye = torch.zeros(c, c, 3, 3, dtype=w3.dtype)
         eye[torch.arange(c), torch.arange(c), 1, 1] = 1
         wid, bid = branch(eye, p + '.rbr_identity')
         w, b = w + wid, b + bid
@@ -255,8 +262,8 @@ def anchors(shapes, strides=(8, 16, 32, 64)):
     pts, st = [], []
     for (h, w), s in zip(shapes, strides):
         gy, gx = torch.meshgrid(torch.arange(h) + 0.5, torch.arange(w) + 0.5, indexing='ij')
-        pts.append(torch.stack([gx, gy], -1).float().reshape(-1, 2))
-        st.append(torch.full((h * w, 1), float(s)))
+        pts.append(torch.stack([gx, gy], -1).to(_PREC).reshape(-1, 2))      # (k + 0.5: exact in either precision)
+        st.append(torch.full((h * w, 1), float(s), dtype=_PREC))
     return torch.cat(pts), torch.cat(st)
 
 
@@ -273,7 +280,7 @@ def decode(reg, cor, pts, st):
 
 
 def head(sd, a, feats):
-    """Detect.forward eval branch (effidehead.py:214-301) -> [B, N, no] fp32."""
+    """Detect.forward eval branch (effidehead.py:214-301) -> [B, N, no] in the working precision."""
     B = feats[0].shape[0]
     cls_all = [[] for _ in CLS_HEADS]
     reg_all, cor_all = [], []
@@ -295,26 +302,30 @@ def head(sd, a, feats):
     cat = lambda parts: torch.cat(parts, -1).permute(0, 2, 1)   # noqa: E731
     pts, st = anchors([f.shape[2:] for f in feats])
     box, corners = decode(cat(reg_all), cat(cor_all), pts, st)
-    ones = torch.ones(B, box.shape[1], 1)
+    ones = torch.ones(B, box.shape[1], 1, dtype=box.dtype)
     return torch.cat([box, ones, corners] + [cat(p) for p in cls_all], -1)
 
 
-def forward(sd, a, x, return_stages=False, round_to=None):
-    """Model.forward (yolo.py:32-40): pred [B,N,no] fp32 and the three neck maps.  ``round_to``: the rounding-aware mode
-    (see ``_RND``) for the fp16 / bf16 engines; ``sd`` stays the fp32 state_dict (it is folded in fp32, then rounded)."""
-    global _RND
+def forward(sd, a, x, return_stages=False, round_to=None, precision=torch.float32):
+    """Model.forward (yolo.py:32-40): pred [B,N,no] and the three neck maps, in ``precision`` (fp32, the default, or fp64: see
+    ``_PREC``).  ``round_to``: the rounding-aware mode (see ``_RND``) for the fp16 / bf16 engines; ``sd`` stays the fp32
+    state_dict (it is folded in ``precision``, then rounded)."""
+    global _RND, _PREC
     if round_to not in (None, torch.float16, torch.bfloat16):
         raise ValueError('round_to must be None, torch.float16 or torch.bfloat16')
-    sd = {k: v.float() for k, v in sd.items()}
-    x = x.float()
-    prev, _RND = _RND, round_to
+    if precision not in (torch.float32, torch.float64):
+        raise ValueError('precision must be torch.float32 or torch.float64')
+    sd = {k: v.to(precision) for k, v in sd.items()}
+    x = x.to(precision)
+    prev, _RND = (_RND, _PREC), round_to
+    _PREC = precision
     try:
         with torch.no_grad():
             bb = backbone(sd, a, _r(x))
             nk = neck(sd, a, bb)
             pred = head(sd, a, nk)
     finally:
-        _RND = prev
+        _RND, _PREC = prev
     if return_stages:
         return pred, nk, bb
     return pred, nk

@@ -384,3 +384,287 @@ def log_dir():
             pass
     os.makedirs(d, exist_ok=True)
     return d
+
+
+# ---- float64 post-processing and its decision margins (tests/test_e2e_cpu.py, tests/test_e2e_gpu.py) ----------------------------
+# The steps and the operation order of oracle/lp_post_ref.c (nms.py:68-125) on a float64 prediction.  The reference uses TWO means
+# of the eight segment maxima c0..c7: the confidence mask tests (c0+...+c6+c6)/8 (ad4 twice, ad5 omitted), the sort key and the
+# greedy step use (c0+...+c7)/8.  Both are restated; "score" below is the sort key, "mask" the masked mean.
+MAX_NMS = 30000
+
+
+def post64_rows(x):
+    """One image's float64 prediction [N,290] -> dict of float64 arrays: box [N,4] xyxy, corners [N,8], cf [N,8] segment maxima,
+    ci [N,8] first-maximum indices, mask [N] and score [N] (see above).  ``x`` is not modified."""
+    x = np.array(x, dtype=np.float64)
+    assert x.ndim == 2 and x.shape[1] == SEG[-1]
+    x[:, 13:] *= x[:, 4:5]
+    box = np.stack([x[:, 0] - x[:, 2] / 2, x[:, 1] - x[:, 3] / 2, x[:, 0] + x[:, 2] / 2, x[:, 1] + x[:, 3] / 2], 1)
+    return dict(post64_scores(x[:, 13:]), box=box, corners=x[:, 5:13].copy())
+
+
+def post64_scores(prob):
+    """cf, ci, mask, score of the (obj-multiplied) probability columns [N,277]."""
+    cf = np.stack([prob[:, a - 13:b - 13].max(1) for a, b in zip(SEG[:-1], SEG[1:])], 1)
+    ci = np.stack([prob[:, a - 13:b - 13].argmax(1) for a, b in zip(SEG[:-1], SEG[1:])], 1)
+    c = [cf[:, k] for k in range(8)]
+    mask = (c[0] + c[1] + c[2] + c[3] + c[4] + c[5] + c[6] + c[6]) / 8.0
+    score = (c[0] + c[1] + c[2] + c[3] + c[4] + c[5] + c[6] + c[7]) / 8.0
+    return dict(cf=cf, ci=ci, mask=mask, score=score)
+
+
+def _conf64(conf_thres):
+    return float(np.float32(conf_thres))          # torch casts the python scalar to the tensor's dtype: the engine compares with this
+
+
+def post64_select(box, mask, score, conf_thres, iou_thres, max_det, max_nms=MAX_NMS):
+    """Mask, stable descending sort, max_nms cut, greedy step (strict >, fp64 IoU = inter / (a_i + a_j - inter)), max_det cut.
+    -> kept anchor indices in output order (int64)."""
+    sel = np.nonzero(mask >= _conf64(conf_thres))[0]
+    order = sel[np.argsort(-score[sel], kind='stable')][:max_nms]
+    b = box[order]
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    sup = np.zeros(len(order), bool)
+    keep = []
+    for a in range(len(order)):
+        if sup[a]:
+            continue
+        if len(keep) == max_det:
+            break
+        keep.append(order[a])
+        w = np.maximum(0.0, np.minimum(b[a, 2], b[a + 1:, 2]) - np.maximum(b[a, 0], b[a + 1:, 0]))
+        h = np.maximum(0.0, np.minimum(b[a, 3], b[a + 1:, 3]) - np.maximum(b[a, 1], b[a + 1:, 1]))
+        inter = w * h
+        with np.errstate(divide='ignore', invalid='ignore'):
+            sup[a + 1:] |= inter / (area[a] + area[a + 1:] - inter) > float(iou_thres)
+    return np.asarray(keep, np.int64)
+
+
+def nms64(pred, conf_thres, iou_thres, max_det, max_nms=MAX_NMS):
+    """float64 restatement of the post-processing for a batch [B,N,290] (float64; not modified):
+    (list of [n_i,28] float64 rows, list of kept anchor-index arrays), rows laid out as lp_post_ref.c writes them."""
+    out, kept = [], []
+    for x in np.asarray(pred, np.float64):
+        r = post64_rows(x)
+        k = post64_select(r['box'], r['mask'], r['score'], conf_thres, iou_thres, max_det, max_nms)
+        out.append(np.concatenate([r['box'][k], r['corners'][k], r['cf'][k], r['ci'][k].astype(np.float64)], 1))
+        kept.append(k)
+    return out, kept
+
+
+def iou_bounds(box, delta):
+    """Lower and upper bounds [n,n] of the IoU of every pair of xyxy boxes when every corner coordinate may move by <= delta:
+    intersection of the boxes grown by delta over the union of the boxes shrunk by delta, and the other way round.  The intersection
+    bounds hold for any corner order (an inverted box, x2 < x1, intersects nothing); a pair that CAN intersect and has a box thinner
+    than 2 delta on either side (its area may change sign after the move: the formula is then not monotone) gets (-inf, inf)."""
+    x1, y1, x2, y2 = (box[:, k] for k in range(4))
+
+    def pair(lo):                       # lo: shrink (+delta on the near corner), else grow
+        d = delta if lo else -delta
+        a1, b1, a2, b2 = x1 + d, y1 + d, x2 - d, y2 - d
+        w = np.maximum(0.0, np.minimum(a2[:, None], a2[None]) - np.maximum(a1[:, None], a1[None]))
+        h = np.maximum(0.0, np.minimum(b2[:, None], b2[None]) - np.maximum(b1[:, None], b1[None]))
+        return w * h, np.maximum(0.0, a2 - a1) * np.maximum(0.0, b2 - b1)
+    i_lo, a_lo = pair(True)
+    i_up, a_up = pair(False)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        den_up = a_lo[:, None] + a_lo[None] - i_up
+        up = np.where(i_up == 0, 0.0, np.where(den_up > 0, i_up / den_up, np.inf))
+        den_lo = a_up[:, None] + a_up[None] - i_lo
+        lo = np.where(i_lo == 0, 0.0, i_lo / den_lo)
+    thin = (x2 - x1 <= 2 * delta) | (y2 - y1 <= 2 * delta)
+    bad = (thin[:, None] | thin[None]) & (i_up > 0)      # (no possible intersection: the IoU is 0, or 0 / 0 -- never over a threshold)
+    return np.where(bad, -np.inf, lo), np.where(bad, np.inf, up)
+
+
+def decision_margins(pred, conf_thres, iou_thres, max_det, eps_s, eps_p, delta, max_nms=MAX_NMS):
+    """Which decisions of the post-processing of ONE image's float64 prediction [N,290] are firm when every probability may move by
+    <= eps_p, the masked mean and the score by <= eps_s and every box corner by <= delta.
+
+    Returns a dict: ``keep`` the float64 kept anchors (post64_select), ``ambiguous`` the sorted anchor indices whose fate (kept or
+    not) could change, ``nonfirm`` bool [len(keep),8]: class segments of a kept row whose two largest probabilities are within
+    2 eps_p (the argmax is not firm there), ``order_ties``: pairs of kept rows that follow each other with scores within 2 eps_s (their
+    ORDER in the output is not firm), ``candidates``: number of anchors that pass the mask.
+
+    How: P = anchors that can pass the mask (mask >= conf - eps_s); two anchors are NEAR-scored when their scores are within 2 eps_s,
+    i is FIRMLY before j when score_i - score_j > 2 eps_s.  A THREAT of i is another anchor of P, before or near i, whose IoU with
+    i can exceed the threshold (upper bound > iou_thres).  To a fixed point:
+      sure-kept = firmly passes the mask and every threat of it is dead;  dead = some sure-kept anchor firmly before it has an IoU
+      lower bound > iou_thres with it.
+    Under any move within the margins a sure-kept anchor is kept (whatever could suppress it is never kept) and a dead one is not
+    (its suppressor is kept, stays before it and stays over the threshold); by induction over the fixed-point rounds.  Every other
+    anchor of P is ambiguous, and it is so for one of these reasons: its mask value is within eps_s of conf (1); a sure-kept
+    anchor firmly before it straddles the IoU threshold with it (2); a near-scored anchor can overlap it (2, 3); a threat of it is
+    itself ambiguous (5, the closure).  An anchor within eps_s of conf is reported even when it is dead.  (4) the cuts: with more
+    than max_nms anchors in P and the last one in near-scored to the first one out, those near either can fall on either side and are
+    treated like (1); with more possible survivors than max_det, the kept rows whose rank can cross the cut are ambiguous."""
+    r = post64_rows(pred)
+    conf, iou = _conf64(conf_thres), float(iou_thres)
+    keep = post64_select(r['box'], r['mask'], r['score'], conf_thres, iou_thres, max_det, max_nms)
+    score = r['score']
+    P = np.nonzero(r['mask'] >= conf - eps_s)[0]
+    P = P[np.argsort(-score[P], kind='stable')]
+    unsure = np.abs(r['mask'][P] - conf) <= eps_s                       # (1)
+    if len(P) > max_nms:                                                # (4) the max_nms cut
+        cut, out = score[P[max_nms - 1]], score[P[max_nms]]            # the last one in, the first one out
+        if cut - out <= 2 * eps_s:
+            unsure |= (np.abs(score[P] - cut) <= 2 * eps_s) | (np.abs(score[P] - out) <= 2 * eps_s)
+        inside = unsure | (np.arange(len(P)) < max_nms)
+        P, unsure = P[inside], unsure[inside]
+    s = score[P]
+    lo, up = iou_bounds(r['box'][P], delta)
+    gap = s[:, None] - s[None]                                          # gap[i, j] > 2 eps_s: i firmly before j
+    threat = (gap >= -2 * eps_s) & (up > iou) & ~np.eye(len(P), dtype=bool)      # threat[b, i]: b threatens i
+    kills = (gap > 2 * eps_s) & (lo > iou)                              # kills[i, j]: i, if kept, surely suppresses j
+    sure, dead = np.zeros(len(P), bool), np.zeros(len(P), bool)
+    while True:
+        new_sure = ~unsure & ~dead & ~(threat & ~dead[:, None]).any(0)
+        new_dead = (kills & new_sure[:, None]).any(0)
+        if np.array_equal(new_sure, sure) and np.array_equal(new_dead, dead):
+            break
+        sure, dead = new_sure, new_dead
+    amb = (~sure & ~dead) | unsure
+    if int((~dead).sum()) > max_det:                                    # (4) the max_det cut: ranks among the survivors
+        alive = np.nonzero(~dead)[0]                                    # in score order
+        if amb[alive].any():
+            first = alive[amb[alive]][0]                                # from the first ambiguous survivor on, no rank is known
+            amb[alive[s[alive] <= s[first] + 2 * eps_s]] = True
+        elif s[alive[max_det - 1]] - s[alive[max_det]] <= 2 * eps_s:    # all sure: only the order at the cut matters
+            amb[alive[np.abs(s[alive] - s[alive[max_det - 1]]) <= 2 * eps_s]] = True
+            amb[alive[np.abs(s[alive] - s[alive[max_det]]) <= 2 * eps_s]] = True
+    prob = np.array(pred, dtype=np.float64)[keep]
+    prob = prob[:, 13:] * prob[:, 4:5]
+    nonfirm = np.zeros((len(keep), 8), bool)
+    for k, (a, b) in enumerate(zip(SEG[:-1], SEG[1:])):
+        top = np.sort(prob[:, a - 13:b - 13], 1)[:, -2:]
+        nonfirm[:, k] = top[:, 1] - top[:, 0] <= 2 * eps_p
+    ks = score[keep]
+    ties = [(int(keep[i]), int(keep[i + 1])) for i in range(len(keep) - 1) if ks[i] - ks[i + 1] <= 2 * eps_s]
+    return dict(keep=keep, ambiguous=np.sort(P[amb]), nonfirm=nonfirm, order_ties=ties,
+                candidates=int((r['mask'] >= conf).sum()))
+
+
+# ---- whole-model cases of the end-to-end parity tests ------------------------------------------------------------------------------
+# Synthetic weights (build_synthetic's seeded recipe at ``sigma``), input torch.rand(B,3,H,W) of ``seed``: the smallest shapes that
+# reach three head levels (four for P6) and more than one tile of the tiled kernels.
+E2E_CASES = {
+    'yololps': dict(arch='yololps', sigma=0.25, shape=(2, 320, 320), seed=1234),
+    'yololpn': dict(arch='yololpn', sigma=0.6, shape=(2, 320, 256), seed=1234),
+    'yolov6m': dict(arch='yolov6m', sigma=0.25, shape=(1, 320, 320), seed=1234),          # DFL, BottleRep
+    # the P6 case, four head levels: yolov6s6 at its own width (0.5) -- its float64 forward takes under 2 s, no reduction is needed
+    'yolov6s6': dict(arch='yolov6s6', sigma=0.25, shape=(1, 320, 256), seed=1234),
+}
+# Post-processing settings per case: the inference thresholds, and -- where the case meets the input conditions with it (fewer
+# candidates than max_det; at the evaluation confidence 0.03 every anchor is a candidate) -- the evaluation IoU and max_det at conf 0.25.
+E2E_SETTINGS = {
+    'yololps': [(0.4, 0.45, 1000), (0.25, 0.65, 300)], 'yololpn': [(0.4, 0.45, 1000)], 'yolov6m': [(0.4, 0.45, 1000)],
+    'yolov6s6': [(0.4, 0.45, 1000), (0.25, 0.65, 300)],
+}
+# What the float64 oracle and the analyser give for these cases (seed search on the CPU; asserted before an engine is consulted).
+# The synthetic models' outputs hardly depend on the input, so the input seed moves these counts by a few rows only; the seed stays
+# 1234 everywhere.  Per (case, setting): per image (candidates, kept rows) -- these come from the float64 oracle alone and are asserted.
+# Suppressed share = 1 - kept / candidates: yolov6m 93 %, yolov6s6 49 % / 21 % (the two cases that exercise the greedy step), yololpn
+# 4 %, yololps 0 % (its synthetic boxes are inverted, x2 < x1: such a box intersects nothing).  Ambiguous anchors: 0 everywhere, and
+# still 0 with margins 4 x larger (8 x except yololps' second setting).  Non-firm (row, segment) pairs: 0 of 392 .. 2400.  Pairs of
+# kept rows in a near-tie of scores (their ORDER is not firm: they may swap) -- these depend on the margins, i.e. on the fp32 oracle's
+# error on the machine at hand, so they are bounded, not pinned: yololps 0 / 4-7 of 305 rows, yololpn 4-5 of 522, the others 0.
+E2E_EXPECT = {
+    ('yololps', 0): [(49, 49), (49, 49)], ('yololps', 1): [(169, 169), (136, 136)], ('yololpn', 0): [(271, 260), (271, 262)],
+    ('yolov6m', 0): [(323, 21)], ('yolov6s6', 0): [(39, 20)], ('yolov6s6', 1): [(68, 54)],
+}
+E2E_FACTOR = 4.0          # engine error <= 4 x the fp32 oracle's own error against the fp64 oracle (see DESIGN, 4.2)
+_e2e_cache = {}
+
+
+def parity_stats(pred, necks, ref64, necks64):
+    """Error figures of a prediction [B,N,290] and its neck maps against the float64 oracle's: max and rms over the coordinate
+    columns 0..12 (pixels) and over the probability columns, max relative error (rel_err) of the neck maps (``neck_max``; per map as
+    well), and the largest moves of
+    the post-processing's inputs: masked mean / score, and box corner (xyxy)."""
+    p, r = pred.double(), ref64.double()
+    dc, dp = (p - r)[..., :13], (p - r)[..., 13:]
+    out = dict(coord_max=float(dc.abs().max()), coord_rms=float(dc.pow(2).mean().sqrt()),
+               prob_max=float(dp.abs().max()), prob_rms=float(dp.pow(2).mean().sqrt()))
+    for i, (f, rf) in enumerate(zip(necks, necks64)):
+        out['neck%d' % i] = rel_err(f.float().cpu(), rf)
+    out['neck_max'] = max(out['neck%d' % i] for i in range(len(necks64)))
+    s_err = b_err = 0.0
+    for a, b in zip(p.numpy(), r.numpy()):
+        ra, rb = post64_rows(a), post64_rows(b)
+        s_err = max(s_err, float(np.abs(ra['score'] - rb['score']).max()), float(np.abs(ra['mask'] - rb['mask']).max()))
+        b_err = max(b_err, float(np.abs(ra['box'] - rb['box']).max()))
+    out.update(score_max=s_err, box_max=b_err)
+    return out
+
+
+def e2e_model(key):
+    """The case's model on the CPU, unfused (its state dict is what the oracle folds)."""
+    from yolov6.utils.synth import build_synthetic
+    c = E2E_CASES[key]
+    return build_synthetic(os.path.join(REPO, 'configs', c['arch'] + '.py'), sigma=c['sigma']).eval()
+
+
+def e2e_input(key):
+    c = E2E_CASES[key]
+    B, H, W = c['shape']
+    return torch.rand(B, 3, H, W, generator=torch.Generator().manual_seed(c['seed']))
+
+
+def e2e_reference(key, round_to=None):
+    """One case's references, computed once per process and never modified: the float64 oracle (pred64, necks64, backbone64), the
+    fp32 oracle of today, ``e_ref`` = parity_stats(fp32 oracle against fp64 oracle): the reference's own error, and the margins of
+    the decision analysis eps_p, eps_s, delta = 4 x e_ref's prob_max, score_max, box_max.  With ``round_to`` both are the rounding-
+    aware oracle (fp32 accumulation against fp64 between the same 16-bit roundings)."""
+    from oracle import lp_oracle
+    if (key, round_to) not in _e2e_cache:
+        c = E2E_CASES[key]
+        sd = e2e_model(key).state_dict()
+        a = lp_oracle.arch(c['arch'])
+        x = e2e_input(key)
+        if round_to is not None:
+            x = x.to(round_to)
+        p64, n64, b64 = lp_oracle.forward(sd, a, x, return_stages=True, round_to=round_to, precision=torch.float64)
+        p32, n32 = lp_oracle.forward(sd, a, x, round_to=round_to)
+        e_ref = parity_stats(p32, n32, p64, n64)
+        _e2e_cache[(key, round_to)] = dict(
+            x=x, pred64=p64, necks64=n64, bb64=b64, pred32=p32, necks32=n32, e_ref=e_ref, eps_p=E2E_FACTOR * e_ref['prob_max'],
+            eps_s=E2E_FACTOR * e_ref['score_max'], delta=E2E_FACTOR * e_ref['box_max'])
+    return _e2e_cache[(key, round_to)]
+
+
+def e2e_decisions(key, k):
+    """decision_margins of every image of a case at its k-th setting, with the case's own margins (cached with the reference)."""
+    r = e2e_reference(key)
+    if ('dec', k) not in r:
+        conf, iou, max_det = E2E_SETTINGS[key][k]
+        r[('dec', k)] = [decision_margins(p, conf, iou, max_det, r['eps_s'], r['eps_p'], r['delta']) for p in r['pred64'].numpy()]
+    return r[('dec', k)]
+
+
+def assert_e2e_inputs(key, k):
+    """The conditions on the INPUTS of the kept-set tests, from the float64 oracle alone: no ambiguous anchor, >= 16 kept rows per
+    case, fewer candidates than max_det, at most 2 % of the (row, segment) pairs without a firm argmax and at most 5 % of the kept rows
+    in a near-tie of scores; and the recorded counts of E2E_EXPECT."""
+    dec, exp = e2e_decisions(key, k), E2E_EXPECT[(key, k)]
+    max_det = E2E_SETTINGS[key][k][2]
+    assert [len(d['ambiguous']) for d in dec] == [0] * len(dec), [d['ambiguous'] for d in dec]
+    assert sum(len(d['keep']) for d in dec) >= 16
+    assert all(d['candidates'] < max_det for d in dec)
+    nonfirm, pairs = sum(int(d['nonfirm'].sum()) for d in dec), sum(d['nonfirm'].size for d in dec)
+    ties = sum(len(d['order_ties']) for d in dec)
+    assert nonfirm <= 0.02 * pairs and 2 * ties <= 0.05 * sum(len(d['keep']) for d in dec), (nonfirm, pairs, ties)
+    got = [(d['candidates'], len(d['keep'])) for d in dec]
+    assert got == exp, (got, exp)
+    return dec
+
+
+def tie_runs(keep, order_ties):
+    """Positions of ``keep`` split into runs: consecutive rows linked by a near-tie of scores form one run (they may come out in any
+    order), every other row is a run of its own.  -> list of (start, stop)."""
+    linked = set(order_ties)
+    runs, start = [], 0
+    for i in range(len(keep)):
+        if i + 1 == len(keep) or (int(keep[i]), int(keep[i + 1])) not in linked:
+            runs.append((start, i + 1))
+            start = i + 1
+    return runs
