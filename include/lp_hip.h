@@ -616,6 +616,42 @@ int lp_redact_plates_batch(const lp_redact_desc* desc, int n_frames, const float
                            const lp_redact_params* p, int32_t* status /* [n_frames,max_det] */,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* lp_redact_gauss_batch: the third redaction, a Gaussian blur.  The pixel set is that of lp_redact_plates_batch to the letter (rows,
+ * quad, margin, scan rectangle, edge tests, status codes, the NV12 "chroma sample iff any of its four luma pixels" rule); only the
+ * value written is new: a pixel of any row takes G(frame) at that pixel, where G is the frame AS IT WAS BEFORE THE CALL under the
+ * integer separable blur below.  G depends on the frame alone, so the result does not depend on the order of the rows and
+ * overlapping plates store the same bytes; no byte outside the union of the masks changes.  Unlike the mosaic a second call is
+ * NOT idempotent inside the mask: it blurs again.  yolov6/utils/redact.py::redact_plates_np (mode 'gauss') restates it bit for bit.
+ *   Taps are data (yolov6/utils/redact.py::gauss_taps computes them in float64; the device evaluates no exponential):
+ *   t[0..radius], non-increasing, t[0] + 2 * (t[1] + ... + t[radius]) = 16384, radius in 1..LP_REDACT_MAX_RADIUS.
+ *   Blur of one plane of bytes p, indices clamped to the plane (replicate border), int32 throughout:
+ *     hq[i][j]  = (sum_k t[|k|] * p[i][clamp(j + k)] + 32) >> 6          (k = -radius..radius; at most 65280)
+ *     out[i][j] = (sum_k t[|k|] * hq[clamp(i + k)][j] + (1 << 21)) >> 22  (the sum stays below 2^31)
+ *   A constant plane comes out unchanged.  BGR: the three channels, the same taps.  NV12: Y with taps / radius; U and V with
+ *   taps_c / radius_c, each on the half-resolution chroma plane in chroma coordinates (the clamp too); the matrix plays no part.
+ * Two kernels: the first only reads the frames and writes the workspace: per frame a table of h0 x w0 4-byte entries
+ * (c0, c1, c2, 0), one per pixel (NV12: the pixel's blurred luma and its block's blurred U, V), each table at a 16-byte
+ * multiple; it fills every frame-anchored 32 x 32 tile that the scan rectangle of a row touches, one workgroup per tile, the tile
+ * and its halo staged through LDS once.  The second (the write kernel of lp_redact_plates_batch at cell 1) reads det, count and
+ * entries the first wrote in the same call, and writes the frames; the workspace may hold anything on entry.  Every blur launch
+ * of a call precedes its first write launch.  At most LP_FRAMES_PER_LAUNCH frames of one format per launch, descriptors and taps
+ * by value in the kernel arguments: nothing is uploaded, no host sync, capturable in a graph.
+ * Every argument is checked before the first launch (LP_ERR_ARG; nothing is launched): whatever lp_redact_plates_batch rejects for
+ * descriptors, det, count, status, margin and max_det; radius outside 1..LP_REDACT_MAX_RADIUS; taps that increase; a tap total
+ * other than 16384; with an NV12 frame the same three on radius_c and taps_c; a workspace that is null, not 16-byte aligned or
+ * smaller than lp_redact_gauss_workspace_bytes.  n_frames == 0: LP_OK. */
+#define LP_REDACT_MAX_RADIUS 48
+typedef struct lp_redact_gauss_params {
+    double margin;                                  /* as lp_redact_params */
+    int radius, radius_c;                           /* of taps (BGR, Y) and of taps_c (U, V; read only with an NV12 frame) */
+    uint16_t taps[LP_REDACT_MAX_RADIUS + 1];        /* t[0..radius] */
+    uint16_t taps_c[LP_REDACT_MAX_RADIUS + 1];
+} lp_redact_gauss_params;
+size_t lp_redact_gauss_workspace_bytes(const lp_redact_desc* desc, int n_frames, const lp_redact_gauss_params* p);  /* 0 for bad arguments */
+int lp_redact_gauss_batch(const lp_redact_desc* desc, int n_frames, const float* det, const int32_t* count, int max_det,
+                          const lp_redact_gauss_params* p, int32_t* status /* [n_frames,max_det] */,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* lp_lookback_update: the look-back delay of redaction.  lp_track_update_hold covers a tracked plate from its first detection on; a
  * plate enters the picture small or blurred and is detected a few frames later, and those first frames would be stored readable.
  * A small device-resident delay line keeps, per stream, the redaction rows of the last `depth` frames, adds rows to those past

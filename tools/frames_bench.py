@@ -2,7 +2,7 @@
 """Frames benchmark: rescaled detections from host frames, end to end, per frame and batched.
 
     python tools/frames_bench.py [--model yololps] [--size 640] [--dtype f16] [--frame 1080 1920] [--batches 8 32 64]
-                                 [--crops N] [--redact [--redact-cell 16]]
+                                 [--crops N] [--redact [--redact-cell 16] [--redact-sigma 8]]
     python tools/frames_bench.py --tile [--tile-baseline] [--tile-frame 2160 3840] [--tile-size 640] [--tile-overlap 128]
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot] [--redact [--hold [--lookback D]]] [--nv12]
@@ -42,12 +42,14 @@ same for tiled detection: frames/s of ``detect_tiled_with_crops`` for both kinds
 With ``--redact`` (also with ``--nv12``) the plate-redaction stage (runtime.redact_plates, in place on the device frames) is timed
 at the end of the same event chain, on the ``--crops`` quads of each frame (4 when ``--crops`` is not given): ``redact`` = the mosaic
 (lp_redact_plates_batch's two kernels, cell means + write), ``redact_fill`` = the fill (the write kernel alone), so their
-difference is what the cell means cost; and the mosaic's share of the detect stage.  With ``--nv12`` the NV12 planes themselves are
-redacted.
+difference is what the cell means cost, ``redact_gauss`` = the Gaussian blur of ``--redact-sigma`` (lp_redact_gauss_batch: the tile
+blur + the same write kernel); and the mosaic's and the blur's share of the detect stage.  With ``--nv12`` the NV12 planes themselves
+are redacted.
 With ``--track --redact [--hold]`` (also with ``--nv12``: the streams' frames are then NV12) the update and the mosaic behind it
 are timed from events on the tracker's own rows, every stream seeing another frame in every step so that tracks are missed;
 ``--hold`` runs a second tracker with ``enable_hold`` on the same frames, alternating, and redacts along its ``last_hold``:
-``update_ms`` / ``update_hold_ms``, ``redact_ms`` / ``redact_hold_ms`` and the rows per frame each mosaic covered.
+``update_ms`` / ``update_hold_ms``, ``redact_ms`` / ``redact_hold_ms``, ``redact_gauss_ms`` / ``redact_gauss_hold_ms`` (the blur along
+the same rows) and the rows per frame each covered.
 ``--lookback D`` adds a third tracker with the hold and a ``LookbackRedactor`` of that depth behind it: ``update_lookback_ms`` (the
 same update), ``lookback_ms`` (lp_lookback_update) and ``redact_lookback_ms`` (the mosaic on the frames that leave the delay, along
 the rows released for them).
@@ -85,6 +87,7 @@ def parse():
     ap.add_argument('--crops', type=int, default=0, help='plate crops per frame to time (0: no crop stage)')
     ap.add_argument('--redact', action='store_true', help='also time the plate-redaction stage (mosaic, and fill) on the quads of --crops (4 without it)')
     ap.add_argument('--redact-cell', type=int, default=16, help='with --redact: side of a mosaic cell')
+    ap.add_argument('--redact-sigma', type=float, default=8.0, help='with --redact: sigma of the Gaussian blur (0.5..16)')
     ap.add_argument('--tile', action='store_true', help='measure tiled detection of large frames (detect_tiled) instead')
     ap.add_argument('--tile-baseline', action='store_true', help='with --tile: also time region copies + detect_frames + host merge')
     ap.add_argument('--tile-frame', nargs=2, type=int, default=[2160, 3840], metavar=('H', 'W'))
@@ -383,7 +386,7 @@ def redact_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
         def mark():      # the event between lp_lookback_update and the mosaic of one push
             mid[0] = torch.cuda.Event(enable_timing=True)
             mid[0].record()
-    times = {name: dict(update=[], redact=[], lookback=[]) for name in trackers}
+    times = {name: dict(update=[], redact=[], redact_gauss=[], lookback=[]) for name in trackers}
     rows = {name: [] for name in trackers}
     warm = max(3, args.lookback + 1)
     for k in range(warm + args.reps + 1):
@@ -394,7 +397,7 @@ def redact_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
             runtime.rescale_round_batch(det, count, net_hw, [f.shape for f in frames])
             if name == 'lookback':      # the delay keeps references and the uploader reuses its buffer: copies, before the clock
                 frames = [Nv12Frame(f.y.clone(), f.uv.clone(), f.matrix) if isinstance(f, Nv12Frame) else f.clone() for f in frames]
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             ev[0].record()
             det_out = trk.update(det, count)[0]
             ev[1].record()
@@ -405,6 +408,9 @@ def redact_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
                 rdet, rcount = (det_out, count) if name == 'plain' else trk.last_hold[:2]
                 runtime.redact_plates(frames, rdet, rcount, 'mosaic', args.redact_cell)
             ev[2].record()
+            if name != 'lookback':      # the blur along the same rows, behind the mosaic (its time does not depend on the bytes)
+                runtime.redact_plates(frames, rdet, rcount, 'gauss', sigma=args.redact_sigma)
+                ev[3].record()
             torch.cuda.synchronize()
             if k > warm:
                 times[name]['update'].append(ev[0].elapsed_time(ev[1]))
@@ -413,8 +419,9 @@ def redact_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
                     times[name]['redact'].append(mid[0].elapsed_time(ev[2]))
                 else:
                     times[name]['redact'].append(ev[1].elapsed_time(ev[2]))
+                    times[name]['redact_gauss'].append(ev[2].elapsed_time(ev[3]))
                 rows[name].append(float(rcount.clamp(0, rdet.shape[1]).float().mean()))
-    r = dict(redact_cell=args.redact_cell, reps=args.reps)
+    r = dict(redact_cell=args.redact_cell, redact_sigma=args.redact_sigma, reps=args.reps)
     for name in trackers:
         sfx = '' if name == 'plain' else '_' + name
         if name == 'lookback':
@@ -423,6 +430,8 @@ def redact_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
             r['lookback_state_mib'] = round(lb.state.numel() * 4 / 2 ** 20, 2)
         r['update%s_ms' % sfx] = round(float(np.median(times[name]['update'])), 4)
         r['redact%s_ms' % sfx] = round(float(np.median(times[name]['redact'])), 4)
+        if name != 'lookback':
+            r['redact_gauss%s_ms' % sfx] = round(float(np.median(times[name]['redact_gauss'])), 4)
         r['redact%s_rows_per_frame' % sfx] = round(float(np.mean(rows[name])), 2)
     return r
 
@@ -563,7 +572,7 @@ def nv12_mode(args, model, dev, tdt):
                 rcount = torch.full((B,), rn, dtype=torch.int32, device=dev)
                 rst = torch.empty(B, rn, dtype=torch.int32, device=dev)
                 for v in names.values():
-                    v.extend(['redact', 'redact_fill'])
+                    v.extend(['redact', 'redact_fill', 'redact_gauss'])
             times = {kind: {k: [] for k in v} for kind, v in names.items()}
             for _ in range(args.reps + 1):
                 for kind in ('bgr', 'nv12'):
@@ -591,6 +600,8 @@ def nv12_mode(args, model, dev, tdt):
                         ev[i + 1].record()
                         runtime.redact_plates(views[kind], rdet, rcount, 'fill', status=rst)
                         ev[i + 2].record()
+                        runtime.redact_plates(views[kind], rdet, rcount, 'gauss', status=rst, sigma=args.redact_sigma)
+                        ev[i + 3].record()
                     sync()
                     for i, k in enumerate(names[kind]):
                         times[kind][k].append(ev[i].elapsed_time(ev[i + 1]))
@@ -608,8 +619,9 @@ def nv12_mode(args, model, dev, tdt):
                     if args.crops:
                         st['convert_pct_of_detect'] = round(100.0 * med['convert'] / med['detect'], 2)
                 if args.redact:
-                    st['redact_rows_per_frame'], st['redact_cell'] = rn, args.redact_cell
+                    st['redact_rows_per_frame'], st['redact_cell'], st['redact_sigma'] = rn, args.redact_cell, args.redact_sigma
                     st['redact_pct_of_detect'] = round(100.0 * med['redact'] / med['detect'], 2)
+                    st['redact_gauss_pct_of_detect'] = round(100.0 * med['redact_gauss'] / med['detect'], 2)
                 r['stage_ms_' + kind] = st
             sp = times['bgr']['letterbox'][1:]
             r['letterbox_nv12_over_bgr'] = round(r['stage_ms_nv12']['letterbox'] / r['stage_ms_bgr']['letterbox'], 4)
@@ -740,7 +752,7 @@ def main():
             dbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             views = [dbuf[j * f.nbytes:(j + 1) * f.nbytes].view(f.shape) for j, f in enumerate(fr)]
             times = {k: [] for k in ('h2d', 'letterbox', 'detect', 'rescale') + (('crops',) if args.crops else ())
-                     + (('redact', 'redact_fill') if args.redact else ())}
+                     + (('redact', 'redact_fill', 'redact_gauss') if args.redact else ())}
             if args.redact:
                 rn = args.crops or 4
                 rdet = torch.from_numpy(synthetic_quads(B, rn, h0, w0, seed=B)).to(dev)
@@ -772,6 +784,8 @@ def main():
                     ev[i + 1].record()
                     runtime.redact_plates(views, rdet, rcount, 'fill', status=rst)
                     ev[i + 2].record()
+                    runtime.redact_plates(views, rdet, rcount, 'gauss', status=rst, sigma=args.redact_sigma)
+                    ev[i + 3].record()
                 sync()
                 for i, k in enumerate(times):
                     times[k].append(ev[i].elapsed_time(ev[i + 1]))
@@ -792,7 +806,9 @@ def main():
                 del cdet, ccount, cout, cst
             if args.redact:
                 stages[str(B)]['redact_rows_per_frame'], stages[str(B)]['redact_cell'] = rn, args.redact_cell
+                stages[str(B)]['redact_sigma'] = args.redact_sigma
                 stages[str(B)]['redact_pct_of_detect'] = round(100.0 * med['redact'] / med['detect'], 2)
+                stages[str(B)]['redact_gauss_pct_of_detect'] = round(100.0 * med['redact_gauss'] / med['detect'], 2)
             del host, dbuf, views
     out['batched_fps'] = batched
     out['stage_ms'] = stages

@@ -6,7 +6,7 @@
                           [--tile 640 640 [--tile-overlap 0.2] [--no-tile-overview] [--merge-metric iou|ios]]
                           [--track [--track-max-age 5] [--track-iou 0.3] [--track-expand 0.5] [--best-shots [--crop-size 64 192]]]
                           [--nv12 bt601|bt709|bt601f|bt709f [--nv12-size W H]]
-                          [--redact mosaic|fill [--redact-cell 16] [--redact-margin 0.1]
+                          [--redact mosaic|fill|gauss [--redact-cell 16] [--redact-sigma 8] [--redact-margin 0.1]
                            [--redact-hold [--redact-hold-min-hits 1] [--redact-lookback D [--redact-lookback-max-back N]]]]
 """
 import argparse
@@ -65,9 +65,11 @@ _FLAGS = [
                     help='send frames as NV12 with this matrix (bt601, bt709: limited range; bt601f, bt709f: full range): decoded images '
                          'are encoded on the host as a stand-in for a decoder; a source ending in .nv12 is a raw stream of packed frames')),
     ('--nv12-size', dict(nargs=2, type=int, default=None, metavar=('W', 'H'), help='frame size of .nv12 sources')),
-    ('--redact', dict(default=None, choices=['mosaic', 'fill'], metavar='MODE',
-                      help='also write every frame with its detected plates made unreadable (mosaic, or a black fill) to redacted/')),
+    ('--redact', dict(default=None, choices=['mosaic', 'fill', 'gauss'], metavar='MODE',
+                      help='also write every frame with its detected plates made unreadable (mosaic, a black fill, or a Gaussian '
+                           'blur) to redacted/')),
     ('--redact-cell', dict(type=int, default=16, help='with --redact mosaic: side of a mosaic cell in pixels (even, 2..64)')),
+    ('--redact-sigma', dict(type=float, default=8.0, help='with --redact gauss: sigma of the blur in pixels (0.5..16)')),
     ('--redact-margin', dict(type=float, default=0.1, help='with --redact: grow every plate by this fraction of its size (0..4)')),
     ('--redact-hold', dict(action='store_true', help='with --track and --redact: keep a tracked plate redacted, where its track predicts '
                                                      'it, in the frames in which the detector misses it (until the track ends)')),
@@ -96,7 +98,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False, save_crops=False, crop_size=(64, 192),
         tile=None, tile_overlap=0.2, no_tile_overview=False, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3,
         track_expand=0.5, best_shots=False, nv12=None, nv12_size=None, redact=None, redact_cell=16,
-        redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1, redact_lookback=None, redact_lookback_max_back=None):
+        redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1, redact_lookback=None, redact_lookback_max_back=None,
+        redact_sigma=8.0):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track or redact) and not osp.exists(out_dir):
@@ -112,7 +115,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
                       track_iou=track_iou, track_expand=track_expand, best_shots=best_shots, nv12=nv12, nv12_size=nv12_size,
                       redact=redact, redact_cell=redact_cell, redact_margin=redact_margin, redact_hold=redact_hold,
                       redact_hold_min_hits=redact_hold_min_hits, redact_lookback=redact_lookback,
-                      redact_lookback_max_back=redact_lookback_max_back).infer(
+                      redact_lookback_max_back=redact_lookback_max_back, redact_sigma=redact_sigma).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

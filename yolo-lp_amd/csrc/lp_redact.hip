@@ -15,9 +15,19 @@
 // sums, the sample count of its second and third channel, and the store of one pixel; the units, the geometry, the inside test,
 // the reduction and the cell table are the kernels'.
 //
+// lp_redact_gauss_batch is the third redaction, a Gaussian blur, with the same hazard and the same cure: redact_gauss_kernel only
+// reads the frames and writes, for every frame-anchored GS_TILE x GS_TILE tile that the rectangle of a row touches, the blurred
+// value of each of its pixels into a per-pixel table (the mosaic's table at cell 1; a value depends on the frame alone, so a tile
+// that two plates touch is written twice with the same words); redact_write_kernel serves unchanged with cell = 1.  One workgroup
+// blurs one tile: the tile and its halo go through LDS once (clamped coordinates: the replicate border), the horizontal pass fills
+// a 16-bit LDS array, the vertical pass reads it; integers only, the taps are data in the kernel arguments.
+//
 // The size of a plate is device data, so the launch shape cannot follow it: per frame RD_WGS workgroups loop over the units
 // (row r, split s), r < n_b, s < RD_SPLIT -- a frame without plates costs its workgroups one load of the count.  Descriptors
 // travel by value in the kernel arguments (40 bytes x 64): nothing is uploaded, no host sync, capturable in a graph.
+#include <algorithm>
+#include <atomic>
+#include <cstdlib>
 #include <vector>
 
 #include "lp_internal.h"
@@ -40,6 +50,92 @@ struct RdEntry {
 struct RdTable { RdEntry f[LP_FRAMES_PER_LAUNCH]; };
 static_assert(sizeof(RdTable) < 4096, "the table travels as kernel arguments: under 4 KiB");
 
+// ---- the blur of lp_redact_gauss_batch -------------------------------------------------------------------------------------
+constexpr int GS_TILE = 32;             // side of a blur tile in pixels (even: an NV12 tile is whole 2 x 2 blocks)
+constexpr int GS_OUT_BYTES = GS_TILE * GS_TILE * 3;      // LDS: the blurred bytes of a tile (BGR: 3 per pixel; NV12: Y, then UV)
+
+constexpr int GS_GROUP = 4;             // adjacent outputs of a pass that one thread computes from one sliding run of samples
+constexpr int GS_LOADS = 8;             // global byte loads a thread issues back to back while a tile is staged
+constexpr int GS_WINDOW = 2 * LP_REDACT_MAX_RADIUS + 1 + 2 * (GS_GROUP - 1);
+
+// The taps as the passes read them, by value in the kernel arguments: the whole window t[|i - R|], i = 0..2R, widened to int, with
+// GS_GROUP - 1 zeros on either side, so that sample m of a run weighs w[m - j + GS_GROUP - 1] for output j, in or out of its window.
+struct GsTaps {
+    int r, rc;
+    int w[GS_WINDOW], wc[GS_WINDOW];
+};
+static_assert(sizeof(RdTable) + sizeof(GsTaps) < 4096, "table and taps travel as kernel arguments: under 4 KiB");
+
+// LDS of one tile of a plane of C interleaved channels at radius R: the staged bytes and the 16-bit horizontal sums
+constexpr int gs_in_bytes(int tile, int R, int C) { return (tile + 2 * R) * (tile + 2 * R) * C; }
+constexpr int gs_hq_bytes(int tile, int R, int C) { return (tile + 2 * R) * tile * C * 2; }
+
+__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// Blur the tile [y0, y0 + th) x [x0, x0 + tw) of a ph x pw plane of C interleaved byte channels (rows `pitch` bytes apart) into
+// out[th][tw * C], all 256 threads of the workgroup.  in: (th + 2R) x (tw + 2R) x C bytes, hq: (th + 2R) x tw x C shorts.
+//   1. stage: the bytes of the tile + halo in row-major order, adjacent threads adjacent bytes, GS_LOADS loads in flight per thread
+//      (the byte loads are latency, not bandwidth); coordinates clamped to the plane, so every frame byte is loaded once per tile
+//      and the passes need no border case
+//   2. horizontal: hq = (sum_k t[|k|] * in[.][x + k * C] + 32) >> 6 for every staged row (the halo rows feed the vertical pass)
+//   3. vertical: out = (sum_k t[|k|] * hq[i + k][x] + 2^21) >> 22
+// In both passes a thread computes GS_GROUP adjacent outputs along the pass's direction from one run of 2R + GS_GROUP samples, each
+// read from LDS once, a quarter of the reads of a tap-by-tap loop.  Past a clipped tile's edge a run reads
+// up to GS_GROUP - 1 samples of the next row (still inside the array as it is sized for a whole tile); they reach only outputs
+// that are not stored.  The sums are int32 (at most 16384 * 255 and 16384 * 65280 < 2^31; their order is free); a tap and a
+// sample are below 2^24, so the products are 24-bit multiplies (full rate).  Ends behind a barrier: out is readable, in and hq are free.
+template <int C>
+__device__ __forceinline__ void blur_plane(const unsigned char* __restrict__ src, int pitch, int ph, int pw, int y0, int x0, int th, int tw,
+                                           int R, const int* __restrict__ win, unsigned char* in, unsigned short* hq,
+                                           unsigned char* out) {
+    static_assert(GS_GROUP == 4 && GS_TILE % GS_GROUP == 0, "the passes are written for runs of four");
+    const int tid = threadIdx.y * 64 + threadIdx.x;
+    const int ih = th + 2 * R, irow = (tw + 2 * R) * C, orow = tw * C, run = 2 * R + GS_GROUP;
+    for (int p0 = tid; p0 < ih * irow; p0 += 256 * GS_LOADS) {
+        unsigned char v[GS_LOADS];
+#pragma unroll
+        for (int u = 0; u < GS_LOADS; ++u) {       // all loads of a batch are issued before the first is used
+            const int p = p0 + 256 * u < ih * irow ? p0 + 256 * u : p0;
+            const int r = p / irow, b = p - r * irow, c = b / C;
+            v[u] = src[(long long)clampi(y0 - R + r, ph - 1) * pitch + (long long)clampi(x0 - R + c, pw - 1) * C + (b - c * C)];
+        }
+#pragma unroll
+        for (int u = 0; u < GS_LOADS; ++u)
+            if (p0 + 256 * u < ih * irow) in[p0 + 256 * u] = v[u];
+    }
+    __syncthreads();
+    const int ngx = (tw + GS_GROUP - 1) / GS_GROUP * C;      // runs per staged row: a group of pixels x a channel
+    for (int p = tid; p < ih * ngx; p += 256) {
+        const int r = p / ngx, gi = p - r * ngx, pg = gi / C, ch = gi - pg * C;
+        const unsigned char* q = in + r * irow + pg * (GS_GROUP * C) + ch;
+        int acc[GS_GROUP] = {0, 0, 0, 0};
+        for (int m = 0; m < run; ++m) {
+            const int v = q[m * C];
+#pragma unroll
+            for (int j = 0; j < GS_GROUP; ++j) acc[j] += __mul24(win[m - j + GS_GROUP - 1], v);
+        }
+        unsigned short* o = hq + r * orow + pg * (GS_GROUP * C) + ch;
+#pragma unroll
+        for (int j = 0; j < GS_GROUP; ++j)
+            if (pg * GS_GROUP + j < tw) o[j * C] = (unsigned short)((acc[j] + 32) >> 6);
+    }
+    __syncthreads();
+    for (int p = tid; p < (th + GS_GROUP - 1) / GS_GROUP * orow; p += 256) {
+        const int g = p / orow, x = p - g * orow;
+        const unsigned short* q = hq + g * (GS_GROUP * orow) + x;
+        int acc[GS_GROUP] = {0, 0, 0, 0};
+        for (int m = 0; m < run; ++m) {
+            const int v = q[m * orow];
+#pragma unroll
+            for (int j = 0; j < GS_GROUP; ++j) acc[j] += __mul24(win[m - j + GS_GROUP - 1], v);
+        }
+#pragma unroll
+        for (int j = 0; j < GS_GROUP; ++j)
+            if (g * GS_GROUP + j < th) out[(g * GS_GROUP + j) * orow + x] = (unsigned char)((acc[j] + (1 << 21)) >> 22);
+    }
+    __syncthreads();
+}
+
 struct BgrSink {
     // this lane's share of the channel sums over the pixels [ya, yb) x [xa, xb) of one cell, lanes along the cell's rows
     static __device__ __forceinline__ void gather(const RdEntry& f, int ya, int yb, int xa, int xb, int lane, int* acc) {
@@ -54,6 +150,18 @@ struct BgrSink {
     static __device__ __forceinline__ void put(const RdEntry& f, int i, int j, unsigned v) {
         unsigned char* q = f.p0 + (long long)i * f.pitch0 + (long long)j * 3;
         q[0] = (unsigned char)v; q[1] = (unsigned char)(v >> 8); q[2] = (unsigned char)(v >> 16);
+    }
+    // LDS bytes of the staged tile and of its horizontal sums at these radii
+    static int gauss_in_bytes(int R, int) { return gs_in_bytes(GS_TILE, R, 3); }
+    static int gauss_hq_bytes(int R, int) { return gs_hq_bytes(GS_TILE, R, 3); }
+    // the table entries (b, g, r) of the tile [y0, y0 + th) x [x0, x0 + tw)
+    static __device__ __forceinline__ void gauss_tile(const RdEntry& f, const GsTaps& tp, int y0, int x0, int th, int tw,
+                                                      unsigned char* in, unsigned short* hq, unsigned char* out, unsigned* table) {
+        blur_plane<3>(f.p0, f.pitch0, f.h0, f.w0, y0, x0, th, tw, tp.r, tp.w, in, hq, out);
+        for (int p = threadIdx.y * 64 + threadIdx.x; p < th * tw; p += 256) {
+            const int i = p / tw, j = p - i * tw;
+            table[(long long)(y0 + i) * f.w0 + x0 + j] = (unsigned)out[3 * p] | ((unsigned)out[3 * p + 1] << 8) | ((unsigned)out[3 * p + 2] << 16);
+        }
     }
 };
 
@@ -78,6 +186,21 @@ struct Nv12Sink {
     static __device__ __forceinline__ void put(const RdEntry& f, int i, int j, unsigned v) {
         f.p0[(long long)i * f.pitch0 + j] = (unsigned char)v;
         *reinterpret_cast<unsigned short*>(f.p1 + (long long)(i >> 1) * f.pitch1 + (j >> 1) * 2) = (unsigned short)(v >> 8);
+    }
+    // the two planes are blurred one after the other through the same LDS: Y at radius R, then UV (2 channels, half the tile) at Rc
+    static int gauss_in_bytes(int R, int Rc) { return std::max(gs_in_bytes(GS_TILE, R, 1), gs_in_bytes(GS_TILE / 2, Rc, 2)); }
+    static int gauss_hq_bytes(int R, int Rc) { return std::max(gs_hq_bytes(GS_TILE, R, 1), gs_hq_bytes(GS_TILE / 2, Rc, 2)); }
+    // the table entries (y of the pixel, u and v of its block); y0, x0, th and tw are even, as h0, w0 and GS_TILE are
+    static __device__ __forceinline__ void gauss_tile(const RdEntry& f, const GsTaps& tp, int y0, int x0, int th, int tw,
+                                                      unsigned char* in, unsigned short* hq, unsigned char* out, unsigned* table) {
+        unsigned char* out_uv = out + GS_TILE * GS_TILE;
+        blur_plane<1>(f.p0, f.pitch0, f.h0, f.w0, y0, x0, th, tw, tp.r, tp.w, in, hq, out);
+        blur_plane<2>(f.p1, f.pitch1, f.h0 >> 1, f.w0 >> 1, y0 >> 1, x0 >> 1, th >> 1, tw >> 1, tp.rc, tp.wc, in, hq, out_uv);
+        for (int p = threadIdx.y * 64 + threadIdx.x; p < th * tw; p += 256) {
+            const int i = p / tw, j = p - i * tw;
+            const unsigned char* uv = out_uv + ((i >> 1) * (tw >> 1) + (j >> 1)) * 2;
+            table[(long long)(y0 + i) * f.w0 + x0 + j] = (unsigned)out[p] | ((unsigned)uv[0] << 8) | ((unsigned)uv[1] << 16);
+        }
     }
 };
 
@@ -203,6 +326,39 @@ __global__ __launch_bounds__(256) void redact_write_kernel(const RdTable tab, co
     }
 }
 
+// grid (RD_WGS, frames of this launch), block (64, 4), dynamic LDS [out GS_OUT_BYTES | hq | in], in at byte in_off.  Unit (r, s): the
+// workgroup takes the tiles s, s + RD_SPLIT, ... of the frame-anchored tiles that the row's rectangle touches (row-major), one tile
+// at a time.  Every thread derives the same rectangle from the same row, so the loops and their barriers are uniform.  Reads the
+// frames, writes the workspace.
+template <typename SINK>
+__global__ __launch_bounds__(256) void redact_gauss_kernel(const RdTable tab, const GsTaps tp, const float* __restrict__ det,
+                                                           const int32_t* __restrict__ count, int max_det, double s, int in_off,
+                                                           unsigned* __restrict__ ws) {
+    extern __shared__ __align__(16) unsigned char gs_lds[];
+    const int n = clamp_count(count[blockIdx.y], max_det);
+    if (n == 0) return;
+    const RdEntry f = tab.f[blockIdx.y];
+    unsigned* table = ws + f.ws_off;
+    unsigned char* out = gs_lds;
+    unsigned short* hq = reinterpret_cast<unsigned short*>(gs_lds + GS_OUT_BYTES);
+    unsigned char* in = gs_lds + in_off;
+    const long long units = (long long)n * RD_SPLIT;
+    for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+        const int r = (int)(u / RD_SPLIT), sp = (int)(u % RD_SPLIT);
+        double x[4], y[4];
+        RdRect rc;
+        const int st = redact_quad(det + ((long long)blockIdx.y * max_det + r) * LP_DET_COLS, s, f.h0, f.w0, x, y, &rc);
+        if (st == 3 || rc.i0 >= rc.i1 || rc.j0 >= rc.j1) continue;
+        const int I0 = rc.i0 / GS_TILE, J0 = rc.j0 / GS_TILE, nJ = (rc.j1 - 1) / GS_TILE - J0 + 1;
+        const long long ntiles = (long long)((rc.i1 - 1) / GS_TILE - I0 + 1) * nJ;
+        for (long long t = sp; t < ntiles; t += RD_SPLIT) {
+            const int y0 = (I0 + (int)(t / nJ)) * GS_TILE, x0 = (J0 + (int)(t % nJ)) * GS_TILE;
+            const int th = y0 + GS_TILE < f.h0 ? GS_TILE : f.h0 - y0, tw = x0 + GS_TILE < f.w0 ? GS_TILE : f.w0 - x0;
+            SINK::gauss_tile(f, tp, y0, x0, th, tw, in, hq, out, table);
+        }
+    }
+}
+
 // The rules of one descriptor; an empty string: fine.
 std::string desc_fault(const lp_redact_desc& d) {
     if (d.format != 0 && d.format != 1) return "unknown format";
@@ -236,6 +392,55 @@ void launch_redact(const RdTable& tab, int nf, const float* det, const int32_t* 
     if (means) hipLaunchKernelGGL((redact_means_kernel<SINK>), grid, block, 0, st, tab, det, count, max_det, s, cell, (unsigned*)ws);
     else hipLaunchKernelGGL((redact_write_kernel<SINK>), grid, block, 0, st, tab, det, count, max_det, s, cell, fill,
                             (const unsigned*)(p.mode == 0 ? ws : nullptr), status);
+}
+
+// The rules of a tap vector t[0..radius]; an empty string: fine.
+std::string taps_fault(int radius, const uint16_t* t, const char* name) {
+    if (radius < 1 || radius > LP_REDACT_MAX_RADIUS) return std::string(name) + ": radius must be in 1..48";
+    long long total = t[0];
+    for (int k = 1; k <= radius; ++k) {
+        if (t[k] > t[k - 1]) return std::string(name) + " must not increase";
+        total += 2 * (long long)t[k];
+    }
+    if (total != 16384) return std::string(name) + ": t[0] + 2 * sum t[1..radius] must be 16384";
+    return "";
+}
+
+std::string gauss_params_fault(const lp_redact_gauss_params& p, bool nv12) {
+    if (!(p.margin >= 0.0 && p.margin <= 4.0)) return "margin must be in [0, 4]";
+    const std::string why = taps_fault(p.radius, p.taps, "taps");
+    if (!why.empty() || !nv12) return why;
+    return taps_fault(p.radius_c, p.taps_c, "taps_c");
+}
+
+bool any_nv12(const lp_redact_desc* desc, int n_frames) {
+    for (int b = 0; b < n_frames; ++b)
+        if (desc[b].format == 1) return true;
+    return false;
+}
+
+// dynamic LDS of redact_gauss_kernel<SINK> at these radii; *in_off: where the staged bytes start
+template <typename SINK>
+int gauss_lds_bytes(int R, int Rc, int* in_off) {
+    *in_off = GS_OUT_BYTES + SINK::gauss_hq_bytes(R, Rc);
+    return *in_off + SINK::gauss_in_bytes(R, Rc);
+}
+constexpr int GS_MAX_LDS = GS_OUT_BYTES + gs_hq_bytes(GS_TILE, LP_REDACT_MAX_RADIUS, 3) + gs_in_bytes(GS_TILE, LP_REDACT_MAX_RADIUS, 3);
+static_assert(GS_MAX_LDS <= 160 * 1024, "a tile at the largest radius must fit the LDS of a CU");
+
+template <typename SINK>
+int gauss_lds_attr() {
+    static std::atomic<unsigned long long> attr_done{0};
+    return set_max_lds_once(redact_gauss_kernel<SINK>, GS_MAX_LDS, attr_done, "redact gauss");
+}
+
+template <typename SINK>
+void launch_gauss(const RdTable& tab, int nf, const GsTaps& tp, const float* det, const int32_t* count, int max_det, double margin,
+                  void* ws, hipStream_t st) {
+    int in_off = 0;
+    const int lds = gauss_lds_bytes<SINK>(tp.r, tp.rc, &in_off);
+    hipLaunchKernelGGL((redact_gauss_kernel<SINK>), dim3(RD_WGS, (unsigned)nf), dim3(64, 4), (size_t)lds, st, tab, tp, det, count, max_det,
+                       1.0 + margin, in_off, (unsigned*)ws);
 }
 
 }  // namespace
@@ -292,6 +497,69 @@ extern "C" int lp_redact_plates_batch(const lp_redact_desc* desc, int n_frames, 
             int32_t* sb = status + (size_t)r.b0 * max_det;
             if (r.format == 1) launch_redact<Nv12Sink>(r.tab, r.nf, dt, count + r.b0, max_det, *p, fill, workspace, sb, pass == 0, st);
             else launch_redact<BgrSink>(r.tab, r.nf, dt, count + r.b0, max_det, *p, fill, workspace, sb, pass == 0, st);
+            LP_HIP_CHECK(hipGetLastError());
+        }
+    return LP_OK;
+}
+
+extern "C" size_t lp_redact_gauss_workspace_bytes(const lp_redact_desc* desc, int n_frames, const lp_redact_gauss_params* p) {
+    if (!desc || !p || n_frames < 1 || !gauss_params_fault(*p, any_nv12(desc, n_frames)).empty()) return 0;
+    long long entries = 0;
+    for (int b = 0; b < n_frames; ++b) {
+        if (desc[b].h0 < 1 || desc[b].w0 < 1) return 0;
+        entries += table_entries(desc[b], 1);
+    }
+    return (size_t)entries * 4;
+}
+
+extern "C" int lp_redact_gauss_batch(const lp_redact_desc* desc, int n_frames, const float* det, const int32_t* count, int max_det,
+                                     const lp_redact_gauss_params* p, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const std::string fn = "lp_redact_gauss_batch: ";
+    if (n_frames < 0 || !desc || !p || !status) return fail(LP_ERR_ARG, fn + "bad arguments (need desc, p, status, n_frames >= 0)");
+    if (max_det < 1) return fail(LP_ERR_ARG, fn + "max_det must be >= 1");
+    const std::string why = gauss_params_fault(*p, any_nv12(desc, n_frames));
+    if (!why.empty()) return fail(LP_ERR_ARG, fn + why);
+    for (int b = 0; b < n_frames; ++b) {       // every frame is checked before the first launch
+        const std::string bad = desc_fault(desc[b]);
+        if (!bad.empty()) return fail(LP_ERR_ARG, fn + bad + " (frame " + std::to_string(b) + ")");
+    }
+    if (n_frames == 0) return LP_OK;
+    if (!det || !count) return fail(LP_ERR_ARG, fn + "null det or count");
+    const size_t need = lp_redact_gauss_workspace_bytes(desc, n_frames, p);
+    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need)
+        return fail(LP_ERR_ARG, fn + "workspace must be 16-byte aligned and hold " + std::to_string(need) + " bytes");
+    hipStream_t st = (hipStream_t)stream;
+    const bool nv12 = any_nv12(desc, n_frames);
+    GsTaps tp = {};
+    tp.r = p->radius;
+    tp.rc = nv12 ? p->radius_c : 1;            // taps_c is read only with an NV12 frame
+    for (int i = 0; i <= 2 * tp.r; ++i) tp.w[i + GS_GROUP - 1] = p->taps[std::abs(i - tp.r)];
+    for (int i = 0; nv12 && i <= 2 * tp.rc; ++i) tp.wc[i + GS_GROUP - 1] = p->taps_c[std::abs(i - tp.rc)];
+    if (int rc = gauss_lds_attr<BgrSink>()) return rc;
+    if (int rc = nv12 ? gauss_lds_attr<Nv12Sink>() : LP_OK) return rc;
+    // a launch = a run of at most LP_FRAMES_PER_LAUNCH consecutive frames of one format
+    struct Run { int b0, nf, format; RdTable tab; };
+    std::vector<Run> runs;
+    long long off = 0;
+    for (int b = 0; b < n_frames; ++b) {
+        const lp_redact_desc& d = desc[b];
+        if (runs.empty() || runs.back().format != d.format || runs.back().nf == LP_FRAMES_PER_LAUNCH) runs.push_back({b, 0, d.format, {}});
+        Run& r = runs.back();
+        r.tab.f[r.nf++] = {d.p0, d.p1, d.pitch0, d.pitch1, d.h0, d.w0, off};
+        off += table_entries(d, 1);
+    }
+    lp_redact_params wp = {};                  // the write pass: the mosaic's, its table at cell 1
+    wp.mode = 0;
+    wp.cell = 1;
+    wp.margin = p->margin;
+    for (int pass = 0; pass < 2; ++pass)       // every tile is blurred before the first byte of a frame is replaced
+        for (const Run& r : runs) {
+            const float* dt = det + (size_t)r.b0 * max_det * LP_DET_COLS;
+            int32_t* sb = status + (size_t)r.b0 * max_det;
+            if (pass == 0 && r.format == 1) launch_gauss<Nv12Sink>(r.tab, r.nf, tp, dt, count + r.b0, max_det, p->margin, workspace, st);
+            else if (pass == 0) launch_gauss<BgrSink>(r.tab, r.nf, tp, dt, count + r.b0, max_det, p->margin, workspace, st);
+            else if (r.format == 1) launch_redact<Nv12Sink>(r.tab, r.nf, dt, count + r.b0, max_det, wp, 0u, workspace, sb, false, st);
+            else launch_redact<BgrSink>(r.tab, r.nf, dt, count + r.b0, max_det, wp, 0u, workspace, sb, false, st);
             LP_HIP_CHECK(hipGetLastError());
         }
     return LP_OK;

@@ -22,7 +22,7 @@ With ``nv12`` the frames travel as NV12 (``yolov6.utils.nv12``): decoded images 
 video decoder, ``.nv12`` sources are raw streams of packed frames; on a GPU the planes are uploaded (half the bytes of BGR) and
 read by the fused letterbox, a BGR frame exists on the device only where crops are cut; on the CPU every frame goes through
 ``nv12_to_bgr_np`` into the existing path.
-With ``redact`` every detection's plate is made unreadable in the frame itself, by a mosaic or a fill (``runtime.redact_plates`` on a
+With ``redact`` every detection's plate is made unreadable in the frame itself, by a mosaic, a fill or a Gaussian blur (``runtime.redact_plates`` on a
 GPU, in place on the device frames and behind everything that reads them; ``redact_plates_np`` on the CPU), and the frame is
 written to ``<save_dir>/redacted/``.  NV12 frames are redacted as NV12 and converted only to be saved.
 With ``redact_lookback`` = D every frame is redacted D frames late, so that the frames before a plate's first detection are
@@ -49,7 +49,7 @@ class Inferer:
     def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True, tile=None, tile_overlap=0.2,
                  tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5, best_shots=False,
                  nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1,
-                 redact_lookback=None, redact_lookback_max_back=None):
+                 redact_lookback=None, redact_lookback_max_back=None, redact_sigma=8.0):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -64,9 +64,9 @@ class Inferer:
         ``nv12`` = 'bt601' | 'bt709' | 'bt601f' | 'bt709f': send every frame as NV12 with that matrix (decoded images are encoded
         with ``bgr_to_nv12_np``, an odd last row or column cut off as a decoder would never deliver one); ``nv12_size`` = (w, h)
         of the frames of ``.nv12`` sources, which need ``nv12``.
-        ``redact`` = 'mosaic' | 'fill' (black): ``infer`` also writes every frame with the plates of its detections made unreadable
-        (``yolov6.utils.redact`` states the rules): the quad of every row, grown by ``redact_margin`` of its size about its centre,
-        in cells of ``redact_cell`` pixels (mosaic).
+        ``redact`` = 'mosaic' | 'fill' (black) | 'gauss': ``infer`` also writes every frame with the plates of its detections made
+        unreadable (``yolov6.utils.redact`` states the rules): the quad of every row, grown by ``redact_margin`` of its size about
+        its centre, in cells of ``redact_cell`` pixels (mosaic) or under a Gaussian of ``redact_sigma`` pixels, 0.5..16 (gauss).
         ``redact_hold`` (with ``track`` and ``redact``): a plate that is being tracked stays redacted in the frames in which
         the detector misses it, at the box and corners its track predicts, until the track ends (rule 11 of
         ``yolov6.utils.track``); a track needs ``redact_hold_min_hits`` detections before it is held.  The rows returned and
@@ -78,8 +78,9 @@ class Inferer:
         output is what it is without it."""
         self.__dict__.update(locals())
         if redact is not None:
-            from yolov6.utils.redact import check_params
-            check_params(redact, redact_cell, redact_margin)
+            from yolov6.utils.redact import check_params, check_sigma
+            if check_params(redact, redact_cell, redact_margin)[0] == 2:
+                self.redact_sigma = check_sigma(redact_sigma)
         if redact_hold and not (track and redact is not None):
             raise ValueError('redact_hold needs track=True and redact=MODE')
         if redact_lookback is not None:
@@ -354,7 +355,8 @@ class Inferer:
         if self.redact_hold:
             self._tracker.enable_hold(min_hits=self.redact_hold_min_hits)
         if self.redact_lookback is not None:
-            kw = dict(max_back=self.redact_lookback_max_back, mode=self.redact, cell=self.redact_cell, margin=self.redact_margin)
+            kw = dict(max_back=self.redact_lookback_max_back, mode=self.redact, cell=self.redact_cell, margin=self.redact_margin,
+                      sigma=self.redact_sigma)
             if self.device.type != 'cpu':
                 self._lookback = runtime.LookbackRedactor(self._tracker, self.redact_lookback, **kw)
             else:
@@ -521,7 +523,7 @@ class Inferer:
                     det[k, :len(d)] = d
                 count = torch.tensor([len(d) for d in dets], dtype=torch.int32).to(self.device)
             dev_frames = list(dev_frames)[:n]
-            runtime.redact_plates(dev_frames, det, count, self.redact, self.redact_cell, self.redact_margin)
+            runtime.redact_plates(dev_frames, det, count, self.redact, self.redact_cell, self.redact_margin, sigma=self.redact_sigma)
             self._redacted.extend(Nv12Frame(f.y.cpu().numpy(), f.uv.cpu().numpy(), f.matrix) if isinstance(f, Nv12Frame)
                                   else f.cpu().numpy() for f in dev_frames)
         else:
@@ -532,7 +534,8 @@ class Inferer:
                 det, count = np.zeros((n, m, 28), np.float32), [len(d) for d in dets]
                 for k, d in enumerate(dets):
                     det[k, :len(d)] = d.detach().float().cpu().numpy()
-            self._redacted.extend(redact_plates_np(list(frames), det, count, self.redact, self.redact_cell, self.redact_margin)[0])
+            self._redacted.extend(redact_plates_np(list(frames), det, count, self.redact, self.redact_cell, self.redact_margin,
+                                                   sigma=self.redact_sigma)[0])
 
     def _redact_delayed(self, frames, dev_frames=None):
         """With ``redact_lookback``: hand the group's frames to the delay line behind the group's tracker update and queue, with

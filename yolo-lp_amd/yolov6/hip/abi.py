@@ -33,6 +33,7 @@ LP_NV12_PER_LAUNCH = 32     # lp_preprocess_nv12_batch: slots per launch (its ta
 LP_MERGE_MAX_TILES, LP_MERGE_MAX_CANDIDATES = 64, 16384   # lp_merge_tiles: tiles per frame, tiles_of_frame * max_det_t
 LP_TRACK_MAX_TRACKS, LP_TRACK_MAX_DETS, LP_TRACK_MAX_CLS = 128, 128, 64   # lp_track_update: slots per stream, rows per frame, classes per head
 LP_REDACT_MAX_CELL = 64    # lp_redact_plates_batch: largest mosaic cell
+LP_REDACT_MAX_RADIUS = 48  # lp_redact_gauss_batch: largest blur radius (taps per side)
 LP_LOOKBACK_MAX_DEPTH = 32    # lp_lookback_update: frames of delay
 LP_EVAL_NCOUNTS = 43  # lp_eval_counts: length of the counts vector (include/lp_hip.h)
 
@@ -84,6 +85,12 @@ class RedactDesc(ctypes.Structure):
 class RedactParams(ctypes.Structure):
     """lp_redact_params"""
     _fields_ = [('mode', c_int), ('cell', c_int), ('margin', c_double), ('fill', ctypes.c_ubyte * 3)]
+
+
+class RedactGaussParams(ctypes.Structure):
+    """lp_redact_gauss_params"""
+    _fields_ = [('margin', c_double), ('radius', c_int), ('radius_c', c_int), ('taps', ctypes.c_uint16 * (LP_REDACT_MAX_RADIUS + 1)),
+                ('taps_c', ctypes.c_uint16 * (LP_REDACT_MAX_RADIUS + 1))]
 
 
 class TileRef(ctypes.Structure):
@@ -179,6 +186,9 @@ SYMBOLS = {
     'lp_redact_workspace_bytes': (c_size_t, [POINTER(RedactDesc), c_int, POINTER(RedactParams)]),
     'lp_redact_plates_batch': (c_int, [POINTER(RedactDesc), c_int, c_void_p, c_void_p, c_int, POINTER(RedactParams), c_void_p, c_void_p,
                                        c_size_t, c_void_p]),
+    'lp_redact_gauss_workspace_bytes': (c_size_t, [POINTER(RedactDesc), c_int, POINTER(RedactGaussParams)]),
+    'lp_redact_gauss_batch': (c_int, [POINTER(RedactDesc), c_int, c_void_p, c_void_p, c_int, POINTER(RedactGaussParams), c_void_p, c_void_p,
+                                      c_size_t, c_void_p]),
     'lp_lookback_state_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'lp_lookback_update': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                    POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1093,13 +1093,17 @@ def detect_frames_with_crops(model, frames, img_size, conf_thres, iou_thres, max
     return _unpad_with_crops(frames, det, count, crop_hw)
 
 
+#: redact_plates(mode='gauss'): the tables of one lp_redact_gauss_batch call stay under this many bytes (a 4K frame takes 33 MB)
+GAUSS_WS_CAP = 256 << 20
+
+
 def _redact_workspace(device, need):
     """The cell table of ``redact_plates`` on ``device``'s current stream, grown to ``need`` bytes (+ 256 for ``_aligned``); one per
     (device, stream), as ``_nms_workspace``.  It needs no zeroing: a call reads only entries it has written itself."""
     return _stream_workspace(_redact_ws, device, need)
 
 
-def redact_plates(frames, det, count, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0), status=None):
+def redact_plates(frames, det, count, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0), status=None, sigma=None):
     """Make the plates of B device frames unreadable IN PLACE (lp_redact_plates_batch, two launches per 64 frames on the current
     stream, no host read): ``frames`` is a list of contiguous uint8 CUDA [h,w,3] BGR tensors or of ``Nv12Frame`` with CUDA planes
     (one kind; NV12 is redacted in its own planes, no BGR copy exists), ``det`` [>= B,max_det,28] + ``count`` int32 on the device
@@ -1108,12 +1112,15 @@ def redact_plates(frames, det, count, mode='mosaic', cell=16, margin=0.1, fill=(
     corners are no convex quad of area >= 1, scaled by ``1 + margin`` about the centre.  ``mode`` 'mosaic': a pixel takes the mean of
     its ``cell`` x ``cell`` cell (even, 2..64; the grid is anchored to the frame, the means are of the frame before the call, so
     overlapping plates and the order of the rows do not matter); 'fill': ``fill`` = (B, G, R), converted with the frame's matrix
-    for NV12.  Writes into the caller's tensors and returns status [B,max_det] int32: 1 = corners, 2 = box, 3 = neither usable
+    for NV12; 'gauss': a pixel takes the frame as it was before the call under the integer Gaussian of ``sigma`` (0.5..16, None:
+    8.0; lp_redact_gauss_batch, whose table takes 4 bytes per frame pixel: the frames go in runs whose tables stay under
+    ``GAUSS_WS_CAP``), so the order of the rows and overlaps do not matter either, but a second call blurs again.
+    Writes into the caller's tensors and returns status [B,max_det] int32: 1 = corners, 2 = box, 3 = neither usable
     (nothing written), 0 = no such row.  yolov6.utils.redact.redact_plates_np is the same computation on the CPU, bit for bit.
 
     REDACTION GOES LAST: ``plate_crops``, ``PlateTracker.update_with_shots`` and the best-shot gallery must read the frames
     BEFORE this call on the same stream, or they cut mosaics."""
-    from yolov6.utils.redact import check_params, fill_bytes
+    from yolov6.utils.redact import check_params, check_sigma, fill_bytes
     if not frames:
         raise ValueError('redact_plates needs at least one frame')
     dev, nv12 = _frames_on(frames, 'redact_plates')
@@ -1130,6 +1137,10 @@ def redact_plates(frames, det, count, mode='mosaic', cell=16, margin=0.1, fill=(
         else:
             d.p0, d.p1, d.pitch0, d.format = f.data_ptr(), None, 3 * f.shape[1], 0
         d.h0, d.w0 = f.shape[0], f.shape[1]
+    if m == 2:
+        with torch.cuda.device(dev):
+            _redact_gauss(desc, [4 * f.shape[0] * f.shape[1] + 16 for f in frames], det, count, status, margin, check_sigma(sigma), dev)
+        return status
     # one call per run of frames that share the fill's bytes: a BGR list or a mosaic is one run, an NV12 fill one per matrix
     fills = [fill_bytes(fill, f.matrix if nv12 and m == 1 else None) for f in frames]
     lib, b0 = abi.load(), 0
@@ -1147,6 +1158,34 @@ def redact_plates(frames, det, count, mode='mosaic', cell=16, margin=0.1, fill=(
                       'lp_redact_plates_batch')
             b0 = b1
     return status
+
+
+def _gauss_params(margin, sigma):
+    """lp_redact_gauss_params of a public sigma: the taps of sigma for BGR and Y, of sigma / 2 for U and V."""
+    from yolov6.utils.redact import gauss_taps
+    t, tc = gauss_taps(sigma), gauss_taps(sigma / 2)
+    p = abi.RedactGaussParams(margin, len(t) - 1, len(tc) - 1)
+    p.taps[:len(t)] = [int(v) for v in t]
+    p.taps_c[:len(tc)] = [int(v) for v in tc]
+    return p
+
+
+def _redact_gauss(desc, table_bytes, det, count, status, margin, sigma, dev):
+    """lp_redact_gauss_batch over consecutive runs of the frames of ``desc`` whose tables (``table_bytes`` bounds each frame's) stay
+    under ``GAUSS_WS_CAP`` together, at least one frame per run: frames are independent, so the split does not show."""
+    lib, params, max_det = abi.load(), _gauss_params(margin, sigma), det.shape[1]
+    n, b0 = len(table_bytes), 0
+    while b0 < n:
+        b1, total = b0 + 1, table_bytes[b0]
+        while b1 < n and total + table_bytes[b1] <= GAUSS_WS_CAP:
+            total += table_bytes[b1]
+            b1 += 1
+        run = ctypes.cast(ctypes.byref(desc, b0 * ctypes.sizeof(abi.RedactDesc)), ctypes.POINTER(abi.RedactDesc))
+        need = lib.lp_redact_gauss_workspace_bytes(run, b1 - b0, ctypes.byref(params))
+        ws = _redact_workspace(dev, need)
+        abi.check(lib.lp_redact_gauss_batch(run, b1 - b0, _dptr(det[b0:b1]), _dptr(count[b0:b1]), max_det, ctypes.byref(params),
+                                            _dptr(status[b0:b1]), _aligned(ws), need, _stream_ptr(dev)), 'lp_redact_gauss_batch')
+        b0 = b1
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1523,7 +1562,7 @@ class LookbackRedactor(LookbackHost):
     (lp_lookback_update; ``yolov6.utils.lookback`` states the rule, and ``LookbackNp`` there is the same object on numpy).  It
     needs a ``PlateTracker`` with ``enable_hold`` called (RuntimeError otherwise).  ``max_back``: frames before the first detection
     that are covered (default ``depth``); ``back_cap``: back rows a stored frame can take (default ``max_tracks``); ``mode``,
-    ``cell``, ``margin``, ``fill``: as ``redact_plates``.
+    ``cell``, ``margin``, ``fill``, ``sigma``: as ``redact_plates``.
 
     ``push(frames, stream_of, flush)`` right after ``tracker.update(...)`` / ``update_with_shots(...)`` of the same frames
     enqueues lp_lookback_update on ``tracker.last_hold``, ``last_tid`` and ``slot_buffer`` and keeps REFERENCES to the frames per
@@ -1537,10 +1576,10 @@ class LookbackRedactor(LookbackHost):
     Crops and best shots read the frames at update time, before any redaction of them is enqueued, so the order rule
     "redaction goes last" holds by construction."""
 
-    def __init__(self, tracker, depth, max_back=None, back_cap=None, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0)):
+    def __init__(self, tracker, depth, max_back=None, back_cap=None, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0), sigma=None):
         if not isinstance(tracker, PlateTracker):
             raise TypeError('LookbackRedactor needs a PlateTracker (LookbackNp is the CPU form)')
-        self._init_host(tracker, depth, max_back, back_cap, mode, cell, margin, fill)
+        self._init_host(tracker, depth, max_back, back_cap, mode, cell, margin, fill, sigma)
         self.device = tracker.device
         self.state = None          # allocated by the first push: the entries' rows follow max_det
         self._rows = None
@@ -1628,7 +1667,7 @@ class LookbackRedactor(LookbackHost):
         return _persistent(self._status, (n, rows), lambda: torch.empty(n, rows, dtype=torch.int32, device=self.device))
 
     def _redact(self, frames, rel, tails, out):
-        kw = dict(mode=self.mode, cell=self.cell, margin=self.margin, fill=self.fill)
+        kw = dict(mode=self.mode, cell=self.cell, margin=self.margin, fill=self.fill, sigma=self.sigma)
         rel_det, rel_count, _, tail_det, tail_count, _ = out
         B, rows = rel_det.shape[:2]
         if rel:

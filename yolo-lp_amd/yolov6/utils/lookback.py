@@ -79,8 +79,8 @@ class LookbackHost:
     """The host side the two delay lines share: which frame leaves at which b follows from per-stream counters kept here, so
     nothing is read back.  A subclass gives ``_update`` (the rule, on its arrays) and ``_redact``."""
 
-    def _init_host(self, tracker, depth, max_back, back_cap, mode, cell, margin, fill):
-        from yolov6.utils.redact import check_params, fill_bytes
+    def _init_host(self, tracker, depth, max_back, back_cap, mode, cell, margin, fill, sigma=None):
+        from yolov6.utils.redact import check_params, check_sigma, fill_bytes
         if getattr(tracker, '_hold', None) is None:
             raise RuntimeError('call enable_hold() on the tracker first')
         self.tracker = tracker
@@ -89,6 +89,7 @@ class LookbackHost:
         check_params(mode, cell, margin)
         fill_bytes(fill)
         self.mode, self.cell, self.margin, self.fill = mode, int(cell), float(margin), tuple(int(v) for v in fill)
+        self.sigma = check_sigma(sigma) if mode == 'gauss' else sigma
         self._f = [0] * self.n_streams          # the host's copy of the counters f and base
         self._base = [0] * self.n_streams
         self._held = [dict() for _ in range(self.n_streams)]      # frame number -> the caller's frame, by reference
@@ -166,8 +167,8 @@ class LookbackNp(LookbackHost):
     constructor, ``push``, ``flush_all``, ``dropped`` and ``reset`` as ``yolov6.hip.runtime.LookbackRedactor``, on numpy arrays with
     ``redact_plates_np``; ``update`` is the rule alone."""
 
-    def __init__(self, tracker, depth, max_back=None, back_cap=None, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0)):
-        self._init_host(tracker, depth, max_back, back_cap, mode, cell, margin, fill)
+    def __init__(self, tracker, depth, max_back=None, back_cap=None, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0), sigma=None):
+        self._init_host(tracker, depth, max_back, back_cap, mode, cell, margin, fill, sigma)
         S, T, D = self.n_streams, self.max_tracks, self.depth
         self.f = np.zeros(S, np.int32)
         self.base = np.zeros(S, np.int32)
@@ -305,7 +306,7 @@ class LookbackNp(LookbackHost):
 
     def _redact(self, frames, rel, tails, out):
         from yolov6.utils.redact import redact_plates_np
-        kw = dict(mode=self.mode, cell=self.cell, margin=self.margin, fill=self.fill)
+        kw = dict(mode=self.mode, cell=self.cell, margin=self.margin, fill=self.fill, sigma=self.sigma)
         rel_det, rel_count, _, tail_det, tail_count, _ = out
         done = []
         if rel:

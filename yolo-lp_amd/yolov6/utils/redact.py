@@ -5,22 +5,33 @@ frame, or by a fill.  The quad of a row is the rule of the crops (``plate_crop.p
 convex quad of area >= 1, else the box), scaled by ``1 + margin`` about its centre.  A pixel belongs to a row iff its centre lies
 in the quad, edges included; a mosaic pixel takes the mean (rounded half up) of its cell OF THE FRAME AS IT WAS BEFORE THE CALL, so
 the result does not depend on the order of the rows, overlapping plates agree, and redacting twice changes only what the first pass changed.
+A gauss pixel takes G(frame) at that pixel: the frame AS IT WAS BEFORE THE CALL under the integer separable Gaussian of
+``gauss_blur_np`` (taps ``gauss_taps(sigma)``, replicate border).  G depends on the frame alone, so the order of the rows does not
+matter and overlapping plates agree here too; but a second call is NOT idempotent inside the mask: it blurs the blurred pixels again.
 
 BGR frames are uint8 [h, w, 3] arrays; an ``Nv12Frame`` is redacted in its own planes: the same cells on Y, cells of
-cell/2 x cell/2 samples on U and V, a chroma sample replaced iff any of its four luma pixels is.  The matrix plays no part, and the
-result is NOT the BGR result of the converted frame (a mean does not commute with the clamped conversion).
+cell/2 x cell/2 samples on U and V, a chroma sample replaced iff any of its four luma pixels is.  Gauss blurs Y with
+``gauss_taps(sigma)`` and U, V with ``gauss_taps(sigma / 2)`` on the half-resolution chroma plane, in chroma coordinates (the border
+clamp too).  The matrix plays no part, and the result is NOT the BGR result of the converted frame (neither a mean nor a blur
+commutes with the clamped conversion).
 
-The operations run in the kernel's order (fp64 geometry without fused multiply-adds, integer means), so this mirror and the
-kernels agree bit for bit.  It is the CPU path of ``Inferer(..., redact=...)`` and the checker of the kernels.
+The operations run in the kernel's order (fp64 geometry without fused multiply-adds, integer means, integer blur), so this
+mirror and the kernels agree bit for bit.  It is the CPU path of ``Inferer(..., redact=...)`` and the checker of the kernels.
 """
+import math
+
 import numpy as np
 
 from yolov6.utils.nv12 import Nv12Frame, bgr_to_nv12_np, is_nv12_list
 from yolov6.utils.plate_crop import ST_EMPTY, plate_quad
 
-MODES = ('mosaic', 'fill')
+MODES = ('mosaic', 'fill', 'gauss')
 MAX_CELL = 64
 MAX_MARGIN = 4.0
+MAX_RADIUS = 48                # LP_REDACT_MAX_RADIUS: ceil(3 * MAX_SIGMA)
+MIN_SIGMA, MAX_SIGMA = 0.5, 16.0
+DEFAULT_SIGMA = 8.0
+TAP_ONE = 16384                # the taps of a blur sum to 2^14
 EDGE_ORDER = (0, 3, 2, 1)      # p0 -> p3 -> p2 -> p1 (-> p0): the label orientation TL -> BL -> BR -> TR
 
 
@@ -34,6 +45,55 @@ def check_params(mode, cell, margin):
     if not 0.0 <= margin <= MAX_MARGIN:
         raise ValueError('margin %r: need 0 <= margin <= %g' % (margin, MAX_MARGIN))
     return MODES.index(mode), cell, margin
+
+
+def check_sigma(sigma):
+    """The sigma of a gauss redaction as a float (None: 8.0), or a ValueError outside [0.5, 16] (a NaN included)."""
+    sigma = DEFAULT_SIGMA if sigma is None else float(sigma)
+    if not MIN_SIGMA <= sigma <= MAX_SIGMA:
+        raise ValueError('sigma %r: need %g <= sigma <= %g' % (sigma, MIN_SIGMA, MAX_SIGMA))
+    return sigma
+
+
+def gauss_taps(sigma):
+    """int32 [R + 1]: the taps q[0..R] of the integer Gaussian of ``sigma`` in [0.25, 16] (the chroma planes take half the
+    public sigma), R = ceil(3 sigma) <= 48.  From g[k] = exp(-k^2 / (2 sigma^2)) and S = g[0] + 2 sum g[1..R] in float64:
+    q[k] = floor(16384 g[k] / S + 0.5) for k >= 1 and q[0] = 16384 - 2 sum q[1..R], so q[0] + 2 sum q[1..R] is 16384 exactly.
+    The taps are data: no device evaluates an exponential."""
+    sigma = float(sigma)
+    if not MIN_SIGMA / 2 <= sigma <= MAX_SIGMA:
+        raise ValueError('sigma %r: gauss_taps needs %g <= sigma <= %g' % (sigma, MIN_SIGMA / 2, MAX_SIGMA))
+    R = int(math.ceil(3.0 * sigma))
+    g = [math.exp(-(k * k) / (2.0 * sigma * sigma)) for k in range(R + 1)]
+    S = g[0] + 2.0 * sum(g[1:])
+    q = [0] + [int(math.floor(TAP_ONE * g[k] / S + 0.5)) for k in range(1, R + 1)]
+    q[0] = TAP_ONE - 2 * sum(q[1:])
+    return np.asarray(q, np.int32)
+
+
+def gauss_blur_np(plane, taps):
+    """uint8 array of ``plane``'s shape ([h, w] or [h, w, C]; the channels are blurred separately): the separable integer blur
+    with the taps q[0..R], indices clamped to the plane (replicate border).  Horizontal:
+    hq = (sum_k q[|k|] p[i, clamp(j + k)] + 32) >> 6 (at most 65280: 16 bits); vertical:
+    out = (sum_k q[|k|] hq[clamp(i + k), j] + 2^21) >> 22 (the sum stays below 2^31).  A constant plane comes out unchanged."""
+    plane = np.asarray(plane)
+    q = [int(t) for t in np.asarray(taps).reshape(-1)]
+    R = len(q) - 1
+    if plane.dtype != np.uint8 or plane.ndim not in (2, 3) or R < 1 or q[0] + 2 * sum(q[1:]) != TAP_ONE or min(q) < 0:
+        raise ValueError('gauss_blur_np needs a uint8 [h, w] or [h, w, C] plane and taps q[0..R >= 1] >= 0 with q[0] + 2 sum q[1..R] = %d'
+                         % TAP_ONE)
+    h, w = plane.shape[:2]
+    ii = np.clip(np.arange(-R, h + R), 0, h - 1)
+    jj = np.clip(np.arange(-R, w + R), 0, w - 1)
+    p = plane.astype(np.int64)[:, jj]                                   # [h, w + 2R, ...]
+    acc = q[0] * p[:, R:R + w]
+    for k in range(1, R + 1):
+        acc += q[k] * (p[:, R - k:R - k + w] + p[:, R + k:R + k + w])
+    hq = ((acc + 32) >> 6)[ii]                                          # [h + 2R, w, ...]
+    acc = q[0] * hq[R:R + h]
+    for k in range(1, R + 1):
+        acc += q[k] * (hq[R - k:R - k + h] + hq[R + k:R + k + h])
+    return ((acc + (1 << 21)) >> 22).astype(np.uint8)
 
 
 def fill_bytes(fill, matrix=None):
@@ -113,10 +173,13 @@ def cell_means(plane, cell):
     return np.repeat(np.repeat(val, cell, axis=0), cell, axis=1)[:h, :w]
 
 
-def redact_frame_np(frame, rows, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0)):
+def redact_frame_np(frame, rows, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0), sigma=None):
     """One frame: (redacted copy, status int32 [len(rows)]).  ``frame``: uint8 [h, w, 3] BGR, or an ``Nv12Frame`` with host
-    planes (the result is a new packed ``Nv12Frame``); ``rows`` [n, >= 12] fp32 in frame pixels; ``fill`` = (B, G, R)."""
+    planes (the result is a new packed ``Nv12Frame``); ``rows`` [n, >= 12] fp32 in frame pixels; ``fill`` = (B, G, R);
+    ``sigma``: of the gauss mode (None: 8.0), ignored by the others as ``cell`` is by fill."""
     m, cell, margin = check_params(mode, cell, margin)
+    if m == 2:
+        sigma = check_sigma(sigma)
     rows = np.asarray(rows, np.float32)
     if rows.size == 0:
         rows = rows.reshape(0, 12)
@@ -128,6 +191,10 @@ def redact_frame_np(frame, rows, mode='mosaic', cell=16, margin=0.1, fill=(0, 0,
         if m == 0:
             out.y[mask] = cell_means(out.y, cell)[mask]
             out.uv[cmask] = cell_means(out.uv, cell // 2)[cmask]
+        elif m == 2:
+            if mask.any():
+                out.y[mask] = gauss_blur_np(out.y, gauss_taps(sigma))[mask]
+                out.uv[cmask] = gauss_blur_np(out.uv, gauss_taps(sigma / 2))[cmask]
         else:
             out.y[mask] = fy
             out.uv[cmask] = (fu, fv)
@@ -137,17 +204,23 @@ def redact_frame_np(frame, rows, mode='mosaic', cell=16, margin=0.1, fill=(0, 0,
         raise ValueError('frame must be a uint8 [h, w, 3] array, got %s %s' % (frame.dtype, frame.shape))
     out = frame.copy()
     status, mask = frame_mask(rows, frame.shape[0], frame.shape[1], margin)
-    out[mask] = cell_means(out, cell)[mask] if m == 0 else fill_bytes(fill)
+    if m == 2:
+        if mask.any():
+            out[mask] = gauss_blur_np(out, gauss_taps(sigma))[mask]
+    else:
+        out[mask] = cell_means(out, cell)[mask] if m == 0 else fill_bytes(fill)
     return out, status
 
 
-def redact_plates_np(frames, det, count, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0)):
-    """The specification of ``lp_redact_plates_batch``: ``frames`` a list of B uint8 [h, w, 3] BGR arrays or of B ``Nv12Frame``
+def redact_plates_np(frames, det, count, mode='mosaic', cell=16, margin=0.1, fill=(0, 0, 0), sigma=None):
+    """The specification of ``lp_redact_plates_batch`` and, for ``mode`` 'gauss' (``sigma`` in [0.5, 16], None: 8.0), of
+    ``lp_redact_gauss_batch``: ``frames`` a list of B uint8 [h, w, 3] BGR arrays or of B ``Nv12Frame``
     with host planes (one kind), ``det`` [>= B, max_det, 28] and ``count`` [>= B] as the padded detectors return them, in frame
     pixels.  Rows r < clamp(count[b], 0, max_det) of frame b are redacted; ``fill`` is (B, G, R), converted with the frame's
     matrix for NV12.  Returns (frames_out, status): new frames of the same kind (the inputs are not written) and int32
     [B, max_det] with 1 = corners, 2 = box, 3 = neither usable (nothing written), 0 = no such row."""
-    check_params(mode, cell, margin)
+    if check_params(mode, cell, margin)[0] == 2:
+        sigma = check_sigma(sigma)
     frames = list(frames)
     is_nv12_list(frames)
     det = np.asarray(det, np.float32)
@@ -160,6 +233,6 @@ def redact_plates_np(frames, det, count, mode='mosaic', cell=16, margin=0.1, fil
     out = []
     for b, f in enumerate(frames):
         n = max(0, min(int(count[b]), max_det))
-        o, status[b, :n] = redact_frame_np(f, det[b, :n], mode, cell, margin, fill)
+        o, status[b, :n] = redact_frame_np(f, det[b, :n], mode, cell, margin, fill, sigma)
         out.append(o)
     return out, status
