@@ -668,3 +668,47 @@ def tie_runs(keep, order_ties):
             runs.append((start, i + 1))
             start = i + 1
     return runs
+
+
+# ---- the bilinear resize by its definition, and the bar of the 8-bit fixed-point scheme against it ------------------------------
+# (tests/test_letterbox_cpu.py, tests/test_letterbox_gpu.py)
+def _axis64(dst, src, coord=None):
+    """Per destination index of one axis: the two neighbours and the weight of the second, in float64.  ``coord(d, src, dst)``
+    gives the source coordinate; the default is the definition, pixel centres at half-integers: (d + 0.5) * src / dst - 0.5.
+    The coordinate is clamped to [0, src - 1] (replicate border)."""
+    d = np.arange(dst, dtype=np.float64)
+    c = (d + 0.5) * src / dst - 0.5 if coord is None else coord(d, src, dst)
+    c = np.clip(c, 0.0, float(src - 1))
+    i0 = np.floor(c).astype(np.int64)
+    return i0, np.minimum(i0 + 1, src - 1), c - i0
+
+
+def bilinear64(im_u8, new_wh, coord=None):
+    """uint8 [h, w, C] (or [h, w]) -> float64 [nh, nw, C], unrounded: bilinear interpolation written from its definition (half-pixel
+    centres, replicate border, a linear blend of the two neighbours per axis).  No fixed point, no 11-bit weights; nothing of
+    ``data_augment`` is used.  ``coord``: another coordinate rule, for the deliberately wrong resizes of the tests."""
+    im = np.asarray(im_u8).astype(np.float64)
+    if im.ndim == 2:
+        im = im[:, :, None]
+    h, w = im.shape[:2]
+    nw, nh = int(new_wh[0]), int(new_wh[1])
+    y0, y1, ty = _axis64(nh, h, coord)
+    x0, x1, tx = _axis64(nw, w, coord)
+    if nh * w <= h * nw:                                     # the smaller intermediate first; the blend is separable
+        rows = im[y0] * (1.0 - ty)[:, None, None] + im[y1] * ty[:, None, None]
+        return rows[:, x0] * (1.0 - tx)[None, :, None] + rows[:, x1] * tx[None, :, None]
+    cols = im[:, x0] * (1.0 - tx)[None, :, None] + im[:, x1] * tx[None, :, None]
+    return cols[y0] * (1.0 - ty)[:, None, None] + cols[y1] * ty[:, None, None]
+
+
+def linear_u8_bar(src_hw):
+    """(lo, hi): the interval that (8-bit fixed-point INTER_LINEAR result) - (float64 bilinear) must stay in, in grey levels, for
+    a source of ``src_hw``; derived from the scheme, not measured (the derivation: tests/test_letterbox_cpu.py).
+      weights   per axis the second weight is rint(f * 2048) with a0 + a1 = 2048, f the fraction of the float32 coordinate:
+                |a1 / 2048 - f_true| <= 0.5 / 2048 + (half a float32 ulp of the coordinate, at most spacing(src) / 2); a blend
+                of two values in 0..255 moves by at most 255 times that, and the vertical blend of two such rows adds its own
+      >> 4      loses less than 1/128 level in all (the two rows' losses are weighted by b0 + b1 = 2048)
+      >> 16     twice, each loses less than 1/4 level
+      (+2) >> 2 of an integer number of quarter levels: the result minus the quarter-level value is one of 0, -1/4, +1/4, +1/2"""
+    w = sum(255.0 * (0.5 / 2048 + float(np.spacing(np.float32(s))) / 2) for s in src_hw)
+    return -(0.25 + 0.5 + 1.0 / 128 + w) - 1e-9, 0.5 + w + 1e-9

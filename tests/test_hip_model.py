@@ -949,7 +949,8 @@ def test_gather_detections_rccl_on_side_stream():
                                          (300, 500, [320, 416]), (2000, 1500, [640, 640])])
 @pytest.mark.parametrize('dtype', [torch.float32, torch.float16])
 def test_preprocess_letterbox_matches_host_mirror(h0, w0, size, dtype):
-    """lp_preprocess_letterbox == the host mirror's letterbox + transpose + /255 (bit-exact: same integer bilinear)."""
+    """lp_preprocess_letterbox == the host mirror's letterbox + transpose + /255 (bit-exact: same integer bilinear).  bfloat16,
+    which Inferer.precess_image does not produce, and the kernels' edge shapes: tests/test_letterbox_gpu.py."""
     from yolov6.hip.runtime import preprocess_letterbox
     from yolov6.core.inferer import Inferer
     rng = np.random.default_rng(h0 + w0)

@@ -42,7 +42,10 @@ template <typename K> inline int set_max_lds_once(K kernel, int bytes, std::atom
 }
 
 // Per-axis coefficients of the OpenCV INTER_LINEAR fixed-point resize (preprocess_kernel, letterbox_kernel): source index and the
-// two 11-bit weights of destination index d at scale src/dst.
+// two 11-bit weights of destination index d at scale src/dst.  resize_coef and resize_blend are, bit for bit, _linear_coef and
+// resize_linear_u8 of yolov6/data/data_augment.py, which the suite pins to the float64 definition of bilinear interpolation within
+// [-(3/4 + 1/128 + w), 1/2 + w] levels, w = 255 (1/4096 + half a float32 ulp of the coordinate) per axis (DESIGN.md 4.2.1;
+// tests/test_letterbox_cpu.py, tests/test_letterbox_gpu.py).  Parity with cv2 itself is not testable where OpenCV is absent.
 __device__ __forceinline__ void resize_coef(int d, double scale, int src, int* s0, int* a0, int* a1) {
     // cv::resize: fx = (dx + 0.5) * scale - 0.5 ; sx = floor(fx) ; fx -= sx ; clamps at the borders
     float f = (float)((d + 0.5) * scale - 0.5);

@@ -6,8 +6,11 @@
 //                              of every detection row.
 // The bilinear resize is the fixed-point scheme of OpenCV's INTER_LINEAR for 8-bit images (11-bit coefficients,
 // horizontal then vertical pass, the (>>4, >>16, +2, >>2) rounding of VResizeLinear) -- restated from the published
-// algorithm; OpenCV is not installed in this image, so against cv2 itself this is "parity unpinned".  The host
-// mirror (yolov6/data/data_augment.py) implements the same integer arithmetic in numpy and the two are bit-exact.
+// algorithm.  The host mirror (yolov6/data/data_augment.py) implements the same integer arithmetic in numpy; it is
+// pinned to the float64 definition of bilinear interpolation within a derived bar (tests/test_letterbox_cpu.py), and
+// this kernel equals it bit for bit at the edge shapes of tests/test_letterbox_gpu.py (1-pixel sources, clamped
+// runs, ratio 1, a 21x reduction, source columns beyond 4096; fp32, fp16, bf16).  Parity with cv2 itself cannot be
+// tested here: OpenCV is not installed and no fixture of its output exists.
 #include "lp_internal.h"
 
 namespace lp {

@@ -3,10 +3,18 @@ yolov6/data/data_augment.py:30-61).  The reference resizes with
 ``cv2.resize(INTER_LINEAR)``; OpenCV is not installed in this image, so when it is
 missing the resize is ``resize_linear_u8`` below: OpenCV's fixed-point scheme for
 8-bit images (11-bit coefficients, horizontal pass, then the ``>>4, >>16, +2, >>2``
-vertical pass) restated in numpy integer arithmetic from the published algorithm --
-"parity unpinned" against cv2 itself, bit-exact against the HIP kernel
-``lp_preprocess_letterbox`` (tests/test_hip_model.py).  Pre-processing is a next-row
-item, not part of the measured hot path."""
+vertical pass) restated in numpy integer arithmetic from the published algorithm.
+What holds for it:
+  - it is pinned to the float64 definition of bilinear interpolation (half-pixel
+    centres, replicate border) within a bar derived from the scheme, about
+    [-0.89, +0.63] grey levels, and never more than one level from the rounded
+    definition (tests/test_letterbox_cpu.py);
+  - the HIP kernels ``lp_preprocess_letterbox``, ``lp_preprocess_tiles_batch`` and
+    ``lp_preprocess_nv12_batch`` equal it bit for bit at the shapes where their
+    tiling, stores and clamps change (tests/test_letterbox_gpu.py);
+  - parity with cv2 itself cannot be tested here: the library is absent and no
+    fixture of its output exists.
+Pre-processing is a next-row item, not part of the measured hot path."""
 import numpy as np
 
 try:
