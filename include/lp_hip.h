@@ -718,6 +718,50 @@ int lp_lookback_update(void* state, int n_streams, int max_tracks, int depth, in
                        float* rel_det, int32_t* rel_count, int32_t* rel_frame,
                        float* tail_det, int32_t* tail_count, int32_t* tail_frame, void* stream);
 
+/* lp_watch_match: look the reads of the tracks that ended in a tracker call up in a device-resident watchlist (stolen vehicles,
+ * permits, subscribers), tolerating misreads: a weighted Hamming distance over the eight heads that charges less for a position the
+ * vote itself was unsure about and for pairs of characters listed as confusable.  Called right behind lp_track_update (any of its
+ * forms) on the same stream; all pointers are DEVICE pointers; nothing is uploaded or read back, nothing is allocated, capturable
+ * in a graph.  The reference has nothing here; yolov6/utils/watch.py::watch_match_np restates the rules below on every int32.
+ *   entries: uint8 [n_entries,8], 8-byte aligned, 0 <= n_entries <= LP_WATCH_MAX_ENTRIES, one row per plate, one id per head: 0..63
+ *   a class id, 255 the wildcard (the position is not compared), 64..254 match nothing (the host constructors refuse them; the
+ *   kernel treats them as a mismatch of weight 16).
+ *   confuse: uint8 [3,64,64] in sixteenths, 0..16 (larger values are read as 16), 4-byte aligned, or NULL for 16 everywhere; group
+ *   0 is head 0, group 1 head 1, group 2 heads 2..7; the row is the read id, the column the entry id; the diagonal is never read.
+ *   ended_i, ended_f [n_streams,max_ended,12], ended_count [n_streams]: as lp_track_update left them.  The reads are, per stream s,
+ *   the lines j < min(max(ended_count[s], 0), max_ended): best[p] = ended_i[s][j][4 + p], share[p] = ended_f[s][j][p].
+ * Per read, entry e and position p, w = entries[e][p]:
+ *   1. q_p = share[p] > 0 ? min((int)(share[p] * 255.0f), 255) + 1 : 1 (the fp32 product, truncated; false for NaN): 1..256;
+ *   2. w == 255: cost 0, no mismatch; 0 <= best[p] < 64 and w == best[p]: cost 0, no mismatch; otherwise one mismatch of cost
+ *      q_p * c, c = confuse[g(p)][best[p]][w] when best[p] and w are both in 0..63, else 16;
+ *   3. mism(e) and cost(e) are the int32 sums over the eight positions (cost <= 8 * 256 * 16 = LP_WATCH_MAX_COST); e is accepted iff
+ *      mism(e) <= max_mismatch and cost(e) <= max_cost.
+ *   match_i: int32 [n_streams,max_ended,4], line-parallel to ended_i: (entry, mismatches, cost, n_hits) = the accepted entry with
+ *   the smallest (cost, index), its two sums, and the number of accepted entries (above 1: ambiguous; duplicates count, the lowest
+ *   index wins).  (-1, 0, 0, 0) for a line without an accepted entry, for every line at or past its stream's count and for every
+ *   line when n_entries == 0.  Every line is written by every call.  All reductions are an unsigned minimum or an integer sum: the
+ *   result does not depend on the order of the workgroups.
+ * Three launches: a one-workgroup kernel numbers the valid reads (a prefix sum over the clamped counts) and clears their keys; the
+ * scan, one workgroup per LP_WATCH_BLOCK_ENTRIES entries, holds its entries in registers (the list is read from memory once per
+ * call) and walks the reads in blocks of LP_WATCH_QUERY_BLOCK, each block through an LDS table (position, entry id, read) ->
+ * (cost, mismatch), then one atomic minimum and one atomic add per workgroup and read with a hit; a tail kernel writes match_i.
+ * max_ended == 0 launches nothing; n_entries == 0 launches the tail alone.
+ *   workspace: 16-byte aligned, lp_watch_workspace_bytes(n_streams, max_ended) bytes; it may hold anything on entry.
+ * What it does not do: no insertions or deletions; no alert while a track is live (ended records only); one best entry plus a count,
+ * not a ranked list; no update in place of the list.
+ * Every argument is checked before the first launch (LP_ERR_ARG, nothing launched): n_entries outside 0..LP_WATCH_MAX_ENTRIES,
+ * n_streams < 1, max_ended < 0, n_streams * max_ended * 12 at or above 2^31, max_mismatch outside 0..8, max_cost outside
+ * 0..LP_WATCH_MAX_COST; with max_ended > 0: ended_count or match_i null; with n_entries > 0 as well: entries, ended_i, ended_f or the
+ * workspace null, the three alignments, a workspace that is too small; match_i or the workspace overlapping an input or each other. */
+#define LP_WATCH_MAX_ENTRIES (1 << 24)
+#define LP_WATCH_MAX_COST 32768
+#define LP_WATCH_BLOCK_ENTRIES 2048   /* entries per workgroup of the scan: 256 lanes x 8 */
+#define LP_WATCH_QUERY_BLOCK 16       /* reads per LDS table */
+size_t lp_watch_workspace_bytes(int n_streams, int max_ended);   /* 0: bad arguments */
+int lp_watch_match(const unsigned char* entries, int n_entries, const unsigned char* confuse /* NULL: all 16 */,
+                   const int32_t* ended_i, const float* ended_f, const int32_t* ended_count, int n_streams, int max_ended,
+                   int max_mismatch, int max_cost, int32_t* match_i, void* workspace, size_t workspace_bytes, void* stream);
+
 /* lp_eval_counts: the matching loops of Evaler.eval (yolov6/core/evaler.py:153-243, box_iou general.py:93-115) for a
  * batch of images, one workgroup per image.
  *   det [B,max_det,28] fp32 + det_count [B]: detections as lp_nms returns them (xyxy, 8 corner coords, 8 confs, 8 ids)

@@ -6,6 +6,7 @@
     python tools/frames_bench.py --tile [--tile-baseline] [--tile-frame 2160 3840] [--tile-size 640] [--tile-overlap 128]
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot] [--redact [--hold [--lookback D]]] [--nv12]
+                                 [--watch N [--watch-mismatch 1]]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
@@ -102,6 +103,10 @@ def parse():
                                                         'and the redaction along its rows')
     ap.add_argument('--lookback', type=int, default=0, metavar='D', help='with --track --redact --hold: also time the look-back delay of '
                                                                          'that depth (LookbackRedactor) behind the update with the hold')
+    ap.add_argument('--watch', type=int, default=0, metavar='N', help='with --track: also time the lookup of the ended reads in a seeded '
+                                                                      'random watchlist of N entries (lp_watch_match); every stream is '
+                                                                      'flushed once per step so that there are reads')
+    ap.add_argument('--watch-mismatch', type=int, default=1, help='with --watch: positions that may differ')
     ap.add_argument('--nv12', nargs='?', const='bt709', default=None, choices=['bt601', 'bt709', 'bt601f', 'bt709f'], metavar='MATRIX',
                     help='also send the same seeded frames as NV12 with this matrix and compare (default matrix: bt709)')
     ap.add_argument('--runs', type=int, default=3, help='timed runs of the frames/s figures (the spread is reported)')
@@ -340,6 +345,8 @@ def track_mode(args, model, dev, tdt):
             out['best_shot'] = best_shot_stages(args, model, dev, tdt, frames, x, (H, W))
         if args.redact:
             out['redact'] = redact_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
+        if args.watch:
+            out['watch'] = watch_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
 
         # the full case: 128 live tracks x 128 rows per stream, every pair above the threshold
         full = runtime.PlateTracker(B, max_tracks=128, max_age=0, ncls=model, device=dev)
@@ -362,6 +369,50 @@ def track_mode(args, model, dev, tdt):
         out['full_128x128_ms'] = round(float(np.median(ms[1:])), 4)
         out['full_128x128_matched'] = int((tid >= 0).sum())
     print(json.dumps(out))
+
+
+def watch_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
+    """--track --watch N: device time of lp_watch_match behind the update, from events on one stream.  The list is seeded and
+    random (ids within the model's head widths); every step flushes every stream, so the tracks the step began end in it and
+    their reads are looked up (``reads_per_step``).  ``block_ms`` is the same call on exactly one query block of synthetic reads:
+    the scan's cost per pass over the list, whatever the detector finds."""
+    import torch
+    from yolov6.hip import abi, runtime
+    from yolov6.utils.track import ncls_of
+    size, stride = [args.size, args.size], int(model.stride.max())
+    B, conf, iou, max_det = args.track_batch, args.conf, args.iou, args.max_det
+    N, QB = args.watch, abi.LP_WATCH_QUERY_BLOCK
+    rng = np.random.default_rng(1)
+    ncls = ncls_of(model)
+    wl = runtime.Watchlist(np.stack([rng.integers(0, n, N, dtype=np.uint8) for n in ncls], 1), device=dev)
+    trk = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
+    # one query block of synthetic reads on one stream
+    bi, bf = np.zeros((1, QB, 12), np.int32), np.zeros((1, QB, 12), np.float32)
+    bi[0, :, 4:], bf[0, :, :8] = np.stack([rng.integers(0, n, QB) for n in ncls], 1), rng.random((QB, 8))
+    block = [torch.from_numpy(a).to(dev) for a in (bi, bf, np.array([QB], np.int32))]
+    ms, block_ms, reads = [], [], []
+    for k in range(args.reps + 2):
+        frames = batcher.put([pool[(j + k) % len(pool)] for j in range(B)])
+        xx, _ = runtime.preprocess_frames(frames, size, stride, tdt, batch=B, out=x)
+        det, count, _ = runtime.detect_padded(model, xx, conf, iou, max_det)
+        runtime.rescale_round_batch(det, count, net_hw, [f.shape for f in frames])
+        ended_i, ended_f, ended_count = trk.update(det, count, flush=[1] * B)[2:]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+        wl.match(ended_i, ended_f, ended_count, args.watch_mismatch)
+        ev[1].record()
+        ev[2].record()
+        wl.match(*block, args.watch_mismatch)
+        ev[3].record()
+        torch.cuda.synchronize()
+        if k >= 2:
+            ms.append(ev[0].elapsed_time(ev[1]))
+            block_ms.append(ev[2].elapsed_time(ev[3]))
+            reads.append(int(ended_count.clamp(0, ended_i.shape[1]).sum()))
+    med, bmed, nreads = float(np.median(ms)), float(np.median(block_ms)), float(np.mean(reads))
+    return dict(entries=N, max_mismatch=args.watch_mismatch, reps=args.reps, watch_ms=round(med, 4), reads_per_step=round(nreads, 1),
+                pairs_per_s=round(N * nreads / (med * 1e-3), 1), block_reads=QB, block_ms=round(bmed, 4),
+                block_pairs_per_s=round(N * QB / (bmed * 1e-3), 1), block_list_bytes_per_s=round(N * 8 / (bmed * 1e-3), 1))
 
 
 def redact_stages(args, model, dev, tdt, batcher, pool, x, net_hw):

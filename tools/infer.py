@@ -8,6 +8,8 @@
                           [--nv12 bt601|bt709|bt601f|bt709f [--nv12-size W H]]
                           [--redact mosaic|fill|gauss [--redact-cell 16] [--redact-sigma 8] [--redact-margin 0.1]
                            [--redact-hold [--redact-hold-min-hits 1] [--redact-lookback D [--redact-lookback-max-back N]]]]
+                          [--track --watchlist FILE [--watch-mismatch 1] [--watch-cost F]
+                           [--watch-confusable "0D 0Q 8B 2Z 5S" [--watch-confusable-weight 4]]]
 """
 import argparse
 import os
@@ -79,6 +81,16 @@ _FLAGS = [
                                     'plate\'s first detection are covered too, where its first two detections extrapolate it')),
     ('--redact-lookback-max-back', dict(type=int, default=None, metavar='N',
                                         help='with --redact-lookback: frames before the first detection that are covered (default D)')),
+    ('--watchlist', dict(type=str, default=None, metavar='FILE',
+                         help='with --track: look the read of every ended track up in this list (one plate per line: the plate text with * '
+                              'or ? for any character, or eight ids with * for any) and write hits.txt beside plates.txt')),
+    ('--watch-mismatch', dict(type=int, default=1, help='with --watchlist: positions that may differ (0..8)')),
+    ('--watch-cost', dict(type=float, default=None, metavar='F',
+                          help='with --watchlist: largest total cost of the differing positions, in fully confident mismatches (a position '
+                               'the vote was unsure about costs less; default: no limit)')),
+    ('--watch-confusable', dict(type=str, default=None, metavar='PAIRS',
+                                help='with --watchlist: pairs of characters that are misread for each other, e.g. "0D 0Q 8B 2Z 5S"')),
+    ('--watch-confusable-weight', dict(type=int, default=4, help='with --watch-confusable: what such a pair costs, in sixteenths of a mismatch (0..16)')),
 ]
 
 
@@ -99,7 +111,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         tile=None, tile_overlap=0.2, no_tile_overview=False, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3,
         track_expand=0.5, best_shots=False, nv12=None, nv12_size=None, redact=None, redact_cell=16,
         redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1, redact_lookback=None, redact_lookback_max_back=None,
-        redact_sigma=8.0):
+        redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None, watch_confusable=None, watch_confusable_weight=4):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track or redact) and not osp.exists(out_dir):
@@ -115,7 +127,9 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
                       track_iou=track_iou, track_expand=track_expand, best_shots=best_shots, nv12=nv12, nv12_size=nv12_size,
                       redact=redact, redact_cell=redact_cell, redact_margin=redact_margin, redact_hold=redact_hold,
                       redact_hold_min_hits=redact_hold_min_hits, redact_lookback=redact_lookback,
-                      redact_lookback_max_back=redact_lookback_max_back, redact_sigma=redact_sigma).infer(
+                      redact_lookback_max_back=redact_lookback_max_back, redact_sigma=redact_sigma, watchlist=watchlist,
+                      watch_mismatch=watch_mismatch, watch_cost=watch_cost, watch_confusable=watch_confusable,
+                      watch_confusable_weight=watch_confusable_weight).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

@@ -1,0 +1,319 @@
+// Matching the reads of ended plate tracks against a device-resident watchlist: lp_watch_match (include/lp_hip.h).  A weighted
+// Hamming distance over the eight heads, N entries x Q reads, behind lp_track_update's ended records.  The reference has nothing
+// here; the written-down specification is yolov6/utils/watch.py (watch_match_np), which these kernels match on every int32
+// (tests/test_watch_gpu.py).  Everything is integer except one fp32 product per read and position; the reductions are an
+// unsigned minimum and an integer sum, so the result does not depend on the order in which workgroups arrive.
+//
+// watch_prep_kernel (one workgroup): the clamped counts of the streams are prefix-summed in LDS, read k of the call (stream s,
+//   line j) gets the position off[s] + j and its line goes to qlist[k]; keys and counts of every position are cleared.
+// watch_scan_kernel: one workgroup of 256 threads per LP_WATCH_BLOCK_ENTRIES entries.  Every lane owns eight entries, each one
+//   8-byte load (lane t takes entries base + r * 256 + t: coalesced), their ids mapped to table columns once -- 0..63 the id, 64
+//   WILD, 65 "matches nothing" -- and parked in LDS (16 KiB; held in registers across the unrolled loops they cost the kernel
+//   a thousand spilled registers).  So the list is read from memory once per call, however many reads there are.  The workgroup
+//   walks the valid reads in blocks of LP_WATCH_QUERY_BLOCK = 16.  Per block it builds the LDS table
+//     T[position][column][read] = (cost << 8) | mismatch        (80-byte column pitch: 16 reads + one 16-byte slot, so that
+//   the 16-byte reads of lanes on different columns spread over all bank slots), and an (entry, read) pair is then eight LDS
+//   lookups and adds with no branch: one ds_read_b128 fetches a column's values for four reads.  The sums sit in one register:
+//   mismatches in bits 0..3, cost in bits 8..24; both limits are tested by one subtraction from (limit | guard bit) per field.
+//   A lane keeps, per read, the minimum of (sum | r << 4) over its accepted entries -- (cost, index) order, since its entries
+//   ascend with r -- and their number; lanes that accepted something combine into LDS (64-bit minimum of
+//   cost << 32 | index << 4 | mismatches, integer add), and one thread per read with a hit issues one global atomicMin and one
+//   atomicAdd.  Workgroups with nothing accepted issue no atomic.  Blocks of four, eight and twelve reads run the same code on
+//   that many table columns only (template parameter Q4).
+// watch_tail_kernel: one thread per line of match_i turns key and count into (entry, mismatches, cost, n_hits), and writes
+//   (-1, 0, 0, 0) into every other line.
+#include "lp_internal.h"
+#include "lp_streams.h"
+
+namespace lp {
+
+namespace {
+
+constexpr int W_T = 256;                                   // threads of a scan workgroup
+constexpr int W_R = LP_WATCH_BLOCK_ENTRIES / W_T;          // entries per lane
+constexpr int W_QB = LP_WATCH_QUERY_BLOCK;
+constexpr int W_COLS = 66;                                 // 0..63 ids, 64 WILD, 65 matches nothing
+constexpr int W_PITCH = W_QB + 4;                          // dwords between two columns of the table
+constexpr int W_PREP_T = 1024;
+constexpr unsigned W_COST_SHIFT = 8;
+constexpr unsigned W_GUARD = (1u << 4) | (1u << 25);       // the bits a field keeps iff it is within its limit
+constexpr unsigned W_OUTSIDE = 0x10000u << W_COST_SHIFT;   // start value of a lane's entries past N: a cost above every limit
+static_assert(W_R == 8 && W_QB == 16, "lp_watch.hip is written for 8 entries per lane and blocks of 16 reads");
+
+struct WatchWs {                                           // carve-up of the caller's workspace, L = n_streams * max_ended
+    unsigned long long* keys;                              // [L] by read position
+    int32_t* cnts;                                         // [L]
+    int32_t* qlist;                                        // [L] line of read k
+    int32_t* off;                                          // [n_streams] position of the stream's first read
+    int32_t* nvalid;                                       // [1]
+    size_t bytes;
+};
+WatchWs watch_carve(void* base, size_t S, size_t max_ended) {
+    const size_t L = S * max_ended;
+    char* p = (char*)base;
+    WatchWs w;
+    w.keys = (unsigned long long*)p;
+    w.cnts = (int32_t*)(p + 8 * L);
+    w.qlist = (int32_t*)(p + 12 * L);
+    w.off = (int32_t*)(p + 16 * L);
+    w.nvalid = (int32_t*)(p + 16 * L + 4 * S);
+    w.bytes = (16 * L + 4 * S + 4 + 15) & ~(size_t)15;
+    return w;
+}
+
+__device__ __forceinline__ int clamp_count(int c, int max_ended) { return c < 0 ? 0 : (c > max_ended ? max_ended : c); }
+
+// grid (1), block (1024)
+__global__ __launch_bounds__(W_PREP_T) void watch_prep_kernel(const int32_t* __restrict__ ended_count, int S, int max_ended, WatchWs ws) {
+    __shared__ int s_scan[W_PREP_T];
+    const int tid = threadIdx.x;
+    int base = 0;
+    for (int s0 = 0; s0 < S; s0 += W_PREP_T) {                         // (block-uniform control flow)
+        const int s = s0 + tid;
+        const int c = s < S ? clamp_count(ended_count[s], max_ended) : 0;
+        s_scan[tid] = c;
+        __syncthreads();
+        for (int d = 1; d < W_PREP_T; d <<= 1) {                       // inclusive prefix sum
+            const int v = tid >= d ? s_scan[tid - d] : 0;
+            __syncthreads();
+            s_scan[tid] += v;
+            __syncthreads();
+        }
+        if (s < S) ws.off[s] = base + s_scan[tid] - c;
+        base += s_scan[W_PREP_T - 1];
+        __syncthreads();
+    }
+    if (tid == 0) ws.nvalid[0] = base;
+    const int L = S * max_ended;
+    for (int l = tid; l < L; l += W_PREP_T) {
+        const int s = l / max_ended, j = l - s * max_ended;
+        ws.keys[l] = ~0ull;
+        ws.cnts[l] = 0;
+        if (j < clamp_count(ended_count[s], max_ended)) ws.qlist[ws.off[s] + j] = l;     // off[s] + j < L; off[] is behind a barrier
+    }
+}
+
+// ids of four entry bytes -> table columns
+__device__ __forceinline__ unsigned to_columns(unsigned x) {
+    unsigned out = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned b = (x >> (8 * k)) & 0xffu;
+        out |= (b < 64u ? b : (b == 255u ? 64u : 65u)) << (8 * k);
+    }
+    return out;
+}
+
+struct ScanLds {
+    unsigned T[8 * W_COLS * W_PITCH];                      // 8 positions x 66 columns x 20 dwords = 42240 bytes
+    uint2 ent[LP_WATCH_BLOCK_ENTRIES];                     // the workgroup's entries as table columns, entry r of lane t at r * 256 + t
+    int best[W_QB * 8];
+    unsigned qp[W_QB * 8];
+    unsigned long long key[W_QB];
+    int cnt[W_QB];
+};
+static_assert(LP_TRACK_MAX_CLS == 64, "the table has 64 id columns");
+constexpr int W_ENDED_COLS = 12;                           // ended_i / ended_f: words of a record
+
+// One block of 4 * Q4 reads (the reads k0 .. k0 + nq - 1, nq <= 4 * Q4), from the staged best / qp to the global atomics.
+template <int Q4>
+__device__ __forceinline__ void scan_block(ScanLds& lds, int nlane, int idx0, const unsigned char* __restrict__ confuse,
+                                           unsigned limits, int k0, int nq, const WatchWs& ws) {
+    constexpr int NQ = 4 * Q4;
+    const int tid = threadIdx.x;
+    // ---- the table: one unit = (position, four id columns or the two special ones, read) -------------------------------------------
+    for (int u = tid; u < 8 * 17 * NQ; u += W_T) {
+        const int q = u % NQ, pc = u / NQ, p = pc / 17, c4 = pc - p * 17;
+        const int b = lds.best[q * 8 + p];
+        const unsigned qp = lds.qp[q * 8 + p];
+        const bool inr = (unsigned)b < 64u;
+        unsigned* col0 = lds.T + (p * W_COLS + c4 * 4) * W_PITCH + q;
+        if (c4 == 16) {
+            col0[0] = 0u;                                              // WILD
+            col0[W_PITCH] = ((qp * 16u) << W_COST_SHIFT) | 1u;         // an id that matches nothing
+            continue;
+        }
+        unsigned cw = 0x10101010u;
+        if (confuse != nullptr && inr) cw = *(const unsigned*)(confuse + ((p < 2 ? p : 2) * 4096 + b * 64 + c4 * 4));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            unsigned c = (cw >> (8 * k)) & 0xffu;
+            c = c > 16u ? 16u : c;                                     // a table the host did not check cannot leave the cost field
+            unsigned v = ((qp * c) << W_COST_SHIFT) | 1u;
+            if (inr && c4 * 4 + k == b) v = 0u;
+            col0[k * W_PITCH] = v;
+        }
+    }
+    __syncthreads();
+    // ---- the scan --------------------------------------------------------------------------------------------------------------
+    unsigned best[NQ], cnt[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) { best[q] = ~0u; cnt[q] = 0u; }
+#pragma unroll 1
+    for (int r = 0; r < W_R; ++r) {
+        unsigned acc[NQ];
+        const uint2 ent = lds.ent[r * W_T + tid];
+        const unsigned start = r < nlane ? 0u : W_OUTSIDE;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) acc[q] = start;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const unsigned col = ((p < 4 ? ent.x : ent.y) >> (8 * (p & 3))) & 0xffu;
+            const uint4* row = (const uint4*)(lds.T + (p * W_COLS) * W_PITCH) + col * (W_PITCH / 4);
+#pragma unroll
+            for (int g = 0; g < Q4; ++g) {
+                const uint4 v = row[g];
+                acc[4 * g] += v.x; acc[4 * g + 1] += v.y; acc[4 * g + 2] += v.z; acc[4 * g + 3] += v.w;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const bool ok = ((limits - acc[q]) & W_GUARD) == W_GUARD;
+            const unsigned key = acc[q] | ((unsigned)r << 4);
+            best[q] = ok && key < best[q] ? key : best[q];
+            cnt[q] += ok ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        if (cnt[q] != 0u) {
+            const unsigned r = (best[q] >> 4) & 7u;
+            const unsigned long long key = ((unsigned long long)(best[q] >> W_COST_SHIFT) << 32) |
+                                           ((unsigned long long)(unsigned)(idx0 + (int)r * W_T) << 4) | (best[q] & 15u);
+            atomicMin(&lds.key[q], key);
+            atomicAdd(&lds.cnt[q], (int)cnt[q]);
+        }
+    }
+    __syncthreads();
+    if (tid < nq && lds.cnt[tid] > 0) {
+        atomicMin(&ws.keys[k0 + tid], lds.key[tid]);
+        atomicAdd(&ws.cnts[k0 + tid], lds.cnt[tid]);
+    }
+}
+
+// grid (ceil(N / LP_WATCH_BLOCK_ENTRIES)), block (256)
+__global__ __launch_bounds__(W_T) void watch_scan_kernel(const uint2* __restrict__ entries, int N, const unsigned char* __restrict__ confuse,
+                                                         const int32_t* __restrict__ ended_i, const float* __restrict__ ended_f,
+                                                         unsigned limits, WatchWs ws) {
+    __shared__ __attribute__((aligned(16))) ScanLds lds;
+    const int tid = threadIdx.x;
+    const int nv = ws.nvalid[0];
+    if (nv <= 0) return;                                               // (block-uniform)
+    const int idx0 = blockIdx.x * LP_WATCH_BLOCK_ENTRIES + tid;         // < 2^24 + 2048
+    int nlane = 0;                                                     // this lane's entries below N: r < nlane
+#pragma unroll
+    for (int r = 0; r < W_R; ++r) {
+        const int idx = idx0 + r * W_T;
+        uint2 v = make_uint2(0u, 0u);
+        if (idx < N) { v = entries[idx]; nlane = r + 1; }
+        lds.ent[r * W_T + tid] = make_uint2(to_columns(v.x), to_columns(v.y));     // read back by this lane alone
+    }
+    for (int k0 = 0; k0 < nv; k0 += W_QB) {                            // nv <= n_streams * max_ended: k0 + q indexes qlist, keys, cnts
+        const int nq = nv - k0 < W_QB ? nv - k0 : W_QB;
+        if (tid < W_QB * 8) {
+            const int q = tid >> 3, p = tid & 7;
+            int b = -1;
+            unsigned qp = 1u;
+            if (q < nq) {
+                const int line = ws.qlist[k0 + q];
+                b = ended_i[(long long)line * W_ENDED_COLS + 4 + p];
+                const float share = ended_f[(long long)line * W_ENDED_COLS + p];
+                if (share > 0.f) qp = (unsigned)(int)fminf(share * 255.0f, 255.0f) + 1u;
+            }
+            lds.best[tid] = b;
+            lds.qp[tid] = qp;
+        }
+        if (tid < W_QB) { lds.key[tid] = ~0ull; lds.cnt[tid] = 0; }
+        __syncthreads();
+        if (nq <= 4) scan_block<1>(lds, nlane, idx0, confuse, limits, k0, nq, ws);
+        else if (nq <= 8) scan_block<2>(lds, nlane, idx0, confuse, limits, k0, nq, ws);
+        else if (nq <= 12) scan_block<3>(lds, nlane, idx0, confuse, limits, k0, nq, ws);
+        else scan_block<4>(lds, nlane, idx0, confuse, limits, k0, nq, ws);
+        __syncthreads();                                               // the next block stages over best / qp / key / cnt and the table
+    }
+}
+
+// grid (ceil(L / 256)), block (256).  scanned == 0 (an empty list): every line is (-1, 0, 0, 0) and the workspace is not read.
+__global__ __launch_bounds__(256) void watch_tail_kernel(const int32_t* __restrict__ ended_count, int S, int max_ended, int scanned, WatchWs ws,
+                                                         int32_t* __restrict__ match_i) {
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= S * max_ended) return;
+    const int s = l / max_ended, j = l - s * max_ended;
+    int e = -1, mism = 0, cost = 0, n = 0;
+    if (scanned && j < clamp_count(ended_count[s], max_ended)) {
+        const int k = ws.off[s] + j;
+        n = ws.cnts[k];
+        if (n > 0) {
+            const unsigned long long key = ws.keys[k];
+            e = (int)((key >> 4) & 0xfffffffull);
+            mism = (int)(key & 15ull);
+            cost = (int)(key >> 32);
+        }
+    }
+    int32_t* out = match_i + (long long)l * 4;
+    out[0] = e; out[1] = mism; out[2] = cost; out[3] = n;
+}
+
+bool watch_dims_ok(int n_streams, int max_ended) {
+    return n_streams >= 1 && max_ended >= 0 && (long long)n_streams * max_ended * W_ENDED_COLS < 0x80000000ll;
+}
+
+}  // namespace
+
+}  // namespace lp
+
+using namespace lp;
+
+extern "C" size_t lp_watch_workspace_bytes(int n_streams, int max_ended) {
+    if (!watch_dims_ok(n_streams, max_ended)) return 0;
+    return watch_carve(nullptr, (size_t)n_streams, (size_t)max_ended).bytes;
+}
+
+extern "C" int lp_watch_match(const unsigned char* entries, int n_entries, const unsigned char* confuse, const int32_t* ended_i,
+                              const float* ended_f, const int32_t* ended_count, int n_streams, int max_ended, int max_mismatch, int max_cost,
+                              int32_t* match_i, void* workspace, size_t workspace_bytes, void* stream) {
+    const std::string fn = "lp_watch_match: ";
+    if (n_entries < 0 || n_entries > LP_WATCH_MAX_ENTRIES)
+        return fail(LP_ERR_ARG, fn + "n_entries " + std::to_string(n_entries) + " (need 0.." + std::to_string(LP_WATCH_MAX_ENTRIES) + ")");
+    if (!watch_dims_ok(n_streams, max_ended))
+        return fail(LP_ERR_ARG, fn + "need n_streams >= 1, max_ended >= 0 and n_streams * max_ended * 12 < 2^31");
+    if (max_mismatch < 0 || max_mismatch > 8 || max_cost < 0 || max_cost > LP_WATCH_MAX_COST)
+        return fail(LP_ERR_ARG, fn + "need max_mismatch in 0..8 and max_cost in 0.." + std::to_string(LP_WATCH_MAX_COST));
+    if (max_ended == 0) return LP_OK;                                  // no line to write
+    const bool scan = n_entries > 0;
+    if (!ended_count || !match_i || (scan && (!entries || !ended_i || !ended_f || !workspace))) return fail(LP_ERR_ARG, fn + "null pointer");
+    const WatchWs ws = watch_carve(workspace, (size_t)n_streams, (size_t)max_ended);
+    if (scan) {
+        if (((uintptr_t)entries & 7) != 0 || ((uintptr_t)confuse & 3) != 0 || ((uintptr_t)workspace & 15) != 0)
+            return fail(LP_ERR_ARG, fn + "entries must be 8-byte, confuse 4-byte and the workspace 16-byte aligned");
+        if (workspace_bytes < ws.bytes)
+            return fail(LP_ERR_ARG, fn + "workspace of " + std::to_string(workspace_bytes) + " bytes, need " + std::to_string(ws.bytes));
+    }
+    {   // neither match_i nor the workspace may overlap an input or each other
+        const size_t L = (size_t)n_streams * max_ended;
+        const Region reg[] = {{entries, (size_t)n_entries * 8, false},
+                              {confuse, scan && confuse ? (size_t)3 * 64 * 64 : 0, false},
+                              {ended_i, scan ? L * W_ENDED_COLS * 4 : 0, false},
+                              {ended_f, scan ? L * W_ENDED_COLS * 4 : 0, false},
+                              {ended_count, (size_t)n_streams * 4, false},
+                              {match_i, L * 16, true},
+                              {workspace, scan ? ws.bytes : 0, true}};
+        if (regions_clash(reg, (int)(sizeof(reg) / sizeof(reg[0]))))
+            return fail(LP_ERR_ARG, fn + "match_i and the workspace may overlap neither an input nor each other");
+    }
+
+    hipStream_t st = (hipStream_t)stream;
+    const int L = n_streams * max_ended;
+    if (scan) {
+        hipLaunchKernelGGL(watch_prep_kernel, dim3(1), dim3(W_PREP_T), 0, st, ended_count, n_streams, max_ended, ws);
+        LP_HIP_CHECK(hipGetLastError());
+        const unsigned limits = ((unsigned)max_mismatch | ((unsigned)max_cost << W_COST_SHIFT)) | W_GUARD;
+        hipLaunchKernelGGL(watch_scan_kernel, dim3((unsigned)ceil_div(n_entries, LP_WATCH_BLOCK_ENTRIES)), dim3(W_T), 0, st, (const uint2*)entries,
+                           n_entries, confuse, ended_i, ended_f, limits, ws);
+        LP_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(watch_tail_kernel, dim3((unsigned)ceil_div(L, 256)), dim3(256), 0, st, ended_count, n_streams, max_ended, scan ? 1 : 0, ws,
+                       match_i);
+    LP_HIP_CHECK(hipGetLastError());
+    return LP_OK;
+}

@@ -49,7 +49,8 @@ class Inferer:
     def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True, tile=None, tile_overlap=0.2,
                  tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5, best_shots=False,
                  nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1,
-                 redact_lookback=None, redact_lookback_max_back=None, redact_sigma=8.0):
+                 redact_lookback=None, redact_lookback_max_back=None, redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None,
+                 watch_confusable=None, watch_confusable_weight=4):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -75,8 +76,18 @@ class Inferer:
         stream, and once a new track's second detection has fixed its velocity the frames still inside the delay also get a row
         for it, at most ``redact_lookback_max_back`` (default D) frames before its first detection (``yolov6.utils.lookback``).
         ``redacted/<image name>`` is written when the frame leaves the delay, the rest at the end of the source; every other
-        output is what it is without it."""
+        output is what it is without it.
+        ``watchlist`` = the path of a watchlist file (with ``track``; ``yolov6.utils.watch`` states the rule and
+        ``parse_watchlist`` the format): the read of every ended track is looked up in it, tolerating ``watch_mismatch`` misread
+        positions of a total cost of at most ``watch_cost`` fully confident mismatches (None: no limit); ``watch_confusable`` =
+        pairs of characters of the ``ads`` names (``'0D 0Q 8B 2Z 5S'``) that cost only ``watch_confusable_weight`` sixteenths of a
+        mismatch.  ``infer`` writes ``hits.txt`` beside ``plates.txt``; every other output is what it is without it."""
         self.__dict__.update(locals())
+        if watchlist is not None:
+            from yolov6.utils.watch import check_params, cost_units
+            if not track:
+                raise ValueError('watchlist needs track=True')
+            check_params(watch_mismatch, cost_units(watch_cost))
         if redact is not None:
             from yolov6.utils.redact import check_params, check_sigma
             if check_params(redact, redact_cell, redact_margin)[0] == 2:
@@ -156,6 +167,10 @@ class Inferer:
         ``<save_dir>/shots/<k>_<id>.png`` (RGB), and ``<save_dir>/shots.txt`` has one line ``id frame row status sharpness file``
         per line of ``plates.txt``: the stream's frame index and the row the shot was cut from, the crop's status (1 corners,
         2 box) and its Laplacian energy; a track without a shot has ``id 0 0 0 0 -``.
+
+        With ``watchlist`` ``<save_dir>/hits.txt`` has one line ``id first last text entry entry_text mismatches cost n_hits`` per
+        ended track whose read an entry of the list accepts: the line of ``plates.txt`` up to the text, the index and text of the
+        accepted entry of the smallest (cost, index), its two sums, and the number of accepted entries (above 1: ambiguous).
 
         With ``redact`` every frame is also written, its plates redacted along the rows returned, as
         ``<save_dir>/redacted/<image name>`` (``.png`` for a frame of a video or a raw stream)."""
@@ -352,6 +367,16 @@ class Inferer:
         else:
             self._tracker = PlateTrackerNp(1 + len(videos), **kw)
         self._track_tids, self._track_lines, self._track_ended, self._track_shots = deque(), [], [], []
+        self._track_hits = []           # with watchlist: the match_i line of every ended record
+        if self.watchlist is not None:
+            from yolov6.utils import watch
+            with open(self.watchlist) as f:
+                entries = watch.parse_watchlist(f, self.pro_names, self.alp_names, self.ads_names)
+            confuse = None
+            if self.watch_confusable:
+                confuse = watch.confuse_table(watch.confusable_pairs(self.watch_confusable), 2, self.watch_confusable_weight, self.ads_names)
+            wl = runtime.Watchlist(entries, confuse, self.device) if self.device.type != 'cpu' else watch.WatchlistNp(entries, confuse)
+            self._tracker.enable_watch(wl, self.watch_mismatch, self.watch_cost)
         if self.redact_hold:
             self._tracker.enable_hold(min_hits=self.redact_hold_min_hits)
         if self.redact_lookback is not None:
@@ -377,11 +402,16 @@ class Inferer:
             ended_i, ended_f, ended_count = ended_i.cpu().numpy(), ended_f.cpu().numpy(), ended_count.cpu().numpy()
         if torch.is_tensor(shot_i):
             shot_i, shot_q = shot_i.cpu().numpy(), shot_q.cpu().numpy().view(np.uint64)
+        match_i = self._tracker.last_watch          # of the same update, line-parallel to ended_i
+        if torch.is_tensor(match_i):
+            match_i = match_i.cpu().numpy()
         for s, c in enumerate(ended_count.tolist()):
             if c > ended_i.shape[1]:
                 LOGGER.warning('stream %d: %d tracks ended in one step, %d recorded' % (s, c, ended_i.shape[1]))
             for k in range(min(c, ended_i.shape[1])):
                 self._track_ended.append((ended_i[s, k].copy(), ended_f[s, k].copy()))
+                if match_i is not None:
+                    self._track_hits.append(match_i[s, k].copy())
                 if shot_i is not None:
                     crop = shot_crops[s, k] if shot_i[s, k, 3] else None
                     crop = crop.cpu().numpy() if torch.is_tensor(crop) else (None if crop is None else crop.copy())
@@ -445,6 +475,15 @@ class Inferer:
             for ri, rf in self._track_ended:
                 text = plate_text(ri[4:12], self.pro_names, self.alp_names, self.ads_names)
                 f.write('%d %d %d %d %s %s\n' % (ri[0], ri[1], ri[2], ri[3], text, ' '.join('%g' % v for v in rf[:8])))
+        if self.watchlist is not None:
+            from yolov6.utils.watch import entry_text
+            names = (self.pro_names, self.alp_names, self.ads_names)
+            entries = self._tracker._watch[0].entries_np
+            with open(osp.join(save_dir, 'hits.txt'), 'w') as f:
+                for (ri, _), m in zip(self._track_ended, self._track_hits):
+                    if m[0] >= 0:
+                        f.write('%d %d %d %s %d %s %d %d %d\n' % (ri[0], ri[1], ri[2], plate_text(ri[4:12], *names), m[0],
+                                                                  entry_text(entries[m[0]], *names), m[1], m[2], m[3]))
         if self.best_shots:
             from PIL import Image
             os.makedirs(osp.join(save_dir, 'shots'), exist_ok=True)

@@ -1345,6 +1345,59 @@ def _persistent(cache, key, make):
     return buf
 
 
+class Watchlist:
+    """A watchlist on the device (lp_watch_match; ``yolov6.utils.watch`` states the rule and ``watch_match_np`` there is the
+    same computation on the CPU, on every int32): ``entries`` [N,8] ids (0..63, 255 = wildcard; ``watch.parse_watchlist`` reads
+    a file), ``confuse`` [3,64,64] sixteenths or None (``watch.confuse_table``).  Validated and uploaded once; a changed list is
+    a new object.  ``n``: its length; ``entries_np`` / ``confuse_np``: the checked host copies."""
+
+    def __init__(self, entries, confuse=None, device='cuda'):
+        from yolov6.utils import watch
+        self.entries_np = watch.check_entries(entries)
+        self.confuse_np = None if confuse is None else watch.check_confuse(confuse)
+        self.n = len(self.entries_np)
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise ValueError('Watchlist lives on a GPU (watch_match_np is the CPU form)')
+        self.device = torch.device('cuda', torch.cuda.current_device() if dev.index is None else dev.index)
+        self.entries = torch.from_numpy(self.entries_np).to(self.device)
+        self.confuse = None if self.confuse_np is None else torch.from_numpy(self.confuse_np).to(self.device)
+        self._out = {}
+
+    def buffers(self, S, max_ended):
+        """The persistent (match_i [S,max_ended,4] int32, workspace) of a ``match`` of that shape."""
+        key = (int(S), int(max_ended))
+        need = abi.load().lp_watch_workspace_bytes(*key)
+        return _persistent(self._out, key, lambda: (torch.empty(key[0], key[1], 4, dtype=torch.int32, device=self.device),
+                                                    torch.empty(need + 256, dtype=torch.uint8, device=self.device)))
+
+    def match(self, ended_i, ended_f, ended_count, max_mismatch=1, max_cost=None):
+        """match_i [S,max_ended,4] int32 = (entry, mismatches, cost, n_hits) per line of the ended records of a
+        ``PlateTracker.update`` (device tensors), enqueued on the current stream with no host read: the accepted entry of the
+        smallest (cost, index), -1 for none, and how many were accepted.  ``max_mismatch`` 0..8; ``max_cost``: a float in fully
+        confident mismatches (``watch.cost_units`` makes it the integer of the rule; None: no limit).  Persistent buffers per
+        (S, max_ended): a later call of the same shape overwrites what the earlier one returned."""
+        from yolov6.utils import watch
+        return self._match(ended_i, ended_f, ended_count, *watch.check_params(max_mismatch, watch.cost_units(max_cost)))
+
+    def _match(self, ended_i, ended_f, ended_count, mm, mc):
+        """``match`` with the two limits as the checked integers of the rule."""
+        if ended_i.dim() != 3 or ended_i.shape[2] != 12 or ended_i.dtype != torch.int32 or ended_f.shape != ended_i.shape \
+                or ended_f.dtype != torch.float32 or ended_count.dtype != torch.int32 or ended_count.shape != ended_i.shape[:1]:
+            raise ValueError('ended_i int32 / ended_f fp32 must be [S,max_ended,12] and ended_count int32 [S]')
+        for t in (ended_i, ended_f, ended_count):
+            if t.device != self.device or not t.is_contiguous():
+                raise ValueError('the ended records must be contiguous tensors on the watchlist\'s device %s' % self.device)
+        S, max_ended = ended_i.shape[:2]
+        match_i, ws = self.buffers(S, max_ended)
+        base = _aligned(ws)
+        with torch.cuda.device(self.device):
+            abi.check(abi.load().lp_watch_match(_dptr(self.entries), self.n, _dptr(self.confuse), _dptr(ended_i), _dptr(ended_f),
+                                                _dptr(ended_count), S, max_ended, mm, mc, _dptr(match_i), ctypes.c_void_p(base),
+                                                ws.numel() - (base - ws.data_ptr()), _stream_ptr(self.device)), 'lp_watch_match')
+        return match_i
+
+
 class PlateTracker:
     """``n_streams`` independent device-resident plate trackers of ``max_tracks`` slots each (lp_track_update, one workgroup per
     stream): detections of consecutive frames are associated by the IoU of expanded, velocity-predicted boxes
@@ -1377,6 +1430,9 @@ class PlateTracker:
         self.last_hold = None
         #: the tid buffer [B,max_det] the last ``update`` filled (what ``LookbackRedactor.push`` reads), else None
         self.last_tid = None
+        self._watch = None
+        #: match_i [S,max_ended,4] int32 of the last ``update`` after ``enable_watch``, line-parallel to its ended_i, else None
+        self.last_watch = None
 
     def reset(self, streams=None):
         """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0; their best-shot
@@ -1419,7 +1475,26 @@ class PlateTracker:
                                                       _dptr(tid), _dptr(self.slot_buffer(B, max_det)), _dptr(ended_i), _dptr(ended_f),
                                                       _dptr(ended_count), max_ended, hp, _dptr(hold[0]), _dptr(hold[1]), _dptr(hold[2]),
                                                       _stream_ptr(self.device)), 'lp_track_update_hold')
+        if self._watch is not None:
+            wl, mm, mc = self._watch
+            self.last_watch = wl._match(ended_i, ended_f, ended_count, mm, mc)
         return out
+
+    # ---- the ended reads looked up in a watchlist (lp_watch_match; yolov6/utils/watch.py states the rule) ----------------------
+    def enable_watch(self, watchlist, max_mismatch=1, max_cost=None):
+        """From now on every ``update`` / ``update_with_shots`` / ``flush_all*`` also enqueues, behind the tracker on the same
+        stream, the lookup of the records it ended in ``watchlist`` (a ``Watchlist`` on this device) and leaves match_i
+        [S,max_ended,4] int32 = (entry, mismatches, cost, n_hits), line-parallel to ended_i, in ``last_watch``.  ``max_cost``: a float
+        in fully confident mismatches (``watch.cost_units``; None: no limit).  Returns, state and every other buffer are what
+        they are without it.  ``enable_watch(None)`` turns it off."""
+        from yolov6.utils import watch
+        self.last_watch = None
+        if watchlist is None:
+            self._watch = None
+            return
+        if not isinstance(watchlist, Watchlist) or watchlist.device != self.device:
+            raise ValueError('enable_watch needs a Watchlist on the tracker\'s device %s' % self.device)
+        self._watch = (watchlist,) + watch.check_params(max_mismatch, watch.cost_units(max_cost))
 
     # ---- redaction held over missed frames (lp_track_update_hold; rule 11 of yolov6/utils/track.py) -----------------------------
     def enable_hold(self, min_hits=1, max_misses=None):

@@ -180,6 +180,9 @@ class PlateTrackerNp:
         self._hold = None
         #: (det_hold, count_hold, tid_hold) of the last ``update`` after ``enable_hold`` (rule 11), else None
         self.last_hold = None
+        self._watch = None
+        #: match_i [S, max_ended, 4] int32 of the last ``update`` after ``enable_watch``, line-parallel to its ended_i, else None
+        self.last_watch = None
 
     _SLOT_ARRAYS = ('id', 'first', 'last', 'hits', 'misses', 'box', 'cor', 'vel', 'votes', 'total')
 
@@ -197,6 +200,15 @@ class PlateTrackerNp:
         if min_hits < 1 or max_misses < 0:
             raise ValueError('hold needs min_hits >= 1 and max_misses >= 0')
         self._hold = dict(min_hits=min_hits, max_misses=max_misses, out={})
+
+    def enable_watch(self, watchlist, max_mismatch=1, max_cost=None):
+        """From now on every ``update`` / ``flush_all`` also looks the records it ended up in ``watchlist`` -- anything with
+        ``entries_np`` and ``confuse_np`` (``watch.WatchlistNp``, ``runtime.Watchlist``) -- and leaves match_i [S, max_ended, 4] int32
+        in ``last_watch`` (``yolov6.utils.watch`` states the rule; ``max_cost``: a float in fully confident mismatches, None: no
+        limit).  Every other output stays what it is.  ``enable_watch(None)`` turns it off."""
+        from yolov6.utils import watch
+        self.last_watch = None
+        self._watch = None if watchlist is None else (watchlist,) + watch.check_params(max_mismatch, watch.cost_units(max_cost))
 
     def hold_buffers(self, B, max_det):
         """The persistent (det_hold [B,max_det+max_tracks,28] fp32, count_hold [B] int32, tid_hold [B,max_det+max_tracks] int32)
@@ -393,4 +405,8 @@ class PlateTrackerNp:
             ended_count[s] = len(ended[s])
             for k, (ri, rf) in enumerate(ended[s][:max_ended]):
                 ended_i[s, k], ended_f[s, k] = ri, rf
+        if self._watch is not None:
+            from yolov6.utils.watch import watch_match_np
+            wl, mm, mc = self._watch
+            self.last_watch = watch_match_np(wl.entries_np, wl.confuse_np, ended_i, ended_f, ended_count, mm, mc)
         return det_out, tid, ended_i, ended_f, ended_count
