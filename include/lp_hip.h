@@ -762,6 +762,55 @@ int lp_watch_match(const unsigned char* entries, int n_entries, const unsigned c
                    const int32_t* ended_i, const float* ended_f, const int32_t* ended_count, int n_streams, int max_ended,
                    int max_mismatch, int max_cost, int32_t* match_i, void* workspace, size_t workspace_bytes, void* stream);
 
+/* lp_tile_gate_luma_batch / lp_tile_gate_update: skip the unchanged tiles of fixed-camera frames in tiled detection.  On a fixed
+ * camera nearly every tile of a frame shows the pixels of the frame before, and a tile that has not changed yields the same
+ * detections again; these two calls find, per (stream, tile), whether the tile changed against the frame its cached detections were
+ * computed on.  The caller runs the network on the flagged tiles only and keeps the rows of the others (runtime.TileGate).  The
+ * reference has nothing here; yolov6/utils/tile_gate.py (luma_blocks_np, gate_update_np) restates the rules below on every integer.
+ * All frame, grid, table and state pointers are DEVICE pointers; desc, stream_of and n_tiles are HOST arrays.  Nothing is uploaded
+ * or read back, nothing is allocated, both calls can be captured in a graph.
+ *   Luma: a BGR frame gives L = (29 B + 150 G + 77 R + 128) >> 8; an NV12 frame gives L = Y (the chroma plane is not read: a change
+ *   of chroma alone is invisible there).
+ *   Block sums (lp_tile_gate_luma_batch): blocks[by][bx] = the sum of L over the pixels y in [4 by, min(4 by + 4, h0)), x in
+ *   [4 bx, min(4 bx + 4, w0)): uint16 [ceil(h0 / 4)][ceil(w0 / 4)], at most 4080.  Every frame byte is read once, none past the last
+ *   pixel of a row; frames and grids of one call may have any sizes.
+ *   Tile region: tile (y0, x0, th, tw) owns the blocks by in [y0 >> 2, (y0 + th - 1) >> 2], bx likewise (every block it overlaps).
+ *   Cells: inside a tile's block range, 4 x 4 blocks anchored at the tile's first block, smaller at the end of a range;
+ *   npix(cell) = the frame pixels of its blocks, A(cell) = sum |blocks - ref| over its blocks (int32); the cell is changed iff
+ *   16 A > thres16 * npix (thres16 = the threshold in sixteenths of a luma level per pixel, 0..4080).
+ *   State: tiles int32 [n_streams][max_tiles][LP_TILE_GATE_TILE_WORDS] = (y0, x0, th, tw, ref_off, 0, 0, 0) per tile of a stream's plan,
+ *   written once by the caller; ref uint16 [ref_elems], tile (s, t) owning the nby * nbx elements from its ref_off (the regions of
+ *   different tiles must not overlap); age int32 [n_streams][max_tiles], -1 = never detected (the caller fills it with -1; writing -1
+ *   resets a tile).  n_tiles[s] <= max_tiles <= LP_MERGE_MAX_TILES: the tiles of stream s.
+ *   lp_tile_gate_update, per frame b of stream s = stream_of[b] >= 0 (a stream at most once per call; desc[b].blocks, h0, w0 are read,
+ *   the planes are not) and tile t < n_tiles[s]: ncell = the number of changed cells, 0 if age < 0 (ref is then not read);
+ *   flag = age < 0 || ncell >= min_cells || (refresh > 0 && age + 1 >= refresh).  Flagged: ref <- blocks over the tile's region and
+ *   age <- (age < 0 && refresh > 0) ? t % refresh : 0 (the periodic refreshes of a plan are staggered over the period); not flagged:
+ *   ref untouched, age += 1.  So ref is always the frame the tile was last flagged on: slow drift accumulates until it crosses
+ *   the threshold.  flag uint8 / ncell int32 [n_frames][max_tiles]: every entry is written; t >= n_tiles[s] gives (0, 0); a frame with
+ *   stream_of -1 is not gated: (1, 0) for every t, no state read or written.  A table entry that is not inside its frame or whose
+ *   region leaves ref gives (1, -1) and touches no state.
+ * One luma kernel over two pixel sources (a lane sums 16 pixels x 4 rows with 16-byte loads), one update workgroup per (frame, tile).
+ * Every argument is checked before the first launch (LP_ERR_ARG names the frame; nothing is launched): null desc, planes, grids or
+ * state pointers, format, h0 or w0 < 1, pitch0 below the row's bytes, misaligned grids or state, max_tiles outside
+ * 1..LP_MERGE_MAX_TILES, n_tiles[s] outside 0..max_tiles, stream_of[b] outside -1..n_streams-1, a stream twice in one call, thres16,
+ * min_cells < 1, refresh < 0, ref_elems outside 1..2^31-1, and an output (a grid; ref, age, flag, ncell) overlapping an input or
+ * another output. */
+#define LP_MERGE_MAX_TILES 64   /* tiles per frame: the limit of lp_merge_tiles, which takes what the gate passes on */
+#define LP_TILE_GATE_TILE_WORDS 8
+typedef struct lp_tile_gate_desc {
+    const unsigned char* p0;    /* BGR: the frame, uint8 [h0][w0][3]; NV12: the luma plane.  Any alignment; read only */
+    int pitch0;                 /* bytes between rows: >= 3 * w0 (BGR), >= w0 (NV12) */
+    int h0, w0;                 /* >= 1 (the luma plane of an NV12 frame alone is read, so odd sizes are fine here) */
+    int format;                 /* 0 BGR, 1 NV12 */
+    unsigned short* blocks;     /* the frame's block grid, uint16 [ceil(h0 / 4)][ceil(w0 / 4)], 2-byte aligned */
+} lp_tile_gate_desc;
+int lp_tile_gate_luma_batch(const lp_tile_gate_desc* desc, int n_frames, void* stream);
+int lp_tile_gate_update(const lp_tile_gate_desc* desc, int n_frames, const int* stream_of /* HOST [n_frames] */, int n_streams,
+                        const int32_t* tiles, const int* n_tiles /* HOST [n_streams] */, int max_tiles,
+                        unsigned short* ref, long long ref_elems, int32_t* age, int thres16, int min_cells, int refresh,
+                        unsigned char* flag, int32_t* ncell, void* stream);
+
 /* lp_eval_counts: the matching loops of Evaler.eval (yolov6/core/evaler.py:153-243, box_iou general.py:93-115) for a
  * batch of images, one workgroup per image.
  *   det [B,max_det,28] fp32 + det_count [B]: detections as lp_nms returns them (xyxy, 8 corner coords, 8 confs, 8 ids)

@@ -5,6 +5,7 @@
                                  [--crops N] [--redact [--redact-cell 16] [--redact-sigma 8]]
     python tools/frames_bench.py --tile [--tile-baseline] [--tile-frame 2160 3840] [--tile-size 640] [--tile-overlap 128]
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
+    python tools/frames_bench.py --tile --gate [--gate-moving K] [--gate-thres F] [--gate-refresh N] [--nv12 [bt709]] [--tile-frame 2160 3840] [--runs 3]
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot] [--redact [--hold [--lookback D]]] [--nv12]
                                  [--watch N [--watch-mismatch 1]]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
@@ -96,6 +97,11 @@ def parse():
     ap.add_argument('--tile-overlap', type=int, default=128, help='tile overlap in pixels')
     ap.add_argument('--tile-frames', type=int, default=4, help='frames per detect_tiled call')
     ap.add_argument('--tile-batch', type=int, default=32, help='tiles per forward')
+    ap.add_argument('--gate', action='store_true', help='with --tile: measure the tile gate (runtime.TileGate) on fixed-camera frames -- the seeded '
+                                                        'frames held still per stream -- against detect_tiled_padded on the same frames')
+    ap.add_argument('--gate-moving', type=int, default=0, metavar='K', help='with --gate: patches of 96 x 32 px per frame that move a few pixels per step')
+    ap.add_argument('--gate-thres', type=float, default=2.0, metavar='F', help='with --gate: the gate\'s thres (luma levels per pixel)')
+    ap.add_argument('--gate-refresh', type=int, default=50, metavar='N', help='with --gate: the gate\'s refresh (calls after which a tile is detected again anyway; 0: never)')
     ap.add_argument('--track', action='store_true', help='measure plate tracking (PlateTracker.update behind detect_frames) instead')
     ap.add_argument('--track-batch', type=int, default=32, help='with --track: camera streams = frames per step')
     ap.add_argument('--best-shot', action='store_true', help='with --track: also time crops + sharpness + gallery behind the update')
@@ -264,6 +270,96 @@ def tile_mode(args, model, dev, tdt):
         out['stage_pct_of_detect'] = {k: round(100.0 * med[k] / med['detect'], 2) for k in names if k != 'detect'}
         out['merged_counts'] = count.cpu().tolist()
         out['candidates_per_frame'] = [int(count_t[f * (len(tiles) // F):(f + 1) * (len(tiles) // F)].clamp(0, tmd).sum()) for f in range(F)]
+    print(json.dumps(out))
+
+
+def gate_mode(args, model, dev, tdt):
+    """--tile --gate: the tile gate on still frames with ``--gate-moving`` moving patches.  Reports under ``gate``: the active tiles
+    per frame and the forwards per call of the gated path, frames/s with and without the gate (alternating in the same run, on the
+    same frames), the device time by events of each of the gate's two kernels, and the luma kernel's read rate."""
+    import torch
+    from yolov6.hip import runtime
+    size = [args.size, args.size]
+    h0, w0 = args.tile_frame
+    tile = args.tile_size or args.size
+    F, B, K = args.tile_frames, args.tile_batch, args.gate_moving
+    conf, iou, max_det = args.conf, args.iou, args.max_det
+    rng = np.random.default_rng(0)
+    still = [rng.integers(0, 256, (h0, w0, 3), dtype=np.uint8) for _ in range(F)]
+    STEPS, PH, PW = 8, 32, 96
+    patches = rng.integers(0, 256, (F, max(K, 1), PH, PW, 3), dtype=np.uint8)
+    origin = np.stack([rng.integers(0, h0 - PH - 4 * STEPS, (F, max(K, 1))), rng.integers(0, w0 - PW - 6 * STEPS, (F, max(K, 1)))], -1)
+    host = []                               # host[k][f]: the frames of step k (the patches 3 px down and 5 px right per step)
+    for k in range(STEPS if K else 1):
+        step = []
+        for f in range(F):
+            img = still[f].copy()
+            for j in range(K):
+                y, x = int(origin[f, j, 0]) + 3 * k, int(origin[f, j, 1]) + 5 * k
+                img[y:y + PH, x:x + PW] = patches[f, j]
+            step.append(img)
+        host.append(step)
+    if args.nv12:
+        from yolov6.utils.nv12 import bgr_to_nv12_np
+        steps = [[bgr_to_nv12_np(f, args.nv12).to(dev) for f in st] for st in host]
+    else:
+        steps = [[torch.from_numpy(f).to(dev) for f in st] for st in host]
+    kw = dict(tile_hw=(tile, tile), overlap=args.tile_overlap, batch=B)
+    sync = torch.cuda.synchronize
+    with torch.no_grad():
+        runtime.prepare_for(model, (B, 3, *size), tdt)
+        gate = runtime.TileGate(model, [(h0, w0)] * F, size, conf, iou, max_det, thres=args.gate_thres, refresh=args.gate_refresh, **kw)
+        n_tiles = len(gate.plans[0])
+
+        def gated(k):
+            return gate.detect_padded(steps[k % len(steps)])
+
+        def plain(k):
+            return runtime.detect_tiled_padded(model, steps[k % len(steps)], size, conf, iou, max_det, **kw)
+
+        calls = max(len(steps), args.frames // (F * 8))
+        for k in range(len(steps)):         # warm-up: both paths over every step once
+            gated(k)
+            plain(k)
+        sync()
+        fps = dict(gated=[], plain=[])
+        before = dict(gate.stats)
+        for _ in range(args.runs):
+            for name, fn in (('gated', gated), ('plain', plain)):
+                t0 = time.perf_counter()
+                for k in range(calls):
+                    fn(k)
+                sync()
+                fps[name].append(round(calls * F / (time.perf_counter() - t0), 2))
+        n_calls = gate.stats['calls'] - before['calls']
+        out = dict(metric='frames/s of tiled detection of fixed-camera frames with and without the tile gate', model=args.model,
+                   dtype=args.dtype, frame=[h0, w0], tile=tile, overlap=args.tile_overlap, tiles_per_frame=n_tiles, frames_per_call=F,
+                   tiles_per_forward=B, runs=args.runs, nv12=args.nv12)
+        g = out['gate'] = dict(moving=K, thres=args.gate_thres, refresh=args.gate_refresh, steps=len(steps), calls_per_run=calls)
+        g['active_tiles_per_frame'] = round((gate.stats['tiles_detected'] - before['tiles_detected']) / (n_calls * F), 3)
+        g['forwards_per_call'] = round((gate.stats['forwards'] - before['forwards']) / n_calls, 3)
+        g['gated_fps_runs'], g['plain_fps_runs'] = fps['gated'], fps['plain']
+        g['gated_fps'], g['plain_fps'] = float(np.median(fps['gated'])), float(np.median(fps['plain']))
+        g['gated_over_plain'] = round(g['gated_fps'] / g['plain_fps'], 3)
+        # the device time of the two kernels, by events
+        frames = steps[0]
+        desc = gate._describe(frames, list(range(F)), bool(args.nv12))
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        luma_ms, update_ms = [], []
+        for _ in range(args.reps + 1):
+            ev[0].record()
+            gate._luma(desc)
+            ev[1].record()
+            gate._update(desc, list(range(F)))
+            ev[2].record()
+            sync()
+            luma_ms.append(ev[0].elapsed_time(ev[1]))
+            update_ms.append(ev[1].elapsed_time(ev[2]))
+        read = F * h0 * w0 * (1 if args.nv12 else 3)
+        g['luma_ms_runs'], g['update_ms_runs'] = [round(v, 4) for v in luma_ms[1:]], [round(v, 4) for v in update_ms[1:]]
+        g['luma_ms'], g['update_ms'] = float(np.median(luma_ms[1:])), float(np.median(update_ms[1:]))
+        g['luma_bytes_read'] = read
+        g['luma_read_bytes_per_s'] = round(read / (g['luma_ms'] * 1e-3), 1)
     print(json.dumps(out))
 
 
@@ -738,6 +834,8 @@ def main():
             layer.switch_to_deploy()
     model = model.to(dev).to(tdt)
     model.lp_graph = True                   # as Inferer sets it
+    if args.tile and args.gate:
+        return gate_mode(args, model, dev, tdt)
     if args.tile:
         return tile_mode(args, model, dev, tdt)
     if args.track:

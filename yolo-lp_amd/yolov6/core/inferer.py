@@ -27,6 +27,9 @@ GPU, in place on the device frames and behind everything that reads them; ``reda
 written to ``<save_dir>/redacted/``.  NV12 frames are redacted as NV12 and converted only to be saved.
 With ``redact_lookback`` = D every frame is redacted D frames late, so that the frames before a plate's first detection are
 covered too (``runtime.LookbackRedactor`` on a GPU, ``LookbackNp`` on the CPU; ``yolov6.utils.lookback`` states the rule).
+With ``tile`` and ``tile_gate`` the source is taken as one fixed camera: a tile whose pixels have not changed since it was last
+detected is not run through the network again, its rows come from a cache (``runtime.TileGate`` on a GPU, ``TileGateNp`` on the
+CPU; ``yolov6.utils.tile_gate`` states the rule).
 """
 import math
 import os
@@ -50,7 +53,8 @@ class Inferer:
                  tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5, best_shots=False,
                  nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1,
                  redact_lookback=None, redact_lookback_max_back=None, redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None,
-                 watch_confusable=None, watch_confusable_weight=4):
+                 watch_confusable=None, watch_confusable_weight=4, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1,
+                 tile_gate_refresh=50):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -81,8 +85,18 @@ class Inferer:
         ``parse_watchlist`` the format): the read of every ended track is looked up in it, tolerating ``watch_mismatch`` misread
         positions of a total cost of at most ``watch_cost`` fully confident mismatches (None: no limit); ``watch_confusable`` =
         pairs of characters of the ``ads`` names (``'0D 0Q 8B 2Z 5S'``) that cost only ``watch_confusable_weight`` sixteenths of a
-        mismatch.  ``infer`` writes ``hits.txt`` beside ``plates.txt``; every other output is what it is without it."""
+        mismatch.  ``infer`` writes ``hits.txt`` beside ``plates.txt``; every other output is what it is without it.
+        ``tile_gate`` (with ``tile``): the whole source is ONE fixed-camera stream, every frame of the size of the first (another
+        size raises); a tile is run through the network only when a 16 x 16 cell of it has changed by more than ``tile_gate_thres``
+        luma levels per pixel (in at least ``tile_gate_min_cells`` cells) since the tile was last detected, or every
+        ``tile_gate_refresh`` frames (0: never); the other tiles keep their rows.  Tile groups are then one frame per call."""
         self.__dict__.update(locals())
+        if tile_gate:
+            from yolov6.utils.tile_gate import check_params as check_gate
+            if tile is None:
+                raise ValueError('tile_gate needs tile=(H, W)')
+            check_gate(tile_gate_thres, tile_gate_min_cells, tile_gate_refresh)
+        self._gate = None
         if watchlist is not None:
             from yolov6.utils.watch import check_params, cost_units
             if not track:
@@ -175,6 +189,7 @@ class Inferer:
         With ``redact`` every frame is also written, its plates redacted along the rows returned, as
         ``<save_dir>/redacted/<image name>`` (``.png`` for a frame of a video or a raw stream)."""
         self._redacted = deque()
+        self._gate = None       # with tile_gate: made at the first frame
         if self.track:
             self._track_begin(crop_size)
         if self.device.type != 'cpu' and (self.tile is not None or self.batch_size > 1 or self.nv12 is not None):
@@ -201,6 +216,10 @@ class Inferer:
             if self.redact_lookback is not None:        # right behind the tracker's flush: the frames still inside the delay
                 self._lookback_collect(self._lookback.flush_all())
                 self._write_delayed(save_dir)
+        if self._gate is not None:
+            st = self._gate.stats
+            LOGGER.info('Tile gate: %d of %d tiles detected (%d calls, %d forwards)' % (st['tiles_detected'], st['tiles_seen'], st['calls'],
+                                                                                       st['forwards']))
         LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
         return results
 
@@ -231,6 +250,8 @@ class Inferer:
                 det = runtime.detect(self.model.model, img, conf_thres, iou_thres, max_det)[0]
             elif self.tile is None:
                 det = non_max_suppression(self.model(img), conf_thres, iou_thres, classes, agnostic_nms, max_det=max_det)[0]
+            elif self.tile_gate:
+                det = self.gated_rows_cpu(img_src, conf_thres, iou_thres, classes, agnostic_nms, max_det)
             else:
                 det = self.tiled_rows_cpu(img_src, conf_thres, iou_thres, classes, agnostic_nms, max_det)
             seconds = time.time() - t1
@@ -295,23 +316,44 @@ class Inferer:
                 items, n_tiles = [], 0
                 while pending is not None:
                     k = len(plan_tiles(pending[0].shape, self.tile, self.tile_overlap, self.tile_overview))
-                    if items and n_tiles + k > B:
+                    if items and (n_tiles + k > B or self.tile_gate):      # the gate takes one frame of a stream per call
                         break
                     items.append(pending)
                     n_tiles += k
                     pending = next(frames, None)
                 yield items, kw
 
+        def gate_padded(model, dev_frames, img_size, conf, iou, mdet, **kw):
+            """``detect_tiled_padded`` through the gate (made at the first frame, whose size is the stream's); copies, since the
+            gate's outputs are persistent."""
+            if self._gate is None:
+                self._gate = runtime.TileGate(model, [tuple(dev_frames[0].shape[:2])], img_size, conf, iou, mdet, thres=self.tile_gate_thres,
+                                              min_cells=self.tile_gate_min_cells, refresh=self.tile_gate_refresh, **kw)
+            self._gate_check_shape(dev_frames[0].shape, self._gate.shapes[0])
+            det, count = self._gate.detect_padded(dev_frames)
+            return det.clone(), count.clone()
+
+        def gate_detect(*a, **kw):
+            det, count = gate_padded(*a, **kw)
+            return runtime._unpad(det, count.cpu().tolist())
+
+        def gate_with_crops(model, dev_frames, img_size, conf, iou, mdet, crop_hw, **kw):
+            det, count = gate_padded(model, dev_frames, img_size, conf, iou, mdet, **kw)
+            return runtime._unpad_with_crops(dev_frames, det, count, runtime._crop_size(crop_hw))
+
         if self.tile is None:
             groups, detect, detect_with_crops = frame_groups(), runtime.detect_frames, runtime.detect_frames_with_crops
+            padded = runtime.detect_frames_padded
+        elif self.tile_gate:
+            groups, detect, detect_with_crops, padded = tile_groups(), gate_detect, gate_with_crops, gate_padded
         else:
             groups, detect, detect_with_crops = tile_groups(), runtime.detect_tiled, runtime.detect_tiled_with_crops
+            padded = runtime.detect_tiled_padded
         batcher = FrameBatcher(self.device)
         for items, kw in groups:
             t1 = time.time()
             dev_frames = batcher.put([f for f, _ in items])
             if self.track:      # detect -> track -> (crops) enqueued back to back on the device, then the host reads
-                padded = runtime.detect_frames_padded if self.tile is None else runtime.detect_tiled_padded
                 det, count = padded(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det, **kw)
                 det, tid = self._track_update(det, count, [p for _, p in items], dev_frames)
                 if save_crops:
@@ -335,9 +377,18 @@ class Inferer:
         from yolov6.utils.tiles import MAX_CANDIDATES, merge_tiles_np
         tiles = plan_tiles(img_src.shape, self.tile, self.tile_overlap, self.tile_overview)
         tmd = max(1, min(int(max_det), MAX_CANDIDATES // len(tiles)))
+        det_t, count_t = self._tiles_cpu([img_src], [(0,) + t for t in tiles], tmd, conf_thres, iou_thres, classes, agnostic_nms)
+        det, count, _ = merge_tiles_np(det_t, count_t, [(0,) + t for t in tiles], [img_src.shape], iou_thres, max_det,
+                                       self.merge_metric, border)
+        return torch.from_numpy(det[0, :int(count[0])].copy())
+
+    def _tiles_cpu(self, frames, tiles, tmd, conf_thres, iou_thres, classes, agnostic_nms):
+        """The per-tile half of ``tiled_rows_cpu``: (det_t [T, tmd, 28] fp32, count_t [T]) of the tiles (frame index, y0, x0, th, tw)
+        of the BGR ``frames``, in tile pixels, rounded."""
         det_t = np.zeros((len(tiles), tmd, 28), np.float32)
         count_t = np.zeros(len(tiles), np.int32)
-        for t, (y0, x0, th, tw) in enumerate(tiles):
+        for t, (f, y0, x0, th, tw) in enumerate(tiles):
+            img_src = frames[f]
             region = np.ascontiguousarray(img_src[y0:y0 + th, x0:x0 + tw])
             img, _ = self.precess_image(region, self.img_size, self.stride, self.half, auto=False)
             img = img.to(self.device)[None]
@@ -346,9 +397,25 @@ class Inferer:
                 det[:, :12] = self.rescale(img.shape[2:], det[:, :12], region.shape).round()
                 det_t[t, :len(det)] = det.detach().float().cpu().numpy()
             count_t[t] = len(det)
-        det, count, _ = merge_tiles_np(det_t, count_t, [(0,) + t for t in tiles], [img_src.shape], iou_thres, max_det,
-                                       self.merge_metric, border)
-        return torch.from_numpy(det[0, :int(count[0])].copy())
+        return det_t, count_t
+
+    def gated_rows_cpu(self, img_src, conf_thres, iou_thres, classes, agnostic_nms, max_det, border=1):
+        """``tiled_rows_cpu`` through ``TileGateNp`` (made at the first frame): the per-tile inference runs on the flagged tiles
+        only."""
+        if self._gate is None:
+            from yolov6.utils.tile_gate import TileGateNp
+            run = lambda frames, tiles, tmd: self._tiles_cpu(frames, tiles, tmd, conf_thres, iou_thres, classes, agnostic_nms)   # noqa: E731
+            self._gate = TileGateNp(run, [img_src.shape[:2]], self.tile, iou_thres, max_det, self.tile_overlap, self.tile_overview,
+                                    self.merge_metric, border, thres=self.tile_gate_thres, min_cells=self.tile_gate_min_cells,
+                                    refresh=self.tile_gate_refresh)
+        self._gate_check_shape(img_src.shape, self._gate.state.shapes[0])
+        return torch.from_numpy(self._gate.detect([img_src])[0])
+
+    @staticmethod
+    def _gate_check_shape(shape, first):
+        if tuple(shape[:2]) != tuple(first):
+            raise ValueError('tile_gate (--tile-gate) takes the source as one fixed camera: a frame of %d x %d after frames of %d x %d'
+                             % (shape[0], shape[1], first[0], first[1]))
 
     # ---- tracking (``track=True``) ---------------------------------------------------------------------------------------
     TRACK_SLOTS = 64        # tracks alive at once per stream

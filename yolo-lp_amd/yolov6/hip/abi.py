@@ -37,6 +37,7 @@ LP_REDACT_MAX_RADIUS = 48  # lp_redact_gauss_batch: largest blur radius (taps pe
 LP_LOOKBACK_MAX_DEPTH = 32    # lp_lookback_update: frames of delay
 LP_WATCH_MAX_ENTRIES, LP_WATCH_MAX_COST = 1 << 24, 32768   # lp_watch_match: entries of a watchlist, the largest cost of an entry
 LP_WATCH_BLOCK_ENTRIES, LP_WATCH_QUERY_BLOCK = 2048, 16   # ... entries per workgroup of its scan, reads per LDS table
+LP_TILE_GATE_TILE_WORDS = 8   # lp_tile_gate_update: int32 words per entry of the device tile table
 LP_EVAL_NCOUNTS = 43  # lp_eval_counts: length of the counts vector (include/lp_hip.h)
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # .../yolo-lp_amd
@@ -93,6 +94,11 @@ class RedactGaussParams(ctypes.Structure):
     """lp_redact_gauss_params"""
     _fields_ = [('margin', c_double), ('radius', c_int), ('radius_c', c_int), ('taps', ctypes.c_uint16 * (LP_REDACT_MAX_RADIUS + 1)),
                 ('taps_c', ctypes.c_uint16 * (LP_REDACT_MAX_RADIUS + 1))]
+
+
+class TileGateDesc(ctypes.Structure):
+    """lp_tile_gate_desc"""
+    _fields_ = [('p0', c_void_p), ('pitch0', c_int), ('h0', c_int), ('w0', c_int), ('format', c_int), ('blocks', c_void_p)]
 
 
 class TileRef(ctypes.Structure):
@@ -197,6 +203,9 @@ SYMBOLS = {
     'lp_watch_workspace_bytes': (c_size_t, [c_int, c_int]),
     'lp_watch_match': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
+    'lp_tile_gate_luma_batch': (c_int, [POINTER(TileGateDesc), c_int, c_void_p]),
+    'lp_tile_gate_update': (c_int, [POINTER(TileGateDesc), c_int, POINTER(c_int), c_int, c_void_p, POINTER(c_int), c_int, c_void_p,
+                                    ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'lp_eval_counts': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'lp_check_sigmoid_monotone': (c_int, [c_void_p, c_void_p]),
     'lp_debug_poison_lds': (c_int, [c_void_p]),
