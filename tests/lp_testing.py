@@ -232,6 +232,53 @@ def assert_elementwise(got, ref64, mag64, K, dtype, transcendental=False, slack6
                                 int((ratio > 1).sum()), ratio.numel()))
 
 
+# The precise expf of the device library (the build has no fast-math): its documented maximum error is 1 ulp (HIP's math API
+# tables); no copy of that document ships with the toolchain, so the figure is restated here, not read from it.
+DFL_EXP_ULPS = 1
+
+
+def dfl_box_bounds(dist64, mag64, pts64, st64, nb, exp_ulps=DFL_EXP_ULPS):
+    """Elementwise bounds of the box columns of a DFL head whose logits are exact fp32 values, derived from the operation count of
+    MODE_DECODE's DFL branch; nothing here is measured, and nothing depends on the engine's storage type (everything after the
+    logits is fp32).  ``dist64`` [..,N,4]: the float64 distances sum_i p_i proj_i of the four sides, ``mag64`` the same sum over
+    |proj_i|, ``pts64`` [N,2] / ``st64`` [N,1] the anchors.  -> (bound of prediction columns 0..3 (cx, cy, w, h), bound of
+    candidate-row columns 0..3 (x1, y1, x2, y2)), float64 [..,N,4].
+
+    With u = 2^-24 and E = ``exp_ulps``:
+      e_i = expf(z_i - m)     z_i - m is exact; E ulps = 2 E u relative
+      s = e_0 + ... (nb - 1 adds)      (2 E + nb - 1) u relative (all terms positive)
+      p_i = e_i / s           2 E + (2 E + nb - 1) + 1 = (4 E + nb) u
+      p_i * proj_i, then nb - 1 adds of same-signed or mixed terms: + nb u relative to sum p_i |proj_i|
+      => |d^ - d| <= 1.1 (4 E + 2 nb) u sum p_i |proj_i|          (1.1: the second-order terms)
+    Every fp32 operation of the decode then adds half an ulp of ITS result (<= u |result|, the result being within the incoming
+    error of the float64 one) and passes the incoming errors on linearly: c = ax -+ d, s = c1 + c2, w = c2 - c1, and for the
+    candidate rows cx -+ bw / 2; / 2 and * stride (a power of two) are exact."""
+    u = 2.0 ** -24
+    d, mag = dist64.double(), mag64.double()
+    a = torch.cat([pts64, pts64], -1).double()
+    st = st64.double()
+    half_ulp = lambda v, e: u * (v.abs() + e)
+    ed = 1.1 * (4 * exp_ulps + 2 * nb) * u * mag
+    c = a + d * torch.tensor([-1.0, -1.0, 1.0, 1.0], dtype=torch.float64)           # x1 y1 x2 y2 in grid units
+    ec = ed + half_ulp(c, ed)
+    e_in = ec[..., :2] + ec[..., 2:]
+    s, w = c[..., :2] + c[..., 2:], c[..., 2:] - c[..., :2]
+    es, ew = e_in + half_ulp(s, e_in), e_in + half_ulp(w, e_in)
+    pred_bound = torch.cat([es / 2, ew], -1) * st
+    cxy, wh = s / 2 * st, w * st
+    e_row = (es / 2 + ew / 2) * st
+    rows_bound = torch.cat([e_row + half_ulp(cxy - wh / 2, e_row), e_row + half_ulp(cxy + wh / 2, e_row)], -1)
+    return pred_bound, rows_bound
+
+
+def bound_excess(got, ref64, bound64):
+    """(max over elements of |got - ref64| / bound64, the ratios); a non-finite ``got`` counts as infinitely far."""
+    g = got.cpu().double()
+    ratio = (g - ref64.double()).abs() / bound64.double()
+    ratio = torch.where(torch.isfinite(g), ratio, torch.full_like(ratio, float('inf')))
+    return float(ratio.max()), ratio
+
+
 def _trim(B, h, w, cin, cout, k, budget=0.5e9):
     """Batch size of the exact test for a case of the parity tests: as many images as keep the float64 CPU reference under
     ``budget`` multiply-adds (the tile geometry of the block-tiled kernels depends on B: it gets a sweep of its own)."""
