@@ -747,7 +747,7 @@ int lp_lookback_update(void* state, int n_streams, int max_tracks, int depth, in
  * (cost, mismatch), then one atomic minimum and one atomic add per workgroup and read with a hit; a tail kernel writes match_i.
  * max_ended == 0 launches nothing; n_entries == 0 launches the tail alone.
  *   workspace: 16-byte aligned, lp_watch_workspace_bytes(n_streams, max_ended) bytes; it may hold anything on entry.
- * What it does not do: no insertions or deletions; no alert while a track is live (ended records only); one best entry plus a count,
+ * What it does not do: no insertions or deletions; no alert while a track is live (ended records only: lp_watch_live does that); one best entry plus a count,
  * not a ranked list; no update in place of the list.
  * Every argument is checked before the first launch (LP_ERR_ARG, nothing launched): n_entries outside 0..LP_WATCH_MAX_ENTRIES,
  * n_streams < 1, max_ended < 0, n_streams * max_ended * 12 at or above 2^31, max_mismatch outside 0..8, max_cost outside
@@ -761,6 +761,58 @@ size_t lp_watch_workspace_bytes(int n_streams, int max_ended);   /* 0: bad argum
 int lp_watch_match(const unsigned char* entries, int n_entries, const unsigned char* confuse /* NULL: all 16 */,
                    const int32_t* ended_i, const float* ended_f, const int32_t* ended_count, int n_streams, int max_ended,
                    int max_mismatch, int max_cost, int32_t* match_i, void* workspace, size_t workspace_bytes, void* stream);
+
+/* lp_watch_live: look the reads of the tracks that are still LIVE up in a watchlist, once per track and read.  lp_watch_match answers
+ * when a track has ended, max_age frames after the plate was last seen; a permit holder waiting at a barrier, or a stolen vehicle
+ * still in the picture, needs the answer while its track lives.  A memo per tracker slot keeps the answer, so that a track is looked
+ * up when it reaches min_hits detections and again only when its voted read changes: a stream of 25 frames a second with a handful of
+ * cars causes a handful of scans of the list per car, not 25 a second.  Called behind lp_track_update (any of its forms; behind
+ * lp_watch_match of the ended records if that runs too) on the same stream; all pointers but ncls are DEVICE pointers; nothing is
+ * uploaded or read back, nothing is allocated, capturable in a graph.  The tracker state is read, never written.  The reference has
+ * nothing here; yolov6/utils/watch_live.py::LiveWatchNp restates the rules below on every int32.
+ *   track_state: the state of lp_track_update (16-byte aligned) as its last call left it; ncls: HOST int [8], the tracker's.
+ *   memo: int32 [n_streams,max_tracks,8], 16-byte aligned, lp_watch_live_state_bytes bytes, all zero = empty (the caller zeroes it
+ *   once, zeroes a stream's part together with the tracker's, and zeroes all of it when the list or a limit changes):
+ *   id + 1, key_lo, key_hi, entry, mismatches, cost, n_hits, last_at_lookup.
+ * Every stream s < n_streams is processed, whether or not the tracker call gave it a frame; every slot t < max_tracks, in order:
+ *   1. a slot is live iff hits > 0; a slot that is not live gets a zero memo line;
+ *   2. its read is rule 8 of lp_track_update unchanged: best_p = the first index of the largest votes[p][0..ncls[p]) (0 for an
+ *      all-zero head), share_p = votes[p][best_p] / total[p] if total[p] > 0 else 0 (one fp32 division); key = the eight best_p as
+ *      bytes, best_0..3 in key_lo and best_4..7 in key_hi, least significant byte first;
+ *   3. it is a candidate iff it is live and hits >= min_hits (a missed slot, misses > 0, is a candidate like any other), and fresh
+ *      iff it is a candidate and (memo.id != id + 1 or memo.key != key);
+ *   4. the fresh slots of stream s in ascending slot order are its queries j = 0, 1, ..., in the ended-record layout (the record
+ *      the track would leave if it ended now): q_i[s][j] = (id, first, last, hits, best_0..7), q_f[s][j] = (share_0..7, box x1, y1,
+ *      x2, y2), q_slot[s][j] = t, q_count[s] = their number; lines past the count are zero, with q_slot -1
+ *      (q_i int32 / q_f fp32 [n_streams,max_tracks,12], q_slot int32 [n_streams,max_tracks], q_count int32 [n_streams]);
+ *   5. m = lp_watch_match(entries, confuse, q_i, q_f, q_count, max_ended = max_tracks, max_mismatch, max_cost), unchanged;
+ *   6. every fresh slot: memo[s][t] = (id + 1, key_lo, key_hi, m.entry, m.mismatches, m.cost, m.n_hits, last); a lookup that found
+ *      nothing is memoised too (entry -1), so it is not repeated;
+ *   7. live_i int32 [n_streams,max_tracks,8], 16-byte aligned, one row per slot: for a live slot whose memo holds its id
+ *      (id, entry, mismatches, cost, n_hits, fresh ? 1 : 0, hits, last_at_lookup); for every other slot (-1, -1, 0, 0, 0, 0, 0, 0).
+ * An alert is a row with fresh == 1 and entry >= 0; fresh == 0 and entry >= 0 is a standing hit.  A new track in a reused slot
+ * never inherits the memo (its id differs).  Every word of q_*, live_i is written by every call.
+ * Five launches: live_gather_kernel (one workgroup per stream, steps 1 to 4: thread t reads slot t's first 16 bytes and memo line;
+ * a slot that is not a candidate is not read further, nor is one whose memo holds its id with last == last_at_lookup, since votes
+ * change only on a match and a match sets last; the other candidates' heads are read by one thread per (slot, head); the fresh
+ * slots are numbered by ballot and prefix count), the three of lp_watch_match with its match_i in the workspace, and
+ * live_scatter_kernel (one workgroup per stream, steps 6 and 7).
+ *   workspace: 16-byte aligned, lp_watch_live_workspace_bytes(n_streams, max_tracks) bytes; it may hold anything on entry.
+ * What it does not do: the read is the one at the end of the tracker call (several frames of a stream in one call: at most one
+ * lookup per track); the memoised cost is as of the lookup (a read whose key stays while its shares move is not scored again; the
+ * ended-record match stays the final word); and, as lp_watch_match, no insertions or deletions, one best entry plus a count.
+ * Every argument is checked before the first launch (LP_ERR_ARG, nothing launched): n_streams < 1, max_tracks outside
+ * 1..LP_TRACK_MAX_TRACKS, n_streams * max_tracks * 12 at or above 2^31, ncls null or a width outside 1..LP_TRACK_MAX_CLS,
+ * min_hits < 1, n_entries outside 0..LP_WATCH_MAX_ENTRIES, max_mismatch outside 0..8, max_cost outside 0..LP_WATCH_MAX_COST, a null
+ * pointer (entries only with n_entries > 0; confuse may be NULL), track_state, memo, live_i or the workspace not 16-byte aligned,
+ * entries not 8-byte or confuse not 4-byte aligned (n_entries > 0), a workspace that is too small, and a written buffer (memo, q_*,
+ * live_i, workspace) that overlaps the state, the list or another one. */
+size_t lp_watch_live_state_bytes(int n_streams, int max_tracks);       /* of the memo; 0: bad arguments */
+size_t lp_watch_live_workspace_bytes(int n_streams, int max_tracks);   /* 0: bad arguments */
+int lp_watch_live(const void* track_state, int n_streams, int max_tracks, const int* ncls /* HOST [8] */, int min_hits, int32_t* memo,
+                  const unsigned char* entries, int n_entries, const unsigned char* confuse /* NULL: all 16 */,
+                  int max_mismatch, int max_cost, int32_t* q_i, float* q_f, int32_t* q_slot, int32_t* q_count, int32_t* live_i,
+                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* lp_tile_gate_luma_batch / lp_tile_gate_update: skip the unchanged tiles of fixed-camera frames in tiled detection.  On a fixed
  * camera nearly every tile of a frame shows the pixels of the frame before, and a tile that has not changed yields the same

@@ -7,7 +7,7 @@
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
     python tools/frames_bench.py --tile --gate [--gate-moving K] [--gate-thres F] [--gate-refresh N] [--nv12 [bt709]] [--tile-frame 2160 3840] [--runs 3]
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot] [--redact [--hold [--lookback D]]] [--nv12]
-                                 [--watch N [--watch-mismatch 1]]
+                                 [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
@@ -113,6 +113,9 @@ def parse():
                                                                       'random watchlist of N entries (lp_watch_match); every stream is '
                                                                       'flushed once per step so that there are reads')
     ap.add_argument('--watch-mismatch', type=int, default=1, help='with --watch: positions that may differ')
+    ap.add_argument('--watch-live', action='store_true', help='with --watch: also time the lookup of the live tracks (lp_watch_live), on a '
+                                                              'step with fresh reads and on one without')
+    ap.add_argument('--watch-live-min-hits', type=int, default=1, help='with --watch-live: detections a track needs before it is looked up')
     ap.add_argument('--nv12', nargs='?', const='bt709', default=None, choices=['bt601', 'bt709', 'bt601f', 'bt709f'], metavar='MATRIX',
                     help='also send the same seeded frames as NV12 with this matrix and compare (default matrix: bt709)')
     ap.add_argument('--runs', type=int, default=3, help='timed runs of the frames/s figures (the spread is reported)')
@@ -443,6 +446,8 @@ def track_mode(args, model, dev, tdt):
             out['redact'] = redact_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
         if args.watch:
             out['watch'] = watch_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
+            if args.watch_live:
+                out['watch_live'] = watch_live_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
 
         # the full case: 128 live tracks x 128 rows per stream, every pair above the threshold
         full = runtime.PlateTracker(B, max_tracks=128, max_age=0, ncls=model, device=dev)
@@ -509,6 +514,69 @@ def watch_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
     return dict(entries=N, max_mismatch=args.watch_mismatch, reps=args.reps, watch_ms=round(med, 4), reads_per_step=round(nreads, 1),
                 pairs_per_s=round(N * nreads / (med * 1e-3), 1), block_reads=QB, block_ms=round(bmed, 4),
                 block_pairs_per_s=round(N * QB / (bmed * 1e-3), 1), block_list_bytes_per_s=round(N * 8 / (bmed * 1e-3), 1))
+
+
+def watch_live_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
+    """--track --watch N --watch-live: device time of lp_watch_live behind the update, from events on one stream, on the seeded list
+    of ``watch_stages``.  Every step detects another batch of frames and updates the tracker with the lookup held back, then
+    enqueues the lookup three times: the first call sees the step's fresh reads (``fresh_reads_per_step`` of the
+    ``candidate_slots_per_step`` slots with enough hits; ``fresh_reads_runs`` lists them, since the seeded frames repeat and most
+    steps bring few); the second sees the same state again and so has no fresh read: the steady state a deployment pays in every
+    frame in which no track is new and no vote flips; the third follows a zeroed memo, so every candidate is fresh (``cold_ms``,
+    ``cold_reads``): the worst case.  ``track_ms`` is lp_track_update of the same step, for the ratio."""
+    import torch
+    from yolov6.hip import runtime
+    from yolov6.utils.track import ncls_of
+    size, stride = [args.size, args.size], int(model.stride.max())
+    B, conf, iou, max_det = args.track_batch, args.conf, args.iou, args.max_det
+    N, min_hits = args.watch, args.watch_live_min_hits
+    rng = np.random.default_rng(1)
+    wl = runtime.Watchlist(np.stack([rng.integers(0, n, N, dtype=np.uint8) for n in ncls_of(model)], 1), device=dev)
+    trk = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
+    trk.enable_live_watch(wl, min_hits, args.watch_mismatch)
+    times = dict(track=[], fresh=[], steady=[], cold=[])
+    fresh, steady_fresh, cand, cold = [], [], [], []
+    for k in range(args.reps + 2):
+        frames = batcher.put([pool[(j + k) % len(pool)] for j in range(B)])
+        xx, _ = runtime.preprocess_frames(frames, size, stride, tdt, batch=B, out=x)
+        det, count, _ = runtime.detect_padded(model, xx, conf, iou, max_det)
+        runtime.rescale_round_batch(det, count, net_hw, [f.shape for f in frames])
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        held, trk._live = trk._live, None          # the update alone; the lookup it would enqueue at its end follows by hand
+        ev[0].record()
+        trk.update(det, count)
+        ev[1].record()
+        trk._live = held
+        trk._live_watch()
+        ev[2].record()
+        n_fresh = trk.last_live_reads[3].sum()
+        n_fresh = int(n_fresh)                     # (a host read: between the two timed calls, not inside one)
+        mid = torch.cuda.Event(enable_timing=True)
+        mid.record()
+        trk._live_watch()
+        ev[3].record()
+        n_steady = int(trk.last_live_reads[3].sum())
+        trk.live_memo.zero_()
+        ev += [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[4].record()
+        trk._live_watch()
+        ev[5].record()
+        torch.cuda.synchronize()
+        if k >= 2:
+            times['track'].append(ev[0].elapsed_time(ev[1]))
+            times['fresh'].append(ev[1].elapsed_time(ev[2]))
+            times['steady'].append(mid.elapsed_time(ev[3]))
+            fresh.append(n_fresh)
+            times['cold'].append(ev[4].elapsed_time(ev[5]))
+            steady_fresh.append(n_steady)
+            cold.append(int(trk.last_live_reads[3].sum()))
+            cand.append(int((trk.state.view(B, -1)[:, 16:].view(B, 128, -1)[:, :, 3] >= min_hits).sum()))
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    return dict(entries=N, max_mismatch=args.watch_mismatch, min_hits=min_hits, reps=args.reps, watch_live_ms=round(med['fresh'], 4),
+                fresh_reads_per_step=round(float(np.mean(fresh)), 1), fresh_reads_runs=fresh, watch_live_runs_ms=[round(v, 4) for v in times['fresh']],
+                cold_ms=round(med['cold'], 4), cold_reads=round(float(np.mean(cold)), 1), candidate_slots_per_step=round(float(np.mean(cand)), 1),
+                steady_ms=round(med['steady'], 4), steady_fresh_reads=int(max(steady_fresh)), track_ms=round(med['track'], 4),
+                steady_over_track=round(med['steady'] / med['track'], 4))
 
 
 def redact_stages(args, model, dev, tdt, batcher, pool, x, net_hw):

@@ -9,7 +9,8 @@
                           [--redact mosaic|fill|gauss [--redact-cell 16] [--redact-sigma 8] [--redact-margin 0.1]
                            [--redact-hold [--redact-hold-min-hits 1] [--redact-lookback D [--redact-lookback-max-back N]]]]
                           [--track --watchlist FILE [--watch-mismatch 1] [--watch-cost F]
-                           [--watch-confusable "0D 0Q 8B 2Z 5S" [--watch-confusable-weight 4]]]
+                           [--watch-confusable "0D 0Q 8B 2Z 5S" [--watch-confusable-weight 4]]
+                           [--watch-live [--watch-live-min-hits 3]]]
                           [--tile H W --tile-gate [--tile-gate-thres 2.0] [--tile-gate-min-cells 1] [--tile-gate-refresh 50]]
 """
 import argparse
@@ -92,6 +93,9 @@ _FLAGS = [
     ('--watch-confusable', dict(type=str, default=None, metavar='PAIRS',
                                 help='with --watchlist: pairs of characters that are misread for each other, e.g. "0D 0Q 8B 2Z 5S"')),
     ('--watch-confusable-weight', dict(type=int, default=4, help='with --watch-confusable: what such a pair costs, in sixteenths of a mismatch (0..16)')),
+    ('--watch-live', dict(action='store_true', help='with --watchlist: also look a track up while it is still live, once it has enough '
+                                                    'detections and again when its voted read changes, and write alerts.txt')),
+    ('--watch-live-min-hits', dict(type=int, default=3, metavar='N', help='with --watch-live: detections a track needs before it is looked up')),
     ('--tile-gate', dict(action='store_true', help='with --tile: the source is one fixed camera (frames of one size); run the network only on '
                                                    'the tiles whose pixels changed since they were last detected, keep the rows of the others')),
     ('--tile-gate-thres', dict(type=float, default=2.0, metavar='F',
@@ -119,7 +123,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         track_expand=0.5, best_shots=False, nv12=None, nv12_size=None, redact=None, redact_cell=16,
         redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1, redact_lookback=None, redact_lookback_max_back=None,
         redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None, watch_confusable=None, watch_confusable_weight=4,
-        tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1, tile_gate_refresh=50):
+        watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1, tile_gate_refresh=50):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track or redact) and not osp.exists(out_dir):
@@ -137,7 +141,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
                       redact_hold_min_hits=redact_hold_min_hits, redact_lookback=redact_lookback,
                       redact_lookback_max_back=redact_lookback_max_back, redact_sigma=redact_sigma, watchlist=watchlist,
                       watch_mismatch=watch_mismatch, watch_cost=watch_cost, watch_confusable=watch_confusable,
-                      watch_confusable_weight=watch_confusable_weight, tile_gate=tile_gate, tile_gate_thres=tile_gate_thres,
+                      watch_confusable_weight=watch_confusable_weight, watch_live=watch_live, watch_live_min_hits=watch_live_min_hits,
+                      tile_gate=tile_gate, tile_gate_thres=tile_gate_thres,
                       tile_gate_min_cells=tile_gate_min_cells, tile_gate_refresh=tile_gate_refresh).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))

@@ -1,0 +1,262 @@
+// Looking the reads of LIVE plate tracks up in a watchlist, with a memo per track: lp_watch_live (include/lp_hip.h).  The ended-record
+// lookup of lp_watch_match fires when a track has been unseen for max_age frames; a car waiting at a barrier, or a stolen one still
+// in the picture, needs the answer while its track lives.  The reference has nothing here; the written-down specification is
+// yolov6/utils/watch_live.py (LiveWatchNp), which this file matches on every int32 (tests/test_watch_live_gpu.py).
+//
+// Two kernels, one in front of and one behind the unchanged scan of lp_watch.hip; both take one workgroup per stream and read the
+// tracker state as lp_track_update left it (layout: the header comment of lp_track.hip), never writing it.
+// live_gather_kernel, steps 1 to 4 of the rule: thread t < 128 reads slot t's first words (id, first, last, hits; 16 bytes) and its
+//   memo line.  A slot that is not live gets a zero memo line.  A candidate (hits >= min_hits) whose memo holds its id and whose
+//   `last` equals the memo's last_at_lookup cannot have a new key -- votes change only on a match, and a match sets `last` -- so it
+//   is not fresh and its votes are not read; this changes no output byte.  For every other candidate the eight threads
+//   (slot, head) each read one head: the argmax over ncls[p] <= 64 floats, lowest index on a tie, and the share, restating rule 8
+//   of lp_track.hip's read_head to the letter (tests pin the two together).  Thread t packs the key and decides `fresh`; the fresh
+//   slots are numbered in slot order by ballot and prefix count over the two waves of 128 slots, as track_kernel numbers ending
+//   tracks, and their lines go out in the ended-record layout.  Lines past the count are zeroed (q_slot -1), and pos[s][t] -- the
+//   query line of slot t, -1 for none -- is left in the workspace for the scatter.
+// lp_watch_match on (q_i, q_f, q_count) with max_ended = max_tracks; its match_i lies in the workspace.
+// live_scatter_kernel, steps 6 and 7: thread t memoises the answer of a fresh slot (key repacked from its query line) and writes the
+//   slot's row of live_i from the memo.
+#include "lp_internal.h"
+#include "lp_streams.h"
+
+namespace lp {
+
+namespace {
+
+constexpr int WL_SLOTS = LP_TRACK_MAX_TRACKS;   // 128
+constexpr int WL_HEADS = 8;
+constexpr int WL_T = WL_SLOTS * WL_HEADS;       // most threads of a gather workgroup: one per (slot, head)
+// the tracker state, restated from lp_track.hip: 16 header words per stream, 544 words per slot
+constexpr int WL_HDR_WORDS = 16, WL_W_BOX = 8, WL_W_TOTAL = 24, WL_W_VOTES = 32;
+constexpr int WL_SLOT_WORDS = WL_W_VOTES + WL_HEADS * LP_TRACK_MAX_CLS;
+constexpr int WL_Q_COLS = 12;                   // q_i / q_f: words of a line (the ended-record layout)
+constexpr int WL_MEMO_WORDS = 8, WL_LIVE_COLS = 8;
+static_assert(WL_SLOT_WORDS == 544 && WL_SLOTS == 128 && LP_TRACK_MAX_CLS == 64, "lp_watch_live.hip restates the state layout of lp_track.hip");
+
+struct LiveNcls { int v[WL_HEADS]; };
+
+struct LiveWs {                                 // carve-up of the caller's workspace, L = n_streams * max_tracks
+    int32_t* pos;                               // [L] query line of a slot, -1: none
+    int32_t* match_i;                           // [L, 4] of lp_watch_match
+    void* watch;                                // the workspace of lp_watch_match
+    size_t watch_bytes, bytes;
+};
+LiveWs live_carve(void* base, size_t S, size_t T) {
+    const size_t L = S * T, pos_bytes = (4 * L + 15) & ~(size_t)15;
+    char* p = (char*)base;
+    LiveWs w;
+    w.pos = (int32_t*)p;
+    w.match_i = (int32_t*)(p + pos_bytes);
+    w.watch = p + pos_bytes + 16 * L;
+    w.watch_bytes = lp_watch_workspace_bytes((int)S, (int)T);
+    w.bytes = pos_bytes + 16 * L + w.watch_bytes;
+    return w;
+}
+
+bool live_dims_ok(int n_streams, int max_tracks) {
+    return n_streams >= 1 && max_tracks >= 1 && max_tracks <= LP_TRACK_MAX_TRACKS && (long long)n_streams * max_tracks * WL_Q_COLS < 0x80000000ll;
+}
+
+// grid (n_streams), block (max(128, max_tracks * 8 rounded up to 64))
+__global__ __launch_bounds__(WL_T) void live_gather_kernel(const int* __restrict__ state, int T, long long sstride, const LiveNcls ncls, int min_hits,
+                                                          int32_t* __restrict__ memo, int32_t* __restrict__ q_i, float* __restrict__ q_f,
+                                                          int32_t* __restrict__ q_slot, int32_t* __restrict__ q_count, int32_t* __restrict__ pos) {
+    __shared__ int s_need[WL_SLOTS], s_pos[WL_SLOTS], s_best[WL_SLOTS * WL_HEADS];
+    __shared__ float s_share[WL_SLOTS * WL_HEADS];
+    __shared__ int s_wcnt[2];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* const sst = state + (long long)s * sstride + WL_HDR_WORDS;
+    const long long line0 = (long long)s * T;                          // first slot / query line of the stream; line0 + T <= S * T
+    const int hslot = tid >> 3, head = tid & 7;                        // the (slot, head) this thread serves
+    // ---- steps 1 and 3: live, candidate, and whether the votes have to be read ------------------------------------------------------
+    bool cand = false, need = false;
+    int m_id = 0, m_lo = 0, m_hi = 0;
+    if (tid < WL_SLOTS) {
+        if (tid < T) {
+            const int4 h = *(const int4*)(sst + (long long)tid * WL_SLOT_WORDS);       // id, first, last, hits
+            int4* mline = (int4*)(memo + (line0 + tid) * WL_MEMO_WORDS);
+            if (h.w > 0) {
+                const int4 m0 = mline[0];
+                m_id = m0.x; m_lo = m0.y; m_hi = m0.z;
+                cand = h.w >= min_hits;
+                need = cand && !(m_id == h.x + 1 && mline[1].w == h.z);
+            } else {
+                mline[0] = make_int4(0, 0, 0, 0);
+                mline[1] = make_int4(0, 0, 0, 0);
+            }
+        }
+        s_need[tid] = need ? 1 : 0;
+    }
+    __syncthreads();
+    // ---- step 2: rule 8, one thread per (slot, head) -------------------------------------------------------------------------------
+    if (hslot < T && s_need[hslot]) {
+        const int* sl = sst + (long long)hslot * WL_SLOT_WORDS;
+        const float* v = (const float*)(sl + WL_W_VOTES + head * LP_TRACK_MAX_CLS);
+        const int nc = ncls.v[head];
+        int bi = 0;
+        float bv = v[0];
+#pragma unroll 4
+        for (int c = 1; c < nc; ++c) {
+            const float x = v[c];
+            if (x > bv) { bv = x; bi = c; }
+        }
+        const float tot = __int_as_float(sl[WL_W_TOTAL + head]);
+        s_best[tid] = bi;
+        s_share[tid] = tot > 0.f ? bv / tot : 0.f;
+    }
+    __syncthreads();
+    // ---- steps 3 and 4: fresh slots, numbered in slot order ------------------------------------------------------------------------
+    bool fresh = false;
+    if (need) {
+        unsigned lo = 0, hi = 0;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            lo |= (unsigned)s_best[tid * WL_HEADS + p] << (8 * p);
+            hi |= (unsigned)s_best[tid * WL_HEADS + 4 + p] << (8 * p);
+        }
+        const int4 h = *(const int4*)(sst + (long long)tid * WL_SLOT_WORDS);
+        fresh = m_id != h.x + 1 || m_lo != (int)lo || m_hi != (int)hi;
+    }
+    const unsigned long long fm = __ballot(fresh);
+    if (tid < WL_SLOTS && lane == 0) s_wcnt[wave] = __popcll(fm);
+    __syncthreads();
+    const int nfresh = s_wcnt[0] + s_wcnt[1];
+    if (tid < WL_SLOTS) {
+        const int j = fresh ? (wave == 1 ? s_wcnt[0] : 0) + __popcll(fm & ((1ull << lane) - 1ull)) : -1;
+        s_pos[tid] = j;
+        if (tid < T) {
+            pos[line0 + tid] = j;
+            if (fresh) q_slot[line0 + j] = tid;
+            if (tid >= nfresh) q_slot[line0 + tid] = -1;
+        }
+    }
+    if (tid == 0) q_count[s] = nfresh;
+    __syncthreads();
+    if (hslot < T && s_pos[hslot] >= 0) {                              // the record the track would leave if it ended now
+        const int* sl = sst + (long long)hslot * WL_SLOT_WORDS;
+        int32_t* ri = q_i + (line0 + s_pos[hslot]) * WL_Q_COLS;
+        float* rf = q_f + (line0 + s_pos[hslot]) * WL_Q_COLS;
+        ri[4 + head] = s_best[tid];
+        rf[head] = s_share[tid];
+        if (head < 4) { ri[head] = sl[head]; rf[8 + head] = __int_as_float(sl[WL_W_BOX + head]); }
+    }
+    for (int w = nfresh * WL_Q_COLS + tid; w < T * WL_Q_COLS; w += blockDim.x) {       // the lines past the count
+        q_i[line0 * WL_Q_COLS + w] = 0;
+        q_f[line0 * WL_Q_COLS + w] = 0.f;
+    }
+}
+
+// grid (n_streams), block (128)
+__global__ __launch_bounds__(WL_SLOTS) void live_scatter_kernel(const int* __restrict__ state, int T, long long sstride,
+                                                               const int32_t* __restrict__ q_i, const int32_t* __restrict__ pos,
+                                                               const int32_t* __restrict__ match_i, int32_t* __restrict__ memo,
+                                                               int32_t* __restrict__ live_i) {
+    const int s = blockIdx.x, t = threadIdx.x;
+    if (t >= T) return;
+    const long long line = (long long)s * T + t;
+    const int4 h = *(const int4*)(state + (long long)s * sstride + WL_HDR_WORDS + (long long)t * WL_SLOT_WORDS);   // id, first, last, hits
+    int4* mline = (int4*)(memo + line * WL_MEMO_WORDS);
+    int4 out0 = make_int4(-1, -1, 0, 0), out1 = make_int4(0, 0, 0, 0);
+    const int j = pos[line];
+    if (j >= 0) {                                                      // step 6 (a fresh slot is live)
+        const int32_t* ri = q_i + ((long long)s * T + j) * WL_Q_COLS;
+        const int4 m = *(const int4*)(match_i + ((long long)s * T + j) * 4);            // entry, mismatches, cost, n_hits
+        unsigned lo = 0, hi = 0;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            lo |= (unsigned)ri[4 + p] << (8 * p);
+            hi |= (unsigned)ri[8 + p] << (8 * p);
+        }
+        mline[0] = make_int4(h.x + 1, (int)lo, (int)hi, m.x);
+        mline[1] = make_int4(m.y, m.z, m.w, h.z);
+        out0 = make_int4(h.x, m.x, m.y, m.z);
+        out1 = make_int4(m.w, 1, h.w, h.z);
+    } else if (h.w > 0) {
+        const int4 m0 = mline[0];
+        if (m0.x == h.x + 1) {
+            const int4 m1 = mline[1];
+            out0 = make_int4(h.x, m0.w, m1.x, m1.y);
+            out1 = make_int4(m1.z, 0, h.w, m1.w);
+        }
+    }
+    int4* row = (int4*)(live_i + line * WL_LIVE_COLS);
+    row[0] = out0;
+    row[1] = out1;
+}
+
+}  // namespace
+
+}  // namespace lp
+
+using namespace lp;
+
+extern "C" size_t lp_watch_live_state_bytes(int n_streams, int max_tracks) {
+    if (!live_dims_ok(n_streams, max_tracks)) return 0;
+    return (size_t)n_streams * max_tracks * WL_MEMO_WORDS * 4;
+}
+
+extern "C" size_t lp_watch_live_workspace_bytes(int n_streams, int max_tracks) {
+    if (!live_dims_ok(n_streams, max_tracks)) return 0;
+    return live_carve(nullptr, (size_t)n_streams, (size_t)max_tracks).bytes;
+}
+
+extern "C" int lp_watch_live(const void* track_state, int n_streams, int max_tracks, const int* ncls, int min_hits, int32_t* memo,
+                             const unsigned char* entries, int n_entries, const unsigned char* confuse, int max_mismatch, int max_cost,
+                             int32_t* q_i, float* q_f, int32_t* q_slot, int32_t* q_count, int32_t* live_i, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    const std::string fn = "lp_watch_live: ";
+    if (!live_dims_ok(n_streams, max_tracks))
+        return fail(LP_ERR_ARG, fn + "need n_streams >= 1, max_tracks in 1.." + std::to_string(LP_TRACK_MAX_TRACKS) +
+                                    " and n_streams * max_tracks * 12 < 2^31");
+    if (!ncls) return fail(LP_ERR_ARG, fn + "null pointer (ncls)");
+    LiveNcls nc;
+    for (int h = 0; h < WL_HEADS; ++h) {
+        if (ncls[h] < 1 || ncls[h] > LP_TRACK_MAX_CLS)
+            return fail(LP_ERR_ARG, fn + "ncls of head " + std::to_string(h) + " must be in 1.." + std::to_string(LP_TRACK_MAX_CLS));
+        nc.v[h] = ncls[h];
+    }
+    if (min_hits < 1) return fail(LP_ERR_ARG, fn + "min_hits must be >= 1");
+    if (n_entries < 0 || n_entries > LP_WATCH_MAX_ENTRIES)
+        return fail(LP_ERR_ARG, fn + "n_entries " + std::to_string(n_entries) + " (need 0.." + std::to_string(LP_WATCH_MAX_ENTRIES) + ")");
+    if (max_mismatch < 0 || max_mismatch > 8 || max_cost < 0 || max_cost > LP_WATCH_MAX_COST)
+        return fail(LP_ERR_ARG, fn + "need max_mismatch in 0..8 and max_cost in 0.." + std::to_string(LP_WATCH_MAX_COST));
+    if (!track_state || !memo || !q_i || !q_f || !q_slot || !q_count || !live_i || !workspace || (n_entries > 0 && !entries))
+        return fail(LP_ERR_ARG, fn + "null pointer");
+    if (((uintptr_t)track_state & 15) != 0 || ((uintptr_t)memo & 15) != 0 || ((uintptr_t)live_i & 15) != 0 || ((uintptr_t)workspace & 15) != 0)
+        return fail(LP_ERR_ARG, fn + "the tracker state, the memo, live_i and the workspace must be 16-byte aligned");
+    if (n_entries > 0 && (((uintptr_t)entries & 7) != 0 || ((uintptr_t)confuse & 3) != 0))
+        return fail(LP_ERR_ARG, fn + "entries must be 8-byte and confuse 4-byte aligned");
+    const LiveWs ws = live_carve(workspace, (size_t)n_streams, (size_t)max_tracks);
+    if (workspace_bytes < ws.bytes)
+        return fail(LP_ERR_ARG, fn + "workspace of " + std::to_string(workspace_bytes) + " bytes, need " + std::to_string(ws.bytes));
+    const long long sstride = (long long)WL_HDR_WORDS + (long long)max_tracks * WL_SLOT_WORDS;
+    {   // no buffer that is written may overlap the state, the list or another one
+        const size_t L = (size_t)n_streams * max_tracks;
+        const Region reg[] = {{track_state, (size_t)n_streams * (size_t)sstride * 4, false},
+                              {entries, (size_t)n_entries * 8, false},
+                              {confuse, n_entries > 0 && confuse ? (size_t)3 * 64 * 64 : 0, false},
+                              {memo, L * WL_MEMO_WORDS * 4, true},
+                              {q_i, L * WL_Q_COLS * 4, true},
+                              {q_f, L * WL_Q_COLS * 4, true},
+                              {q_slot, L * 4, true},
+                              {q_count, (size_t)n_streams * 4, true},
+                              {live_i, L * WL_LIVE_COLS * 4, true},
+                              {workspace, ws.bytes, true}};
+        if (regions_clash(reg, (int)(sizeof(reg) / sizeof(reg[0]))))
+            return fail(LP_ERR_ARG, fn + "the memo, the queries, live_i and the workspace may overlap neither an input nor each other");
+    }
+
+    hipStream_t st = (hipStream_t)stream;
+    const int threads = max_tracks * WL_HEADS <= WL_SLOTS ? WL_SLOTS : round_up(max_tracks * WL_HEADS, 64);
+    hipLaunchKernelGGL(live_gather_kernel, dim3((unsigned)n_streams), dim3((unsigned)threads), 0, st, (const int*)track_state, max_tracks, sstride, nc,
+                       min_hits, memo, q_i, q_f, q_slot, q_count, ws.pos);
+    LP_HIP_CHECK(hipGetLastError());
+    if (int rc = lp_watch_match(entries, n_entries, confuse, q_i, q_f, q_count, n_streams, max_tracks, max_mismatch, max_cost, ws.match_i, ws.watch,
+                                ws.watch_bytes, stream))
+        return rc;
+    hipLaunchKernelGGL(live_scatter_kernel, dim3((unsigned)n_streams), dim3(WL_SLOTS), 0, st, (const int*)track_state, max_tracks, sstride, q_i, ws.pos,
+                       ws.match_i, memo, live_i);
+    LP_HIP_CHECK(hipGetLastError());
+    return LP_OK;
+}

@@ -53,8 +53,8 @@ class Inferer:
                  tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5, best_shots=False,
                  nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1,
                  redact_lookback=None, redact_lookback_max_back=None, redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None,
-                 watch_confusable=None, watch_confusable_weight=4, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1,
-                 tile_gate_refresh=50):
+                 watch_confusable=None, watch_confusable_weight=4, watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0,
+                 tile_gate_min_cells=1, tile_gate_refresh=50):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -86,6 +86,9 @@ class Inferer:
         positions of a total cost of at most ``watch_cost`` fully confident mismatches (None: no limit); ``watch_confusable`` =
         pairs of characters of the ``ads`` names (``'0D 0Q 8B 2Z 5S'``) that cost only ``watch_confusable_weight`` sixteenths of a
         mismatch.  ``infer`` writes ``hits.txt`` beside ``plates.txt``; every other output is what it is without it.
+        ``watch_live`` (with ``watchlist``): a track is also looked up while it is still live, as soon as it has
+        ``watch_live_min_hits`` detections and again whenever its voted read changes (``yolov6.utils.watch_live`` states the rule;
+        the limits are those of ``watchlist``); ``infer`` writes ``alerts.txt``.
         ``tile_gate`` (with ``tile``): the whole source is ONE fixed-camera stream, every frame of the size of the first (another
         size raises); a tile is run through the network only when a 16 x 16 cell of it has changed by more than ``tile_gate_thres``
         luma levels per pixel (in at least ``tile_gate_min_cells`` cells) since the tile was last detected, or every
@@ -102,6 +105,11 @@ class Inferer:
             if not track:
                 raise ValueError('watchlist needs track=True')
             check_params(watch_mismatch, cost_units(watch_cost))
+        if watch_live:
+            from yolov6.utils.watch_live import check_min_hits
+            if watchlist is None:
+                raise ValueError('watch_live needs watchlist=FILE')
+            check_min_hits(watch_live_min_hits)
         if redact is not None:
             from yolov6.utils.redact import check_params, check_sigma
             if check_params(redact, redact_cell, redact_margin)[0] == 2:
@@ -185,6 +193,9 @@ class Inferer:
         With ``watchlist`` ``<save_dir>/hits.txt`` has one line ``id first last text entry entry_text mismatches cost n_hits`` per
         ended track whose read an entry of the list accepts: the line of ``plates.txt`` up to the text, the index and text of the
         accepted entry of the smallest (cost, index), its two sums, and the number of accepted entries (above 1: ambiguous).
+        With ``watch_live`` ``<save_dir>/alerts.txt`` has one line ``frame id text entry entry_text mismatches cost n_hits hits``
+        per alert, in the order they fired: the stream frame of the detection that caused the lookup, the track's id and read at
+        that moment, the accepted entry as in ``hits.txt``, and the detections the track had.
 
         With ``redact`` every frame is also written, its plates redacted along the rows returned, as
         ``<save_dir>/redacted/<image name>`` (``.png`` for a frame of a video or a raw stream)."""
@@ -444,6 +455,9 @@ class Inferer:
                 confuse = watch.confuse_table(watch.confusable_pairs(self.watch_confusable), 2, self.watch_confusable_weight, self.ads_names)
             wl = runtime.Watchlist(entries, confuse, self.device) if self.device.type != 'cpu' else watch.WatchlistNp(entries, confuse)
             self._tracker.enable_watch(wl, self.watch_mismatch, self.watch_cost)
+            if self.watch_live:
+                self._tracker.enable_live_watch(wl, self.watch_live_min_hits, self.watch_mismatch, self.watch_cost)
+        self._track_alerts = []         # with watch_live: (frame, id, best [8], entry, mismatches, cost, n_hits, hits) per alert
         if self.redact_hold:
             self._tracker.enable_hold(min_hits=self.redact_hold_min_hits)
         if self.redact_lookback is not None:
@@ -483,6 +497,14 @@ class Inferer:
                     crop = shot_crops[s, k] if shot_i[s, k, 3] else None
                     crop = crop.cpu().numpy() if torch.is_tensor(crop) else (None if crop is None else crop.copy())
                     self._track_shots.append((shot_i[s, k].copy(), int(shot_q[s, k]), crop))
+        if self._tracker.last_live is not None:     # the alerts of the same update
+            from yolov6.utils.watch_live import alerts_of
+            live_i, (q_i, _, q_slot, _) = self._tracker.last_live, self._tracker.last_live_reads
+            if torch.is_tensor(live_i):
+                live_i, q_i, q_slot = live_i.cpu().numpy(), q_i.cpu().numpy(), q_slot.cpu().numpy()
+            for s, t in alerts_of(live_i):
+                row, j = live_i[s, t], int(np.nonzero(q_slot[s] == t)[0][0])
+                self._track_alerts.append((row[7], row[0], q_i[s, j, 4:12].copy()) + tuple(row[1:5]) + (row[6],))
 
     def _track_update(self, det, count, paths, frames=None):
         """One tracker update of a padded group: det [B,max_det,28] + count [B] (numpy on the CPU, device tensors on a GPU) of
@@ -551,6 +573,14 @@ class Inferer:
                     if m[0] >= 0:
                         f.write('%d %d %d %s %d %s %d %d %d\n' % (ri[0], ri[1], ri[2], plate_text(ri[4:12], *names), m[0],
                                                                   entry_text(entries[m[0]], *names), m[1], m[2], m[3]))
+        if self.watch_live:
+            from yolov6.utils.watch import entry_text
+            names = (self.pro_names, self.alp_names, self.ads_names)
+            entries = self._tracker._watch[0].entries_np
+            with open(osp.join(save_dir, 'alerts.txt'), 'w') as f:
+                for frame, tid, best, e, mism, cost, n, hits in self._track_alerts:
+                    f.write('%d %d %s %d %s %d %d %d %d\n' % (frame, tid, plate_text(best, *names), e, entry_text(entries[e], *names), mism,
+                                                              cost, n, hits))
         if self.best_shots:
             from PIL import Image
             os.makedirs(osp.join(save_dir, 'shots'), exist_ok=True)

@@ -203,6 +203,10 @@ SYMBOLS = {
     'lp_watch_workspace_bytes': (c_size_t, [c_int, c_int]),
     'lp_watch_match': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
+    'lp_watch_live_state_bytes': (c_size_t, [c_int, c_int]),
+    'lp_watch_live_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'lp_watch_live': (c_int, [c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'lp_tile_gate_luma_batch': (c_int, [POINTER(TileGateDesc), c_int, c_void_p]),
     'lp_tile_gate_update': (c_int, [POINTER(TileGateDesc), c_int, POINTER(c_int), c_int, c_void_p, POINTER(c_int), c_int, c_void_p,
                                     ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

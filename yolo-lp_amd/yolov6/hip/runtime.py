@@ -1642,11 +1642,18 @@ class PlateTracker:
         self._watch = None
         #: match_i [S,max_ended,4] int32 of the last ``update`` after ``enable_watch``, line-parallel to its ended_i, else None
         self.last_watch = None
+        self._live = None
+        #: live_i [S,max_tracks,8] int32 of the last ``update`` after ``enable_live_watch``, else None
+        self.last_live = None
+        #: (q_i, q_f, q_slot, q_count) of that lookup: the fresh reads in the ended-record layout, else None
+        self.last_live_reads = None
 
     def reset(self, streams=None):
         """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0; their best-shot
-        galleries (``enable_best_shot``) are emptied with them."""
+        galleries (``enable_best_shot``) are emptied with them, and their memo of ``enable_live_watch``."""
         _zero_streams(self.state, self.n_streams, streams)
+        if self._live is not None:
+            _zero_streams(self._live['memo'], self.n_streams, streams)
         if self._shots is not None:
             _zero_streams(self._shots['state'], self.n_streams, streams)
 
@@ -1687,7 +1694,58 @@ class PlateTracker:
         if self._watch is not None:
             wl, mm, mc = self._watch
             self.last_watch = wl._match(ended_i, ended_f, ended_count, mm, mc)
+        if self._live is not None:
+            self._live_watch()
         return out
+
+    # ---- the live tracks looked up in a watchlist (lp_watch_live; yolov6/utils/watch_live.py states the rule) -----------------
+    def enable_live_watch(self, watchlist, min_hits=3, max_mismatch=1, max_cost=None):
+        """From now on every ``update`` / ``update_with_shots`` / ``flush_all*`` also enqueues, at its end on the same stream
+        (behind the lookup of ``enable_watch`` if that is on), the lookup of the LIVE tracks of at least ``min_hits`` hits in
+        ``watchlist`` (a ``Watchlist`` on this device): once per track when it gets there, and again only when its voted read
+        changes; a memo per slot, owned by the tracker, holds the answers.  ``last_live`` = live_i [S,max_tracks,8] int32, one
+        row per slot: (id, entry, mismatches, cost, n_hits, fresh, hits, last_at_lookup), or (-1, -1, 0, 0, 0, 0, 0, 0) for a
+        slot without a looked-up track; a row with fresh == 1 and entry >= 0 is an alert.  ``last_live_reads`` = (q_i, q_f,
+        q_slot, q_count): the reads looked up in this call.  Persistent buffers, no host read, no allocation per call.  Returns,
+        state and every other buffer are what they are without it.  Calling it again zeroes the memo;
+        ``enable_live_watch(None)`` turns it off.  ``PlateTrackerNp.enable_live_watch`` is the same on the CPU, on every int32."""
+        from yolov6.utils import watch, watch_live
+        self.last_live = self.last_live_reads = None
+        if watchlist is None:
+            self._live = None
+            return
+        if not isinstance(watchlist, Watchlist) or watchlist.device != self.device:
+            raise ValueError('enable_live_watch needs a Watchlist on the tracker\'s device %s' % self.device)
+        min_hits = watch_live.check_min_hits(min_hits)
+        mm, mc = watch.check_params(max_mismatch, watch.cost_units(max_cost))
+        S, T, dev, lib = self.n_streams, self.max_tracks, self.device, abi.load()
+        i32 = dict(dtype=torch.int32, device=dev)
+        self._live = dict(
+            watchlist=watchlist, min_hits=min_hits, limits=(mm, mc), ncls=(ctypes.c_int * 8)(*self.ncls),
+            memo=torch.zeros(lib.lp_watch_live_state_bytes(S, T) // 4, **i32).view(S, T, 8),
+            live_i=torch.empty(S, T, 8, **i32), q_i=torch.empty(S, T, 12, **i32),
+            q_f=torch.empty(S, T, 12, dtype=torch.float32, device=dev), q_slot=torch.empty(S, T, **i32), q_count=torch.empty(S, **i32),
+            ws=torch.empty(lib.lp_watch_live_workspace_bytes(S, T) + 256, dtype=torch.uint8, device=dev))
+
+    @property
+    def live_memo(self):
+        """The memo of ``enable_live_watch``: int32 [S,max_tracks,8] on the device (id + 1, key_lo, key_hi, entry, mismatches,
+        cost, n_hits, last_at_lookup), else None."""
+        return None if self._live is None else self._live['memo']
+
+    def _live_watch(self):
+        """Enqueue lp_watch_live on the state as it stands."""
+        lw = self._live
+        wl, ws = lw['watchlist'], lw['ws']
+        base = _aligned(ws)
+        with torch.cuda.device(self.device):
+            abi.check(abi.load().lp_watch_live(_dptr(self.state), self.n_streams, self.max_tracks, lw['ncls'], lw['min_hits'], _dptr(lw['memo']),
+                                               _dptr(wl.entries), wl.n, _dptr(wl.confuse), lw['limits'][0], lw['limits'][1], _dptr(lw['q_i']),
+                                               _dptr(lw['q_f']), _dptr(lw['q_slot']), _dptr(lw['q_count']), _dptr(lw['live_i']),
+                                               ctypes.c_void_p(base), ws.numel() - (base - ws.data_ptr()), _stream_ptr(self.device)),
+                      'lp_watch_live')
+        self.last_live = lw['live_i']
+        self.last_live_reads = (lw['q_i'], lw['q_f'], lw['q_slot'], lw['q_count'])
 
     # ---- the ended reads looked up in a watchlist (lp_watch_match; yolov6/utils/watch.py states the rule) ----------------------
     def enable_watch(self, watchlist, max_mismatch=1, max_cost=None):

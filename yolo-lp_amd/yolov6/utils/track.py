@@ -183,6 +183,11 @@ class PlateTrackerNp:
         self._watch = None
         #: match_i [S, max_ended, 4] int32 of the last ``update`` after ``enable_watch``, line-parallel to its ended_i, else None
         self.last_watch = None
+        self._live = None
+        #: live_i [S, max_tracks, 8] int32 of the last ``update`` after ``enable_live_watch``, else None
+        self.last_live = None
+        #: (q_i, q_f, q_slot, q_count) of that lookup: the fresh reads in the ended-record layout, else None
+        self.last_live_reads = None
 
     _SLOT_ARRAYS = ('id', 'first', 'last', 'hits', 'misses', 'box', 'cor', 'vel', 'votes', 'total')
 
@@ -191,6 +196,8 @@ class PlateTrackerNp:
         for s in (range(self.n_streams) if streams is None else streams):
             for name in self._SLOT_ARRAYS + ('frame', 'next_id', 'dropped'):
                 getattr(self, name)[s] = 0
+        if self._live is not None:
+            self._live.reset(streams)
 
     def enable_hold(self, min_hits=1, max_misses=None):
         """From now on every ``update`` also fills ``hold_buffers`` (rule 11): the frame's rows followed by a predicted row for
@@ -209,6 +216,16 @@ class PlateTrackerNp:
         from yolov6.utils import watch
         self.last_watch = None
         self._watch = None if watchlist is None else (watchlist,) + watch.check_params(max_mismatch, watch.cost_units(max_cost))
+
+    def enable_live_watch(self, watchlist, min_hits=3, max_mismatch=1, max_cost=None):
+        """From now on every ``update`` / ``flush_all`` also looks the reads of the LIVE tracks of at least ``min_hits`` hits up in
+        ``watchlist``, once per track and voted read (``yolov6.utils.watch_live`` states the rule), and leaves live_i
+        [S, max_tracks, 8] int32 in ``last_live`` and the fresh reads (q_i, q_f, q_slot, q_count) in ``last_live_reads``.  Every
+        other output and the state stay what they are.  Calling it again starts from an empty memo; ``enable_live_watch(None)``
+        turns it off."""
+        from yolov6.utils.watch_live import LiveWatchNp
+        self.last_live = self.last_live_reads = None
+        self._live = None if watchlist is None else LiveWatchNp(self, watchlist, min_hits, max_mismatch, max_cost)
 
     def hold_buffers(self, B, max_det):
         """The persistent (det_hold [B,max_det+max_tracks,28] fp32, count_hold [B] int32, tid_hold [B,max_det+max_tracks] int32)
@@ -409,4 +426,8 @@ class PlateTrackerNp:
             from yolov6.utils.watch import watch_match_np
             wl, mm, mc = self._watch
             self.last_watch = watch_match_np(wl.entries_np, wl.confuse_np, ended_i, ended_f, ended_count, mm, mc)
+        if self._live is not None:
+            lw = self._live
+            self.last_live = lw.step()
+            self.last_live_reads = (lw.q_i, lw.q_f, lw.q_slot, lw.q_count)
         return det_out, tid, ended_i, ended_f, ended_count

@@ -30,7 +30,7 @@ Rules:
      every line when N = 0.
 
 What it does not do: no insertions or deletions (a read that lost or gained a character matches nothing nearby); no alert while a
-track is still live (ended records only); one best entry plus a count, not a ranked list; no persistence or update in place of
+track is still live (ended records only: ``yolov6.utils.watch_live`` does that); one best entry plus a count, not a ranked list; no persistence or update in place of
 the list (a changed list is a new ``Watchlist``).
 """
 import numpy as np
