@@ -13,6 +13,19 @@
  *     allocates no device memory.  `stream` is a hipStream_t passed as void* (NULL = default stream).
  *   - activations inside an engine are NHWC with the channel count padded to a multiple of 8; the element
  *     type is the engine's activation dtype (lp_dtype).  Accumulation is always fp32 (MFMA).
+ *   - what an op writes (tests/test_containment_gpu.py): ALL stored channels of every pixel of its destination tensors, the
+ *     padding channels (logical count up to the next multiple of 8; the space-to-depth input: 12 up to 16) as zero whatever
+ *     the memory held before -- consumers multiply them by zero-packed weights, and a stale Inf there would become NaN --
+ *     and no other byte: not of the arena (other tensors, the up to 255 bytes between a tensor's end and the next 256-byte
+ *     boundary, the arena's last 256 bytes), not in front of or behind it, not in the caller's frame.  A tensor whose op a
+ *     fused form carries (fused stem, fused 1x1 + 3x3 stride 2, fused BiFusion, the planar stem's space-to-depth input) is
+ *     not written at all.  lp_engine_forward writes all B * num_anchors * LP_PRED_COLS floats of pred and nothing around
+ *     them.  lp_engine_forward_det writes inside `workspace` (and, for levels whose class predictors do not fit the row
+ *     kernel, the prediction scratch behind the arena's last tensor): of an anchor that does not pass the confidence mask,
+ *     columns 12..27 of its candidate row are never written, and columns 0..11 only where the level's box predictors run
+ *     in the dense form (LP_VARIANT_BOX_DENSE, or a level that does not fit the streaming box kernel, e.g. a DFL head),
+ *     which computes the box columns of every anchor.  lp_nms / lp_nms_candidates write det, count, keep (every element:
+ *     rows past count[b] zero, keep -1 there) and the workspace; lp_nms also the obj * cls products into pred.
  */
 #ifndef LP_HIP_H
 #define LP_HIP_H

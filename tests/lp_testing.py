@@ -759,3 +759,172 @@ def linear_u8_bar(src_hw):
       (+2) >> 2 of an integer number of quarter levels: the result minus the quarter-level value is one of 0, -1/4, +1/4, +1/2"""
     w = sum(255.0 * (0.5 / 2048 + float(np.spacing(np.float32(s))) / 2) for s in src_hw)
     return -(0.25 + 0.5 + 1.0 / 128 + w) - 1e-9, 0.5 + w + 1e-9
+
+
+# ---- containment: which bytes of a buffer did a run change (tests/test_containment_cpu.py, tests/test_containment_gpu.py) ---------
+def merge_intervals(intervals):
+    """Sorted union of half-open byte intervals [a, b): empty ones dropped, overlapping and adjacent ones merged."""
+    out = []
+    for a, b in sorted((int(a), int(b)) for a, b in intervals):
+        if b <= a:
+            continue
+        if out and a <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], b)
+        else:
+            out.append([a, b])
+    return [(a, b) for a, b in out]
+
+
+def layout_regions(base, need, total, tensors):
+    """Named regions (name, a, b) that tile a buffer of ``total`` bytes holding an arena of ``need`` bytes at offset ``base`` (the
+    256-byte aligned start inside the allocation): ``tensors`` = (name, offset in the arena, bytes) back to back, each rounded up to
+    256 bytes.  'unaligned head', the tensors, 'slack after <name>' (the rounding), 'behind the tensors' (whatever the arena holds
+    behind its last tensor, e.g. a prediction scratch), 'arena tail' (the arena's last 256 bytes) and 'allocation slack'."""
+    out = [('unaligned head', 0, base)]
+    end = 0
+    for name, off, nbytes in sorted(tensors, key=lambda t: t[1]):
+        if nbytes == 0:
+            continue
+        assert off >= end and off % 256 == 0, (name, off, end)
+        if off > end:
+            out.append(('gap before ' + name, base + end, base + off))
+        out.append((name, base + off, base + off + nbytes))
+        end = (off + nbytes + 255) // 256 * 256
+        out.append(('slack after ' + name, base + off + nbytes, base + end))
+    assert end + 256 <= need <= total - base, (end, need, total, base)
+    out += [('behind the tensors', base + end, base + need - 256), ('arena tail', base + need - 256, base + need),
+            ('allocation slack', base + need, total)]
+    return [r for r in out if r[2] > r[1]]
+
+
+class ByteWatch:
+    """Which bytes of a 1-D uint8 buffer changed since a snapshot, outside a set of allowed byte intervals.  The comparison runs on
+    the buffer's device; a check that finds nothing costs one synchronisation (the count), one that finds something reads the
+    offsets back as well.  ``regions``: (name, a, b) of the buffer, used to say where a changed byte lies."""
+
+    def __init__(self, buf, regions=()):
+        assert buf.dtype == torch.uint8 and buf.dim() == 1 and buf.is_contiguous()
+        self.buf, self.regions = buf, sorted((str(n), int(a), int(b)) for n, a, b in regions)
+        self._masks = {}
+        self.snapshot()
+
+    def snapshot(self):
+        self.snap = self.buf.clone()
+
+    def _watched(self, allowed):
+        key = tuple(merge_intervals((max(0, a), min(self.buf.numel(), b)) for a, b in allowed))
+        if key not in self._masks:
+            m = torch.ones(self.buf.numel(), dtype=torch.bool, device=self.buf.device)
+            for a, b in key:
+                m[a:b] = False
+            self._masks = {key: m}                       # one mask at a time: a walk repeats the same allowed set
+        return self._masks[key]
+
+    def changed(self, allowed):
+        """bool [n] on the device: changed and not allowed."""
+        return (self.buf != self.snap) & self._watched(allowed)
+
+    def count(self, allowed):
+        """0-d tensor on the device (no synchronisation): number of changed bytes outside ``allowed``."""
+        return self.changed(allowed).sum()
+
+    def region_of(self, off):
+        for name, a, b in self.regions:
+            if a <= off < b:
+                return name
+        return 'unnamed'
+
+    def report(self, allowed):
+        """dict: ``count``, ``first``, ``last`` (offsets, None when nothing changed), ``offsets`` (int64 numpy array of every changed
+        byte outside ``allowed``) and ``regions``: [(name, count, first, last)] in buffer order."""
+        bad = self.changed(allowed)
+        n = int(bad.sum())
+        if n == 0:
+            return dict(count=0, first=None, last=None, offsets=np.zeros(0, np.int64), regions=[])
+        offs = torch.nonzero(bad).flatten().cpu().numpy().astype(np.int64)
+        per = {}
+        for o in offs.tolist():
+            name = self.region_of(o)
+            c, f, _ = per.get(name, (0, o, o))
+            per[name] = (c + 1, f, o)
+        return dict(count=n, first=int(offs[0]), last=int(offs[-1]), offsets=offs,
+                    regions=[(name,) + per[name] for name in sorted(per, key=lambda k: per[k][1])])
+
+    def assert_contained(self, allowed, what=''):
+        r = self.report(allowed)
+        if r['count']:
+            raise AssertionError('%s: %d byte(s) changed outside the allowed intervals, first at %d, last at %d: %s' % (
+                what, r['count'], r['first'], r['last'],
+                '; '.join('%s: %d byte(s), offsets %d..%d' % reg for reg in r['regions'])))
+
+
+def engine_tensor_span(eng, tid):
+    """(a, b, view) of engine tensor ``tid`` for the bound shape, from lp_engine_tensor_info: its full stored byte interval
+    [a, b) = [off, off + B*h*w*cs*esz) inside ``eng.arena`` (offsets of that uint8 buffer, the aligned base included) and a
+    [B,h,w,cs] view that includes the padding channels.  (A network input that the space-to-depth rewrite replaced is not placed:
+    its offset is that of the tensor behind it, and the interval means nothing.)"""
+    import ctypes
+    from yolov6.hip import abi
+    off, c, cs, h, w = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    abi.check(eng.lib.lp_engine_tensor_info(eng.h, tid, ctypes.byref(off), ctypes.byref(c), ctypes.byref(cs), ctypes.byref(h),
+                                            ctypes.byref(w)), 'lp_engine_tensor_info')
+    B = eng.bound[0]
+    esz = torch.empty(0, dtype=eng.dtype).element_size()
+    a = (eng.arena.data_ptr() + 255) // 256 * 256 - eng.arena.data_ptr() + off.value
+    b = a + B * h.value * w.value * cs.value * esz
+    return a, b, eng.arena[a:b].view(eng.dtype).view(B, h.value, w.value, cs.value)
+
+
+def arena_regions(eng, names, placed=None):
+    """layout_regions of ``eng.arena`` for the bound shape: ``names`` = {tensor id: name}; ``placed``: ids that lie in the arena
+    (default: all of ``names``)."""
+    base = (eng.arena.data_ptr() + 255) // 256 * 256 - eng.arena.data_ptr()
+    need = eng.lib.lp_engine_arena_bytes(eng.h, *eng.bound)
+    tensors = []
+    for tid in (names if placed is None else placed):
+        a, b, _ = engine_tensor_span(eng, tid)
+        tensors.append((names[tid], a - base, b - a))
+    return layout_regions(base, need, eng.arena.numel(), tensors)
+
+
+def spill_case(first_rank, n_orig=6000, n_copy=2000):
+    """One crafted image for the greedy step's spilled kept list: ``n_orig`` pairwise disjoint 8 x 8 boxes on a 10-px grid with
+    strictly decreasing, distinct scores (row r has rank r), then ``n_copy`` lower-scored copies of the boxes ranked
+    first_rank .. first_rank + n_copy - 1, each shifted by 1 px in x: IoU 56 / 72 with its original, disjoint from every other
+    box.  obj = 1 and the same single probability in every class segment, a multiple of 2^-14 below 1: the eight-term sums are exact,
+    so mask value = score = that probability.  -> (pred float32 [1, n_orig + n_copy, 290], float64 xyxy boxes, scores)."""
+    n = n_orig + n_copy
+    assert first_rank + n_copy <= n_orig and n < 16000
+    r = np.arange(n_orig)
+    cx, cy = 10.0 * (r % 100) + 4.0, 10.0 * (r // 100) + 4.0
+    src = np.arange(first_rank, first_rank + n_copy)
+    cx, cy = np.concatenate([cx, cx[src] + 1.0]), np.concatenate([cy, cy[src]])
+    score = (16000.0 - np.arange(n)) / 16384.0
+    p = np.zeros((1, n, 290), np.float32)
+    p[0, :, 0], p[0, :, 1], p[0, :, 2], p[0, :, 3], p[0, :, 4] = cx, cy, 8.0, 8.0, 1.0
+    p[0, :, 5:13] = np.stack([cx - 4, cy - 4, cx + 4, cy - 4, cx + 4, cy + 4, cx - 4, cy + 4], 1)
+    for a in SEG[:-1]:
+        p[0, :, a + 1] = score
+    box = np.stack([cx - 4.0, cy - 4.0, cx + 4.0, cy + 4.0], 1)
+    return p, box, score
+
+
+def assert_spill_preconditions(p, box, score, first_rank, n_orig, n_copy, conf, iou, max_det, cache=4096):
+    """What the spilled-list test needs, from the C oracle and float64 geometry alone: the oracle keeps exactly the originals in rank
+    order; the only box over the IoU threshold with a copy is its original; returns the kept ranks of those originals."""
+    from oracle import lp_post
+    rows, keep, _ = lp_post.nms_c(p, conf, iou, max_det)
+    assert max_det > cache - 64 and float(score.min()) > conf
+    assert np.array_equal(keep[0], np.arange(n_orig)), 'the oracle does not keep exactly the originals in order'
+    assert np.all(np.diff(score) < 0)
+    c = box[n_orig:]
+    w = np.maximum(0.0, np.minimum(c[:, None, 2], box[None, :, 2]) - np.maximum(c[:, None, 0], box[None, :, 0]))
+    h = np.maximum(0.0, np.minimum(c[:, None, 3], box[None, :, 3]) - np.maximum(c[:, None, 1], box[None, :, 1]))
+    inter = w * h
+    over = inter / (64.0 + 64.0 - inter) > iou
+    over[np.arange(n_copy), n_orig + np.arange(n_copy)] = False            # a box and itself
+    assert np.array_equal(over.sum(1), np.ones(n_copy, np.int64))
+    orig = over.argmax(1)
+    assert np.array_equal(orig, first_rank + np.arange(n_copy))
+    assert np.allclose(inter[np.arange(n_copy), orig], 56.0) and int((inter > 0).sum()) == 2 * n_copy
+    return rows, keep, orig                                              # (kept rank of original r is r: the oracle keeps 0..n_orig-1)
