@@ -253,6 +253,14 @@ int lp_engine_copy_tuning(lp_engine* dst, const lp_engine* src);
  *   count     device int32 [B]
  *   keep      device int32 [B,max_det] anchor index of every kept row, or NULL
  *   workspace device scratch of at least lp_nms_workspace_bytes(B,N) bytes
+ * Ties and NaN (lp_nms and lp_engine_forward_det + lp_nms_candidates alike; torch.max's and torch's descending sort's rules):
+ *   - the arg-max of a head (det columns 20..27) is the FIRST column whose probability equals the head's largest one.  Two logits
+ *     whose fp32 sigmoids are the same number tie: from about 17 up every sigmoid is 1.0f and the first such column wins, not
+ *     the one with the largest logit;
+ *   - a NaN probability wins its head: the maximum (det columns 12..19) is NaN and the index that of the head's first NaN;
+ *   - a NaN in one of the first seven heads makes the masked mean NaN, the comparison with conf false: no candidate;
+ *   - a NaN only in the last head (the mask does not read it) leaves the anchor a candidate with a NaN score.  NaN scores, of
+ *     either sign, sort before every number, among themselves by ascending anchor; equal scores by ascending anchor.
  * ------------------------------------------------------------------------------------------------- */
 size_t lp_nms_workspace_bytes(int B, int N);
 int lp_nms(float* pred, int B, int N, double conf_thres, double iou_thres, int max_det, float* det, int32_t* count,

@@ -49,11 +49,19 @@ def nms_c(pred, conf_thres, iou_thres, max_det):
     return [rows[b, :cnt[b]].copy() for b in range(B)], [keep[b, :cnt[b]].copy() for b in range(B)], p
 
 
+def order_desc(scores):
+    """Stable descending order in which a NaN comes before every number (torch's descending sort; numpy's puts it last), NaNs
+    among themselves by ascending index: the order of ``cand_cmp``."""
+    scores = np.asarray(scores)
+    nan = np.isnan(scores)
+    return np.lexsort((np.where(nan, 0, -scores), ~nan))
+
+
 def greedy_nms_np(boxes, scores, iou_thres):
     """torchvision.ops.nms CPU semantics restated with numpy fp32 ops.  -> kept indices (int64)."""
     boxes = np.asarray(boxes, np.float32)
     scores = np.asarray(scores, np.float32)
-    order = np.argsort(-scores, kind='stable')
+    order = order_desc(scores)
     x1, y1, x2, y2 = (boxes[:, i] for i in range(4))
     areas = (x2 - x1) * (y2 - y1)
     sup = np.zeros(len(order), bool)
@@ -91,7 +99,7 @@ def nms_np(pred, conf_thres, iou_thres, max_det, max_nms=30000):
         score = (det[:, 12] + det[:, 13] + det[:, 14] + det[:, 15] + det[:, 16] + det[:, 17] + det[:, 18]
                  + det[:, 19]) / np.float32(8.0)
         if len(det) > max_nms:
-            top = np.argsort(-score, kind='stable')[:max_nms]
+            top = order_desc(score)[:max_nms]
             det, score, sel = det[top], score[top], sel[top]
         k = greedy_nms_np(det[:, :4], score, iou_thres)[:max_det]
         out.append(det[k])

@@ -28,9 +28,13 @@ static const int SEG[9] = {13, 44, 68, 105, 142, 179, 216, 253, 290};  /* nms.py
 
 typedef struct { float score; int idx; } cand_t;
 
-/* descending score, ties by ascending original index (= stable sort, descending) */
+/* descending score, ties by ascending original index (= stable sort, descending); a NaN score (a NaN only in the last head: the
+ * mask does not read it) sorts before every number, as in torch's descending sort, NaNs among themselves by ascending index:
+ * a strict weak order on every input */
 static int cand_cmp(const void* a, const void* b) {
     const cand_t* x = (const cand_t*)a; const cand_t* y = (const cand_t*)b;
+    const int xn = x->score != x->score, yn = y->score != y->score;
+    if (xn != yn) return xn ? -1 : 1;
     if (x->score > y->score) return -1;
     if (x->score < y->score) return 1;
     return (x->idx > y->idx) - (x->idx < y->idx);

@@ -204,18 +204,25 @@ def assert_bits(got, want, what=''):
                              % (what, n, got.numel(), float((g - w).abs().nan_to_num(float('inf')).max()), bad))
 
 
+def elementwise_bound(ref64, mag64, K, dtype, transcendental=False, slack64=None):
+    """The bound of ``elementwise_excess`` per element (float64); ``K`` may be a tensor that broadcasts against ``mag64``."""
+    r, m = ref64.double(), mag64.double()
+    bound = ulp(r, dtype) + 1.1 * K * 2.0 ** -24 * m
+    if transcendental:
+        bound = bound + 4 * 2.0 ** -23 * r.abs()
+    if slack64 is not None:
+        bound = bound + slack64.double()
+    return bound
+
+
 def elementwise_excess(got, ref64, mag64, K, dtype, transcendental=False, slack64=None):
     """max over elements of |got - ref64| / bound, bound = ulp_T(ref64) + 1.1 K 2^-24 mag64 (+ 4 * 2^-23 |ref64|):
     one ulp of the storage type (half an ulp of rounding + a boundary flip), the standard bound K u sum|x||w| of an fp32
     accumulation of K terms in any order (u = 2^-24) times the Lipschitz constant 1.1 of SiLU (1 for none / ReLU: covered), and
     for an epilogue with v_exp_f32, v_rcp_f32 (1 ulp each) and a multiply, 4 * 2^-23 relative.  ``slack64``: a further derived
     absolute term (the residual epilogue rounds the activation to the storage type BEFORE the add: one more ulp_T of it)."""
-    g, r, m = got.cpu().double(), ref64.double(), mag64.double()
-    bound = ulp(r, dtype) + 1.1 * K * 2.0 ** -24 * m
-    if transcendental:
-        bound = bound + 4 * 2.0 ** -23 * r.abs()
-    if slack64 is not None:
-        bound = bound + slack64.double()
+    g, r = got.cpu().double(), ref64.double()
+    bound = elementwise_bound(ref64, mag64, K, dtype, transcendental, slack64)
     ratio = (g - r).abs() / bound
     ratio = torch.where(torch.isfinite(g), ratio, torch.full_like(ratio, float('inf')))
     return float(ratio.max()), ratio
@@ -928,3 +935,363 @@ def assert_spill_preconditions(p, box, score, first_rank, n_orig, n_copy, conf, 
     assert np.array_equal(orig, first_rank + np.arange(n_copy))
     assert np.allclose(inter[np.arange(n_copy), orig], 56.0) and int((inter > 0).sum()) == 2 * n_copy
     return rows, keep, orig                                              # (kept rank of original r is r: the oracle keeps 0..n_orig-1)
+
+
+# ---- the head's class path on coded logits (tests/test_head_cls_cpu.py, tests/test_head_cls_gpu.py) ---------------------
+# Logits whose arg-max, ties and saturation are known from float64 alone.  Six CODE channels carry +-s by the bits of a per-anchor
+# code t; column i of head k weighs them +-1 by the bits of its own code perm_k(i) (a seeded draw per head and level), so its logit is
+# (6 - 2 d) s, d the Hamming distance of the two codes.  Zeroing code channel j at an anchor ties the columns coded t and
+# t ^ (1 << j) exactly.  One OFFSET channel per head (weight 1 on that head's columns only) sets the category of each
+# (anchor, head); a few NOISE channels per head (weights +-1/4 and a bias shared by the head's columns: order and ties survive) move
+# the head's logits by |n| <= 1.  Every value is an integer or a multiple of 1/16 far below 2^8, so every storage type holds it and
+# every sum is exact in fp32.
+#   anchors with s = 4:   resolved: the offset that puts the head's largest logit at 11, 7, 3, -1 or -3 (the next one is 8 lower)
+#                         +48 all saturated (every logit >= 23), -160 all zero (every logit <= -135)
+#   anchors with s = 12:  offset +1: the columns at distance <= 2 are saturated (>= 24), those at distance 3 are at 0 .. 2; the
+#                         first saturated column is then rarely the column of the largest logit.  +96 all saturated, -208 all zero.
+# Two scales because the rule of admissibility below wants a clear gap in PROBABILITY under every saturated column (s = 4 would put
+# a column at logit 12 beneath one at 20), while a resolved head must keep all its logits inside [-88, 12] (s = 12 spans 144).
+CLS_B, CLS_MAPS = 3, ((12, 20), (6, 10), (3, 5))
+CLS_LEVEL_OFF = (0, 240, 300, 315)
+CLS_N = CLS_LEVEL_OFF[-1]
+CLS_NC = SEG[-1] - SEG[0]                                  # 277
+CLS_HEAD0 = tuple(a - SEG[0] for a in SEG)                 # first class column of each head, and 277
+CLS_SAT, CLS_ZERO = 20.0, -128.0                           # logits from which the fp32 sigmoid is exactly 1.0f / +0.0f
+CLS_MARGIN = 1e-3
+CLS_PLANTED_TILES = {2: 0, 7: 6, 12: 7}                    # 32-row tile of level 0 -> number of its anchors that pass at any threshold
+RES, PSAT, ASAT, AZERO = 0, 1, 2, 3
+_RES_TOP = np.array([11.0, 7.0, 3.0, -1.0, -3.0])
+
+
+def _cls_codes(rng):
+    """perm_k for the eight heads: distinct 6-bit codes, drawn as whole pairs {2a, 2a + 1} so that the bit-0 partner of a code is
+    (nearly) always a column of the same head, in random column order."""
+    out = []
+    for w in (b - a for a, b in zip(SEG[:-1], SEG[1:])):
+        pairs = rng.permutation(32)[:(w + 1) // 2]
+        codes = np.concatenate([2 * pairs, 2 * pairs + 1])[:w]
+        out.append(rng.permutation(codes))
+    return out
+
+
+def cls_case_data(widths, seed):
+    """The coded data of one case.  -> dict: ``levels`` [(x [B,C,h,w], wc [277,C], bc [277])] float64 tensors, ``plan``: the
+    categories drawn (numpy, [B,N,8]; nothing asserts them -- every expectation comes from ``cls_reference``)."""
+    rng = np.random.RandomState(seed)
+    B, N = CLS_B, CLS_N
+    codes = [_cls_codes(rng) for _ in CLS_MAPS]                     # [level][head] -> codes of the head's columns
+    level_of = np.searchsorted(np.array(CLS_LEVEL_OFF[1:]), np.arange(N), side='right')
+    big = np.zeros((B, N), bool)                                    # s = 12 anchors
+    t = np.zeros((B, N), np.int64)
+    zj = np.full((B, N), -1)                                        # zeroed code channel, or -1
+    cat = np.zeros((B, N, 8), np.int64)
+    off = np.zeros((B, N, 8))
+    free = np.ones((B, N), bool)
+    hw0 = CLS_MAPS[0][0] * CLS_MAPS[0][1]
+
+    def set_all(b, n, big_, c, o):
+        big[b, n], zj[b, n], cat[b, n], off[b, n], free[b, n] = big_, -1, c, o, False
+        t[b, n] = rng.randint(64)
+    def res_off(b, n, top):
+        """Per head the offset that puts the largest logit of a resolved head of an s = 4 anchor at ``top``."""
+        bits = 63 if zj[b, n] < 0 else 63 & ~(1 << zj[b, n])
+        dmin = np.array([min(bin((int(c) ^ int(t[b, n])) & bits).count('1') for c in codes[level_of[n]][k]) for k in range(8)])
+        return top - 4.0 * (bin(bits).count('1') - 2 * dmin)
+    for tile, npass in CLS_PLANTED_TILES.items():                   # planted tiles: (32 - npass) anchors at 0, npass anchors at 1
+        for r in range(32):
+            b, n = divmod(32 * tile + r, hw0)
+            if r < 32 - npass:
+                set_all(b, n, True, AZERO, -208.0)
+            else:
+                set_all(b, n, True, PSAT, 1.0)
+    order = [divmod(f, N) for f in rng.permutation(B * N) if free.flat[f]]
+    for c, (b, n) in zip(range(CLS_NC), order):                     # one anchor per class column: resolved there, strong elsewhere
+        k = int(np.searchsorted(np.array(CLS_HEAD0[1:]), c, side='right'))
+        sat = rng.rand(8) < 0.2
+        low = rng.choice([h for h in range(7) if h != k])            # (see below: an s = 4 anchor stays clear of mask value 1)
+        sat[k] = sat[low] = False
+        cat[b, n] = np.where(sat, ASAT, RES)
+        t[b, n] = codes[level_of[n]][k][c - CLS_HEAD0[k]]
+        top = rng.choice(_RES_TOP[:3], 8)
+        top[low] = -1.0
+        off[b, n] = np.where(sat, 48.0, res_off(b, n, top))
+        off[b, n, k] = rng.choice(_RES_TOP[:2]) - 24.0
+        free[b, n] = False
+    for b, n in order[CLS_NC:]:
+        lv = level_of[n]
+        kk = rng.randint(8)
+        t[b, n] = rng.choice(codes[lv][kk])
+        u = rng.rand(8)
+        if rng.rand() < 0.35:
+            big[b, n] = True
+            cat[b, n] = np.where(u < 0.74, PSAT, np.where(u < 0.90, ASAT, AZERO))
+            off[b, n] = np.choose(cat[b, n], [0.0, 1.0, 96.0, -208.0])
+        else:
+            if rng.rand() < 0.65:
+                zj[b, n] = 0 if rng.rand() < 0.6 else rng.randint(1, 6)
+            cat[b, n] = np.where(u < 0.70, RES, np.where(u < 0.80, ASAT, AZERO))
+            # one of the heads the mask reads is resolved at a logit <= 0: the s = 4 anchors' mask values stay below 15/16, the
+            # s = 12 anchors without a zero head are at exactly 1, and the threshold of the 10 % pass rate fits between the two
+            low = rng.randint(7)
+            cat[b, n, low] = RES
+            off[b, n] = np.choose(cat[b, n], [0.0, 0.0, 48.0, -160.0])
+            res = cat[b, n] == RES
+            top = rng.choice(_RES_TOP, 8)
+            top[low] = rng.choice(_RES_TOP[3:])
+            off[b, n][res] = res_off(b, n, top)[res]
+    levels = []
+    for lv, (C, (h, w)) in enumerate(zip(widths, CLS_MAPS)):
+        n0, n1 = CLS_LEVEL_OFF[lv], CLS_LEVEL_OFF[lv + 1]
+        nchunk = max(1, (C + 31) // 32)                             # 32 channels: the fp32 K-chunk (the 16-bit one is two of them)
+        special = [(i % nchunk) * 32 + (i // nchunk) * 2 + 1 for i in range(14)]      # code 0..5, offset 0..7, over all chunks
+        assert len(set(special)) == 14 and max(special) < C, special
+        noise = np.array([c for c in range(C) if c not in special])
+        x = np.zeros((B, n1 - n0, C))
+        x[:, :, noise] = rng.randint(-4, 5, (B, n1 - n0, len(noise))) / 4.0
+        s = np.where(big[:, n0:n1], 12.0, 4.0)
+        for j in range(6):
+            bit = (t[:, n0:n1] >> j) & 1
+            x[:, :, special[j]] = np.where(zj[:, n0:n1] == j, 0.0, s * (2 * bit - 1))
+        wc, bc = np.zeros((CLS_NC, C)), np.zeros(CLS_NC)
+        for k in range(8):
+            a, e = CLS_HEAD0[k], CLS_HEAD0[k + 1]
+            x[:, :, special[6 + k]] = off[:, n0:n1, k]
+            wc[a:e, special[6 + k]] = 1.0
+            for j in range(6):
+                wc[a:e, special[j]] = 2.0 * ((codes[lv][k] >> j) & 1) - 1.0
+            wc[a:e, rng.choice(noise, 3, replace=False)] = rng.choice([-0.25, 0.25], 3)
+            bc[a:e] = rng.randint(-4, 5) / 16.0
+        levels.append((torch.from_numpy(x.reshape(B, h, w, C)).permute(0, 3, 1, 2).contiguous(), torch.from_numpy(wc), torch.from_numpy(bc)))
+    return dict(levels=levels, plan=dict(big=big, t=t, zj=zj, cat=cat, off=off))
+
+
+def cls_logits64(levels):
+    """(logits, sum |x||w| + |b|, number of summed terms) of the class predictors in float64: [B,N,277], [B,N,277], [N]."""
+    L, M, K = [], [], []
+    for x, wc, bc in levels:
+        Bn, C = x.shape[:2]
+        xf = x.permute(0, 2, 3, 1).reshape(Bn, -1, C)
+        L.append(xf @ wc.T + bc)
+        M.append(xf.abs() @ wc.abs().T + bc.abs())
+        K.append(torch.full((xf.shape[1],), C + 1.0, dtype=torch.float64))
+    return torch.cat(L, 1), torch.cat(M, 1), torch.cat(K)
+
+
+def _head_slices():
+    return [slice(a, b) for a, b in zip(CLS_HEAD0[:-1], CLS_HEAD0[1:])]
+
+
+def cls_reference(levels, dtype):
+    """Everything the class-path tests expect, from float64 alone.  Asserts the exactness of the sums (as ``assert_grid_exact``)
+    and the rule of ADMISSIBILITY: for every (anchor, head) with largest logit m, every column either ties with m --
+      (a) its logit equals m, (b) it and m are >= 20 (both sigmoids are exactly 1.0f), (c) it and m are <= -128 (both exactly +0.0f)
+    -- or (d) its float64 sigmoid lies below that of m by at least twice the slack ``elementwise_bound`` grants it (fp32 output,
+    transcendental); and no logit lies in (12, 20) or (-128, -88), where the fp32 result depends on the implementation.
+    -> dict (numpy): ``logits`` float32 [B,N,277] (exact), ``prob`` float64, ``bound`` the elementwise bound of the probabilities,
+    ``ci`` [B,N,8] the expected arg-max (the first tying column), ``cmax`` [B,N,8] the column of the largest logit (its first),
+    ``kind`` [B,N,8]: 'S' saturated (1.0f), 'Z' zero (+0.0f), 'V' a value inside the bound, ``ntie`` [B,N,8] the number of tying
+    columns, ``tie2`` [B,N,8,2] the two columns of an exact two-way tie (-1 elsewhere), ``best`` float64 [B,N,8] the largest
+    sigmoid, ``mask`` float64 [B,N] (ad4 twice)."""
+    for x, wc, bc in levels:
+        assert_grid_exact([x], wc, bc, dtype, fan_in=wc.shape[1])
+    L, M, K = cls_logits64(levels)
+    to_exact_f32(L)
+    assert not bool(((L > 12) & (L < CLS_SAT)).any()) and not bool(((L > CLS_ZERO) & (L < -88)).any())
+    P = torch.sigmoid(L)
+    bound = elementwise_bound(P, M, K[None, :, None], torch.float32, transcendental=True)
+    n = L.shape[:2]
+    ci, cmax, ntie = (np.zeros(n + (8,), np.int64) for _ in range(3))
+    kind = np.full(n + (8,), 'V')
+    tie2 = np.full(n + (8, 2), -1)
+    best = np.zeros(n + (8,))
+    for k, sl in enumerate(_head_slices()):
+        l, p, bd = L[..., sl], P[..., sl], bound[..., sl]
+        m = l.max(-1, keepdim=True).values
+        a, b, c = l == m, (l >= CLS_SAT) & (m >= CLS_SAT), (l <= CLS_ZERO) & (m <= CLS_ZERO)
+        tie = a | b | c
+        d = torch.sigmoid(m) - p >= 2 * bd
+        assert bool((tie != d).all()), 'head %d: a column neither ties with the largest logit nor is clear of it' % k
+        ci[..., k] = tie.int().argmax(-1).numpy()
+        cmax[..., k] = a.int().argmax(-1).numpy()
+        ntie[..., k] = tie.sum(-1).numpy()
+        kind[..., k] = np.where(m[..., 0].numpy() >= CLS_SAT, 'S', np.where(m[..., 0].numpy() <= CLS_ZERO, 'Z', 'V'))
+        two = (a.sum(-1) == 2) & (tie.sum(-1) == 2)
+        idx = torch.nonzero(a & two[..., None])                           # rows come in column order: two per tying pair
+        tie2[..., k, :][two.numpy()] = idx[:, -1].reshape(-1, 2).numpy()
+        best[..., k] = p.max(-1).values.numpy()
+    mask = (best[..., :7].sum(-1) + best[..., 6]) / 8.0
+    return dict(logits=L.float().numpy(), prob=P.numpy(), bound=bound.numpy(), mag=M.numpy(), K=K.numpy(), ci=ci, cmax=cmax,
+                kind=kind, ntie=ntie, tie2=tie2, best=best, mask=mask)
+
+
+def cls_thresholds(mask):
+    """Two confidence thresholds: of the multiples of 2^-12 that no mask value of the reference comes within CLS_MARGIN of, the
+    two whose pass rates are nearest 10 % and 60 % (the larger threshold of equally good ones)."""
+    v = mask.flatten()
+    cands = np.arange(1, 4096) / 4096.0
+    cands = cands[np.abs(v[None] - cands[:, None]).min(1) > CLS_MARGIN]
+    rate = (v[None] >= cands[:, None]).mean(1)
+    return [float(cands[len(cands) - 1 - np.abs(rate - r)[::-1].argmin()]) for r in (0.10, 0.60)]
+
+
+def cls_coverage(ref, confs):
+    """Shares and counts the tests assert (DESIGN 4.1 has the table), from the reference: over the (anchor, head) pairs -- ``tie2``
+    exact two-way ties, ``sat_first`` saturated with arg-max != column of the largest logit, ``all_sat`` / ``all_zero`` (arg-max 0);
+    ``columns``: class columns that are the expected arg-max at an anchor passing the lower threshold; ``cross_tile`` /
+    ``cross_wave`` / ``cross_window``: two-way ties of passing anchors whose columns lie in different 32-column tiles / on different
+    sides of column 96 or 192 / in different 64-column windows; ``tile_counts``: per threshold the set of pass counts of the
+    32-row tiles of every level."""
+    ci, cmax, kind, ntie = ref['ci'], ref['cmax'], ref['kind'], ref['ntie']
+    pairs = float(ci.size)
+    nc = np.array([b - a for a, b in zip(CLS_HEAD0[:-1], CLS_HEAD0[1:])])
+    ok = ref['mask'] >= min(confs)
+    cols = set()
+    for k in range(8):
+        cols |= set((CLS_HEAD0[k] + ci[..., k][ok]).tolist())
+    t2 = ref['tie2'] + np.array(CLS_HEAD0[:8])[None, None, :, None]
+    t2 = t2[(ref['tie2'][..., 0] >= 0) & ok[..., None]]
+    wave = lambda c: (c >= 96).astype(int) + (c >= 192)
+    counts = []
+    for conf in confs:
+        seen = set()
+        for lv in range(len(CLS_MAPS)):
+            rows = (ref['mask'][:, CLS_LEVEL_OFF[lv]:CLS_LEVEL_OFF[lv + 1]] >= conf).flatten()
+            seen |= set(int(rows[i:i + 32].sum()) for i in range(0, len(rows), 32))
+        counts.append(seen)
+    return dict(tie2=float((ref['tie2'][..., 0] >= 0).sum()) / pairs,
+                sat_first=float(((kind == 'S') & (ci != cmax) & (ntie < nc)).sum()) / pairs,
+                all_sat=float(((kind == 'S') & (ntie == nc)).sum()) / pairs, all_zero=float((kind == 'Z').sum()) / pairs,
+                columns=len(cols), cross_tile=int((t2[:, 0] // 32 != t2[:, 1] // 32).sum()),
+                cross_wave=int((wave(t2[:, 0]) != wave(t2[:, 1])).sum()), cross_window=int((t2[:, 0] // 64 != t2[:, 1] // 64).sum()),
+                tile_counts=counts)
+
+
+def score_key_hi(sc32):
+    """High word of lp_score.inc::score_key for float32 scores (numpy uint32): descending-orderable bits, a NaN of either sign 0."""
+    sc32 = np.ascontiguousarray(sc32, np.float32)
+    u = sc32.view(np.uint32)
+    u = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+    return np.where(np.isnan(sc32), np.uint32(0), ~u).astype(np.uint32)
+
+
+def sum8_f32(cf, last=7):
+    """Left-to-right fp32 sum of cf[..., 0..6] and cf[..., last], / 8 (score_mask_value: last = 6, score_value: last = 7)."""
+    cf = np.asarray(cf, np.float32)
+    s = cf[..., 0] + cf[..., 1]
+    for k in (2, 3, 4, 5, 6, last):
+        s = (s + cf[..., k]).astype(np.float32)
+    return (s / np.float32(8.0)).astype(np.float32)
+
+
+def sigmoid32(v):
+    """rcp(1 + exp(-v)) in numpy float32: not the device's bits, but the same properties (1.0f from 20 up, +0.0f from -128 down,
+    monotone, NaN for NaN)."""
+    v = np.asarray(v, np.float32)
+    with np.errstate(over='ignore', invalid='ignore'):
+        return (np.float32(1.0) / (np.float32(1.0) + np.exp(-v))).astype(np.float32)
+
+
+CLS_MUTANTS = ('logit_argmax', 'last_equal', 'boundary', 'nan_dropped', 'mask_cf7', 'windows_desc')
+
+
+def cls_emulate(logits32, mutant=None):
+    """numpy emulation of the class path in head_det_kernel's operation order on fp32 logits [R,277]: per head the NaN-propagating
+    maximum of the LOGITS, its sigmoid, the mask (ad4 twice) and the score as left-to-right fp32 sums, and the FIRST column whose
+    sigmoid equals the maximum (both NaN: the first NaN), looked for in the 64-column windows in ascending order.  ``mutant``: one
+    of CLS_MUTANTS, the same path subtly wrong.  -> dict cf [R,8] float32, ci [R,8], mask [R], score [R] float32."""
+    assert mutant is None or mutant in CLS_MUTANTS
+    x = np.asarray(logits32, np.float32)
+    sg = sigmoid32(x)
+    edges = list(CLS_HEAD0)
+    if mutant == 'boundary':
+        edges = [0] + [e + 1 for e in edges[1:-1]] + [edges[-1]]
+    cf, ci = np.zeros((len(x), 8), np.float32), np.zeros((len(x), 8), np.int64)
+    for k in range(8):
+        a, b = edges[k], edges[k + 1]
+        with np.errstate(invalid='ignore'):
+            mx = np.fmax.reduce(x[:, a:b], 1) if mutant == 'nan_dropped' else x[:, a:b].max(1)
+        cf[:, k] = sigmoid32(mx)
+        hit = sg[:, a:b] == cf[:, k:k + 1]
+        if mutant != 'nan_dropped':
+            hit |= np.isnan(cf[:, k:k + 1]) & np.isnan(x[:, a:b])
+        if mutant == 'logit_argmax':
+            hit = (x[:, a:b] == mx[:, None]) | (np.isnan(mx)[:, None] & np.isnan(x[:, a:b]))
+        if mutant == 'windows_desc':
+            win = np.where(hit, (np.arange(a, b) // 64)[None], -1)
+            hit &= win == win.max(1, keepdims=True)
+        ci[:, k] = (b - a - 1 - hit[:, ::-1].argmax(1)) if mutant == 'last_equal' else hit.argmax(1)
+    return dict(cf=cf, ci=ci, mask=sum8_f32(cf, 7 if mutant == 'mask_cf7' else 6), score=sum8_f32(cf, 7))
+
+
+def cls_nan_data(dtype_width, head, seed):
+    """The small non-finite case: the coded data of ``cls_case_data`` at width ``dtype_width`` on every level, plus ONE channel
+    (a noise channel no head weighs) with weight +inf on the middle column of ``head`` and 0 elsewhere.  Its feature cycles over
+    the pixels through 0 (0 * inf: that column is NaN), +1 (+inf: probability 1.0, a tie with every saturated column), -1 (-inf:
+    probability 0) and +1.  -> (levels, class column 0..276 that carries the weight)"""
+    d = cls_case_data((dtype_width,) * 3, seed)
+    col = (CLS_HEAD0[head] + CLS_HEAD0[head + 1]) // 2
+    levels = []
+    for x, wc, bc in d['levels']:
+        free = [c for c in range(wc.shape[1]) if float(wc[:, c].abs().sum()) == 0]
+        ch = free[len(free) // 2]
+        wc = wc.clone()
+        wc[col, ch] = float('inf')
+        x = x.clone()
+        Bn, C, h, w = x.shape
+        pat = torch.tensor([0.0, 1.0, -1.0, 1.0], dtype=torch.float64)[torch.arange(Bn * h * w) % 4].reshape(Bn, h, w)
+        x[:, ch] = pat
+        levels.append((x, wc, bc))
+    return levels, col
+
+
+def cls_nan_expected(levels):
+    """Expectation of the non-finite case from the reference's torch.max: the float64 logits, the probabilities every admissible
+    implementation must return -- 1.0 from logit 20 up, 0.0 from -128 down, NaN for NaN, else the float64 sigmoid --, and per head
+    torch.max of them (the first maximum; a NaN wins, the first one).  -> dict (numpy) cf [B,N,8] float64, ci [B,N,8], mask [B,N]
+    (NaN where a head 0..6 is NaN), ``nan`` [B,N,277] bool."""
+    L, _, _ = cls_logits64(levels)
+    P = torch.where(L >= CLS_SAT, torch.ones_like(L), torch.where(L <= CLS_ZERO, torch.zeros_like(L), torch.sigmoid(L)))
+    assert bool((torch.isnan(P) == torch.isnan(L)).all())
+    cf, ci = zip(*[torch.max(P[..., sl], -1) for sl in _head_slices()])
+    cf, ci = torch.stack(cf, -1).numpy(), torch.stack(ci, -1).numpy()
+    return dict(logits=L.float().numpy(), cf=cf, ci=ci, mask=(cf[..., :7].sum(-1) + cf[..., 6]) / 8.0, nan=torch.isnan(L).numpy())
+
+
+_cls_cache = {}
+
+
+def cls_case(dtype, widths, seed=100):
+    """Data, reference, thresholds and coverage of a case, computed once per process and never modified."""
+    key = (dtype, tuple(widths), seed)
+    if key not in _cls_cache:
+        d = cls_case_data(widths, seed)
+        ref = cls_reference(d['levels'], dtype)
+        confs = cls_thresholds(ref['mask'])
+        _cls_cache[key] = dict(levels=d['levels'], ref=ref, confs=confs, cov=cls_coverage(ref, confs))
+    return _cls_cache[key]
+
+
+def cls_check(ref, conf, passed, cf, ci, key_hi=None):
+    """What the tests assert of a class path's result at threshold ``conf``, against ``cls_reference``: ``passed`` [B,N] bool is
+    the reference's set; at the passing anchors ``ci`` [B,N,8] is the expected arg-max, ``cf`` [B,N,8] float32 is exactly 1.0f
+    for a saturated head, exactly +0.0f for a zero one and else inside the elementwise bound of the largest float64 sigmoid, and
+    ``key_hi`` [B,N] is score_key of the left-to-right fp32 sum of the eight / 8.  -> list of the quantities that differ (empty:
+    all hold), so that a test can also require that a wrong result IS noticed."""
+    bad = []
+    want = ref['mask'] >= conf
+    assert float(np.abs(ref['mask'] - conf).min()) > CLS_MARGIN
+    if not np.array_equal(np.asarray(passed, bool), want):
+        bad.append('candidates')
+    cf, ci = np.asarray(cf, np.float32)[want], np.asarray(ci)[want]
+    if not np.array_equal(ci, ref['ci'][want]):
+        bad.append('arg-max')
+    kind, best = ref['kind'][want], ref['best'][want]
+    col = np.array(CLS_HEAD0[:8])[None] + ref['ci'][want]
+    bound = np.take_along_axis(ref['bound'][want], col, -1)
+    bits = cf.view(np.uint32)
+    ok = np.where(kind == 'S', bits == 0x3f800000, np.where(kind == 'Z', bits == 0, np.abs(cf.astype(np.float64) - best) <= bound))
+    if not ok.all():
+        bad.append('maximum')
+    if key_hi is not None and not np.array_equal(np.asarray(key_hi)[want], score_key_hi(sum8_f32(cf, 7))):
+        bad.append('key')
+    return bad

@@ -56,7 +56,10 @@ NmsWs nms_carve(void* base, int B, int N) {
 // The rows may be one pyramid level of the anchors only (detections-only forward, levels whose class predictors still go
 // through a prediction scratch): RPI prediction rows per image = anchors anchor0 .. anchor0 + RPI of the N per image;
 // write_box false leaves columns 0..11 of the candidate rows to the decode kernel that has written them already.
-__global__ __launch_bounds__(256) void score_kernel(float* __restrict__ pred, int B, int RPI, int anchor0, int N, float conf_f,
+// amdgpu_waves_per_eu(5): the kernel waits for its row loads most of the time, five waves per SIMD instead of four are 7 % of its
+// time (80 -> 75 us for 32 x 8400 rows).  With the NaN-aware second fold of score_heads the allocator wants 100 registers, four
+// over the limit of five waves; held to 96 it spills six of them (profiles/head_cls_score_kernel_ab.txt).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void score_kernel(float* __restrict__ pred, int B, int RPI, int anchor0, int N, float conf_f,
                                                    float* __restrict__ rows, unsigned long long* __restrict__ keys,
                                                    int32_t* __restrict__ cnt, int NP, int write_box) {
     constexpr int NK = (NCOL + 15) / 16;   // 19 column slots per lane
