@@ -883,6 +883,26 @@ int lp_tile_gate_update(const lp_tile_gate_desc* desc, int n_frames, const int* 
                         const int32_t* tiles, const int* n_tiles /* HOST [n_streams] */, int max_tiles,
                         unsigned short* ref, long long ref_elems, int32_t* age, int thres16, int min_cells, int refresh,
                         unsigned char* flag, int32_t* ncell, void* stream);
+/* lp_tile_gate_update_gain: lp_tile_gate_update for frames whose exposure or daylight drifts (gate_update_gain_np in
+ * yolov6/utils/tile_gate.py, on every integer).  A common factor on every pixel of a tile changes every cell under the rule above;
+ * here the reference is scaled by one gain per tile before the cells are compared.  Q12: 4096 is a gain of 1.
+ *   Gain of a cell: R_c / C_c = the sum of ref / of blocks over the cell's blocks (<= 65280); R_c == 0: no gain; otherwise
+ *   g_c = min((C_c * 4096 + (R_c >> 1)) / R_c, 65535) in unsigned 32-bit arithmetic.
+ *   Gain of the tile: m = the cells with a gain; m == 0: G_raw = 4096; otherwise G_raw = the lower median of the g_c, the value of
+ *   rank (m - 1) / 2 of the sorted gains.  out_of_range = G_raw < gain_lo || G_raw > gain_hi; G = G_raw clamped to the range.
+ *   Changed cell: A_g = sum |blocks * 4096 - ref * G| over its blocks (int32: a term <= 4080 * 16384); changed iff
+ *   A_g > thres16 * npix * 256.  With G == 4096 that is lp_tile_gate_update's test.
+ *   flag = age < 0 || out_of_range || ncell >= min_cells || (refresh > 0 && age + 1 >= refresh); ref and age move as above.
+ *   gain int32 [n_frames][max_tiles] = G_raw.  (flag, ncell, gain) = (1, 0, 0) for a never-detected tile (ref is not read) and for
+ *   every t of a frame with stream_of -1, (0, 0, 0) for t >= n_tiles[s], (1, -1, 0) for a bad table entry, which touches no state.
+ * The same workgroup per (frame, tile); the median is selected by two radix passes over 256-bin LDS histograms of integer counts.
+ * The checks are lp_tile_gate_update's, and: gain non-null, 4-byte aligned and part of the overlap check;
+ * 1 <= gain_lo <= 4096 <= gain_hi <= 16384.  Capturable, allocates nothing, no host read. */
+int lp_tile_gate_update_gain(const lp_tile_gate_desc* desc, int n_frames, const int* stream_of /* HOST [n_frames] */, int n_streams,
+                             const int32_t* tiles, const int* n_tiles /* HOST [n_streams] */, int max_tiles,
+                             unsigned short* ref, long long ref_elems, int32_t* age, int thres16, int min_cells, int refresh,
+                             int gain_lo, int gain_hi, unsigned char* flag, int32_t* ncell,
+                             int32_t* gain /* [n_frames][max_tiles] */, void* stream);
 
 /* lp_eval_counts: the matching loops of Evaler.eval (yolov6/core/evaler.py:153-243, box_iou general.py:93-115) for a
  * batch of images, one workgroup per image.

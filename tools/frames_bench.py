@@ -6,6 +6,7 @@
     python tools/frames_bench.py --tile [--tile-baseline] [--tile-frame 2160 3840] [--tile-size 640] [--tile-overlap 128]
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
     python tools/frames_bench.py --tile --gate [--gate-moving K] [--gate-thres F] [--gate-refresh N] [--nv12 [bt709]] [--tile-frame 2160 3840] [--runs 3]
+    python tools/frames_bench.py --tile --gate --gate-illum gain --gate-drift A [--gate-drift-period 8] [--gate-moving K] [--nv12 [bt709]] [--runs 3]
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot] [--redact [--hold [--lookback D]]] [--nv12]
                                  [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
@@ -102,6 +103,11 @@ def parse():
     ap.add_argument('--gate-moving', type=int, default=0, metavar='K', help='with --gate: patches of 96 x 32 px per frame that move a few pixels per step')
     ap.add_argument('--gate-thres', type=float, default=2.0, metavar='F', help='with --gate: the gate\'s thres (luma levels per pixel)')
     ap.add_argument('--gate-refresh', type=int, default=50, metavar='N', help='with --gate: the gate\'s refresh (calls after which a tile is detected again anyway; 0: never)')
+    ap.add_argument('--gate-illum', default='none', choices=['none', 'gain'], help='with --gate: also measure the gate with this illum on frames '
+                    'whose brightness drifts (--gate-drift), beside illum none and the plain path')
+    ap.add_argument('--gate-drift', type=float, default=0.0, metavar='A', help='with --gate: the frames of step k are multiplied by '
+                    '1 + A sin(2 pi k / P) on the device (0 <= A < 1); their base is scaled so that nothing saturates at 1 + A')
+    ap.add_argument('--gate-drift-period', type=int, default=8, metavar='P', help='with --gate-drift: steps per period (a multiple of 8 with --gate-moving)')
     ap.add_argument('--track', action='store_true', help='measure plate tracking (PlateTracker.update behind detect_frames) instead')
     ap.add_argument('--track-batch', type=int, default=32, help='with --track: camera streams = frames per step')
     ap.add_argument('--best-shot', action='store_true', help='with --track: also time crops + sharpness + gallery behind the update')
@@ -276,6 +282,29 @@ def tile_mode(args, model, dev, tdt):
     print(json.dumps(out))
 
 
+def gate_host_steps(args, top=256):
+    """host[k][f]: the seeded still frames of the gate modes, pixels below ``top``, with ``--gate-moving`` patches of 96 x 32 px that
+    move 3 px down and 5 px right per step (8 steps; one step without patches)."""
+    h0, w0 = args.tile_frame
+    F, K = args.tile_frames, args.gate_moving
+    rng = np.random.default_rng(0)
+    still = [rng.integers(0, top, (h0, w0, 3), dtype=np.uint8) for _ in range(F)]
+    STEPS, PH, PW = 8, 32, 96
+    patches = rng.integers(0, top, (F, max(K, 1), PH, PW, 3), dtype=np.uint8)
+    origin = np.stack([rng.integers(0, h0 - PH - 4 * STEPS, (F, max(K, 1))), rng.integers(0, w0 - PW - 6 * STEPS, (F, max(K, 1)))], -1)
+    host = []
+    for k in range(STEPS if K else 1):
+        step = []
+        for f in range(F):
+            img = still[f].copy()
+            for j in range(K):
+                y, x = int(origin[f, j, 0]) + 3 * k, int(origin[f, j, 1]) + 5 * k
+                img[y:y + PH, x:x + PW] = patches[f, j]
+            step.append(img)
+        host.append(step)
+    return host
+
+
 def gate_mode(args, model, dev, tdt):
     """--tile --gate: the tile gate on still frames with ``--gate-moving`` moving patches.  Reports under ``gate``: the active tiles
     per frame and the forwards per call of the gated path, frames/s with and without the gate (alternating in the same run, on the
@@ -287,21 +316,7 @@ def gate_mode(args, model, dev, tdt):
     tile = args.tile_size or args.size
     F, B, K = args.tile_frames, args.tile_batch, args.gate_moving
     conf, iou, max_det = args.conf, args.iou, args.max_det
-    rng = np.random.default_rng(0)
-    still = [rng.integers(0, 256, (h0, w0, 3), dtype=np.uint8) for _ in range(F)]
-    STEPS, PH, PW = 8, 32, 96
-    patches = rng.integers(0, 256, (F, max(K, 1), PH, PW, 3), dtype=np.uint8)
-    origin = np.stack([rng.integers(0, h0 - PH - 4 * STEPS, (F, max(K, 1))), rng.integers(0, w0 - PW - 6 * STEPS, (F, max(K, 1)))], -1)
-    host = []                               # host[k][f]: the frames of step k (the patches 3 px down and 5 px right per step)
-    for k in range(STEPS if K else 1):
-        step = []
-        for f in range(F):
-            img = still[f].copy()
-            for j in range(K):
-                y, x = int(origin[f, j, 0]) + 3 * k, int(origin[f, j, 1]) + 5 * k
-                img[y:y + PH, x:x + PW] = patches[f, j]
-            step.append(img)
-        host.append(step)
+    host = gate_host_steps(args)
     if args.nv12:
         from yolov6.utils.nv12 import bgr_to_nv12_np
         steps = [[bgr_to_nv12_np(f, args.nv12).to(dev) for f in st] for st in host]
@@ -363,6 +378,111 @@ def gate_mode(args, model, dev, tdt):
         g['luma_ms'], g['update_ms'] = float(np.median(luma_ms[1:])), float(np.median(update_ms[1:]))
         g['luma_bytes_read'] = read
         g['luma_read_bytes_per_s'] = round(read / (g['luma_ms'] * 1e-3), 1)
+    print(json.dumps(out))
+
+
+def gate_drift_mode(args, model, dev, tdt):
+    """--tile --gate --gate-illum gain --gate-drift A [--gate-drift-period P]: the gate under a drift of the brightness.  The still
+    frames of the gate mode (their base scaled so that no pixel reaches 255 at 1 + A) are multiplied on the device by
+    1 + A sin(2 pi k / P) for step k (an NV12 frame: its luma plane).  Four paths alternate in every run over the same number of
+    calls: the gate with illum none on the frames WITHOUT drift (what the gate was built for), the gate with illum none and with
+    illum gain on the drifting frames, and ``detect_tiled_padded`` on the drifting frames.  Reports under ``gate``: per path the
+    active tiles per frame and frames/s, and the device time by events of lp_tile_gate_update and lp_tile_gate_update_gain on
+    the same descriptors (a steady frame: the cell passes, no copy of ref)."""
+    import torch
+    from yolov6.hip import runtime
+    from yolov6.utils.nv12 import Nv12Frame, bgr_to_nv12_np
+    A, P = float(args.gate_drift), int(args.gate_drift_period)
+    if not 0.0 <= A < 1.0 or P < 1 or (args.gate_moving and P % 8):
+        raise SystemExit('--gate-drift needs 0 <= A < 1 and a period >= 1 (a multiple of 8 with --gate-moving)')
+    size = [args.size, args.size]
+    h0, w0 = args.tile_frame
+    tile = args.tile_size or args.size
+    F, B, K = args.tile_frames, args.tile_batch, args.gate_moving
+    conf, iou, max_det = args.conf, args.iou, args.max_det
+    host = gate_host_steps(args, top=int(254.0 / (1.0 + A)) + 1)        # pixel * (1 + A) + 1/2 < 255
+    gains = [1.0 + A * float(np.sin(2.0 * np.pi * k / P)) for k in range(P)]
+
+    def device_frames(step, g):
+        out = []
+        for f in step:
+            if args.nv12:
+                f = bgr_to_nv12_np(f, args.nv12).to(dev)
+                px = f.y
+            else:
+                px = torch.from_numpy(f).to(dev)
+            if g != 1.0:
+                px = (px.to(torch.float32) * g + 0.5).to(torch.uint8)     # on the device
+            out.append(Nv12Frame(px, f.uv, args.nv12) if args.nv12 else px)
+        return out
+
+    still = [device_frames(st, 1.0) for st in host]
+    drift = [device_frames(host[k % len(host)], g) for k, g in enumerate(gains)]
+    assert max(int((f.y if args.nv12 else f).max()) for st in drift for f in st) < 255
+    kw = dict(tile_hw=(tile, tile), overlap=args.tile_overlap, batch=B)
+    sync = torch.cuda.synchronize
+    with torch.no_grad():
+        runtime.prepare_for(model, (B, 3, *size), tdt)
+        mk = lambda illum: runtime.TileGate(model, [(h0, w0)] * F, size, conf, iou, max_det, thres=args.gate_thres,   # noqa: E731
+                                            refresh=args.gate_refresh, illum=illum, **kw)
+        gates = dict(still_none=mk('none'), drift_none=mk('none'), drift_gain=mk('gain'))
+        n_tiles = len(gates['drift_gain'].plans[0])
+        paths = dict(still_none=lambda k: gates['still_none'].detect_padded(still[k % len(still)]),
+                     drift_none=lambda k: gates['drift_none'].detect_padded(drift[k % P]),
+                     drift_gain=lambda k: gates['drift_gain'].detect_padded(drift[k % P]),
+                     plain=lambda k: runtime.detect_tiled_padded(model, drift[k % P], size, conf, iou, max_det, **kw))
+        calls = max(P, args.frames // (F * 8))
+        for k in range(P):                  # warm-up: every path over a period once
+            for fn in paths.values():
+                fn(k)
+        sync()
+        fps = {name: [] for name in paths}
+        before = {name: dict(gt.stats) for name, gt in gates.items()}
+        for _ in range(args.runs):
+            for name, fn in paths.items():
+                t0 = time.perf_counter()
+                for k in range(calls):
+                    fn(k)
+                sync()
+                fps[name].append(round(calls * F / (time.perf_counter() - t0), 2))
+        out = dict(metric='frames/s of tiled detection of fixed-camera frames under a drift of the brightness, with and without the gain of the tile gate',
+                   model=args.model, dtype=args.dtype, frame=[h0, w0], tile=tile, overlap=args.tile_overlap, tiles_per_frame=n_tiles,
+                   frames_per_call=F, tiles_per_forward=B, runs=args.runs, nv12=args.nv12)
+        g = out['gate'] = dict(moving=K, thres=args.gate_thres, refresh=args.gate_refresh, illum=args.gate_illum, drift=A, drift_period=P,
+                               gain_min=round(min(gains), 4), gain_max=round(max(gains), 4), calls_per_run=calls)
+        for name, gt in gates.items():
+            n_calls = gt.stats['calls'] - before[name]['calls']
+            g[name + '_active_tiles_per_frame'] = round((gt.stats['tiles_detected'] - before[name]['tiles_detected']) / (n_calls * F), 3)
+            g[name + '_tiles_detected'] = gt.stats['tiles_detected'] - before[name]['tiles_detected']
+        g['drift_gain_tiles_out_of_range'] = gates['drift_gain'].stats['tiles_out_of_range'] - before['drift_gain']['tiles_out_of_range']
+        for name in paths:
+            g[name + '_fps_runs'], g[name + '_fps'] = fps[name], float(np.median(fps[name]))
+        g['gain_over_none_under_drift'] = round(g['drift_gain_fps'] / g['drift_none_fps'], 3)
+        g['gain_under_drift_over_none_on_still'] = round(g['drift_gain_fps'] / g['still_none_fps'], 3)
+        g['gain_over_plain'] = round(g['drift_gain_fps'] / g['plain_fps'], 3)
+        # the device time of the kernels, by events, on the same descriptors: every cell of every tile is walked, no tile is flagged
+        frames = drift[P // 4]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        ms = dict(luma=[], update=[], update_gain=[])
+        d_none = gates['drift_none']._describe(frames, list(range(F)), bool(args.nv12))
+        d_gain = gates['drift_gain']._describe(frames, list(range(F)), bool(args.nv12))
+        for _ in range(args.reps + 2):      # two are dropped: with illum none the first flags every tile and moves ref to these frames
+            ev[0].record()
+            gates['drift_gain']._luma(d_gain)
+            ev[1].record()
+            gates['drift_gain']._update(d_gain, list(range(F)))
+            ev[2].record()
+            gates['drift_none']._luma(d_none)
+            ev[3].record()
+            gates['drift_none']._update(d_none, list(range(F)))
+            ev[4].record()
+            sync()
+            ms['luma'].append(ev[0].elapsed_time(ev[1]))
+            ms['update_gain'].append(ev[1].elapsed_time(ev[2]))
+            ms['update'].append(ev[3].elapsed_time(ev[4]))
+        for name, v in ms.items():
+            g[name + '_ms_runs'], g[name + '_ms'] = [round(x, 4) for x in v[2:]], float(np.median(v[2:]))
+        g['update_gain_over_update'] = round(g['update_gain_ms'] / g['update_ms'], 3)
     print(json.dumps(out))
 
 
@@ -903,6 +1023,8 @@ def main():
     model = model.to(dev).to(tdt)
     model.lp_graph = True                   # as Inferer sets it
     if args.tile and args.gate:
+        if args.gate_illum == 'gain' or args.gate_drift:
+            return gate_drift_mode(args, model, dev, tdt)
         return gate_mode(args, model, dev, tdt)
     if args.tile:
         return tile_mode(args, model, dev, tdt)

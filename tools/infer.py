@@ -11,7 +11,8 @@
                           [--track --watchlist FILE [--watch-mismatch 1] [--watch-cost F]
                            [--watch-confusable "0D 0Q 8B 2Z 5S" [--watch-confusable-weight 4]]
                            [--watch-live [--watch-live-min-hits 3]]]
-                          [--tile H W --tile-gate [--tile-gate-thres 2.0] [--tile-gate-min-cells 1] [--tile-gate-refresh 50]]
+                          [--tile H W --tile-gate [--tile-gate-thres 2.0] [--tile-gate-min-cells 1] [--tile-gate-refresh 50]
+                           [--tile-gate-illum none|gain] [--tile-gate-max-gain 1.5]]
 """
 import argparse
 import os
@@ -102,6 +103,11 @@ _FLAGS = [
                                help='with --tile-gate: luma levels per pixel a 16 x 16 cell must change by (0..255)')),
     ('--tile-gate-min-cells', dict(type=int, default=1, metavar='N', help='with --tile-gate: changed cells that make a tile run again')),
     ('--tile-gate-refresh', dict(type=int, default=50, metavar='N', help='with --tile-gate: frames after which a tile runs again anyway (0: never)')),
+    ('--tile-gate-illum', dict(choices=('none', 'gain'), default='none',
+                               help='with --tile-gate: gain = compare a tile after scaling its reference by one estimated gain per tile, so that '
+                                    'an exposure step or a cloud does not run every tile again')),
+    ('--tile-gate-max-gain', dict(type=float, default=1.5, metavar='F',
+                                  help='with --tile-gate-illum gain: a tile whose gain leaves [1 / F, F] runs again (1..4)')),
 ]
 
 
@@ -123,7 +129,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         track_expand=0.5, best_shots=False, nv12=None, nv12_size=None, redact=None, redact_cell=16,
         redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1, redact_lookback=None, redact_lookback_max_back=None,
         redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None, watch_confusable=None, watch_confusable_weight=4,
-        watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1, tile_gate_refresh=50):
+        watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1, tile_gate_refresh=50,
+        tile_gate_illum='none', tile_gate_max_gain=1.5):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track or redact) and not osp.exists(out_dir):
@@ -143,7 +150,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
                       watch_mismatch=watch_mismatch, watch_cost=watch_cost, watch_confusable=watch_confusable,
                       watch_confusable_weight=watch_confusable_weight, watch_live=watch_live, watch_live_min_hits=watch_live_min_hits,
                       tile_gate=tile_gate, tile_gate_thres=tile_gate_thres,
-                      tile_gate_min_cells=tile_gate_min_cells, tile_gate_refresh=tile_gate_refresh).infer(
+                      tile_gate_min_cells=tile_gate_min_cells, tile_gate_refresh=tile_gate_refresh,
+                      tile_gate_illum=tile_gate_illum, tile_gate_max_gain=tile_gate_max_gain).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

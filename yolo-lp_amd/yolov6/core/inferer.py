@@ -54,7 +54,7 @@ class Inferer:
                  nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1,
                  redact_lookback=None, redact_lookback_max_back=None, redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None,
                  watch_confusable=None, watch_confusable_weight=4, watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0,
-                 tile_gate_min_cells=1, tile_gate_refresh=50):
+                 tile_gate_min_cells=1, tile_gate_refresh=50, tile_gate_illum='none', tile_gate_max_gain=1.5):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -92,13 +92,17 @@ class Inferer:
         ``tile_gate`` (with ``tile``): the whole source is ONE fixed-camera stream, every frame of the size of the first (another
         size raises); a tile is run through the network only when a 16 x 16 cell of it has changed by more than ``tile_gate_thres``
         luma levels per pixel (in at least ``tile_gate_min_cells`` cells) since the tile was last detected, or every
-        ``tile_gate_refresh`` frames (0: never); the other tiles keep their rows.  Tile groups are then one frame per call."""
+        ``tile_gate_refresh`` frames (0: never); the other tiles keep their rows.  Tile groups are then one frame per call.
+        ``tile_gate_illum='gain'`` compares the cells after the tile's reference is scaled by one gain per tile (the median of its
+        cells' gains), so an exposure step or a cloud does not re-detect everything; a gain outside
+        [1 / ``tile_gate_max_gain``, ``tile_gate_max_gain``] does."""
         self.__dict__.update(locals())
         if tile_gate:
-            from yolov6.utils.tile_gate import check_params as check_gate
+            from yolov6.utils.tile_gate import check_illum, check_params as check_gate
             if tile is None:
                 raise ValueError('tile_gate needs tile=(H, W)')
             check_gate(tile_gate_thres, tile_gate_min_cells, tile_gate_refresh)
+            check_illum(tile_gate_illum, tile_gate_max_gain)
         self._gate = None
         if watchlist is not None:
             from yolov6.utils.watch import check_params, cost_units
@@ -201,6 +205,7 @@ class Inferer:
         ``<save_dir>/redacted/<image name>`` (``.png`` for a frame of a video or a raw stream)."""
         self._redacted = deque()
         self._gate = None       # with tile_gate: made at the first frame
+        self._gate_gains = []   # with tile_gate_illum='gain': the smallest and largest estimated gain so far (Q12)
         if self.track:
             self._track_begin(crop_size)
         if self.device.type != 'cpu' and (self.tile is not None or self.batch_size > 1 or self.nv12 is not None):
@@ -229,8 +234,12 @@ class Inferer:
                 self._write_delayed(save_dir)
         if self._gate is not None:
             st = self._gate.stats
-            LOGGER.info('Tile gate: %d of %d tiles detected (%d calls, %d forwards)' % (st['tiles_detected'], st['tiles_seen'], st['calls'],
-                                                                                       st['forwards']))
+            gains = ''
+            if self.tile_gate_illum == 'gain':
+                gains = '; no gain estimated' if not self._gate_gains else '; gain %.3f..%.3f, %d tiles out of range' % (
+                    self._gate_gains[0] / 4096.0, self._gate_gains[1] / 4096.0, st['tiles_out_of_range'])
+            LOGGER.info('Tile gate: %d of %d tiles detected (%d calls, %d forwards)%s' % (st['tiles_detected'], st['tiles_seen'], st['calls'],
+                                                                                         st['forwards'], gains))
         LOGGER.info('Average model+NMS rate: %.1f FPS' % fps.accumulate())
         return results
 
@@ -339,9 +348,11 @@ class Inferer:
             gate's outputs are persistent."""
             if self._gate is None:
                 self._gate = runtime.TileGate(model, [tuple(dev_frames[0].shape[:2])], img_size, conf, iou, mdet, thres=self.tile_gate_thres,
-                                              min_cells=self.tile_gate_min_cells, refresh=self.tile_gate_refresh, **kw)
+                                              min_cells=self.tile_gate_min_cells, refresh=self.tile_gate_refresh, illum=self.tile_gate_illum,
+                                              max_gain=self.tile_gate_max_gain, **kw)
             self._gate_check_shape(dev_frames[0].shape, self._gate.shapes[0])
             det, count = self._gate.detect_padded(dev_frames)
+            self._gate_note_gains()
             return det.clone(), count.clone()
 
         def gate_detect(*a, **kw):
@@ -418,9 +429,17 @@ class Inferer:
             run = lambda frames, tiles, tmd: self._tiles_cpu(frames, tiles, tmd, conf_thres, iou_thres, classes, agnostic_nms)   # noqa: E731
             self._gate = TileGateNp(run, [img_src.shape[:2]], self.tile, iou_thres, max_det, self.tile_overlap, self.tile_overview,
                                     self.merge_metric, border, thres=self.tile_gate_thres, min_cells=self.tile_gate_min_cells,
-                                    refresh=self.tile_gate_refresh)
+                                    refresh=self.tile_gate_refresh, illum=self.tile_gate_illum, max_gain=self.tile_gate_max_gain)
         self._gate_check_shape(img_src.shape, self._gate.state.shapes[0])
-        return torch.from_numpy(self._gate.detect([img_src])[0])
+        det = self._gate.detect([img_src])[0]
+        self._gate_note_gains()
+        return torch.from_numpy(det)
+
+    def _gate_note_gains(self):
+        """Keep the smallest and largest gain the gate has estimated (0 = no estimate) for the log line."""
+        seen = [g for gn in self._gate.last_gain for g in gn if g]
+        if seen:
+            self._gate_gains = [min(seen + self._gate_gains[:1]), max(seen + self._gate_gains[1:])]
 
     @staticmethod
     def _gate_check_shape(shape, first):

@@ -210,6 +210,9 @@ SYMBOLS = {
     'lp_tile_gate_luma_batch': (c_int, [POINTER(TileGateDesc), c_int, c_void_p]),
     'lp_tile_gate_update': (c_int, [POINTER(TileGateDesc), c_int, POINTER(c_int), c_int, c_void_p, POINTER(c_int), c_int, c_void_p,
                                     ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'lp_tile_gate_update_gain': (c_int, [POINTER(TileGateDesc), c_int, POINTER(c_int), c_int, c_void_p, POINTER(c_int), c_int, c_void_p,
+                                         ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
     'lp_eval_counts': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'lp_check_sigmoid_monotone': (c_int, [c_void_p, c_void_p]),
     'lp_debug_poison_lds': (c_int, [c_void_p]),

@@ -1353,12 +1353,19 @@ class TileGate:
     independently of its batch slot).  A steady call allocates nothing on the device; the returned tensors are persistent per
     combination of streams: a later call with the same ``stream_of`` overwrites them.
     ``last_flags`` / ``last_ncell``: per frame of the last call the host lists over its tiles (a frame of stream -1: all 1 / 0);
-    ``stats``: calls, tiles_seen, tiles_detected, forwards, summed since construction."""
+    ``stats``: calls, tiles_seen, tiles_detected, forwards, summed since construction.
+    ``illum='gain'`` (lp_tile_gate_update_gain) tolerates exposure and daylight drift: the cells of a tile are compared after the
+    reference is scaled by the tile's gain, the median of its cells' gains, within [1 / ``max_gain``, ``max_gain``]; outside that
+    range the tile is detected again.  The one host read then carries 9 bytes per slot; ``last_gain`` holds the Q12 gains of
+    the last call (4096 = 1; 0: no estimate -- a never-detected tile, a frame of stream -1, and always with ``illum='none'``), and
+    ``stats`` has ``tiles_out_of_range`` as well."""
 
     def __init__(self, model, frame_shapes, img_size, conf_thres, iou_thres, max_det, tile_hw=None, overlap=0.2, overview=True,
-                 metric='iou', border=1, batch=32, tile_max_det=None, thres=2.0, min_cells=1, refresh=50):
+                 metric='iou', border=1, batch=32, tile_max_det=None, thres=2.0, min_cells=1, refresh=50, illum='none', max_gain=1.5):
         from yolov6.utils import tile_gate as tg
         self.thres16, self.min_cells, self.refresh = tg.check_params(thres, min_cells, refresh)
+        self.gain_lo, self.gain_hi = tg.check_illum(illum, max_gain)
+        self.illum = illum
         if metric not in _METRICS:
             raise ValueError('metric must be one of %s' % sorted(_METRICS))
         self.model, self.img_size = model, img_size
@@ -1396,13 +1403,18 @@ class TileGate:
             starts = np.cumsum([0] + [(a * b + 7) // 8 * 8 for a, b in cells])
             self._grids = torch.zeros(int(starts[-1]), dtype=torch.int16, device=dev)
             self._grid_ptr = [self._grids.data_ptr() + 2 * int(o) for o in starts[:-1]]
-            self._out = torch.zeros(5 * S * Tmax, dtype=torch.uint8, device=dev)   # ncell int32 [S*Tmax], then flag uint8 [S*Tmax]: one read
-            self._out_host = torch.zeros(5 * S * Tmax, dtype=torch.uint8).pin_memory()
+            # ncell int32 [S*Tmax], in gain mode gain int32 [S*Tmax], then flag uint8 [S*Tmax]: one read
+            self._out_words = 2 if illum == 'gain' else 1
+            nb = (4 * self._out_words + 1) * S * Tmax
+            self._out = torch.zeros(nb, dtype=torch.uint8, device=dev)
+            self._out_host = torch.zeros(nb, dtype=torch.uint8).pin_memory()
             self.cache_det = torch.zeros(S, Tmax, self.tile_max_det, abi.LP_DET_COLS, dtype=torch.float32, device=dev)
             self.cache_count = torch.zeros(S, Tmax, dtype=torch.int32, device=dev)
         self._calls = {}
-        self.last_flags, self.last_ncell = [], []
+        self.last_flags, self.last_ncell, self.last_gain = [], [], []
         self.stats = dict(calls=0, tiles_seen=0, tiles_detected=0, forwards=0)
+        if illum == 'gain':
+            self.stats['tiles_out_of_range'] = 0
 
     def reset(self, streams=None):
         """Forget ``streams`` (all for None): their tiles count as never detected and their cached rows are cleared."""
@@ -1441,10 +1453,15 @@ class TileGate:
     def _update(self, desc, streams):
         """lp_tile_gate_update on the current stream: flags and changed-cell counts of the call into ``_out``, ref and age moved on."""
         S, Tmax, n = self.n_streams, self.max_tiles, len(streams)
-        abi.check(abi.load().lp_tile_gate_update(desc, n, (ctypes.c_int * n)(*streams), S, _dptr(self._table), self._n_tiles, Tmax,
-                                                 _dptr(self.ref), self._ref_elems, _dptr(self.age), self.thres16, self.min_cells,
-                                                 self.refresh, ctypes.c_void_p(self._out.data_ptr() + 4 * S * Tmax), _dptr(self._out),
-                                                 _stream_ptr(self.device)), 'lp_tile_gate_update')
+        head = (desc, n, (ctypes.c_int * n)(*streams), S, _dptr(self._table), self._n_tiles, Tmax, _dptr(self.ref), self._ref_elems,
+                _dptr(self.age), self.thres16, self.min_cells, self.refresh)
+        flag = ctypes.c_void_p(self._out.data_ptr() + 4 * self._out_words * S * Tmax)
+        if self.illum == 'gain':
+            gain = ctypes.c_void_p(self._out.data_ptr() + 4 * S * Tmax)
+            abi.check(abi.load().lp_tile_gate_update_gain(*head, self.gain_lo, self.gain_hi, flag, _dptr(self._out), gain,
+                                                          _stream_ptr(self.device)), 'lp_tile_gate_update_gain')
+        else:
+            abi.check(abi.load().lp_tile_gate_update(*head, flag, _dptr(self._out), _stream_ptr(self.device)), 'lp_tile_gate_update')
 
     def detect_padded(self, frames, stream_of=None):
         from yolov6.utils import tile_gate as tg
@@ -1461,7 +1478,7 @@ class TileGate:
                 raise ValueError('TileGate: a frame of %s on stream %d, whose frames are %s: a stream has one fixed frame size'
                                  % (tuple(frames[f].shape[:2]), so[f], self.shapes[so[f]]))
         S, Tmax, n = self.n_streams, self.max_tiles, len(gated)
-        flags, ncell = [None] * len(frames), [None] * len(frames)
+        flags, ncell, gains = [None] * len(frames), [None] * len(frames), [None] * len(frames)
         det_g = count_g = None
         todo = []
         with torch.cuda.device(dev):
@@ -1473,10 +1490,12 @@ class TileGate:
                 self._out_host.copy_(self._out, non_blocking=True)
                 torch.cuda.current_stream(dev).synchronize()          # the one host read of a call: the host builds the tile batches
                 host = self._out_host.numpy()
-                nc_all, fl_all = host[:4 * S * Tmax].view(np.int32).reshape(S, Tmax), host[4 * S * Tmax:].reshape(S, Tmax)
+                words = host[:4 * self._out_words * S * Tmax].view(np.int32).reshape(self._out_words, S, Tmax)
+                nc_all, fl_all = words[0], host[4 * self._out_words * S * Tmax:].reshape(S, Tmax)
                 for k, f in enumerate(gated):
                     nt = len(self.plans[so[f]])
                     flags[f], ncell[f] = fl_all[k, :nt].tolist(), nc_all[k, :nt].tolist()
+                    gains[f] = words[1][k, :nt].tolist() if self.illum == 'gain' else [0] * nt
                     if min(ncell[f]) < 0:
                         raise RuntimeError('TileGate: the device tile table of stream %d is damaged' % so[f])
                     todo += [(f, t) for t in range(nt) if flags[f][t]]
@@ -1496,8 +1515,10 @@ class TileGate:
             self.stats['tiles_seen'] += sum(len(self.plans[so[f]]) for f in gated)
             self.stats['tiles_detected'] += len(todo)
             self.stats['forwards'] += -(-len(todo) // self.batch)
+            if self.illum == 'gain':
+                self.stats['tiles_out_of_range'] += tg.count_out_of_range([gains[f] for f in gated], self.gain_lo, self.gain_hi)
             if n == len(frames):
-                self.last_flags, self.last_ncell = flags, ncell
+                self.last_flags, self.last_ncell, self.last_gain = flags, ncell, gains
                 return det_g, count_g
             # frames of stream -1: not gated, nothing kept
             loose = [f for f, s in enumerate(so) if s < 0]
@@ -1506,7 +1527,7 @@ class TileGate:
                                                  self.overlap, self.overview, self.metric, self.border, self.batch, self._arg_tile_max_det)
             for f, fr in zip(loose, lf):
                 nt = len(plan_tiled([tuple(fr.shape[:2])], self.img_size, self.max_det, self.tile_hw, self.overlap, self.overview)[0])
-                flags[f], ncell[f] = [1] * nt, [0] * nt
+                flags[f], ncell[f], gains[f] = [1] * nt, [0] * nt, [0] * nt
                 self.stats['tiles_seen'] += nt
                 self.stats['tiles_detected'] += nt
                 self.stats['forwards'] += -(-nt // self.batch)
@@ -1517,7 +1538,7 @@ class TileGate:
                 det[g], count[g] = det_g, count_g
             u = torch.tensor(loose, dtype=torch.int64, device=dev)
             det[u], count[u] = det_u, count_u
-        self.last_flags, self.last_ncell = flags, ncell
+        self.last_flags, self.last_ncell, self.last_gain = flags, ncell, gains
         return det, count
 
     def detect(self, frames, stream_of=None):
