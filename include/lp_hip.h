@@ -196,7 +196,8 @@ int lp_engine_profile_ops(lp_engine* e, const void* x, int x_dtype, float* pred,
  * 3x3 stride-1 kernel, nbuf 3).  LP_VARIANT_PIPE_P belongs to the stem only (op 1, over the space-to-depth image the input op
  * writes): with it the stem gathers its pixels from the caller's NCHW frame itself and the input op is skipped, whenever the
  * frame passed to lp_engine_forward has the engine's 16-bit dtype (other dtypes: input op + the stem's other variant).
- * lp_engine_set_op_variant forces one (tests, experiments): LP_ERR_UNSUPPORTED if it does not fit the op. */
+ * lp_engine_set_op_variant forces one (tests, experiments): LP_ERR_UNSUPPORTED if it does not fit the op, and then nothing changes:
+ * the variants and fused forms that were on, the remembered tuning and the prepared launches stay as they were. */
 enum { LP_VARIANT_STREAM64 = 16, LP_VARIANT_STREAM128 = 17, LP_VARIANT_ROWS = 18,
        /* pipelined 3x3 stride-1 kernel (persistent, 3-slot LDS ring, nbuf 3): 128 couts x 256 px, 64 x 512, 128 x 128, 32 x 512 */
        LP_VARIANT_PIPE_D = 32, LP_VARIANT_PIPE_B = 33, LP_VARIANT_PIPE_F = 34, LP_VARIANT_PIPE_C = 35,
@@ -228,6 +229,12 @@ enum { LP_VARIANT_BOX_SPARSE = 46, LP_VARIANT_BOX_DENSE = 47 };
  * one op; an engine created under LP_S2P16=1 runs every eligible layer on it (by rule, never by timing). */
 enum { LP_VARIANT_PIPE16_S2A = 48, LP_VARIANT_PIPE16_S2B = 49 };
 int lp_engine_op_carrier(const lp_engine* e, int op, int frame_direct);
+/* The library's own view of the frozen graph (tests): the tensor ids op `op` reads -- src[0..n_src), -1 behind them; res, or -1 --
+ * and writes -- dst[0..2], -1 for none (the second destination of a two-destination conv, the three of a pool chain; head ops
+ * write pred, not a tensor) -- as they stand after lp_engine_finalize, i.e. after the space-to-depth rewrite of the stem: the input
+ * op then writes a tensor of 12 channels at half resolution that the host never declared, the stem reads it, and the declared
+ * input tensor is unused.  Any pointer may be NULL.  No other effect. */
+int lp_engine_op_io(const lp_engine* e, int op, int* src /*[LP_MAX_SRC]*/, int* n_src, int* res, int* dst /*[3]*/);
 int lp_engine_autotune(lp_engine* e, const void* x, int x_dtype, float* pred, void* stream, int reps);
 int lp_engine_op_variant(const lp_engine* e, int op, int* cfg, int* nbuf);
 int lp_engine_set_op_variant(lp_engine* e, int op, int cfg, int nbuf);

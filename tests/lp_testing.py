@@ -1295,3 +1295,276 @@ def cls_check(ref, conf, passed, cf, ci, key_hi=None):
     if key_hi is not None and not np.array_equal(np.asarray(key_hi)[want], score_key_hi(sum8_f32(cf, 7))):
         bad.append('key')
     return bad
+
+
+# ---- graphs at the edges of the fused forms' legality rules (tests/test_graph_rules_cpu.py, tests/test_graph_rules_gpu.py) ------------
+# Four engine forms skip writing a tensor because a scan of the frozen graph says nobody else reads it: the planar stem and the
+# fused stem (LP_VARIANT_PIPE_P on op 1, LP_VARIANT_FUSED_STEM2 on op 2), the fused 1x1 + 3x3 stride-2 form (LP_VARIANT_FUSED_PW_S2)
+# and the fused BiFusion form (LP_VARIANT_FUSED_BIFUSION).  Per form one builder: ``change`` None is the BASE graph the form must
+# accept, every other value of its *_CHANGES table a graph that differs from the base in that one thing and must be refused.  The
+# builders record what they add (``RuleGraph.nodes``), so that ``rule_graph_expected`` can state every tensor's bits in float64.
+RULE_MARK = 0x7FA5                      # a NaN in fp16 and in bf16 that no kernel produces from finite data: "never written"
+PIPE_P, FUSED_STEM2, FUSED_PW_S2, FUSED_BIFUSION = 36, 37, 38, 45          # lp_hip.h's variant codes of the four forms
+
+
+def _zero_data(name, wshape, nbias, stage):
+    return np.zeros(wshape, np.float32), np.zeros(nbias, np.float32)
+
+
+class RuleGraph:
+    """Records a small op graph while adding it to ``eng`` (a runtime.Engine that is not finished yet).  Tensors are named;
+    ``t[name]`` is the id, ``op[name]`` the op index of the layer that writes it.  ``data(name, weight shape, bias length, stage)``
+    -> (weight, bias) supplies the layers' parameters (default: zeros); stage 1 = a layer over network inputs, 2 = over the outputs
+    of stage 1, 3 = anything later (grid_rule_data keeps each stage's sums exact)."""
+
+    def __init__(self, eng, data=None):
+        self.eng, self.data = eng, data or _zero_data
+        self.t, self.chan, self.sl = {'input': eng.input_id}, {eng.input_id: 3}, {eng.input_id: 0}
+        self.op, self.nodes, self.sources = {'input': 0}, [dict(kind='input', op=0, dsts=[eng.input_id])], []
+        self.form = self.form_op = None
+        self.carried_ops, self.carried_tensors = [], []
+
+    def _tensor(self, name, c, sl):
+        assert name not in self.t, name
+        tid = self.eng.tensor(c, sl)
+        self.t[name], self.chan[tid], self.sl[tid] = tid, c, sl
+        return tid
+
+    def source(self, name, c, sl):
+        """A tensor no op writes: the test fills it.  A multiple of 8 channels, so that it has no padding channels."""
+        assert c % 8 == 0
+        self.sources.append(name)
+        return self._tensor(name, c, sl)
+
+    def conv(self, name, srcs, cout, k, s, act, res=None, stage=3, also=None):
+        """act(conv(cat(srcs)) + b) [+ RES_ALPHA * res] -> tensor ``name``; ``also`` = (name2, cout2): a two-destination launch."""
+        from yolov6.hip import abi
+        ids = [self.t[n] for n in srcs]
+        sl = self.sl[ids[0]]
+        cin, c2 = sum(self.chan[i] for i in ids), (also[1] if also else 0)
+        w, b = self.data(name, (cout + c2, cin, k, k), cout + c2, stage)
+        wn, bn = (np.ascontiguousarray(np.asarray(v, dtype=np.float32)) for v in (w, b))
+        dst = self._tensor(name, cout, sl + (s == 2))
+        dst2 = self._tensor(also[0], c2, sl + (s == 2)) if also else -1
+        self.eng._add_conv(ids, wn, bn, k, s, {'none': abi.LP_ACT_NONE, 'relu': abi.LP_ACT_RELU}[act], dst, dst2,
+                           res=None if res is None else self.t[res], alpha=RES_ALPHA if res is not None else 0.0)
+        self.op[name] = len(self.nodes)
+        self.nodes.append(dict(kind='conv', op=len(self.nodes), name=name, srcs=ids, res=None if res is None else self.t[res], k=k, s=s,
+                               act=act, w=w, b=b, dsts=[dst] + ([dst2] if also else []), split=cout))
+        return dst
+
+    def deconv(self, name, src, cout, stage=3):
+        """2x2 stride-2 transposed convolution with bias, no activation."""
+        from yolov6.hip import abi
+        sid = self.t[src]
+        w, b = self.data(name, (self.chan[sid], cout, 2, 2), cout, stage)
+        wn, bn = (np.ascontiguousarray(np.asarray(v, dtype=np.float32)) for v in (w, b))
+        dst = self._tensor(name, cout, self.sl[sid] - 1)
+        abi.check(self.eng.lib.lp_engine_add_deconv2x2(self.eng.h, sid, dst, self.eng._ptr(wn), self.eng._ptr(bn)), 'lp_engine_add_deconv2x2')
+        self.op[name] = len(self.nodes)
+        self.nodes.append(dict(kind='deconv', op=len(self.nodes), name=name, srcs=[sid], res=None, w=w, b=b, dsts=[dst]))
+        return dst
+
+    def tail(self, name):
+        """Two downstream readers of tensor ``name`` (the output of a fused kernel): one reads it as a source, one as a residual."""
+        c = self.chan[self.t[name]]
+        self.conv('t1', [name], c, 1, 1, 'relu')
+        self.conv('t2', ['t1'], c, 1, 1, 'relu', res=name)
+
+    def carries(self, form, form_op, ops, tensors):
+        """What the accepted form does: ``form`` on op ``form_op`` carries the ops ``ops``; the named ``tensors`` stay unwritten."""
+        self.form, self.form_op, self.carried_ops, self.carried_tensors = form, self.op[form_op], [self.op[o] for o in ops], list(tensors)
+        return self
+
+
+# change -> does the PLANAR stem still take op 1 (the fused stem must refuse every one of them)
+STEM_CHANGES = {
+    'stem_read_by_later_conv': True, 'stem_second_source_of_later_conv': True, 'stem_residual_of_later_op': True,
+    'l2_residual': True, 'l2_two_destinations': True, 'l2_two_sources': True, 'stem_act_none': True, 'l2_act_none': True,
+    'stem_two_destinations': False, 'input_second_reader': False,
+}
+
+
+def stem_rule_graph(eng, change=None, data=None):
+    """input -> stem 3x3 s2 ReLU 3 -> 24 (op 1) -> l2 3x3 s2 ReLU 24 -> 64 (op 2) -> two readers of l2 only."""
+    assert change is None or change in STEM_CHANGES, change
+    g = RuleGraph(eng, data)
+    s_act, l_act = ('none' if change == 'stem_act_none' else 'relu'), ('none' if change == 'l2_act_none' else 'relu')
+    g.conv('stem', ['input'], 24, 3, 2, s_act, stage=1, also=('stem_b', 8) if change == 'stem_two_destinations' else None)
+    if change in ('l2_two_sources', 'stem_second_source_of_later_conv'):
+        g.source('e1', 8, 1)
+    if change == 'l2_residual':
+        g.source('r2', 64, 2)
+    g.conv('l2', ['stem', 'e1'] if change == 'l2_two_sources' else ['stem'], 64, 3, 2, l_act, stage=2,
+           res='r2' if change == 'l2_residual' else None, also=('l2_b', 8) if change == 'l2_two_destinations' else None)
+    g.tail('l2')
+    if change == 'stem_read_by_later_conv':
+        g.conv('x1', ['stem'], 8, 1, 1, 'relu')
+    if change == 'stem_second_source_of_later_conv':
+        g.conv('x1', ['e1', 'stem'], 8, 1, 1, 'relu')
+    if change == 'stem_residual_of_later_op':                 # a 1x1 layer at the stem's scale: over a transposed conv of l2's output
+        g.deconv('up', 'l2', 24)
+        g.conv('x1', ['up'], 24, 1, 1, 'relu', res='stem')
+    if change == 'input_second_reader':
+        g.conv('x1', ['input'], 8, 3, 2, 'relu', stage=1)
+    return g.carries(FUSED_STEM2, 'l2', ['input', 'stem'], ['stem'])
+
+
+PW_CHANGES = ('p_read_by_later_conv', 'p_residual_of_later_op', 'op_between', 'lanes_differ', 'p_read_on_other_lane', 'p_two_destinations',
+              'p_residual', 'p_two_sources', 'c_residual', 'c_two_destinations')
+
+
+def pw_rule_graph(eng, change=None, data=None):
+    """x (64 channels, stride 8) -> p 1x1 ReLU 64 -> 64 -> c 3x3 s2 ReLU 64 -> 64 (the op right behind p) -> two readers of c only."""
+    assert change is None or change in PW_CHANGES, change
+    g = RuleGraph(eng, data)
+    g.source('x', 64, 3)
+    for name, c, sl, when in (('x2', 8, 3, 'p_two_sources'), ('rp', 64, 3, 'p_residual'), ('rc', 64, 4, 'c_residual')):
+        if change == when:
+            g.source(name, c, sl)
+    if change == 'lanes_differ':
+        eng.lane(1)
+    g.conv('p', ['x', 'x2'] if change == 'p_two_sources' else ['x'], 64, 1, 1, 'relu', stage=1, res='rp' if change == 'p_residual' else None,
+           also=('p_b', 8) if change == 'p_two_destinations' else None)
+    eng.lane(0)
+    if change == 'op_between':
+        g.conv('x1', ['x'], 8, 1, 1, 'relu', stage=1)
+    g.conv('c', ['p'], 64, 3, 2, 'relu', stage=2, res='rc' if change == 'c_residual' else None,
+           also=('c_b', 8) if change == 'c_two_destinations' else None)
+    g.tail('c')
+    if change == 'p_read_by_later_conv':
+        g.conv('x1', ['p'], 8, 1, 1, 'relu')
+    if change == 'p_residual_of_later_op':
+        g.conv('x1', ['x'], 64, 1, 1, 'relu', stage=1, res='p')
+    if change == 'p_read_on_other_lane':
+        eng.lane(1)
+        g.conv('x1', ['p'], 8, 1, 1, 'relu')
+        eng.lane(0)
+    return g.carries(FUSED_PW_S2, 'c', ['p'], ['p'])
+
+
+BF_CHANGES = ('u_read_by_later_conv', 'a_read_by_later_conv', 'u_residual_of_later_op', 'a_residual_of_later_op', 'cv3_residual',
+              'cv3_two_destinations', 'cv3_act_none', 'sources_reordered', 'third_source_128', 'cv1_first_of_two_destinations')
+
+
+def bifusion_rule_graph(eng, change=None, data=None):
+    """The graph of test_bifusion_fused_equals_its_three_ops: x0 (64 channels, stride 16), x1 (128, stride 8), d (64, stride 8);
+    u = transposed conv of x0 (op 1), a = cv1 = 1x1 ReLU 128 -> 64 of x1 (op 2), cv3 = 1x1 ReLU over [u, a, d] -> 64 (op 3), then
+    two readers of cv3 only."""
+    assert change is None or change in BF_CHANGES, change
+    g = RuleGraph(eng, data)
+    g.source('x0', 64, 4)
+    g.source('x1', 128, 3)
+    g.source('d', 128 if change == 'third_source_128' else 64, 3)
+    if change == 'cv3_residual':
+        g.source('r3', 64, 3)
+    g.deconv('u', 'x0', 64, stage=1)
+    g.conv('a', ['x1'], 64, 1, 1, 'relu', stage=1, also=('a_b', 8) if change == 'cv1_first_of_two_destinations' else None)
+    g.conv('cv3', ['a', 'u', 'd'] if change == 'sources_reordered' else ['u', 'a', 'd'], 64, 1, 1, 'none' if change == 'cv3_act_none' else 'relu',
+           stage=2, res='r3' if change == 'cv3_residual' else None, also=('cv3_b', 8) if change == 'cv3_two_destinations' else None)
+    g.tail('cv3')
+    for name, src in (('u_read_by_later_conv', 'u'), ('a_read_by_later_conv', 'a')):
+        if change == name:
+            g.conv('x1r', [src], 8, 1, 1, 'relu')
+    for name, src in (('u_residual_of_later_op', 'u'), ('a_residual_of_later_op', 'a')):
+        if change == name:
+            g.conv('x1r', ['d'], 64, 1, 1, 'relu', stage=1, res=src)
+    return g.carries(FUSED_BIFUSION, 'cv3', ['u', 'a'], ['u', 'a'])
+
+
+RULE_GRAPHS = {'stem': (stem_rule_graph, tuple(STEM_CHANGES)), 'pw': (pw_rule_graph, PW_CHANGES), 'bifusion': (bifusion_rule_graph, BF_CHANGES)}
+
+
+def engine_state(eng, tiles=False):
+    """What a refused request must leave alone: per op (variant, ring depth), the carrier with and without a direct frame, and --
+    ``tiles``: an arena is bound -- the tile choice and the prepared tile (None where the op's kernel has no tiles)."""
+    out = []
+    for i in range(eng.lib.lp_engine_num_ops(eng.h)):
+        row = [eng.variant(i), eng.lib.lp_engine_op_carrier(eng.h, i, 1), eng.lib.lp_engine_op_carrier(eng.h, i, 0)]
+        if tiles:
+            try:
+                row.append(eng.tile(i))
+            except RuntimeError:
+                row.append(None)
+        out.append(tuple(row))
+    return out
+
+
+def grid_unit(t64):
+    """The largest power of two (at most 1) that every element of ``t64`` is a multiple of."""
+    for k in range(0, 24):
+        s = t64 * float(2 ** k)
+        if torch.equal(torch.round(s), s):
+            return 2.0 ** -k
+    raise AssertionError('not grid data')
+
+
+def grid_rule_data(dtype, seed=0):
+    """``data`` of a RuleGraph whose sums stay exact over three and more chained layers: stage 1 and 2 as E.fused_data draws them
+    (x, w multiples of 1/4 in [-2, 2], the second layer's bias sized so that its outputs need rounding), later layers four weights
+    of +-1 per output channel (and tap / phase) and a small bias, so that neither the grid unit nor the magnitudes grow much."""
+    import zlib
+    xw, bb, _ = GRID_RANGE[dtype]
+
+    def data(name, wshape, nbias, stage):
+        s = seed + zlib.crc32(name.encode()) % 100000
+        if stage == 1:
+            return grid_rand(wshape, s, -2.0, 2.0), grid_rand((nbias,), s + 1, -8.0, 32.0, 1.0 / 16)
+        if stage == 2:
+            lim = 2.0 if wshape[1] * wshape[2] * wshape[3] <= 9 * 32 else 1.0          # by fan-in, as E.fused_data
+            return grid_rand(wshape, s, -lim, lim), grid_rand((nbias,), s + 1, -bb / 4, bb, 1.0 / 16)
+        g = torch.Generator().manual_seed(s)
+        w = torch.zeros(wshape, dtype=torch.float64)
+        transposed = wshape[2] == 2                                   # [Cin][Cout][2][2], else [Cout][Cin][k][k]
+        nout, nin = (wshape[1], wshape[0]) if transposed else (wshape[0], wshape[1])
+        for o in range(nout):
+            for tap in range(wshape[2] * wshape[3]):
+                idx = torch.randperm(nin, generator=g)[:4]
+                sign = torch.randint(0, 2, (len(idx),), generator=g).double() * 2 - 1
+                if transposed:
+                    w[idx, o, tap // wshape[3], tap % wshape[3]] = sign
+                else:
+                    w[o, idx, tap // wshape[3], tap % wshape[3]] = sign
+        return w, grid_rand((nbias,), s + 1, -8.0, 32.0, 1.0 / 16)
+    return data
+
+
+def rule_graph_inputs(g, dtype, B, H, W, seed=0):
+    """Grid values for the frame and every source tensor of a RuleGraph at frame size H x W: {tensor id: float64 [B,C,h,w]};
+    multiples of 1/4 in [-2, 2], residual sources (names starting with 'r') in the storage type's residual range."""
+    vals = {g.t['input']: grid_rand((B, 3, H, W), seed + 3, -2.0, 2.0)}
+    for i, name in enumerate(g.sources):
+        tid = g.t[name]
+        lim = GRID_RANGE[dtype][2] if name.startswith('r') else 2.0
+        vals[tid] = grid_rand((B, g.chan[tid], H >> g.sl[tid], W >> g.sl[tid]), seed + 10 + i, -lim, lim)
+    return vals
+
+
+def rule_graph_expected(g, vals, dtype):
+    """Expected bits of every tensor an op of the RuleGraph writes, from float64: {tensor id: tensor of ``dtype``}.  Per layer the
+    sum is asserted to be exact in fp32 in ANY order: every product and the bias are multiples of unit = unit(x) * unit(w), and
+    sum |x||w| + |b| -- the actual magnitudes, per output element -- stays below 2^24 units; the expected tensor is then the
+    float64 sum under exact_epilogue (one rounding, a second one behind the residual add).  ``vals`` is not modified."""
+    import torch.nn.functional as F
+    val = {t: v.clone() for t, v in vals.items()}
+    for t, v in val.items():
+        assert torch.equal(v.to(dtype).double(), v), 'the storage type does not hold an input'
+    want = {}
+    for n in g.nodes[1:]:
+        x = torch.cat([val[s] for s in n['srcs']], 1)
+        w, b = torch.as_tensor(n['w']).double(), torch.as_tensor(n['b']).double()
+        assert torch.equal(w.to(dtype).double(), w) and torch.equal(b.float().double(), b), n['name']
+        if n['kind'] == 'deconv':
+            op = lambda a, c, d: F.conv_transpose2d(a, c, d, stride=2)
+        else:
+            op = lambda a, c, d, n=n: F.conv2d(a, c, d, stride=n['s'], padding=n['k'] // 2)
+        pre, mag = op(x, w, b), op(x.abs(), w.abs(), b.abs())
+        unit = grid_unit(x) * grid_unit(w)
+        assert grid_unit(b) >= unit and float(mag.max()) < 2 ** 24 * unit, (n['name'], float(mag.max()), unit)
+        res = None if n['res'] is None else val[n['res']]
+        y = exact_epilogue(pre, n.get('act', 'none'), dtype, res)
+        assert bool(torch.isfinite(y.float()).all()), n['name']
+        parts = [y] if len(n['dsts']) == 1 else [y[:, :n['split']], y[:, n['split']:]]
+        for t, p in zip(n['dsts'], parts):
+            want[t], val[t] = p.contiguous(), p.double()
+    return want

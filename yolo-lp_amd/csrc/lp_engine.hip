@@ -1600,41 +1600,50 @@ extern "C" int lp_engine_set_op_variant(lp_engine* e, int op_idx, int cfg, int n
     if (op.kind == OP_INPUT || op.kind == OP_POOL || op.mode != MODE_ACT) return fail(LP_ERR_UNSUPPORTED, "lp_engine_set_op_variant: op has no variants");
     const int ks = op.kind == OP_CONV ? op.ksize : 1, stv = op.kind == OP_CONV ? op.stride : 1;
     const int cb = conv_shape(e->dtype, op.cfg, ks, stv).CB;
+    // Validate first, mutate after: a refused request (LP_ERR_UNSUPPORTED) leaves the op, its fused / planar forms, the remembered
+    // tuning and the prepared launches as they were.  A fused form switches off the forms listed before it below; any other
+    // variant switches all four off.
+    const int before[9] = {op.cfg, op.nbuf, op.stream_wc, op.stream_rd, op.pipe, op.planar, op.fused, op.fused_pw, op.fused_bf};
+    auto commit = [&]() -> int {
+        if (e->arena && op_idx < (int)e->launches.size()) {
+            const int rc = prepare_op(e, (size_t)op_idx);
+            if (rc) {       // (a fused / planar form without a tile for the bound shape)
+                op.cfg = before[0]; op.nbuf = before[1]; op.stream_wc = before[2]; op.stream_rd = before[3]; op.pipe = before[4];
+                op.planar = before[5]; op.fused = before[6]; op.fused_pw = before[7]; op.fused_bf = before[8];
+                const std::string why = g_err;
+                prepare_op(e, (size_t)op_idx);
+                return fail(rc, why);
+            }
+        }
+        e->tuned.erase({e->B, e->H, e->W});
+        return LP_OK;
+    };
     if (cfg == LP_VARIANT_FUSED_BIFUSION) {       // BiFusion: transposed conv + cv1 + this cv3 as one kernel
         if (op.bf_up < 0 || nbuf != 3) return fail(LP_ERR_UNSUPPORTED, "lp_engine_set_op_variant: not the cv3 of a 64-channel BiFusion level");
         op.fused_bf = 1;
-        e->tuned.erase({e->B, e->H, e->W});
-        if (e->arena && op_idx < (int)e->launches.size()) return prepare_op(e, (size_t)op_idx);
-        return LP_OK;
+        return commit();
     }
-    op.fused_bf = 0;
     if (cfg == LP_VARIANT_FUSED_PW_S2) {          // the 1x1 layer before this 3x3 stride-2 layer + this layer as one kernel
         if (!pw_fused_possible(e, (size_t)op_idx) || nbuf != 3)
             return fail(LP_ERR_UNSUPPORTED, "lp_engine_set_op_variant: no 1x1 layer of at most 64 channels feeds this 3x3 stride-2 layer alone");
+        op.fused_bf = 0;
         op.fused_pw = 1;
-        e->tuned.erase({e->B, e->H, e->W});
-        if (e->arena && op_idx < (int)e->launches.size()) return prepare_op(e, (size_t)op_idx);
-        return LP_OK;
+        return commit();
     }
-    op.fused_pw = 0;
     if (cfg == LP_VARIANT_FUSED_STEM2) {          // stem + this layer as one kernel: on top of whatever variants run for other frame dtypes
         if (op_idx != 2 || !stem2_fused_possible(e) || nbuf != 3)
             return fail(LP_ERR_UNSUPPORTED, "lp_engine_set_op_variant: only the layer behind the stem (3x3 stride 2, <= 64 channels) has the fused form");
+        op.fused_bf = op.fused_pw = 0;
         op.fused = 1;
-        e->tuned.erase({e->B, e->H, e->W});
-        if (e->arena && op_idx < (int)e->launches.size()) return prepare_op(e, (size_t)op_idx);
-        return LP_OK;
+        return commit();
     }
-    op.fused = 0;
     if (cfg == LP_VARIANT_PIPE_D + PIPE_P) {      // the stem reading the caller's frame: on top of whatever variant runs for other frame dtypes
         if (op_idx != 1 || !stem_planar_possible(e) || nbuf != 3)
             return fail(LP_ERR_UNSUPPORTED, "lp_engine_set_op_variant: only the stem over the space-to-depth image has the planar form");
+        op.fused_bf = op.fused_pw = op.fused = 0;
         op.planar = 1;
-        e->tuned.erase({e->B, e->H, e->W});
-        if (e->arena && op_idx < (int)e->launches.size()) return prepare_op(e, (size_t)op_idx);
-        return LP_OK;
+        return commit();
     }
-    op.planar = 0;
     if ((cfg >= LP_VARIANT_PIPE_D && cfg < LP_VARIANT_PIPE_D + PIPE_COUNT) || pipe_is_16(cfg - LP_VARIANT_PIPE_D)) {
         const int pc = cfg - LP_VARIANT_PIPE_D;
         if (!conv_pipe_fits(e->dtype, pc, cb, ks, stv, op.mode, op.nct, op.nphase, op.nchunks) || op.kind != OP_CONV || nbuf != 3)
@@ -1656,9 +1665,8 @@ extern "C" int lp_engine_set_op_variant(lp_engine* e, int op_idx, int cfg, int n
         op.cfg = cfg;
         op.nbuf = nbuf;
     }
-    e->tuned.erase({e->B, e->H, e->W});
-    if (e->arena && op_idx < (int)e->launches.size()) return prepare_op(e, (size_t)op_idx);
-    return LP_OK;
+    op.fused_bf = op.fused_pw = op.fused = op.planar = 0;
+    return commit();
 }
 
 // Where the tile choice of an op's current form lives and which launch holds its prepared geometry: the fused / planar forms keep
@@ -1717,6 +1725,16 @@ extern "C" int lp_engine_op_carrier(const lp_engine* e, int op, int frame_direct
         if (e->ops[1].planar && op == 0) return 1;
     }
     return -1;
+}
+
+extern "C" int lp_engine_op_io(const lp_engine* e, int op, int* src, int* n_src, int* res, int* dst) {
+    if (!e || !e->finalized || op < 0 || op >= (int)e->ops.size()) return fail(LP_ERR_ARG, "lp_engine_op_io: engine not finalized, or op index");
+    const Op& o = e->ops[(size_t)op];
+    if (src) for (int k = 0; k < LP_MAX_SRC; ++k) src[k] = k < o.nsrc ? o.src[k] : -1;
+    if (n_src) *n_src = o.nsrc;
+    if (res) *res = o.res;
+    if (dst) { dst[0] = o.dst; dst[1] = o.dst2; dst[2] = o.dst3; }
+    return LP_OK;
 }
 
 extern "C" int lp_engine_op_variant(const lp_engine* e, int op, int* cfg, int* nbuf) {

@@ -149,6 +149,7 @@ SYMBOLS = {
     'lp_engine_set_single_lane': (c_int, [c_void_p, c_int]),
     'lp_engine_set_mfma16': (c_int, [c_void_p, c_int]),
     'lp_engine_op_carrier': (c_int, [c_void_p, c_int, c_int]),
+    'lp_engine_op_io': (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     'lp_engine_num_ops': (c_int, [c_void_p]),
     'lp_engine_op_info': (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                   POINTER(c_double), POINTER(c_double)]),

@@ -443,6 +443,20 @@ class Engine:
         abi.check(self.lib.lp_engine_op_tile(self.h, op, ctypes.byref(c), ctypes.byref(th), ctypes.byref(tw)), 'lp_engine_op_tile')
         return c.value, th.value, tw.value
 
+    def variant(self, op):
+        """(cfg, nbuf) of op ``op``'s current kernel variant (lp_engine_op_variant)."""
+        cfg, nb = ctypes.c_int(), ctypes.c_int()
+        abi.check(self.lib.lp_engine_op_variant(self.h, op, ctypes.byref(cfg), ctypes.byref(nb)), 'lp_engine_op_variant')
+        return cfg.value, nb.value
+
+    def op_io(self, op):
+        """(sources, residual or -1, destinations) of op ``op`` as the frozen graph has them, i.e. after the space-to-depth rewrite of
+        the stem (lp_engine_op_io): lists of tensor ids."""
+        src, dst = (ctypes.c_int * abi.LP_MAX_SRC)(), (ctypes.c_int * 3)()
+        n, res = ctypes.c_int(), ctypes.c_int()
+        abi.check(self.lib.lp_engine_op_io(self.h, op, src, ctypes.byref(n), ctypes.byref(res), dst), 'lp_engine_op_io')
+        return list(src[:n.value]), res.value, [t for t in dst if t >= 0]
+
     def tensor_view(self, tid):
         """Zero-copy [B,C,h,w] view (channels_last strides) of an arena tensor."""
         off, c, cs, h, w = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
