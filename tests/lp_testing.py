@@ -1568,3 +1568,270 @@ def rule_graph_expected(g, vals, dtype):
         for t, p in zip(n['dsts'], parts):
             want[t], val[t] = p.contiguous(), p.double()
     return want
+
+
+# ---- scenes at the edges of the greedy NMS schedule, and a model of that schedule (tests/test_nms_schedule_cpu.py, _gpu.py) ----
+# greedy_kernel (csrc/lp_nms.hip) resolves the sorted candidates 64 at a time: chunk c's candidates are struck by the kept list
+# through chunk c - 2 (fifteen waves, each a 1-in-15 share of the list, eight entries per trip = 120 list entries per trip of the
+# block, then a remainder loop; a ring of three masks), by the SURVIVORS of chunk c - 1 (xt & kept_prev) and by the earlier survivors
+# of their own chunk (mt, resolved in candidate order); candidates are staged 1024 = 16 chunks at a time.  The scenes below put one
+# decision on every such edge.  Their geometry is spill_case's, denser: 8 x 8 boxes in CELLS of a 16-px grid, 128 cells per row; a
+# cell holds a CHAIN, member s being the cell's box shifted by s px in x.  With iou_thres 0.7 the only pairs over the threshold are
+# members one shift apart (IoU 56/72) and identical boxes; two apart 48/80, three apart 40/88, other cells 0: every decision has a
+# margin of more than 0.07.  Row r of a scene has rank r (strictly decreasing exact scores); to_pred scatters the ranks over the
+# anchors of a prediction tensor, so the sort is part of every case.
+NMS_IOU, NMS_CONF = 0.7, 0.25
+NMS_CHAIN_IOU = (1.0, 56.0 / 72.0, 48.0 / 80.0, 40.0 / 88.0)          # by the difference of two members' shifts
+NMS_MUTANTS = ('no_remainder', 'last_share', 'stale_T', 'ring2', 'late_batch', 'xt_alive', 'xt_any', 'no_xt', 'no_mt', 'mt_dead_kills',
+               'no_cut')
+SHARE_KS = (1, 14, 15, 16, 105, 119, 120, 121, 135, 240, 241)
+CUT_MS = (1, 63, 64, 65, 190, 200)
+NC_EDGES = (1, 2, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025)
+SORT_EDGES = (16383, 16384, 16385)
+
+
+def chain(*ranks):
+    """rank -> (cell, shift) of one chain: its members in rank order share the cell of the first, member s shifted by s px."""
+    assert len(ranks) <= 4 and list(ranks) == sorted(ranks)
+    return {r: (ranks[0], s) for s, r in enumerate(ranks)}
+
+
+def copies(ranks, of):
+    """rank -> (cell, shift) making ``ranks`` copies (1 px to the right) of the singles ranked ``of``."""
+    return {int(r): (int(o), 1) for r, o in zip(ranks, of)}
+
+
+def cell_expect(cell, shift, max_det):
+    """The kept ranks in closed form: cells are independent; inside a cell, in rank order, a member is kept unless a kept member of
+    the cell is at most one shift away (NMS_CHAIN_IOU: differences 0 and 1 are over the threshold, 2 and 3 are not)."""
+    held, keep = {}, []
+    for r in range(len(cell)):
+        h = held.setdefault(int(cell[r]), [])
+        if all(abs(int(shift[r]) - s) > 1 for s in h):
+            h.append(int(shift[r]))
+            keep.append(r)
+    return np.asarray(keep[:max_det], np.int64)
+
+
+def nms_scene(name, n, special=None, sort_scores=False, max_det=None, score=None):
+    """A scene of ``n`` ranks: ``special`` maps rank -> (cell, shift); every other rank is a single in the cell of its own number
+    (cells named by a special rank are therefore cells of lower ranks, or stay empty).  Scores (16000 - r) / 16384, or
+    (32767 - r) / 32768 with ``sort_scores``: multiples of 2^-14 / 2^-15 below 1, so the eight-term sums are exact and mask value =
+    score.  -> dict(name, n, cell, shift, box [n,4] float64 xyxy, score float64, iou, conf, max_det, expect = kept ranks)."""
+    cell, shift = np.arange(n), np.zeros(n, np.int64)
+    for r, (c, s) in (special or {}).items():
+        assert 0 <= r < n and 0 <= c <= r and 0 <= s <= 3, (name, r, c, s)
+        cell[r], shift[r] = c, s
+    x1, y1 = 16.0 * (cell % 128) + shift, 16.0 * (cell // 128)
+    if score is None:
+        score = (32767.0 - np.arange(n)) / 32768.0 if sort_scores else (16000.0 - np.arange(n)) / 16384.0
+        assert n < 16000 or sort_scores
+    max_det = n if max_det is None else max_det
+    return dict(name=name, n=n, cell=cell, shift=shift, box=np.stack([x1, y1, x1 + 8.0, y1 + 8.0], 1), score=np.asarray(score, np.float64),
+                iou=NMS_IOU, conf=2.0 ** -16 if sort_scores else NMS_CONF, max_det=max_det, expect=cell_expect(cell, shift, max_det))
+
+
+def _edge_chains(b, in_chunk=True):
+    """The chains around the chunk boundary b (rank b is lane 0 of a chunk); all offsets are distinct mod 64."""
+    sp = {}
+    for ch in ((b - 1, b, b + 1),             # killer in lane 63, victim lane 0 of the next chunk, the victim's copy must live
+               (b - 4, b - 3, b + 2),         # the victim dies inside its chunk (mt): its xt bit on b + 2 must not count
+               (b - 6, b + 6),                # a plain kill across the edge (xt)
+               (b - 130, b - 8, b + 8),       # the victim is dead by the kept list; its copy in the next chunk lives
+               (b - 71, b - 10, b + 10),      # the victim dies in wave 0 through xt & kept_prev; its copy in the next chunk lives
+               (b - 133, b + 12)):            # a kill through the kept list
+        sp.update(chain(*ch))
+    if in_chunk:
+        sp.update(chain(b + 20, b + 21, b + 22, b + 23))      # keep, kill, keep, kill inside one chunk
+    return sp
+
+
+def scene_chunk_edges(bounds=(192, 256, 320), max_det=None, name='chunk_edges'):
+    sp = {}
+    for b in bounds:
+        sp.update(_edge_chains(b))
+    return nms_scene(name, bounds[-1] + 128, sp, max_det=max_det)
+
+
+def scene_share(K):
+    """K singles (kept position = rank), 128 copies of rank 0 (they die, and keep the ranks behind them clear of the xt path), then one
+    copy of every single in a seeded order: each has exactly one killer, at kept position = its rank."""
+    order = np.random.default_rng(900 + K).permutation(K)
+    sp = copies(range(K, K + 128), [0] * 128)
+    sp.update(copies(range(K + 128, 2 * K + 128), order))
+    return nms_scene('share_%d' % K, 2 * K + 128, sp)
+
+
+def scene_ring(pattern='SSCSSSCCSCSSCSS'):
+    """Chunks of 64 singles (S) and of 64 copies of the first chunk (C: the whole chunk is dead by the kept list)."""
+    assert pattern[0] == 'S'
+    sp = {}
+    for c, kind in enumerate(pattern):
+        if kind == 'C':
+            sp.update(copies(range(64 * c, 64 * c + 64), range(64)))
+    return nms_scene('ring', 64 * len(pattern), sp)
+
+
+def scene_batch_edges():
+    """The cross-edge chains at the first chunks of the second and third staged batch, and in each of those chunks 16 candidates
+    that only the kept list suppresses."""
+    sp = {}
+    for i, b in enumerate((1024, 2048)):
+        sp.update(_edge_chains(b, in_chunk=False))
+        sp.update(copies(range(b + 30, b + 46), range(200 + 16 * i, 216 + 16 * i)))
+    return nms_scene('batch_edges', 2176, sp)
+
+
+def scene_nc(n):
+    """n candidates, every third one a copy of the one before it."""
+    return nms_scene('nc_%d' % n, n, copies(range(2, n, 3), range(1, n, 3)))
+
+
+def scene_sort(n):
+    return nms_scene('sort_%d' % n, n, sort_scores=True, max_det=31000)
+
+
+def scene_ties():
+    """130 candidates of ONE score: the order is the anchor order.  Rank 0 and rank 129 are singles, (1, 2), (3, 4), ... (127, 128)
+    overlapping pairs -- (63, 64) and (127, 128) across a chunk edge -- whose winner is the lower anchor."""
+    return nms_scene('ties', 130, copies(range(2, 129, 2), range(1, 128, 2)), score=np.full(130, 0.5))
+
+
+def scene_threshold(below):
+    """Two 8 x 6 boxes 2 px apart in y: IoU = 32 / 64 = 0.5 exactly.  At iou_thres 0.5 the second is kept (the test is a strict >), at
+    the next double below 0.5 it is suppressed."""
+    sc = nms_scene('thr_below' if below else 'thr_at', 2)
+    sc['box'] = np.array([[0.0, 0.0, 8.0, 6.0], [0.0, 2.0, 8.0, 8.0]])
+    sc['iou'] = float(np.nextafter(0.5, 0.0)) if below else 0.5
+    sc['expect'] = np.array([0] if below else [0, 1], np.int64)
+    return sc
+
+
+_NMS_SCENES = {}
+
+
+def nms_schedule_scenes():
+    """name -> scene, every scene whose overlap matrix the schedule model is run on (the sort scenes are singles only)."""
+    if not _NMS_SCENES:
+        sc = [scene_chunk_edges()] + [scene_share(K) for K in SHARE_KS] + [scene_ring(), scene_batch_edges()]
+        sc += [scene_chunk_edges((192, 256), M, 'cut_%d' % M) for M in CUT_MS] + [scene_nc(n) for n in NC_EDGES] + [scene_ties()]
+        _NMS_SCENES.update((s['name'], s) for s in sc)
+    return _NMS_SCENES
+
+
+def scene_perm(sc, N, seed):
+    """Anchors of the ranks: a seeded draw of n of the N anchors, ascending where all scores are equal (ties go by the anchor)."""
+    a = np.random.default_rng(seed).permutation(N)[:sc['n']]
+    return np.sort(a) if sc['n'] > 1 and sc['score'][0] == sc['score'][-1] else a
+
+
+def to_pred(sc, N, perm):
+    """float32 [1, N, 290]: rank r at anchor perm[r], obj = 1, in each class segment one column with the rank's score; the other
+    anchors keep score 0 (below conf) and an empty box."""
+    assert len(perm) == sc['n'] <= N and len(np.unique(perm)) == sc['n']
+    b = sc['box']
+    cx, cy, w, h = (b[:, 0] + b[:, 2]) / 2, (b[:, 1] + b[:, 3]) / 2, b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]
+    p = np.zeros((1, N, 290), np.float32)
+    p[0, :, 4] = 1.0
+    p[0, perm, 0], p[0, perm, 1], p[0, perm, 2], p[0, perm, 3] = cx, cy, w, h
+    p[0, perm, 5:13] = np.stack([b[:, 0], b[:, 1], b[:, 2], b[:, 1], b[:, 2], b[:, 3], b[:, 0], b[:, 3]], 1)
+    for a in SEG[:-1]:
+        p[0, perm, a + 1] = sc['score']
+    return p
+
+
+def assert_scene_geometry(sc):
+    """From float64 geometry alone: the scores are fp32 values whose eight-term fp32 sum is exact, strictly decreasing (or all equal)
+    and above conf; every pair of boxes with a common point lies in one cell and has the IoU of its shift difference; no IoU is
+    within 0.07 of the threshold.  -> the boolean overlap matrix (IoU > iou_thres) in rank order; None for a scene of more than
+    4096 singles, whose boxes are shown disjoint cell by cell instead."""
+    s, b, n = sc['score'], sc['box'], sc['n']
+    s32 = s.astype(np.float32)
+    eight = s32.copy()
+    for _ in range(7):
+        eight = eight + s32
+    assert np.array_equal(s32.astype(np.float64), s) and np.array_equal(eight / np.float32(8.0), s32), sc['name']
+    assert np.all(np.diff(s) < 0) or np.all(s == s[0]), sc['name']
+    assert float(s.min()) > sc['conf'] and np.array_equal(b.astype(np.float32).astype(np.float64), b), sc['name']
+    if n > 4096:
+        cx, cy = b[:, 0] // 16, b[:, 1] // 16
+        assert not sc['shift'].any() and len(np.unique(cy * 128 + cx)) == n, sc['name']
+        assert np.all(b[:, 2] <= 16 * cx + 16) and np.all(b[:, 3] <= 16 * cy + 16) and np.all(b[:, 2] > b[:, 0]), sc['name']
+        return None
+    w = np.maximum(0.0, np.minimum(b[:, None, 2], b[None, :, 2]) - np.maximum(b[:, None, 0], b[None, :, 0]))
+    h = np.maximum(0.0, np.minimum(b[:, None, 3], b[None, :, 3]) - np.maximum(b[:, None, 1], b[None, :, 1]))
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    inter = w * h
+    iou = inter / (area[:, None] + area[None, :] - inter)
+    if sc['name'].startswith('thr_'):
+        assert iou[0, 1] == 0.5 and inter[0, 1] == 32.0, sc['name']
+    else:
+        same = sc['cell'][:, None] == sc['cell'][None, :]
+        assert np.array_equal(inter > 0, same), sc['name']
+        want = np.asarray(NMS_CHAIN_IOU)[np.abs(sc['shift'][:, None] - sc['shift'][None, :])]
+        assert np.allclose(iou[same], want[same], rtol=0, atol=1e-15) and float(np.abs(iou - sc['iou']).min()) > 0.07, sc['name']
+    over = iou > sc['iou']
+    np.fill_diagonal(over, False)
+    return over
+
+
+def greedy_plain_np(over, max_det):
+    """The textbook greedy loop over a boolean overlap matrix in rank order -> kept ranks."""
+    sup, keep = np.zeros(len(over), bool), []
+    for i in range(len(over)):
+        if sup[i]:
+            continue
+        if len(keep) == max_det:
+            break
+        keep.append(i)
+        sup[i + 1:] |= over[i, i + 1:]
+    return np.asarray(keep, np.int64)
+
+
+def greedy_schedule_np(over, max_det, mutant=None):
+    """greedy_kernel's decomposition of the same loop, restated (see the head of this section); ``mutant`` names ONE defect of
+    NMS_MUTANTS.  The model exists to show that the scenes discriminate; the reference of the GPU tests is the C oracle."""
+    assert mutant is None or mutant in NMS_MUTANTS
+    n, NSW = len(over), 15
+    kept, T_after, dead_of = [], [], []
+    pidx, alive_prev, kept_prev = np.zeros(0, np.int64), np.zeros(0, bool), np.zeros(0, bool)
+    for c in range((n + 63) // 64):
+        idx = np.arange(64 * c, min(n, 64 * c + 64))
+        # dead: the kept list as it stood when chunk c - 1 was resolved, i.e. through chunk c - 2; wave w tests entries w, w + 15, ...
+        back = 3 if mutant == 'stale_T' else 2
+        T = T_after[c - back] if c >= back else 0
+        tested = []
+        for w in range(NSW):
+            k = w
+            while k + 7 * NSW < T:                                     # a trip of eight tests
+                tested += [k + u * NSW for u in range(8)]
+                k += 8 * NSW
+            if mutant != 'no_remainder':
+                tested += list(range(k, T, NSW))
+        if mutant == 'last_share':
+            tested = [k for k in tested if k % NSW != NSW - 1]
+        assert mutant in ('no_remainder', 'last_share') or sorted(tested) == list(range(T))
+        dead = over[np.ix_(np.asarray(kept, np.int64)[np.asarray(tested, np.int64)], idx)].any(0)
+        if mutant == 'ring2' and c >= 3:
+            dead |= dead_of[c - 3][:len(idx)]
+        # xt: the candidates of chunk c - 1 that overlap; honoured for its survivors only
+        src = {'xt_alive': alive_prev, 'xt_any': np.ones(len(pidx), bool), 'no_xt': np.zeros(len(pidx), bool)}.get(mutant, kept_prev)
+        hit = over[np.ix_(pidx[src], idx)].any(0)
+        # mt: the earlier candidates of the chunk itself
+        mt = np.triu(over[np.ix_(idx, idx)], 1)
+        if mutant == 'late_batch' and c and c % 16 == 0:
+            dead[:], hit[:], mt[:] = False, False, False
+        alive = ~dead & ~hit
+        todo, keptmask = alive.copy(), np.zeros(len(idx), bool)
+        for k in range(len(idx)):
+            if todo[k]:
+                keptmask[k] = True
+            if (todo[k] and mutant != 'no_mt') or (alive[k] and mutant == 'mt_dead_kills'):
+                todo &= ~mt[k]
+        kept += idx[keptmask].tolist()
+        T_after.append(len(kept))
+        dead_of.append(dead)
+        pidx, alive_prev, kept_prev = idx, alive, keptmask
+        if len(kept) >= max_det:
+            break
+    return np.asarray(kept if mutant == 'no_cut' else kept[:max_det], np.int64)
