@@ -591,6 +591,58 @@ int lp_best_shot_update(void* state, int n_streams, int max_tracks, int crop_h, 
                         double min_score, unsigned char* shot_crops, int32_t* shot_i, unsigned long long* shot_q, float* shot_det,
                         void* stream);
 
+/* lp_stack_update: one denoised picture per plate track.  The rectified crops a track shows are aligned to their running sum by
+ * an integer shift and summed on the device; when the track ends, the rounded mean is handed out next to its record: n crops
+ * divide the noise variance by n.  Called behind lp_best_shot_update with the same arguments (it shares the crops, status and
+ * sharp buffers); the frame table travels as kernel arguments (one launch per LP_FRAMES_PER_LAUNCH frames, one workgroup per
+ * (stream, slot), plus one closing launch): nothing is uploaded, no host sync, no allocation, capturable in a graph.  The
+ * reference has nothing here; yolov6/utils/stack.py::StackNp restates the rules below bit for bit.  All sums are integer, so the
+ * result does not depend on their order.
+ *   state: DEVICE, 16-byte aligned, lp_stack_state_bytes(n_streams, max_tracks, crop_h, crop_w) bytes, all zero = empty (the
+ *   caller zeroes it once; zeroing a stream's lp_stack_state_bytes(1, ...) bytes resets that stream).  Per stream: its own frame
+ *   counter and max_tracks entries indexed by the tracker's slot, each id + 1 (0 = empty), n, first_frame, last_frame and acc,
+ *   uint16 [crop_h,crop_w,3] (16-byte aligned): the sum of the n aligned crops.
+ *   det, count, tid, slot, crops, status, sharp, stream_of, ended_i, ended_count: as for lp_best_shot_update.
+ *   p: search 0..4, max_frames 1..255, min_score and min_width finite (|x| <= 3e38), min_sharp.
+ *   Outputs (DEVICE): stack_crops [n_streams,max_ended,crop_h,crop_w,3] uint8, stack_i [n_streams,max_ended,4] int32 = n,
+ *   first_frame, last_frame, valid.  The call first zeroes stack_i; the crop bytes of a record without a stack are left as they
+ *   were.
+ * Per stream the frames are taken in ascending b (stream_of -1: skipped):
+ *   1. rows r < min(max(count, 0), max_det, max_crops, LP_TRACK_MAX_DETS) with tid[r] >= 0 take part, in ascending r, g = slot[r]
+ *      (a row whose slot is outside 0..max_tracks-1 is skipped);
+ *   2. if entry g holds another id it is retired (5); an entry that does not hold id becomes {id + 1, n = 0};
+ *   3. the row is eligible iff status[r] == 1 (a crop cut along the box is not rectified and is never mixed in), (double)score >=
+ *      min_score with score = (c12 + ... + c19) / 8.0f summed left to right in fp32 (false for NaN), (double)(det[2] - det[0]) >=
+ *      min_width, one fp32 subtraction (false for NaN; the plate's width in frame pixels), sharp[r] >= min_sharp, and the entry's
+ *      n < max_frames;
+ *   4. align: y(p) = 29 B + 150 G + 77 R, un-rounded.  With n == 0, search == 0, crop_h <= 2 search or crop_w <= 2 search the
+ *      shift d is (0, 0).  Otherwise the candidates (dy, dx) of [-search, search]^2 are numbered k = 0.. in the order of
+ *      (dy^2 + dx^2, dy, dx) (k = 0 is (0, 0)), cost_k = the sum over i in [R, crop_h-R), j in [R, crop_w-R) of
+ *      | n * y(crop[i+dy][j+dx]) - y(acc[i][j]) | (the new crop against the running SUM, no division; every term is below 2^24,
+ *      the sum over a 1024 x 1024 crop needs 44 bits: unsigned 64-bit), and d is the candidate of the smallest (cost, k).
+ *      accumulate: acc[i][j][c] += crop[clamp(i+dy, 0, crop_h-1)][clamp(j+dx, 0, crop_w-1)][c] (an entry with n == 0 starts from
+ *      zero), n += 1, first_frame is set when n was 0, last_frame = the stream's frame counter.  255 * 255 = 65025 fits uint16:
+ *      that is why max_frames <= 255;
+ *   5. retire entry g: e = the first index < min(ended_count[s], max_ended) with ended_i[s][e][0] == the entry's id; if there is
+ *      one and n >= 1: stack_crops[s][e] = (acc + (n >> 1)) / n per channel, stack_i[s][e] = (n, first_frame, last_frame, 1).
+ *      Either way the entry becomes empty (id + 1 = 0, n = 0; an occupant whose record was cut off by max_ended is dropped
+ *      silently);
+ *   6. the stream's frame counter goes up.  After the stream's last frame (also for a stream without frames in the call) every
+ *      non-empty entry whose id is among the call's records is retired, in slot order.  Live tracks stay.
+ * What the rule does not do: the shift is an integer translation of at most `search` pixels, with no rotation, scale or
+ * sub-pixel step; every frame has the same weight; a track whose plate really changes (an occlusion) is averaged through it;
+ * min_sharp compares Laplacian energies, which are not comparable across cameras.
+ * Every argument is checked before the first launch (LP_ERR_ARG): the rules of lp_best_shot_update for the shared arguments, p and
+ * its ranges, the alignment of state and sharp, and that the state, stack_crops and stack_i overlap neither an input nor each
+ * other. */
+typedef struct lp_stack_params { double min_score, min_width; unsigned long long min_sharp; int search, max_frames; } lp_stack_params;
+size_t lp_stack_state_bytes(int n_streams, int max_tracks, int crop_h, int crop_w);   /* 0: bad arguments */
+int lp_stack_update(void* state, int n_streams, int max_tracks, int crop_h, int crop_w,
+                    const float* det, const int32_t* count, int B, int max_det, const int32_t* tid, const int32_t* slot,
+                    const unsigned char* crops, const int32_t* status, const unsigned long long* sharp, int max_crops,
+                    const int* stream_of /* HOST [B] */, const int32_t* ended_i, const int32_t* ended_count, int max_ended,
+                    const lp_stack_params* p, unsigned char* stack_crops, int32_t* stack_i, void* stream);
+
 /* lp_redact_plates_batch: make the plates of B frames unreadable IN PLACE, by a mosaic or a fill, in BGR frames or in the planes of
  * NV12 frames; at most LP_FRAMES_PER_LAUNCH frames per launch, descriptors by value in the kernel arguments: nothing is uploaded,
  * no host sync, capturable in a graph, so the call can be enqueued behind lp_rescale_round_batch.  It goes LAST: whatever reads the

@@ -7,7 +7,7 @@
                                  [--tile-frames 4] [--tile-batch 32] [--runs 3]
     python tools/frames_bench.py --tile --gate [--gate-moving K] [--gate-thres F] [--gate-refresh N] [--nv12 [bt709]] [--tile-frame 2160 3840] [--runs 3]
     python tools/frames_bench.py --tile --gate --gate-illum gain --gate-drift A [--gate-drift-period 8] [--gate-moving K] [--nv12 [bt709]] [--runs 3]
-    python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot] [--redact [--hold [--lookback D]]] [--nv12]
+    python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot [--stack]] [--redact [--hold [--lookback D]]] [--nv12]
                                  [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
 
@@ -32,6 +32,8 @@ frames/s of FrameBatcher + ``detect_frames`` alone and of ``detect_frames_padded
 of the voted rows and track ids, ``--runs`` timed runs each in the same process, alternating; the device time of the update
 from events (median of ``--reps``) next to the detect stage of the same chain, at the bench's own detection density; and the
 update alone on a full frame per stream (128 live tracks x 128 rows, every pair above the threshold: 16384 sorted keys).
+``--stack`` (with ``--best-shot``) adds lp_stack_update behind the gallery: its device time from events (median of ``--reps``) with 1, 8
+and 32 constant rectified rows per stream, every one searched over 25 candidates and summed in every call.
 ``--best-shot`` adds the best-shot stages of ``PlateTracker.update_with_shots`` to that event chain, right behind the update:
 plate crops (16 slots of 64x192 per frame), lp_crop_sharpness and lp_best_shot_update, each from events, at the bench's own
 detection density; and a worst case on 16 constant rows per stream whose sharpness is made to grow with every call, so that
@@ -111,6 +113,8 @@ def parse():
     ap.add_argument('--track', action='store_true', help='measure plate tracking (PlateTracker.update behind detect_frames) instead')
     ap.add_argument('--track-batch', type=int, default=32, help='with --track: camera streams = frames per step')
     ap.add_argument('--best-shot', action='store_true', help='with --track: also time crops + sharpness + gallery behind the update')
+    ap.add_argument('--stack', action='store_true', help='with --track --best-shot: also time lp_stack_update (PlateTracker.enable_stack) behind '
+                                                         'the gallery, at 1, 8 and 32 live tracks per stream')
     ap.add_argument('--hold', action='store_true', help='with --track --redact: also time the update with the redaction hold (enable_hold) '
                                                         'and the redaction along its rows')
     ap.add_argument('--lookback', type=int, default=0, metavar='D', help='with --track --redact --hold: also time the look-back delay of '
@@ -562,6 +566,8 @@ def track_mode(args, model, dev, tdt):
 
         if args.best_shot:
             out['best_shot'] = best_shot_stages(args, model, dev, tdt, frames, x, (H, W))
+            if args.stack:
+                out['stack'] = stack_stages(args, model, dev, frames)
         if args.redact:
             out['redact'] = redact_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
         if args.watch:
@@ -835,6 +841,41 @@ def best_shot_stages(args, model, dev, tdt, frames, x, net_hw):
     res['worst_bytes_copied_per_stream'] = 16 * 64 * 192 * 3
     state = worst._shots['state'].view(B, -1)[:, 16:].view(B, 128, -1)[:, :16, :32].contiguous().view(torch.int32)
     res['worst_shots_replaced_last_call'] = int((state[:, :, 4] == args.reps).sum())      # frame index of the shot = the last call
+    return res
+
+
+def stack_stages(args, model, dev, frames, live=(1, 8, 32)):
+    """--track --best-shot --stack: device time of lp_stack_update behind the gallery, from events on one stream, with L constant
+    rectified rows per stream (L live tracks, each searched over 25 candidates and summed in every call after the first)."""
+    import torch
+    from yolov6.hip import runtime
+    B, (h0, w0) = args.track_batch, args.frame
+    so = list(range(B))
+    res = {}
+    for L in live:
+        trk = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
+        trk.enable_best_shot((64, 192), max_crops=L)
+        trk.enable_stack()
+        rows = synthetic_quads(B, 4 * L, h0, w0, seed=2)[:, ::4].copy()       # the rows with four proper corners: status 1
+        rows[:, :, 12:20] = 0.5
+        det, count = torch.from_numpy(rows).to(dev), torch.full((B,), L, dtype=torch.int32, device=dev)
+        ms = []
+        for _ in range(args.reps + 1):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            trk.update(det, count)
+            crops, status, sharp = trk._shot_crops(frames, det, count, so, trk.max_tracks)
+            runtime.crop_sharpness(crops, status, out=sharp)
+            trk._shot_gallery(det, count, so, trk.max_tracks)
+            ev[0].record()
+            trk._stack_update(det, count, so, trk.max_tracks)
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms.append(ev[0].elapsed_time(ev[1]))
+        a = np.array(ms[1:])        # (the first call sums without a search: its entries are empty)
+        n = trk._stack['state'].view(B, -1)[:, 16:].view(B, 128, -1)[:, :, :16].contiguous().view(torch.int32)[:, :, 1]
+        res['live_%d' % L] = dict(stack_ms=dict(median=round(float(np.median(a)), 4), min=round(float(a.min()), 4), max=round(float(a.max()), 4)),
+                                  crops_summed_per_call=int((n == args.reps + 1).sum()), tracks=B * L,
+                                  sad_terms_per_call=B * L * 25 * 60 * 188, sum_bytes_per_call=B * L * 64 * 192 * 6 * 2)
     return res
 
 

@@ -4,7 +4,8 @@
     python tools/infer.py --weights weights/yololps.pt --source data/images --yaml data/dataset.yaml [--half]
                           [--batch-size 32] [--fixed-shape] [--save-crops [--crop-size 64 192]]
                           [--tile 640 640 [--tile-overlap 0.2] [--no-tile-overview] [--merge-metric iou|ios]]
-                          [--track [--track-max-age 5] [--track-iou 0.3] [--track-expand 0.5] [--best-shots [--crop-size 64 192]]]
+                          [--track [--track-max-age 5] [--track-iou 0.3] [--track-expand 0.5] [--best-shots [--crop-size 64 192]
+                           [--stack-shots [--stack-search 2] [--stack-max-frames 64] [--stack-min-width 0]]]]
                           [--nv12 bt601|bt709|bt601f|bt709f [--nv12-size W H]]
                           [--redact mosaic|fill|gauss [--redact-cell 16] [--redact-sigma 8] [--redact-margin 0.1]
                            [--redact-hold [--redact-hold-min-hits 1] [--redact-lookback D [--redact-lookback-max-back N]]]]
@@ -66,6 +67,13 @@ _FLAGS = [
     ('--track-expand', dict(type=float, default=0.5, help='boxes are grown by this fraction of their size on every side before the IoU')),
     ('--best-shots', dict(action='store_true', help='with --track: keep the sharpest rectified crop (--crop-size) of every track and write '
                                                     'shots/<line>_<id>.png and shots.txt, line-parallel to plates.txt')),
+    ('--stack-shots', dict(action='store_true', help='with --best-shots: also average the rectified crops of every track, each aligned by '
+                                                     'a small integer shift, into one denoised picture and write stacks/<line>_<id>.png and '
+                                                     'stacks.txt, line-parallel to plates.txt')),
+    ('--stack-search', dict(type=int, default=2, metavar='N', help='with --stack-shots: largest shift of the alignment in pixels (0..4)')),
+    ('--stack-max-frames', dict(type=int, default=64, metavar='N', help='with --stack-shots: crops averaged per track at most (1..255)')),
+    ('--stack-min-width', dict(type=float, default=0.0, metavar='F',
+                               help='with --stack-shots: only plates at least this wide in frame pixels are averaged')),
     ('--nv12', dict(default=None, choices=['bt601', 'bt709', 'bt601f', 'bt709f'], metavar='MATRIX',
                     help='send frames as NV12 with this matrix (bt601, bt709: limited range; bt601f, bt709f: full range): decoded images '
                          'are encoded on the host as a stand-in for a decoder; a source ending in .nv12 is a raw stream of packed frames')),
@@ -126,7 +134,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         view_img=True, classes=None, agnostic_nms=False, project=osp.join(ROOT, 'runs/inference'), name='exp',
         hide_labels=False, hide_conf=False, half=False, batch_size=1, fixed_shape=False, save_crops=False, crop_size=(64, 192),
         tile=None, tile_overlap=0.2, no_tile_overview=False, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3,
-        track_expand=0.5, best_shots=False, nv12=None, nv12_size=None, redact=None, redact_cell=16,
+        track_expand=0.5, best_shots=False, stack_shots=False, stack_search=2, stack_max_frames=64, stack_min_width=0.0, nv12=None, nv12_size=None, redact=None, redact_cell=16,
         redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1, redact_lookback=None, redact_lookback_max_back=None,
         redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None, watch_confusable=None, watch_confusable_weight=4,
         watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1, tile_gate_refresh=50,
@@ -143,7 +151,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         tile_overlap = int(tile_overlap)        # pixels
     results = Inferer(source, weights, device, yaml, img_size, half, batch_size=batch_size, auto=not fixed_shape, tile=tile,
                       tile_overlap=tile_overlap, tile_overview=not no_tile_overview, merge_metric=merge_metric, track=track, track_max_age=track_max_age,
-                      track_iou=track_iou, track_expand=track_expand, best_shots=best_shots, nv12=nv12, nv12_size=nv12_size,
+                      track_iou=track_iou, track_expand=track_expand, best_shots=best_shots, stack_shots=stack_shots, stack_search=stack_search,
+                      stack_max_frames=stack_max_frames, stack_min_width=stack_min_width, nv12=nv12, nv12_size=nv12_size,
                       redact=redact, redact_cell=redact_cell, redact_margin=redact_margin, redact_hold=redact_hold,
                       redact_hold_min_hits=redact_hold_min_hits, redact_lookback=redact_lookback,
                       redact_lookback_max_back=redact_lookback_max_back, redact_sigma=redact_sigma, watchlist=watchlist,

@@ -18,6 +18,8 @@ characters over its frames (``runtime.PlateTracker`` on a GPU, ``PlateTrackerNp`
 voted rows and writes ``tracks.txt`` (one line per frame row) and ``plates.txt`` (one line per track).
 With ``best_shots`` every track also keeps the sharpest rectified crop it has shown (``PlateTracker.update_with_shots`` on a GPU,
 ``BestShotNp`` on the CPU): ``shots/<line>_<id>.png`` and ``shots.txt``, line-parallel to ``plates.txt``.
+With ``stack_shots`` every track's rectified crops are also aligned and averaged into one denoised picture
+(``PlateTracker.enable_stack`` on a GPU, ``StackNp`` on the CPU): ``stacks/<line>_<id>.png`` and ``stacks.txt``.
 With ``nv12`` the frames travel as NV12 (``yolov6.utils.nv12``): decoded images are encoded on the host as a stand-in for a
 video decoder, ``.nv12`` sources are raw streams of packed frames; on a GPU the planes are uploaded (half the bytes of BGR) and
 read by the fused letterbox, a BGR frame exists on the device only where crops are cut; on the CPU every frame goes through
@@ -54,7 +56,8 @@ class Inferer:
                  nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1,
                  redact_lookback=None, redact_lookback_max_back=None, redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None,
                  watch_confusable=None, watch_confusable_weight=4, watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0,
-                 tile_gate_min_cells=1, tile_gate_refresh=50, tile_gate_illum='none', tile_gate_max_gain=1.5):
+                 tile_gate_min_cells=1, tile_gate_refresh=50, tile_gate_illum='none', tile_gate_max_gain=1.5, stack_shots=False,
+                 stack_search=2, stack_max_frames=64, stack_min_width=0.0):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -66,6 +69,9 @@ class Inferer:
         than ``track_max_age`` frames ends.
         ``best_shots`` (with ``track``): every track keeps the sharpest plate crop among the first ``SHOT_ROWS`` rows of its
         frames (``yolov6.utils.best_shot`` states the rules); ``infer`` writes one image per ended track that has one.
+        ``stack_shots`` (with ``best_shots``): the rectified crops of a track, at most ``stack_max_frames`` of them, each from a
+        plate at least ``stack_min_width`` frame pixels wide, are aligned by an integer shift of at most ``stack_search`` pixels and
+        averaged (``yolov6.utils.stack`` states the rule and what it does not do); ``infer`` writes one more image per ended track.
         ``nv12`` = 'bt601' | 'bt709' | 'bt601f' | 'bt709f': send every frame as NV12 with that matrix (decoded images are encoded
         with ``bgr_to_nv12_np``, an odd last row or column cut off as a decoder would never deliver one); ``nv12_size`` = (w, h)
         of the frames of ``.nv12`` sources, which need ``nv12``.
@@ -129,6 +135,11 @@ class Inferer:
             raise ValueError('redact_hold_min_hits must be >= 1')
         if best_shots and not track:
             raise ValueError('best_shots needs track=True')
+        if stack_shots:
+            from yolov6.utils.stack import check_params as check_stack
+            if not best_shots:
+                raise ValueError('stack_shots needs best_shots=True')
+            check_stack(stack_search, stack_max_frames, stack_min_width)
         if merge_metric not in ('iou', 'ios'):
             raise ValueError("merge_metric must be 'iou' or 'ios'")
         if nv12 is not None and nv12 not in MATRICES:
@@ -193,6 +204,10 @@ class Inferer:
         ``<save_dir>/shots/<k>_<id>.png`` (RGB), and ``<save_dir>/shots.txt`` has one line ``id frame row status sharpness file``
         per line of ``plates.txt``: the stream's frame index and the row the shot was cut from, the crop's status (1 corners,
         2 box) and its Laplacian energy; a track without a shot has ``id 0 0 0 0 -``.
+
+        With ``stack_shots`` the average of the aligned rectified crops of line k is written as ``<save_dir>/stacks/<k>_<id>.png``
+        (RGB), and ``<save_dir>/stacks.txt`` has one line ``id n first last file`` per line of ``plates.txt``: the crops averaged
+        and the stream's frame index of the first and the last of them; a track without a stack has ``id 0 0 0 -``.
 
         With ``watchlist`` ``<save_dir>/hits.txt`` has one line ``id first last text entry entry_text mismatches cost n_hits`` per
         ended track whose read an entry of the list accepts: the line of ``plates.txt`` up to the text, the index and text of the
@@ -464,6 +479,7 @@ class Inferer:
         else:
             self._tracker = PlateTrackerNp(1 + len(videos), **kw)
         self._track_tids, self._track_lines, self._track_ended, self._track_shots = deque(), [], [], []
+        self._track_stacks = []         # with stack_shots: (stack_i line, crop or None) of every ended record
         self._track_hits = []           # with watchlist: the match_i line of every ended record
         if self.watchlist is not None:
             from yolov6.utils import watch
@@ -494,6 +510,12 @@ class Inferer:
             else:
                 from yolov6.utils.best_shot import BestShotNp
                 self._gallery = BestShotNp(1 + len(videos), self.TRACK_SLOTS, crop_size)
+        if self.stack_shots:
+            kw = dict(search=self.stack_search, max_frames=self.stack_max_frames, min_width=self.stack_min_width)
+            if self.device.type != 'cpu':
+                self._tracker.enable_stack(**kw)
+            else:
+                self._tracker.enable_stack(crop_hw=crop_size, max_crops=self.SHOT_ROWS, **kw)
 
     def _track_collect(self, ended_i, ended_f, ended_count, shot_crops=None, shot_i=None, shot_q=None, shot_det=None):
         """Keep the ended records of one update and, with ``best_shots``, their shots (the host read of a GPU update; of the
@@ -503,6 +525,9 @@ class Inferer:
         if torch.is_tensor(shot_i):
             shot_i, shot_q = shot_i.cpu().numpy(), shot_q.cpu().numpy().view(np.uint64)
         match_i = self._tracker.last_watch          # of the same update, line-parallel to ended_i
+        stack_crops, stack_i = self._tracker.last_stack if self.stack_shots else (None, None)
+        if torch.is_tensor(stack_i):
+            stack_i = stack_i.cpu().numpy()
         if torch.is_tensor(match_i):
             match_i = match_i.cpu().numpy()
         for s, c in enumerate(ended_count.tolist()):
@@ -516,6 +541,10 @@ class Inferer:
                     crop = shot_crops[s, k] if shot_i[s, k, 3] else None
                     crop = crop.cpu().numpy() if torch.is_tensor(crop) else (None if crop is None else crop.copy())
                     self._track_shots.append((shot_i[s, k].copy(), int(shot_q[s, k]), crop))
+                if stack_i is not None:
+                    crop = stack_crops[s, k] if stack_i[s, k, 3] else None
+                    crop = crop.cpu().numpy() if torch.is_tensor(crop) else (None if crop is None else crop.copy())
+                    self._track_stacks.append((stack_i[s, k].copy(), crop))
         if self._tracker.last_live is not None:     # the alerts of the same update
             from yolov6.utils.watch_live import alerts_of
             live_i, (q_i, _, q_slot, _) = self._tracker.last_live, self._tracker.last_live_reads
@@ -544,6 +573,8 @@ class Inferer:
             det_out, tid, ended_i, ended_f, ended_count = self._tracker.update(det, count, streams, max_ended=max_ended)
             shots = self._gallery.update_from_frames(frames, det, count, tid, self._tracker.last_slot, streams, ended_i, ended_count,
                                                      self.SHOT_ROWS)
+            if self.stack_shots:
+                self._tracker.update_stack(frames, det, count, streams)
             self._track_collect(ended_i, ended_f, ended_count, *shots)
         if torch.is_tensor(det_out):
             det_out, tid = det_out.clone(), tid.clone()     # the tracker's buffers are persistent
@@ -575,6 +606,8 @@ class Inferer:
             _, tid, ended_i, ended_f, ended_count = self._tracker.flush_all()
             shots = self._gallery.update_from_frames([], np.zeros((0, 1, 28), np.float32), [], tid, self._tracker.last_slot, [], ended_i,
                                                      ended_count, self.SHOT_ROWS)
+            if self.stack_shots:
+                self._tracker.update_stack([], np.zeros((0, 1, 28), np.float32), [], [])
             self._track_collect(ended_i, ended_f, ended_count, *shots)
         os.makedirs(save_dir, exist_ok=True)
         with open(osp.join(save_dir, 'tracks.txt'), 'w') as f:
@@ -610,6 +643,16 @@ class Inferer:
                         name = osp.join('shots', '%d_%d.png' % (k, ri[0]))
                         Image.fromarray(np.ascontiguousarray(crop[:, :, ::-1])).save(osp.join(save_dir, name))
                     f.write('%d %d %d %d %d %s\n' % (ri[0], si[0], si[1], si[2], q, name))
+        if self.stack_shots:
+            from PIL import Image
+            os.makedirs(osp.join(save_dir, 'stacks'), exist_ok=True)
+            with open(osp.join(save_dir, 'stacks.txt'), 'w') as f:
+                for k, ((ri, _), (ki, crop)) in enumerate(zip(self._track_ended, self._track_stacks)):
+                    name = '-'
+                    if crop is not None:
+                        name = osp.join('stacks', '%d_%d.png' % (k, ri[0]))
+                        Image.fromarray(np.ascontiguousarray(crop[:, :, ::-1])).save(osp.join(save_dir, name))
+                    f.write('%d %d %d %d %s\n' % (ri[0], ki[0], ki[1], ki[2], name))
 
     def _frames_ahead(self, prefetch_frames, imread_bgr):
         """(frame, path) of every source in LoadData's order: image files decoded ahead on the pool, videos read in turn."""

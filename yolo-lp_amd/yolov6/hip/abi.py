@@ -116,6 +116,12 @@ class TrackHoldParams(ctypes.Structure):
     _fields_ = [('min_hits', c_int), ('max_misses', c_int)]
 
 
+class StackParams(ctypes.Structure):
+    """lp_stack_params"""
+    _fields_ = [('min_score', c_double), ('min_width', c_double), ('min_sharp', ctypes.c_ulonglong), ('search', c_int),
+                ('max_frames', c_int)]
+
+
 class ConvDesc(ctypes.Structure):
     """lp_conv_desc"""
     _fields_ = [('n_src', c_int), ('src', c_int * LP_MAX_SRC), ('dst', c_int), ('ksize', c_int), ('stride', c_int),
@@ -192,6 +198,10 @@ SYMBOLS = {
     'lp_best_shot_update': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, POINTER(c_int), c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p]),
+    'lp_stack_state_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'lp_stack_update': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_int, POINTER(c_int), c_void_p, c_void_p, c_int, POINTER(StackParams), c_void_p,
+                                c_void_p, c_void_p]),
     'lp_redact_workspace_bytes': (c_size_t, [POINTER(RedactDesc), c_int, POINTER(RedactParams)]),
     'lp_redact_plates_batch': (c_int, [POINTER(RedactDesc), c_int, c_void_p, c_void_p, c_int, POINTER(RedactParams), c_void_p, c_void_p,
                                        c_size_t, c_void_p]),

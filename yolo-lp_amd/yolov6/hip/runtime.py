@@ -1669,6 +1669,10 @@ class PlateTracker:
         self._out = {}
         self._slot = {}
         self._shots = None
+        self._stack = None
+        #: (stack_crops [S,max_ended,Hc,Wc,3] uint8, stack_i [S,max_ended,4] int32) of the last ``update_with_shots`` after
+        #: ``enable_stack``, line-parallel to its ended_i, else None
+        self.last_stack = None
         self._hold = None
         #: (det_hold, count_hold, tid_hold) of the last ``update`` after ``enable_hold``, else None
         self.last_hold = None
@@ -1685,8 +1689,11 @@ class PlateTracker:
 
     def reset(self, streams=None):
         """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0; their best-shot
-        galleries (``enable_best_shot``) are emptied with them, and their memo of ``enable_live_watch``."""
+        galleries (``enable_best_shot``) and stacks (``enable_stack``) are emptied with them, and their memo of
+        ``enable_live_watch``."""
         _zero_streams(self.state, self.n_streams, streams)
+        if self._stack is not None:
+            _zero_streams(self._stack['state'], self.n_streams, streams)
         if self._live is not None:
             _zero_streams(self._live['memo'], self.n_streams, streams)
         if self._shots is not None:
@@ -1851,6 +1858,7 @@ class PlateTracker:
         if not abs(float(min_score)) <= 3.0e38:
             raise ValueError('min_score must be finite (|min_score| <= 3e38)')
         nbytes = abi.load().lp_best_shot_state_bytes(self.n_streams, self.max_tracks, Hc, Wc)
+        self._stack = self.last_stack = None        # (a stack is made for the gallery's crop size: enable_stack again)
         self._shots = dict(crop_hw=(Hc, Wc), max_crops=int(max_crops), min_score=float(min_score), out={},
                            state=torch.zeros(nbytes, dtype=torch.uint8, device=self.device),
                            blank=torch.zeros(1, 1, 3, dtype=torch.uint8, device=self.device))
@@ -1898,7 +1906,10 @@ class PlateTracker:
         crops, status, sharp = self._shot_crops(frames, det, count, stream_of, max_ended)
         if B:
             crop_sharpness(crops, status, out=sharp)
-        return out + self._shot_gallery(det, count, stream_of, max_ended)
+        shots = self._shot_gallery(det, count, stream_of, max_ended)
+        if self._stack is not None:
+            self.last_stack = self._stack_update(det, count, stream_of, max_ended)
+        return out + shots
 
     def _shot_crops(self, frames, det, count, stream_of, max_ended):
         """The crop stage of ``update_with_shots``: (crops, status, sharp) of ``shot_buffers``, the first two written."""
@@ -1926,6 +1937,56 @@ class PlateTracker:
                                                      max_ended, sh['min_score'], _dptr(shot_crops), _dptr(shot_i), _dptr(shot_q),
                                                      _dptr(shot_det), _stream_ptr(self.device)), 'lp_best_shot_update')
         return shot_crops, shot_i, shot_q, shot_det
+
+    # ---- one denoised picture per track (lp_stack_update; yolov6/utils/stack.py states the rule and its limits) ------------------
+    def enable_stack(self, search=2, max_frames=64, min_width=0.0, min_sharp=0):
+        """From now on every ``update_with_shots`` / ``flush_all_with_shots`` also enqueues, behind the gallery on the same
+        stream, lp_stack_update on the same crops: the rectified (status 1) crops of every track, at most ``max_frames`` (1..255)
+        of them, each from a plate at least ``min_width`` frame pixels wide and of a sharpness of at least ``min_sharp``, are
+        aligned by an integer shift of at most ``search`` (0..4) pixels and summed, and the rounded mean of a track that ends is
+        left in ``last_stack`` = (stack_crops [S,max_ended,Hc,Wc,3] uint8, stack_i [S,max_ended,4] int32 = n, first_frame,
+        last_frame, valid), line-parallel to ended_i; persistent buffers per shape, the crop of a record without a stack (valid 0)
+        is left as it was.  It needs ``enable_best_shot`` first and shares its ``crop_hw``, ``max_crops`` and ``min_score``.  The
+        nine returns, the tracker's and the gallery's state are what they are without it.  Calling it again starts from empty
+        stacks; ``enable_stack(None)`` turns it off.  ``PlateTrackerNp.enable_stack`` with ``yolov6.utils.stack.StackNp`` is the
+        same computation on the CPU, bit for bit."""
+        from yolov6.utils import stack
+        self.last_stack = None
+        if search is None:
+            self._stack = None
+            return
+        if self._shots is None:
+            raise RuntimeError('call enable_best_shot() first')
+        sh = self._shots
+        search, max_frames, min_width, min_sharp, min_score = stack.check_params(search, max_frames, min_width, min_sharp, sh['min_score'])
+        nbytes = abi.load().lp_stack_state_bytes(self.n_streams, self.max_tracks, *sh['crop_hw'])
+        self._stack = dict(params=abi.StackParams(min_score, min_width, min_sharp, search, max_frames), out={},
+                           state=torch.zeros(nbytes, dtype=torch.uint8, device=self.device))
+
+    def stack_buffers(self, max_ended=None):
+        """The persistent (stack_crops [S,max_ended,Hc,Wc,3] uint8, stack_i [S,max_ended,4] int32) of an ``update_with_shots``
+        with that ``max_ended`` after ``enable_stack``."""
+        if self._stack is None:
+            raise RuntimeError('call enable_stack() first')
+        S, dev, (Hc, Wc) = self.n_streams, self.device, self._shots['crop_hw']
+        key = self.max_tracks if max_ended is None else int(max_ended)
+        return _persistent(self._stack['out'], key, lambda: (torch.zeros(S, key, Hc, Wc, 3, dtype=torch.uint8, device=dev),
+                                                             torch.empty(S, key, 4, dtype=torch.int32, device=dev)))
+
+    def _stack_update(self, det, count, stream_of, max_ended):
+        """The stack stage of ``update_with_shots`` behind the gallery stage of the same arguments: (stack_crops, stack_i)."""
+        sh, sk, S, (B, max_det) = self._shots, self._stack, self.n_streams, det.shape[:2]
+        crops, status, sharp = self.shot_buffers(B, max_ended)[:3]
+        _, tid, ended_i, _, ended_count = self.buffers(B, max_det, max_ended)
+        stack_crops, stack_i = self.stack_buffers(max_ended)
+        so, _ = _host_lists(stream_of, B)
+        with torch.cuda.device(self.device):
+            abi.check(abi.load().lp_stack_update(_dptr(sk['state']), S, self.max_tracks, sh['crop_hw'][0], sh['crop_hw'][1], _dptr(det),
+                                                 _dptr(count), B, max_det, _dptr(tid), _dptr(self.slot_buffer(B, max_det)), _dptr(crops),
+                                                 _dptr(status), _dptr(sharp), sh['max_crops'], so, _dptr(ended_i), _dptr(ended_count),
+                                                 max_ended, ctypes.byref(sk['params']), _dptr(stack_crops), _dptr(stack_i),
+                                                 _stream_ptr(self.device)), 'lp_stack_update')
+        return stack_crops, stack_i
 
     def flush_all_with_shots(self, max_det=1, max_ended=None):
         """``flush_all`` with the best shots of the tracks it ends: ``update_with_shots`` of zero frames."""

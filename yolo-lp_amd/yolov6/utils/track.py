@@ -183,6 +183,10 @@ class PlateTrackerNp:
         self._watch = None
         #: match_i [S, max_ended, 4] int32 of the last ``update`` after ``enable_watch``, line-parallel to its ended_i, else None
         self.last_watch = None
+        self._stack = None
+        #: (stack_crops, stack_i) of the last ``update_stack`` after ``enable_stack``, line-parallel to the ended records, else None
+        self.last_stack = None
+        self._last_ended = None
         self._live = None
         #: live_i [S, max_tracks, 8] int32 of the last ``update`` after ``enable_live_watch``, else None
         self.last_live = None
@@ -198,6 +202,42 @@ class PlateTrackerNp:
                 getattr(self, name)[s] = 0
         if self._live is not None:
             self._live.reset(streams)
+        if self._stack is not None:
+            self._stack['np'].reset(streams)
+
+    def enable_stack(self, search=2, max_frames=64, min_width=0.0, min_sharp=0, crop_hw=(64, 192), max_crops=16, min_score=0.0):
+        """One denoised picture per track (``yolov6.utils.stack`` states the rule and its limits): from now on ``update_stack``,
+        called right behind an ``update``, aligns and sums the rectified crops of that update's tracks and leaves (stack_crops
+        [S, max_ended, Hc, Wc, 3] uint8, stack_i [S, max_ended, 4] int32 = n, first_frame, last_frame, valid) of the tracks it
+        ended in ``last_stack``.  The first four arguments are those of ``runtime.PlateTracker.enable_stack``; ``crop_hw``,
+        ``max_crops`` and ``min_score`` are what the device tracker shares with its gallery.  Every output of ``update`` and the
+        state stay what they are.  Calling it again starts from empty stacks; ``enable_stack(None)`` turns it off."""
+        from yolov6.utils.stack import StackNp
+        self.last_stack = None
+        if search is None:
+            self._stack = None
+            return
+        if int(max_crops) < 1:
+            raise ValueError('max_crops must be >= 1')
+        self._stack = dict(max_crops=int(max_crops), out={},
+                           np=StackNp(self.n_streams, self.max_tracks, crop_hw, search, max_frames, min_score, min_width, min_sharp))
+
+    def update_stack(self, frames, det, count, stream_of=None):
+        """The stack stage behind ``update(det, count, stream_of, ...)`` of the same arguments: ``frames[b]`` uint8 [h, w, 3] BGR
+        (may be missing or None where ``stream_of`` is -1) is cut along the first ``max_crops`` rows of ``det`` as given.  Returns
+        ``last_stack``; stack_crops is persistent per ``max_ended``, the crop of a record without a stack is left as it was."""
+        if self._stack is None:
+            raise RuntimeError('call enable_stack() first')
+        if self._last_ended is None:
+            raise RuntimeError('update_stack follows an update')
+        sk, (ended_i, ended_count) = self._stack, self._last_ended
+        key = ended_i.shape[1]
+        buf = sk['out'].get(key)
+        if buf is None:
+            buf = sk['out'][key] = np.zeros((self.n_streams, key) + sk['np'].crop_hw + (3,), np.uint8)
+        self.last_stack = sk['np'].update_from_frames(frames, det, count, self.last_tid, self.last_slot, stream_of, ended_i, ended_count,
+                                                      sk['max_crops'], stack_crops=buf)
+        return self.last_stack
 
     def enable_hold(self, min_hits=1, max_misses=None):
         """From now on every ``update`` also fills ``hold_buffers`` (rule 11): the frame's rows followed by a predicted row for
@@ -422,6 +462,7 @@ class PlateTrackerNp:
             ended_count[s] = len(ended[s])
             for k, (ri, rf) in enumerate(ended[s][:max_ended]):
                 ended_i[s, k], ended_f[s, k] = ri, rf
+        self._last_ended = (ended_i, ended_count)
         if self._watch is not None:
             from yolov6.utils.watch import watch_match_np
             wl, mm, mc = self._watch
