@@ -821,6 +821,75 @@ def test_inflight_pipeline_matches_single_engine():
     assert pipe.engines[0] is eng0 and all(e.tuned == eng0.tuned and len(e.tuned) == 1 for e in pipe.engines)
 
 
+def test_tuned_choices_survive_a_rebind_and_copy_tuning(monkeypatch):
+    """What the library remembers of a tuned shape is the whole kernel choice of every op -- variant, tile and the fused forms (the
+    full-width yololps has all four: test_graph_rules_gpu.py).  ``state`` reads it back through the ABI; every assertion holds
+    whichever variants the timing prefers.  Binding another shape and the first one again, copy_tuning before and after a bind, and
+    a refused set_variant all leave the tuned state, and the prediction bits with it; an accepted set_tile forgets the bound shape
+    (both shapes are made to forget here: a shape that is not remembered runs with the choices of the shape bound before it)."""
+    import lp_testing as X
+    from yolov6.hip import runtime
+    from yolov6.utils.synth import build_synthetic
+    for name in ('LP_NO_MFMA16', 'LP_S2P16', 'LP_TUNE_CFG128', 'LP_TUNE_NBUF', 'LP_NO_STEM_S2D', 'LP_SINGLE_LANE', 'LP_LANES', 'LP_AUTOTUNE',
+                 'LP_NO_PLANAR', 'LP_NO_FUSED_STEM', 'LP_NO_FUSED_PW', 'LP_NO_FUSED_BF'):
+        monkeypatch.delenv(name, raising=False)
+    forms = (X.PIPE_P, X.FUSED_STEM2, X.FUSED_PW_S2, X.FUSED_BIFUSION)
+    A, B = (2, 128, 128), (2, 128, 192)
+    m = build_synthetic(CFG('yololps')).eval()
+    xA, xB = (torch.rand(s[0], 3, s[1], s[2], generator=torch.Generator().manual_seed(7)).cuda().half() for s in (A, B))
+    new = lambda: runtime.Engine.from_model(m, torch.float16, torch.device('cuda:0'))   # noqa: E731
+
+    def state(eng):
+        out = []
+        for i in range(eng.lib.lp_engine_num_ops(eng.h)):
+            try:
+                tile = eng.tile(i)
+            except RuntimeError:
+                tile = None
+            out.append((eng.variant(i), tile, eng.lib.lp_engine_op_carrier(eng.h, i, 1)))
+        return out
+
+    def next_tile(eng):
+        """An accepted set_tile: the next choice of the first op whose tile is its plain one (clamped, never refused)."""
+        i, (_, tile, _) = next((i, s) for i, s in enumerate(state(eng)) if s[1] is not None and s[0][0] not in forms)
+        eng.set_tile(i, tile[0] + 1)
+        assert eng.tile(i)[0] == tile[0] + 1
+
+    e1 = new()
+    assert e1.autotune
+    pA = e1.forward(xA).clone()                                  # binds, tunes, runs
+    sA = state(e1)
+    e1.forward(xB)
+    assert B in e1.tuned
+    e1.bind(*A)
+    assert state(e1) == sA and A in e1.tuned and torch.equal(e1.forward(xA), pA)
+
+    e2 = new()
+    e2.copy_tuning(e1)                                           # before any bind: applied by the bind
+    assert torch.equal(e2.forward(xA), pA) and state(e2) == sA
+    e3 = new()
+    e3.bind(*A)
+    e3.copy_tuning(e1)                                           # bound already: applied at once
+    assert state(e3) == sA
+
+    with pytest.raises(RuntimeError, match='-4'):
+        e1.set_variant(3, X.FUSED_STEM2, 3)                      # only the layer behind the stem has it
+    assert state(e1) == sA
+    e1.bind(*B)
+    e1.bind(*A)
+    assert state(e1) == sA                                       # ... and shape A is still remembered
+    e1.bind(*B)
+    next_tile(e1)                                                # forgets shape B
+    e1.bind(*A)
+    assert state(e1) == sA
+    next_tile(e1)                                                # forgets shape A
+    hand = state(e1)
+    assert hand != sA
+    e1.bind(*B)
+    e1.bind(*A)
+    assert state(e1) == hand
+
+
 def test_inflight_detections_only_pipeline_with_a_shape_change():
     """``InflightForward.submit_det`` (bench.py's default path: several batches in flight, the head writes NMS candidates, the
     NMS runs on the caller's stream): every batch gets the detections ``detect_padded`` gives it, also when the batch shape

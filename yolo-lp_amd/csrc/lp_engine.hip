@@ -28,7 +28,24 @@ struct Tensor {
     int h, w;
 };
 
-struct Op {
+// The kernel choice of one op: what lp_engine_autotune picks, lp_engine_set_op_variant / _tile force and lp_engine::tuned remembers.
+struct Choice {
+    int cfg = CFG_A, nbuf = 1, tile = 0;
+    int stream_wc = 0, stream_rd = 2;   // stream_wc != 0: the streaming 1x1 kernel (2 or 4 cout tiles per wave) runs this op
+    int rows = 0;                       // OP_HEAD_CLS: the row-writer kernel (lp_head_rows.inc) runs this op
+    int pipe = 0;                       // != 0: the pipelined 3x3 stride-1 kernel (lp_conv3x3_pipe.inc), configuration pipe - 1
+    int planar = 0;                     // stem over the space-to-depth image only: != 0: when the caller's frame has the engine's dtype, the
+                                        // PIPE_P kernel reads it directly and the input op is skipped (planar - 1 = its tile choice)
+    int fused = 0;                      // ERBlock_2[0] (op 2) only: != 0: when the caller's frame has the engine's dtype, input op, stem and this
+                                        // layer run as ONE kernel (lp_stem2_fused.inc; fused - 1 = its tile choice)
+    int fused_pw = 0;                   // 3x3 stride-2 layer behind a 1x1 layer (BiFusion's downsample(cv2(x))): != 0: the two run as ONE kernel
+                                        // (lp_pw_s2_fused.inc; fused_pw - 1 = its tile choice); the 1x1 op before it is then skipped
+    int fused_bf = 0;                   // BiFusion's cv3 (1x1 over [upsample(x0), cv1(x1), d]): != 0: transposed conv, cv1 and cv3 run as ONE kernel
+                                        // (lp_bifusion_fused.inc); the two ops it carries (Op::bf_up, bf_cv1) are then skipped
+    Choice& choice() { return *this; }  // (of an Op or a Launch, which derive from it)
+};
+
+struct Op : Choice {
     int kind = OP_CONV;
     int nsrc = 0;
     int src[LP_MAX_SRC] = {-1, -1, -1, -1};
@@ -46,32 +63,20 @@ struct Op {
     bool signal = false;     // some op on another lane waits for this one
     std::vector<float> weight, bias, proj;  // host fp32, reference layouts
     // filled by finalize
-    int cfg = CFG_A, mode = MODE_ACT, nct = 1, nchunks = 0, nphase = 1, nbuf = 1, tile = 0;
-    int stream_wc = 0, stream_rd = 2;   // stream_wc != 0: the streaming 1x1 kernel (2 or 4 cout tiles per wave) runs this op
-    int rows = 0;                       // OP_HEAD_CLS: the row-writer kernel (lp_head_rows.inc) runs this op
+    int mode = MODE_ACT, nct = 1, nchunks = 0, nphase = 1;
     size_t det_scratch = (size_t)-1;    // OP_HEAD_CLS whose detections-only form needs a prediction scratch: its arena offset (after bind)
     int box_sparse = 1;                 // OP_HEAD_BOX, detections-only forward: boxes of the level's candidates only (LP_VARIANT_BOX_SPARSE / _DENSE)
-    int pipe = 0;                       // != 0: the pipelined 3x3 stride-1 kernel (lp_conv3x3_pipe.inc), configuration pipe - 1
-    int fused_pw = 0;                   // 3x3 stride-2 layer behind a 1x1 layer (BiFusion's downsample(cv2(x))): != 0: the two run as ONE kernel
-                                        // (lp_pw_s2_fused.inc; fused_pw - 1 = its tile choice); the 1x1 op before it is then skipped
-    int fused_bf = 0;                   // BiFusion's cv3 (1x1 over [upsample(x0), cv1(x1), d]): != 0: transposed conv, cv1 and cv3 run as ONE kernel
-                                        // (lp_bifusion_fused.inc); the two ops it carries (bf_up, bf_cv1) are then skipped
-    int bf_up = -1, bf_cv1 = -1;        // ... their indices (lp_engine_finalize: bifusion_fused_possible), and on those ops: bf_carrier = the cv3 op
-    int bf_carrier = -1;
-    int fused = 0;                      // ERBlock_2[0] (op 2) only: != 0: when the caller's frame has the engine's dtype, input op, stem and this
-                                        // layer run as ONE kernel (lp_stem2_fused.inc; fused - 1 = its tile choice)
-    int planar = 0;                     // stem over the space-to-depth image only: != 0: when the caller's frame has the engine's dtype, the
-                                        // PIPE_P kernel reads it directly and the input op is skipped (planar - 1 = its tile choice)
+    int bf_up = -1, bf_cv1 = -1;        // the cv3 of a BiFusion level that can run fused (fused_bf): the two ops it then carries (lp_engine_finalize:
+    int bf_carrier = -1;                // bifusion_fused_possible), and on those ops: bf_carrier = the cv3 op
     int chunk_begin[LP_MAX_SRC + 1] = {0, 0, 0, 0, 0};
     size_t w_off = 0, b_off = 0, proj_off = 0;  // byte offsets in the packed blob
     long long w_phase_stride = 0;              // elements
 };
 
-struct Launch {
+struct Launch : Choice {       // the choice it was prepared for; the fused / planar launches overwrite `pipe` with their kernel's
     ConvArgs a;
     long long pred_off = 0;
-    int cfg = 0, mode = 0, ks = 1, st = 1, nbuf = 1;
-    int stream_wc = 0, stream_rd = 2, cb_pack = 0, rows = 0, pipe = 0;
+    int mode = 0, ks = 1, st = 1, cb_pack = 0;
     bool is_conv = false;
 };
 
@@ -134,11 +139,11 @@ struct lp_engine {
     Launch stem2_fused;               // ops[0..2] as the fused kernel (valid when ops[2].fused)
     std::map<int, Launch> pw_fused;   // op index of the 3x3 layer -> the fused 1x1 + 3x3 launch (valid when that op's fused_pw)
     std::map<int, Launch> bf_fused;   // op index of BiFusion's cv3 -> the fused launch (valid when that op's fused_bf)
-    std::map<std::vector<int>, std::vector<std::vector<int>>> tuned;  // (B,H,W) -> per-op {cfg, nbuf, tile, stream_wc, stream_rd, rows, pipe, planar, fused, fused_pw}
+    std::map<std::vector<int>, std::vector<Choice>> tuned;   // (B,H,W) -> the autotuner's choice per op (apply_tuned)
 };
 
-struct lp_engine;
 static int prepare_op(lp_engine* e, size_t idx);
+static int* op_tile_slot(lp_engine* e, int op_idx, int* bias, const Launch** L);
 static unsigned long long* g_stamps = nullptr;
 extern "C" void lpdbg_set_stamps(void* p) { g_stamps = (unsigned long long*)p; }   // debug hook (LP_STAMPS builds)
 static bool valid_tensor(const lp_engine* e, int id) { return id >= 0 && id < (int)e->tensors.size(); }
@@ -613,6 +618,14 @@ extern "C" size_t lp_engine_arena_bytes(const lp_engine* e, int B, int H, int W)
     return place(e, B, H, W, nullptr);
 }
 
+// The remembered choices of the bound shape, if it was tuned, into the ops; the caller prepares the launches.
+static bool apply_tuned(lp_engine* e) {
+    const auto it = e->tuned.find({e->B, e->H, e->W});
+    if (it == e->tuned.end()) return false;
+    for (size_t i = 0; i < e->ops.size(); ++i) e->ops[i].choice() = it->second[i];
+    return true;
+}
+
 extern "C" int lp_engine_bind(lp_engine* e, void* dev_arena, size_t bytes, int B, int H, int W) {
     if (!e || !e->finalized) return fail(LP_ERR_STATE, "lp_engine_bind: finalize first");
     const int gran = size_granule(e);
@@ -637,9 +650,7 @@ extern "C" int lp_engine_bind(lp_engine* e, void* dev_arena, size_t bytes, int B
     for (int l = 0; l < e->n_levels; ++l) e->level_off[l + 1] = e->level_off[l] + (H >> (3 + l)) * (W >> (3 + l));
     e->n_anchors = e->level_off[e->n_levels];
     if (!e->dev_w) return fail(LP_ERR_STATE, "lp_engine_bind: upload the weights first");
-    auto it = e->tuned.find({B, H, W});
-    if (it != e->tuned.end())
-        for (size_t i = 0; i < e->ops.size(); ++i) { e->ops[i].cfg = it->second[i][0]; e->ops[i].nbuf = it->second[i][1]; e->ops[i].tile = it->second[i][2]; e->ops[i].stream_wc = it->second[i][3]; e->ops[i].stream_rd = it->second[i][4]; e->ops[i].rows = it->second[i][5]; e->ops[i].pipe = it->second[i][6]; e->ops[i].planar = it->second[i][7]; e->ops[i].fused = it->second[i][8]; e->ops[i].fused_pw = it->second[i][9]; e->ops[i].fused_bf = it->second[i].size() > 10 ? it->second[i][10] : 0; }
+    apply_tuned(e);
     e->launches.assign(e->ops.size(), Launch());
     for (size_t i = 0; i < e->ops.size(); ++i) {
         int rc = prepare_op(e, i);
@@ -819,15 +830,10 @@ static int prepare_op(lp_engine* e, size_t idx) {
         }
     }
     a.stamps = g_stamps;
-    L.cfg = op.cfg;
+    L.choice() = op;
     L.mode = op.mode;
     L.ks = ks;
     L.st = stv;
-    L.nbuf = op.nbuf;
-    L.stream_wc = op.stream_wc;
-    L.stream_rd = op.stream_rd;
-    L.rows = op.rows;
-    L.pipe = op.pipe;
     L.cb_pack = cb_pack;
     if (op.planar) {                    // the same layer as the PIPE_P kernel: its own tile geometry, src[0] patched per call
         Launch& P = e->stem_planar;
@@ -1319,6 +1325,54 @@ extern "C" int lp_engine_autotune(lp_engine* e, const void* x, int x_dtype, floa
     LP_HIP_CHECK(hipEventCreate(&evp.a));
     LP_HIP_CHECK(hipEventCreate(&evp.b));
     const hipEvent_t e0 = evp.a, e1 = evp.b;
+    int trc = LP_OK;        // an event call failed: nothing more is timed, and the tuner returns "autotune: event timing failed"
+    // best of three rounds of `reps` x (the ops `seq` as prepared) between the two events; < 0: failed (trc)
+    auto time_best = [&](std::initializer_list<size_t> seq) -> float {
+        float ms_min = -1.f;
+        for (int round = 0; round < 3 && trc == LP_OK; ++round) {
+            float ms = 0.f;
+            if (hipEventRecord(e0, st) != hipSuccess) { trc = LP_ERR_HIP; break; }
+            for (int r = 0; r < reps; ++r)
+                for (size_t k : seq) run_op(e, k, x, x_dtype, pred, st);
+            if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { trc = LP_ERR_HIP; break; }
+            if (ms_min < 0.f || ms < ms_min) ms_min = ms;
+        }
+        return trc ? -1.f : ms_min;
+    };
+    // ... of op i alone, behind one warm launch of it
+    auto time_current = [&](size_t i) -> float { return run_op(e, i, x, x_dtype, pred, st) == LP_OK ? time_best({i}) : -1.f; };
+    // The tile choices 0..2 of op i's current form (op_tile_slot: where the choice lives, and the launch that holds its geometry): a choice the
+    // form does not have is skipped, and the walk ends where the prepared TH x TW repeats.  -> the fastest choice where that was strictly
+    // faster than *best, which then becomes its time; -1: none was
+    auto walk_tiles = [&](size_t i, float* best) -> int {
+        int bias = 0, won = -1, last_th = -1, last_tw = -1;
+        const Launch* L = nullptr;
+        int* const slot = op_tile_slot(e, (int)i, &bias, &L);
+        for (int tile = 0; tile < 3 && slot && trc == LP_OK; ++tile) {
+            *slot = tile + bias;
+            if (prepare_op(e, i) != LP_OK) continue;
+            if (L->a.TH == last_th && L->a.TW == last_tw) break;   // no further candidates
+            last_th = L->a.TH;
+            last_tw = L->a.TW;
+            const float ms = time_current(i);
+            if (ms >= 0.f && (*best < 0.f || ms < *best)) { *best = ms; won = tile; }
+        }
+        return won;
+    };
+    // One fused / planar form of op i (`form`: its field of the op, 0 = off, which it is here; else tile choice + 1): kept, with its fastest tile,
+    // only where that is strictly faster than t_sep, the time of the ops it replaces as tuned so far.  tiled = false: the form has one candidate.
+    auto try_form = [&](size_t i, int& form, float t_sep, bool tiled) -> int {
+        float t_form = -1.f;
+        int won = -1;
+        if (trc == LP_OK) {
+            form = 1;       // on: op_tile_slot answers for this form now
+            if (tiled) won = walk_tiles(i, &t_form);
+            else if (prepare_op(e, i) == LP_OK && (t_form = time_current(i)) >= 0.f) won = 0;
+        }
+        if (trc) return fail(trc, "autotune: event timing failed");
+        form = (won >= 0 && t_form < t_sep) ? won + 1 : 0;
+        return prepare_op(e, i);
+    };
     for (size_t i = 0; i < e->ops.size(); ++i) {
         Op& op = e->ops[i];
         if (e->launches[i].is_conv && op.kind == OP_HEAD_CLS && rows_fits(e, op) && !getenv("LP_NO_HEAD_ROWS")) {
@@ -1327,19 +1381,11 @@ extern "C" int lp_engine_autotune(lp_engine* e, const void* x, int x_dtype, floa
             int best_rows = 0;
             for (int rows = 0; rows <= 1; ++rows) {
                 op.rows = rows;
-                if (prepare_op(e, i) != LP_OK || run_op(e, i, x, x_dtype, pred, st) != LP_OK) continue;
-                float ms_min = -1.f;
-                for (int round = 0; round < 3; ++round) {
-                    LP_HIP_CHECK(hipEventRecord(e0, st));
-                    for (int r = 0; r < reps; ++r) run_op(e, i, x, x_dtype, pred, st);
-                    LP_HIP_CHECK(hipEventRecord(e1, st));
-                    LP_HIP_CHECK(hipEventSynchronize(e1));
-                    float ms = 0.f;
-                    LP_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-                    if (ms_min < 0.f || ms < ms_min) ms_min = ms;
-                }
-                if (best < 0.f || ms_min < best) { best = ms_min; best_rows = rows; }
+                if (prepare_op(e, i) != LP_OK) continue;
+                const float ms = time_current(i);
+                if (ms >= 0.f && (best < 0.f || ms < best)) { best = ms; best_rows = rows; }
             }
+            if (trc) return fail(trc, "autotune: event timing failed");
             op.rows = best_rows;
             rc = prepare_op(e, i);
             if (rc) return rc;
@@ -1349,38 +1395,16 @@ extern "C" int lp_engine_autotune(lp_engine* e, const void* x, int x_dtype, floa
         const int cb = conv_shape(e->dtype, op.cfg, 1, 1).CB;
         int best_cfg = op.cfg, best_nb = op.nbuf, best_tile = op.tile, best_wc = 0, best_rd = 2, best_pipe = 0;
         float best_ms = -1.f;
-        int trc = LP_OK;
-        auto time_current = [&]() -> float {   // best of three rounds of `reps` launches of the op as prepared; < 0: failed
-            if (run_op(e, i, x, x_dtype, pred, st) != LP_OK) return -1.f;   // warm
-            float ms_min = -1.f;
-            for (int round = 0; round < 3; ++round) {
-                if (hipEventRecord(e0, st) != hipSuccess) { trc = LP_ERR_HIP; return -1.f; }
-                for (int r = 0; r < reps; ++r) run_op(e, i, x, x_dtype, pred, st);
-                float ms = 0.f;
-                if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                    hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { trc = LP_ERR_HIP; return -1.f; }
-                if (ms_min < 0.f || ms < ms_min) ms_min = ms;
-            }
-            return ms_min;
-        };
         op.stream_wc = 0;
         op.pipe = 0;
         const bool fam16 = op_fam16(e, op);       // only the 16x16x32 variants are candidates then (another fp32 summation order)
         for (int cfg = 0; cfg < CFG_COUNT && !fam16; ++cfg) {
             if (conv_shape(e->dtype, cfg, 1, 1).CB != cb) continue;
             for (int nb = 1; nb <= (cfg == CFG_C ? 1 : 2); ++nb) {
-                int last_th = -1, last_tw = -1;
-                for (int tile = 0; tile < 3; ++tile) {
-                    op.cfg = cfg;
-                    op.nbuf = nb;
-                    op.tile = tile;
-                    if (prepare_op(e, i) != LP_OK) continue;
-                    if (e->launches[i].a.TH == last_th && e->launches[i].a.TW == last_tw) break;   // no further candidates
-                    last_th = e->launches[i].a.TH;
-                    last_tw = e->launches[i].a.TW;
-                    const float ms = time_current();
-                    if (ms >= 0.f && (best_ms < 0.f || ms < best_ms)) { best_ms = ms; best_cfg = cfg; best_nb = nb; best_tile = tile; }
-                }
+                op.cfg = cfg;
+                op.nbuf = nb;
+                const int tile = walk_tiles(i, &best_ms);
+                if (tile >= 0) { best_cfg = cfg; best_nb = nb; best_tile = tile; }
             }
         }
         // 1x1 stride-1 layers: the streaming kernel reads the same packing
@@ -1392,7 +1416,7 @@ extern "C" int lp_engine_autotune(lp_engine* e, const void* x, int x_dtype, floa
                     op.stream_wc = wc;
                     op.stream_rd = rd;
                     if (prepare_op(e, i) != LP_OK) continue;
-                    const float ms = time_current();
+                    const float ms = time_current(i);
                     if (ms >= 0.f && (best_ms < 0.f || ms < best_ms)) { best_ms = ms; best_wc = wc; best_rd = rd; }
                 }
             }
@@ -1404,17 +1428,9 @@ extern "C" int lp_engine_autotune(lp_engine* e, const void* x, int x_dtype, floa
             for (int pc = fam16 ? PIPE16_D : 0; pc < (fam16 ? PIPE_S2_END : PIPE_COUNT); ++pc) {
                 if (fam16 && !pipe_is_16(pc)) continue;
                 if (!conv_pipe_fits(e->dtype, pc, cb, op.ksize, op.stride, op.mode, op.nct, op.nphase, op.nchunks)) continue;
-                int last_th = -1, last_tw = -1;
-                for (int tile = 0; tile < 3; ++tile) {
-                    op.pipe = pc + 1;
-                    op.tile = tile;
-                    if (prepare_op(e, i) != LP_OK) continue;
-                    if (e->launches[i].a.TH == last_th && e->launches[i].a.TW == last_tw) break;
-                    last_th = e->launches[i].a.TH;
-                    last_tw = e->launches[i].a.TW;
-                    const float ms = time_current();
-                    if (ms >= 0.f && (best_ms < 0.f || ms < best_ms)) { best_ms = ms; best_pipe = pc + 1; pipe_tile = tile; }
-                }
+                op.pipe = pc + 1;
+                const int tile = walk_tiles(i, &best_ms);
+                if (tile >= 0) { best_pipe = pc + 1; pipe_tile = tile; }
             }
             op.pipe = 0;
             if (fam16 && !best_pipe) best_pipe = fam16_default_pipe(e, op);
@@ -1433,127 +1449,27 @@ extern "C" int lp_engine_autotune(lp_engine* e, const void* x, int x_dtype, floa
         if (rc) return rc;
         // the stem may read the caller's frame itself and make the input op unnecessary: worth it if it beats the two together
         if (i == 1 && stem_planar_possible(e) && frame_direct(e, x, x_dtype) && !getenv("LP_NO_PLANAR")) {
-            float t_in = -1.f;
-            for (int round = 0; round < 3 && trc == LP_OK; ++round) {
-                float ms = 0.f;
-                if (hipEventRecord(e0, st) != hipSuccess) { trc = LP_ERR_HIP; break; }
-                for (int r = 0; r < reps; ++r) run_op(e, 0, x, x_dtype, pred, st);
-                if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { trc = LP_ERR_HIP; break; }
-                if (t_in < 0.f || ms < t_in) t_in = ms;
-            }
-            int best_planar = 0, last_th = -1, last_tw = -1;
-            float best_pl = -1.f;
-            for (int tile = 0; tile < 3 && trc == LP_OK && t_in >= 0.f; ++tile) {
-                op.planar = tile + 1;
-                if (prepare_op(e, i) != LP_OK) continue;
-                if (e->stem_planar.a.TH == last_th && e->stem_planar.a.TW == last_tw) break;
-                last_th = e->stem_planar.a.TH;
-                last_tw = e->stem_planar.a.TW;
-                const float ms = time_current();
-                if (ms >= 0.f && (best_pl < 0.f || ms < best_pl)) { best_pl = ms; best_planar = tile + 1; }
-            }
-            if (trc) return fail(trc, "autotune: event timing failed");
-            op.planar = (best_planar && best_pl < best_ms + t_in) ? best_planar : 0;
-            rc = prepare_op(e, i);
+            const float t_in = time_best({0});
+            rc = try_form(i, op.planar, best_ms + t_in, true);
             if (rc) return rc;
         }
         // ... or run as one kernel with the layer behind it: against the three ops as tuned so far
         if (i == 2 && stem2_fused_possible(e) && frame_direct(e, x, x_dtype) && !getenv("LP_NO_PLANAR") && !getenv("LP_NO_FUSED_STEM")) {
-            auto time_ops = [&](size_t first, size_t last) -> float {     // best of three rounds of `reps` x (ops first..last)
-                float ms_min = -1.f;
-                for (int round = 0; round < 3 && trc == LP_OK; ++round) {
-                    float ms = 0.f;
-                    if (hipEventRecord(e0, st) != hipSuccess) { trc = LP_ERR_HIP; break; }
-                    for (int r = 0; r < reps; ++r)
-                        for (size_t k = first; k <= last; ++k) run_op(e, k, x, x_dtype, pred, st);
-                    if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { trc = LP_ERR_HIP; break; }
-                    if (ms_min < 0.f || ms < ms_min) ms_min = ms;
-                }
-                return ms_min;
-            };
-            op.fused = 0;
-            const float t_sep = time_ops(0, 2);
-            int best_f = 0, last_th = -1, last_tw = -1;
-            float best_fms = -1.f;
-            for (int tile = 0; tile < 3 && trc == LP_OK && t_sep >= 0.f; ++tile) {
-                op.fused = tile + 1;
-                if (prepare_op(e, i) != LP_OK) continue;
-                if (e->stem2_fused.a.TH == last_th && e->stem2_fused.a.TW == last_tw) break;
-                last_th = e->stem2_fused.a.TH;
-                last_tw = e->stem2_fused.a.TW;
-                if (run_op(e, 2, x, x_dtype, pred, st) != LP_OK) continue;
-                const float ms = time_ops(2, 2);
-                if (ms >= 0.f && (best_fms < 0.f || ms < best_fms)) { best_fms = ms; best_f = tile + 1; }
-            }
-            if (trc) return fail(trc, "autotune: event timing failed");
-            op.fused = (best_f && best_fms < t_sep) ? best_f : 0;
-            rc = prepare_op(e, i);
+            rc = try_form(i, op.fused, time_best({0, 1, 2}), true);
             if (rc) return rc;
         }
         // a 1x1 layer + this 3x3 stride-2 layer as one kernel: against the two ops as tuned
         if (pw_fused_possible(e, i) && !getenv("LP_NO_FUSED_PW")) {
-            auto time_pair = [&](size_t first) -> float {
-                float ms_min = -1.f;
-                for (int round = 0; round < 3 && trc == LP_OK; ++round) {
-                    float ms = 0.f;
-                    if (hipEventRecord(e0, st) != hipSuccess) { trc = LP_ERR_HIP; break; }
-                    for (int r = 0; r < reps; ++r)
-                        for (size_t k = first; k <= i; ++k) run_op(e, k, x, x_dtype, pred, st);
-                    if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { trc = LP_ERR_HIP; break; }
-                    if (ms_min < 0.f || ms < ms_min) ms_min = ms;
-                }
-                return ms_min;
-            };
-            op.fused_pw = 0;
-            const float t_sep = time_pair(i - 1);
-            int best_f = 0, last_th = -1, last_tw = -1;
-            float best_fms = -1.f;
-            for (int tile = 0; tile < 3 && trc == LP_OK && t_sep >= 0.f; ++tile) {
-                op.fused_pw = tile + 1;
-                if (prepare_op(e, i) != LP_OK) continue;
-                const ConvArgs& fa = e->pw_fused[(int)i].a;
-                if (fa.TH == last_th && fa.TW == last_tw) break;
-                last_th = fa.TH;
-                last_tw = fa.TW;
-                if (run_op(e, i, x, x_dtype, pred, st) != LP_OK) continue;
-                const float ms = time_pair(i);
-                if (ms >= 0.f && (best_fms < 0.f || ms < best_fms)) { best_fms = ms; best_f = tile + 1; }
-            }
-            if (trc) return fail(trc, "autotune: event timing failed");
-            op.fused_pw = (best_f && best_fms < t_sep) ? best_f : 0;
-            rc = prepare_op(e, i);
+            rc = try_form(i, op.fused_pw, time_best({i - 1, i}), true);
             if (rc) return rc;
         }
         // BiFusion's transposed conv + cv1 + this cv3 as one kernel: against the three ops as tuned
         if (op.bf_up >= 0 && !getenv("LP_NO_FUSED_BF")) {
-            auto time_set = [&](bool fused_form) -> float {
-                float ms_min = -1.f;
-                for (int round = 0; round < 3 && trc == LP_OK; ++round) {
-                    float ms = 0.f;
-                    if (hipEventRecord(e0, st) != hipSuccess) { trc = LP_ERR_HIP; break; }
-                    for (int r = 0; r < reps; ++r) {
-                        if (!fused_form) { run_op(e, (size_t)op.bf_up, x, x_dtype, pred, st); run_op(e, (size_t)op.bf_cv1, x, x_dtype, pred, st); }
-                        run_op(e, i, x, x_dtype, pred, st);
-                    }
-                    if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { trc = LP_ERR_HIP; break; }
-                    if (ms_min < 0.f || ms < ms_min) ms_min = ms;
-                }
-                return ms_min;
-            };
-            op.fused_bf = 0;
-            const float t_sep = time_set(false);
-            op.fused_bf = 1;
-            float t_fused = -1.f;
-            if (prepare_op(e, i) == LP_OK && run_op(e, i, x, x_dtype, pred, st) == LP_OK) t_fused = time_set(true);
-            if (trc) return fail(trc, "autotune: event timing failed");
-            op.fused_bf = (t_sep >= 0.f && t_fused >= 0.f && t_fused < t_sep) ? 1 : 0;
-            rc = prepare_op(e, i);
+            rc = try_form(i, op.fused_bf, time_best({(size_t)op.bf_up, (size_t)op.bf_cv1, i}), false);
             if (rc) return rc;
         }
     }
-    std::vector<std::vector<int>> choice;
-    for (const Op& op : e->ops) choice.push_back({op.cfg, op.nbuf, op.tile, op.stream_wc, op.stream_rd, op.rows, op.pipe, op.planar, op.fused, op.fused_pw, op.fused_bf});
-    e->tuned[{e->B, e->H, e->W}] = choice;
+    e->tuned[{e->B, e->H, e->W}].assign(e->ops.begin(), e->ops.end());      // (the Choice part of every op)
     return LP_OK;
 }
 
@@ -1566,17 +1482,11 @@ extern "C" int lp_engine_copy_tuning(lp_engine* dst, const lp_engine* src) {
             return fail(LP_ERR_ARG, "lp_engine_copy_tuning: engines were built from different graphs");
     }
     dst->tuned = src->tuned;      // applied by lp_engine_bind for the shapes it contains
-    if (dst->arena) {
-        auto it = dst->tuned.find({dst->B, dst->H, dst->W});
-        if (it != dst->tuned.end())
-            for (size_t i = 0; i < dst->ops.size(); ++i) {
-                Op& op = dst->ops[i];
-                op.cfg = it->second[i][0]; op.nbuf = it->second[i][1]; op.tile = it->second[i][2];
-                op.stream_wc = it->second[i][3]; op.stream_rd = it->second[i][4]; op.rows = it->second[i][5]; op.pipe = it->second[i][6]; op.planar = it->second[i][7]; op.fused = it->second[i][8]; op.fused_pw = it->second[i][9]; op.fused_bf = it->second[i].size() > 10 ? it->second[i][10] : 0;
-                int rc = prepare_op(dst, i);
-                if (rc) return rc;
-            }
-    }
+    if (dst->arena && apply_tuned(dst))
+        for (size_t i = 0; i < dst->ops.size(); ++i) {
+            int rc = prepare_op(dst, i);
+            if (rc) return rc;
+        }
     return LP_OK;
 }
 
@@ -1603,13 +1513,12 @@ extern "C" int lp_engine_set_op_variant(lp_engine* e, int op_idx, int cfg, int n
     // Validate first, mutate after: a refused request (LP_ERR_UNSUPPORTED) leaves the op, its fused / planar forms, the remembered
     // tuning and the prepared launches as they were.  A fused form switches off the forms listed before it below; any other
     // variant switches all four off.
-    const int before[9] = {op.cfg, op.nbuf, op.stream_wc, op.stream_rd, op.pipe, op.planar, op.fused, op.fused_pw, op.fused_bf};
+    const Choice before = op;
     auto commit = [&]() -> int {
         if (e->arena && op_idx < (int)e->launches.size()) {
             const int rc = prepare_op(e, (size_t)op_idx);
             if (rc) {       // (a fused / planar form without a tile for the bound shape)
-                op.cfg = before[0]; op.nbuf = before[1]; op.stream_wc = before[2]; op.stream_rd = before[3]; op.pipe = before[4];
-                op.planar = before[5]; op.fused = before[6]; op.fused_pw = before[7]; op.fused_bf = before[8];
+                op.choice() = before;      // (tile and rows as well: nothing since the snapshot changes them)
                 const std::string why = g_err;
                 prepare_op(e, (size_t)op_idx);
                 return fail(rc, why);
@@ -1691,12 +1600,12 @@ extern "C" int lp_engine_set_op_tile(lp_engine* e, int op_idx, int choice) {
     const Launch* L = nullptr;
     int* slot = op_tile_slot(e, op_idx, &bias, &L);
     if (!slot) return fail(LP_ERR_UNSUPPORTED, "lp_engine_set_op_tile: the op's kernel has no output tiles");
-    const int before = *slot;
+    const Choice before = e->ops[op_idx];
     *slot = choice + bias;
     e->tuned.erase({e->B, e->H, e->W});
     if (e->arena && op_idx < (int)e->launches.size()) {
         const int rc = prepare_op(e, (size_t)op_idx);
-        if (rc) { *slot = before; prepare_op(e, (size_t)op_idx); }      // (the fused / planar forms have a finite list of tiles)
+        if (rc) { e->ops[op_idx].choice() = before; prepare_op(e, (size_t)op_idx); }      // (the fused / planar forms have a finite list of tiles)
         return rc;
     }
     return LP_OK;
