@@ -894,6 +894,63 @@ int lp_watch_live(const void* track_state, int n_streams, int max_tracks, const 
                   int max_mismatch, int max_cost, int32_t* q_i, float* q_f, int32_t* q_slot, int32_t* q_count, int32_t* live_i,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* lp_sight_update: a device-resident log of sightings.  Every read that ends in a tracker call is matched against the recent reads
+ * of all streams -- the car the exit camera reads now is the car the entry camera read 40 minutes ago; a plate hidden for longer than
+ * max_age comes back as a new track of the vehicle whose track has just ended -- and is then appended to the ring the call has just
+ * scanned.  Called behind lp_track_update (any of its forms; behind lp_watch_match / lp_watch_live if they run too) on the same stream;
+ * all pointers are DEVICE pointers; nothing is uploaded or read back, nothing is allocated, capturable in a graph.  The reference has
+ * nothing here; yolov6/utils/sight.py::sight_update_np restates the rules below on every int32 of sight_i and of the log.
+ *   state: int32 [1 + capacity,8], 16-byte aligned, lp_sight_state_bytes(capacity) bytes, 1 <= capacity <= LP_SIGHT_MAX_CAPACITY; all
+ *   zero = empty (the caller zeroes it once, and again to clear the log).  Row 0 is the header (total, 0, 0, 0, 0, 0, 0, 0), total = the
+ *   reads appended since the last clear (the caller keeps it below 2^31); row 1 + slot holds w0, w1 = the eight ids as bytes (position p
+ *   in byte p & 3 of word p >> 2), w2, w3 = the eight position weights minus 1 as bytes, w4 = stream, w5 = track id, w6 = stamp, w7 =
+ *   seq = the value of total when the read was appended.  Append number t lives in slot t % capacity; fill = min(total, capacity).
+ *   confuse: as lp_watch_match (uint8 [3,64,64] sixteenths, 4-byte aligned, or NULL for 16 everywhere).
+ *   pair: uint8 [n_streams,n_streams] or NULL: pair[s_read][s_entry] != 0 means that entries logged from stream s_entry are candidates
+ *   for the reads of stream s_read (NULL: every pair, the same stream included; with a pair, a stored stream outside 0..n_streams-1 is
+ *   allowed nowhere).
+ *   ended_i, ended_f [n_streams,max_ended,12], ended_count [n_streams]: as lp_track_update left them, exactly as lp_watch_match takes them.
+ *   now: int32 [1] on the DEVICE, 4-byte aligned, >= 0: the caller's clock (seconds, a frame or call number; the log does not interpret
+ *   it), so that the call can sit in a captured graph while the caller bumps the value in place.  window >= 0, min_hits >= 1.
+ *   1. A read is a line j < min(max(ended_count[s], 0), max_ended) whose hits (ended_i[s][j][3]) are >= min_hits; other lines are neither
+ *      looked up nor appended, and their row of sight_i is the empty row.
+ *   2. Every read is matched against the log as it stood before the call (the reads of one call do not see each other).  Per position p:
+ *      q_r = rule 1 of lp_watch_match on share[p], q_e = the stored weight; id_r = best[p] if 0 <= best[p] < 64, else "matches nothing";
+ *      equal ids in 0..63 cost 0; anything else is one mismatch of cost min(q_r, q_e) * c, c = confuse[g(p)][id_r][id_e] when both ids are
+ *      in 0..63, else 16 (symmetric in the two uncertainties: both sides are voted reads; there are no wildcards).
+ *   3. An entry is accepted iff its slot is filled, pair allows it, 0 <= now - stamp <= window (the difference in 64 bits), mism <=
+ *      max_mismatch and cost <= max_cost.  Among the accepted entries the winner has the smallest (cost, age rank), age rank = total - 1 -
+ *      seq: 0 is the newest.
+ *   4. sight_i: int32 [n_streams,max_ended,8], 16-byte aligned, line-parallel to ended_i: (slot, mismatches, cost, n_hits, prev_stream,
+ *      prev_id, prev_stamp, prev_seq), n_hits = the number of accepted entries; the empty row is (-1, 0, 0, 0, -1, -1, 0, 0).  The prev_*
+ *      words are copied out because the winning slot may be overwritten by this same call's appends.  Every line is written by every call.
+ *   5. After all matching, read k of the call, in (stream, line) order over the reads, is append number total + k with stamp now: a stored
+ *      id is best[p] if it is in 0..63, else 254; a stored weight is q_r - 1; the track id is ended_i[s][j][0].  Of V > capacity reads only
+ *      the last capacity are written.  total grows by V.
+ * All reductions are an unsigned minimum or an integer sum: the result does not depend on the order of the workgroups.
+ * Four launches: a one-workgroup kernel numbers the reads (a prefix sum), clears their keys and copies total into the workspace; the scan,
+ * one workgroup per LP_SIGHT_BLOCK_ENTRIES slots, holds its slots in LDS (the log is read from memory once per call) and walks the reads in
+ * blocks of LP_SIGHT_QUERY_BLOCK through an LDS table (position, stored id, read) -> confusion weight, then one atomic minimum of
+ * cost << 32 | age rank << 4 | mismatches and one atomic add per workgroup and read with a hit; a tail kernel writes sight_i from the old
+ * rows; only then an append kernel writes the new slots (plain vector stores) and total.  max_ended == 0 launches nothing.
+ *   workspace: 16-byte aligned, lp_sight_workspace_bytes(n_streams, max_ended) bytes; it may hold anything on entry.
+ * What it does not do: no insertions or deletions (the reads stay positional); one best earlier sighting plus a count, not a chain; now
+ * must not run backwards (entries stamped after now simply do not match); fewer than 2^31 appends between clears; the log is not a part
+ * of the tracker's state (it survives a reset of the tracker, where track ids restart: prev_seq, not prev_id, names a sighting).
+ * Every argument is checked before the first launch (LP_ERR_ARG, nothing launched): capacity outside 1..LP_SIGHT_MAX_CAPACITY,
+ * n_streams < 1, max_ended < 0, n_streams * max_ended * 12 at or above 2^31, window < 0, min_hits < 1, max_mismatch outside 0..8, max_cost
+ * outside 0..LP_WATCH_MAX_COST; with max_ended > 0: a null pointer (confuse and pair may be NULL), the five alignments, a workspace that is
+ * too small; the log, sight_i or the workspace overlapping an input or each other. */
+#define LP_SIGHT_MAX_CAPACITY (1 << 24)
+#define LP_SIGHT_BLOCK_ENTRIES 1024   /* slots per workgroup of the scan: 256 lanes x 4 */
+#define LP_SIGHT_QUERY_BLOCK 16       /* reads per LDS table */
+size_t lp_sight_state_bytes(int capacity);                          /* 0: bad arguments */
+size_t lp_sight_workspace_bytes(int n_streams, int max_ended);      /* 0: bad arguments */
+int lp_sight_update(int32_t* state, int capacity, const unsigned char* confuse /* NULL: all 16 */, const unsigned char* pair /* NULL: all */,
+                    const int32_t* ended_i, const float* ended_f, const int32_t* ended_count, int n_streams, int max_ended,
+                    const int32_t* now /* DEVICE [1] */, int window, int min_hits, int max_mismatch, int max_cost, int32_t* sight_i,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* lp_tile_gate_luma_batch / lp_tile_gate_update: skip the unchanged tiles of fixed-camera frames in tiled detection.  On a fixed
  * camera nearly every tile of a frame shows the pixels of the frame before, and a tile that has not changed yields the same
  * detections again; these two calls find, per (stream, tile), whether the tile changed against the frame its cached detections were

@@ -8,7 +8,7 @@
     python tools/frames_bench.py --tile --gate [--gate-moving K] [--gate-thres F] [--gate-refresh N] [--nv12 [bt709]] [--tile-frame 2160 3840] [--runs 3]
     python tools/frames_bench.py --tile --gate --gate-illum gain --gate-drift A [--gate-drift-period 8] [--gate-moving K] [--nv12 [bt709]] [--runs 3]
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot [--stack]] [--redact [--hold [--lookback D]]] [--nv12]
-                                 [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]]
+                                 [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]] [--sightings C]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
@@ -122,6 +122,9 @@ def parse():
     ap.add_argument('--watch', type=int, default=0, metavar='N', help='with --track: also time the lookup of the ended reads in a seeded '
                                                                       'random watchlist of N entries (lp_watch_match); every stream is '
                                                                       'flushed once per step so that there are reads')
+    ap.add_argument('--sightings', type=int, default=0, metavar='C', help='with --track: also time the update of a full, seeded log of '
+                                                                          'sightings of C slots on the ended reads (lp_sight_update), '
+                                                                          'and lp_watch_match on a list of C entries and the same reads')
     ap.add_argument('--watch-mismatch', type=int, default=1, help='with --watch: positions that may differ')
     ap.add_argument('--watch-live', action='store_true', help='with --watch: also time the lookup of the live tracks (lp_watch_live), on a '
                                                               'step with fresh reads and on one without')
@@ -574,6 +577,8 @@ def track_mode(args, model, dev, tdt):
             out['watch'] = watch_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
             if args.watch_live:
                 out['watch_live'] = watch_live_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
+        if args.sightings:
+            out['sightings'] = sight_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
 
         # the full case: 128 live tracks x 128 rows per stream, every pair above the threshold
         full = runtime.PlateTracker(B, max_tracks=128, max_age=0, ncls=model, device=dev)
@@ -640,6 +645,69 @@ def watch_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
     return dict(entries=N, max_mismatch=args.watch_mismatch, reps=args.reps, watch_ms=round(med, 4), reads_per_step=round(nreads, 1),
                 pairs_per_s=round(N * nreads / (med * 1e-3), 1), block_reads=QB, block_ms=round(bmed, 4),
                 block_pairs_per_s=round(N * QB / (bmed * 1e-3), 1), block_list_bytes_per_s=round(N * 8 / (bmed * 1e-3), 1))
+
+
+def sight_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
+    """--track --sightings C: device time of lp_sight_update behind the update, from events on one stream, on a log of C slots that
+    is full of seeded random reads (ids within the model's head widths, every slot inside the window: the scan's worst case), and of
+    lp_watch_match on a seeded list of C entries with the same reads and limits, as the reference point.  Every step flushes every
+    stream, so the tracks the step began end in it (``reads_per_step``).  ``block_ms`` / ``watch_block_ms``: the two calls on exactly
+    one query block of synthetic reads."""
+    import torch
+    from yolov6.hip import abi, runtime
+    from yolov6.utils.track import ncls_of
+    size, stride = [args.size, args.size], int(model.stride.max())
+    B, conf, iou, max_det = args.track_batch, args.conf, args.iou, args.max_det
+    N, QB, mm = args.sightings, abi.LP_SIGHT_QUERY_BLOCK, args.watch_mismatch
+    rng = np.random.default_rng(1)
+    ncls = ncls_of(model)
+    ids = np.stack([rng.integers(0, n, N, dtype=np.uint8) for n in ncls], 1)
+    wl = runtime.Watchlist(ids, device=dev)
+    rows = np.zeros((1 + N, 8), np.int32)
+    rows[0, 0] = N
+    rows[1:, 0:2] = ids.view(np.int32)
+    rows[1:, 2:4] = rng.integers(0, 256, (N, 8), dtype=np.uint8).view(np.int32)
+    rows[1:, 4], rows[1:, 5], rows[1:, 7] = rng.integers(0, B, N), np.arange(N) % 1000, np.arange(N)
+    logs = [runtime.SightLog(N, n_streams, device=dev) for n_streams in (B, 1)]
+    for log in logs:
+        log.state.copy_(torch.from_numpy(rows))
+    trk = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
+    bi, bf = np.zeros((1, QB, 12), np.int32), np.zeros((1, QB, 12), np.float32)
+    bi[0, :, 3], bi[0, :, 4:], bf[0, :, :8] = 1, np.stack([rng.integers(0, n, QB) for n in ncls], 1), rng.random((QB, 8))
+    block = [torch.from_numpy(a).to(dev) for a in (bi, bf, np.array([QB], np.int32))]
+    now = torch.ones(1, dtype=torch.int32, device=dev)
+    times, reads = dict(sight=[], watch=[], sight_block=[], watch_block=[]), []
+    for k in range(args.reps + 2):
+        frames = batcher.put([pool[(j + k) % len(pool)] for j in range(B)])
+        xx, _ = runtime.preprocess_frames(frames, size, stride, tdt, batch=B, out=x)
+        det, count, _ = runtime.detect_padded(model, xx, conf, iou, max_det)
+        runtime.rescale_round_batch(det, count, net_hw, [f.shape for f in frames])
+        ended = trk.update(det, count, flush=[1] * B)[2:]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(8)]
+        ev[0].record()
+        logs[0].update(*ended, now, window=1 << 30, max_mismatch=mm)
+        ev[1].record()
+        ev[2].record()
+        wl.match(*ended, mm)
+        ev[3].record()
+        ev[4].record()
+        logs[1].update(*block, now, window=1 << 30, max_mismatch=mm)
+        ev[5].record()
+        ev[6].record()
+        wl.match(*block, mm)
+        ev[7].record()
+        torch.cuda.synchronize()
+        if k >= 2:
+            for j, name in enumerate(('sight', 'watch', 'sight_block', 'watch_block')):
+                times[name].append(ev[2 * j].elapsed_time(ev[2 * j + 1]))
+            reads.append(int(ended[2].clamp(0, ended[0].shape[1]).sum()))
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    nreads = float(np.mean(reads))
+    return dict(capacity=N, max_mismatch=mm, reps=args.reps, sight_ms=round(med['sight'], 4), reads_per_step=round(nreads, 1),
+                watch_ms=round(med['watch'], 4), sight_over_watch=round(med['sight'] / med['watch'], 3),
+                pairs_per_s=round(N * nreads / (med['sight'] * 1e-3), 1), block_reads=QB, block_ms=round(med['sight_block'], 4),
+                watch_block_ms=round(med['watch_block'], 4), block_over_watch_block=round(med['sight_block'] / med['watch_block'], 3),
+                block_log_bytes_per_s=round(N * 32 / (med['sight_block'] * 1e-3), 1))
 
 
 def watch_live_stages(args, model, dev, tdt, batcher, pool, x, net_hw):

@@ -12,6 +12,7 @@
                           [--track --watchlist FILE [--watch-mismatch 1] [--watch-cost F]
                            [--watch-confusable "0D 0Q 8B 2Z 5S" [--watch-confusable-weight 4]]
                            [--watch-live [--watch-live-min-hits 3]]]
+                          [--track --sightings C [--sight-window N] [--sight-min-hits 1] [--sight-mismatch 1] [--sight-cost F]]
                           [--tile H W --tile-gate [--tile-gate-thres 2.0] [--tile-gate-min-cells 1] [--tile-gate-refresh 50]
                            [--tile-gate-illum none|gain] [--tile-gate-max-gain 1.5]]
 """
@@ -105,6 +106,15 @@ _FLAGS = [
     ('--watch-live', dict(action='store_true', help='with --watchlist: also look a track up while it is still live, once it has enough '
                                                     'detections and again when its voted read changes, and write alerts.txt')),
     ('--watch-live-min-hits', dict(type=int, default=3, metavar='N', help='with --watch-live: detections a track needs before it is looked up')),
+    ('--sightings', dict(type=int, default=None, metavar='C',
+                         help='with --track: keep a log of the last C reads of all streams, match the read of every ended track against the '
+                              'earlier ones (a broken track, the same vehicle on another video) and write resightings.txt beside plates.txt; '
+                              '--watch-confusable applies')),
+    ('--sight-window', dict(type=int, default=None, metavar='N', help='with --sightings: frames of the source a sighting stays a candidate (default: no limit)')),
+    ('--sight-min-hits', dict(type=int, default=1, metavar='N', help='with --sightings: detections a track needs to be matched and logged')),
+    ('--sight-mismatch', dict(type=int, default=1, help='with --sightings: positions that may differ (0..8)')),
+    ('--sight-cost', dict(type=float, default=None, metavar='F',
+                          help='with --sightings: largest total cost of the differing positions, in fully confident mismatches (default: no limit)')),
     ('--tile-gate', dict(action='store_true', help='with --tile: the source is one fixed camera (frames of one size); run the network only on '
                                                    'the tiles whose pixels changed since they were last detected, keep the rows of the others')),
     ('--tile-gate-thres', dict(type=float, default=2.0, metavar='F',
@@ -138,7 +148,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1, redact_lookback=None, redact_lookback_max_back=None,
         redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None, watch_confusable=None, watch_confusable_weight=4,
         watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1, tile_gate_refresh=50,
-        tile_gate_illum='none', tile_gate_max_gain=1.5):
+        tile_gate_illum='none', tile_gate_max_gain=1.5, sightings=None, sight_window=None, sight_min_hits=1, sight_mismatch=1, sight_cost=None):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track or redact) and not osp.exists(out_dir):
@@ -160,7 +170,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
                       watch_confusable_weight=watch_confusable_weight, watch_live=watch_live, watch_live_min_hits=watch_live_min_hits,
                       tile_gate=tile_gate, tile_gate_thres=tile_gate_thres,
                       tile_gate_min_cells=tile_gate_min_cells, tile_gate_refresh=tile_gate_refresh,
-                      tile_gate_illum=tile_gate_illum, tile_gate_max_gain=tile_gate_max_gain).infer(
+                      tile_gate_illum=tile_gate_illum, tile_gate_max_gain=tile_gate_max_gain, sightings=sightings, sight_window=sight_window,
+                      sight_min_hits=sight_min_hits, sight_mismatch=sight_mismatch, sight_cost=sight_cost).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

@@ -57,7 +57,8 @@ class Inferer:
                  redact_lookback=None, redact_lookback_max_back=None, redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None,
                  watch_confusable=None, watch_confusable_weight=4, watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0,
                  tile_gate_min_cells=1, tile_gate_refresh=50, tile_gate_illum='none', tile_gate_max_gain=1.5, stack_shots=False,
-                 stack_search=2, stack_max_frames=64, stack_min_width=0.0):
+                 stack_search=2, stack_max_frames=64, stack_min_width=0.0, sightings=None, sight_window=None, sight_min_hits=1,
+                 sight_mismatch=1, sight_cost=None):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -95,6 +96,12 @@ class Inferer:
         ``watch_live`` (with ``watchlist``): a track is also looked up while it is still live, as soon as it has
         ``watch_live_min_hits`` detections and again whenever its voted read changes (``yolov6.utils.watch_live`` states the rule;
         the limits are those of ``watchlist``); ``infer`` writes ``alerts.txt``.
+        ``sightings`` = C (with ``track``; ``yolov6.utils.sight`` states the rule): a log of the last C reads of all streams; the
+        read of every ended track of at least ``sight_min_hits`` detections is matched against the reads logged at most
+        ``sight_window`` frames of the source earlier (None: no limit), tolerating ``sight_mismatch`` misread positions of a total
+        cost of at most ``sight_cost`` fully confident mismatches (None: no limit; ``watch_confusable`` is shared), and is then
+        logged itself: a track broken by an occlusion names its first part, a vehicle on a second video its pass on the first.
+        ``infer`` writes ``resightings.txt``; every other output is what it is without it.
         ``tile_gate`` (with ``tile``): the whole source is ONE fixed-camera stream, every frame of the size of the first (another
         size raises); a tile is run through the network only when a 16 x 16 cell of it has changed by more than ``tile_gate_thres``
         luma levels per pixel (in at least ``tile_gate_min_cells`` cells) since the tile was last detected, or every
@@ -115,6 +122,14 @@ class Inferer:
             if not track:
                 raise ValueError('watchlist needs track=True')
             check_params(watch_mismatch, cost_units(watch_cost))
+        if sightings is not None:
+            from yolov6.utils.sight import check_call, check_log
+            from yolov6.utils.watch import check_params, cost_units
+            if not track:
+                raise ValueError('sightings needs track=True')
+            check_log(sightings, 1)
+            check_call(0, 0 if sight_window is None else sight_window, sight_min_hits)
+            check_params(sight_mismatch, cost_units(sight_cost))
         if watch_live:
             from yolov6.utils.watch_live import check_min_hits
             if watchlist is None:
@@ -215,6 +230,12 @@ class Inferer:
         With ``watch_live`` ``<save_dir>/alerts.txt`` has one line ``frame id text entry entry_text mismatches cost n_hits hits``
         per alert, in the order they fired: the stream frame of the detection that caused the lookup, the track's id and read at
         that moment, the accepted entry as in ``hits.txt``, and the detections the track had.
+
+        With ``sightings`` ``<save_dir>/resightings.txt`` has one line ``id first last text prev_stream prev_id prev_stamp now
+        mismatches cost n_hits`` per ended track with an earlier sighting: the line of ``plates.txt`` up to the text, the stream,
+        track id and stamp of the best earlier sighting (the smallest (cost, age)), the stamp of this one, the two sums and the
+        number of earlier sightings accepted.  A stamp is the number of the source's frame whose update ended the track (of the
+        last frame of a batch; the number of frames for the final flush), counted over the whole source.
 
         With ``redact`` every frame is also written, its plates redacted along the rows returned, as
         ``<save_dir>/redacted/<image name>`` (``.png`` for a frame of a video or a raw stream)."""
@@ -492,6 +513,17 @@ class Inferer:
             self._tracker.enable_watch(wl, self.watch_mismatch, self.watch_cost)
             if self.watch_live:
                 self._tracker.enable_live_watch(wl, self.watch_live_min_hits, self.watch_mismatch, self.watch_cost)
+        self._track_sights = []         # with sightings: (sight_i line, now) of every ended record
+        self._track_seen = 0            # frames of the source handed to the tracker so far
+        if self.sightings is not None:
+            from yolov6.utils import sight, watch
+            confuse = None
+            if self.watch_confusable:
+                confuse = watch.confuse_table(watch.confusable_pairs(self.watch_confusable), 2, self.watch_confusable_weight, self.ads_names)
+            make = runtime.SightLog if self.device.type != 'cpu' else sight.SightLogNp
+            log = make(self.sightings, 1 + len(videos), confuse, device=self.device)
+            window = (1 << 31) - 1 if self.sight_window is None else self.sight_window      # the largest int32: no limit
+            self._tracker.enable_sightings(log, window, self.sight_min_hits, self.sight_mismatch, self.sight_cost)
         self._track_alerts = []         # with watch_live: (frame, id, best [8], entry, mismatches, cost, n_hits, hits) per alert
         if self.redact_hold:
             self._tracker.enable_hold(min_hits=self.redact_hold_min_hits)
@@ -530,6 +562,9 @@ class Inferer:
             stack_i = stack_i.cpu().numpy()
         if torch.is_tensor(match_i):
             match_i = match_i.cpu().numpy()
+        sight_i = self._tracker.last_sight if self.sightings is not None else None     # of the same update too
+        if torch.is_tensor(sight_i):
+            sight_i = sight_i.cpu().numpy()
         for s, c in enumerate(ended_count.tolist()):
             if c > ended_i.shape[1]:
                 LOGGER.warning('stream %d: %d tracks ended in one step, %d recorded' % (s, c, ended_i.shape[1]))
@@ -537,6 +572,8 @@ class Inferer:
                 self._track_ended.append((ended_i[s, k].copy(), ended_f[s, k].copy()))
                 if match_i is not None:
                     self._track_hits.append(match_i[s, k].copy())
+                if sight_i is not None:
+                    self._track_sights.append((sight_i[s, k].copy(), self._track_now))
                 if shot_i is not None:
                     crop = shot_crops[s, k] if shot_i[s, k, 3] else None
                     crop = crop.cpu().numpy() if torch.is_tensor(crop) else (None if crop is None else crop.copy())
@@ -563,6 +600,7 @@ class Inferer:
         self._track_last_paths = list(paths)
         # a slot's track lives at least max_age + 1 frames: so many records at most can end in B frames
         max_ended = self._tracker.max_tracks * (B // (self.track_max_age + 1) + 1)
+        self._track_clock(len(paths))
         if not self.best_shots:
             det_out, tid, ended_i, ended_f, ended_count = self._tracker.update(det, count, streams, max_ended=max_ended)
             self._track_collect(ended_i, ended_f, ended_count)
@@ -579,6 +617,14 @@ class Inferer:
         if torch.is_tensor(det_out):
             det_out, tid = det_out.clone(), tid.clone()     # the tracker's buffers are persistent
         return det_out, tid
+
+    def _track_clock(self, n_frames):
+        """Set the clock of the sightings for the tracker call that takes the next ``n_frames`` frames of the source: the number of
+        the last of them (0 frames: the final flush, stamped with the number of frames)."""
+        self._track_seen += n_frames
+        self._track_now = self._track_seen - (1 if n_frames else 0)
+        if self.sightings is not None:
+            self._tracker.sight_now[0] = self._track_now
 
     def _track_frame(self, det, img_path, max_det, frame=None):
         """The voted rows of one frame's rescaled detections ([n, 28] tensor); its track ids are queued for ``infer``."""
@@ -598,6 +644,7 @@ class Inferer:
     def _track_finish(self, save_dir):
         """Flush every stream and write tracks.txt / plates.txt."""
         from yolov6.utils.track import plate_text
+        self._track_clock(0)
         if not self.best_shots:
             self._track_collect(*self._tracker.flush_all()[2:])
         elif self.device.type != 'cpu':
@@ -625,6 +672,13 @@ class Inferer:
                     if m[0] >= 0:
                         f.write('%d %d %d %s %d %s %d %d %d\n' % (ri[0], ri[1], ri[2], plate_text(ri[4:12], *names), m[0],
                                                                   entry_text(entries[m[0]], *names), m[1], m[2], m[3]))
+        if self.sightings is not None:
+            names = (self.pro_names, self.alp_names, self.ads_names)
+            with open(osp.join(save_dir, 'resightings.txt'), 'w') as f:
+                for (ri, _), (m, now) in zip(self._track_ended, self._track_sights):
+                    if m[0] >= 0:
+                        f.write('%d %d %d %s %d %d %d %d %d %d %d\n' % (ri[0], ri[1], ri[2], plate_text(ri[4:12], *names), m[4], m[5], m[6], now,
+                                                                        m[1], m[2], m[3]))
         if self.watch_live:
             from yolov6.utils.watch import entry_text
             names = (self.pro_names, self.alp_names, self.ads_names)

@@ -1642,6 +1642,93 @@ class Watchlist:
         return match_i
 
 
+class SightLog:
+    """A log of sightings on the device (lp_sight_update; ``yolov6.utils.sight`` states the rule and ``sight_update_np`` there is
+    the same computation on the CPU, on every int32): a ring of ``capacity`` reads of ``n_streams`` streams that one call scans
+    for the earlier sightings of the reads that end and then appends them to.  ``confuse`` [3,64,64] sixteenths or None
+    (``watch.confuse_table``); ``pair`` uint8 [S,S] or None: pair[s_read][s_entry] != 0 lets entries of stream s_entry match reads
+    of stream s_read.  The object owns the zeroed state (int32 [1 + capacity, 8]) and persistent output buffers per
+    (S, max_ended)."""
+
+    def __init__(self, capacity, n_streams, confuse=None, pair=None, device='cuda'):
+        from yolov6.utils import sight, watch
+        self.capacity, self.n_streams = sight.check_log(capacity, n_streams)
+        self.confuse_np = None if confuse is None else watch.check_confuse(confuse)
+        self.pair_np = sight.check_pair(pair, self.n_streams)
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise ValueError('SightLog lives on a GPU (SightLogNp is the CPU form)')
+        self.device = torch.device('cuda', torch.cuda.current_device() if dev.index is None else dev.index)
+        self.confuse = None if self.confuse_np is None else torch.from_numpy(self.confuse_np).to(self.device)
+        self.pair = None if self.pair_np is None else torch.from_numpy(self.pair_np).to(self.device)
+        nbytes = abi.load().lp_sight_state_bytes(self.capacity)
+        #: int32 [1 + capacity, 8] on the device: the header row and one row per slot
+        self.state = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.device).view(1 + self.capacity, 8)
+        self._now = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._bound = 0          # no fewer than the appends since the last clear: every call adds its lines
+        self._out = {}
+
+    @property
+    def total(self):
+        """The reads appended since the last ``clear`` (a host read, outside the hot path)."""
+        return int(self.state[0, 0].item())
+
+    def clear(self):
+        """Empty the log."""
+        self.state.zero_()
+        self._bound = 0
+
+    def buffers(self, S, max_ended):
+        """The persistent (sight_i [S,max_ended,8] int32, workspace) of an ``update`` of that shape."""
+        key = (int(S), int(max_ended))
+        need = abi.load().lp_sight_workspace_bytes(*key)
+        return _persistent(self._out, key, lambda: (torch.empty(key[0], key[1], 8, dtype=torch.int32, device=self.device),
+                                                    torch.empty(need + 256, dtype=torch.uint8, device=self.device)))
+
+    def update(self, ended_i, ended_f, ended_count, now, window, min_hits=1, max_mismatch=1, max_cost=None):
+        """sight_i [S,max_ended,8] int32 = (slot, mismatches, cost, n_hits, prev_stream, prev_id, prev_stamp, prev_seq) per line of
+        the ended records of a ``PlateTracker.update`` (device tensors): the best earlier sighting within ``window`` of ``now`` of
+        every read of at least ``min_hits`` hits, (-1, 0, 0, 0, -1, -1, 0, 0) for none; then the reads are appended.  Enqueued on the
+        current stream with no host read.  ``now``: an int (copied into a buffer of the log's with one enqueued copy) or a device
+        int32 [1] that the call reads in place; ``max_cost``: a float in fully confident mismatches (None: no limit).  Persistent
+        buffers per (S, max_ended): a later call of the same shape overwrites what the earlier one returned."""
+        from yolov6.utils import sight, watch
+        mm, mc = watch.check_params(max_mismatch, watch.cost_units(max_cost))
+        if torch.is_tensor(now):
+            _, window, min_hits = sight.check_call(0, window, min_hits)
+        else:
+            now, window, min_hits = sight.check_call(now, window, min_hits)
+            self._now.fill_(now)
+            now = self._now
+        return self._update(ended_i, ended_f, ended_count, now, window, min_hits, mm, mc)
+
+    def _update(self, ended_i, ended_f, ended_count, now, window, min_hits, mm, mc):
+        """``update`` with ``now`` on the device and the parameters as the checked integers of the rule."""
+        if ended_i.dim() != 3 or ended_i.shape[2] != 12 or ended_i.dtype != torch.int32 or ended_f.shape != ended_i.shape \
+                or ended_f.dtype != torch.float32 or ended_count.dtype != torch.int32 or ended_count.shape != ended_i.shape[:1]:
+            raise ValueError('ended_i int32 / ended_f fp32 must be [S,max_ended,12] and ended_count int32 [S]')
+        if now.dtype != torch.int32 or now.numel() != 1:
+            raise ValueError('now must be an int or a device int32 [1]')
+        for t in (ended_i, ended_f, ended_count, now):
+            if t.device != self.device or not t.is_contiguous():
+                raise ValueError('the ended records and now must be contiguous tensors on the log\'s device %s' % self.device)
+        S, max_ended = ended_i.shape[:2]
+        if S != self.n_streams:
+            raise ValueError('the ended records must have the log\'s %d streams' % self.n_streams)
+        from yolov6.utils.sight import MAX_APPENDS
+        if self._bound + S * max_ended > MAX_APPENDS:
+            raise RuntimeError('the log takes fewer than 2^31 appends between clears: clear() it')
+        self._bound += S * max_ended
+        sight_i, ws = self.buffers(S, max_ended)
+        base = _aligned(ws)
+        with torch.cuda.device(self.device):
+            abi.check(abi.load().lp_sight_update(_dptr(self.state), self.capacity, _dptr(self.confuse), _dptr(self.pair), _dptr(ended_i),
+                                                 _dptr(ended_f), _dptr(ended_count), S, max_ended, _dptr(now), window, min_hits, mm, mc,
+                                                 _dptr(sight_i), ctypes.c_void_p(base), ws.numel() - (base - ws.data_ptr()),
+                                                 _stream_ptr(self.device)), 'lp_sight_update')
+        return sight_i
+
+
 class PlateTracker:
     """``n_streams`` independent device-resident plate trackers of ``max_tracks`` slots each (lp_track_update, one workgroup per
     stream): detections of consecutive frames are associated by the IoU of expanded, velocity-predicted boxes
@@ -1686,11 +1773,16 @@ class PlateTracker:
         self.last_live = None
         #: (q_i, q_f, q_slot, q_count) of that lookup: the fresh reads in the ended-record layout, else None
         self.last_live_reads = None
+        self._sight = None
+        #: sight_i [S,max_ended,8] int32 of the last ``update`` after ``enable_sightings``, line-parallel to its ended_i, else None
+        self.last_sight = None
+        #: int32 [1] on the device: the clock of ``enable_sightings``, incremented by one per call; the caller may set it
+        self.sight_now = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def reset(self, streams=None):
         """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0; their best-shot
         galleries (``enable_best_shot``) and stacks (``enable_stack``) are emptied with them, and their memo of
-        ``enable_live_watch``."""
+        ``enable_live_watch``.  The log of ``enable_sightings`` and ``sight_now`` stay as they are."""
         _zero_streams(self.state, self.n_streams, streams)
         if self._stack is not None:
             _zero_streams(self._stack['state'], self.n_streams, streams)
@@ -1738,7 +1830,32 @@ class PlateTracker:
             self.last_watch = wl._match(ended_i, ended_f, ended_count, mm, mc)
         if self._live is not None:
             self._live_watch()
+        if self._sight is not None:
+            log, params = self._sight
+            self.last_sight = log._update(ended_i, ended_f, ended_count, self.sight_now, *params)
+            self.sight_now.add_(1)
         return out
+
+    # ---- the ended reads matched against the earlier reads of all streams (lp_sight_update; yolov6/utils/sight.py states the rule) ----
+    def enable_sightings(self, log, window=0, min_hits=1, max_mismatch=1, max_cost=None):
+        """From now on every ``update`` / ``update_with_shots`` / ``flush_all*`` also enqueues, at its end on the same stream (behind
+        the lookups of ``enable_watch`` and ``enable_live_watch``), lp_sight_update of the records it ended on ``log`` (a ``SightLog``
+        of this device and of the tracker's ``n_streams``), and leaves sight_i [S,max_ended,8] int32 = (slot, mismatches, cost, n_hits,
+        prev_stream, prev_id, prev_stamp, prev_seq), line-parallel to ended_i, in ``last_sight``.  The clock is ``sight_now``, a device
+        int32 [1]: the call reads it in place and then increments it by one on the device, so that left alone it counts the
+        tracker's calls; a caller with a clock of its own sets the tensor before every call (``sight_now.fill_(t)`` or a copy).
+        ``window`` is in the clock's units.  No host read, no allocation per call; a caller
+        that replays a captured update counts those appends itself (fewer than 2^31 between two ``log.clear()``).  Returns, state
+        and every other buffer are what they are without it.  ``enable_sightings(None)`` turns it off."""
+        from yolov6.utils import sight, watch
+        self.last_sight = None
+        if log is None:
+            self._sight = None
+            return
+        if not isinstance(log, SightLog) or log.device != self.device or log.n_streams != self.n_streams:
+            raise ValueError('enable_sightings needs a SightLog of %d streams on the tracker\'s device %s' % (self.n_streams, self.device))
+        _, window, min_hits = sight.check_call(0, window, min_hits)
+        self._sight = (log, (window, min_hits) + watch.check_params(max_mismatch, watch.cost_units(max_cost)))
 
     # ---- the live tracks looked up in a watchlist (lp_watch_live; yolov6/utils/watch_live.py states the rule) -----------------
     def enable_live_watch(self, watchlist, min_hits=3, max_mismatch=1, max_cost=None):

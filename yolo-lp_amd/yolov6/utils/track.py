@@ -192,6 +192,11 @@ class PlateTrackerNp:
         self.last_live = None
         #: (q_i, q_f, q_slot, q_count) of that lookup: the fresh reads in the ended-record layout, else None
         self.last_live_reads = None
+        self._sight = None
+        #: sight_i [S, max_ended, 8] int32 of the last ``update`` after ``enable_sightings``, line-parallel to its ended_i, else None
+        self.last_sight = None
+        #: int32 [1]: the clock of ``enable_sightings``, incremented by one per call; the caller may set it
+        self.sight_now = np.zeros(1, np.int32)
 
     _SLOT_ARRAYS = ('id', 'first', 'last', 'hits', 'misses', 'box', 'cor', 'vel', 'votes', 'total')
 
@@ -266,6 +271,23 @@ class PlateTrackerNp:
         from yolov6.utils.watch_live import LiveWatchNp
         self.last_live = self.last_live_reads = None
         self._live = None if watchlist is None else LiveWatchNp(self, watchlist, min_hits, max_mismatch, max_cost)
+
+    def enable_sightings(self, log, window=0, min_hits=1, max_mismatch=1, max_cost=None):
+        """From now on every ``update`` / ``flush_all`` also matches the records it ended against the earlier reads in ``log`` (a
+        ``sight.SightLogNp`` of the tracker's ``n_streams``) and appends them to it (``yolov6.utils.sight`` states the rule), behind
+        the lookups of ``enable_watch`` and ``enable_live_watch``; sight_i [S, max_ended, 8] int32 is left in ``last_sight``.  The
+        clock is ``sight_now`` [1]: read by the call, then incremented by one (a caller with a clock of its own sets it before
+        every call).  Every other output and the state stay what they are; the log survives ``reset``.
+        ``enable_sightings(None)`` turns it off."""
+        from yolov6.utils import sight, watch
+        self.last_sight = None
+        if log is None:
+            self._sight = None
+            return
+        if not isinstance(log, sight.SightLogNp) or log.n_streams != self.n_streams:
+            raise ValueError('enable_sightings needs a SightLogNp of %d streams' % self.n_streams)
+        _, window, min_hits = sight.check_call(0, window, min_hits)
+        self._sight = (log, (window, min_hits) + watch.check_params(max_mismatch, watch.cost_units(max_cost)))
 
     def hold_buffers(self, B, max_det):
         """The persistent (det_hold [B,max_det+max_tracks,28] fp32, count_hold [B] int32, tid_hold [B,max_det+max_tracks] int32)
@@ -471,4 +493,10 @@ class PlateTrackerNp:
             lw = self._live
             self.last_live = lw.step()
             self.last_live_reads = (lw.q_i, lw.q_f, lw.q_slot, lw.q_count)
+        if self._sight is not None:
+            from yolov6.utils.sight import sight_update_np
+            log, params = self._sight
+            self.last_sight = sight_update_np(log.state, log.confuse_np, log.pair_np, ended_i, ended_f, ended_count,
+                                              int(self.sight_now[0]), *params)
+            self.sight_now += 1
         return det_out, tid, ended_i, ended_f, ended_count
