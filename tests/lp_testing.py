@@ -1835,3 +1835,388 @@ def greedy_schedule_np(over, max_det, mutant=None):
         if len(kept) >= max_det:
             break
     return np.asarray(kept if mutant == 'no_cut' else kept[:max_det], np.int64)
+
+
+# ---- the tracker's add-ons together (tests/test_all_on_cpu.py, tests/test_all_on_gpu.py) ---------------------------------------------
+# One scene through a tracker with best shot, stack, hold, look-back, watchlist, live watch and sightings all enabled.  The numpy chain
+# ``AllOnNp`` composes the single specifications (PlateTrackerNp with every enable_*, BestShotNp, LookbackNp) in the order the product
+# enqueues them; with a subset of ``ALL_ON_FEATURES`` it is the single-feature chain, with a ``mutant`` one deliberate mis-composition.
+ALL_ON_FEATURES = ('shot', 'stack', 'hold', 'lookback', 'watch', 'live', 'sight')
+ALL_ON_NEEDS = {'stack': ('shot',), 'lookback': ('hold',)}                       # what a feature cannot be enabled without
+ALL_ON_OUTPUTS = {                                                               # feature -> the outputs of a step that are its own
+    'track': ('det_out', 'tid', 'slot', 'ended_i', 'ended_f', 'ended_count'), 'hold': ('det_hold', 'count_hold', 'tid_hold'),
+    'watch': ('match_i',), 'live': ('live_i', 'q_i', 'q_f', 'q_slot', 'q_count'), 'sight': ('sight_i',),
+    'shot': ('shot_crops', 'shot_i', 'shot_q', 'shot_det'), 'stack': ('stack_crops', 'stack_i'), 'lookback': ('released',),
+}
+ALL_ON_MUTANTS = ('redact_first', 'stale_ended', 'stale_slot', 'lookback_no_copy', 'reset_skips_tracker', 'reset_skips_gallery',
+                  'reset_skips_stack', 'reset_skips_memo', 'reset_skips_lookback')
+ALL_ON = dict(n_streams=3, max_det=6, Bs=(1, 3, 70, 2, 0), frame_hw=(40, 120), crop_hw=(8, 24), max_crops=6, max_ended=2, depth=4, seed=2269,
+              reset_before=3, reset_streams=(1,), poison=0xAB,
+              track=dict(max_tracks=70, match_thres=0.3, new_thres=0.2, expand=0.5, max_age=18),
+              shot=dict(min_score=0.2), stack=dict(search=2, max_frames=5, min_width=8.0, min_sharp=1), hold=dict(min_hits=2),
+              redact=dict(mode='mosaic', cell=4, margin=0.1), watch=dict(max_mismatch=1, max_cost=0.75), live=dict(min_hits=2),
+              sight=dict(window=5, min_hits=1, max_mismatch=8, max_cost=6.0), sight_capacity=64)
+_all_on_cache = {}
+
+
+def all_on_scene(seed):
+    """The calls [(det, count, stream_of, flush, frames)] of the all-on tests: ``test_track_cpu.random_track_case`` on the shapes of
+    ALL_ON (two objects per stream that live inside the frame), plus, in every frame of stream 0, a passer-by in each free row: a
+    5 x 3 box on its own cell of an 8 x 5 grid, seen once, so that stream 0 fills its 70 slots past lane 64 and its tracks end by age,
+    many more per call than ``max_ended``; call 3 flushes stream 2 without showing it a frame; seeded frames that move from call to
+    call, so that every crop sees other pixels."""
+    import test_track_cpu as C
+    p = ALL_ON
+    calls = C.random_track_case(seed, n_streams=p['n_streams'], max_det=p['max_det'], n_obj=2, extent=40, Bs=p['Bs'])
+    rng = np.random.default_rng(seed + 1000)
+    H, W = p['frame_hw']
+    base = rng.integers(0, 256, (H + 16, W + 64, 3), dtype=np.uint8)
+    base[::2] //= 3                                                             # rows of two brightnesses: sharpness differs with the cut
+    out, k, f = [], 0, 0
+    for c, (det, count, stream_of, flush) in enumerate(calls):
+        det, count, flush = det.copy(), count.copy(), list(flush)
+        if c == 3:
+            stream_of = [s if s != 2 else 1 for s in stream_of]
+            flush[2] = 1
+        for b, s in enumerate(stream_of):
+            n = int(count[b])
+            if s != 0 or not 0 <= n < p['max_det']:
+                continue
+            for r in range(n, p['max_det']):
+                cell = k % 120
+                x, y = 1 + 8 * (cell % 15), 1 + 5 * (cell // 15)
+                det[b, r] = C.make_row((x, y, x + 5, y + 3), ids=rng.integers(0, 24, 8), conf=(rng.integers(3, 9, 8) / 8.0))
+                k += 1
+            count[b] = p['max_det']
+        frames = []
+        for b in range(len(det)):
+            dy, dx = (5 * f) % 16, (7 * f) % 64
+            frames.append(np.ascontiguousarray(base[dy:dy + H, dx:dx + W]))
+            f += 1
+        out.append((det, count, list(stream_of), flush, frames))
+    return out
+
+
+def all_on_watchlist(calls):
+    """Entries for the scene: every other read that a plain run ends within ``max_ended`` and every third read a live track of at least
+    two hits shows, unchanged, between random entries."""
+    from yolov6.utils.track import PlateTrackerNp
+    p = ALL_ON
+    rng = np.random.default_rng(5)
+    trk, ended, live = PlateTrackerNp(p['n_streams'], **p['track']), [], []
+    for det, count, stream_of, flush, _ in calls:
+        _, _, ei, _, ec = trk.update(det, count, stream_of, flush, p['max_ended'])
+        ended += [ei[s, j, 4:] for s in range(p['n_streams']) for j in range(min(int(ec[s]), p['max_ended']))]
+        live += [trk.read(s, t)[0] for s, t in np.argwhere(trk.hits >= 2)]
+    rows = []
+    for r in ended[::2] + live[::3]:
+        if ((r >= 0) & (r < 64)).all():
+            rows += [r, rng.integers(0, 24, 8)]
+    return np.array(rows, np.uint8).reshape(-1, 8)
+
+
+def all_on_case():
+    """(calls, watchlist entries, confusion table) of the all-on tests, made once per process and never modified."""
+    if 'case' not in _all_on_cache:
+        from yolov6.utils.watch import confuse_table
+        calls = all_on_scene(ALL_ON['seed'])
+        _all_on_cache['case'] = (calls, all_on_watchlist(calls), confuse_table([(1, 2), (3, 8), (0, 13)], weight=3))
+    return _all_on_cache['case']
+
+
+def all_on_features(features):
+    """``features`` with what they need, in the order of ALL_ON_FEATURES."""
+    on = set(features)
+    for f in features:
+        on |= set(ALL_ON_NEEDS.get(f, ()))
+    assert on <= set(ALL_ON_FEATURES), on
+    return tuple(f for f in ALL_ON_FEATURES if f in on)
+
+
+class AllOnNp:
+    """The numpy chain of one tracker call with ``features`` enabled, in the product's order:
+      1. the frames are uploaded into the slots of a ring that every call reuses (``FrameBatcher``);
+      2. the tracker's update: rules 1..11, then the watchlist, the live watch and the sightings on the records it ended;
+      3. the crops are cut from the uploaded frames; the gallery, then the stack, read them with this call's tid, slot and records;
+      4. COPIES of the frames enter the delay line, and the frames that leave it are redacted along the rows released for them.
+    ``step`` returns the outputs by name (ALL_ON_OUTPUTS), each a copy.  ``mutant``: one of ALL_ON_MUTANTS."""
+
+    def __init__(self, features=ALL_ON_FEATURES, mutant=None, entries=None, confuse=None):
+        from yolov6.utils.best_shot import BestShotNp
+        from yolov6.utils.lookback import LookbackNp
+        from yolov6.utils.sight import SightLogNp
+        from yolov6.utils.track import PlateTrackerNp
+        from yolov6.utils.watch import WatchlistNp
+        assert mutant is None or mutant in ALL_ON_MUTANTS
+        p = ALL_ON
+        self.on, self.mutant = all_on_features(features), mutant
+        S, T = p['n_streams'], p['track']['max_tracks']
+        self.trk = trk = PlateTrackerNp(S, **p['track'])
+        self.gal = self.lb = self.log = None
+        if entries is None:
+            _, entries, confuse = all_on_case()
+        wl = WatchlistNp(entries, confuse)
+        if 'hold' in self.on:
+            trk.enable_hold(**p['hold'])
+        if 'watch' in self.on:
+            trk.enable_watch(wl, **p['watch'])
+        if 'live' in self.on:
+            trk.enable_live_watch(wl, p['live']['min_hits'], **p['watch'])
+        if 'sight' in self.on:
+            self.log = SightLogNp(p['sight_capacity'], S, confuse)
+            trk.enable_sightings(self.log, **p['sight'])
+        if 'shot' in self.on:
+            self.gal = BestShotNp(S, T, p['crop_hw'], p['shot']['min_score'])
+        if 'stack' in self.on:
+            trk.enable_stack(crop_hw=p['crop_hw'], max_crops=p['max_crops'], min_score=p['shot']['min_score'], **p['stack'])
+        if 'lookback' in self.on:
+            self.lb = LookbackNp(trk, p['depth'], **p['redact'])
+        self.ring = {}                  # slot b of the upload ring -> its persistent array
+        self.prev_ended = None          # (ended_i, ended_count) of the previous call
+        self.slot_cache = {}            # (B, max_det) -> (tid, slot) as the previous call of that shape left them
+
+    def reset(self, streams):
+        """``PlateTracker.reset(streams)`` plus the delay line's: tracker, live memo, stack, gallery, delay line."""
+        skip = {'reset_skips_tracker': (self.trk, self.trk._SLOT_ARRAYS + ('frame', 'next_id', 'dropped')),
+                'reset_skips_gallery': (self.gal, self.gal._ARRAYS if self.gal is not None else ()),
+                'reset_skips_stack': (self.trk._stack['np'], self.trk._stack['np']._ARRAYS) if self.trk._stack is not None else (None, ()),
+                'reset_skips_memo': (self.trk._live, ('memo',))}.get(self.mutant, (None, ()))
+        kept = {name: getattr(skip[0], name).copy() for name in skip[1]} if skip[0] is not None else {}
+        self.trk.reset(streams)
+        if self.gal is not None:
+            self.gal.reset(streams)
+        if self.lb is not None and self.mutant != 'reset_skips_lookback':
+            self.lb.reset(streams)
+        for name, a in kept.items():
+            getattr(skip[0], name)[...] = a
+
+    def step(self, det, count, stream_of, flush, frames):
+        from yolov6.utils.redact import redact_plates_np
+        p, trk, B = ALL_ON, self.trk, len(det)
+        up = []
+        for b, fr in enumerate(frames):                                         # 1
+            buf = self.ring.get(b)
+            if buf is None:
+                buf = self.ring[b] = np.empty_like(fr)
+            buf[:] = fr
+            up.append(buf)
+        o = trk.update(det, count, stream_of, flush, p['max_ended'])            # 2
+        out = dict(zip(ALL_ON_OUTPUTS['track'], (o[0], o[1], trk.last_slot, o[2], o[3], o[4])))
+        if 'hold' in self.on:
+            out.update(zip(ALL_ON_OUTPUTS['hold'], trk.last_hold))
+            if self.mutant == 'redact_first' and B:                             # the frames are redacted where they lie, before the cut
+                for buf, red in zip(up, redact_plates_np(up, trk.last_hold[0], trk.last_hold[1], **p['redact'])[0]):
+                    buf[:] = red
+        if 'watch' in self.on:
+            out['match_i'] = trk.last_watch
+        if 'live' in self.on:
+            out.update(zip(ALL_ON_OUTPUTS['live'], (trk.last_live,) + tuple(trk.last_live_reads)))
+        if 'sight' in self.on:
+            out['sight_i'] = trk.last_sight
+        ended = (o[2], o[4])
+        if self.mutant == 'stale_ended' and self.prev_ended is not None:
+            ended = self.prev_ended
+        tid, slot = o[1], trk.last_slot
+        if self.mutant == 'stale_slot':                                         # the cached buffer of the shape, as it was before this call
+            tid, slot = self.slot_cache.get(det.shape[:2], (np.full_like(tid, -1), np.full_like(slot, -1)))
+        self.prev_ended, self.slot_cache[det.shape[:2]] = (o[2].copy(), o[4].copy()), (o[1].copy(), trk.last_slot.copy())
+        poison = lambda: np.full((p['n_streams'], p['max_ended']) + tuple(p['crop_hw']) + (3,), p['poison'], np.uint8)   # noqa: E731
+        if self.gal is not None:                                                # 3
+            out.update(zip(ALL_ON_OUTPUTS['shot'], self.gal.update_from_frames(up, det, count, tid, slot, stream_of, ended[0], ended[1],
+                                                                                p['max_crops'], shot_crops=poison())))
+        if 'stack' in self.on:
+            if self.mutant in ('stale_ended', 'stale_slot'):
+                res = trk._stack['np'].update_from_frames(up, det, count, tid, slot, stream_of, ended[0], ended[1], p['max_crops'],
+                                                          stack_crops=poison())
+            else:
+                trk._stack['out'][p['max_ended']] = poison()
+                res = trk.update_stack(up, det, count, stream_of)
+            out.update(zip(ALL_ON_OUTPUTS['stack'], res))
+        if self.lb is not None:                                                 # 4
+            held = up if self.mutant == 'lookback_no_copy' else [f.copy() for f in up]
+            out['released'] = self.lb.push(held, stream_of, flush)
+        return {k: ([(s, g, f.copy()) for s, g, f in v] if k == 'released' else np.array(v, copy=True)) for k, v in out.items()}
+
+
+def all_on_run(features=ALL_ON_FEATURES, mutant=None, reset=True, first=0):
+    """The scene's calls from call ``first`` on through a fresh AllOnNp: (chain, [outputs of each call]); ``reset``: with the reset of
+    ALL_ON['reset_streams'] in front of call ALL_ON['reset_before']."""
+    calls = all_on_case()[0]
+    chain, outs = AllOnNp(features, mutant), []
+    for c, call in enumerate(calls):
+        if c < first:
+            continue
+        if reset and c == ALL_ON['reset_before']:
+            chain.reset(ALL_ON['reset_streams'])
+        outs.append(chain.step(*call))
+    return chain, outs
+
+
+def all_on_reference():
+    """(chain, outputs per call) of the all-on run with the reset, once per process."""
+    if 'ref' not in _all_on_cache:
+        _all_on_cache['ref'] = all_on_run()
+    return _all_on_cache['ref']
+
+
+def all_on_differences(a, b, names=None):
+    """The names of the outputs in which two runs (lists of step outputs) differ anywhere, sorted; a name only one run has counts."""
+    diff = set()
+    for x, y in zip(a, b):
+        for k in (set(x) | set(y)) if names is None else names:
+            if k not in x or k not in y:
+                diff.add(k)
+            elif k == 'released':
+                same = [(s, g) for s, g, _ in x[k]] == [(s, g) for s, g, _ in y[k]] and all(np.array_equal(f, h) for (_, _, f), (_, _, h) in zip(x[k], y[k]))
+                if not same:
+                    diff.add(k)
+            elif x[k].shape != y[k].shape or x[k].dtype != y[k].dtype or x[k].tobytes() != y[k].tobytes():
+                diff.add(k)
+    return sorted(diff)
+
+
+def all_on_conditions(seed=None):
+    """What the scene of ``seed`` (None: the tests' own) reaches, counted on the all-on numpy chain alone: a dict of counters, each of
+    which the CPU test wants above zero before anything else runs."""
+    from yolov6.utils.lookback import LookbackNp
+    from yolov6.utils.watch_live import alerts_of
+    p = ALL_ON
+    if seed is None:
+        calls, entries, confuse = all_on_case()
+    else:
+        from yolov6.utils.watch import confuse_table
+        calls = all_on_scene(seed)
+        entries, confuse = all_on_watchlist(calls), confuse_table([(1, 2), (3, 8), (0, 13)], weight=3)
+    chain = AllOnNp(entries=entries, confuse=confuse)
+    near = LookbackNp(chain.trk, p['depth'], max_back=0, **p['redact'])          # the same delay line without the frames before the first detection
+    n = dict(by_age=0, by_flush=0, overflow=0, held=0, back_before_first=0, shot_replaced=0, stack_n2=0, watch_hit=0, alert=0, resighting=0,
+             slot_64=0, split=0, untracked=0, idle_flush=0, dropped=0, shot_valid=0, cut_with_entry=0)
+    for c, (det, count, stream_of, flush, frames) in enumerate(calls):
+        if c == p['reset_before']:
+            chain.reset(p['reset_streams'])
+            near.reset(p['reset_streams'])
+        live_before = [int(chain.trk.live(s).sum()) for s in range(p['n_streams'])]
+        o = chain.step(det, count, stream_of, flush, frames)
+        near.push([f.copy() for f in frames], stream_of, flush)
+        ec = o['ended_count']
+        n['overflow'] += int((ec > p['max_ended']).sum())
+        n['held'] += int((o['count_hold'] - np.clip(count, 0, p['max_det'])).sum())
+        n['watch_hit'] += int((o['match_i'][..., 0] >= 0).sum())
+        n['alert'] += len(alerts_of(o['live_i']))
+        n['resighting'] += int((o['sight_i'][..., 0] >= 0).sum())
+        n['stack_n2'] += int(((o['stack_i'][..., 3] == 1) & (o['stack_i'][..., 0] >= 2)).sum())
+        n['shot_valid'] += int(o['shot_i'][..., 3].sum())
+        n['slot_64'] += int((chain.trk.hits[:, 64:] > 0).sum())                   # live after the call
+        n['untracked'] += sum(1 for s in stream_of if s < 0)
+        n['idle_flush'] += sum(1 for s in range(p['n_streams']) if flush[s] and s not in stream_of and live_before[s] > 0)
+        n['by_flush'] += sum(int(ec[s]) for s in range(p['n_streams']) if flush[s] and s not in stream_of)
+        n['by_age'] += sum(int(ec[s]) for s in range(p['n_streams']) if not flush[s])
+        if len(stream_of) > 64:
+            n['split'] += sum(1 for s in range(p['n_streams']) if s in stream_of[:64] and s in stream_of[64:])
+    n['back_before_first'] = chain.lb.stats['back_rows'] - near.stats['back_rows']
+    n['shot_replaced'] = chain.gal.stats['replaced']
+    n['dropped'] = int(chain.trk.dropped.sum())
+    n['cut_with_entry'] = int((chain.gal.idp1 != 0).sum())
+    return n
+
+
+# The Inferer with every flag (tests/test_all_on_cpu.py on the CPU path, tests/test_all_on_gpu.py on the GPU paths): feature sets of
+# tools/infer.py's keywords; 'all' is their union.  A watchlist file is added to 'watch' and 'live' by ``all_on_infer``.
+INFER_CROP = (16, 48)
+INFER_SETS = {
+    'crops': dict(save_crops=True),
+    'shots': dict(best_shots=True),
+    'stacks': dict(best_shots=True, stack_shots=True, stack_search=1, stack_max_frames=4, stack_min_width=8.0),
+    'sightings': dict(sightings=4, sight_window=12, sight_mismatch=8),
+    'watch': dict(), 'live': dict(watch_live=True, watch_live_min_hits=2),
+    'hold': dict(redact='mosaic', redact_cell=8, redact_hold=True),
+    'lookback': dict(redact='mosaic', redact_cell=8, redact_hold=True, redact_lookback=4),
+}
+INFER_FRAMES = 12
+
+
+def all_on_infer_source(tmp):
+    """(checkpoint, image folder) under ``tmp``: the tiny synthetic yololps and twelve 128 x 160 frames of ``test_sight_cpu.
+    blinking_frames`` (the plate is hidden for four frames: its track breaks and comes back)."""
+    from PIL import Image
+    from yolov6.utils.synth import build_synthetic
+    import test_sight_cpu as SC
+    m = build_synthetic(os.path.join(REPO, 'configs', 'yololps.py'), width=0.0625, sigma=1.5)
+    torch.save({'model': m.half(), 'ema': None, 'epoch': 0}, str(tmp / 'tiny.pt'))
+    (tmp / 'imgs').mkdir()
+    for k, f in enumerate(SC.blinking_frames(INFER_FRAMES, range(3, 7))):
+        Image.fromarray(f).save(str(tmp / 'imgs' / ('f%02d.png' % k)))
+    return tmp / 'tiny.pt', tmp / 'imgs'
+
+
+def files_under(root):
+    """{path relative to ``root``: bytes} of every file below it."""
+    out = {}
+    for d, _, names in os.walk(str(root)):
+        for n in names:
+            p = os.path.join(d, n)
+            with open(p, 'rb') as f:
+                out[os.path.relpath(p, str(root))] = f.read()
+    return out
+
+
+def all_on_infer(infer, tmp, ckpt, src, tag, names=None, **kw):
+    """``infer.run`` with the sets ``names`` of INFER_SETS alone (default: tracking alone and every set) and with all of INFER_SETS at
+    once, under ``tmp / tag``: {set name: its files}.  The plates.txt of the first run gives the watchlist: the first read, the last
+    read with a wildcard, one read that nothing shows."""
+    base = dict(weights=str(ckpt), source=str(src), yaml=None, img_size=[128, 160], conf_thres=0.06, iou_thres=0.45, max_det=20,
+                not_save_img=True, save_txt=True, track=True, track_max_age=2, track_iou=0.25, track_expand=0.25, crop_size=INFER_CROP)
+    base.update(kw)
+    root, out = tmp / tag, {}
+    sets = dict(INFER_SETS, track={})
+    names = (('track',) + tuple(INFER_SETS)) if names is None else tuple(names)
+    assert 'watchlist' not in sets[names[0]] and names[0] not in ('watch', 'live')
+    for name in names + ('all',):
+        s = {k: v for n in INFER_SETS for k, v in sets[n].items()} if name == 'all' else dict(sets[name])
+        if name in ('watch', 'live', 'all'):
+            s['watchlist'] = str(root / 'watch.txt')
+        infer.run(save_dir=str(root / name), **dict(base, **s))
+        out[name] = files_under(root / name)
+        if name == names[0]:
+            reads = [line.split()[4:12] for line in out[name]['plates.txt'].decode().splitlines()]
+            assert reads, 'the run ended no track'
+            rows = [reads[0], ['255'] + reads[-1][1:], [str((int(v) + 5) % 24) for v in reads[0]]]
+            (root / 'watch.txt').write_text('\n'.join(' '.join(r) for r in rows) + '\n')
+    return out
+
+
+def assert_all_on_files(files, what=''):
+    """Every file of every single-feature run is byte-identical in the all-on run (of the hold-only run all but the redacted frames,
+    which the look-back redacts further); every feature left something to compare.  -> {set name: files compared}."""
+    both = files['all']
+    n = {}
+    for name, own in files.items():
+        if name == 'all':
+            continue
+        names = [p for p in own if not (name == 'hold' and p.startswith('redacted' + os.sep))]
+        missing = [p for p in names if p not in both]
+        assert not missing, '%s %s: the all-on run has no %s' % (what, name, missing[:4])
+        differ = [p for p in names if own[p] != both[p]]
+        assert not differ, '%s %s: %d of %d files differ in the all-on run, first %s' % (what, name, len(differ), len(names), sorted(differ)[:4])
+        n[name] = len(names)
+    has = lambda pre: sum(1 for p in both if p.startswith(pre))                 # noqa: E731
+    assert has('shots' + os.sep) >= 1 and has('stacks' + os.sep) >= 1 and has('redacted' + os.sep) == INFER_FRAMES, (what, sorted(both)[:8])
+    assert has(os.path.join('imgs', 'crops') + os.sep) >= INFER_FRAMES // 2
+    for name in ('hits.txt', 'alerts.txt', 'resightings.txt', 'plates.txt', 'tracks.txt', 'shots.txt', 'stacks.txt'):
+        assert both[name].strip(), '%s: %s of the all-on run is empty' % (what, name)
+    return n
+
+
+def all_on_stream_part(out, stream_of, s):
+    """The part of one step's outputs that belongs to stream ``s``: the rows of its frames, its lines of the per-stream outputs and
+    the frames it released; the sightings (one log for all streams) are left out."""
+    rows = [b for b, v in enumerate(stream_of) if v == s]
+    part = {}
+    for k, v in out.items():
+        if k == 'released':
+            part[k] = [(t, g, f) for t, g, f in v if t == s]
+        elif k in ('det_out', 'tid', 'slot', 'det_hold', 'count_hold', 'tid_hold'):
+            part[k] = v[rows]
+        elif k != 'sight_i':
+            part[k] = v[s]
+    return part
