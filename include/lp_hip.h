@@ -732,6 +732,47 @@ int lp_redact_gauss_batch(const lp_redact_desc* desc, int n_frames, const float*
                           const lp_redact_gauss_params* p, int32_t* status /* [n_frames,max_det] */,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* lp_jpeg_encode_batch: complete baseline JPEG files of B frames, written on the device: no pixel crosses PCIe, only the files do.
+ * The reference has nothing here; yolov6/utils/jpeg.py states the format and restates it in numpy byte for byte:
+ * SOF0, 8 bits, 4:2:0 (MCU 16 x 16: four Y blocks, Cb, Cr), the Annex K quantisation tables scaled by quality 1..100 as libjpeg
+ * scales them, the Annex K.3 Huffman tables, restart intervals of `restart` MCUs along the linear MCU order (each byte aligned with
+ * 1-bits, DC predictors 0 at its start, RSTm with m modulo 8 between them), 0x00 after every 0xFF of entropy data, sizes that are
+ * no multiple of 16 padded by replication, SOF0 carrying the true size.
+ *   Sources (the descriptor style of lp_redact_desc, plus the NV12 matrix).  format 0: a BGR frame, uint8 [h0][w0][3], rows pitch0 >=
+ *   3 * w0 bytes apart, any alignment, converted by the integer JFIF rule of jpeg.py.  format 1: an NV12 frame under the plane rules
+ *   of lp_nv12_desc whose matrix is 2 (bt601f): its planes are JFIF already and feed the transform as they are.  Any other matrix
+ *   is LP_ERR_ARG here: convert such a frame with lp_nv12_to_bgr_batch first.  1 <= h0, w0 <= 65535.
+ *   headers (DEVICE) uint8 [n_frames][header_len]: SOI .. SOS of each frame as jpeg.py::jpeg_header makes them (equal lengths; they
+ *   must state the quality and restart of `params`, which the kernels derive their tables from).
+ *   out (DEVICE) uint8 [n_frames][cap], nbytes (DEVICE) int32 [n_frames].  On return out[f][0 .. nbytes[f]) is the whole file,
+ *   EOI included.  A file that needs more than cap bytes leaves nbytes[f] = -needed and writes nothing of frame f; no byte at or
+ *   beyond out[f] + cap is ever written.  1 <= cap < 2^31.
+ *   workspace (DEVICE, 16-byte aligned, lp_jpeg_workspace_bytes): 768 bytes per MCU (the int16 coefficients, 3 bytes per padded
+ *   pixel) + 8 bytes per restart interval (stuffed length, offset), rounded up to 16; it may hold anything on entry.
+ * Four launches per LP_JPEG_PER_LAUNCH frames (lp_jpeg.hip), descriptors and tables by value in the kernel arguments: nothing is
+ * uploaded, no host read, no allocation.  Every argument is checked before the first launch (LP_ERR_ARG names the frame;
+ * nothing is launched or written): null desc, params, headers, out, nbytes; quality outside 1..100; restart outside
+ * 1..LP_JPEG_MAX_RESTART; the frame rules above; cap or header_len < 1; a workspace that is null, misaligned or too small.
+ * n_frames == 0: LP_OK.  lp_jpeg_workspace_bytes returns 0 for arguments lp_jpeg_encode_batch would reject. */
+#define LP_JPEG_MAX_RESTART 32
+#define LP_JPEG_PER_LAUNCH 32
+typedef struct lp_jpeg_desc {
+    const unsigned char* p0;    /* BGR: the frame.  NV12: the luma plane */
+    const unsigned char* p1;    /* BGR: NULL.  NV12: the chroma plane (2-byte aligned, U first) */
+    int pitch0, pitch1;
+    int h0, w0;
+    int format;                 /* 0 BGR, 1 NV12 */
+    int matrix;                 /* NV12: must be 2 (bt601f); BGR: ignored */
+} lp_jpeg_desc;
+typedef struct lp_jpeg_params {
+    int quality;                /* 1..100 */
+    int restart;                /* MCUs per restart interval, 1..LP_JPEG_MAX_RESTART */
+} lp_jpeg_params;
+size_t lp_jpeg_workspace_bytes(const lp_jpeg_desc* desc, int n_frames, int restart);
+int lp_jpeg_encode_batch(const lp_jpeg_desc* desc, int n_frames, const lp_jpeg_params* params, const unsigned char* headers,
+                         int header_len, unsigned char* out, size_t cap, int32_t* nbytes, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* lp_lookback_update: the look-back delay of redaction.  lp_track_update_hold covers a tracked plate from its first detection on; a
  * plate enters the picture small or blurred and is detected a few frames later, and those first frames would be stored readable.
  * A small device-resident delay line keeps, per stream, the redaction rows of the last `depth` frames, adds rows to those past

@@ -10,6 +10,7 @@
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot [--stack]] [--redact [--hold [--lookback D]]] [--nv12]
                                  [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]] [--sightings C]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
+    python tools/frames_bench.py --jpeg Q [--jpeg-frames 4] [--jpeg-restart 16] [--tile-frame 2160 3840] [--nv12 [bt601f]] [--redact]
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
   - frames/s of the per-frame path (upload, lp_preprocess_letterbox, detect at B=1 with hipGraph replay, lp_rescale_round,
@@ -131,6 +132,11 @@ def parse():
     ap.add_argument('--watch-live-min-hits', type=int, default=1, help='with --watch-live: detections a track needs before it is looked up')
     ap.add_argument('--nv12', nargs='?', const='bt709', default=None, choices=['bt601', 'bt709', 'bt601f', 'bt709f'], metavar='MATRIX',
                     help='also send the same seeded frames as NV12 with this matrix and compare (default matrix: bt709)')
+    ap.add_argument('--jpeg', type=int, default=None, metavar='Q', help='measure the JPEG stage instead (also with --nv12 and --redact): '
+                    'runtime.encode_jpeg at quality Q with its reads against D2H + PIL on one thread, on --jpeg-frames frames of --tile-frame '
+                    'and on a batch of 64 crops of 64 x 192')
+    ap.add_argument('--jpeg-frames', type=int, default=4, help='with --jpeg: frames per call')
+    ap.add_argument('--jpeg-restart', type=int, default=16, help='with --jpeg: MCUs per restart interval (1..32)')
     ap.add_argument('--runs', type=int, default=3, help='timed runs of the frames/s figures (the spread is reported)')
     return ap.parse_args()
 
@@ -1101,6 +1107,102 @@ def synthetic_quads(n_frames, n, h0, w0, seed=0):
     return rows
 
 
+def scene_frames(n, h0, w0, seed=0, sigma=6.0):
+    """n seeded BGR frames with the statistics of footage rather than of noise (a JPEG of uniform noise measures nothing): a few
+    low-frequency sinusoids per channel, 40 flat rectangles, and Gaussian sensor noise of ``sigma`` levels."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[:h0, :w0].astype(np.float32)
+    out = []
+    for _ in range(n):
+        img = np.empty((h0, w0, 3), np.float32)
+        for c in range(3):
+            fx, fy, p = rng.uniform(1 / 900, 1 / 90, 3), rng.uniform(1 / 900, 1 / 90, 3), rng.uniform(0, 6.28, 3)
+            img[..., c] = 128 + sum(28 * np.sin(xx * a + yy * b + q) for a, b, q in zip(fx, fy, p))
+        for _ in range(40):
+            y, x = int(rng.integers(0, h0)), int(rng.integers(0, w0))
+            img[y:y + int(rng.integers(8, h0 // 4 + 9)), x:x + int(rng.integers(8, w0 // 4 + 9))] = rng.uniform(0, 255, 3)
+        img += rng.normal(0, sigma, img.shape).astype(np.float32)
+        out.append(np.clip(np.rint(img), 0, 255).astype(np.uint8))
+    return out
+
+
+def jpeg_mode(args, dev):
+    """--jpeg Q: stage ``jpeg`` = runtime.encode_jpeg with its two host reads, wall time with a sync either side; stage
+    ``jpeg_host`` = what a caller has without it, less the PNG's deflate: D2H of the frame, BGR -> RGB, PIL's JPEG at the same
+    quality and subsampling on one thread; both on the same device frames, alternating, the median of --reps, with the bytes per
+    frame of each.  ``device_ms`` = the four launches of encode_jpeg_padded alone from events.  Two workloads: --jpeg-frames frames
+    of --tile-frame (with --nv12 as NV12 planes of that matrix, with --redact after a mosaic on 4 quads per frame), and one
+    [64, 64, 192, 3] crop tensor."""
+    import io
+    import torch
+    from PIL import Image
+    from yolov6.hip import runtime
+    from yolov6.utils.nv12 import bgr_to_nv12_np, nv12_to_bgr_np
+    q, restart, sync = args.jpeg, args.jpeg_restart, torch.cuda.synchronize
+    h0, w0 = args.tile_frame
+    host = scene_frames(args.jpeg_frames, h0, w0)
+    if args.nv12:
+        host_nv = [bgr_to_nv12_np(f[:h0 & ~1, :w0 & ~1], args.nv12) for f in host]
+        frames = [f.to(dev) for f in host_nv]
+    else:
+        frames = [torch.from_numpy(f).to(dev) for f in host]
+    if args.redact:
+        rdet = torch.from_numpy(synthetic_quads(len(frames), 4, h0, w0)).to(dev)
+        runtime.redact_plates(frames, rdet, torch.full((len(frames),), 4, dtype=torch.int32, device=dev), 'mosaic', args.redact_cell)
+    crops = torch.from_numpy(np.stack([f[y:y + 64, x:x + 192] for f in scene_frames(2, 512, 1536, seed=1)
+                                       for y in range(0, 256, 64) for x in range(0, 1536, 192)])).to(dev)
+    assert crops.shape == (64, 64, 192, 3)
+
+    def host_path(fr):
+        sizes = []
+        for f in fr:
+            if args.nv12 and not torch.is_tensor(f):
+                from yolov6.utils.nv12 import Nv12Frame
+                bgr = nv12_to_bgr_np(Nv12Frame(f.y.cpu().numpy(), f.uv.cpu().numpy(), f.matrix))
+            else:
+                bgr = f.cpu().numpy()
+            buf = io.BytesIO()
+            Image.fromarray(np.ascontiguousarray(bgr[:, :, ::-1])).save(buf, format='JPEG', quality=q, subsampling=2)
+            sizes.append(buf.tell())
+        return sizes
+
+    def timed(fn):
+        sync()
+        t0 = time.perf_counter()
+        r = fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e3, r
+
+    out = dict(metric='JPEG stage: frames/s of runtime.encode_jpeg (reads included) against D2H + PIL on one thread', quality=q,
+               restart=restart, reps=args.reps, nv12=args.nv12, redact=bool(args.redact))
+    for name, work, n, hw in (('frames', frames, len(frames), (h0, w0)), ('crops', [crops], 64, (64, 192))):
+        units = list(crops) if name == 'crops' else work
+        t = dict(jpeg=[], jpeg_host=[], device=[])
+        retries0 = runtime.jpeg_stats['retries']
+        for rep in range(args.reps + 1):        # the first repetition warms up both paths and is dropped
+            ms, files = timed(lambda: runtime.encode_jpeg(work, q, restart))
+            t['jpeg'].append(ms)
+            ms, sizes = timed(lambda: host_path(units))
+            t['jpeg_host'].append(ms)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            sync()
+            ev[0].record()
+            runtime.encode_jpeg_padded(work, q, restart)
+            ev[1].record()
+            sync()
+            t['device'].append(ev[0].elapsed_time(ev[1]))
+        med = {k: float(np.median(v[1:])) for k, v in t.items()}
+        src_bytes = hw[0] * hw[1] * (1.5 if args.nv12 and name == 'frames' else 3.0)
+        out[name] = dict(n=n, size=list(hw), jpeg_ms=round(med['jpeg'], 3), jpeg_host_ms=round(med['jpeg_host'], 3),
+                         device_ms=round(med['device'], 3), jpeg_fps=round(n / med['jpeg'] * 1e3, 1),
+                         jpeg_host_fps=round(n / med['jpeg_host'] * 1e3, 1), speedup=round(med['jpeg_host'] / med['jpeg'], 2),
+                         bytes_per_frame=round(float(np.mean([len(f) for f in files])), 1),
+                         bytes_per_frame_host=round(float(np.mean(sizes)), 1), source_MB_per_frame=round(src_bytes / 1e6, 3),
+                         retries=runtime.jpeg_stats['retries'] - retries0)
+    print(json.dumps(out))
+    return out
+
+
 def sampled_rows(h0, rh):
     """Distinct source rows the bilinear resize reads for rh output rows (the y0 / y1 of resize_coef, lp_internal.h)."""
     if rh == h0:
@@ -1125,6 +1227,8 @@ def main():
         raise SystemExit('frames_bench.py measures the GPU path: no GPU')
     dev = torch.device('cuda', 0)
     tdt = {'f16': torch.float16, 'f32': torch.float32}[args.dtype]
+    if args.jpeg is not None:
+        return jpeg_mode(args, dev)
     model = fuse_model(build_synthetic(os.path.join(ROOT, 'configs', args.model + '.py'), sigma=SIGMA[args.model])).eval()
     for layer in model.modules():
         if isinstance(layer, RepVGGBlock):

@@ -13,6 +13,7 @@
                            [--watch-confusable "0D 0Q 8B 2Z 5S" [--watch-confusable-weight 4]]
                            [--watch-live [--watch-live-min-hits 3]]]
                           [--track --sightings C [--sight-window N] [--sight-min-hits 1] [--sight-mismatch 1] [--sight-cost F]]
+                          [--save-jpeg Q]
                           [--tile H W --tile-gate [--tile-gate-thres 2.0] [--tile-gate-min-cells 1] [--tile-gate-refresh 50]
                            [--tile-gate-illum none|gain] [--tile-gate-max-gain 1.5]]
 """
@@ -126,6 +127,9 @@ _FLAGS = [
                                     'an exposure step or a cloud does not run every tile again')),
     ('--tile-gate-max-gain', dict(type=float, default=1.5, metavar='F',
                                   help='with --tile-gate-illum gain: a tile whose gain leaves [1 / F, F] runs again (1..4)')),
+    ('--save-jpeg', dict(type=int, default=None, metavar='Q',
+                         help='write the redacted frames, the crops, the shots and the stacks as baseline JPEG (.jpg) of quality Q '
+                              '(1..100), encoded on the GPU, instead of PNG')),
 ]
 
 
@@ -148,7 +152,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1, redact_lookback=None, redact_lookback_max_back=None,
         redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None, watch_confusable=None, watch_confusable_weight=4,
         watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1, tile_gate_refresh=50,
-        tile_gate_illum='none', tile_gate_max_gain=1.5, sightings=None, sight_window=None, sight_min_hits=1, sight_mismatch=1, sight_cost=None):
+        tile_gate_illum='none', tile_gate_max_gain=1.5, sightings=None, sight_window=None, sight_min_hits=1, sight_mismatch=1, sight_cost=None,
+        save_jpeg=None):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track or redact) and not osp.exists(out_dir):
@@ -171,7 +176,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
                       tile_gate=tile_gate, tile_gate_thres=tile_gate_thres,
                       tile_gate_min_cells=tile_gate_min_cells, tile_gate_refresh=tile_gate_refresh,
                       tile_gate_illum=tile_gate_illum, tile_gate_max_gain=tile_gate_max_gain, sightings=sightings, sight_window=sight_window,
-                      sight_min_hits=sight_min_hits, sight_mismatch=sight_mismatch, sight_cost=sight_cost).infer(
+                      sight_min_hits=sight_min_hits, sight_mismatch=sight_mismatch, sight_cost=sight_cost,
+                      save_jpeg=save_jpeg).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

@@ -51,6 +51,8 @@ from yolov6.utils.nv12 import MATRICES, Nv12Frame, bgr_to_nv12_np, nv12_to_bgr_n
 
 
 class Inferer:
+    JPEG_RESTART = 16       # MCUs per restart interval of the files ``save_jpeg`` writes
+
     def __init__(self, source, weights, device, yaml, img_size, half, batch_size=1, auto=True, tile=None, tile_overlap=0.2,
                  tile_overview=True, merge_metric='iou', track=False, track_max_age=5, track_iou=0.3, track_expand=0.5, best_shots=False,
                  nv12=None, nv12_size=None, redact=None, redact_cell=16, redact_margin=0.1, redact_hold=False, redact_hold_min_hits=1,
@@ -58,7 +60,7 @@ class Inferer:
                  watch_confusable=None, watch_confusable_weight=4, watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0,
                  tile_gate_min_cells=1, tile_gate_refresh=50, tile_gate_illum='none', tile_gate_max_gain=1.5, stack_shots=False,
                  stack_search=2, stack_max_frames=64, stack_min_width=0.0, sightings=None, sight_window=None, sight_min_hits=1,
-                 sight_mismatch=1, sight_cost=None):
+                 sight_mismatch=1, sight_cost=None, save_jpeg=None):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -108,8 +110,15 @@ class Inferer:
         ``tile_gate_refresh`` frames (0: never); the other tiles keep their rows.  Tile groups are then one frame per call.
         ``tile_gate_illum='gain'`` compares the cells after the tile's reference is scaled by one gain per tile (the median of its
         cells' gains), so an exposure step or a cloud does not re-detect everything; a gain outside
-        [1 / ``tile_gate_max_gain``, ``tile_gate_max_gain``] does."""
+        [1 / ``tile_gate_max_gain``, ``tile_gate_max_gain``] does.
+        ``save_jpeg`` = Q in 1..100: the redacted frames, the crops of ``save_crops``, the shots and the stacks are written as
+        baseline JPEG files ``.jpg`` of that quality instead of PNG (``yolov6.utils.jpeg`` states the format): on a GPU by
+        ``runtime.encode_jpeg``, from the device frames where they are there, on the CPU by ``encode_jpeg_np``, the same bytes.
+        ``shots.txt`` and ``stacks.txt`` name the ``.jpg`` files; everything else is what it is without it."""
         self.__dict__.update(locals())
+        if save_jpeg is not None:
+            from yolov6.utils.jpeg import check_params as check_jpeg
+            self.save_jpeg = check_jpeg(save_jpeg, self.JPEG_RESTART, device=True)[0]
         if tile_gate:
             from yolov6.utils.tile_gate import check_illum, check_params as check_gate
             if tile is None:
@@ -238,7 +247,10 @@ class Inferer:
         last frame of a batch; the number of frames for the final flush), counted over the whole source.
 
         With ``redact`` every frame is also written, its plates redacted along the rows returned, as
-        ``<save_dir>/redacted/<image name>`` (``.png`` for a frame of a video or a raw stream)."""
+        ``<save_dir>/redacted/<image name>`` (``.png`` for a frame of a video or a raw stream).
+
+        With ``save_jpeg`` the redacted frames (``redacted/<stem>.jpg``), the crops, the shots and the stacks are ``.jpg`` files of
+        the same stems, and ``shots.txt`` / ``stacks.txt`` name those."""
         self._redacted = deque()
         self._gate = None       # with tile_gate: made at the first frame
         self._gate_gains = []   # with tile_gate_illum='gain': the smallest and largest estimated gain so far (Q12)
@@ -688,24 +700,14 @@ class Inferer:
                     f.write('%d %d %s %d %s %d %d %d %d\n' % (frame, tid, plate_text(best, *names), e, entry_text(entries[e], *names), mism,
                                                               cost, n, hits))
         if self.best_shots:
-            from PIL import Image
-            os.makedirs(osp.join(save_dir, 'shots'), exist_ok=True)
+            names = self._write_track_images(save_dir, 'shots', [s[2] for s in self._track_shots])
             with open(osp.join(save_dir, 'shots.txt'), 'w') as f:
-                for k, ((ri, _), (si, q, crop)) in enumerate(zip(self._track_ended, self._track_shots)):
-                    name = '-'
-                    if crop is not None:
-                        name = osp.join('shots', '%d_%d.png' % (k, ri[0]))
-                        Image.fromarray(np.ascontiguousarray(crop[:, :, ::-1])).save(osp.join(save_dir, name))
+                for (ri, _), (si, q, crop), name in zip(self._track_ended, self._track_shots, names):
                     f.write('%d %d %d %d %d %s\n' % (ri[0], si[0], si[1], si[2], q, name))
         if self.stack_shots:
-            from PIL import Image
-            os.makedirs(osp.join(save_dir, 'stacks'), exist_ok=True)
+            names = self._write_track_images(save_dir, 'stacks', [s[1] for s in self._track_stacks])
             with open(osp.join(save_dir, 'stacks.txt'), 'w') as f:
-                for k, ((ri, _), (ki, crop)) in enumerate(zip(self._track_ended, self._track_stacks)):
-                    name = '-'
-                    if crop is not None:
-                        name = osp.join('stacks', '%d_%d.png' % (k, ri[0]))
-                        Image.fromarray(np.ascontiguousarray(crop[:, :, ::-1])).save(osp.join(save_dir, name))
+                for (ri, _), (ki, crop), name in zip(self._track_ended, self._track_stacks, names):
                     f.write('%d %d %d %d %s\n' % (ri[0], ki[0], ki[1], ki[2], name))
 
     def _frames_ahead(self, prefetch_frames, imread_bgr):
@@ -776,8 +778,11 @@ class Inferer:
                 count = torch.tensor([len(d) for d in dets], dtype=torch.int32).to(self.device)
             dev_frames = list(dev_frames)[:n]
             runtime.redact_plates(dev_frames, det, count, self.redact, self.redact_cell, self.redact_margin, sigma=self.redact_sigma)
-            self._redacted.extend(Nv12Frame(f.y.cpu().numpy(), f.uv.cpu().numpy(), f.matrix) if isinstance(f, Nv12Frame)
-                                  else f.cpu().numpy() for f in dev_frames)
+            if self.save_jpeg is not None:      # the files leave the device, not the frames
+                self._redacted.extend(self._jpeg_files(dev_frames))
+            else:
+                self._redacted.extend(Nv12Frame(f.y.cpu().numpy(), f.uv.cpu().numpy(), f.matrix) if isinstance(f, Nv12Frame)
+                                      else f.cpu().numpy() for f in dev_frames)
         else:
             from yolov6.utils.redact import redact_plates_np
             if hold is not None:
@@ -805,7 +810,9 @@ class Inferer:
 
     def _lookback_collect(self, done):
         for s, _, f in done:
-            if isinstance(f, Nv12Frame) and f.is_tensor:
+            if self.save_jpeg is not None and (f.is_cuda if isinstance(f, Nv12Frame) or torch.is_tensor(f) else False):
+                f = self._jpeg_files([f])[0]
+            elif isinstance(f, Nv12Frame) and f.is_tensor:
                 f = Nv12Frame(f.y.cpu().numpy(), f.uv.cpu().numpy(), f.matrix)
             elif torch.is_tensor(f):
                 f = f.cpu().numpy()
@@ -818,26 +825,74 @@ class Inferer:
 
     def write_redacted(self, img_path, frame, save_dir):
         """One redacted frame (BGR array or host ``Nv12Frame``) as ``<save_dir>/redacted/<image name>``, by the writer of
-        ``save_annotated``; a frame that is no image file (video, raw stream) is named ``<stem>.png``."""
+        ``save_annotated``; a frame that is no image file (video, raw stream) is named ``<stem>.png``.  With ``save_jpeg``:
+        ``redacted/<stem>.jpg``, and ``frame`` may be the finished file (``bytes``)."""
         from PIL import Image
+        os.makedirs(osp.join(save_dir, 'redacted'), exist_ok=True)
+        if self.save_jpeg is not None:      # ``frame`` may be the file already (encoded from the device frame)
+            data = frame if isinstance(frame, bytes) else self._jpeg_files([frame])[0]
+            with open(osp.join(save_dir, 'redacted', osp.splitext(osp.basename(img_path))[0] + '.jpg'), 'wb') as f:
+                f.write(data)
+            return
         if isinstance(frame, Nv12Frame):
             frame = nv12_to_bgr_np(frame)
         name = osp.basename(img_path)
         if self.files.checkext(img_path) != 'image':
             name = osp.splitext(name)[0] + '.png'
-        os.makedirs(osp.join(save_dir, 'redacted'), exist_ok=True)
         Image.fromarray(np.ascontiguousarray(frame[:, :, ::-1])).save(osp.join(save_dir, 'redacted', name))
 
     def write_crops(self, img_path, crops_bgr, save_dir):
         """Plate crops of one image (uint8 [n, h, w, 3] BGR, a tensor or an array) as ``<save_dir>/<rel>/crops/<stem>_<k>.png``, RGB."""
         from PIL import Image
-        if torch.is_tensor(crops_bgr):
-            crops_bgr = crops_bgr.cpu().numpy()
         crop_dir = osp.join(save_dir, osp.relpath(osp.dirname(img_path), osp.dirname(self.source)), 'crops')
         os.makedirs(crop_dir, exist_ok=True)
         stem = osp.splitext(osp.basename(img_path))[0]
+        if self.save_jpeg is not None:
+            for k, data in enumerate(self._jpeg_files(list(crops_bgr))):
+                with open(osp.join(crop_dir, '%s_%d.jpg' % (stem, k)), 'wb') as f:
+                    f.write(data)
+            return
+        if torch.is_tensor(crops_bgr):
+            crops_bgr = crops_bgr.cpu().numpy()
         for k, crop in enumerate(crops_bgr):
             Image.fromarray(np.ascontiguousarray(crop[:, :, ::-1])).save(osp.join(crop_dir, '%s_%d.png' % (stem, k)))
+
+    def _jpeg_files(self, frames):
+        """With ``save_jpeg``: the ``.jpg`` files (``bytes``) of a list of BGR frames or ``Nv12Frame``s, on the host or on the
+        device.  On a GPU host frames are uploaded and every frame goes through ``runtime.encode_jpeg`` in one call; on the
+        CPU each through ``encode_jpeg_np``: the same bytes."""
+        frames = list(frames)
+        if not frames:
+            return []
+        if self.device.type != 'cpu':
+            from yolov6.hip import runtime
+            dev = []
+            for f in frames:
+                if isinstance(f, Nv12Frame):
+                    dev.append(f if f.is_cuda else f.to(self.device))
+                else:
+                    dev.append(f if torch.is_tensor(f) and f.is_cuda else torch.as_tensor(np.ascontiguousarray(f)).to(self.device))
+            return runtime.encode_jpeg(dev, self.save_jpeg, self.JPEG_RESTART)
+        from yolov6.utils.jpeg import encode_jpeg_np
+        return [encode_jpeg_np(f.numpy() if torch.is_tensor(f) else f, self.save_jpeg, self.JPEG_RESTART) for f in frames]
+
+    def _write_track_images(self, save_dir, folder, crops):
+        """The shots or the stacks of the ended tracks (``crops``: a BGR array or None per line of ``plates.txt``) as
+        ``<folder>/<line>_<id>.png`` (``.jpg`` with ``save_jpeg``, all encoded in one call); the relative names, '-' for None."""
+        from PIL import Image
+        os.makedirs(osp.join(save_dir, folder), exist_ok=True)
+        ext = 'png' if self.save_jpeg is None else 'jpg'
+        names = ['-' if crop is None else osp.join(folder, '%d_%d.%s' % (k, ri[0], ext))
+                 for k, ((ri, _), crop) in enumerate(zip(self._track_ended, crops))]
+        live = [(name, crop) for name, crop in zip(names, crops) if crop is not None]
+        if self.save_jpeg is not None:
+            for (name, _), data in zip(live, self._jpeg_files([crop for _, crop in live])):
+                with open(osp.join(save_dir, name), 'wb') as f:
+                    f.write(data)
+        else:
+            for name, crop in live:
+                Image.fromarray(np.ascontiguousarray(crop[:, :, ::-1])).save(osp.join(save_dir, name))
+        return names
 
     @staticmethod
     def save_annotated(img_bgr, rows, save_path):

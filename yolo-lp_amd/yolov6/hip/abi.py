@@ -34,7 +34,8 @@ LP_MERGE_MAX_TILES, LP_MERGE_MAX_CANDIDATES = 64, 16384   # lp_merge_tiles: tile
 LP_TRACK_MAX_TRACKS, LP_TRACK_MAX_DETS, LP_TRACK_MAX_CLS = 128, 128, 64   # lp_track_update: slots per stream, rows per frame, classes per head
 LP_REDACT_MAX_CELL = 64    # lp_redact_plates_batch: largest mosaic cell
 LP_REDACT_MAX_RADIUS = 48  # lp_redact_gauss_batch: largest blur radius (taps per side)
-LP_LOOKBACK_MAX_DEPTH = 32    # lp_lookback_update: frames of delay
+LP_JPEG_MAX_RESTART, LP_JPEG_PER_LAUNCH = 32, 32   # lp_jpeg_encode_batch: MCUs per restart interval, frames per launch
+LP_LOOKBACK_MAX_DEPTH = 32   # lp_lookback_update: frames of delay
 LP_WATCH_MAX_ENTRIES, LP_WATCH_MAX_COST = 1 << 24, 32768   # lp_watch_match: entries of a watchlist, the largest cost of an entry
 LP_WATCH_BLOCK_ENTRIES, LP_WATCH_QUERY_BLOCK = 2048, 16   # ... entries per workgroup of its scan, reads per LDS table
 LP_SIGHT_MAX_CAPACITY = 1 << 24   # lp_sight_update: slots of a log of sightings
@@ -96,6 +97,17 @@ class RedactGaussParams(ctypes.Structure):
     """lp_redact_gauss_params"""
     _fields_ = [('margin', c_double), ('radius', c_int), ('radius_c', c_int), ('taps', ctypes.c_uint16 * (LP_REDACT_MAX_RADIUS + 1)),
                 ('taps_c', ctypes.c_uint16 * (LP_REDACT_MAX_RADIUS + 1))]
+
+
+class JpegDesc(ctypes.Structure):
+    """lp_jpeg_desc"""
+    _fields_ = [('p0', c_void_p), ('p1', c_void_p), ('pitch0', c_int), ('pitch1', c_int), ('h0', c_int), ('w0', c_int),
+                ('format', c_int), ('matrix', c_int)]
+
+
+class JpegParams(ctypes.Structure):
+    """lp_jpeg_params"""
+    _fields_ = [('quality', c_int), ('restart', c_int)]
 
 
 class TileGateDesc(ctypes.Structure):
@@ -210,6 +222,9 @@ SYMBOLS = {
     'lp_redact_gauss_workspace_bytes': (c_size_t, [POINTER(RedactDesc), c_int, POINTER(RedactGaussParams)]),
     'lp_redact_gauss_batch': (c_int, [POINTER(RedactDesc), c_int, c_void_p, c_void_p, c_int, POINTER(RedactGaussParams), c_void_p, c_void_p,
                                       c_size_t, c_void_p]),
+    'lp_jpeg_workspace_bytes': (c_size_t, [POINTER(JpegDesc), c_int, c_int]),
+    'lp_jpeg_encode_batch': (c_int, [POINTER(JpegDesc), c_int, POINTER(JpegParams), c_void_p, c_int, c_void_p, c_size_t, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
     'lp_lookback_state_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'lp_lookback_update': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                    POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
