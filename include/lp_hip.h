@@ -732,6 +732,80 @@ int lp_redact_gauss_batch(const lp_redact_desc* desc, int n_frames, const float*
                           const lp_redact_gauss_params* p, int32_t* status /* [n_frames,max_det] */,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* lp_overlay_draw_batch: draw the detections of B frames onto them IN PLACE -- box outline, corner-quad outline, a label plate and
+ * the label's glyphs (track id and the eight heads' characters) -- in BGR frames or in the planes of NV12 frames (no BGR copy of an
+ * NV12 frame exists); at most LP_FRAMES_PER_LAUNCH frames of one format per launch pair, descriptors, styles and palette by value
+ * in the kernel arguments: nothing is uploaded, no host sync, capturable in a graph.  It goes LAST on a stream: crops and best
+ * shots read the frames first, redaction comes next, the overlay after it, so outlines sit on top of a mosaic.  The reference
+ * draws nothing; yolov6/utils/overlay.py::draw_plates_np restates the rules below byte for byte.
+ *   det [n_frames,max_det,28] fp32 in frame pixels + count [n_frames] int32 (DEVICE).  Rows r < n_b = clamp(count[b], 0, max_det)
+ *   are painted in row order, a later row over an earlier one; a row paints up to four layers in the order box outline, quad
+ *   outline, label plate, label glyphs.  Every layer is a blend that ends in a byte: one call with n rows equals n calls of one row.
+ *   tid [n_frames,max_det] int32 (DEVICE, may be NULL): the track id of a row, < 0 for none.  style [n_frames,max_det] int32
+ *   (DEVICE, may be NULL: style 0): the row's entry of p->styles; < 0 skips the row (status 0); >= n_styles takes the last.
+ *   Which shape: the quad rule of lp_plate_crops_batch.  status [n_frames,max_det] int32: 1 corners: the box outline in the box
+ *   colour (only with p->draw_box and a box, columns 0..3, that is finite with sides >= 1 px), then the quad outline in the quad
+ *   colour; 2 box: the box outline alone, in the box colour, whatever draw_box says; 3: nothing is drawn, no label either; 0 for
+ *   r >= n_b and for a skipped row.
+ *   Outline of thickness t (0: none) of the closed polygon p0 -> p3 -> p2 -> p1 -> p0: pixel (i, j) belongs iff the squared
+ *   distance from its centre P = (j + 0.5, i + 0.5) to any of the four segments is <= (t / 2)^2 (round joins; a zero-length
+ *   segment is a point).  fp64 on the row's fp32 values, op by op (no fused multiply-add), no division; per segment a -> b:
+ *     ex = bx - ax, ey = by - ay, L = ex * ex + ey * ey, dx = px - ax, dy = py - ay, d = dx * ex + dy * ey
+ *     d <= 0: dx * dx + dy * dy <= hw2;  d >= L: fx = px - bx, fy = py - by, fx * fx + fy * fy <= hw2;
+ *     else cr = dx * ey - dy * ex, cr * cr <= hw2 * L;     hw = 0.5 * t, hw2 = hw * hw.
+ *   Scan rectangle: rows [clamp(floor(min y - hw), 0, h0), clamp(ceil(max y + hw), 0, h0)), columns likewise in x and w0 (clamped
+ *   in double, then converted, as lp_redact_plates_batch clamps).
+ *   Label (p->label): glyphs '#', the decimal digits of tid, ' ' (only with tid >= 0 and p->show_id), then for head h = 0..7:
+ *   v = row[20 + h]; glyph_of[h][(int)v] when v is finite and 0 <= v < 64, the '?' glyph otherwise and for an entry >= n_glyphs
+ *   (0xFFFF by convention); at most LP_OVERLAY_MAX_GLYPHS.  atlas (DEVICE) uint8 [n_glyphs][gh][gw] coverage with the fixed
+ *   indices 0..9 digits, 10 '#', 11 ' ', 12 '?'; glyph_of (DEVICE) uint16 [8][64].  W = n * gw + 2 * pad, H = gh + 2 * pad.  With
+ *   the quad's integer bounds bx0 = floor(min x), by0 = floor(min y), by1 = ceil(max y), each clamped to +-2^20 in double and then
+ *   converted, and q = (t + 1) / 2: ly = by0 - q - H, and ly = by1 + q when that is < 0; lx = max(min(bx0, w0 - W), 0).  The
+ *   rectangle [ly, ly + H) x [lx, lx + W) is clipped to the frame.  Plate layer: every pixel of it at coverage 255.  Glyph layer:
+ *   coverage atlas[g_k][i - ly - pad][j - lx - pad - k * gw] for the pixels of cell k.
+ *   Blend of opacity a (0..256) and coverage c (255 for outlines and the plate): w = a * c <= 65280 and, per channel in int32,
+ *   out = (fg * w + dst * (65280 - w) + 32640) / 65280: w = 0 leaves the byte, w = 65280 stores fg exactly.
+ *   NV12: Y per pixel; a chroma sample once per layer with wbar = (w00 + w01 + w10 + w11 + 2) >> 2 over its four luma pixels,
+ *   U and V separately.  Colours are bytes in the frame's own format: (B,G,R), or (Y,U,V); no matrix plays a part.
+ *   Palette: a row with tid >= 0 takes palette[tid % n_palette] as its quad and plate colours (n_palette 0: none).
+ *   No other byte changes: pitch padding, pixels of no layer, rows at or past n_b, frames whose count is <= 0.
+ * Two kernels per launch pair (lp_overlay.hip): the first, a thread per (frame, row), writes a fixed-size record and a bounding
+ * rectangle per row into the workspace, and status; the second, a 256-thread workgroup per frame-anchored 32 x 32 tile and a thread
+ * per 2 x 2 pixel block, culls the rows against its tile into an LDS list in row order, returns before reading a pixel when the
+ * list is empty, and otherwise loads its block once, blends the listed rows in order in registers and stores the block once: every
+ * pixel has one owner, so the in-place painter's order needs no atomics.  The workspace may hold anything on entry.
+ * Every argument is checked before the first launch (LP_ERR_ARG names the frame; nothing is launched): whatever
+ * lp_redact_plates_batch rejects for descriptors, det, count, status and max_det; null p, atlas or glyph_of; n_styles outside
+ * 1..LP_OVERLAY_MAX_STYLES; t or pad outside 0..16 or an opacity outside 0..256 in a used style; n_palette outside
+ * 0..LP_OVERLAY_MAX_PALETTE; n_glyphs outside 13..LP_OVERLAY_MAX_ATLAS; gh or gw outside 1..LP_OVERLAY_MAX_CELL; a workspace that is
+ * null, not 16-byte aligned or smaller than lp_overlay_workspace_bytes.  n_frames == 0: LP_OK. */
+#define LP_OVERLAY_MAX_STYLES 8
+#define LP_OVERLAY_MAX_GLYPHS 20
+#define LP_OVERLAY_MAX_THICKNESS 16
+#define LP_OVERLAY_MAX_PAD 16
+#define LP_OVERLAY_MAX_PALETTE 64
+#define LP_OVERLAY_MAX_ATLAS 1024
+#define LP_OVERLAY_MAX_CELL 64
+typedef struct lp_overlay_style {
+    unsigned char box[3], quad[3], plate[3], text[3];   /* the colours of the four layers, bytes in the frame's own format */
+    int t;                                              /* outline thickness in pixels, 0..16 (0: no outline) */
+    int a_line, a_plate, a_text;                        /* opacity 0..256 of the outlines, the label plate, the glyphs */
+    int pad;                                            /* pixels between the label's edge and its glyphs, 0..16 */
+} lp_overlay_style;
+typedef struct lp_overlay_params {
+    int n_styles;                                       /* 1..LP_OVERLAY_MAX_STYLES */
+    lp_overlay_style styles[LP_OVERLAY_MAX_STYLES];
+    int n_palette;                                      /* 0..LP_OVERLAY_MAX_PALETTE */
+    unsigned char palette[LP_OVERLAY_MAX_PALETTE][3];
+    int n_glyphs, gh, gw;                               /* the atlas: [n_glyphs][gh][gw] */
+    int show_id, label, draw_box;                       /* booleans */
+} lp_overlay_params;
+size_t lp_overlay_workspace_bytes(int n_frames, int max_det);      /* 288 bytes per (frame, row); 0 for bad arguments */
+int lp_overlay_draw_batch(const lp_redact_desc* desc, int n_frames, const float* det, const int32_t* count, int max_det,
+                          const int32_t* tid /* may be NULL */, const int32_t* style /* may be NULL */, const lp_overlay_params* p,
+                          const unsigned char* atlas, const uint16_t* glyph_of, int32_t* status /* [n_frames,max_det] */,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* lp_jpeg_encode_batch: complete baseline JPEG files of B frames, written on the device: no pixel crosses PCIe, only the files do.
  * The reference has nothing here; yolov6/utils/jpeg.py states the format and restates it in numpy byte for byte:
  * SOF0, 8 bits, 4:2:0 (MCU 16 x 16: four Y blocks, Cb, Cr), the Annex K quantisation tables scaled by quality 1..100 as libjpeg

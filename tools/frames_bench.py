@@ -11,6 +11,7 @@
                                  [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]] [--sightings C]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
     python tools/frames_bench.py --jpeg Q [--jpeg-frames 4] [--jpeg-restart 16] [--tile-frame 2160 3840] [--nv12 [bt601f]] [--redact]
+    python tools/frames_bench.py --annotate [--annotate-plates N] [--jpeg-frames 4] [--tile-frame 2160 3840] [--nv12 [bt601f]]
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
   - frames/s of the per-frame path (upload, lp_preprocess_letterbox, detect at B=1 with hipGraph replay, lp_rescale_round,
@@ -135,7 +136,11 @@ def parse():
     ap.add_argument('--jpeg', type=int, default=None, metavar='Q', help='measure the JPEG stage instead (also with --nv12 and --redact): '
                     'runtime.encode_jpeg at quality Q with its reads against D2H + PIL on one thread, on --jpeg-frames frames of --tile-frame '
                     'and on a batch of 64 crops of 64 x 192')
-    ap.add_argument('--jpeg-frames', type=int, default=4, help='with --jpeg: frames per call')
+    ap.add_argument('--jpeg-frames', type=int, default=4, help='with --jpeg or --annotate: frames per call')
+    ap.add_argument('--annotate', action='store_true', help='measure the overlay stage instead (also with --nv12): runtime.draw_plates on '
+                    '--jpeg-frames frames of --tile-frame with 0, 4 and 64 plates per frame, against D2H + PIL drawing on one thread and '
+                    'against the JPEG encode of the same frames')
+    ap.add_argument('--annotate-plates', type=int, default=None, metavar='N', help='with --annotate: only N plates per frame')
     ap.add_argument('--jpeg-restart', type=int, default=16, help='with --jpeg: MCUs per restart interval (1..32)')
     ap.add_argument('--runs', type=int, default=3, help='timed runs of the frames/s figures (the spread is reported)')
     return ap.parse_args()
@@ -1203,6 +1208,103 @@ def jpeg_mode(args, dev):
     return out
 
 
+def annotate_mode(args, dev):
+    """--annotate: stage ``overlay`` = runtime.draw_plates on --jpeg-frames frames of --tile-frame (with --nv12 as NV12 planes) with
+    0, 4 and 64 plates per frame (--annotate-plates N: that many), from device events, the frames restored outside the window; beside
+    it, on the same frames in the same run and alternating with it: ``host`` = what a caller has without it, D2H of the frame plus
+    the PIL drawing of ``Inferer.save_annotated`` on one thread, no file write (wall clock); and ``jpeg`` = the launches of
+    ``runtime.encode_jpeg_padded`` of the annotated frames (events).  The median of --reps after one dropped warm-up repetition.
+    ``overlay_device`` = the two launches alone: the call captured in a graph, 50 replays between two events (from the second
+    replay on the frames are drawn on already; the work is the same), so the wrapper's host time is out."""
+    import torch
+    from PIL import Image, ImageDraw
+    from yolov6.hip import runtime
+    from yolov6.utils.nv12 import Nv12Frame, bgr_to_nv12_np, nv12_to_bgr_np
+    from yolov6.utils.overlay import Style, build_atlas
+    sync = torch.cuda.synchronize
+    h0, w0 = args.tile_frame
+    nf = args.jpeg_frames
+    host = scene_frames(nf, h0, w0)
+    if args.nv12:
+        clean = [bgr_to_nv12_np(f[:h0 & ~1, :w0 & ~1], args.nv12).to(dev) for f in host]
+        work = [Nv12Frame(f.y.clone(), f.uv.clone(), f.matrix) for f in clean]
+    else:
+        clean = [torch.from_numpy(f).to(dev) for f in host]
+        work = [f.clone() for f in clean]
+    names = [chr(65 + k) for k in range(26)] + [str(k) for k in range(10)]
+    font = runtime.OverlayFont(*build_atlas(names[:31], names[:24], names, size=24), device=dev)
+    styles = [Style(t=2, a_line=256, a_plate=160, a_text=256, pad=3)]
+    palette = np.array([[40, 40, 200], [40, 140, 40], [200, 80, 40], [20, 140, 200]], np.uint8)
+
+    def restore():
+        for w, c in zip(work, clean):
+            if args.nv12:
+                w.y.copy_(c.y)
+                w.uv.copy_(c.uv)
+            else:
+                w.copy_(c)
+
+    def events(fn):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        sync()
+        ev[0].record()
+        fn()
+        ev[1].record()
+        sync()
+        return ev[0].elapsed_time(ev[1])
+
+    def host_path(rows):
+        for f, rr in zip(work, rows):
+            if args.nv12:
+                bgr = nv12_to_bgr_np(Nv12Frame(f.y.cpu().numpy(), f.uv.cpu().numpy(), f.matrix))
+            else:
+                bgr = f.cpu().numpy()
+            im = Image.fromarray(np.ascontiguousarray(bgr[:, :, ::-1]))
+            draw = ImageDraw.Draw(im)
+            for r in rr:                                            # Inferer.save_annotated, less the file
+                draw.rectangle([float(v) for v in r[:4]], outline=(255, 64, 64), width=2)
+                draw.polygon([float(v) for v in r[4:12]], outline=(64, 255, 64))
+
+    out = dict(metric='overlay stage: ms per frame of runtime.draw_plates against D2H + PIL drawing on one thread, and the JPEG encode behind it',
+               frame=[h0, w0], frames=nf, reps=args.reps, nv12=args.nv12, glyph=[font.gh, font.gw])
+    plates = [args.annotate_plates] if args.annotate_plates is not None else [0, 4, 64]
+    rng = np.random.default_rng(7)
+    for P in plates:
+        rows = synthetic_quads(nf, max(P, 1), h0, w0, seed=P)
+        rows[:, :, 20:28] = rng.integers(0, 24, rows[:, :, 20:28].shape)
+        det = torch.from_numpy(rows).to(dev)
+        count = torch.full((nf,), P, dtype=torch.int32, device=dev)
+        tid = torch.arange(nf * max(P, 1), dtype=torch.int32, device=dev).view(nf, -1).contiguous()
+        t = dict(overlay=[], host=[], jpeg=[])
+        for rep in range(args.reps + 1):                            # the first repetition warms up every path and is dropped
+            restore()
+            t['overlay'].append(events(lambda: runtime.draw_plates(work, det, count, font, tid=tid, styles=styles, palette=palette)))
+            t['jpeg'].append(events(lambda: runtime.encode_jpeg_padded(work, 90, 16)))
+            restore()
+            sync()
+            t0 = time.perf_counter()
+            host_path(rows[:, :P])
+            t['host'].append((time.perf_counter() - t0) * 1e3)
+        # the two launches alone: the call captured in a graph, 50 replays between two events (the wrapper's host time is out)
+        draw = lambda: runtime.draw_plates(work, det, count, font, tid=tid, styles=styles, palette=palette)      # noqa: E731
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            draw()
+        dev_ms = []
+        for rep in range(4):
+            restore()
+            dev_ms.append(events(lambda: [g.replay() for _ in range(50)]) / 50)
+        med = {k: float(np.median(v[1:])) / nf for k, v in t.items()}
+        out['plates_%d' % P] = dict(overlay_ms_per_frame=round(med['overlay'], 4), host_ms_per_frame=round(med['host'], 3),
+                                    jpeg_ms_per_frame=round(med['jpeg'], 4),
+                                    overlay_device_ms_per_frame=round(float(np.median(dev_ms[1:])) / nf, 5),
+                                    overlay_runs_ms=[round(v / nf, 4) for v in t['overlay'][1:]],
+                                    overlay_over_jpeg=round(med['overlay'] / med['jpeg'], 4),
+                                    host_over_overlay=round(med['host'] / med['overlay'], 1))
+    print(json.dumps(out))
+    return out
+
+
 def sampled_rows(h0, rh):
     """Distinct source rows the bilinear resize reads for rh output rows (the y0 / y1 of resize_coef, lp_internal.h)."""
     if rh == h0:
@@ -1229,6 +1331,8 @@ def main():
     tdt = {'f16': torch.float16, 'f32': torch.float32}[args.dtype]
     if args.jpeg is not None:
         return jpeg_mode(args, dev)
+    if args.annotate:
+        return annotate_mode(args, dev)
     model = fuse_model(build_synthetic(os.path.join(ROOT, 'configs', args.model + '.py'), sigma=SIGMA[args.model])).eval()
     for layer in model.modules():
         if isinstance(layer, RepVGGBlock):

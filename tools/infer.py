@@ -14,6 +14,7 @@
                            [--watch-live [--watch-live-min-hits 3]]]
                           [--track --sightings C [--sight-window N] [--sight-min-hits 1] [--sight-mismatch 1] [--sight-cost F]]
                           [--save-jpeg Q]
+                          [--overlay [--overlay-font TTF] [--overlay-size 24] [--overlay-thickness 2] [--overlay-alpha 256 160 256]]
                           [--tile H W --tile-gate [--tile-gate-thres 2.0] [--tile-gate-min-cells 1] [--tile-gate-refresh 50]
                            [--tile-gate-illum none|gain] [--tile-gate-max-gain 1.5]]
 """
@@ -130,6 +131,15 @@ _FLAGS = [
     ('--save-jpeg', dict(type=int, default=None, metavar='Q',
                          help='write the redacted frames, the crops, the shots and the stacks as baseline JPEG (.jpg) of quality Q '
                               '(1..100), encoded on the GPU, instead of PNG')),
+    ('--overlay', dict(action='store_true', help='also write every frame with box, corner quad and a label (track id with --track, '
+                                                 'the eight characters) drawn on it, on the GPU, to annotated/ (.jpg with --save-jpeg)')),
+    ('--overlay-font', dict(type=str, default=None, metavar='TTF',
+                            help='with --overlay: TrueType file of the label glyphs (default: PIL\'s built-in font, without CJK: the '
+                                 'province then shows ?)')),
+    ('--overlay-size', dict(type=int, default=24, metavar='PX', help='with --overlay: glyph size in pixels (4..60)')),
+    ('--overlay-thickness', dict(type=int, default=2, metavar='N', help='with --overlay: outline thickness in pixels (0..16)')),
+    ('--overlay-alpha', dict(nargs=3, type=int, default=[256, 160, 256], metavar=('L', 'P', 'T'),
+                             help='with --overlay: opacity 0..256 of the outlines, the label plate and the text')),
 ]
 
 
@@ -153,10 +163,10 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         redact_sigma=8.0, watchlist=None, watch_mismatch=1, watch_cost=None, watch_confusable=None, watch_confusable_weight=4,
         watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1, tile_gate_refresh=50,
         tile_gate_illum='none', tile_gate_max_gain=1.5, sightings=None, sight_window=None, sight_min_hits=1, sight_mismatch=1, sight_cost=None,
-        save_jpeg=None):
+        save_jpeg=None, overlay=False, overlay_font=None, overlay_size=24, overlay_thickness=2, overlay_alpha=(256, 160, 256)):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
-    if (save_img or save_txt or save_crops or track or redact) and not osp.exists(out_dir):
+    if (save_img or save_txt or save_crops or track or redact or overlay) and not osp.exists(out_dir):
         os.makedirs(out_dir)
     else:
         LOGGER.warning('Save directory already existed')
@@ -177,7 +187,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
                       tile_gate_min_cells=tile_gate_min_cells, tile_gate_refresh=tile_gate_refresh,
                       tile_gate_illum=tile_gate_illum, tile_gate_max_gain=tile_gate_max_gain, sightings=sightings, sight_window=sight_window,
                       sight_min_hits=sight_min_hits, sight_mismatch=sight_mismatch, sight_cost=sight_cost,
-                      save_jpeg=save_jpeg).infer(
+                      save_jpeg=save_jpeg, overlay=overlay, overlay_font=overlay_font, overlay_size=overlay_size,
+                      overlay_thickness=overlay_thickness, overlay_alpha=tuple(overlay_alpha)).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

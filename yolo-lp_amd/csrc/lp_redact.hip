@@ -445,6 +445,9 @@ void launch_gauss(const RdTable& tab, int nf, const GsTaps& tp, const float* det
 
 }  // namespace
 
+// the descriptor rules for the other entry points that take lp_redact_desc (lp_overlay.hip)
+std::string redact_desc_fault(const lp_redact_desc& d) { return desc_fault(d); }
+
 }  // namespace lp
 
 using namespace lp;

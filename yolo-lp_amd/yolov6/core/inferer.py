@@ -32,6 +32,9 @@ covered too (``runtime.LookbackRedactor`` on a GPU, ``LookbackNp`` on the CPU; `
 With ``tile`` and ``tile_gate`` the source is taken as one fixed camera: a tile whose pixels have not changed since it was last
 detected is not run through the network again, its rows come from a cache (``runtime.TileGate`` on a GPU, ``TileGateNp`` on the
 CPU; ``yolov6.utils.tile_gate`` states the rule).
+With ``overlay`` every frame is also written with its rows drawn on it -- box, corner quad, a label with the track id and the eight
+characters -- to ``<save_dir>/annotated/`` (``runtime.draw_plates`` on a clone of the device frame on a GPU, ``draw_plates_np`` on
+the CPU; ``yolov6.utils.overlay`` states the rule); ``save_annotated`` and the images of ``save_img`` are what they are without it.
 """
 import math
 import os
@@ -60,7 +63,8 @@ class Inferer:
                  watch_confusable=None, watch_confusable_weight=4, watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0,
                  tile_gate_min_cells=1, tile_gate_refresh=50, tile_gate_illum='none', tile_gate_max_gain=1.5, stack_shots=False,
                  stack_search=2, stack_max_frames=64, stack_min_width=0.0, sightings=None, sight_window=None, sight_min_hits=1,
-                 sight_mismatch=1, sight_cost=None, save_jpeg=None):
+                 sight_mismatch=1, sight_cost=None, save_jpeg=None, overlay=False, overlay_font=None, overlay_size=24, overlay_thickness=2,
+                 overlay_alpha=(256, 160, 256)):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -114,8 +118,22 @@ class Inferer:
         ``save_jpeg`` = Q in 1..100: the redacted frames, the crops of ``save_crops``, the shots and the stacks are written as
         baseline JPEG files ``.jpg`` of that quality instead of PNG (``yolov6.utils.jpeg`` states the format): on a GPU by
         ``runtime.encode_jpeg``, from the device frames where they are there, on the CPU by ``encode_jpeg_np``, the same bytes.
-        ``shots.txt`` and ``stacks.txt`` name the ``.jpg`` files; everything else is what it is without it."""
+        ``shots.txt`` and ``stacks.txt`` name the ``.jpg`` files; everything else is what it is without it.
+        ``overlay``: ``infer`` also writes every frame with its detections drawn on it -- box, corner quad and a label with the
+        track id (with ``track``) and the eight characters (the voted read with ``track``) -- as ``annotated/<image name>``
+        (``annotated/<stem>.jpg`` with ``save_jpeg``; ``yolov6.utils.overlay`` states the rules).  On a GPU the drawing is
+        ``runtime.draw_plates`` on a clone of the device frame, behind the redaction where that is on, so outlines sit on a
+        mosaic and the group's other consumers see the frame without them; on the CPU ``draw_plates_np``, the same bytes.  The glyphs are
+        rendered once on the host from the yaml's names at ``overlay_size`` pixels with the TrueType file ``overlay_font`` (None:
+        PIL's default font, which has no CJK glyphs: the province then shows '?'); ``overlay_thickness`` is the outlines' width
+        (0..16), ``overlay_alpha`` the opacities 0..256 of outlines, label plate and text.  With ``redact_hold`` the predicted rows
+        of missed tracks are drawn in a second style.  Not with ``redact_lookback`` (the frame drawn on would not be redacted yet)."""
         self.__dict__.update(locals())
+        self._overlay = None
+        if overlay:
+            if redact_lookback is not None:
+                raise ValueError('overlay does not go with redact_lookback: the frame is redacted frames later')
+            self._overlay_styles = self.make_overlay_styles(overlay_size, overlay_thickness, overlay_alpha)
         if save_jpeg is not None:
             from yolov6.utils.jpeg import check_params as check_jpeg
             self.save_jpeg = check_jpeg(save_jpeg, self.JPEG_RESTART, device=True)[0]
@@ -183,6 +201,10 @@ class Inferer:
         self.pro_names = names.get('names')
         self.alp_names = names.get('alps')
         self.ads_names = names.get('ads')
+        if overlay:
+            from yolov6.utils.overlay import build_atlas
+            self._overlay = build_atlas(self.pro_names or [], self.alp_names or [], self.ads_names or [], overlay_size, overlay_font)
+            self._overlay_dev = None        # runtime.OverlayFont: uploaded with the first group
         self.img_size = self.check_img_size(self.img_size, s=self.stride)
         self.half = half
 
@@ -250,8 +272,12 @@ class Inferer:
         ``<save_dir>/redacted/<image name>`` (``.png`` for a frame of a video or a raw stream).
 
         With ``save_jpeg`` the redacted frames (``redacted/<stem>.jpg``), the crops, the shots and the stacks are ``.jpg`` files of
-        the same stems, and ``shots.txt`` / ``stacks.txt`` name those."""
+        the same stems, and ``shots.txt`` / ``stacks.txt`` name those.
+
+        With ``overlay`` every frame is also written with its rows drawn on it as ``<save_dir>/annotated/<image name>``
+        (``annotated/<stem>.jpg`` with ``save_jpeg``)."""
         self._redacted = deque()
+        self._annotated = deque()
         self._gate = None       # with tile_gate: made at the first frame
         self._gate_gains = []   # with tile_gate_illum='gain': the smallest and largest estimated gain so far (Q12)
         if self.track:
@@ -272,6 +298,8 @@ class Inferer:
                 results.append(det)
                 if self.redact is not None and self.redact_lookback is None:
                     self.write_redacted(img_path, self._redacted.popleft(), save_dir)
+                if self._overlay is not None:
+                    self.write_redacted(img_path, self._annotated.popleft(), save_dir, 'annotated')
                 if self.track:
                     self._track_lines += ['%s %d %d' % (img_path, r, t) for r, t in enumerate(self._track_tids.popleft().tolist())]
             self._write_delayed(save_dir)
@@ -338,6 +366,7 @@ class Inferer:
                     from yolov6.utils.plate_crop import plate_crops_np
                     crops = [plate_crops_np(img_src, det.detach().float().cpu().numpy(), crop_size)[0]]
             self._redact_group([img_src if img_nv12 is None else img_nv12], [det], [frame] if gpu else None)     # last: it writes the frame
+            self._overlay_group([img_src if img_nv12 is None else img_nv12], [det], [frame] if gpu else None)
             yield [(img_src, img_path)], [det], crops, seconds
 
     def _gpu_groups(self, conf_thres, iou_thres, max_det, save_crops, crop_size):
@@ -437,6 +466,7 @@ class Inferer:
             else:
                 dets, crops = detect(self.model.model, dev_frames, self.img_size, conf_thres, iou_thres, max_det, **kw), None
             self._redact_group([f for f, _ in items], dets, dev_frames)     # behind the crops and the shots, before the next put
+            self._overlay_group([f for f, _ in items], dets, dev_frames, (det, count, tid) if self.track else None)    # behind the redaction, on clones
             yield items, dets, crops, time.time() - t1
 
     def tiled_rows_cpu(self, img_src, conf_thres, iou_thres, classes, agnostic_nms, max_det, border=1):
@@ -794,6 +824,76 @@ class Inferer:
             self._redacted.extend(redact_plates_np(list(frames), det, count, self.redact, self.redact_cell, self.redact_margin,
                                                    sigma=self.redact_sigma)[0])
 
+    #: with ``overlay`` and ``track``: quad and label plate take OVERLAY_PALETTE[track id % 8], (B, G, R)
+    OVERLAY_PALETTE = ((40, 40, 200), (40, 140, 40), (200, 80, 40), (20, 140, 200), (160, 40, 160), (140, 140, 20), (90, 90, 90), (30, 80, 140))
+
+    @staticmethod
+    def make_overlay_styles(size, thickness, alpha):
+        """The two styles of ``overlay``: 0 for a frame's own rows, 1 (another box and quad colour) for the rows ``redact_hold``
+        predicts for missed tracks.  ``alpha`` = (outlines, label plate, text), 0..256."""
+        from yolov6.utils.overlay import Style, check_styles
+        a_line, a_plate, a_text = (int(v) for v in alpha)
+        base = Style(t=int(thickness), a_line=a_line, a_plate=a_plate, a_text=a_text, pad=max(1, min(16, int(size) // 8)))
+        return check_styles([base, base._replace(box=(0, 128, 255), quad=(0, 128, 255))])
+
+    def _overlay_group(self, frames, dets, dev_frames=None, dev_rows=None):
+        """With ``overlay``: queue for ``infer`` the frames of one group with their final rows ``dets`` drawn on them, right behind
+        ``_redact_group``.  On a GPU clones of ``dev_frames`` (redacted already where ``redact`` is on) are drawn on
+        (``runtime.draw_plates``) and either encoded there (``save_jpeg``: only the files leave the device) or read back; on the
+        CPU ``draw_plates_np`` draws on the redacted copies, or on ``frames``.  With ``track`` the label carries the track id and the
+        voted read: ``dev_rows`` = (det_out, count, tid) where the group's tracker update left them on the device, else the rows
+        are padded from ``dets`` and the ids queued for ``tracks.txt``.  With ``redact_hold`` the rows and ids are ``last_hold``'s,
+        taken where they lie, the predicted ones -- arange(rows) >= count -- in style 1."""
+        if self._overlay is None:
+            return
+        n = len(frames)
+        hold = self._tracker.last_hold if self.redact_hold else None
+        rows = int(hold[0].shape[1]) if hold is not None else max([len(d) for d in dets] + [1])
+        counts = np.array([len(d) for d in dets], np.int32)
+        tid = None
+        if hold is not None:
+            tid = hold[2]
+        elif self.track and dev_rows is None:
+            tid = np.full((n, rows), -1, np.int32)
+            for k, t in enumerate(list(self._track_tids)[-n:]):
+                tid[k, :len(t)] = t
+        kw = dict(styles=self._overlay_styles, palette=np.array(self.OVERLAY_PALETTE, np.uint8) if self.track else None)
+        if dev_frames is not None:
+            from yolov6.hip import runtime
+            if self._overlay_dev is None:
+                self._overlay_dev = runtime.OverlayFont(*self._overlay, device=self.device)
+            if hold is not None:
+                own = torch.from_numpy(counts).to(self.device)
+                kw['style'] = (torch.arange(rows, device=self.device)[None, :] >= own[:, None]).to(torch.int32).contiguous()
+                det, count = hold[0], hold[1]       # on the device: no host read, no copy
+            elif dev_rows is not None:
+                det, count, tid = dev_rows
+            else:
+                det = torch.zeros(n, rows, 28, dtype=torch.float32, device=self.device)
+                for k, d in enumerate(dets):
+                    det[k, :len(d)] = d
+                count = torch.from_numpy(counts).to(self.device)
+            if tid is not None:
+                kw['tid'] = tid if torch.is_tensor(tid) else torch.from_numpy(tid).to(self.device)
+            clones = [Nv12Frame(f.y.clone(), f.uv.clone(), f.matrix) if isinstance(f, Nv12Frame) else f.clone() for f in list(dev_frames)[:n]]
+            runtime.draw_plates(clones, det, count, self._overlay_dev, **kw)
+            if self.save_jpeg is not None:      # the files leave the device, not the frames
+                self._annotated.extend(self._jpeg_files(clones))
+            else:
+                self._annotated.extend(Nv12Frame(f.y.cpu().numpy(), f.uv.cpu().numpy(), f.matrix) if isinstance(f, Nv12Frame)
+                                       else f.cpu().numpy() for f in clones)
+        else:
+            from yolov6.utils.overlay import draw_plates_np
+            base = list(self._redacted)[-n:] if self.redact is not None else list(frames)
+            if hold is not None:
+                det, count = hold[0], hold[1]
+                kw['style'] = (np.arange(rows)[None, :] >= counts[:, None]).astype(np.int32)
+            else:
+                det, count = np.zeros((n, rows, 28), np.float32), counts
+                for k, d in enumerate(dets):
+                    det[k, :len(d)] = d.detach().float().cpu().numpy()
+            self._annotated.extend(draw_plates_np(base, det, count, *self._overlay, tid=tid, **kw)[0])
+
     def _redact_delayed(self, frames, dev_frames=None):
         """With ``redact_lookback``: hand the group's frames to the delay line behind the group's tracker update and queue, with
         their paths, the frames that leave it (host BGR arrays or host ``Nv12Frame``s).  On a GPU the device frames are copied
@@ -823,15 +923,16 @@ class Inferer:
         while self.redact_lookback is not None and self._redacted:
             self.write_redacted(*self._redacted.popleft(), save_dir)
 
-    def write_redacted(self, img_path, frame, save_dir):
+    def write_redacted(self, img_path, frame, save_dir, folder='redacted'):
         """One redacted frame (BGR array or host ``Nv12Frame``) as ``<save_dir>/redacted/<image name>``, by the writer of
         ``save_annotated``; a frame that is no image file (video, raw stream) is named ``<stem>.png``.  With ``save_jpeg``:
-        ``redacted/<stem>.jpg``, and ``frame`` may be the finished file (``bytes``)."""
+        ``redacted/<stem>.jpg``, and ``frame`` may be the finished file (``bytes``).  ``folder``: 'annotated' for the frames
+        of ``overlay``, written the same way."""
         from PIL import Image
-        os.makedirs(osp.join(save_dir, 'redacted'), exist_ok=True)
+        os.makedirs(osp.join(save_dir, folder), exist_ok=True)
         if self.save_jpeg is not None:      # ``frame`` may be the file already (encoded from the device frame)
             data = frame if isinstance(frame, bytes) else self._jpeg_files([frame])[0]
-            with open(osp.join(save_dir, 'redacted', osp.splitext(osp.basename(img_path))[0] + '.jpg'), 'wb') as f:
+            with open(osp.join(save_dir, folder, osp.splitext(osp.basename(img_path))[0] + '.jpg'), 'wb') as f:
                 f.write(data)
             return
         if isinstance(frame, Nv12Frame):
@@ -839,7 +940,7 @@ class Inferer:
         name = osp.basename(img_path)
         if self.files.checkext(img_path) != 'image':
             name = osp.splitext(name)[0] + '.png'
-        Image.fromarray(np.ascontiguousarray(frame[:, :, ::-1])).save(osp.join(save_dir, 'redacted', name))
+        Image.fromarray(np.ascontiguousarray(frame[:, :, ::-1])).save(osp.join(save_dir, folder, name))
 
     def write_crops(self, img_path, crops_bgr, save_dir):
         """Plate crops of one image (uint8 [n, h, w, 3] BGR, a tensor or an array) as ``<save_dir>/<rel>/crops/<stem>_<k>.png``, RGB."""

@@ -34,6 +34,7 @@ LP_MERGE_MAX_TILES, LP_MERGE_MAX_CANDIDATES = 64, 16384   # lp_merge_tiles: tile
 LP_TRACK_MAX_TRACKS, LP_TRACK_MAX_DETS, LP_TRACK_MAX_CLS = 128, 128, 64   # lp_track_update: slots per stream, rows per frame, classes per head
 LP_REDACT_MAX_CELL = 64    # lp_redact_plates_batch: largest mosaic cell
 LP_REDACT_MAX_RADIUS = 48  # lp_redact_gauss_batch: largest blur radius (taps per side)
+LP_OVERLAY_MAX_STYLES, LP_OVERLAY_MAX_GLYPHS, LP_OVERLAY_MAX_PALETTE = 8, 20, 64   # lp_overlay_draw_batch: styles, glyphs of a label, palette entries
 LP_JPEG_MAX_RESTART, LP_JPEG_PER_LAUNCH = 32, 32   # lp_jpeg_encode_batch: MCUs per restart interval, frames per launch
 LP_LOOKBACK_MAX_DEPTH = 32   # lp_lookback_update: frames of delay
 LP_WATCH_MAX_ENTRIES, LP_WATCH_MAX_COST = 1 << 24, 32768   # lp_watch_match: entries of a watchlist, the largest cost of an entry
@@ -97,6 +98,19 @@ class RedactGaussParams(ctypes.Structure):
     """lp_redact_gauss_params"""
     _fields_ = [('margin', c_double), ('radius', c_int), ('radius_c', c_int), ('taps', ctypes.c_uint16 * (LP_REDACT_MAX_RADIUS + 1)),
                 ('taps_c', ctypes.c_uint16 * (LP_REDACT_MAX_RADIUS + 1))]
+
+
+class OverlayStyle(ctypes.Structure):
+    """lp_overlay_style"""
+    _fields_ = [('box', ctypes.c_ubyte * 3), ('quad', ctypes.c_ubyte * 3), ('plate', ctypes.c_ubyte * 3), ('text', ctypes.c_ubyte * 3),
+                ('t', c_int), ('a_line', c_int), ('a_plate', c_int), ('a_text', c_int), ('pad', c_int)]
+
+
+class OverlayParams(ctypes.Structure):
+    """lp_overlay_params"""
+    _fields_ = [('n_styles', c_int), ('styles', OverlayStyle * LP_OVERLAY_MAX_STYLES), ('n_palette', c_int),
+                ('palette', (ctypes.c_ubyte * 3) * LP_OVERLAY_MAX_PALETTE), ('n_glyphs', c_int), ('gh', c_int), ('gw', c_int),
+                ('show_id', c_int), ('label', c_int), ('draw_box', c_int)]
 
 
 class JpegDesc(ctypes.Structure):
@@ -222,6 +236,9 @@ SYMBOLS = {
     'lp_redact_gauss_workspace_bytes': (c_size_t, [POINTER(RedactDesc), c_int, POINTER(RedactGaussParams)]),
     'lp_redact_gauss_batch': (c_int, [POINTER(RedactDesc), c_int, c_void_p, c_void_p, c_int, POINTER(RedactGaussParams), c_void_p, c_void_p,
                                       c_size_t, c_void_p]),
+    'lp_overlay_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'lp_overlay_draw_batch': (c_int, [POINTER(RedactDesc), c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, POINTER(OverlayParams),
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'lp_jpeg_workspace_bytes': (c_size_t, [POINTER(JpegDesc), c_int, c_int]),
     'lp_jpeg_encode_batch': (c_int, [POINTER(JpegDesc), c_int, POINTER(JpegParams), c_void_p, c_int, c_void_p, c_size_t, c_void_p,
                                      c_void_p, c_size_t, c_void_p]),
