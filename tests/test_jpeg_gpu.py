@@ -99,7 +99,7 @@ def test_runs_under_the_workspace_cap(monkeypatch):
             if name == 'lp_jpeg_encode_batch':
                 return lambda desc, n, *a: (calls.append(n), lib.lp_jpeg_encode_batch(desc, n, *a))[1]
             return getattr(lib, name)
-    monkeypatch.setattr(runtime, 'JPEG_WS_CAP', 2 * (4 * 776 + 16))
+    monkeypatch.setattr(runtime.jpeg, 'JPEG_WS_CAP', 2 * (4 * 776 + 16))
     monkeypatch.setattr(abi, 'load', lambda: Counting())
     assert runtime.encode_jpeg([torch.from_numpy(f).cuda() for f in frames], 80, 4) == want
     assert calls == [2, 2, 1, 1, 1, 1, 1, 1, 1]

@@ -111,7 +111,7 @@ def test_workspace_cap_splits_the_call(monkeypatch):
     monkeypatch.setattr(abi, 'load', lambda: Spy())
     det, count = rows_for(BGR_SHAPES, 650), torch.tensor([12, 12, 1, 12], dtype=torch.int32, device='cuda')
     for cap, want_calls in ((1, [1, 1, 1, 1]), (4 * 37 * 53 + 16 + 4 * 70 * 131 + 16, [2, 2]), (runtime.GAUSS_WS_CAP, [4])):
-        monkeypatch.setattr(runtime, 'GAUSS_WS_CAP', cap)
+        monkeypatch.setattr(runtime.redact, 'GAUSS_WS_CAP', cap)
         calls.clear()
         buf, frames = bgr_buffer(BGR_SHAPES, 651)
         assert check_call(buf, frames, det, count, ws_poison=(0xA5,), sigma=2.5, margin=0.1) > 0
