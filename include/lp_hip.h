@@ -1066,6 +1066,75 @@ int lp_sight_update(int32_t* state, int capacity, const unsigned char* confuse /
                     const int32_t* now /* DEVICE [1] */, int window, int min_hits, int max_mismatch, int max_cost, int32_t* sight_i,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* lp_zone_update: tripwires and zones on the LIVE plate tracks -- line crossings with a direction, zone entry and exit, dwell alerts,
+ * occupancy and in / out counts.  The tracker, the watchlists and the sightings log say which plate; a gate, a car park or a street also
+ * asks which way it went and how long it has been there.  Called behind lp_track_update (any of its forms; behind lp_watch_match,
+ * lp_watch_live and lp_sight_update if they run too) on the same stream; all pointers but ncls are DEVICE pointers; nothing is uploaded or
+ * read back, nothing is allocated, capturable in a graph.  The tracker state is read, never written.  The reference has nothing here;
+ * yolov6/utils/zones.py::ZoneEventsNp restates the rules below on every int32 of the four outputs and of the memo.
+ *   track_state: the state of lp_track_update (16-byte aligned) as its last call left it; ncls: HOST int [8], the tracker's.
+ *   zone_map: int32 [n_streams, LP_ZONE_MAP_WORDS], 16-byte aligned, the packed geometry of every stream, in pixels of its frames, all
+ *   values finite: words 0, 1 = n_lines (0..LP_ZONE_MAX_LINES), n_zones (0..LP_ZONE_MAX_ZONES); 2..15 = 0; 16 + 4 l .. = line l, the
+ *   directed segment A -> B, as fp32 bits ax, ay, bx, by; 80 + 4 z .. = zone z as n_verts (3..LP_ZONE_MAX_VERTS), min_dwell (>= 0, 0: no
+ *   dwell alert), 0, 0; 112 + 32 z + 2 v .. = vertex v of zone z, a simple polygon (convex or not), as fp32 bits x, y; everything past
+ *   a count is 0.  The caller validates it (yolov6/utils/zones.py::check_packed); the kernel clamps the three counts to their ranges.
+ *   memo: int32 [n_streams, max_tracks + 2, 16], 16-byte aligned, lp_zone_state_bytes bytes, all zero = empty (the caller zeroes it
+ *   once, zeroes a stream's part together with the tracker's, and all of it when the map changes).  Row t < max_tracks, one per slot:
+ *   id + 1, last (the track's last matched frame when the anchor was taken), the anchor's x and y as fp32 bits, inside_mask |
+ *   alerted_mask << 8, enter_frame[8], 0, 0, 0.  Row max_tracks: the +1 totals per line; row max_tracks + 1: the -1 totals (int32, wrap).
+ * Arithmetic: a point or vertex is widened from fp32 to fp64; every later operation is one IEEE fp64 subtract or multiply, rounded on
+ * its own, in the written order (no fused multiply-add, no division): cross(P, Q, R) = (Qx - Px) * (Ry - Py) - (Qy - Py) * (Rx - Px).
+ * Every comparison is a plain float compare, false for NaN.  Anchor of a slot: ((x1 + x2) * 0.5f, (y1 + y2) * 0.5f) of the stored box in
+ * fp32 (the tracker's cx, cy); an anchor with |x| <= FLT_MAX and |y| <= FLT_MAX is finite, any other crosses no line and is in no zone.
+ * Crossing of line l by the move P0 -> P1: d0 = cross(A, B, P0), d1 = cross(A, B, P1); direction +1 iff d0 <= 0 and d1 > 0, -1 iff
+ * d0 > 0 and d1 <= 0 (a point on the line is on the negative side: a stop on the line is counted once); and the move must pass between
+ * the ends: e0 = cross(P0, P1, A), e1 = cross(P0, P1, B), (e0 <= 0 and e1 > 0) or (e0 > 0 and e1 <= 0).  Inside a zone: the crossing
+ * number over the edges (Vi, Vj), j = (i + 1) % n: an edge toggles iff (yi > py) != (yj > py) and, with t = (xj - xi) * (py - yi) -
+ * (px - xi) * (yj - yi), t > 0 if yj > yi, else t < 0.
+ * Every stream s < n_streams is processed, whether or not the tracker call gave it a frame; every slot t < max_tracks, in order; now =
+ * the stream's frame counter:
+ *   1. a slot is eligible iff hits > 0 and hits >= min_hits;
+ *   2. a non-empty memo line whose slot is not eligible or holds another id is gone: for every zone of its inside mask, ascending, an
+ *      event of kind 5 (ended inside) with frame = memo.last, value = memo.last - enter_frame[z], the memo's anchor, key 0, hits 0; the
+ *      line is zeroed;
+ *   3. an eligible slot with an empty memo line starts a track: no crossing is tested; every zone it is inside emits kind 2 (enter) with
+ *      enter_frame[z] = last;
+ *   4. an eligible slot whose memo holds its id: the lines, ascending: a crossing of memo anchor -> current anchor emits kind 1 with
+ *      value +1 / -1, and that total goes up by one; the zones, ascending: outside -> inside emits kind 2, sets enter_frame[z] = last and
+ *      clears the zone's alerted bit; inside -> outside emits kind 3 (left) with value = last - enter_frame[z]; the memo takes the new
+ *      anchor, last and inside mask;
+ *   5. behind each zone's transition in 3 and 4: iff the track is inside z, min_dwell[z] > 0, the alerted bit is clear and now -
+ *      enter_frame[z] >= min_dwell[z]: kind 4 (dwell) with value = now - enter_frame[z], and the bit is set (a missed but live track
+ *      keeps dwelling);
+ *   6. an event line, int32 [12]: kind, the line or zone index, id, slot, frame (last for kinds 1..4), value, the anchor's x and y as fp32
+ *      bits, key_lo, key_hi (the eight voted ids of rule 8 of lp_track_update, packed as the memo of lp_watch_live packs them; 0 for
+ *      kind 5), hits, 0;
+ *   7. zone_ev [n_streams, max_events, 12]: a stream's events in the order produced (by slot; within a slot step 2, the lines, then the
+ *      zones with each transition followed by its alert); zone_count [n_streams]: the number produced, not capped -- lines at or past
+ *      max_events are not written, lines from the count to max_events are zero; zone_occ [n_streams, 8]: the eligible tracks inside each
+ *      zone after the call; zone_totals [n_streams, 2, 16]: a copy of the two total rows.  All int32, 16-byte aligned; every word of the
+ *      four is written by every call.  The int32 differences wrap.
+ * One launch, one workgroup of 128 threads per stream, lane t = slot t: the stream's geometry is staged in LDS once; a lane reads its
+ * slot's first 16 bytes, its box and its memo line; the votes are read only for a slot that emits an event of kind 1 to 4; the events are
+ * counted per lane, numbered by a prefix sum over the workgroup and written by their lane; zone_occ and the totals are integer
+ * reductions in LDS.
+ * What it does not do: positions are those at the end of the tracker call (several frames of a stream in one call are tested on the
+ * chord; a track born and ended inside one call is unseen); a track that touches a line and turns back yields +1 then -1; a track that
+ * ends inside a zone is kind 5, not kind 3; no speed estimate, no homography; the anchor is the plate, not the vehicle's footprint.
+ * Every argument is checked before the launch (LP_ERR_ARG, nothing launched): n_streams < 1, max_tracks outside
+ * 1..LP_TRACK_MAX_TRACKS, max_events < 0, the words of the state, of the map or of zone_ev at or above 2^31, ncls null or a width
+ * outside 1..LP_TRACK_MAX_CLS, min_hits < 1, a null pointer (zone_ev only with max_events > 0), the state, the map, the memo or an
+ * output not 16-byte aligned, and a written buffer (memo, the four outputs) that overlaps the state, the map or another one. */
+#define LP_ZONE_MAX_LINES 16
+#define LP_ZONE_MAX_ZONES 8
+#define LP_ZONE_MAX_VERTS 16
+#define LP_ZONE_MAP_WORDS 368   /* 16 + 4 * 16 + 4 * 8 + 2 * 16 * 8 */
+size_t lp_zone_state_bytes(int n_streams, int max_tracks);             /* of the memo; 0: bad arguments */
+int lp_zone_update(const void* track_state, int n_streams, int max_tracks, const int* ncls /* HOST [8] */,
+                   const void* zone_map /* DEVICE, the packed geometry */, int min_hits, int32_t* memo,
+                   int32_t* zone_ev, int32_t* zone_count, int max_events, int32_t* zone_occ, int32_t* zone_totals,
+                   void* stream);
+
 /* lp_tile_gate_luma_batch / lp_tile_gate_update: skip the unchanged tiles of fixed-camera frames in tiled detection.  On a fixed
  * camera nearly every tile of a frame shows the pixels of the frame before, and a tile that has not changed yields the same
  * detections again; these two calls find, per (stream, tile), whether the tile changed against the frame its cached detections were

@@ -8,7 +8,7 @@
     python tools/frames_bench.py --tile --gate [--gate-moving K] [--gate-thres F] [--gate-refresh N] [--nv12 [bt709]] [--tile-frame 2160 3840] [--runs 3]
     python tools/frames_bench.py --tile --gate --gate-illum gain --gate-drift A [--gate-drift-period 8] [--gate-moving K] [--nv12 [bt709]] [--runs 3]
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot [--stack]] [--redact [--hold [--lookback D]]] [--nv12]
-                                 [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]] [--sightings C]
+                                 [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]] [--sightings C] [--zones L Z]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
     python tools/frames_bench.py --jpeg Q [--jpeg-frames 4] [--jpeg-restart 16] [--tile-frame 2160 3840] [--nv12 [bt601f]] [--redact]
     python tools/frames_bench.py --annotate [--annotate-plates N] [--jpeg-frames 4] [--tile-frame 2160 3840] [--nv12 [bt601f]]
@@ -131,6 +131,8 @@ def parse():
     ap.add_argument('--watch-live', action='store_true', help='with --watch: also time the lookup of the live tracks (lp_watch_live), on a '
                                                               'step with fresh reads and on one without')
     ap.add_argument('--watch-live-min-hits', type=int, default=1, help='with --watch-live: detections a track needs before it is looked up')
+    ap.add_argument('--zones', nargs=2, type=int, default=None, metavar=('L', 'Z'), help='with --track: also time lp_zone_update '
+                    '(PlateTracker.enable_zones) behind the update, with L seeded lines (0..16) and Z seeded zones of 16 vertices (0..8) per stream')
     ap.add_argument('--nv12', nargs='?', const='bt709', default=None, choices=['bt601', 'bt709', 'bt601f', 'bt709f'], metavar='MATRIX',
                     help='also send the same seeded frames as NV12 with this matrix and compare (default matrix: bt709)')
     ap.add_argument('--jpeg', type=int, default=None, metavar='Q', help='measure the JPEG stage instead (also with --nv12 and --redact): '
@@ -590,6 +592,8 @@ def track_mode(args, model, dev, tdt):
                 out['watch_live'] = watch_live_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
         if args.sightings:
             out['sightings'] = sight_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
+        if args.zones:
+            out['zones'] = zone_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
 
         # the full case: 128 live tracks x 128 rows per stream, every pair above the threshold
         full = runtime.PlateTracker(B, max_tracks=128, max_age=0, ncls=model, device=dev)
@@ -782,6 +786,59 @@ def watch_live_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
                 cold_ms=round(med['cold'], 4), cold_reads=round(float(np.mean(cold)), 1), candidate_slots_per_step=round(float(np.mean(cand)), 1),
                 steady_ms=round(med['steady'], 4), steady_fresh_reads=int(max(steady_fresh)), track_ms=round(med['track'], 4),
                 steady_over_track=round(med['steady'] / med['track'], 4))
+
+
+def zone_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
+    """--track --zones L Z: device time of lp_zone_update behind the update, from events on one stream, with L seeded lines and Z
+    seeded 16-vertex zones (min_dwell 1) per stream, spread over the frame.  Every step detects another batch of frames and updates
+    the tracker with the zone stage held back (``track_ms``: lp_track_update_hold of the same call), then enqueues the stage twice:
+    the first call sees the step's moves (``zones_ms``, ``events_per_step``, ``eligible_slots_per_step``), the second the same state
+    again, where nothing moves: the cost of a frame without events (``steady_ms``)."""
+    import torch
+    from yolov6.hip import runtime
+    size, stride = [args.size, args.size], int(model.stride.max())
+    B, conf, iou, max_det = args.track_batch, args.conf, args.iou, args.max_det
+    (L, Z), (h0, w0) = args.zones, args.frame
+    rng = np.random.default_rng(2)
+    lines = [[tuple(rng.uniform(0, (w0, h0, w0, h0))) for _ in range(L)] for _ in range(B)]
+
+    def star():
+        ang = np.linspace(0, 2 * np.pi, 16, endpoint=False)
+        rad = np.where(np.arange(16) % 2 == 0, 0.45, 0.2) * min(h0, w0) * rng.uniform(0.5, 1.0)
+        return np.stack([rng.uniform(0.3, 0.7) * w0 + rad * np.cos(ang), rng.uniform(0.3, 0.7) * h0 + rad * np.sin(ang)], 1), 1
+    zones = [[star() for _ in range(Z)] for _ in range(B)]
+    trk = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
+    trk.enable_zones(runtime.ZoneMap(B, lines, zones, device=dev))
+    times, events, eligible = dict(track=[], zones=[], steady=[]), [], []
+    for k in range(args.reps + 2):
+        frames = batcher.put([pool[(j + k) % len(pool)] for j in range(B)])
+        xx, _ = runtime.preprocess_frames(frames, size, stride, tdt, batch=B, out=x)
+        det, count, _ = runtime.detect_padded(model, xx, conf, iou, max_det)
+        runtime.rescale_round_batch(det, count, net_hw, [f.shape for f in frames])
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        held, trk._zones = trk._zones, None        # the update alone; the stage it would enqueue at its end follows by hand
+        ev[0].record()
+        trk.update(det, count)
+        ev[1].record()
+        trk._zones = held
+        trk._zone_update()
+        ev[2].record()
+        n_events = int(trk.last_zone[1].sum())     # (a host read: between the two timed calls, not inside one)
+        ev[3].record()
+        trk._zone_update()
+        ev[4].record()
+        torch.cuda.synchronize()
+        if k >= 2:
+            times['track'].append(ev[0].elapsed_time(ev[1]))
+            times['zones'].append(ev[1].elapsed_time(ev[2]))
+            times['steady'].append(ev[3].elapsed_time(ev[4]))
+            events.append(n_events)
+            eligible.append(int((trk.state.view(B, -1)[:, 16:].view(B, 128, -1)[:, :, 3] > 0).sum()))
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    return dict(lines=L, zones=Z, verts=16, streams=B, reps=args.reps, zones_ms=round(med['zones'], 4), steady_ms=round(med['steady'], 4),
+                track_ms=round(med['track'], 4), zones_over_track=round(med['zones'] / med['track'], 4),
+                zones_runs_ms=[round(v, 4) for v in times['zones']], track_runs_ms=[round(v, 4) for v in times['track']],
+                events_per_step=round(float(np.mean(events)), 1), eligible_slots_per_step=round(float(np.mean(eligible)), 1))
 
 
 def redact_stages(args, model, dev, tdt, batcher, pool, x, net_hw):

@@ -9,9 +9,9 @@
 //   memo line.  A slot that is not live gets a zero memo line.  A candidate (hits >= min_hits) whose memo holds its id and whose
 //   `last` equals the memo's last_at_lookup cannot have a new key -- votes change only on a match, and a match sets `last` -- so it
 //   is not fresh and its votes are not read; this changes no output byte.  For every other candidate the eight threads
-//   (slot, head) each read one head: the argmax over ncls[p] <= 64 floats, lowest index on a tie, and the share, restating rule 8
-//   of lp_track.hip's read_head to the letter (tests pin the two together).  Thread t packs the key and decides `fresh`; the fresh
-//   slots are numbered in slot order by ballot and prefix count over the two waves of 128 slots, as track_kernel numbers ending
+//   (slot, head) each read one head: the argmax over ncls[p] <= 64 floats, lowest index on a tie, and the share (track_read_head of
+//   lp_track_read.inc, rule 8 of lp_track.hip's read_head to the letter; tests pin the two together).  Thread t packs the key and
+//   decides `fresh`; the fresh slots are numbered in slot order by ballot and prefix count over the two waves, as track_kernel numbers ending
 //   tracks, and their lines go out in the ended-record layout.  Lines past the count are zeroed (q_slot -1), and pos[s][t] -- the
 //   query line of slot t, -1 for none -- is left in the workspace for the scatter.
 // lp_watch_match on (q_i, q_f, q_count) with max_ended = max_tracks; its match_i lies in the workspace.
@@ -19,20 +19,19 @@
 //   slot's row of live_i from the memo.
 #include "lp_internal.h"
 #include "lp_streams.h"
+#include "lp_track_read.inc"
 
 namespace lp {
 
 namespace {
 
-constexpr int WL_SLOTS = LP_TRACK_MAX_TRACKS;   // 128
-constexpr int WL_HEADS = 8;
+constexpr int WL_SLOTS = TR_SLOTS;              // 128
+constexpr int WL_HEADS = TR_HEADS;
 constexpr int WL_T = WL_SLOTS * WL_HEADS;       // most threads of a gather workgroup: one per (slot, head)
-// the tracker state, restated from lp_track.hip: 16 header words per stream, 544 words per slot
-constexpr int WL_HDR_WORDS = 16, WL_W_BOX = 8, WL_W_TOTAL = 24, WL_W_VOTES = 32;
-constexpr int WL_SLOT_WORDS = WL_W_VOTES + WL_HEADS * LP_TRACK_MAX_CLS;
+// the tracker state: lp_track_read.inc
+constexpr int WL_HDR_WORDS = TR_HDR_WORDS, WL_W_BOX = TR_W_BOX, WL_SLOT_WORDS = TR_SLOT_WORDS;
 constexpr int WL_Q_COLS = 12;                   // q_i / q_f: words of a line (the ended-record layout)
 constexpr int WL_MEMO_WORDS = 8, WL_LIVE_COLS = 8;
-static_assert(WL_SLOT_WORDS == 544 && WL_SLOTS == 128 && LP_TRACK_MAX_CLS == 64, "lp_watch_live.hip restates the state layout of lp_track.hip");
 
 struct LiveNcls { int v[WL_HEADS]; };
 
@@ -91,19 +90,11 @@ __global__ __launch_bounds__(WL_T) void live_gather_kernel(const int* __restrict
     __syncthreads();
     // ---- step 2: rule 8, one thread per (slot, head) -------------------------------------------------------------------------------
     if (hslot < T && s_need[hslot]) {
-        const int* sl = sst + (long long)hslot * WL_SLOT_WORDS;
-        const float* v = (const float*)(sl + WL_W_VOTES + head * LP_TRACK_MAX_CLS);
-        const int nc = ncls.v[head];
-        int bi = 0;
-        float bv = v[0];
-#pragma unroll 4
-        for (int c = 1; c < nc; ++c) {
-            const float x = v[c];
-            if (x > bv) { bv = x; bi = c; }
-        }
-        const float tot = __int_as_float(sl[WL_W_TOTAL + head]);
+        int bi;
+        float sh;
+        track_read_head(sst + (long long)hslot * WL_SLOT_WORDS, head, ncls.v[head], bi, sh);
         s_best[tid] = bi;
-        s_share[tid] = tot > 0.f ? bv / tot : 0.f;
+        s_share[tid] = sh;
     }
     __syncthreads();
     // ---- steps 3 and 4: fresh slots, numbered in slot order ------------------------------------------------------------------------

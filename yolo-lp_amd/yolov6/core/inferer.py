@@ -64,7 +64,7 @@ class Inferer:
                  tile_gate_min_cells=1, tile_gate_refresh=50, tile_gate_illum='none', tile_gate_max_gain=1.5, stack_shots=False,
                  stack_search=2, stack_max_frames=64, stack_min_width=0.0, sightings=None, sight_window=None, sight_min_hits=1,
                  sight_mismatch=1, sight_cost=None, save_jpeg=None, overlay=False, overlay_font=None, overlay_size=24, overlay_thickness=2,
-                 overlay_alpha=(256, 160, 256)):
+                 overlay_alpha=(256, 160, 256), zones=None, zones_min_hits=1):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -127,7 +127,11 @@ class Inferer:
         rendered once on the host from the yaml's names at ``overlay_size`` pixels with the TrueType file ``overlay_font`` (None:
         PIL's default font, which has no CJK glyphs: the province then shows '?'); ``overlay_thickness`` is the outlines' width
         (0..16), ``overlay_alpha`` the opacities 0..256 of outlines, label plate and text.  With ``redact_hold`` the predicted rows
-        of missed tracks are drawn in a second style.  Not with ``redact_lookback`` (the frame drawn on would not be redacted yet)."""
+        of missed tracks are drawn in a second style.  Not with ``redact_lookback`` (the frame drawn on would not be redacted yet).
+        ``zones`` = the path of a file of lines and zones (with ``track``; ``yolov6.utils.zones`` states the rule and ``parse_zones``
+        the format; a stream prefix names the tracker's stream: 0 = the image files, 1 + k = the k-th video): the live tracks of at
+        least ``zones_min_hits`` detections are tested against them after every tracker call; ``infer`` writes ``crossings.txt`` and
+        ``zones.txt`` and logs the totals per line; every other output is what it is without it."""
         self.__dict__.update(locals())
         self._overlay = None
         if overlay:
@@ -157,6 +161,11 @@ class Inferer:
             check_log(sightings, 1)
             check_call(0, 0 if sight_window is None else sight_window, sight_min_hits)
             check_params(sight_mismatch, cost_units(sight_cost))
+        if zones is not None:
+            from yolov6.utils.watch_live import check_min_hits
+            if not track:
+                raise ValueError('zones needs track=True')
+            check_min_hits(zones_min_hits)
         if watch_live:
             from yolov6.utils.watch_live import check_min_hits
             if watchlist is None:
@@ -567,6 +576,12 @@ class Inferer:
             window = (1 << 31) - 1 if self.sight_window is None else self.sight_window      # the largest int32: no limit
             self._tracker.enable_sightings(log, window, self.sight_min_hits, self.sight_mismatch, self.sight_cost)
         self._track_alerts = []         # with watch_live: (frame, id, best [8], entry, mismatches, cost, n_hits, hits) per alert
+        self._track_zone_events = []    # with zones: (stream, kind, index, frame, id, best [8] or None, value) per event
+        if self.zones is not None:
+            from yolov6.utils import zones as zn
+            lines, polys, self._zone_line_names, self._zone_names = zn.parse_zones(self.zones, 1 + len(videos))
+            make = runtime.ZoneMap if self.device.type != 'cpu' else zn.ZoneMapNp
+            self._tracker.enable_zones(make(1 + len(videos), lines, polys, device=self.device), self.zones_min_hits)
         if self.redact_hold:
             self._tracker.enable_hold(min_hits=self.redact_hold_min_hits)
         if self.redact_lookback is not None:
@@ -632,6 +647,20 @@ class Inferer:
             for s, t in alerts_of(live_i):
                 row, j = live_i[s, t], int(np.nonzero(q_slot[s] == t)[0][0])
                 self._track_alerts.append((row[7], row[0], q_i[s, j, 4:12].copy()) + tuple(row[1:5]) + (row[6],))
+        if self._tracker.last_zone is not None:     # the line and zone events of the same update
+            zone_ev, zone_count = self._tracker.last_zone[:2]
+            if torch.is_tensor(zone_ev):
+                zone_ev, zone_count = zone_ev.cpu().numpy(), zone_count.cpu().numpy()
+            for s, c in enumerate(zone_count.tolist()):
+                if c > zone_ev.shape[1]:
+                    LOGGER.warning('stream %d: %d line and zone events in one step, %d recorded' % (s, c, zone_ev.shape[1]))
+                for e in zone_ev[s, :min(c, zone_ev.shape[1])]:
+                    if e[0] != 5:
+                        best = [int(e[8 + p // 4]) >> 8 * (p % 4) & 0xFF for p in range(8)]
+                    else:                           # ended inside: the read of the ended record of the same id in this call
+                        ended = [ended_i[s, k, 4:12] for k in range(min(int(ended_count[s]), ended_i.shape[1])) if ended_i[s, k, 0] == e[2]]
+                        best = ended[0].copy() if ended else None
+                    self._track_zone_events.append((s, int(e[0]), int(e[1]), int(e[4]), int(e[2]), best, int(e[5])))
 
     def _track_update(self, det, count, paths, frames=None):
         """One tracker update of a padded group: det [B,max_det,28] + count [B] (numpy on the CPU, device tensors on a GPU) of
@@ -729,6 +758,21 @@ class Inferer:
                 for frame, tid, best, e, mism, cost, n, hits in self._track_alerts:
                     f.write('%d %d %s %d %s %d %d %d %d\n' % (frame, tid, plate_text(best, *names), e, entry_text(entries[e], *names), mism,
                                                               cost, n, hits))
+        if self.zones is not None:
+            from yolov6.utils.zones import EVENT_NAMES, KIND_CROSS
+            names = (self.pro_names, self.alp_names, self.ads_names)
+            with open(osp.join(save_dir, 'crossings.txt'), 'w') as fc, open(osp.join(save_dir, 'zones.txt'), 'w') as fz:
+                for s, kind, index, frame, tid, best, value in self._track_zone_events:
+                    text = '-' if best is None else plate_text(best, *names)
+                    if kind == KIND_CROSS:
+                        fc.write('%d %d %s %s %+d\n' % (frame, tid, text, self._zone_line_names[s][index], value))
+                    else:
+                        fz.write('%d %d %s %s %s %d\n' % (frame, tid, text, self._zone_names[s][index], EVENT_NAMES[kind], value))
+            totals = self._tracker.last_zone[3]
+            totals = totals.cpu().numpy() if torch.is_tensor(totals) else totals
+            LOGGER.info('line totals: ' + ('; '.join('%s%s +%d -%d' % ('' if len(self._zone_line_names) == 1 else '%d:' % s, name,
+                                                                      totals[s, 0, l], totals[s, 1, l])
+                                                     for s, ns in enumerate(self._zone_line_names) for l, name in enumerate(ns)) or 'no lines'))
         if self.best_shots:
             names = self._write_track_images(save_dir, 'shots', [s[2] for s in self._track_shots])
             with open(osp.join(save_dir, 'shots.txt'), 'w') as f:

@@ -1,5 +1,5 @@
 """Plate tracking across video frames (lp_track_update; yolov6/utils/track.py states the rules) and the tracker's add-ons: hold,
-best shot, stack, watchlist, live watchlist and sightings."""
+best shot, stack, watchlist, live watchlist, sightings, and lines and zones (lp_zone_update; yolov6/utils/zones.py states the rule)."""
 import ctypes
 
 import torch
@@ -27,6 +27,23 @@ def _zero_streams(state, n_streams, streams):
     else:
         for s in streams:
             st[int(s)].zero_()
+
+
+class ZoneMap:
+    """The lines and zones of ``n_streams`` streams on the device (lp_zone_update; ``yolov6.utils.zones`` states the rule and the
+    packed layout): the constructor of ``zones.ZoneMapNp`` -- ``lines``: per stream a list of (x1, y1, x2, y2); ``zones``: per stream
+    a list of (vertices [n, 2], min_dwell) -- validated on the host and uploaded once; a changed map is a new object.  ``lines_np`` /
+    ``zones_np`` / ``packed_np``: the checked host copies; ``packed``: int32 [S, 368] on the device."""
+
+    def __init__(self, n_streams, lines=None, zones=None, device=None):
+        from yolov6.utils.zones import ZoneMapNp, check_packed
+        ref = ZoneMapNp(n_streams, lines, zones)
+        self.n_streams, self.lines_np, self.zones_np, self.packed_np = ref.n_streams, ref.lines_np, ref.zones_np, ref.packed
+        if self.packed_np.shape[1] != abi.LP_ZONE_MAP_WORDS:
+            raise RuntimeError('the packed zone map and lp_hip.h disagree')
+        check_packed(self.packed_np)
+        self.device = _cuda_device('cuda' if device is None else device, 'ZoneMap lives on a GPU (ZoneMapNp is the CPU form)')
+        self.packed = torch.from_numpy(self.packed_np).to(self.device)
 
 
 class PlateTracker:
@@ -75,11 +92,16 @@ class PlateTracker:
         self.last_sight = None
         #: int32 [1] on the device: the clock of ``enable_sightings``, incremented by one per call; the caller may set it
         self.sight_now = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._zones = None
+        #: (zone_ev [S,max_events,12], zone_count [S], zone_occ [S,8], zone_totals [S,2,16]) int32 of the last ``update`` after
+        #: ``enable_zones``, else None
+        self.last_zone = None
 
     def reset(self, streams=None):
         """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0; their best-shot
         galleries (``enable_best_shot``) and stacks (``enable_stack``) are emptied with them, and their memo of
-        ``enable_live_watch``.  The log of ``enable_sightings`` and ``sight_now`` stay as they are."""
+        ``enable_live_watch`` and of ``enable_zones`` (its totals included, without events).  The log of ``enable_sightings`` and
+        ``sight_now`` stay as they are."""
         _zero_streams(self.state, self.n_streams, streams)
         if self._stack is not None:
             _zero_streams(self._stack['state'], self.n_streams, streams)
@@ -87,6 +109,8 @@ class PlateTracker:
             _zero_streams(self._live['memo'], self.n_streams, streams)
         if self._shots is not None:
             _zero_streams(self._shots['state'], self.n_streams, streams)
+        if self._zones is not None:
+            _zero_streams(self._zones['memo'], self.n_streams, streams)
 
     @property
     def dropped(self):
@@ -131,7 +155,55 @@ class PlateTracker:
             log, params = self._sight
             self.last_sight = log._update(ended_i, ended_f, ended_count, self.sight_now, *params)
             self.sight_now.add_(1)
+        if self._zones is not None:
+            self._zone_update()
         return out
+
+    # ---- lines and zones on the live tracks (lp_zone_update; yolov6/utils/zones.py states the rule) ------------------------------
+    def enable_zones(self, zone_map, min_hits=1, max_events=None):
+        """From now on every ``update`` / ``update_with_shots`` / ``flush_all*`` also enqueues, at its end on the same stream (behind
+        the sightings update), lp_zone_update of the live tracks of at least ``min_hits`` hits on ``zone_map`` (a ``ZoneMap`` of this
+        device and of the tracker's ``n_streams``): directed line crossings, zone entry and exit, dwell alerts, tracks that ended
+        inside a zone.  ``last_zone`` = (zone_ev [S,max_events,12], zone_count [S], zone_occ [S,8], zone_totals [S,2,16]) int32:
+        per stream the events in slot order as (kind, index, id, slot, frame, value, anchor x, y as fp32 bits, key_lo, key_hi, hits,
+        0) with kind 1 = crossed (value +1 / -1), 2 = enter, 3 = left (value: frames inside), 4 = dwell, 5 = ended inside; their
+        number, not capped at ``max_events`` (default 2 * max_tracks); the eligible tracks inside each zone; the +1 and -1 totals
+        per line since the memo was zeroed.  Persistent buffers, no host read, no allocation per call.  Returns, state and every
+        other buffer are what they are without it.  Calling it again zeroes the memo and the totals; ``enable_zones(None)`` turns it
+        off.  ``PlateTrackerNp.enable_zones`` is the same on the CPU, on every int32."""
+        from yolov6.utils import watch_live
+        self.last_zone = None
+        if zone_map is None:
+            self._zones = None
+            return
+        if not isinstance(zone_map, ZoneMap) or zone_map.device != self.device or zone_map.n_streams != self.n_streams:
+            raise ValueError('enable_zones needs a ZoneMap of %d streams on the tracker\'s device %s' % (self.n_streams, self.device))
+        min_hits = watch_live.check_min_hits(min_hits)
+        max_events = 2 * self.max_tracks if max_events is None else int(max_events)
+        if max_events < 0:
+            raise ValueError('max_events must be >= 0')
+        S, T, lib = self.n_streams, self.max_tracks, abi.load()
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self._zones = dict(
+            zone_map=zone_map, min_hits=min_hits, max_events=max_events, ncls=(ctypes.c_int * 8)(*self.ncls),
+            memo=torch.zeros(lib.lp_zone_state_bytes(S, T) // 4, **i32).view(S, T + 2, 16),
+            ev=torch.empty(S, max_events, 12, **i32), count=torch.empty(S, **i32), occ=torch.empty(S, 8, **i32),
+            totals=torch.empty(S, 2, 16, **i32))
+
+    @property
+    def zone_memo(self):
+        """The memo of ``enable_zones``: int32 [S,max_tracks+2,16] on the device (per slot id + 1, last, anchor x, y, inside |
+        alerted << 8, enter_frame[8], 0, 0, 0; then the +1 and the -1 totals per line), else None."""
+        return None if self._zones is None else self._zones['memo']
+
+    def _zone_update(self):
+        """Enqueue lp_zone_update on the state as it stands."""
+        zn = self._zones
+        with torch.cuda.device(self.device):
+            abi.check(abi.load().lp_zone_update(_dptr(self.state), self.n_streams, self.max_tracks, zn['ncls'], _dptr(zn['zone_map'].packed),
+                                                zn['min_hits'], _dptr(zn['memo']), _dptr(zn['ev']), _dptr(zn['count']), zn['max_events'],
+                                                _dptr(zn['occ']), _dptr(zn['totals']), _stream_ptr(self.device)), 'lp_zone_update')
+        self.last_zone = (zn['ev'], zn['count'], zn['occ'], zn['totals'])
 
     # ---- the ended reads matched against the earlier reads of all streams (lp_sight_update; yolov6/utils/sight.py states the rule) ----
     def enable_sightings(self, log, window=0, min_hits=1, max_mismatch=1, max_cost=None):

@@ -197,6 +197,9 @@ class PlateTrackerNp:
         self.last_sight = None
         #: int32 [1]: the clock of ``enable_sightings``, incremented by one per call; the caller may set it
         self.sight_now = np.zeros(1, np.int32)
+        self._zones = None
+        #: (zone_ev, zone_count, zone_occ, zone_totals) of the last ``update`` after ``enable_zones``, else None
+        self.last_zone = None
 
     _SLOT_ARRAYS = ('id', 'first', 'last', 'hits', 'misses', 'box', 'cor', 'vel', 'votes', 'total')
 
@@ -209,6 +212,8 @@ class PlateTrackerNp:
             self._live.reset(streams)
         if self._stack is not None:
             self._stack['np'].reset(streams)
+        if self._zones is not None:
+            self._zones[0].reset(streams)
 
     def enable_stack(self, search=2, max_frames=64, min_width=0.0, min_sharp=0, crop_hw=(64, 192), max_crops=16, min_score=0.0):
         """One denoised picture per track (``yolov6.utils.stack`` states the rule and its limits): from now on ``update_stack``,
@@ -288,6 +293,28 @@ class PlateTrackerNp:
             raise ValueError('enable_sightings needs a SightLogNp of %d streams' % self.n_streams)
         _, window, min_hits = sight.check_call(0, window, min_hits)
         self._sight = (log, (window, min_hits) + watch.check_params(max_mismatch, watch.cost_units(max_cost)))
+
+    def enable_zones(self, zone_map, min_hits=1, max_events=None):
+        """From now on every ``update`` / ``flush_all`` also tests the live tracks of at least ``min_hits`` hits against the lines and
+        zones of ``zone_map`` -- anything with ``n_streams``, ``lines_np`` and ``zones_np`` (``zones.ZoneMapNp``, ``runtime.ZoneMap``)
+        -- behind the sightings update (``yolov6.utils.zones`` states the rule), and leaves (zone_ev [S, max_events, 12], zone_count
+        [S], zone_occ [S, 8], zone_totals [S, 2, 16]) int32 in ``last_zone``; ``max_events`` defaults to 2 * max_tracks.  Every other
+        output and the state stay what they are.  Calling it again starts from an empty memo and zero totals;
+        ``enable_zones(None)`` turns it off."""
+        from yolov6.utils.zones import ZoneEventsNp
+        self.last_zone = None
+        if zone_map is None:
+            self._zones = None
+            return
+        max_events = 2 * self.max_tracks if max_events is None else int(max_events)
+        if max_events < 0:
+            raise ValueError('max_events must be >= 0')
+        self._zones = (ZoneEventsNp(self, zone_map, min_hits), max_events)
+
+    @property
+    def zone_memo(self):
+        """The memo of ``enable_zones``: int32 [S, max_tracks + 2, 16], else None."""
+        return None if self._zones is None else self._zones[0].memo
 
     def hold_buffers(self, B, max_det):
         """The persistent (det_hold [B,max_det+max_tracks,28] fp32, count_hold [B] int32, tid_hold [B,max_det+max_tracks] int32)
@@ -499,4 +526,6 @@ class PlateTrackerNp:
             self.last_sight = sight_update_np(log.state, log.confuse_np, log.pair_np, ended_i, ended_f, ended_count,
                                               int(self.sight_now[0]), *params)
             self.sight_now += 1
+        if self._zones is not None:
+            self.last_zone = self._zones[0].step(self._zones[1])
         return det_out, tid, ended_i, ended_f, ended_count
