@@ -1120,7 +1120,8 @@ int lp_sight_update(int32_t* state, int capacity, const unsigned char* confuse /
  * reductions in LDS.
  * What it does not do: positions are those at the end of the tracker call (several frames of a stream in one call are tested on the
  * chord; a track born and ended inside one call is unseen); a track that touches a line and turns back yields +1 then -1; a track that
- * ends inside a zone is kind 5, not kind 3; no speed estimate, no homography; the anchor is the plate, not the vehicle's footprint.
+ * ends inside a zone is kind 5, not kind 3; everything stays in pixels (lp_speed_update has the calibrated plane); the anchor is the plate, not
+ * the vehicle's footprint.
  * Every argument is checked before the launch (LP_ERR_ARG, nothing launched): n_streams < 1, max_tracks outside
  * 1..LP_TRACK_MAX_TRACKS, max_events < 0, the words of the state, of the map or of zone_ev at or above 2^31, ncls null or a width
  * outside 1..LP_TRACK_MAX_CLS, min_hits < 1, a null pointer (zone_ev only with max_events > 0), the state, the map, the memo or an
@@ -1134,6 +1135,73 @@ int lp_zone_update(const void* track_state, int n_streams, int max_tracks, const
                    const void* zone_map /* DEVICE, the packed geometry */, int min_hits, int32_t* memo,
                    int32_t* zone_ev, int32_t* zone_count, int max_events, int32_t* zone_occ, int32_t* zone_totals,
                    void* stream);
+
+/* lp_speed_update: the speed of the LIVE plate tracks on a calibrated ground plane, with an alert over a limit.  lp_zone_update works in
+ * pixels of the frame, where a pixel near the horizon is many metres; this maps the tracker's anchor through a per-stream homography to
+ * millimetres on a plane and differences the positions over time.  Called behind lp_track_update (any of its forms; behind the other
+ * add-ons if they run too) on the same stream; all pointers but ncls are DEVICE pointers; nothing is uploaded or read back, nothing is
+ * allocated, capturable in a graph.  The tracker state is read, never written.  The reference has nothing here;
+ * yolov6/utils/speed.py::SpeedNp restates the rules below on every int32 of the three outputs and of the memo.
+ *   track_state: the state of lp_track_update (16-byte aligned) as its last call left it; ncls: HOST int [8], the tracker's.
+ *   ground_map: int32 [n_streams, LP_SPEED_MAP_WORDS], 16-byte aligned: words 0..17 = H, a 3x3 fp64 homography, row-major h0..h8, as bit
+ *   pairs (lo, hi), all finite, frame pixels -> metres on the plane the plates move in (calibrated at plate height); 18 = period_us
+ *   (1..10^7), the nominal frame period; 19 = limit_mm_s (>= 0, 0: no alert); 20 = min_gap_us (>= 0); 21 = min_span_us (>= 1); 22 =
+ *   enabled (0 / 1; a stream without a plane is all zero: "none" rows, no events); the rest 0.  The caller validates it
+ *   (yolov6/utils/speed.py::check_packed).
+ *   clock_us: NULL, or int64 [n_streams], 8-byte aligned, read in place: the time of every stream's newest frame in microseconds.
+ *   memo: int32 [n_streams, max_tracks, LP_SPEED_MEMO_WORDS], 16-byte aligned, lp_speed_state_bytes bytes, all zero = empty (the caller
+ *   zeroes it once, zeroes a stream's part together with the tracker's, and all of it when the map changes).  Word 0 = id + 1; 1 = last;
+ *   2 = samples pushed (saturating); 3 = ring head (where the next sample goes); 4, 5 = t_first (lo, hi); 6, 7 = X_first, Y_first; 8..10 =
+ *   the stored estimate speed (-1: none yet), vx, vy in mm/s; 11 = peak; 12 = over | alerted << 16 (over saturates at 65535); 13 =
+ *   span_ms; 14, 15 = 0; 16 + 4 k .. = sample k of a ring of LP_SPEED_RING as t_lo, t_hi, X_mm, Y_mm.  The ring holds n = min(pushed, 8)
+ *   samples, the newest at (head - 1) & 7, the oldest at 0 while pushed < 8, else at head.
+ * World point of a slot: the anchor ((x1 + x2) * 0.5f, (y1 + y2) * 0.5f) of the stored box in fp32 (the tracker's cx, cy), widened to
+ * fp64 as x, y; then one IEEE fp64 operation at a time, rounded on its own, in this order, no fused multiply-add: u = (h0 * x + h1 * y) +
+ * h2, v = (h3 * x + h4 * y) + h5, w = (h6 * x + h7 * y) + h8, X = u / w, Y = v / w (correctly rounded divisions), PX = X * 1000.0, PY = Y *
+ * 1000.0, X_mm = rint(PX), Y_mm = rint(PY) (ties to even).  Valid iff |ax| <= FLT_MAX and |ay| <= FLT_MAX, w > 0, |PX| <= 2^30 and |PY| <=
+ * 2^30 (plain compares, false for NaN).  Everything behind it is integer.
+ * Time of a sample: now = the stream's frame counter, last = the slot's last matched frame: t_us = base - int64(int32(now - last)) *
+ * period_us, base = clock_us[s] if clock_us is given, else int64(now) * period_us.  The int32 and int64 differences wrap.
+ * Every stream s < n_streams is processed, whether or not the tracker call gave it a frame; every slot t < max_tracks, in order:
+ *   1. a slot is eligible iff its stream is enabled, hits > 0 and hits >= min_hits;
+ *   2. a non-empty memo line whose slot is not eligible or holds another id is gone: if it pushed at least 2 samples, an event of kind 3
+ *      (ended) with frame = memo.last, value = peak, aux = the chord speed from the first to the newest sample by the estimator of 5 (0 if
+ *      their dt <= 0), the newest sample's position, key 0, hits 0; the line is zeroed;
+ *   3. an eligible slot with an empty line starts: id + 1 and last are stored, the stored speed is -1; a valid point is pushed as the
+ *      first sample, which is also `first`;
+ *   4. an eligible slot holding its id, with slot.last != memo.last: memo.last = slot.last; if the point is valid and (no sample yet, or
+ *      t - t_newest >= min_gap_us) it is pushed, overwriting the oldest once the ring holds 8.  A call that pushed is fresh for the slot;
+ *   5. only when fresh and n >= 2: o = the oldest, e = the newest sample, dt = t_e - t_o; if dt >= min_span_us: dx, dy int64, d2 = dx * dx +
+ *      dy * dy, s = floor(sqrt(d2)) exact, speed = min(s * 10^6 / dt, 2^31 - 1), vx = sign(dx) * min(|dx| * 10^6 / dt, 2^31 - 1), vy
+ *      likewise, span_ms = min(dt / 1000, 2^31 - 1), peak = max(peak, speed) (integer divisions of non-negative numbers);
+ *   6. only when 5 gave an estimate in this call and limit_mm_s > 0: speed > limit: over += 1, and with over >= confirm and the alerted bit
+ *      clear an event of kind 1 (value = speed, aux = limit, frame = last, the voted read as key_lo, key_hi as lp_watch_live packs it,
+ *      hits) and the bit is set; speed <= limit: over = 0.  One alert per track;
+ *   7. speed_i [n_streams, max_tracks, 8]: (id, speed, vx, vy, X_mm, Y_mm of the newest sample (0, 0 without one), span_ms, n | fresh << 8
+ *      | alerted << 9); a slot that is not eligible: (-1, 0, 0, 0, 0, 0, 0, 0);
+ *   8. speed_ev [n_streams, max_events, 12]: kind, 0, id, slot, frame, value, X_mm, Y_mm, key_lo, key_hi, hits, aux, in slot order (a slot
+ *      yields at most one event per call); speed_count [n_streams]: the number produced, not capped -- lines at or past max_events are
+ *      not written, lines from the count to max_events are zero.  All int32, 16-byte aligned; every word of the three is written by every
+ *      call.
+ * One launch, one workgroup of 128 threads per stream, lane t = slot t: a lane reads its slot's first 16 bytes, its memo header and the
+ * newest sample; only a slot with a new detection reads its box, only a push stores a sample and reads the oldest; the votes are read only
+ * for a slot that alerts; the events are numbered by a prefix sum over the workgroup and written by their lane.
+ * What it does not do: the estimator is the endpoint difference over the ring: no filtering, no acceleration, no lens-distortion model; a
+ * plate sits off the calibrated plane by its mounting-height spread; positions are those at the end of the tracker call; now and the
+ * clock must not run backwards (dt <= 0: no estimate); zones stay in pixels.
+ * Every argument is checked before the launch (LP_ERR_ARG, nothing launched): n_streams < 1, max_tracks outside
+ * 1..LP_TRACK_MAX_TRACKS, max_events < 0, the words of the state or of speed_ev at or above 2^31, ncls null or a width outside
+ * 1..LP_TRACK_MAX_CLS, min_hits < 1, confirm outside 1..65535, a null pointer (speed_ev only with max_events > 0; clock_us may be null),
+ * the state, the map, the memo or an output not 16-byte aligned, a clock not 8-byte aligned, and a written buffer (memo, the three
+ * outputs) that overlaps the state, the map, the clock or another one. */
+#define LP_SPEED_MAP_WORDS 32
+#define LP_SPEED_MEMO_WORDS 48   /* 16 + 4 * LP_SPEED_RING */
+#define LP_SPEED_RING 8
+size_t lp_speed_state_bytes(int n_streams, int max_tracks);            /* of the memo; 0: bad arguments */
+int lp_speed_update(const void* track_state, int n_streams, int max_tracks, const int* ncls /* HOST [8] */,
+                    const void* ground_map /* DEVICE, the packed calibration */, const void* clock_us /* DEVICE int64 [n_streams], may be NULL */,
+                    int min_hits, int confirm, void* memo, void* speed_i, void* speed_ev, void* speed_count, int max_events,
+                    void* stream);
 
 /* lp_tile_gate_luma_batch / lp_tile_gate_update: skip the unchanged tiles of fixed-camera frames in tiled detection.  On a fixed
  * camera nearly every tile of a frame shows the pixels of the frame before, and a tile that has not changed yields the same

@@ -8,7 +8,7 @@
     python tools/frames_bench.py --tile --gate [--gate-moving K] [--gate-thres F] [--gate-refresh N] [--nv12 [bt709]] [--tile-frame 2160 3840] [--runs 3]
     python tools/frames_bench.py --tile --gate --gate-illum gain --gate-drift A [--gate-drift-period 8] [--gate-moving K] [--nv12 [bt709]] [--runs 3]
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot [--stack]] [--redact [--hold [--lookback D]]] [--nv12]
-                                 [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]] [--sightings C] [--zones L Z]
+                                 [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]] [--sightings C] [--zones L Z] [--speed]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
     python tools/frames_bench.py --jpeg Q [--jpeg-frames 4] [--jpeg-restart 16] [--tile-frame 2160 3840] [--nv12 [bt601f]] [--redact]
     python tools/frames_bench.py --annotate [--annotate-plates N] [--jpeg-frames 4] [--tile-frame 2160 3840] [--nv12 [bt601f]]
@@ -131,6 +131,8 @@ def parse():
     ap.add_argument('--watch-live', action='store_true', help='with --watch: also time the lookup of the live tracks (lp_watch_live), on a '
                                                               'step with fresh reads and on one without')
     ap.add_argument('--watch-live-min-hits', type=int, default=1, help='with --watch-live: detections a track needs before it is looked up')
+    ap.add_argument('--speed', action='store_true', help='with --track: also time lp_speed_update (PlateTracker.enable_speed) behind the update, '
+                    'with one oblique calibrated plane per stream')
     ap.add_argument('--zones', nargs=2, type=int, default=None, metavar=('L', 'Z'), help='with --track: also time lp_zone_update '
                     '(PlateTracker.enable_zones) behind the update, with L seeded lines (0..16) and Z seeded zones of 16 vertices (0..8) per stream')
     ap.add_argument('--nv12', nargs='?', const='bt709', default=None, choices=['bt601', 'bt709', 'bt601f', 'bt709f'], metavar='MATRIX',
@@ -594,6 +596,8 @@ def track_mode(args, model, dev, tdt):
             out['sightings'] = sight_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
         if args.zones:
             out['zones'] = zone_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
+        if args.speed:
+            out['speed'] = speed_stages(args, model, dev, tdt, batcher, pool, x, (H, W))
 
         # the full case: 128 live tracks x 128 rows per stream, every pair above the threshold
         full = runtime.PlateTracker(B, max_tracks=128, max_age=0, ncls=model, device=dev)
@@ -839,6 +843,55 @@ def zone_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
                 track_ms=round(med['track'], 4), zones_over_track=round(med['zones'] / med['track'], 4),
                 zones_runs_ms=[round(v, 4) for v in times['zones']], track_runs_ms=[round(v, 4) for v in times['track']],
                 events_per_step=round(float(np.mean(events)), 1), eligible_slots_per_step=round(float(np.mean(eligible)), 1))
+
+
+def speed_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
+    """--track --speed: device time of lp_speed_update behind the update, from events on one stream, with one oblique plane per stream
+    (a limit that about half of the estimates pass, min_span of two frames).  Every step detects another batch of frames and updates
+    the tracker with the speed stage held back (``track_ms``: lp_track_update_hold of the same call), then enqueues the stage twice:
+    the first call sees the step's detections (``speed_ms``, ``fresh_slots_per_step``, ``events_per_step``), the second the same state
+    again, where no slot has a new detection: the cost of a frame without samples (``steady_ms``)."""
+    import torch
+    from yolov6.hip import runtime
+    size, stride = [args.size, args.size], int(model.stride.max())
+    B, conf, iou, max_det = args.track_batch, args.conf, args.iou, args.max_det
+    h0, w0 = args.frame
+    plane = dict(H=(20.0 / w0, 0.0, -10.0, 0.0, -30.0 / h0, 40.0, 0.0, -0.7 / h0, 1.0), period_us=40000, limit_mm_s=3000, min_gap_us=0,
+                 min_span_us=80000)
+    trk = runtime.PlateTracker(B, max_tracks=128, ncls=model, device=dev)
+    trk.enable_speed(runtime.GroundPlane(B, [plane] * B, device=dev))
+    times, events, fresh, eligible = dict(track=[], speed=[], steady=[]), [], [], []
+    for k in range(args.reps + 2):
+        frames = batcher.put([pool[(j + k) % len(pool)] for j in range(B)])
+        xx, _ = runtime.preprocess_frames(frames, size, stride, tdt, batch=B, out=x)
+        det, count, _ = runtime.detect_padded(model, xx, conf, iou, max_det)
+        runtime.rescale_round_batch(det, count, net_hw, [f.shape for f in frames])
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        held, trk._speed = trk._speed, None        # the update alone; the stage it would enqueue at its end follows by hand
+        ev[0].record()
+        trk.update(det, count)
+        ev[1].record()
+        trk._speed = held
+        trk._speed_update()
+        ev[2].record()
+        n_events = int(trk.last_speed[2].sum())    # (host reads: between the two timed calls, not inside one)
+        n_fresh = int((trk.last_speed[0][:, :, 7] >> 8 & 1).sum())
+        ev[3].record()
+        trk._speed_update()
+        ev[4].record()
+        torch.cuda.synchronize()
+        if k >= 2:
+            times['track'].append(ev[0].elapsed_time(ev[1]))
+            times['speed'].append(ev[1].elapsed_time(ev[2]))
+            times['steady'].append(ev[3].elapsed_time(ev[4]))
+            events.append(n_events)
+            fresh.append(n_fresh)
+            eligible.append(int((trk.last_speed[0][:, :, 0] >= 0).sum()))
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    return dict(streams=B, reps=args.reps, speed_ms=round(med['speed'], 4), steady_ms=round(med['steady'], 4), track_ms=round(med['track'], 4),
+                speed_over_track=round(med['speed'] / med['track'], 4), speed_runs_ms=[round(v, 4) for v in times['speed']],
+                track_runs_ms=[round(v, 4) for v in times['track']], events_per_step=round(float(np.mean(events)), 1),
+                fresh_slots_per_step=round(float(np.mean(fresh)), 1), eligible_slots_per_step=round(float(np.mean(eligible)), 1))
 
 
 def redact_stages(args, model, dev, tdt, batcher, pool, x, net_hw):

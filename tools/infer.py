@@ -14,6 +14,7 @@
                            [--watch-live [--watch-live-min-hits 3]]]
                           [--track --sightings C [--sight-window N] [--sight-min-hits 1] [--sight-mismatch 1] [--sight-cost F]]
                           [--track --zones FILE [--zones-min-hits 1]]
+                          [--track --speed FILE [--speed-min-hits 1] [--speed-confirm 2]]
                           [--save-jpeg Q]
                           [--overlay [--overlay-font TTF] [--overlay-size 24] [--overlay-thickness 2] [--overlay-alpha 256 160 256]]
                           [--tile H W --tile-gate [--tile-gate-thres 2.0] [--tile-gate-min-cells 1] [--tile-gate-refresh 50]
@@ -123,6 +124,13 @@ _FLAGS = [
                           'x3 y3 ...`, an optional `S:` stream prefix) in frame pixels; write the crossings of the live tracks to '
                           'crossings.txt and zone entries, exits, dwell alerts and tracks that ended inside to zones.txt')),
     ('--zones-min-hits', dict(type=int, default=1, metavar='N', help='with --zones: detections a track needs before it is tested')),
+    ('--speed', dict(type=str, default=None, metavar='FILE',
+                     help='with --track: a calibration file (`plane h0 .. h8` or `points x y X Y ...`: frame pixels to metres on the plane '
+                          'the plates move in; `fps F` or `period_us N`; `limit KMH`; `gap_ms N`; `span_ms N`; an optional `S:` stream '
+                          'prefix); write peak and chord speed of every ended track to speeds.txt and the tracks over the limit, while '
+                          'they are still live, to speeding.txt')),
+    ('--speed-min-hits', dict(type=int, default=1, metavar='N', help='with --speed: detections a track needs before it is measured')),
+    ('--speed-confirm', dict(type=int, default=2, metavar='N', help='with --speed: estimates in a row over the limit that make an alert')),
     ('--tile-gate', dict(action='store_true', help='with --tile: the source is one fixed camera (frames of one size); run the network only on '
                                                    'the tiles whose pixels changed since they were last detected, keep the rows of the others')),
     ('--tile-gate-thres', dict(type=float, default=2.0, metavar='F',
@@ -170,7 +178,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1, tile_gate_refresh=50,
         tile_gate_illum='none', tile_gate_max_gain=1.5, sightings=None, sight_window=None, sight_min_hits=1, sight_mismatch=1, sight_cost=None,
         save_jpeg=None, overlay=False, overlay_font=None, overlay_size=24, overlay_thickness=2, overlay_alpha=(256, 160, 256),
-        zones=None, zones_min_hits=1):
+        zones=None, zones_min_hits=1, speed=None, speed_min_hits=1, speed_confirm=2):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track or redact or overlay) and not osp.exists(out_dir):
@@ -196,7 +204,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
                       sight_min_hits=sight_min_hits, sight_mismatch=sight_mismatch, sight_cost=sight_cost,
                       save_jpeg=save_jpeg, overlay=overlay, overlay_font=overlay_font, overlay_size=overlay_size,
                       overlay_thickness=overlay_thickness, overlay_alpha=tuple(overlay_alpha), zones=zones,
-                      zones_min_hits=zones_min_hits).infer(
+                      zones_min_hits=zones_min_hits, speed=speed, speed_min_hits=speed_min_hits, speed_confirm=speed_confirm).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

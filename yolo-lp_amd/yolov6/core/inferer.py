@@ -64,7 +64,7 @@ class Inferer:
                  tile_gate_min_cells=1, tile_gate_refresh=50, tile_gate_illum='none', tile_gate_max_gain=1.5, stack_shots=False,
                  stack_search=2, stack_max_frames=64, stack_min_width=0.0, sightings=None, sight_window=None, sight_min_hits=1,
                  sight_mismatch=1, sight_cost=None, save_jpeg=None, overlay=False, overlay_font=None, overlay_size=24, overlay_thickness=2,
-                 overlay_alpha=(256, 160, 256), zones=None, zones_min_hits=1):
+                 overlay_alpha=(256, 160, 256), zones=None, zones_min_hits=1, speed=None, speed_min_hits=1, speed_confirm=2):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -131,7 +131,13 @@ class Inferer:
         ``zones`` = the path of a file of lines and zones (with ``track``; ``yolov6.utils.zones`` states the rule and ``parse_zones``
         the format; a stream prefix names the tracker's stream: 0 = the image files, 1 + k = the k-th video): the live tracks of at
         least ``zones_min_hits`` detections are tested against them after every tracker call; ``infer`` writes ``crossings.txt`` and
-        ``zones.txt`` and logs the totals per line; every other output is what it is without it."""
+        ``zones.txt`` and logs the totals per line; every other output is what it is without it.
+        ``speed`` = the path of a calibration file (with ``track``; ``yolov6.utils.speed`` states the rule and ``parse_ground`` the
+        format, stream prefixes as for ``zones``): a homography from frame pixels to metres on the plane the plates move in, the frame
+        rate and a limit per stream.  The live tracks of at least ``speed_min_hits`` detections are measured after every tracker call;
+        ``infer`` writes ``speeds.txt`` (``id text peak_kmh chord_kmh`` per ended track with at least two samples) and
+        ``speeding.txt`` (``frame id text kmh limit_kmh`` for a track over the limit for ``speed_confirm`` estimates in a row, at the
+        frame it fired); every other output is what it is without it."""
         self.__dict__.update(locals())
         self._overlay = None
         if overlay:
@@ -166,6 +172,13 @@ class Inferer:
             if not track:
                 raise ValueError('zones needs track=True')
             check_min_hits(zones_min_hits)
+        if speed is not None:
+            from yolov6.utils.speed import check_confirm
+            from yolov6.utils.watch_live import check_min_hits
+            if not track:
+                raise ValueError('speed needs track=True')
+            check_min_hits(speed_min_hits)
+            check_confirm(speed_confirm)
         if watch_live:
             from yolov6.utils.watch_live import check_min_hits
             if watchlist is None:
@@ -582,6 +595,12 @@ class Inferer:
             lines, polys, self._zone_line_names, self._zone_names = zn.parse_zones(self.zones, 1 + len(videos))
             make = runtime.ZoneMap if self.device.type != 'cpu' else zn.ZoneMapNp
             self._tracker.enable_zones(make(1 + len(videos), lines, polys, device=self.device), self.zones_min_hits)
+        self._track_speed_events = []   # with speed: (kind, frame, id, best [8] or None, value, aux) per event
+        if self.speed is not None:
+            from yolov6.utils import speed as sp
+            make = runtime.GroundPlane if self.device.type != 'cpu' else sp.GroundPlaneNp
+            ground = make(1 + len(videos), sp.parse_ground(self.speed, 1 + len(videos)), device=self.device)
+            self._tracker.enable_speed(ground, self.speed_min_hits, self.speed_confirm)
         if self.redact_hold:
             self._tracker.enable_hold(min_hits=self.redact_hold_min_hits)
         if self.redact_lookback is not None:
@@ -661,6 +680,19 @@ class Inferer:
                         ended = [ended_i[s, k, 4:12] for k in range(min(int(ended_count[s]), ended_i.shape[1])) if ended_i[s, k, 0] == e[2]]
                         best = ended[0].copy() if ended else None
                     self._track_zone_events.append((s, int(e[0]), int(e[1]), int(e[4]), int(e[2]), best, int(e[5])))
+
+        if self._tracker.last_speed is not None:    # the speed events of the same update
+            _, speed_ev, speed_count = self._tracker.last_speed
+            if torch.is_tensor(speed_ev):
+                speed_ev, speed_count = speed_ev.cpu().numpy(), speed_count.cpu().numpy()
+            for s, c in enumerate(speed_count.tolist()):
+                for e in speed_ev[s, :min(c, speed_ev.shape[1])]:      # (a slot yields at most one: none is lost)
+                    if e[0] != 3:
+                        best = [int(e[8 + p // 4]) >> 8 * (p % 4) & 0xFF for p in range(8)]
+                    else:                           # ended: the read of the ended record of the same id in this call
+                        ended = [ended_i[s, k, 4:12] for k in range(min(int(ended_count[s]), ended_i.shape[1])) if ended_i[s, k, 0] == e[2]]
+                        best = ended[0].copy() if ended else None
+                    self._track_speed_events.append((int(e[0]), int(e[4]), int(e[2]), best, int(e[5]), int(e[11])))
 
     def _track_update(self, det, count, paths, frames=None):
         """One tracker update of a padded group: det [B,max_det,28] + count [B] (numpy on the CPU, device tensors on a GPU) of
@@ -773,6 +805,16 @@ class Inferer:
             LOGGER.info('line totals: ' + ('; '.join('%s%s +%d -%d' % ('' if len(self._zone_line_names) == 1 else '%d:' % s, name,
                                                                       totals[s, 0, l], totals[s, 1, l])
                                                      for s, ns in enumerate(self._zone_line_names) for l, name in enumerate(ns)) or 'no lines'))
+        if self.speed is not None:
+            from yolov6.utils.speed import KIND_ALERT, kmh
+            names = (self.pro_names, self.alp_names, self.ads_names)
+            with open(osp.join(save_dir, 'speeds.txt'), 'w') as fs, open(osp.join(save_dir, 'speeding.txt'), 'w') as fa:
+                for kind, frame, tid, best, value, aux in self._track_speed_events:
+                    text = '-' if best is None else plate_text(best, *names)
+                    if kind == KIND_ALERT:
+                        fa.write('%d %d %s %.1f %.1f\n' % (frame, tid, text, kmh(value), kmh(aux)))
+                    else:
+                        fs.write('%d %s %.1f %.1f\n' % (tid, text, kmh(value), kmh(aux)))
         if self.best_shots:
             names = self._write_track_images(save_dir, 'shots', [s[2] for s in self._track_shots])
             with open(osp.join(save_dir, 'shots.txt'), 'w') as f:

@@ -41,6 +41,7 @@ LP_WATCH_MAX_ENTRIES, LP_WATCH_MAX_COST = 1 << 24, 32768   # lp_watch_match: ent
 LP_WATCH_BLOCK_ENTRIES, LP_WATCH_QUERY_BLOCK = 2048, 16   # ... entries per workgroup of its scan, reads per LDS table
 LP_SIGHT_MAX_CAPACITY = 1 << 24   # lp_sight_update: slots of a log of sightings
 LP_ZONE_MAX_LINES, LP_ZONE_MAX_ZONES, LP_ZONE_MAX_VERTS, LP_ZONE_MAP_WORDS = 16, 8, 16, 368   # lp_zone_update: the packed geometry of a stream
+LP_SPEED_MAP_WORDS, LP_SPEED_MEMO_WORDS, LP_SPEED_RING = 32, 48, 8   # lp_speed_update: the packed calibration of a stream, the memo of a slot
 LP_SIGHT_BLOCK_ENTRIES, LP_SIGHT_QUERY_BLOCK = 1024, 16   # ... slots per workgroup of its scan, reads per LDS table
 LP_TILE_GATE_TILE_WORDS = 8  # lp_tile_gate_update: int32 words per entry of the device tile table
 LP_EVAL_NCOUNTS = 43  # lp_eval_counts: length of the counts vector (include/lp_hip.h)
@@ -260,6 +261,9 @@ SYMBOLS = {
     'lp_zone_state_bytes': (c_size_t, [c_int, c_int]),
     'lp_zone_update': (c_int, [c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                c_void_p, c_void_p]),
+    'lp_speed_state_bytes': (c_size_t, [c_int, c_int]),
+    'lp_speed_update': (c_int, [c_void_p, c_int, c_int, POINTER(c_int), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_int, c_void_p]),
     'lp_tile_gate_luma_batch': (c_int, [POINTER(TileGateDesc), c_int, c_void_p]),
     'lp_tile_gate_update': (c_int, [POINTER(TileGateDesc), c_int, POINTER(c_int), c_int, c_void_p, POINTER(c_int), c_int, c_void_p,
                                     ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

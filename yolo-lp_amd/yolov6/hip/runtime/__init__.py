@@ -28,7 +28,7 @@ from .tiles import (_tile_inputs, detect_tiled, detect_tiled_padded, detect_tile
                     merge_tiles_buffers, plan_tiled, preprocess_tiles)
 from .tile_gate import TileGate
 from .watch import SightLog, Watchlist
-from .tracker import PlateTracker, ZoneMap
+from .tracker import GroundPlane, PlateTracker, ZoneMap
 from .lookback import LookbackRedactor
 
 # names of other packages that callers have always found here as well

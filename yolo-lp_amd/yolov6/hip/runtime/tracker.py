@@ -1,5 +1,6 @@
 """Plate tracking across video frames (lp_track_update; yolov6/utils/track.py states the rules) and the tracker's add-ons: hold,
-best shot, stack, watchlist, live watchlist, sightings, and lines and zones (lp_zone_update; yolov6/utils/zones.py states the rule)."""
+best shot, stack, watchlist, live watchlist, sightings, lines and zones (lp_zone_update; yolov6/utils/zones.py states the rule), and the speed on a calibrated plane
+(lp_speed_update; yolov6/utils/speed.py states the rule)."""
 import ctypes
 
 import torch
@@ -43,6 +44,24 @@ class ZoneMap:
             raise RuntimeError('the packed zone map and lp_hip.h disagree')
         check_packed(self.packed_np)
         self.device = _cuda_device('cuda' if device is None else device, 'ZoneMap lives on a GPU (ZoneMapNp is the CPU form)')
+        self.packed = torch.from_numpy(self.packed_np).to(self.device)
+
+
+class GroundPlane:
+    """The calibrated plane of each of ``n_streams`` streams on the device (lp_speed_update; ``yolov6.utils.speed`` states the rule and
+    the packed layout): the constructor of ``speed.GroundPlaneNp`` -- ``planes``: per stream None or a dict with ``H`` (3 x 3, frame
+    pixels -> metres on the plane the plates move in: calibrate at plate height) and optionally ``period_us``, ``limit_mm_s``,
+    ``min_gap_us``, ``min_span_us`` -- validated on the host and uploaded once; a changed calibration is a new object.
+    ``planes_np`` / ``packed_np``: the checked host copies; ``packed``: int32 [S, 32] on the device."""
+
+    def __init__(self, n_streams, planes=None, device=None):
+        from yolov6.utils.speed import GroundPlaneNp, check_packed
+        ref = GroundPlaneNp(n_streams, planes)
+        self.n_streams, self.planes_np, self.packed_np = ref.n_streams, ref.planes_np, ref.packed
+        if self.packed_np.shape[1] != abi.LP_SPEED_MAP_WORDS:
+            raise RuntimeError('the packed ground map and lp_hip.h disagree')
+        check_packed(self.packed_np)
+        self.device = _cuda_device('cuda' if device is None else device, 'GroundPlane lives on a GPU (GroundPlaneNp is the CPU form)')
         self.packed = torch.from_numpy(self.packed_np).to(self.device)
 
 
@@ -96,6 +115,13 @@ class PlateTracker:
         #: (zone_ev [S,max_events,12], zone_count [S], zone_occ [S,8], zone_totals [S,2,16]) int32 of the last ``update`` after
         #: ``enable_zones``, else None
         self.last_zone = None
+        self._speed = None
+        #: (speed_i [S,max_tracks,8], speed_ev [S,max_events,12], speed_count [S]) int32 of the last ``update`` after
+        #: ``enable_speed``, else None
+        self.last_speed = None
+        #: int64 [S] on the device: the clock of ``enable_speed(..., clock=True)`` in microseconds; the caller fills it before every
+        #: call, a captured graph reads it in place
+        self.speed_clock = torch.zeros(self.n_streams, dtype=torch.int64, device=self.device)
 
     def reset(self, streams=None):
         """Zero the state of ``streams`` (all for None): no tracks, frame counter, next id and ``dropped`` at 0; their best-shot
@@ -111,6 +137,8 @@ class PlateTracker:
             _zero_streams(self._shots['state'], self.n_streams, streams)
         if self._zones is not None:
             _zero_streams(self._zones['memo'], self.n_streams, streams)
+        if self._speed is not None:
+            _zero_streams(self._speed['memo'], self.n_streams, streams)
 
     @property
     def dropped(self):
@@ -157,7 +185,55 @@ class PlateTracker:
             self.sight_now.add_(1)
         if self._zones is not None:
             self._zone_update()
+        if self._speed is not None:
+            self._speed_update()
         return out
+
+    # ---- the speed of the live tracks on a calibrated plane (lp_speed_update; yolov6/utils/speed.py states the rule) ---------------
+    def enable_speed(self, ground, min_hits=1, confirm=2, max_events=None, clock=False):
+        """From now on every ``update`` / ``update_with_shots`` / ``flush_all*`` also enqueues, at its end on the same stream (behind
+        the zones update), lp_speed_update of the live tracks of at least ``min_hits`` hits on ``ground`` (a ``GroundPlane`` of this
+        device and of the tracker's ``n_streams``).  ``last_speed`` = (speed_i [S,max_tracks,8], speed_ev [S,max_events,12], speed_count
+        [S]) int32: per slot (id, speed, vx, vy in mm/s, X_mm, Y_mm of the newest sample, span_ms, n | fresh << 8 | alerted << 9), or
+        (-1, 0, ...) for a slot without an eligible track, speed -1 before the first estimate; per stream the events in slot order as
+        (kind, 0, id, slot, frame, value, X_mm, Y_mm, key_lo, key_hi, hits, aux) with kind 1 = over the plane's limit for ``confirm``
+        estimates in a row (value: the speed, aux: the limit; once per track) and 3 = ended (value: the peak, aux: the chord speed from
+        its first to its last sample); their number, not capped at ``max_events`` (default ``max_tracks``).  With ``clock`` true the
+        time of a stream's newest frame is ``speed_clock``, a device int64 [S] in microseconds that the caller fills before every
+        call; else it is the frame counter times the plane's period.  Persistent buffers, no host read, no allocation per call.
+        Returns, state and every other buffer are what they are without it.  Calling it again zeroes the memo;
+        ``enable_speed(None)`` turns it off.  ``PlateTrackerNp.enable_speed`` is the same on the CPU, on every int32."""
+        from yolov6.utils import speed, watch_live
+        self.last_speed = None
+        if ground is None:
+            self._speed = None
+            return
+        if not isinstance(ground, GroundPlane) or ground.device != self.device or ground.n_streams != self.n_streams:
+            raise ValueError('enable_speed needs a GroundPlane of %d streams on the tracker\'s device %s' % (self.n_streams, self.device))
+        min_hits, confirm = watch_live.check_min_hits(min_hits), speed.check_confirm(confirm)
+        max_events = self.max_tracks if max_events is None else int(max_events)
+        if max_events < 0:
+            raise ValueError('max_events must be >= 0')
+        S, T, lib = self.n_streams, self.max_tracks, abi.load()
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self._speed = dict(
+            ground=ground, clock=self.speed_clock if clock else None, min_hits=min_hits, confirm=confirm, max_events=max_events, ncls=(ctypes.c_int * 8)(*self.ncls),
+            memo=torch.zeros(lib.lp_speed_state_bytes(S, T) // 4, **i32).view(S, T, abi.LP_SPEED_MEMO_WORDS),
+            rows=torch.empty(S, T, 8, **i32), ev=torch.empty(S, max_events, 12, **i32), count=torch.empty(S, **i32))
+
+    def speed_memo(self):
+        """The memo of ``enable_speed``: int32 [S,max_tracks,48] on the device (``yolov6.utils.speed`` states the layout), else None."""
+        return None if self._speed is None else self._speed['memo']
+
+    def _speed_update(self):
+        """Enqueue lp_speed_update on the state as it stands."""
+        sp = self._speed
+        with torch.cuda.device(self.device):
+            abi.check(abi.load().lp_speed_update(_dptr(self.state), self.n_streams, self.max_tracks, sp['ncls'], _dptr(sp['ground'].packed),
+                                                 _dptr(sp['clock']), sp['min_hits'], sp['confirm'], _dptr(sp['memo']), _dptr(sp['rows']),
+                                                 _dptr(sp['ev']), _dptr(sp['count']), sp['max_events'], _stream_ptr(self.device)),
+                      'lp_speed_update')
+        self.last_speed = (sp['rows'], sp['ev'], sp['count'])
 
     # ---- lines and zones on the live tracks (lp_zone_update; yolov6/utils/zones.py states the rule) ------------------------------
     def enable_zones(self, zone_map, min_hits=1, max_events=None):

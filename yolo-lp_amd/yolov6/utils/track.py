@@ -200,6 +200,11 @@ class PlateTrackerNp:
         self._zones = None
         #: (zone_ev, zone_count, zone_occ, zone_totals) of the last ``update`` after ``enable_zones``, else None
         self.last_zone = None
+        self._speed = None
+        #: (speed_i, speed_ev, speed_count) of the last ``update`` after ``enable_speed``, else None
+        self.last_speed = None
+        #: int64 [S]: the clock of ``enable_speed(..., clock=True)`` in microseconds; the caller sets it before every call
+        self.speed_clock = np.zeros(S, np.int64)
 
     _SLOT_ARRAYS = ('id', 'first', 'last', 'hits', 'misses', 'box', 'cor', 'vel', 'votes', 'total')
 
@@ -214,6 +219,8 @@ class PlateTrackerNp:
             self._stack['np'].reset(streams)
         if self._zones is not None:
             self._zones[0].reset(streams)
+        if self._speed is not None:
+            self._speed[0].reset(streams)
 
     def enable_stack(self, search=2, max_frames=64, min_width=0.0, min_sharp=0, crop_hw=(64, 192), max_crops=16, min_score=0.0):
         """One denoised picture per track (``yolov6.utils.stack`` states the rule and its limits): from now on ``update_stack``,
@@ -310,6 +317,29 @@ class PlateTrackerNp:
         if max_events < 0:
             raise ValueError('max_events must be >= 0')
         self._zones = (ZoneEventsNp(self, zone_map, min_hits), max_events)
+
+    def enable_speed(self, ground, min_hits=1, confirm=2, max_events=None, clock=None):
+        """From now on every ``update`` / ``flush_all`` also estimates the speed of the live tracks of at least ``min_hits`` hits on the
+        calibrated plane of ``ground`` -- anything with ``n_streams`` and ``planes_np`` (``speed.GroundPlaneNp``,
+        ``runtime.GroundPlane``) -- behind the zones update (``yolov6.utils.speed`` states the rule), and leaves (speed_i
+        [S, max_tracks, 8], speed_ev [S, max_events, 12], speed_count [S]) int32 in ``last_speed``: per slot (id, speed, vx, vy in mm/s,
+        X_mm, Y_mm, span_ms, flags), and the alerts (kind 1: over the plane's limit for ``confirm`` estimates in a row, once per track)
+        and the ended tracks (kind 3: peak and chord speed); ``max_events`` defaults to ``max_tracks``.  With ``clock`` true the time
+        of a stream's newest frame is ``speed_clock`` [S] (int64 microseconds, set by the caller before every call), else the frame
+        counter times the plane's period.  Every other output and the state stay what they are.  Calling it again starts from an
+        empty memo; ``enable_speed(None)`` turns it off."""
+        from yolov6.utils.speed import SpeedNp
+        self.last_speed = None
+        if ground is None:
+            self._speed = None
+            return
+        if ground.n_streams != self.n_streams:
+            raise ValueError('the ground map has %d streams, the tracker %d' % (ground.n_streams, self.n_streams))
+        self._speed = (SpeedNp(ground, self.max_tracks, min_hits, confirm, max_events), bool(clock))
+
+    def speed_memo(self):
+        """The memo of ``enable_speed``: int32 [S, max_tracks, 48], else None."""
+        return None if self._speed is None else self._speed[0].memo
 
     @property
     def zone_memo(self):
@@ -528,4 +558,6 @@ class PlateTrackerNp:
             self.sight_now += 1
         if self._zones is not None:
             self.last_zone = self._zones[0].step(self._zones[1])
+        if self._speed is not None:
+            self.last_speed = self._speed[0].step(self, self.speed_clock if self._speed[1] else None)
         return det_out, tid, ended_i, ended_f, ended_count
