@@ -274,7 +274,12 @@ def random_track_case(seed, n_streams=3, max_det=20, n_calls=6, max_B=8, n_obj=6
     objects with integer boxes and integer velocities plus +-1 px jitter, births and deaths, rows missing, duplicate rows (equal
     IoUs), NaNs in boxes and confidences, ids with noise (also outside the head), counts below 0 and above max_det with
     arbitrary rows behind the count, skipped frames (-1), streams without frames in a call, and a flush of everything in the
-    last call.  ``Bs``: the calls' frame counts (default: drawn from 1..max_B)."""
+    last call.  ``Bs``: the calls' frame counts (default: drawn from 1..max_B).
+
+    These cases lie on an EXACT GRID: integer coordinates and velocities and confidences k / 8, so every fp32 operation of the
+    tracker on them (expansion by 0 or 0.5, areas, sums of votes) is exact, and a kernel that fused a multiply-add, summed in
+    another order or divided through a reciprocal would still produce these bits.  They test the rules, not the rounding;
+    ``tests/offgrid.py`` has their off-grid twins (``offgrid_twin``) and the constructed cases on which one ulp decides."""
     rng = np.random.default_rng(seed)
     objs = [[] for _ in range(n_streams)]
 

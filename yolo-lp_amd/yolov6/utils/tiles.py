@@ -18,6 +18,15 @@ def _sort_keys(score, slot):
     return ((~u).astype(np.uint64) << np.uint64(32)) | slot.astype(np.uint64)
 
 
+def row_scores(rows):
+    """fp32 [n]: (c12 + ... + c19) / 8 of rows [n, 28], summed left to right."""
+    with np.errstate(all='ignore'):
+        score = rows[:, 12] + rows[:, 13]
+        for c in range(14, 20):
+            score = score + rows[:, c]
+        return score / np.float32(8.0)
+
+
 def overlaps(kept, box, thres, metric):
     """bool [K]: which of the earlier boxes ``kept`` [K,4] overlap ``box`` [4] by more than ``thres`` (fp32 xyxy).
     'iou': torchvision's ``inter / (area_i + area_j - inter) > thres``; 'ios': ``inter / min(area_i, area_j) > thres``;
@@ -125,11 +134,7 @@ def merge_tiles_np(det_t, count_t, tiles, frame_shapes, thres, max_det, metric='
             continue
         rows, tile_of = np.concatenate(rows), np.concatenate(tile_of)
         src_of, slots = np.concatenate(src_of), np.concatenate(slots)
-        with np.errstate(all='ignore'):
-            score = rows[:, 12] + rows[:, 13]
-            for c in range(14, 20):
-                score = score + rows[:, c]
-            score = score / np.float32(8.0)
+        score = row_scores(rows)
         order = np.argsort(_sort_keys(score, slots), kind='stable')
         kept = []
         for i in order:

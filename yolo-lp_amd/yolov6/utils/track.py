@@ -137,6 +137,47 @@ def iou_matrix(a, b):
     return ovr
 
 
+def predict_boxes(box, vel, k):
+    """Rule 1: boxes [..., 4] shifted by (vx * k, vy * k) of ``vel`` [..., 2]; the products are rounded, then the adds."""
+    with np.errstate(all='ignore'):
+        dx, dy = vel[..., 0] * k, vel[..., 1] * k
+        return np.stack([box[..., 0] + dx, box[..., 1] + dy, box[..., 2] + dx, box[..., 3] + dy], -1)
+
+
+def held_geometry(box, cor, vel, k):
+    """Rule 11: (box [4], corners [8]) of a held row: dx = vx * k, dy = vy * k (products rounded), then the adds."""
+    with np.errstate(all='ignore'):
+        d = np.array([vel[0] * k, vel[1] * k], f32)
+        return box + np.tile(d, 2), cor + np.tile(d, 4)
+
+
+def centre_velocity(new, old, k):
+    """Rule 4: (vx, vy) [..., 2] = the move of the centre (x1 + x2) * 0.5f, (y1 + y2) * 0.5f from box ``old`` to ``new`` [..., 4],
+    divided by ``k``."""
+    with np.errstate(all='ignore'):
+        return np.stack([((new[..., 0] + new[..., 2]) * f32(0.5) - (old[..., 0] + old[..., 2]) * f32(0.5)) / k,
+                         ((new[..., 1] + new[..., 3]) * f32(0.5) - (old[..., 1] + old[..., 3]) * f32(0.5)) / k], -1)
+
+
+def new_score(row):
+    """Rule 6: (c12 + ... + c19) / 8.0f of a row, summed left to right."""
+    with np.errstate(all='ignore'):
+        score = row[12] + row[13]
+        for c in range(14, 20):
+            score = score + row[c]
+        return score / f32(8.0)
+
+
+def over_threshold(iou, thres):
+    """Rule 3: (double)iou > thres of fp32 IoUs and a Python float."""
+    return iou.astype(np.float64) > thres
+
+
+def vote_share(v, tot):
+    """Rule 8: votes / total, one fp32 division."""
+    return v / tot
+
+
 def plate_text(ids, pro_names=None, alp_names=None, ads_names=None):
     """The plate string of eight head ids (province, alphabet, six characters) with the three name lists of a data yaml
     (``names`` / ``alps`` / ``ads``); without names, or for an id outside its list, the ids joined by spaces."""
@@ -366,12 +407,7 @@ class PlateTrackerNp:
             if slot_row[t] >= 0 or self.hits[s, t] < hp['min_hits'] or self.misses[s, t] > hp['max_misses']:
                 continue                                  # matched; ended (hits is 0 again); too young; missed for too long
             row = np.zeros(DET_COLS, f32)
-            with np.errstate(all='ignore'):
-                k = f32(self.misses[s, t])
-                dx, dy = self.vel[s, t, 0] * k, self.vel[s, t, 1] * k
-                d = np.array([dx, dy], f32)
-                row[0:4] = self.box[s, t] + np.tile(d, 2)
-                row[4:12] = self.cor[s, t] + np.tile(d, 4)
+            row[0:4], row[4:12] = held_geometry(self.box[s, t], self.cor[s, t], self.vel[s, t], f32(self.misses[s, t]))
             best, share = self.read(s, t)
             row[12:20], row[20:28] = share, best.astype(f32)
             out.append((row, int(self.id[s, t])))
@@ -389,8 +425,12 @@ class PlateTrackerNp:
             best[p] = int(np.argmax(v))              # first index of the largest (the votes are never NaN)
             tot = self.total[s, t, p]
             with np.errstate(all='ignore'):
-                share[p] = v[best[p]] / tot if tot > 0 else f32(0)
+                share[p] = vote_share(v[best[p]], tot) if tot > 0 else f32(0)
         return best, share
+
+    def _add_total(self, s, t, p, conf):
+        """Rule 7: total[p] += conf, one fp32 add."""
+        self.total[s, t, p] = self.total[s, t, p] + conf
 
     def _vote(self, s, t, row):
         for p in range(HEADS):
@@ -398,7 +438,7 @@ class PlateTrackerNp:
             if conf > 0 and v >= 0 and v < f32(self.ncls[p]):
                 with np.errstate(all='ignore'):
                     self.votes[s, t, p, int(v)] = self.votes[s, t, p, int(v)] + conf
-                    self.total[s, t, p] = self.total[s, t, p] + conf
+                    self._add_total(s, t, p, conf)
 
     def _end(self, s, t, ended):
         best, share = self.read(s, t)
@@ -420,12 +460,9 @@ class PlateTrackerNp:
         row_slot = np.full(n, -1, np.int64)
         kf = (self.misses[s] + 1).astype(f32)
         if n and live.any():
-            with np.errstate(all='ignore'):
-                dx, dy = self.vel[s, :, 0] * kf, self.vel[s, :, 1] * kf
-                b = self.box[s]
-                pred = np.stack([b[:, 0] + dx, b[:, 1] + dy, b[:, 2] + dx, b[:, 3] + dy], -1)
+            pred = predict_boxes(self.box[s], self.vel[s], kf)
             iou = iou_matrix(expand_boxes(pred, e), expand_boxes(rows[:n, :4], e))
-            pair = live[:, None] & (iou.astype(np.float64) > self.match_thres)
+            pair = live[:, None] & over_threshold(iou, self.match_thres)
             sl, rw = np.nonzero(pair)
             self.stats['pairs'] += len(sl)
             self.stats['ties'] += len(sl) - len(np.unique(iou[sl, rw]))
@@ -437,9 +474,7 @@ class PlateTrackerNp:
             r = slot_row[t]
             if r >= 0:
                 row, b = rows[r], self.box[s, t]
-                with np.errstate(all='ignore'):
-                    self.vel[s, t, 0] = ((row[0] + row[2]) * f32(0.5) - (b[0] + b[2]) * f32(0.5)) / kf[t]
-                    self.vel[s, t, 1] = ((row[1] + row[3]) * f32(0.5) - (b[1] + b[3]) * f32(0.5)) / kf[t]
+                self.vel[s, t] = centre_velocity(row[0:4], b, kf[t])
                 self.box[s, t], self.cor[s, t] = row[0:4], row[4:12]
                 self.hits[s, t] += 1
                 self.misses[s, t] = 0
@@ -454,12 +489,7 @@ class PlateTrackerNp:
             if row_slot[r] >= 0:
                 continue
             row = rows[r]
-            with np.errstate(all='ignore'):
-                score = row[12] + row[13]
-                for c in range(14, 20):
-                    score = score + row[c]
-                score = score / f32(8.0)
-            if not np.float64(score) >= self.new_thres:
+            if not np.float64(new_score(row)) >= self.new_thres:
                 continue
             free = np.nonzero(~self.live(s))[0]
             if not len(free):
