@@ -806,6 +806,81 @@ int lp_overlay_draw_batch(const lp_redact_desc* desc, int n_frames, const float*
                           const unsigned char* atlas, const uint16_t* glyph_of, int32_t* status /* [n_frames,max_det] */,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* lp_overlay_scene_batch: draw what the tracker knows about the scene onto B frames IN PLACE -- the zones of lp_zone_update as a
+ * translucent fill plus an outline, its directed lines with a marker on their +1 side, a label per line with its running +/-
+ * totals, a label per zone with its occupancy (in an alert colour while a dwell alert fires), and a km/h tag beside every drawn
+ * plate whose track has a speed estimate of lp_speed_update -- in BGR frames or in the planes of NV12 frames, from DEVICE-resident
+ * inputs with no host read.  On a stream it goes after the redaction and BEFORE lp_overlay_draw_batch, so zone fills lie under the
+ * plate outlines.  The reference draws nothing; yolov6/utils/scene.py::draw_scene_np restates the rules below byte for byte.  The
+ * picture agrees with lp_zone_update: a filled pixel is an anchor it would call inside, the marker sits on the side it counts +1.
+ *   stream_of (HOST, may be NULL: frame b is stream b) int32 [n_frames]: the stream of a frame; an entry outside [0, n_streams)
+ *   skips the frame (no byte changes, status 0).  packed (DEVICE) int32 [n_streams][LP_ZONE_MAP_WORDS]: the map lp_zone_update
+ *   takes (the caller has validated it: a zone whose vertex count is outside 3..16 is not drawn).  Three optional groups, each
+ *   all given or all NULL: totals [n_streams][2][16] + occ [n_streams][8] (absent: no labels, no zone is busy); zone_ev
+ *   [n_streams][max_events][12] + zone_count [n_streams] (absent: no alert colour); speed_i [n_streams][max_tracks][8] + det
+ *   [n_frames][max_det][28] + count [n_frames] + tid [n_frames][max_det] + status [n_frames][max_det] (absent: no tags); all
+ *   DEVICE int32 (det fp32) as lp_zone_update, lp_speed_update and lp_track_update leave them.  names (DEVICE, may be NULL: empty
+ *   names) uint16 [n_streams][24][LP_SCENE_MAX_NAME]: lines 0..15, then zones 0..7, glyph indices, 0xFFFF ends a name.
+ *   Layers of a frame of stream s, in this order, each one blend of lp_overlay_draw_batch that ends in a byte (one call equals
+ *   the layers applied one at a time):
+ *   1. zone fills, z ascending: pixel (i, j) belongs iff the crossing number over the zone's edges (Vk, Vk+1 mod n) at P = (j + 0.5,
+ *      i + 0.5) is odd; an edge toggles iff (yi > py) != (yj > py) and, with t = (xj - xi) * (py - yi) - (px - xi) * (yj - yi),
+ *      t > 0 if yj > yi, else t < 0: fp64 on the fp32 vertices, op by op, no fused multiply-add, no division -- lp_zone_update's
+ *      test.  Scan rectangle: the vertices' bounds, clamped as an outline's.  Opacity a_fill, or a_fill_busy when occ[s][z] > 0;
+ *      colour zone, or alert when one of the first min(max(zone_count[s], 0), max_events) event lines has kind 4 and index z.
+ *   2. zone outlines, z ascending: the closed polygon V0 -> V1 -> ... -> V0 by the segment test of lp_overlay_draw_batch at
+ *      thickness t (0: none), opacity a_line, the fill's colour; scan rectangle: the bounds grown by t / 2.
+ *   3. lines, l ascending: the segment A -> B likewise in the line colour; then, as its own layer in the mark colour at a_line, the
+ *      marker: M = ((ax + bx) * 0.5, (ay + by) * 0.5), e = B - A, L = ex * ex + ey * ey, dx = px - Mx, dy = py - My,
+ *      s = ex * dy - ey * dx, u = dx * ex + dy * ey, q = |u| + s; the pixel belongs iff L > 0, s >= 0 and q * q <= (m * m) * L,
+ *      m = marker (0: none): a right isosceles triangle of height m, base on the line, apex on the +1 side.  fp64 op by op, no
+ *      division, no square root.  Scan rectangle: M grown by m, clamped.
+ *   4. zone labels z ascending, then line labels l ascending: plate (plate colour, a_plate) and glyphs (text colour, a_text) as
+ *      lp_overlay_draw_batch blends a label.  Zone: the name, ' ', the digits of occ[s][z]; line: the name, ' ', '+', the digits of
+ *      totals[s][0][l], ' ', '-', the digits of totals[s][1][l]; a value < 0 prints as its 32-bit unsigned value (the totals wrap);
+ *      a name glyph >= n_glyphs shows '?'; at most LP_SCENE_MAX_GLYPHS.  atlas (DEVICE) uint8 [n_glyphs][gh][gw] with the fixed
+ *      indices of lp_overlay_draw_batch and 13 '+', 14 '-', 15 '.', 16 ':'.  Placement: the anchor (x, y) is vertex 0 of a zone, B of
+ *      a line; ax = floor(x), ay0 = floor(y), ay1 = ceil(y), each clamped to +-2^20 in double and converted; W = n * gw + 2 * pad,
+ *      H = gh + 2 * pad, q = (t + 1) / 2; ly = ay0 - q - H, and ly = ay1 + q when that is < 0; lx = max(min(ax, w0 - W), 0); the
+ *      rectangle [ly, ly + H) x [lx, lx + W) is clipped to the frame.
+ *   5. speed tags, rows in row order: row r < clamp(count[b], 0, max_det) with tid >= 0 whose quad status (lp_plate_crops_batch's
+ *      rule) is not 3 gets a tag iff speed_i[s] has a slot with id == tid and speed >= 0, the lowest such slot; kmh = (speed * 36 +
+ *      5000) / 10000 in int64; the tag is a label of the digits of kmh on a plate in the tag colour with bx1 = ceil(max x), by0 =
+ *      floor(min y) of the quad (clamped to +-2^20), ly = by0, lx = max(min(bx1 + q, w0 - W), 0), clipped.  status = 1 for a row
+ *      that gets a tag, else 0.
+ *   NV12: Y per pixel, a chroma sample once per layer with wbar = (w00 + w01 + w10 + w11 + 2) >> 2.  Colours are bytes in the frame's
+ *   own format.  No other byte changes: pitch padding, pixels of no layer, skipped frames.
+ * Two kernels per launch pair of at most LP_FRAMES_PER_LAUNCH frames of one format (lp_overlay_scene.hip), in the ownership
+ * structure of lp_overlay_draw_batch: a setup kernel, a thread per (frame, shape) and per (frame, row), writes fixed-size records
+ * with clamped scan rectangles into the workspace (which may hold anything on entry); the draw kernel, a 256-thread workgroup per
+ * 32 x 32 tile and a thread per 2 x 2 block, culls the frame's 72 shape layers and its tags into an LDS list in layer order, returns
+ * before reading a pixel when the list is empty, and otherwise loads its block once, blends in registers and stores once.  The fill
+ * tests every pixel.  Descriptors, streams and style travel by value in the kernel arguments: nothing is uploaded, no host sync,
+ * capturable in a graph.  Every argument is checked before the first launch (LP_ERR_ARG names the frame; nothing is launched):
+ * whatever lp_redact_plates_batch rejects for descriptors; null desc, packed, p or atlas; n_streams < 1; a group that is half
+ * given; max_events < 1 with events, max_tracks or max_det < 1 with tags; t or pad outside 0..16, marker outside
+ * 0..LP_SCENE_MAX_MARKER, an opacity outside 0..256; n_glyphs outside LP_SCENE_FIXED_GLYPHS..LP_OVERLAY_MAX_ATLAS (an atlas too small
+ * for the fixed glyphs); gh or gw outside 1..LP_OVERLAY_MAX_CELL; a workspace that is null, not 16-byte aligned or smaller than
+ * lp_overlay_scene_workspace_bytes(n_frames, max_det with tags, else 0).  n_frames == 0: LP_OK. */
+#define LP_SCENE_MAX_GLYPHS 36   /* a 12-glyph name, " +", 10 digits, " -", 10 digits */
+#define LP_SCENE_MAX_NAME 12
+#define LP_SCENE_MAX_MARKER 64
+#define LP_SCENE_FIXED_GLYPHS 17
+typedef struct lp_scene_style {
+    unsigned char zone[3], alert[3], line[3], mark[3], plate[3], text[3], tag[3];   /* bytes in the frame's own format */
+    int t;                                              /* thickness of outlines and lines, 0..16 (0: none) */
+    int marker;                                         /* height m of a line's direction marker, 0..64 (0: none) */
+    int a_fill, a_fill_busy, a_line, a_plate, a_text;   /* opacities 0..256 */
+    int pad;                                            /* pixels between a label's edge and its glyphs, 0..16 */
+    int n_glyphs, gh, gw;                               /* the atlas: [n_glyphs][gh][gw] */
+} lp_scene_style;
+size_t lp_overlay_scene_workspace_bytes(int n_frames, int max_det);      /* 4640 bytes per frame + 48 per (frame, row); 0 for bad arguments */
+int lp_overlay_scene_batch(const lp_redact_desc* desc, int n_frames, const int32_t* stream_of /* HOST, may be NULL */, int n_streams,
+                           const int32_t* packed, const int32_t* totals, const int32_t* occ, const int32_t* zone_ev,
+                           const int32_t* zone_count, int max_events, const int32_t* speed_i, int max_tracks, const float* det,
+                           const int32_t* count, const int32_t* tid, int max_det, const lp_scene_style* p, const unsigned char* atlas,
+                           const uint16_t* names /* may be NULL */, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* lp_jpeg_encode_batch: complete baseline JPEG files of B frames, written on the device: no pixel crosses PCIe, only the files do.
  * The reference has nothing here; yolov6/utils/jpeg.py states the format and restates it in numpy byte for byte:
  * SOF0, 8 bits, 4:2:0 (MCU 16 x 16: four Y blocks, Cb, Cr), the Annex K quantisation tables scaled by quality 1..100 as libjpeg

@@ -12,6 +12,7 @@
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
     python tools/frames_bench.py --jpeg Q [--jpeg-frames 4] [--jpeg-restart 16] [--tile-frame 2160 3840] [--nv12 [bt601f]] [--redact]
     python tools/frames_bench.py --annotate [--annotate-plates N] [--jpeg-frames 4] [--tile-frame 2160 3840] [--nv12 [bt601f]]
+    python tools/frames_bench.py --annotate --scene L Z [--scene-cover] [--speed] [--jpeg-frames 4] [--tile-frame 2160 3840] [--nv12 [bt709]]
 
 Input is seeded synthetic host frames (uint8 BGR numpy arrays, 1920x1080 by default).  Prints one JSON line with
   - frames/s of the per-frame path (upload, lp_preprocess_letterbox, detect at B=1 with hipGraph replay, lp_rescale_round,
@@ -144,6 +145,10 @@ def parse():
     ap.add_argument('--annotate', action='store_true', help='measure the overlay stage instead (also with --nv12): runtime.draw_plates on '
                     '--jpeg-frames frames of --tile-frame with 0, 4 and 64 plates per frame, against D2H + PIL drawing on one thread and '
                     'against the JPEG encode of the same frames')
+    ap.add_argument('--scene', nargs=2, type=int, default=None, metavar=('L', 'Z'),
+                    help='with --annotate: measure the scene overlay instead: runtime.draw_scene of L lines and Z zones of 16 vertices '
+                         '(with --speed: and a km/h tag on 16 plates per frame) beside runtime.draw_plates and D2H + PIL polygon / line')
+    ap.add_argument('--scene-cover', action='store_true', help='with --scene: zone 0 covers the whole frame')
     ap.add_argument('--annotate-plates', type=int, default=None, metavar='N', help='with --annotate: only N plates per frame')
     ap.add_argument('--jpeg-restart', type=int, default=16, help='with --jpeg: MCUs per restart interval (1..32)')
     ap.add_argument('--runs', type=int, default=3, help='timed runs of the frames/s figures (the spread is reported)')
@@ -1415,6 +1420,134 @@ def annotate_mode(args, dev):
     return out
 
 
+def scene_mode(args, dev):
+    """--annotate --scene L Z: stage ``scene`` = runtime.draw_scene on --jpeg-frames frames of --tile-frame (with --nv12 as NV12 planes):
+    Z zones of 16 vertices (--scene-cover: zone 0 is the whole frame) and L lines with names, totals and occupancies, one dwell
+    alert, and with --speed a km/h tag on each of 16 plates per frame; from device events, the frames restored outside the window.
+    Beside it on the same frames, alternating: ``plates`` = runtime.draw_plates of those 16 plates, and ``host`` = what a caller has
+    without the stage: D2H of the frame plus PIL ``polygon`` / ``line`` / ``text`` on one thread, no file write (wall clock).  The median
+    of --reps after one dropped warm-up repetition.  ``scene_device`` = the two launches alone: the call captured in a graph, 50
+    replays between two events."""
+    import torch
+    from PIL import Image, ImageDraw
+    from yolov6.hip import runtime
+    from yolov6.utils.nv12 import Nv12Frame, bgr_to_nv12_np, nv12_to_bgr_np
+    from yolov6.utils.overlay import Style, build_atlas
+    from yolov6.utils.scene import SceneStyle, build_scene_atlas, names_of
+    sync = torch.cuda.synchronize
+    h0, w0 = args.tile_frame
+    nf, (L, Z), P = args.jpeg_frames, args.scene, 16
+    host = scene_frames(nf, h0, w0)
+    if args.nv12:
+        clean = [bgr_to_nv12_np(f[:h0 & ~1, :w0 & ~1], args.nv12).to(dev) for f in host]
+        work = [Nv12Frame(f.y.clone(), f.uv.clone(), f.matrix) for f in clean]
+    else:
+        clean = [torch.from_numpy(f).to(dev) for f in host]
+        work = [f.clone() for f in clean]
+    rng = np.random.default_rng(11)
+    zones, lines = [], []
+    for z in range(Z):                                                  # 16-vertex stars on a 4 x 2 grid, a sixth of the height across
+        cx, cy, r = w0 * (2 * (z % 4) + 1) / 8, h0 * (2 * (z // 4) + 1) / 4, h0 / 6
+        v = [(cx + (r if k % 2 == 0 else 0.6 * r) * np.cos(k * np.pi / 8), cy + (r if k % 2 == 0 else 0.6 * r) * np.sin(k * np.pi / 8)) for k in range(16)]
+        if z == 0 and args.scene_cover:
+            v = [(-1.0, -1.0)] + [(w0 * k / 7, -1.0 - k % 2) for k in range(1, 7)] + [(w0 + 1.0, -1.0), (w0 + 1.0, h0 + 1.0)] + \
+                [(w0 * k / 7, h0 + 1.0 + k % 2) for k in range(6, 0, -1)] + [(-1.0, h0 + 1.0)]
+        zones.append((v, 10))
+    for l in range(L):
+        lines.append(tuple(float(v) for v in (rng.uniform(0, w0), rng.uniform(0, h0), rng.uniform(0, w0), rng.uniform(0, h0))))
+    S = nf
+    zm = runtime.ZoneMap(S, [lines] * S, [zones] * S, device=dev)
+    atlas = build_scene_atlas(24)
+    font = runtime.SceneFont(atlas, device=dev)
+    names = names_of((None, None, [['line%02d' % l for l in range(L)]] * S, [['zone%d' % z for z in range(Z)]] * S), atlas)
+    names = torch.from_numpy(names.view(np.int16)).to(dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    ev = torch.zeros(S, 8, 12, **i32)
+    ev[:, 0, 0], ev[:, 0, 1] = 4, min(1, max(Z - 1, 0))
+    zone = (ev, torch.ones(S, **i32), torch.from_numpy(rng.integers(0, 5, (S, 8)).astype(np.int32)).to(dev),
+            torch.from_numpy(rng.integers(0, 5000, (S, 2, 16)).astype(np.int32)).to(dev))
+    rows = synthetic_quads(nf, P, h0, w0, seed=P)
+    rows[:, :, 20:28] = rng.integers(0, 24, rows[:, :, 20:28].shape)
+    det = torch.from_numpy(rows).to(dev)
+    count = torch.full((nf,), P, **i32)
+    tid = torch.arange(P, **i32).repeat(nf, 1).contiguous()
+    speed_i = torch.zeros(S, 64, 8, **i32)
+    speed_i[:, :, 0] = -1
+    speed_i[:, :P, 0] = torch.arange(P, **i32)
+    speed_i[:, :P, 1] = torch.from_numpy(rng.integers(2000, 40000, (S, P)).astype(np.int32)).to(dev)
+    tags = dict(speed=(speed_i,), det=det, count=count, tid=tid) if args.speed else {}
+    style = SceneStyle()
+    pnames = [chr(65 + k) for k in range(26)] + [str(k) for k in range(10)]
+    pfont = runtime.OverlayFont(*build_atlas(pnames[:31], pnames[:24], pnames, size=24), device=dev)
+    pstyles = [Style(t=2, a_line=256, a_plate=160, a_text=256, pad=3)]
+
+    def restore():
+        for w, c in zip(work, clean):
+            if args.nv12:
+                w.y.copy_(c.y)
+                w.uv.copy_(c.uv)
+            else:
+                w.copy_(c)
+
+    def events(fn):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        sync()
+        e[0].record()
+        fn()
+        e[1].record()
+        sync()
+        return e[0].elapsed_time(e[1])
+
+    occ_h, tot_h = zone[2].cpu().numpy(), zone[3].cpu().numpy()
+
+    def host_path():
+        for b, f in enumerate(work):
+            if args.nv12:
+                bgr = nv12_to_bgr_np(Nv12Frame(f.y.cpu().numpy(), f.uv.cpu().numpy(), f.matrix))
+            else:
+                bgr = f.cpu().numpy()
+            im = Image.fromarray(np.ascontiguousarray(bgr[:, :, ::-1]))
+            draw = ImageDraw.Draw(im, 'RGBA')                           # a fill with an alpha blends
+            for z, (v, _) in enumerate(zones):
+                draw.polygon([(float(x), float(y)) for x, y in v], fill=(0, 160, 200, 48), outline=(0, 160, 200, 255))
+                draw.text((float(v[0][0]), float(v[0][1])), 'zone%d %d' % (z, occ_h[b, z]), fill=(255, 255, 255, 255))
+            for l, a in enumerate(lines):
+                draw.line([a[0], a[1], a[2], a[3]], fill=(255, 255, 0, 255), width=2)
+                draw.text((a[2], a[3]), 'line%02d +%d -%d' % (l, tot_h[b, 0, l], tot_h[b, 1, l]), fill=(255, 255, 255, 255))
+            if args.speed:
+                for r in rows[b]:
+                    draw.text((float(r[2]), float(r[1])), '88', fill=(255, 255, 255, 255))
+
+    draw_scene = lambda: runtime.draw_scene(work, zm, font, names=names, zone=zone, style=style, **tags)      # noqa: E731
+    t = dict(scene=[], plates=[], host=[])
+    for rep_ in range(args.reps + 1):                                   # the first repetition warms up every path and is dropped
+        restore()
+        t['scene'].append(events(draw_scene))
+        t['plates'].append(events(lambda: runtime.draw_plates(work, det, count, pfont, tid=tid, styles=pstyles)))
+        restore()
+        sync()
+        t0 = time.perf_counter()
+        host_path()
+        t['host'].append((time.perf_counter() - t0) * 1e3)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        draw_scene()
+    dev_ms = []
+    for rep_ in range(4):
+        restore()
+        dev_ms.append(events(lambda: [g.replay() for _ in range(50)]) / 50)
+    med = {k: float(np.median(v[1:])) / nf for k, v in t.items()}
+    device = float(np.median(dev_ms[1:])) / nf
+    out = dict(metric='scene overlay stage: ms per frame of runtime.draw_scene against runtime.draw_plates of 16 plates and against D2H + PIL '
+                      'polygon / line / text on one thread',
+               frame=[h0, w0], frames=nf, reps=args.reps, nv12=args.nv12, lines=L, zones=Z, cover=bool(args.scene_cover), tags=P if args.speed else 0,
+               glyph=[font.gh, font.gw], scene_ms_per_frame=round(med['scene'], 4), scene_device_ms_per_frame=round(device, 5),
+               plates_ms_per_frame=round(med['plates'], 4), host_ms_per_frame=round(med['host'], 3),
+               scene_runs_ms=[round(v / nf, 4) for v in t['scene'][1:]], host_over_scene_device=round(med['host'] / max(device, 1e-9), 1))
+    print(json.dumps(out))
+    return out
+
+
 def sampled_rows(h0, rh):
     """Distinct source rows the bilinear resize reads for rh output rows (the y0 / y1 of resize_coef, lp_internal.h)."""
     if rh == h0:
@@ -1441,6 +1574,8 @@ def main():
     tdt = {'f16': torch.float16, 'f32': torch.float32}[args.dtype]
     if args.jpeg is not None:
         return jpeg_mode(args, dev)
+    if args.annotate and args.scene is not None:
+        return scene_mode(args, dev)
     if args.annotate:
         return annotate_mode(args, dev)
     model = fuse_model(build_synthetic(os.path.join(ROOT, 'configs', args.model + '.py'), sigma=SIGMA[args.model])).eval()

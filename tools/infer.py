@@ -16,7 +16,8 @@
                           [--track --zones FILE [--zones-min-hits 1]]
                           [--track --speed FILE [--speed-min-hits 1] [--speed-confirm 2]]
                           [--save-jpeg Q]
-                          [--overlay [--overlay-font TTF] [--overlay-size 24] [--overlay-thickness 2] [--overlay-alpha 256 160 256]]
+                          [--overlay [--overlay-font TTF] [--overlay-size 24] [--overlay-thickness 2] [--overlay-alpha 256 160 256]
+                           [--overlay-scene (with --zones and/or --speed)]]
                           [--tile H W --tile-gate [--tile-gate-thres 2.0] [--tile-gate-min-cells 1] [--tile-gate-refresh 50]
                            [--tile-gate-illum none|gain] [--tile-gate-max-gain 1.5]]
 """
@@ -154,6 +155,8 @@ _FLAGS = [
     ('--overlay-thickness', dict(type=int, default=2, metavar='N', help='with --overlay: outline thickness in pixels (0..16)')),
     ('--overlay-alpha', dict(nargs=3, type=int, default=[256, 160, 256], metavar=('L', 'P', 'T'),
                              help='with --overlay: opacity 0..256 of the outlines, the label plate and the text')),
+    ('--overlay-scene', dict(action='store_true', help='with --overlay and --zones and/or --speed: also draw the zones, the lines with '
+                                                       'their direction marker, their names and counts, and a km/h tag per plate')),
 ]
 
 
@@ -178,7 +181,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1, tile_gate_refresh=50,
         tile_gate_illum='none', tile_gate_max_gain=1.5, sightings=None, sight_window=None, sight_min_hits=1, sight_mismatch=1, sight_cost=None,
         save_jpeg=None, overlay=False, overlay_font=None, overlay_size=24, overlay_thickness=2, overlay_alpha=(256, 160, 256),
-        zones=None, zones_min_hits=1, speed=None, speed_min_hits=1, speed_confirm=2):
+        zones=None, zones_min_hits=1, speed=None, speed_min_hits=1, speed_confirm=2, overlay_scene=False):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track or redact or overlay) and not osp.exists(out_dir):
@@ -204,7 +207,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
                       sight_min_hits=sight_min_hits, sight_mismatch=sight_mismatch, sight_cost=sight_cost,
                       save_jpeg=save_jpeg, overlay=overlay, overlay_font=overlay_font, overlay_size=overlay_size,
                       overlay_thickness=overlay_thickness, overlay_alpha=tuple(overlay_alpha), zones=zones,
-                      zones_min_hits=zones_min_hits, speed=speed, speed_min_hits=speed_min_hits, speed_confirm=speed_confirm).infer(
+                      zones_min_hits=zones_min_hits, speed=speed, speed_min_hits=speed_min_hits, speed_confirm=speed_confirm,
+                      overlay_scene=overlay_scene).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

@@ -3,7 +3,8 @@
 // characters, from a caller-supplied coverage atlas), into a BGR frame or into the two planes of an NV12 frame.  The reference
 // draws nothing; the written-down specification is yolov6/utils/overlay.py::draw_plates_np, in the same operation order (fp64
 // geometry without fused multiply-adds: -ffp-contract=off; integer blends), so the two agree byte for byte
-// (tests/test_overlay_gpu.py).  The quad of a row is the rule of the crops and of the redaction, lp_plate_quad.inc.
+// (tests/test_overlay_gpu.py).  The quad of a row is the rule of the crops and of the redaction, lp_plate_quad.inc; the blend, the
+// 2 x 2 block, the segment test and the label layers are lp_overlay_paint.inc, shared with the scene overlay (lp_overlay_scene.hip).
 //
 // Rows are painted in row order, a later row over an earlier one, and a row's layers in the order box, quad, plate, glyphs: an
 // in-place painter's algorithm, whose hazard (two rows touching one pixel from two workgroups) is removed by the structure.
@@ -31,15 +32,8 @@ namespace {
 
 #include "lp_plate_quad.inc"
 
-constexpr int OV_TILE = 32;             // side of a tile in pixels (even: an NV12 tile is whole 2 x 2 blocks)
-constexpr int OV_W_ONE = 65280;         // 256 * 255: the weight that stores the colour exactly
+#include "lp_overlay_paint.inc"
 
-struct OvEntry {
-    unsigned char* p0;                  // BGR: the frame; NV12: the luma plane
-    unsigned char* p1;                  // NV12: the chroma plane
-    int pitch0, pitch1, h0, w0;
-};
-struct OvTable { OvEntry f[LP_FRAMES_PER_LAUNCH]; };
 static_assert(sizeof(OvTable) + sizeof(lp_overlay_params) + 128 < 4096, "table and styles travel as kernel arguments: under 4 KiB");
 
 // What the draw kernel needs of one row.  Rectangles are (i0, i1, j0, j1): rows [i0, i1), columns [j0, j1), clamped to the frame;
@@ -58,25 +52,6 @@ struct OvRec {
 };
 static_assert(sizeof(OvRec) % 16 == 0, "records keep the rectangles behind them 16-byte aligned");
 
-struct OvRect { int i0, i1, j0, j1; };
-static_assert(sizeof(OvRect) == 16, "one 16-byte load per row in the cull");
-
-__device__ __forceinline__ int clamp_count(int n, int max_det) { return n < 0 ? 0 : (n > max_det ? max_det : n); }
-
-// clamp(v, 0, n) in double (a NaN goes to 0), then converted: redact.scan_rect's clamp
-__device__ __forceinline__ int clamp_to(double v, int n) {
-    v = v >= 0.0 ? v : 0.0;
-    v = v < (double)n ? v : (double)n;
-    return (int)v;
-}
-
-// clamp(v, -2^20, 2^20) in double, then converted
-__device__ __forceinline__ int bound20(double v) {
-    v = v >= -1048576.0 ? v : -1048576.0;
-    v = v < 1048576.0 ? v : 1048576.0;
-    return (int)v;
-}
-
 __device__ __forceinline__ double min4(const double v[4]) { return fmin(fmin(v[0], v[1]), fmin(v[2], v[3])); }
 __device__ __forceinline__ double max4(const double v[4]) { return fmax(fmax(v[0], v[1]), fmax(v[2], v[3])); }
 
@@ -86,8 +61,6 @@ __device__ __forceinline__ void outline_rect(const double x[4], const double y[4
     rc[2] = clamp_to(floor(min4(x) - hw), w0); rc[3] = clamp_to(ceil(max4(x) + hw), w0);
     if (rc[0] >= rc[1] || rc[2] >= rc[3]) rc[0] = rc[1] = rc[2] = rc[3] = 0;
 }
-
-__device__ __forceinline__ unsigned pack3(const unsigned char c[3]) { return (unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16); }
 
 __device__ __forceinline__ void grow(OvRect& u, const int rc[4]) {
     if (rc[0] >= rc[1]) return;
@@ -192,98 +165,17 @@ __global__ __launch_bounds__(256) void overlay_setup_kernel(const OvTable tab, c
     rects[g] = u;
 }
 
-// (fg * w + dst * (65280 - w) + 32640) / 65280: at most 255 * 65280 + 32640 < 2^25
-__device__ __forceinline__ int blend(int dst, int fg, int w) {
-    return (int)((unsigned)(fg * w + dst * (OV_W_ONE - w) + OV_W_ONE / 2) / (unsigned)OV_W_ONE);
-}
-
-// The 2 x 2 block of one thread: BGR 12 bytes (pixel k = 2 di + dj, channel c at 3 k + c); NV12 y[0..3] then u, v at 4, 5.
-template <bool NV12>
-struct Block {
-    int v[NV12 ? 6 : 12];
-    bool dirty;
-
-    __device__ __forceinline__ void load(const OvEntry& f, int i, int j, const bool ok[4]) {
-        if (NV12) {
-            if (!ok[0]) return;                                          // even sizes: a block is whole or outside
-            const unsigned char* q = f.p0 + (long long)i * f.pitch0 + j;
-            v[0] = q[0]; v[1] = q[1]; v[2] = q[f.pitch0]; v[3] = q[f.pitch0 + 1];
-            const unsigned uv = *reinterpret_cast<const unsigned short*>(f.p1 + (long long)(i >> 1) * f.pitch1 + (j >> 1) * 2);
-            v[4] = (int)(uv & 255u); v[5] = (int)(uv >> 8);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (!ok[k]) continue;
-                const unsigned char* q = f.p0 + (long long)(i + (k >> 1)) * f.pitch0 + (long long)(j + (k & 1)) * 3;
-                v[3 * k] = q[0]; v[3 * k + 1] = q[1]; v[3 * k + 2] = q[2];
-            }
-        }
-    }
-
-    // one layer: the weights of the four pixels (0 for a pixel outside the frame) and the colour
-    __device__ __forceinline__ void apply(const int w[4], unsigned col) {
-        const int c0 = (int)(col & 255u), c1 = (int)((col >> 8) & 255u), c2 = (int)((col >> 16) & 255u);
-        if ((w[0] | w[1] | w[2] | w[3]) == 0) return;
-        dirty = true;
-        if (NV12) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = blend(v[k], c0, w[k]);
-            const int wb = (w[0] + w[1] + w[2] + w[3] + 2) >> 2;       // the chroma sample: once per layer
-            v[4] = blend(v[4], c1, wb);
-            v[5] = blend(v[5], c2, wb);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                v[3 * k] = blend(v[3 * k], c0, w[k]);
-                v[3 * k + 1] = blend(v[3 * k + 1], c1, w[k]);
-                v[3 * k + 2] = blend(v[3 * k + 2], c2, w[k]);
-            }
-        }
-    }
-
-    __device__ __forceinline__ void store(const OvEntry& f, int i, int j, const bool ok[4]) const {
-        if (NV12) {
-            if (!ok[0]) return;
-            unsigned char* q = f.p0 + (long long)i * f.pitch0 + j;
-            q[0] = (unsigned char)v[0]; q[1] = (unsigned char)v[1];
-            q[f.pitch0] = (unsigned char)v[2]; q[f.pitch0 + 1] = (unsigned char)v[3];
-            *reinterpret_cast<unsigned short*>(f.p1 + (long long)(i >> 1) * f.pitch1 + (j >> 1) * 2) = (unsigned short)(v[4] | (v[5] << 8));
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (!ok[k]) continue;
-                unsigned char* q = f.p0 + (long long)(i + (k >> 1)) * f.pitch0 + (long long)(j + (k & 1)) * 3;
-                q[0] = (unsigned char)v[3 * k]; q[1] = (unsigned char)v[3 * k + 1]; q[2] = (unsigned char)v[3 * k + 2];
-            }
-        }
-    }
-};
-
-// Is the centre (px, py) within sqrt(hw2) of the closed polygon p0 -> p3 -> p2 -> p1 -> p0?  fp64 op by op, no division, the
-// order of yolov6/utils/overlay.py::segment_mask:
-//   ex = bx - ax, ey = by - ay, L = ex * ex + ey * ey, dx = px - ax, dy = py - ay, d = dx * ex + dy * ey
-//   d <= 0: dx * dx + dy * dy <= hw2;  d >= L: fx = px - bx, fy = py - by, fx * fx + fy * fy <= hw2;
-//   else cr = dx * ey - dy * ex, cr * cr <= hw2 * L
+// Is the centre (px, py) within sqrt(hw2) of the closed polygon p0 -> p3 -> p2 -> p1 -> p0?  on_segment (lp_overlay_paint.inc) per edge.
 __device__ __forceinline__ bool on_outline(const double* __restrict__ x, const double* __restrict__ y, double hw2, double px, double py) {
     const int ord[4] = {0, 3, 2, 1};
     bool in = false;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const double ax = x[ord[k]], ay = y[ord[k]], bx = x[ord[(k + 1) & 3]], by = y[ord[(k + 1) & 3]];
-        const double ex = bx - ax, ey = by - ay;
-        const double L = ex * ex + ey * ey;
-        const double dx = px - ax, dy = py - ay;
-        const double d = dx * ex + dy * ey;
-        const double fx = px - bx, fy = py - by;
-        const double cr = dx * ey - dy * ex;
-        const bool hit = d <= 0.0 ? (dx * dx + dy * dy <= hw2) : (d >= L ? (fx * fx + fy * fy <= hw2) : (cr * cr <= hw2 * L));
+        const bool hit = on_segment(x[ord[k]], y[ord[k]], x[ord[(k + 1) & 3]], y[ord[(k + 1) & 3]], hw2, px, py);
         in = in || hit;
     }
     return in;
 }
-
-__device__ __forceinline__ bool touches(const int rc[4], int i, int j) { return i + 2 > rc[0] && i < rc[1] && j + 2 > rc[2] && j < rc[3]; }
-__device__ __forceinline__ bool inside(const int rc[4], int i, int j) { return i >= rc[0] && i < rc[1] && j >= rc[2] && j < rc[3]; }
 
 template <bool NV12>
 __device__ __forceinline__ void draw_outline(Block<NV12>& blk, const int* rc, const double* x, const double* y, double hw2, int wt, unsigned col,
@@ -305,27 +197,8 @@ __device__ __forceinline__ void draw_row(Block<NV12>& blk, const OvRec* __restri
                                          int h0, int w0, int i, int j) {
     draw_outline(blk, R->brect, R->bx, R->by, R->hw2, R->a_line * 255, R->col_box, i, j);
     draw_outline(blk, R->qrect, R->qx, R->qy, R->hw2, R->a_line * 255, R->col_quad, i, j);
-    const int lr[4] = {R->lrect[0], R->lrect[1], R->lrect[2], R->lrect[3]};
-    if (!touches(lr, i, j)) return;
-    int w[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) w[k] = inside(lr, i + (k >> 1), j + (k & 1)) ? R->a_plate * 255 : 0;
-    blk.apply(w, R->col_plate);
-    // glyph cells: rows [ly + pad, + gh), columns [lx + pad, + n * gw), clipped
-    const int ty = R->ly + R->pad, tx = R->lx + R->pad, ng = R->n_glyph;
-    const int tr[4] = {max(ty, 0), min(ty + gh, h0), tx, min(tx + ng * gw, w0)};
-    if (tr[0] >= tr[1] || tr[2] >= tr[3] || !touches(tr, i, j)) return;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int pi = i + (k >> 1), pj = j + (k & 1);
-        w[k] = 0;
-        if (inside(tr, pi, pj)) {
-            const int gi = pi - ty, gj = pj - tx, cell = gj / gw;
-            const int g = R->glyph[cell];
-            w[k] = R->a_text * (int)atlas[((long long)g * gh + gi) * gw + (gj - cell * gw)];
-        }
-    }
-    blk.apply(w, R->col_text);
+    draw_label(blk, R->lrect, R->ly, R->lx, R->pad, R->n_glyph, R->glyph, R->a_plate * 255, R->col_plate, R->a_text, R->col_text, atlas, gh, gw,
+               h0, w0, i, j);
 }
 
 // grid (most tiles of a frame of this launch, frames of this launch), block 256.  count, recs and rects start at the launch's first frame.

@@ -64,7 +64,7 @@ class Inferer:
                  tile_gate_min_cells=1, tile_gate_refresh=50, tile_gate_illum='none', tile_gate_max_gain=1.5, stack_shots=False,
                  stack_search=2, stack_max_frames=64, stack_min_width=0.0, sightings=None, sight_window=None, sight_min_hits=1,
                  sight_mismatch=1, sight_cost=None, save_jpeg=None, overlay=False, overlay_font=None, overlay_size=24, overlay_thickness=2,
-                 overlay_alpha=(256, 160, 256), zones=None, zones_min_hits=1, speed=None, speed_min_hits=1, speed_confirm=2):
+                 overlay_alpha=(256, 160, 256), zones=None, zones_min_hits=1, speed=None, speed_min_hits=1, speed_confirm=2, overlay_scene=False):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -137,13 +137,20 @@ class Inferer:
         rate and a limit per stream.  The live tracks of at least ``speed_min_hits`` detections are measured after every tracker call;
         ``infer`` writes ``speeds.txt`` (``id text peak_kmh chord_kmh`` per ended track with at least two samples) and
         ``speeding.txt`` (``frame id text kmh limit_kmh`` for a track over the limit for ``speed_confirm`` estimates in a row, at the
-        frame it fired); every other output is what it is without it."""
+        frame it fired); every other output is what it is without it.
+        ``overlay_scene`` (with ``overlay`` and ``zones`` and/or ``speed``): the scene is drawn onto the annotated frames before the
+        plates -- zones as a translucent fill plus an outline, lines with a marker on their +1 side, their names with the running
+        totals and occupancies, the alert colour while a dwell alert fires, a km/h tag beside every plate with a speed estimate
+        (``runtime.draw_scene`` on a GPU, ``draw_scene_np`` on the CPU; ``yolov6.utils.scene`` states the rule and what it does not
+        do).  Without it every output file is what it is today."""
         self.__dict__.update(locals())
         self._overlay = None
         if overlay:
             if redact_lookback is not None:
                 raise ValueError('overlay does not go with redact_lookback: the frame is redacted frames later')
             self._overlay_styles = self.make_overlay_styles(overlay_size, overlay_thickness, overlay_alpha)
+        if overlay_scene and not (overlay and (zones is not None or speed is not None)):
+            raise ValueError('overlay_scene needs overlay=True and zones=FILE and/or speed=FILE')
         if save_jpeg is not None:
             from yolov6.utils.jpeg import check_params as check_jpeg
             self.save_jpeg = check_jpeg(save_jpeg, self.JPEG_RESTART, device=True)[0]
@@ -227,6 +234,12 @@ class Inferer:
             from yolov6.utils.overlay import build_atlas
             self._overlay = build_atlas(self.pro_names or [], self.alp_names or [], self.ads_names or [], overlay_size, overlay_font)
             self._overlay_dev = None        # runtime.OverlayFont: uploaded with the first group
+        self._scene = None
+        if overlay_scene:
+            from yolov6.utils.scene import build_scene_atlas
+            self._scene = build_scene_atlas(overlay_size, overlay_font)
+            self._scene_style = self.make_scene_style(overlay_size, overlay_thickness, overlay_alpha)
+            self._scene_dev = None          # (runtime.SceneFont, names on the device): uploaded with the first group
         self.img_size = self.check_img_size(self.img_size, s=self.stride)
         self.half = half
 
@@ -594,7 +607,12 @@ class Inferer:
             from yolov6.utils import zones as zn
             lines, polys, self._zone_line_names, self._zone_names = zn.parse_zones(self.zones, 1 + len(videos))
             make = runtime.ZoneMap if self.device.type != 'cpu' else zn.ZoneMapNp
-            self._tracker.enable_zones(make(1 + len(videos), lines, polys, device=self.device), self.zones_min_hits)
+            self._scene_map = make(1 + len(videos), lines, polys, device=self.device)
+            self._tracker.enable_zones(self._scene_map, self.zones_min_hits)
+        elif self.overlay_scene:            # speed tags alone: a map without lines and zones
+            from yolov6.utils import zones as zn
+            self._scene_map = (runtime.ZoneMap if self.device.type != 'cpu' else zn.ZoneMapNp)(1 + len(videos), device=self.device)
+            self._zone_line_names = self._zone_names = [[] for _ in range(1 + len(videos))]
         self._track_speed_events = []   # with speed: (kind, frame, id, best [8] or None, value, aux) per event
         if self.speed is not None:
             from yolov6.utils import speed as sp
@@ -922,6 +940,14 @@ class Inferer:
         base = Style(t=int(thickness), a_line=a_line, a_plate=a_plate, a_text=a_text, pad=max(1, min(16, int(size) // 8)))
         return check_styles([base, base._replace(box=(0, 128, 255), quad=(0, 128, 255))])
 
+    @staticmethod
+    def make_scene_style(size, thickness, alpha):
+        """The style of ``overlay_scene``: the overlay's thickness, opacities and padding, a marker half a glyph high."""
+        from yolov6.utils.scene import SceneStyle, check_scene_style
+        a_line, a_plate, a_text = (int(v) for v in alpha)
+        return check_scene_style(SceneStyle(t=int(thickness), marker=max(4, int(size) // 2), a_line=a_line, a_plate=a_plate, a_text=a_text,
+                                            pad=max(1, min(16, int(size) // 8))))
+
     def _overlay_group(self, frames, dets, dev_frames=None, dev_rows=None):
         """With ``overlay``: queue for ``infer`` the frames of one group with their final rows ``dets`` drawn on them, right behind
         ``_redact_group``.  On a GPU clones of ``dev_frames`` (redacted already where ``redact`` is on) are drawn on
@@ -962,6 +988,15 @@ class Inferer:
             if tid is not None:
                 kw['tid'] = tid if torch.is_tensor(tid) else torch.from_numpy(tid).to(self.device)
             clones = [Nv12Frame(f.y.clone(), f.uv.clone(), f.matrix) if isinstance(f, Nv12Frame) else f.clone() for f in list(dev_frames)[:n]]
+            if self._scene is not None:         # the scene first: zone fills lie under the plate outlines
+                from yolov6.utils.scene import names_of
+                if self._scene_dev is None:
+                    names = names_of((None, None, self._zone_line_names, self._zone_names), self._scene)
+                    self._scene_dev = (runtime.SceneFont(self._scene, device=self.device), torch.from_numpy(names.view(np.int16)).to(self.device))
+                tags = self._tracker.last_speed is not None and kw.get('tid') is not None
+                runtime.draw_scene(clones, self._scene_map, self._scene_dev[0], names=self._scene_dev[1], stream_of=self._track_last_streams[:n],
+                                   zone=self._tracker.last_zone, speed=self._tracker.last_speed if tags else None, det=det if tags else None,
+                                   count=count if tags else None, tid=kw['tid'] if tags else None, style=self._scene_style)
             runtime.draw_plates(clones, det, count, self._overlay_dev, **kw)
             if self.save_jpeg is not None:      # the files leave the device, not the frames
                 self._annotated.extend(self._jpeg_files(clones))
@@ -978,6 +1013,13 @@ class Inferer:
                 det, count = np.zeros((n, rows, 28), np.float32), counts
                 for k, d in enumerate(dets):
                     det[k, :len(d)] = d.detach().float().cpu().numpy()
+            if self._scene is not None:         # the scene first: zone fills lie under the plate outlines
+                from yolov6.utils.scene import draw_scene_np, names_of
+                names = names_of((None, None, self._zone_line_names, self._zone_names), self._scene)
+                zone, speed = self._tracker.last_zone, self._tracker.last_speed if tid is not None else None
+                tags = {} if speed is None else dict(speed_i=speed[0], det=det, count=count, tid=tid)
+                base = draw_scene_np(base, self._scene_map.packed, self._scene, names, self._track_last_streams[:n],
+                                     *((None,) * 4 if zone is None else (zone[3], zone[2], zone[0], zone[1])), style=self._scene_style, **tags)[0]
             self._annotated.extend(draw_plates_np(base, det, count, *self._overlay, tid=tid, **kw)[0])
 
     def _redact_delayed(self, frames, dev_frames=None):

@@ -35,6 +35,7 @@ LP_TRACK_MAX_TRACKS, LP_TRACK_MAX_DETS, LP_TRACK_MAX_CLS = 128, 128, 64   # lp_t
 LP_REDACT_MAX_CELL = 64    # lp_redact_plates_batch: largest mosaic cell
 LP_REDACT_MAX_RADIUS = 48  # lp_redact_gauss_batch: largest blur radius (taps per side)
 LP_OVERLAY_MAX_STYLES, LP_OVERLAY_MAX_GLYPHS, LP_OVERLAY_MAX_PALETTE = 8, 20, 64   # lp_overlay_draw_batch: styles, glyphs of a label, palette entries
+LP_SCENE_MAX_GLYPHS, LP_SCENE_MAX_NAME, LP_SCENE_MAX_MARKER, LP_SCENE_FIXED_GLYPHS = 36, 12, 64, 17   # lp_overlay_scene_batch: glyphs of a label, of a name, marker height, fixed glyphs
 LP_JPEG_MAX_RESTART, LP_JPEG_PER_LAUNCH = 32, 32   # lp_jpeg_encode_batch: MCUs per restart interval, frames per launch
 LP_LOOKBACK_MAX_DEPTH = 32   # lp_lookback_update: frames of delay
 LP_WATCH_MAX_ENTRIES, LP_WATCH_MAX_COST = 1 << 24, 32768   # lp_watch_match: entries of a watchlist, the largest cost of an entry
@@ -113,6 +114,12 @@ class OverlayParams(ctypes.Structure):
     _fields_ = [('n_styles', c_int), ('styles', OverlayStyle * LP_OVERLAY_MAX_STYLES), ('n_palette', c_int),
                 ('palette', (ctypes.c_ubyte * 3) * LP_OVERLAY_MAX_PALETTE), ('n_glyphs', c_int), ('gh', c_int), ('gw', c_int),
                 ('show_id', c_int), ('label', c_int), ('draw_box', c_int)]
+
+
+class SceneStyle(ctypes.Structure):
+    """lp_scene_style"""
+    _fields_ = [(name, ctypes.c_ubyte * 3) for name in ('zone', 'alert', 'line', 'mark', 'plate', 'text', 'tag')] + \
+               [(name, c_int) for name in ('t', 'marker', 'a_fill', 'a_fill_busy', 'a_line', 'a_plate', 'a_text', 'pad', 'n_glyphs', 'gh', 'gw')]
 
 
 class JpegDesc(ctypes.Structure):
@@ -241,6 +248,10 @@ SYMBOLS = {
     'lp_overlay_workspace_bytes': (c_size_t, [c_int, c_int]),
     'lp_overlay_draw_batch': (c_int, [POINTER(RedactDesc), c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, POINTER(OverlayParams),
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'lp_overlay_scene_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'lp_overlay_scene_batch': (c_int, [POINTER(RedactDesc), c_int, POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, POINTER(SceneStyle), c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_size_t, c_void_p]),
     'lp_jpeg_workspace_bytes': (c_size_t, [POINTER(JpegDesc), c_int, c_int]),
     'lp_jpeg_encode_batch': (c_int, [POINTER(JpegDesc), c_int, POINTER(JpegParams), c_void_p, c_int, c_void_p, c_size_t, c_void_p,
                                      c_void_p, c_size_t, c_void_p]),

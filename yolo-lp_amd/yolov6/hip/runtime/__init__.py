@@ -22,7 +22,8 @@ from .frames import (detect_frames, detect_frames_padded, nv12_to_bgr, preproces
                      rescale_round_batch)
 from .crops import _crop_size, _unpad_with_crops, crop_sharpness, detect_frames_with_crops, plate_crops
 from .redact import GAUSS_WS_CAP, _gauss_params, _redact_workspace, _redact_ws, redact_plates
-from .overlay import OverlayFont, _overlay_params, _overlay_params_memo, _overlay_ws, draw_plates
+from .overlay import (OverlayFont, SceneFont, _overlay_params, _overlay_params_memo, _overlay_ws, _scene_style, _scene_ws, draw_plates,
+                      draw_scene)
 from .jpeg import JPEG_WS_CAP, _jpeg_ws, encode_jpeg, encode_jpeg_padded, jpeg_stats
 from .tiles import (_tile_inputs, detect_tiled, detect_tiled_padded, detect_tiled_with_crops, detect_tiles_padded, merge_tiles,
                     merge_tiles_buffers, plan_tiled, preprocess_tiles)

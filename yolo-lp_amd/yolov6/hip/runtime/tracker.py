@@ -10,6 +10,7 @@ from yolov6.hip import abi
 from ._base import _aligned_span, _check_det_count, _cuda_device, _dptr, _frames_on, _persistent, _stream_ptr
 from .crops import _crop_size, _plate_crops_launch, crop_sharpness
 from .frames import _bgr_frames
+from .overlay import draw_scene
 from .watch import SightLog, Watchlist
 
 
@@ -280,6 +281,20 @@ class PlateTracker:
                                                 zn['min_hits'], _dptr(zn['memo']), _dptr(zn['ev']), _dptr(zn['count']), zn['max_events'],
                                                 _dptr(zn['occ']), _dptr(zn['totals']), _stream_ptr(self.device)), 'lp_zone_update')
         self.last_zone = (zn['ev'], zn['count'], zn['occ'], zn['totals'])
+
+    def draw_scene(self, frames, font, det_out, count, tid, stream_of=None, names=None, style=None, status=None):
+        """``runtime.draw_scene`` of the tracker's own ``ZoneMap`` (``enable_zones``), ``last_zone`` and ``last_speed`` onto ``frames``
+        IN PLACE, after the ``update`` that returned ``det_out`` and ``tid``: zones, lines, their counts, and -- with
+        ``enable_speed`` -- a km/h tag per tracked plate.  ``stream_of`` as that ``update`` took it.  On a stream the order is crops and
+        best shots, redaction, this call, then ``draw_plates``: zone fills lie under the plate outlines.  Returns the tag status
+        [B,max_det] (None without ``enable_speed``).  ``yolov6.utils.scene.draw_scene_np`` on a ``PlateTrackerNp``'s ``last_zone`` /
+        ``last_speed`` gives the same bytes."""
+        if self._zones is None:
+            raise ValueError('draw_scene needs enable_zones (a ZoneMap without lines and zones draws the speed tags alone)')
+        tags = self.last_speed is not None
+        return draw_scene(frames, self._zones['zone_map'], font, names=names, stream_of=stream_of, zone=self.last_zone,
+                          speed=self.last_speed if tags else None, det=det_out if tags else None, count=count if tags else None,
+                          tid=tid if tags else None, style=style, status=status)
 
     # ---- the ended reads matched against the earlier reads of all streams (lp_sight_update; yolov6/utils/sight.py states the rule) ----
     def enable_sightings(self, log, window=0, min_hits=1, max_mismatch=1, max_cost=None):

@@ -65,7 +65,7 @@ to end) -- no filtering, no acceleration, no lens-distortion model; a vehicle's 
 mounting-height spread, which scales its speed by about that spread over the camera's height above the plane; positions are those at
 the end of a call (a stream with several frames in one call gives one sample); ``now`` and the clock must not run backwards -- with
 dt <= 0 there is no estimate; a missed frame gives no sample, the speed reported meanwhile is the last estimate; zones stay in
-pixels; the overlay does not show the speed; speed across cameras is ``sight``'s journey time.
+pixels (``yolov6.utils.scene`` draws the speed as a km/h tag); speed across cameras is ``sight``'s journey time.
 """
 import math
 import os

@@ -61,7 +61,7 @@ them; enabling again zeroes everything.
 What it does not do: positions are those at the end of a call -- a stream with several frames in one call is tested on the chord,
 and a track born and ended inside one call is unseen; a track that touches a line and turns back yields +1 then -1; a track that
 ends inside a zone is kind 5, not kind 3; lines and zones stay in pixels (the speed on a calibrated ground plane is
-``yolov6.utils.speed`` / ``enable_speed``); the anchor is the plate, not the vehicle's footprint; the overlay does not draw the zones.
+``yolov6.utils.speed`` / ``enable_speed``); the anchor is the plate, not the vehicle's footprint (``yolov6.utils.scene`` draws the lines and zones).
 """
 import os
 
