@@ -163,6 +163,291 @@ def exact_conv(xs, wt, bias, k, s, act, dtype, res64=None, alpha=RES_ALPHA):
     return exact_epilogue(pre, act, dtype, res64, alpha), pre
 
 
+# ---- non-finite values (tests/test_nonfinite_cpu.py, tests/test_nonfinite_gpu.py) ------------------------------------------------
+# The reference (oracle/lp_oracle.py: F.conv2d, F.relu, F.silu, F.max_pool2d, softmax) is plain IEEE 754 arithmetic: a NaN operand
+# gives NaN, inf * 0 gives NaN, +inf + -inf gives NaN.  None of that depends on the order of a sum, so on grid data with a few planted
+# NaN / +-inf the expected tensor is still known bit for bit at every finite element and by class at every other.
+NONFINITE = {'nan': float('nan'), '+inf': float('inf'), '-inf': float('-inf')}
+
+
+def plant_nonfinite(t, plan):
+    """A copy of the grid-valued float64 tensor ``t`` with NaN / +inf / -inf written at named positions: ``plan`` is a list of
+    (kind, index) with kind in NONFINITE and index what ``t[index] = value`` takes (integers and slices).  The rest stays on the grid."""
+    assert t.dtype == torch.float64
+    out = t.clone()
+    for kind, idx in plan:
+        out[idx] = NONFINITE[kind]
+    return out
+
+
+def nonfinite_counts(t):
+    """{'nan', '+inf', '-inf', 'finite'} -> number of elements of ``t``."""
+    v = t.double()
+    n, p, m = int(torch.isnan(v).sum()), int((v == NONFINITE['+inf']).sum()), int((v == NONFINITE['-inf']).sum())
+    return {'nan': n, '+inf': p, '-inf': m, 'finite': v.numel() - n - p - m}
+
+
+def conv_nonfinite_ref(xs, wt, bias, k, s, transposed=False, skip=None, terms=False):
+    """Pre-activation sum of a conv layer on data that holds NaN / +-inf, as an explicit float64 product-then-sum over unfolded
+    patches with zero padding, (patches * w).sum(...): IEEE arithmetic with nothing skipped -- a padding tap under an infinite weight
+    is inf * 0 = NaN, a zero weight over a NaN is NaN.  The class of a sum (NaN / +inf / -inf / finite) does not depend on its order,
+    and grid data cannot overflow, so this is the authority; F.conv2d in float64 must show the same NaN / +inf / -inf masks (asserted:
+    a BLAS that skips zero operands would not).  ``transposed``: the 2x2 stride-2 transposed conv (wt [cin, cout, 2, 2]).
+    ``skip`` restates a WRONG convolution for the mutant checks: 'zero_weights' drops the terms whose weight is 0, 'padding' the taps
+    that fall outside the image.  A boolean tensor shaped like ``wt`` drops exactly the marked terms: a kernel that by design does not
+    run some all-zero taps (the fused stem).  ``terms=True`` also returns, per output, the numbers of NaN, +inf and -inf terms of its sum."""
+    import torch.nn.functional as F
+    x = torch.cat(list(xs), 1)
+    B, cin = x.shape[:2]
+    if transposed:
+        cout = wt.shape[1]
+        pat = x.reshape(B, cin, 1, -1)                                           # one term per input channel and output phase
+        wm = wt.permute(1, 2, 3, 0).reshape(cout * 4, cin)                       # [(co, dy, dx), cin]
+        inside = torch.ones(1, cin, x.shape[2] * x.shape[3], dtype=torch.bool)
+    else:
+        cout = wt.shape[0]
+        pat = F.unfold(x, k, padding=k // 2, stride=s).reshape(B, cin * k * k, -1)
+        wm = wt.reshape(cout, cin * k * k)
+        inside = F.unfold(torch.ones(1, cin, x.shape[2], x.shape[3], dtype=torch.float64), k, padding=k // 2, stride=s) > 0
+    pat = pat.reshape(B, 1, wm.shape[1], -1)
+    rows = wm.shape[0]
+    out = torch.empty(B, rows, pat.shape[-1], dtype=torch.float64)
+    cnt = torch.zeros(3, B, rows, pat.shape[-1], dtype=torch.int32) if terms else None
+    step = max(1, int(3e7 // (B * wm.shape[1] * pat.shape[-1])))                # bounds the product tensor at ~240 MB
+    for r0 in range(0, rows, step):
+        wv = wm[r0:r0 + step].reshape(1, -1, wm.shape[1], 1)
+        prod = pat * wv
+        if skip == 'zero_weights':
+            prod = torch.where(wv == 0, torch.zeros_like(prod), prod)
+        elif skip == 'padding':
+            prod = torch.where(inside.reshape(1, 1, wm.shape[1], -1), prod, torch.zeros_like(prod))
+        elif torch.is_tensor(skip):
+            prod = torch.where(skip.reshape(wm.shape)[r0:r0 + step].reshape(1, -1, wm.shape[1], 1), torch.zeros_like(prod), prod)
+        else:
+            assert skip is None
+        out[:, r0:r0 + step] = prod.sum(2)
+        if terms:
+            cnt[0, :, r0:r0 + step] = torch.isnan(prod).sum(2)
+            cnt[1, :, r0:r0 + step] = (prod == NONFINITE['+inf']).sum(2)
+            cnt[2, :, r0:r0 + step] = (prod == NONFINITE['-inf']).sum(2)
+    if transposed:
+        h, w = x.shape[2:]
+
+        def shape(t):                                                            # [..., (co, dy, dx), (y, x)] -> [..., co, 2y + dy, 2x + dx]
+            lead, n = tuple(t.shape[:-2]), t.dim() - 2
+            t = t.reshape(lead + (cout, 2, 2, h, w)).permute(list(range(n)) + [n, n + 3, n + 1, n + 4, n + 2])
+            return t.reshape(lead + (cout, 2 * h, 2 * w))
+        lib = F.conv_transpose2d(x, wt, None, stride=2)
+    else:
+        ho, wo = (x.shape[2] + 2 * (k // 2) - k) // s + 1, (x.shape[3] + 2 * (k // 2) - k) // s + 1
+        shape = lambda t: t.reshape(t.shape[:-1] + (ho, wo))
+        lib = F.conv2d(x, wt, None, stride=s, padding=k // 2)
+    out = shape(out)
+    if skip is None:
+        for kind in ('+inf', '-inf'):
+            assert torch.equal(lib == NONFINITE[kind], out == NONFINITE[kind]), 'F.conv2d and the explicit product sum differ in ' + kind
+        assert torch.equal(torch.isnan(lib), torch.isnan(out)), 'F.conv2d and the explicit product sum differ in their NaN masks'
+        fin = torch.isfinite(out)
+        assert torch.equal(lib[fin], out[fin]), 'F.conv2d and the explicit product sum differ at finite elements of grid data'
+    out = out + bias.view(1, -1, 1, 1)
+    return (out, shape(cnt)) if terms else out
+
+
+def nonfinite_epilogue(pre64, act, dtype, res64=None, alpha=RES_ALPHA, relu=None, res_first=False):
+    """``exact_epilogue`` with the reference's semantics for NaN and infinities: relu maps NaN to NaN, -inf to +0 and +inf to +inf
+    (torch.relu), ONE rounding to the storage type, then from_f32<T>(to_f32(T(act)) + alpha * res) in IEEE arithmetic -- +inf in
+    the activation and -inf in the residual give NaN.  Finite values must still be exact fp32 sums.  ``relu`` / ``res_first``
+    restate WRONG epilogues for the mutant checks: relu='select' is v > 0 ? v : 0, res_first adds the residual in front of the
+    rounding."""
+    assert act in ('none', 'relu')
+
+    def exact32(v64):
+        fin = torch.isfinite(v64)
+        v32 = v64.float()
+        assert torch.equal(v32.double()[fin], v64[fin]), 'the float64 reference is not an fp32 value: the data left the exact regime'
+        return v32
+
+    v = pre64
+    if act == 'relu':
+        sel = torch.where(pre64 > 0, pre64, torch.zeros_like(pre64))
+        v = sel if relu == 'select' else torch.where(torch.isnan(pre64), pre64, sel)      # (= torch.relu: test_nonfinite_cpu.py)
+    if res64 is not None and res_first:
+        return exact32(v + alpha * res64).to(dtype)
+    y = exact32(v).to(dtype)
+    if res64 is not None:
+        fin = torch.isfinite(res64)
+        assert torch.equal(res64.to(dtype).double()[fin], res64[fin])
+        y = exact32(y.double() + alpha * res64).to(dtype)
+    return y
+
+
+def same_nonfinite_mismatches(got, want):
+    """0-d integer tensors (on the device of ``got``) for assert_same_nonfinite: elements whose NaN-ness differs, and non-NaN
+    elements whose bits differ (infinities with their sign; zeros of either sign equal, as in bit_mismatch_count)."""
+    assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
+    iv = torch.int64 if got.dtype == torch.float64 else INT_VIEW[got.dtype]
+    g, w = got.contiguous(), want.to(got.device).contiguous()
+    gn, wn = torch.isnan(g), torch.isnan(w)
+    same = (g.view(iv) == w.view(iv)) | ((g == 0) & (w == 0))
+    return (gn != wn).sum(), (~gn & ~wn & ~same).sum()
+
+
+def assert_same_nonfinite(got, want, what=''):
+    """``got`` (a tensor of a storage type, any device) against the expected tensor of the same type: NaN exactly where ``want`` is
+    NaN (payload and sign free), +inf and -inf equal with their sign, equal bits at every finite element (+0.0 == -0.0, as the exact
+    tests treat it).  The message counts each class on both sides."""
+    nan_bad, bit_bad = same_nonfinite_mismatches(got, want)
+    if int(nan_bad) or int(bit_bad):
+        g, w = got.cpu().double(), want.cpu().double()
+        gn, wn = torch.isnan(g), torch.isnan(w)
+        lost, extra = wn & ~gn, gn & ~wn
+        inf_bad = ~gn & ~wn & (torch.isinf(g) | torch.isinf(w)) & (g != w)
+        fin_bad = torch.isfinite(g) & torch.isfinite(w) & (g != w)
+        first = torch.nonzero(lost | extra | inf_bad | fin_bad)[:4].tolist()
+        raise AssertionError('%s: NaN lost at %d elements (got there: %s), NaN where the reference has none at %d, infinities differ at %d, '
+                             'finite bits differ at %d; got %s, want %s; first at %s'
+                             % (what, int(lost.sum()), g[lost][:4].tolist(), int(extra.sum()), int(inf_bad.sum()), int(fin_bad.sum()),
+                                nonfinite_counts(g), nonfinite_counts(w), first))
+
+
+EPILOGUES4 = (('none', False), ('relu', False), ('none', True), ('relu', True))
+_ALL = slice(None)
+# The planted conv cases: layer, map of the SOURCES, B = 2, and where NaN / +inf / -inf go -- per source tensor (``x``) and in the residual
+# (``res``), image 1 differently from image 0.  A planted element taints its 3x3 footprint for every output channel (an infinity as
+# +inf / -inf by the sign of the weight, as NaN under a zero weight), so a handful per image leaves most outputs finite and still gives
+# each class its share; two infinities with overlapping footprints meet in one sum; an infinite residual sits on a pixel whose
+# activation is infinite too.  test_nonfinite_cpu.py asserts all of that from the reference alone.
+NONFINITE_CONV_CASES = {
+    # 64 -> 128, 3x3: a corner, edges, the interior pixel (7, 8) -- on the boundary of every tile whose height or width divides 8 -- and
+    # channels 15 | 16, the last of one K-chunk and the first of the next (16 channels per chunk in the 16-bit types, 8 in fp32)
+    'conv3x3': dict(cins=[64], cout=128, k=3, s=1, h=16, w=16, epilogues=EPILOGUES4,
+                    x=[[('nan', (0, 15, 0, 0)), ('+inf', (0, 16, 7, 8)), ('+inf', (0, 40, 7, 9)), ('-inf', (0, 63, 15, 5)),
+                        ('nan', (1, 0, 8, 15)), ('+inf', (1, 31, 0, 15)), ('+inf', (1, 32, 4, 4)), ('-inf', (1, 63, 12, 7))]],
+                    res=[('nan', (0, slice(5, 9), 3, 12)), ('-inf', (0, _ALL, 6, 7)), ('+inf', (1, slice(0, 64), 12, 7)), ('nan', (1, 100, 0, 0))]),
+    # stride 2, 32 x 32 in: a pixel at odd coordinates reaches four outputs, one at even coordinates a single one
+    'conv3x3s2': dict(cins=[64], cout=128, k=3, s=2, h=32, w=32, epilogues=EPILOGUES4,
+                      x=[[('nan', (0, 15, 1, 1)), ('nan', (0, 3, 31, 17)), ('+inf', (0, 16, 15, 17)), ('+inf', (0, 40, 15, 19)), ('+inf', (0, 5, 21, 5)),
+                          ('+inf', (0, 50, 25, 25)), ('-inf', (0, 63, 9, 27)), ('-inf', (0, 7, 27, 11)),
+                          ('nan', (1, 0, 17, 31)), ('nan', (1, 20, 5, 9)), ('+inf', (1, 31, 1, 31)), ('+inf', (1, 32, 11, 11)), ('+inf', (1, 33, 21, 21)),
+                          ('-inf', (1, 63, 25, 7)), ('-inf', (1, 2, 7, 23)), ('+inf', (1, 9, 30, 0))]],
+                      res=[('nan', (0, slice(5, 9), 3, 3)), ('-inf', (0, _ALL, 7, 8)), ('+inf', (1, slice(0, 64), 12, 3)), ('nan', (1, 100, 0, 0))]),
+    # the streaming 1x1 kernel over a concat: the last channel of one source and the first of the next
+    'stream1x1': dict(cins=[128, 64, 64], cout=64, k=1, s=1, h=16, w=16, epilogues=EPILOGUES4,
+                      x=[[('nan', (0, 127, 2, slice(3, 6))), ('nan', (1, 127, 15, slice(13, 16)))],
+                         [('+inf', (0, 0, 5, slice(0, 8))), ('-inf', (0, 63, 9, slice(4, 12))), ('+inf', (1, 0, 0, slice(8, 16))), ('-inf', (1, 63, 7, slice(0, 8)))],
+                         [('+inf', (0, 0, 9, slice(8, 14))), ('+inf', (1, 63, 12, slice(2, 10)))]],
+                      res=[('nan', (0, slice(10, 12), 14, 14)), ('-inf', (0, _ALL, 5, 3)), ('+inf', (1, _ALL, 7, 2)), ('nan', (1, 5, 3, 3))]),
+    # the same concat into 128 output channels: the 128-row weight packing, which the wide streaming kernel (WC = 4) needs
+    'stream1x1-128': dict(cins=[128, 64, 64], cout=128, k=1, s=1, h=16, w=16, epilogues=EPILOGUES4,
+                          x=[[('nan', (0, 127, 2, slice(3, 6))), ('nan', (1, 127, 15, slice(13, 16)))],
+                             [('+inf', (0, 0, 5, slice(0, 8))), ('-inf', (0, 63, 9, slice(4, 12))), ('+inf', (1, 0, 0, slice(8, 16))), ('-inf', (1, 63, 7, slice(0, 8)))],
+                             [('+inf', (0, 0, 9, slice(8, 14))), ('+inf', (1, 63, 12, slice(2, 10)))]],
+                          res=[('nan', (0, slice(10, 12), 14, 14)), ('-inf', (0, _ALL, 5, 3)), ('+inf', (1, _ALL, 7, 2)), ('nan', (1, 5, 3, 3))]),
+    # 2x2 stride-2 transposed conv: +inf and -inf in two channels of one pixel meet in every output of that pixel
+    'deconv2x2': dict(cins=[16], cout=24, k=2, s=2, h=6, w=6, transposed=True, epilogues=(('none', False),),
+                      x=[[('nan', (0, 15, 0, 0)), ('+inf', (0, 0, 2, 3)), ('-inf', (0, 8, 2, 3)), ('+inf', (0, 7, 5, 5)), ('-inf', (0, 3, 3, 0)),
+                          ('nan', (1, 0, 5, 2)), ('+inf', (1, 15, 0, 5)), ('+inf', (1, 4, 3, 3)), ('-inf', (1, 9, 4, 0))]], res=None),
+    # two sibling layers in one launch (PAIR_CASES' narrow one: 8 + 24 output channels in one 32-row cout tile)
+    'pair': dict(cins=[16], cout=32, pair=(8, 24), k=3, s=1, h=12, w=20, epilogues=(('none', False), ('relu', False)),
+                 x=[[('nan', (0, 15, 0, 19)), ('+inf', (0, 0, 6, 10)), ('+inf', (0, 8, 6, 11)), ('-inf', (0, 7, 11, 3)),
+                     ('nan', (1, 3, 5, 0)), ('+inf', (1, 15, 0, 0)), ('+inf', (1, 1, 9, 15)), ('-inf', (1, 12, 3, 8))]], res=None),
+}
+_nonfinite_cache = {}
+
+
+def nonfinite_conv_data(name, dtype):
+    """One planted case for storage type ``dtype``: dict of the planted sources ``xs`` and residual ``res``, ``wt``, ``bias``, the float64
+    pre-activation ``pre`` (conv_nonfinite_ref), the (NaN, +inf, -inf) term counts of every sum ``terms``, and ``wants``: the expected
+    tensor per epilogue of the case.  Activations and weights are the same grid values for every dtype: the product sums are computed
+    once per case and never modified."""
+    c = NONFINITE_CONV_CASES[name]
+    B, tr = 2, bool(c.get('transposed'))
+    cin = sum(c['cins'])
+    xs, wt, bias, res = grid_inputs(c['cins'], c['cout'], c['k'], B, c['h'], c['w'], dtype, wshape=(cin, c['cout'], 2, 2) if tr else None,
+                                    res_hw=(c['h'] // c['s'], c['w'] // c['s']) if c['res'] else None)
+    assert_grid_exact(xs, wt, bias, dtype, fan_in=cin if tr else None)
+    xs = [plant_nonfinite(x, plan) for x, plan in zip(xs, c['x'])]
+    if c['res']:
+        res = plant_nonfinite(res, c['res'])
+    if name not in _nonfinite_cache:
+        _nonfinite_cache[name] = conv_nonfinite_ref(xs, wt, torch.zeros_like(bias), c['k'], c['s'], transposed=tr, terms=True)
+    acc, terms = _nonfinite_cache[name]
+    pre = acc + bias.view(1, -1, 1, 1)
+    wants = {(a, r): nonfinite_epilogue(pre, a, dtype, res if r else None) for a, r in c['epilogues']}
+    return dict(case=c, xs=xs, wt=wt, bias=bias, res=res, pre=pre, terms=terms, wants=wants)
+
+
+def nonfinite_weight_data(dtype):
+    """The layer of 'conv3x3' on clean activations with ONE weight +inf, the top-left tap of (cout 5, cin 20): output channel 5 is
+    +-inf by the sign of the activation under that tap, NaN where that activation is 0 and -- the point -- NaN along the top row and
+    the left column, where the tap lies on the zero padding (inf * 0): a kernel that skipped halo taps would give a number there."""
+    c = NONFINITE_CONV_CASES['conv3x3']
+    xs, wt, bias, res = grid_inputs(c['cins'], c['cout'], 3, 2, c['h'], c['w'], dtype, res_hw=(c['h'], c['w']))
+    assert_grid_exact(xs, wt, bias, dtype)
+    wt = plant_nonfinite(wt, [('+inf', (5, 20, 0, 0))])
+    if 'weight' not in _nonfinite_cache:
+        _nonfinite_cache['weight'] = conv_nonfinite_ref(xs, wt, torch.zeros_like(bias), 3, 1)
+    pre = _nonfinite_cache['weight'] + bias.view(1, -1, 1, 1)
+    wants = {(a, r): nonfinite_epilogue(pre, a, dtype, res if r else None) for a, r in EPILOGUES4}
+    return dict(case=c, xs=xs, wt=wt, bias=bias, res=res, pre=pre, wants=wants)
+
+
+# ---- the SPPF pool chain on non-finite data --------------------------------------------------------------------------------------
+POOL_NONFINITE_SHAPES = [(8, 4, 3, 2), (32, 2, 1, 2), (16, 1, 5, 2), (64, 13, 7, 2), (40, 40, 40, 2),          # (c, h, w, B); the last: 1024 threads
+                         (512, 4, 4, 16), (1024, 4, 4, 16), (1024, 4, 4, 32)]                                    # 2, 4 and 8 granules per workgroup
+POOL_GP = {(512, 4, 4, 16): 2, (1024, 4, 4, 16): 4, (1024, 4, 4, 32): 8}
+
+
+def pool_granules(c, h, w, B, esz):
+    """Restatement of pool_launch_t's rule (lp_aux.hip): granules (8 channels) per workgroup = the largest of 8, 4, 2 that divides the
+    granule count, keeps the two LDS planes within 64 KiB and still gives 512 workgroups; else 1."""
+    cs = (c + 7) // 8 * 8
+    for cand in (8, 4, 2):
+        if (cs // 8) % cand == 0 and h * w * cand * 8 * esz * 2 <= 64 * 1024 and B * (cs // 8 // cand) >= 512:
+            return cand
+    return 1
+
+
+def pool_nonfinite_data(c, h, w, B, finite=False):
+    """[B, c, h, w] float64 of values every storage type holds (normal deviates rounded to bf16) and, unless ``finite``, in the eight
+    channels of granule g = image index (so the images differ): channel 0 a NaN in the middle of the map -- it sits at each of the up to
+    25 positions of the windows around it --, channels 1..3 a NaN in the first pixel, in the last pixel and on the middle of the left
+    edge (windows clipped by every border), channel 4 one +inf, channel 5 a 7 x 7 (or the whole map's) block of -inf in the top-left
+    corner: the windows inside it are all -inf through the three pools."""
+    g = torch.Generator().manual_seed(c * 1000 + h * 10 + w)
+    x = torch.randn(B, c, h, w, generator=g).to(torch.bfloat16).double()
+    if finite:
+        return x
+    plan = []
+    for b in range(B):
+        c0 = 8 * (b % (c // 8))
+        plan += [('nan', (b, c0, h // 2, w // 2)), ('nan', (b, c0 + 1, 0, 0)), ('nan', (b, c0 + 2, h - 1, w - 1)), ('nan', (b, c0 + 3, h // 2, 0)),
+                 ('+inf', (b, c0 + 4, h // 3, w - 1 - w // 3)), ('-inf', (b, c0 + 5, slice(0, 7), slice(0, 7)))]
+    return plant_nonfinite(x, plan)
+
+
+def pool_chain_sep(x, op):
+    """The three chained 5x5 stride-1 pools as lp_aux.hip computes them -- a row pass and a column pass over the taps inside the image,
+    left to right / top to bottom -- with the two-operand maximum ``op``: 'maximum' (IEEE 754-2019: NaN propagates), 'maxnum' (a NaN
+    operand is dropped) or 'select' (c > a ? c : a).  -> [y1, y2, y3]."""
+    f = {'maximum': torch.maximum, 'maxnum': torch.fmax, 'select': lambda a, c: torch.where(c > a, c, a)}[op]
+
+    def axis_pass(t, dim):
+        n = t.shape[dim]
+        out = []
+        for i in range(n):
+            m = t.select(dim, max(0, i - 2))
+            for j in range(max(0, i - 2) + 1, min(n - 1, i + 2) + 1):
+                m = f(m, t.select(dim, j))
+            out.append(m)
+        return torch.stack(out, dim)
+    ys = []
+    for _ in range(3):
+        x = axis_pass(axis_pass(x, 3), 2)
+        ys.append(x)
+    return ys
+
+
 def rounding_stats(pre64, act, dtype):
     """Fractions of the pre-rounding outputs (after the activation) that the storage type cannot hold, and that are exact ties."""
     v = (torch.relu(pre64) if act == 'relu' else pre64)

@@ -57,10 +57,12 @@ def _check(eng, dsts, wants, what):
             X.assert_bits(eng.tensor_view(d), w, '%s, output %d' % (what, i))
 
 
-def _walk(eng, ops, dsts, wants, variants, x, tag, B, fused_nan=()):
+def _walk(eng, ops, dsts, wants, variants, x, tag, B, fused_nan=(), check=None, choices=4):
     """Every variant of ``variants`` that takes the ops, and for each the tile choices 0..3 (a choice that repeats the tile before
     it is skipped): poisoned LDS in front of the pipelined kernels, NaN-filled destinations, the exact bits out.  Returns
-    {family: {(TH, TW)}} of what ran."""
+    {family: {(TH, TW)}} of what ran.  ``check``: the comparison in place of _check (tests/test_nonfinite_gpu.py: expected tensors
+    that hold NaN); ``choices``: tile choices 0 .. choices - 1 only."""
+    check = check or _check
     ran = {}
     for cfg, nb in variants:
         try:
@@ -69,7 +71,7 @@ def _walk(eng, ops, dsts, wants, variants, x, tag, B, fused_nan=()):
         except RuntimeError:
             continue                                        # the variant does not fit the layer (or the dtype)
         prev = None
-        for choice in range(4):
+        for choice in range(choices):
             try:
                 for op in ops:
                     eng.set_tile(op, choice)
@@ -86,7 +88,7 @@ def _walk(eng, ops, dsts, wants, variants, x, tag, B, fused_nan=()):
             for d in list(dsts) + list(fused_nan):
                 eng.tensor_view(d).fill_(NAN)
             eng.forward(x)
-            _check(eng, dsts, wants, '%s variant %d/%d choice %d tile %dx%d' % (tag, cfg, nb, choice, th, tw))
+            check(eng, dsts, wants, '%s variant %d/%d choice %d tile %dx%d' % (tag, cfg, nb, choice, th, tw))
             if th:
                 ran.setdefault(_family(cfg), set()).add((th, tw))
                 SEEN.setdefault(_family(cfg), set()).add((th, tw))
@@ -527,7 +529,7 @@ def test_special_values(case, dtype):
 @pytest.mark.parametrize('dtype', [F16, BF16], ids=['f16', 'bf16'])
 def test_signed_zero(dtype):
     """All-zero activations, negative weights, bias -0.0: every product is -0.0 and so is, by IEEE 754, their sum (the accumulators
-    start at the bias): -0.0 in front of the ReLU.  ReLU (v > 0 ? v : 0) must give +0.0, compared as the raw bit pattern.
+    start at the bias): -0.0 in front of the ReLU.  ReLU (the IEEE maximum with +0.0) must give +0.0, compared as the raw bit pattern.
     Without activation the result is a zero whose sign is NOT pinned: the matrix cores return +0.0 for this sum (measured on an
     MI355X: every kernel, fp16 and bf16), a property of the MFMA accumulation and not of the kernels (exact tests)."""
     from yolov6.hip import abi

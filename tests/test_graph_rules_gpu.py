@@ -2,8 +2,8 @@
 convolution and lp_testing.exact_epilogue give the bits of every tensor in advance).
 
 A wrong "nobody else reads it" answer of the library raises no error: it leaves a tensor that some op reads and no kernel wrote.
-NaN poison alone does not show that (a ReLU consumer turns NaN into 0, and a stale tensor of the previous forward of the same input
-is even the right value), so every tensor of the arena is filled with a marked NaN pattern before the forward and EVERY tensor of
+NaN poison alone does not show that (a stale tensor of the previous forward of the same input is even the right value; a ReLU consumer
+no longer turns NaN into 0 -- DESIGN 4.1.5 -- but a NaN behind it only says that SOMETHING upstream was unwritten), so every tensor of the arena is filled with a marked NaN pattern before the forward and EVERY tensor of
 the graph is compared with its expected bits afterwards -- the one a fused form would have kept on chip included.
 
   * every changed graph of lp_testing's tables (the ones test_graph_rules_cpu.py shows to be refused) runs with the tuner on, the

@@ -794,6 +794,14 @@ def test_iou_predicate_product_form_equals_the_division(iou_thres):
     pairs.append(np.array([[0, 0, 0, 0, 0, 0, 0, 0], [0, 0, 10, 10, 10, 0, 20, 10], [5, 5, 1, 1, 0, 0, 10, 10],
                            [0, 0, 1e20, 1e20, 0, 0, 1e20, 1e20], [0, 0, 3e38, 3e38, 0, 0, 3e38, 3e38], [0, 0, 1e-30, 1e-30, 0, 0, 1e-30, 1e-30],
                            [0, 0, 10, 10, 0, 0, 10, 10], [0, 0, 10, 10, 2, 2, 8, 8]], dtype=f32))
+    # NaN and infinite coordinates (tests/test_nonfinite_gpu.py: what a diverged box head hands the NMS): a NaN anywhere makes the IoU
+    # NaN, an infinite side makes it 0 or, inf - inf or inf / inf, NaN -- `> threshold` is false for all of them, in both forms
+    nan, inf = np.nan, np.inf
+    nonfinite = np.array([[nan, 0, 10, 10, 0, 0, 10, 10], [0, 0, 10, 10, 0, nan, 10, 10], [0, 0, 10, nan, 0, 0, 10, nan], [nan] * 8,
+                          [0, 0, inf, 10, 0, 0, 10, 10], [-inf, 0, inf, 10, 0, 0, 10, 10], [0, 0, inf, inf, 0, 0, inf, inf],
+                          [-inf, -inf, inf, inf, -inf, -inf, inf, inf], [inf, inf, inf, inf, 0, 0, 10, 10], [0, 0, 10, 10, -inf, 0, -inf, 10],
+                          [0, 0, 10, 10, 2, 2, inf, 8], [nan, 0, 10, 10, 0, 0, inf, inf], [0, 0, 10, 10, 0, 0, 10, 10]], dtype=f32)
+    pairs.append(nonfinite)
     q = np.ascontiguousarray(np.concatenate(pairs, 0).astype(f32))
     with np.errstate(all='ignore'):
         ia = (q[:, 2] - q[:, 0]) * (q[:, 3] - q[:, 1])
@@ -805,6 +813,7 @@ def test_iou_predicate_product_form_equals_the_division(iou_thres):
         inter = (w * h).astype(f32)
         ovr = inter / ((ia + ja).astype(f32) - inter).astype(f32)
         want = ovr.astype(np.float64) > iou_thres            # torchvision compares in double against the python float
+    assert not want[-len(nonfinite):-1].any() and np.isnan(ovr[-len(nonfinite):-1]).sum() >= 6      # (the last row: a finite sentinel)
     dq = torch.from_numpy(q).cuda()
     out = torch.zeros(len(q), dtype=torch.uint8, device='cuda')
     abi.check(abi.load().lp_check_iou_predicate(ctypes.c_void_p(dq.data_ptr()), len(q), float(iou_thres), ctypes.c_void_p(out.data_ptr()),

@@ -113,19 +113,35 @@ int input_s2d_launch(const void* x, int x_dtype, void* dst, int dtype, int B, in
 // group lives in LDS and each pool is a separable row pass + column pass (max is exact in every dtype, so
 // separability and the activation dtype do not change results).  Out-of-image taps are skipped, which is
 // what -inf padding does.
-// Element-wise max of 8 channels (one 16-B granule; fp32: 32 B).  fp16 uses the packed max (4 instructions, no
-// conversions); max of finite values is exact in every type.
+// Element-wise max of 8 channels (one 16-B granule; fp32: 32 B).  fp16 uses the packed maximum (no conversions); the max
+// of two values is one of them, so the result is exact in every type.  It is the IEEE 754-2019 maximum, not maxNum: a window
+// that holds a NaN gives NaN wherever the NaN sits in it, as F.max_pool2d does (maxNum and `c > a ? c : a` both drop it).
 template <typename T> struct Max8 {
     typedef T V8 __attribute__((ext_vector_type(8)));
     static __device__ __forceinline__ V8 f(V8 a, V8 c) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) a[k] = (float)c[k] > (float)a[k] ? c[k] : a[k];
+        for (int k = 0; k < 8; ++k) a[k] = (T)__builtin_elementwise_maximum((float)a[k], (float)c[k]);
+        return a;
+    }
+};
+// bf16 is the upper half of an fp32: widening is a shift, and the maximum (one of its operands, or a quiet NaN whose quiet bit
+// lies in the upper half) narrows by truncation -- no rounding sequence per element
+template <> struct Max8<bf16> {
+    typedef bf16 V8 __attribute__((ext_vector_type(8)));
+    static __device__ __forceinline__ V8 f(V8 a, V8 c) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float fa = __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, (bf16)a[k]) << 16);
+            const float fc = __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, (bf16)c[k]) << 16);
+            const unsigned m = __builtin_bit_cast(unsigned, __builtin_elementwise_maximum(fa, fc));
+            a[k] = __builtin_bit_cast(bf16, (unsigned short)(m >> 16));
+        }
         return a;
     }
 };
 template <> struct Max8<f16> {
     typedef f16 V8 __attribute__((ext_vector_type(8)));
-    static __device__ __forceinline__ V8 f(V8 a, V8 c) { return __builtin_elementwise_max(a, c); }
+    static __device__ __forceinline__ V8 f(V8 a, V8 c) { return __builtin_elementwise_maximum(a, c); }
 };
 
 // One workgroup per (image, GP granules = 8*GP channels): the plane sits in LDS, three chained separable 5x5 passes.

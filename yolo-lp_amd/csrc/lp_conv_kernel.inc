@@ -117,7 +117,9 @@ enum { ACT_SIGMOID = 3 };   // MODE_PRED; the other codes are lp_act
 // (56 M sigmoids per step in the class predictors alone); 1 ulp is three orders below the parity tolerance.
 __device__ __forceinline__ float sigmoid_fast(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
 template <int ACT> __device__ __forceinline__ float act_c(float v) {
-    if (ACT == LP_ACT_RELU) return v > 0.f ? v : 0.f;
+    // IEEE 754-2019 maximum: NaN stays NaN (torch.relu's result; `v > 0.f ? v : 0.f` stored a NaN pre-activation as +0.0 and
+    // hid a diverged layer from everything behind it), -0.0 and negatives give +0.0.  One v_maximum3_f32 on gfx950.
+    if (ACT == LP_ACT_RELU) return __builtin_elementwise_maximum(v, 0.f);
     if (ACT == LP_ACT_SILU) {
         // The product is pinned in an fp32 register: otherwise some instantiations fold the multiply into the following
         // f32 -> f16 conversion (v_fma_mixlo_f16) and others do not, and kernel variants differ by one f16 ulp.
