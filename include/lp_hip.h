@@ -1017,8 +1017,8 @@ int lp_lookback_update(void* state, int n_streams, int max_tracks, int depth, in
  * (cost, mismatch), then one atomic minimum and one atomic add per workgroup and read with a hit; a tail kernel writes match_i.
  * max_ended == 0 launches nothing; n_entries == 0 launches the tail alone.
  *   workspace: 16-byte aligned, lp_watch_workspace_bytes(n_streams, max_ended) bytes; it may hold anything on entry.
- * What it does not do: no insertions or deletions; no alert while a track is live (ended records only: lp_watch_live does that); one best entry plus a count,
- * not a ranked list; no update in place of the list.
+ * What it does not do: no insertions or deletions (lp_watch_match_indel below tolerates one); no alert while a track is live (ended
+ * records only: lp_watch_live does that); one best entry plus a count, not a ranked list; no update in place of the list.
  * Every argument is checked before the first launch (LP_ERR_ARG, nothing launched): n_entries outside 0..LP_WATCH_MAX_ENTRIES,
  * n_streams < 1, max_ended < 0, n_streams * max_ended * 12 at or above 2^31, max_mismatch outside 0..8, max_cost outside
  * 0..LP_WATCH_MAX_COST; with max_ended > 0: ended_count or match_i null; with n_entries > 0 as well: entries, ended_i, ended_f or the
@@ -1031,6 +1031,47 @@ size_t lp_watch_workspace_bytes(int n_streams, int max_ended);   /* 0: bad argum
 int lp_watch_match(const unsigned char* entries, int n_entries, const unsigned char* confuse /* NULL: all 16 */,
                    const int32_t* ended_i, const float* ended_f, const int32_t* ended_count, int n_streams, int max_ended,
                    int max_mismatch, int max_cost, int32_t* match_i, void* workspace, size_t workspace_bytes, void* stream);
+
+/* lp_watch_match_indel: lp_watch_match that survives one lost or gained character.  When two narrow glyphs merge, a rivet is read as a
+ * character or a 7-character plate is read as 8, every later head moves by one and the positional distance charges four or five
+ * mismatches for one error.  Heads 2..7 share one alphabet and one confusion group, so read head p is also compared with entry head
+ * p + 1 and p - 1.  Arguments, reads and rules 1 and 2 are lp_watch_match's; yolov6/utils/watch.py::watch_match_np(..., indel,
+ * gap_cost, align=True) restates the rules below on every int32.
+ * Per read, entry e and position p let U[p] be the (cost, mismatch) pair of rule 2 for w = entries[e][p], L[p] (p in 2..6) the pair for
+ * w = entries[e][p + 1] and R[p] (p in 3..7) the pair for w = entries[e][p - 1]; 255, ids 64..254 and a best[p] outside 0..63 behave
+ * in L and R as in U.  With indel == 1 an entry is scored under 12 alignments, each U[0] + U[1] plus
+ *   code 0        unshifted: sum U[2..7];
+ *   codes 1..5    the read lost the character at entry head k = 2..6 (code k - 1): sum U[2..k-1] + sum L[k..6]; read head 7 is not
+ *                 compared;
+ *   codes 6..10   the read gained a character at read head k = 2..6 (code k + 4): sum U[2..k-1] + sum R[k+1..7]; read head k and
+ *                 entry head 7 are not compared;
+ *   code 11       the error is at the end: sum U[2..6]; head 7 is compared on neither side;
+ * codes 1..11 add gap_cost (cost units, 0..LP_WATCH_MAX_GAP_COST = one fully confident mismatch) to the cost and 1 to the
+ * mismatches, so the cost stays <= LP_WATCH_MAX_COST.  The entry's score is the alignment with the smallest (cost, mismatches,
+ * code); e is accepted iff THAT alignment has mismatches <= max_mismatch and cost <= max_cost.  Across entries as lp_watch_match:
+ * the smallest (cost, index) wins, n_hits counts the accepted entries.
+ *   match_i: as lp_watch_match; its mismatches count the gap.
+ *   match_align: int32 [n_streams,max_ended]: the winning entry's code; 0 on every line without a hit.  Every line is written.
+ * With indel == 0 only code 0 exists: match_i is lp_watch_match's on every int32 (its scan kernel runs) and match_align is 0.
+ * With max_mismatch == 1 a shifted read must be otherwise exact.
+ * Three launches as lp_watch_match, with the same prep kernel and workspace (lp_watch_workspace_bytes).  The scan builds the same LDS
+ * table in blocks of LP_WATCH_INDEL_QUERY_BLOCK reads; per (entry, read) it does 18 lookups, 8 for U and 5 each for L and R (row p
+ * of the table at the column of the entry's head p + 1 / p - 1), and takes the minimum over the 12 alignments in one pass over the
+ * positions: the prefix sum of U, the best deletion opened so far plus L[p], the best insertion opened so far plus R[p], all on the
+ * word (cost << 12 | mismatches << 4 | code), whose unsigned order is the (cost, mismatches, code) order.  The code travels with the
+ * lane's best entry into the 64-bit key (cost << 32 | index << 8 | code << 4 | mismatches; the index above the code keeps the order
+ * across entries (cost, index)).
+ * What it does not do: more than one gap; gaps in heads 0 and 1 (other alphabets); the sightings log (lp_sight_update stays
+ * positional); a ranked list of matches.
+ * Checked before the first launch (LP_ERR_ARG, nothing launched): everything lp_watch_match checks, indel outside 0..1, gap_cost
+ * outside 0..LP_WATCH_MAX_GAP_COST, match_align null (max_ended > 0), and match_i, match_align or the workspace overlapping an
+ * input or each other. */
+#define LP_WATCH_MAX_GAP_COST 4096
+#define LP_WATCH_INDEL_QUERY_BLOCK 16 /* reads per LDS table of lp_watch_match_indel's scan */
+int lp_watch_match_indel(const unsigned char* entries, int n_entries, const unsigned char* confuse /* NULL: all 16 */,
+                         const int32_t* ended_i, const float* ended_f, const int32_t* ended_count, int n_streams, int max_ended,
+                         int max_mismatch, int max_cost, int indel /* 0 or 1 */, int gap_cost, int32_t* match_i, int32_t* match_align,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* lp_watch_live: look the reads of the tracks that are still LIVE up in a watchlist, once per track and read.  lp_watch_match answers
  * when a track has ended, max_age frames after the plate was last seen; a permit holder waiting at a barrier, or a stolen vehicle
@@ -1070,7 +1111,8 @@ int lp_watch_match(const unsigned char* entries, int n_entries, const unsigned c
  *   workspace: 16-byte aligned, lp_watch_live_workspace_bytes(n_streams, max_tracks) bytes; it may hold anything on entry.
  * What it does not do: the read is the one at the end of the tracker call (several frames of a stream in one call: at most one
  * lookup per track); the memoised cost is as of the lookup (a read whose key stays while its shares move is not scored again; the
- * ended-record match stays the final word); and, as lp_watch_match, no insertions or deletions, one best entry plus a count.
+ * ended-record match stays the final word); and, as lp_watch_match, no insertions or deletions (lp_watch_live_indel below tolerates
+ * one), one best entry plus a count.
  * Every argument is checked before the first launch (LP_ERR_ARG, nothing launched): n_streams < 1, max_tracks outside
  * 1..LP_TRACK_MAX_TRACKS, n_streams * max_tracks * 12 at or above 2^31, ncls null or a width outside 1..LP_TRACK_MAX_CLS,
  * min_hits < 1, n_entries outside 0..LP_WATCH_MAX_ENTRIES, max_mismatch outside 0..8, max_cost outside 0..LP_WATCH_MAX_COST, a null
@@ -1083,6 +1125,23 @@ int lp_watch_live(const void* track_state, int n_streams, int max_tracks, const 
                   const unsigned char* entries, int n_entries, const unsigned char* confuse /* NULL: all 16 */,
                   int max_mismatch, int max_cost, int32_t* q_i, float* q_f, int32_t* q_slot, int32_t* q_count, int32_t* live_i,
                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* lp_watch_live_indel: lp_watch_live whose step 5 is lp_watch_match_indel(..., indel, gap_cost).  Everything else -- the memo and its
+ * eight words, the "look up once per read" rule, the queries, live_i -- is lp_watch_live's, and with indel == 0 every word of them is
+ * what lp_watch_live writes.  One output more:
+ *   8. live_align: int32 [n_streams,max_tracks], one alignment code per slot.  It is STATE beside the memo, in a tensor the caller
+ *      (the tracker) owns and zeroes once together with the memo: a fresh slot gets the code of its lookup, a slot whose row of
+ *      live_i is a standing one (live, memo holds its id, not fresh) keeps the code it has, every other slot gets 0.  So the
+ *      alignment code of a standing hit is the one of its lookup, and a stream whose memo is zeroed needs no zeroing of live_align.
+ *   workspace: 16-byte aligned, lp_watch_live_indel_workspace_bytes(n_streams, max_tracks) bytes (lp_watch_live's plus the
+ *   match_align of step 5).
+ * Checked before the first launch: everything lp_watch_live checks, indel outside 0..1, gap_cost outside
+ * 0..LP_WATCH_MAX_GAP_COST, live_align null or overlapping another buffer. */
+size_t lp_watch_live_indel_workspace_bytes(int n_streams, int max_tracks);   /* 0: bad arguments */
+int lp_watch_live_indel(const void* track_state, int n_streams, int max_tracks, const int* ncls /* HOST [8] */, int min_hits,
+                        int32_t* memo, const unsigned char* entries, int n_entries, const unsigned char* confuse /* NULL: all 16 */,
+                        int max_mismatch, int max_cost, int indel /* 0 or 1 */, int gap_cost, int32_t* q_i, float* q_f, int32_t* q_slot,
+                        int32_t* q_count, int32_t* live_i, int32_t* live_align, void* workspace, size_t workspace_bytes, void* stream);
 
 /* lp_sight_update: a device-resident log of sightings.  Every read that ends in a tracker call is matched against the recent reads
  * of all streams -- the car the exit camera reads now is the car the entry camera read 40 minutes ago; a plate hidden for longer than

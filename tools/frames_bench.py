@@ -8,7 +8,7 @@
     python tools/frames_bench.py --tile --gate [--gate-moving K] [--gate-thres F] [--gate-refresh N] [--nv12 [bt709]] [--tile-frame 2160 3840] [--runs 3]
     python tools/frames_bench.py --tile --gate --gate-illum gain --gate-drift A [--gate-drift-period 8] [--gate-moving K] [--nv12 [bt709]] [--runs 3]
     python tools/frames_bench.py --track [--track-batch 32] [--runs 3] [--best-shot [--stack]] [--redact [--hold [--lookback D]]] [--nv12]
-                                 [--watch N [--watch-mismatch 1] [--watch-live [--watch-live-min-hits 1]]] [--sightings C] [--zones L Z] [--speed]
+                                 [--watch N [--watch-mismatch 1] [--watch-indel] [--watch-live [--watch-live-min-hits 1]]] [--sightings C] [--zones L Z] [--speed]
     python tools/frames_bench.py --nv12 [bt709] [--batches 32] [--crops N] [--runs 3]          (also with --tile)
     python tools/frames_bench.py --jpeg Q [--jpeg-frames 4] [--jpeg-restart 16] [--tile-frame 2160 3840] [--nv12 [bt601f]] [--redact]
     python tools/frames_bench.py --annotate [--annotate-plates N] [--jpeg-frames 4] [--tile-frame 2160 3840] [--nv12 [bt601f]]
@@ -129,6 +129,8 @@ def parse():
                                                                           'sightings of C slots on the ended reads (lp_sight_update), '
                                                                           'and lp_watch_match on a list of C entries and the same reads')
     ap.add_argument('--watch-mismatch', type=int, default=1, help='with --watch: positions that may differ')
+    ap.add_argument('--watch-indel', action='store_true', help='with --watch: also time the lookup that tolerates one lost or gained character '
+                                                               '(lp_watch_match_indel) on the same list, reads and limits')
     ap.add_argument('--watch-live', action='store_true', help='with --watch: also time the lookup of the live tracks (lp_watch_live), on a '
                                                               'step with fresh reads and on one without')
     ap.add_argument('--watch-live-min-hits', type=int, default=1, help='with --watch-live: detections a track needs before it is looked up')
@@ -631,7 +633,8 @@ def watch_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
     """--track --watch N: device time of lp_watch_match behind the update, from events on one stream.  The list is seeded and
     random (ids within the model's head widths); every step flushes every stream, so the tracks the step began end in it and
     their reads are looked up (``reads_per_step``).  ``block_ms`` is the same call on exactly one query block of synthetic reads:
-    the scan's cost per pass over the list, whatever the detector finds."""
+    the scan's cost per pass over the list, whatever the detector finds.  ``--watch-indel``: lp_watch_match_indel (indel = 1, the
+    default gap cost) right behind each of the two calls, on the same list, reads and limits: ``indel_ms`` / ``indel_block_ms``."""
     import torch
     from yolov6.hip import abi, runtime
     from yolov6.utils.track import ncls_of
@@ -646,7 +649,7 @@ def watch_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
     bi, bf = np.zeros((1, QB, 12), np.int32), np.zeros((1, QB, 12), np.float32)
     bi[0, :, 4:], bf[0, :, :8] = np.stack([rng.integers(0, n, QB) for n in ncls], 1), rng.random((QB, 8))
     block = [torch.from_numpy(a).to(dev) for a in (bi, bf, np.array([QB], np.int32))]
-    ms, block_ms, reads = [], [], []
+    ms, block_ms, reads, indel_ms, indel_block_ms = [], [], [], [], []
     for k in range(args.reps + 2):
         frames = batcher.put([pool[(j + k) % len(pool)] for j in range(B)])
         xx, _ = runtime.preprocess_frames(frames, size, stride, tdt, batch=B, out=x)
@@ -660,13 +663,31 @@ def watch_stages(args, model, dev, tdt, batcher, pool, x, net_hw):
         ev[2].record()
         wl.match(*block, args.watch_mismatch)
         ev[3].record()
+        if args.watch_indel:
+            xe = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            xe[0].record()
+            wl.match(ended_i, ended_f, ended_count, args.watch_mismatch, indel=1)
+            xe[1].record()
+            xe[2].record()
+            wl.match(*block, args.watch_mismatch, indel=1)
+            xe[3].record()
         torch.cuda.synchronize()
         if k >= 2:
             ms.append(ev[0].elapsed_time(ev[1]))
             block_ms.append(ev[2].elapsed_time(ev[3]))
             reads.append(int(ended_count.clamp(0, ended_i.shape[1]).sum()))
+            if args.watch_indel:
+                indel_ms.append(xe[0].elapsed_time(xe[1]))
+                indel_block_ms.append(xe[2].elapsed_time(xe[3]))
     med, bmed, nreads = float(np.median(ms)), float(np.median(block_ms)), float(np.mean(reads))
-    return dict(entries=N, max_mismatch=args.watch_mismatch, reps=args.reps, watch_ms=round(med, 4), reads_per_step=round(nreads, 1),
+    extra = {}
+    if args.watch_indel:
+        imed, ibmed = float(np.median(indel_ms)), float(np.median(indel_block_ms))
+        extra = dict(indel_ms=round(imed, 4), indel_over_watch=round(imed / med, 3), indel_block_reads=QB, indel_block_ms=round(ibmed, 4),
+                     indel_block_over_block=round(ibmed / bmed, 3), indel_block_pairs_per_s=round(N * QB / (ibmed * 1e-3), 1),
+                     watch_runs_ms=[round(v, 4) for v in ms], block_runs_ms=[round(v, 4) for v in block_ms],
+                     indel_runs_ms=[round(v, 4) for v in indel_ms], indel_block_runs_ms=[round(v, 4) for v in indel_block_ms])
+    return dict(extra, entries=N, max_mismatch=args.watch_mismatch, reps=args.reps, watch_ms=round(med, 4), reads_per_step=round(nreads, 1),
                 pairs_per_s=round(N * nreads / (med * 1e-3), 1), block_reads=QB, block_ms=round(bmed, 4),
                 block_pairs_per_s=round(N * QB / (bmed * 1e-3), 1), block_list_bytes_per_s=round(N * 8 / (bmed * 1e-3), 1))
 

@@ -11,7 +11,7 @@
                            [--redact-hold [--redact-hold-min-hits 1] [--redact-lookback D [--redact-lookback-max-back N]]]]
                           [--track --watchlist FILE [--watch-mismatch 1] [--watch-cost F]
                            [--watch-confusable "0D 0Q 8B 2Z 5S" [--watch-confusable-weight 4]]
-                           [--watch-live [--watch-live-min-hits 3]]]
+                           [--watch-live [--watch-live-min-hits 3]] [--watch-indel [--watch-gap-cost 1.0]]]
                           [--track --sightings C [--sight-window N] [--sight-min-hits 1] [--sight-mismatch 1] [--sight-cost F]]
                           [--track --zones FILE [--zones-min-hits 1]]
                           [--track --speed FILE [--speed-min-hits 1] [--speed-confirm 2]]
@@ -111,6 +111,10 @@ _FLAGS = [
     ('--watch-live', dict(action='store_true', help='with --watchlist: also look a track up while it is still live, once it has enough '
                                                     'detections and again when its voted read changes, and write alerts.txt')),
     ('--watch-live-min-hits', dict(type=int, default=3, metavar='N', help='with --watch-live: detections a track needs before it is looked up')),
+    ('--watch-indel', dict(action='store_true', help='with --watchlist: also accept a read that lost or gained one character in heads 2..7 '
+                                                     '(counted as one mismatch); hits.txt and alerts.txt gain an alignment column')),
+    ('--watch-gap-cost', dict(type=float, default=1.0, metavar='F', help='with --watch-indel: what the lost or gained character costs, in fully '
+                                                                         'confident mismatches (0..1)')),
     ('--sightings', dict(type=int, default=None, metavar='C',
                          help='with --track: keep a log of the last C reads of all streams, match the read of every ended track against the '
                               'earlier ones (a broken track, the same vehicle on another video) and write resightings.txt beside plates.txt; '
@@ -181,7 +185,8 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
         watch_live=False, watch_live_min_hits=3, tile_gate=False, tile_gate_thres=2.0, tile_gate_min_cells=1, tile_gate_refresh=50,
         tile_gate_illum='none', tile_gate_max_gain=1.5, sightings=None, sight_window=None, sight_min_hits=1, sight_mismatch=1, sight_cost=None,
         save_jpeg=None, overlay=False, overlay_font=None, overlay_size=24, overlay_thickness=2, overlay_alpha=(256, 160, 256),
-        zones=None, zones_min_hits=1, speed=None, speed_min_hits=1, speed_confirm=2, overlay_scene=False):
+        zones=None, zones_min_hits=1, speed=None, speed_min_hits=1, speed_confirm=2, overlay_scene=False,
+        watch_indel=False, watch_gap_cost=1.0):
     save_img = not not_save_img
     out_dir = save_dir if save_dir is not None else osp.join(project, name)
     if (save_img or save_txt or save_crops or track or redact or overlay) and not osp.exists(out_dir):
@@ -208,7 +213,7 @@ def run(weights=osp.join(ROOT, 'yolov6s.pt'), source=osp.join(ROOT, 'data/images
                       save_jpeg=save_jpeg, overlay=overlay, overlay_font=overlay_font, overlay_size=overlay_size,
                       overlay_thickness=overlay_thickness, overlay_alpha=tuple(overlay_alpha), zones=zones,
                       zones_min_hits=zones_min_hits, speed=speed, speed_min_hits=speed_min_hits, speed_confirm=speed_confirm,
-                      overlay_scene=overlay_scene).infer(
+                      overlay_scene=overlay_scene, watch_indel=watch_indel, watch_gap_cost=watch_gap_cost).infer(
         conf_thres, iou_thres, classes, agnostic_nms, max_det, out_dir, save_txt, save_img, hide_labels, hide_conf, view_img,
         save_crops=save_crops, crop_size=tuple(crop_size))
     if save_txt or save_img or save_crops:

@@ -233,6 +233,213 @@ __global__ __launch_bounds__(W_T) void watch_scan_kernel(const uint2* __restrict
     }
 }
 
+// ---- lp_watch_match_indel: the scan that tolerates one lost or gained character -----------------------------------------------------
+// Its own table, word layout and key; prep is shared.  A table word is (cost << 12) | (mismatch << 4): bits 0..3 stay free for the
+// alignment code and bits 9..11 for the lane's entry number, so that an unsigned comparison of two alignment words is the
+// (cost, mismatches, code) order of the rule.  Heads 2..7 share a confusion group, so L[p] and R[p] are row p of the table at the
+// column of the entry's head p + 1 / p - 1: three 16-byte reads per position where the positional scan has one.
+// Four reads (one uint4) are scored at a time, so the live accumulators are 3 x 4 whatever the query block; what grows with the
+// block are the two registers per read that carry a lane's best entry and count across its entries.
+constexpr int X_QB = LP_WATCH_INDEL_QUERY_BLOCK;
+constexpr int X_PITCH = X_QB + 4;                          // dwords between two columns: an odd number of 16-byte slots
+constexpr unsigned X_COST_SHIFT = 12, X_MISM_SHIFT = 4;
+constexpr unsigned X_GUARD = (1u << 8) | (1u << 30);       // the bits a field keeps iff it is within its limit
+constexpr unsigned X_OUTSIDE = 0x10000u << X_COST_SHIFT;   // start value of a lane's entries past N: a cost above every limit
+static_assert(X_QB % 4 == 0 && ((X_PITCH / 4) & 1) == 1, "columns must start on odd multiples of a 16-byte slot");
+
+struct IndelLds {
+    unsigned T[8 * W_COLS * X_PITCH];
+    uint2 ent[LP_WATCH_BLOCK_ENTRIES];                     // as ScanLds::ent
+    int best[X_QB * 8];
+    unsigned qp[X_QB * 8];
+    unsigned long long key[X_QB];
+    int cnt[X_QB];
+};
+
+template <int Q4>
+__device__ __forceinline__ void scan_block_indel(IndelLds& lds, int nlane, int idx0, const unsigned char* __restrict__ confuse,
+                                                 unsigned limits, unsigned gapw, int k0, int nq, const WatchWs& ws) {
+    constexpr int NQ = 4 * Q4;
+    const int tid = threadIdx.x;
+    // ---- the table, as scan_block builds it, in this kernel's word layout ----------------------------------------------------------
+    for (int u = tid; u < 8 * 17 * NQ; u += W_T) {
+        const int q = u % NQ, pc = u / NQ, p = pc / 17, c4 = pc - p * 17;
+        const int b = lds.best[q * 8 + p];
+        const unsigned qp = lds.qp[q * 8 + p];
+        const bool inr = (unsigned)b < 64u;
+        unsigned* col0 = lds.T + (p * W_COLS + c4 * 4) * X_PITCH + q;
+        if (c4 == 16) {
+            col0[0] = 0u;                                              // WILD
+            col0[X_PITCH] = ((qp * 16u) << X_COST_SHIFT) | (1u << X_MISM_SHIFT);       // an id that matches nothing
+            continue;
+        }
+        unsigned cw = 0x10101010u;
+        if (confuse != nullptr && inr) cw = *(const unsigned*)(confuse + ((p < 2 ? p : 2) * 4096 + b * 64 + c4 * 4));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            unsigned c = (cw >> (8 * k)) & 0xffu;
+            c = c > 16u ? 16u : c;
+            unsigned v = ((qp * c) << X_COST_SHIFT) | (1u << X_MISM_SHIFT);
+            if (inr && c4 * 4 + k == b) v = 0u;
+            col0[k * X_PITCH] = v;
+        }
+    }
+    __syncthreads();
+    // ---- the scan ------------------------------------------------------------------------------------------------------------------
+    unsigned best[NQ], cnt[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) { best[q] = ~0u; cnt[q] = 0u; }
+#pragma unroll 1
+    for (int r = 0; r < W_R; ++r) {
+        const uint2 ent = lds.ent[r * W_T + tid];
+        const unsigned start = r < nlane ? 0u : X_OUTSIDE;
+        const uint4* row[8];                                           // row[c]: the entry's head c as a column of position 0's table
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const unsigned col = ((c < 4 ? ent.x : ent.y) >> (8 * (c & 3))) & 0xffu;
+            row[c] = (const uint4*)lds.T + col * (X_PITCH / 4);
+        }
+        constexpr int POS4 = W_COLS * X_PITCH / 4;                     // uint4s between the tables of two positions
+#pragma unroll
+        for (int g = 0; g < Q4; ++g) {
+            unsigned pre[4], del[4], ins[4];                           // prefix of U; the best opened deletion / insertion so far
+            {
+                const uint4 a = row[0][g], b = row[1][POS4 + g];
+                pre[0] = start + a.x + b.x; pre[1] = start + a.y + b.y; pre[2] = start + a.z + b.z; pre[3] = start + a.w + b.w;
+            }
+#pragma unroll
+            for (int p = 2; p < 8; ++p) {
+                const uint4 u4 = row[p][p * POS4 + g];
+                const unsigned u[4] = {u4.x, u4.y, u4.z, u4.w};
+                if (p <= 6) {                                          // open at k = p: codes p - 1 (lost) and p + 4 (gained)
+                    const uint4 l4 = row[p + 1][p * POS4 + g];
+                    const unsigned l[4] = {l4.x, l4.y, l4.z, l4.w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const unsigned od = pre[i] | (unsigned)(p - 1);
+                        del[i] = (p == 2 ? od : (od < del[i] ? od : del[i])) + l[i];
+                    }
+                }
+                if (p >= 3) {
+                    const uint4 r4 = row[p - 1][p * POS4 + g];
+                    const unsigned rr[4] = {r4.x, r4.y, r4.z, r4.w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) ins[i] += rr[i];
+                }
+                if (p <= 6) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const unsigned oi = pre[i] | (unsigned)(p + 4);
+                        ins[i] = p == 2 ? oi : (oi < ins[i] ? oi : ins[i]);
+                    }
+                }
+                if (p == 7) {                                          // code 11, and the shifted alignments pay the gap
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const unsigned e = pre[i] | 11u;
+                        unsigned m = del[i] < ins[i] ? del[i] : ins[i];
+                        m = e < m ? e : m;
+                        del[i] = m + gapw;
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pre[i] += u[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int q = 4 * g + i;
+                const unsigned w = pre[i] < del[i] ? pre[i] : del[i];                  // code 0 wins a tie: its low bits are 0
+                const bool ok = ((limits - w) & X_GUARD) == X_GUARD;
+                const unsigned key = w | ((unsigned)r << 9);
+                best[q] = ok && (key >> X_COST_SHIFT) < (best[q] >> X_COST_SHIFT) ? key : best[q];      // the first of the smallest cost
+                cnt[q] += ok ? 1u : 0u;
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        if (cnt[q] != 0u) {
+            const unsigned r = (best[q] >> 9) & 7u;
+            const unsigned long long key = ((unsigned long long)(best[q] >> X_COST_SHIFT) << 32) |
+                                           ((unsigned long long)(unsigned)(idx0 + (int)r * W_T) << 8) | ((best[q] & 15u) << 4) |
+                                           ((best[q] >> X_MISM_SHIFT) & 15u);
+            atomicMin(&lds.key[q], key);
+            atomicAdd(&lds.cnt[q], (int)cnt[q]);
+        }
+    }
+    __syncthreads();
+    if (tid < nq && lds.cnt[tid] > 0) {
+        atomicMin(&ws.keys[k0 + tid], lds.key[tid]);
+        atomicAdd(&ws.cnts[k0 + tid], lds.cnt[tid]);
+    }
+}
+
+// grid (ceil(N / LP_WATCH_BLOCK_ENTRIES)), block (256)
+__global__ __launch_bounds__(W_T) void watch_scan_indel_kernel(const uint2* __restrict__ entries, int N, const unsigned char* __restrict__ confuse,
+                                                               const int32_t* __restrict__ ended_i, const float* __restrict__ ended_f,
+                                                               unsigned limits, unsigned gapw, WatchWs ws) {
+    __shared__ __attribute__((aligned(16))) IndelLds lds;
+    const int tid = threadIdx.x;
+    const int nv = ws.nvalid[0];
+    if (nv <= 0) return;                                               // (block-uniform)
+    const int idx0 = blockIdx.x * LP_WATCH_BLOCK_ENTRIES + tid;         // < 2^24 + 2048
+    int nlane = 0;
+#pragma unroll
+    for (int r = 0; r < W_R; ++r) {
+        const int idx = idx0 + r * W_T;
+        uint2 v = make_uint2(0u, 0u);
+        if (idx < N) { v = entries[idx]; nlane = r + 1; }
+        lds.ent[r * W_T + tid] = make_uint2(to_columns(v.x), to_columns(v.y));
+    }
+    for (int k0 = 0; k0 < nv; k0 += X_QB) {                            // nv <= n_streams * max_ended: k0 + q indexes qlist, keys, cnts
+        const int nq = nv - k0 < X_QB ? nv - k0 : X_QB;
+        if (tid < X_QB * 8) {
+            const int q = tid >> 3, p = tid & 7;
+            int b = -1;
+            unsigned qp = 1u;
+            if (q < nq) {
+                const int line = ws.qlist[k0 + q];
+                b = ended_i[(long long)line * W_ENDED_COLS + 4 + p];
+                const float share = ended_f[(long long)line * W_ENDED_COLS + p];
+                if (share > 0.f) qp = (unsigned)(int)fminf(share * 255.0f, 255.0f) + 1u;
+            }
+            lds.best[tid] = b;
+            lds.qp[tid] = qp;
+        }
+        if (tid < X_QB) { lds.key[tid] = ~0ull; lds.cnt[tid] = 0; }
+        __syncthreads();
+        if (nq <= 4) scan_block_indel<1>(lds, nlane, idx0, confuse, limits, gapw, k0, nq, ws);
+        else if (X_QB >= 8 && nq <= 8) scan_block_indel<X_QB >= 8 ? 2 : 1>(lds, nlane, idx0, confuse, limits, gapw, k0, nq, ws);
+        else if (X_QB >= 12 && nq <= 12) scan_block_indel<X_QB >= 12 ? 3 : 1>(lds, nlane, idx0, confuse, limits, gapw, k0, nq, ws);
+        else scan_block_indel<X_QB / 4>(lds, nlane, idx0, confuse, limits, gapw, k0, nq, ws);
+        __syncthreads();
+    }
+}
+
+// grid (ceil(L / 256)), block (256): watch_tail_kernel with match_align beside it.  coded == 0: the keys are the positional scan's
+// (index << 4 | mismatches) and every code is 0; coded == 1: index << 8 | code << 4 | mismatches.
+__global__ __launch_bounds__(256) void watch_tail_indel_kernel(const int32_t* __restrict__ ended_count, int S, int max_ended, int scanned, int coded,
+                                                               WatchWs ws, int32_t* __restrict__ match_i, int32_t* __restrict__ match_align) {
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= S * max_ended) return;
+    const int s = l / max_ended, j = l - s * max_ended;
+    int e = -1, mism = 0, cost = 0, n = 0, code = 0;
+    if (scanned && j < clamp_count(ended_count[s], max_ended)) {
+        const int k = ws.off[s] + j;
+        n = ws.cnts[k];
+        if (n > 0) {
+            const unsigned long long key = ws.keys[k];
+            e = coded ? (int)((key >> 8) & 0xffffffull) : (int)((key >> 4) & 0xfffffffull);
+            code = coded ? (int)((key >> 4) & 15ull) : 0;
+            mism = (int)(key & 15ull);
+            cost = (int)(key >> 32);
+        }
+    }
+    int32_t* out = match_i + (long long)l * 4;
+    out[0] = e; out[1] = mism; out[2] = cost; out[3] = n;
+    match_align[l] = code;
+}
+
 // grid (ceil(L / 256)), block (256).  scanned == 0 (an empty list): every line is (-1, 0, 0, 0) and the workspace is not read.
 __global__ __launch_bounds__(256) void watch_tail_kernel(const int32_t* __restrict__ ended_count, int S, int max_ended, int scanned, WatchWs ws,
                                                          int32_t* __restrict__ match_i) {
@@ -314,6 +521,67 @@ extern "C" int lp_watch_match(const unsigned char* entries, int n_entries, const
     }
     hipLaunchKernelGGL(watch_tail_kernel, dim3((unsigned)ceil_div(L, 256)), dim3(256), 0, st, ended_count, n_streams, max_ended, scan ? 1 : 0, ws,
                        match_i);
+    LP_HIP_CHECK(hipGetLastError());
+    return LP_OK;
+}
+
+extern "C" int lp_watch_match_indel(const unsigned char* entries, int n_entries, const unsigned char* confuse, const int32_t* ended_i,
+                                    const float* ended_f, const int32_t* ended_count, int n_streams, int max_ended, int max_mismatch,
+                                    int max_cost, int indel, int gap_cost, int32_t* match_i, int32_t* match_align, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    const std::string fn = "lp_watch_match_indel: ";
+    if (n_entries < 0 || n_entries > LP_WATCH_MAX_ENTRIES)
+        return fail(LP_ERR_ARG, fn + "n_entries " + std::to_string(n_entries) + " (need 0.." + std::to_string(LP_WATCH_MAX_ENTRIES) + ")");
+    if (!watch_dims_ok(n_streams, max_ended))
+        return fail(LP_ERR_ARG, fn + "need n_streams >= 1, max_ended >= 0 and n_streams * max_ended * 12 < 2^31");
+    if (max_mismatch < 0 || max_mismatch > 8 || max_cost < 0 || max_cost > LP_WATCH_MAX_COST)
+        return fail(LP_ERR_ARG, fn + "need max_mismatch in 0..8 and max_cost in 0.." + std::to_string(LP_WATCH_MAX_COST));
+    if (indel < 0 || indel > 1 || gap_cost < 0 || gap_cost > LP_WATCH_MAX_GAP_COST)
+        return fail(LP_ERR_ARG, fn + "need indel in 0..1 and gap_cost in 0.." + std::to_string(LP_WATCH_MAX_GAP_COST));
+    if (max_ended == 0) return LP_OK;                                  // no line to write
+    const bool scan = n_entries > 0;
+    if (!ended_count || !match_i || !match_align || (scan && (!entries || !ended_i || !ended_f || !workspace)))
+        return fail(LP_ERR_ARG, fn + "null pointer");
+    const WatchWs ws = watch_carve(workspace, (size_t)n_streams, (size_t)max_ended);
+    if (scan) {
+        if (((uintptr_t)entries & 7) != 0 || ((uintptr_t)confuse & 3) != 0 || ((uintptr_t)workspace & 15) != 0)
+            return fail(LP_ERR_ARG, fn + "entries must be 8-byte, confuse 4-byte and the workspace 16-byte aligned");
+        if (workspace_bytes < ws.bytes)
+            return fail(LP_ERR_ARG, fn + "workspace of " + std::to_string(workspace_bytes) + " bytes, need " + std::to_string(ws.bytes));
+    }
+    {   // neither output nor the workspace may overlap an input or each other
+        const size_t L = (size_t)n_streams * max_ended;
+        const Region reg[] = {{entries, (size_t)n_entries * 8, false},
+                              {confuse, scan && confuse ? (size_t)3 * 64 * 64 : 0, false},
+                              {ended_i, scan ? L * W_ENDED_COLS * 4 : 0, false},
+                              {ended_f, scan ? L * W_ENDED_COLS * 4 : 0, false},
+                              {ended_count, (size_t)n_streams * 4, false},
+                              {match_i, L * 16, true},
+                              {match_align, L * 4, true},
+                              {workspace, scan ? ws.bytes : 0, true}};
+        if (regions_clash(reg, (int)(sizeof(reg) / sizeof(reg[0]))))
+            return fail(LP_ERR_ARG, fn + "match_i, match_align and the workspace may overlap neither an input nor each other");
+    }
+
+    hipStream_t st = (hipStream_t)stream;
+    const int L = n_streams * max_ended;
+    if (scan) {
+        hipLaunchKernelGGL(watch_prep_kernel, dim3(1), dim3(W_PREP_T), 0, st, ended_count, n_streams, max_ended, ws);
+        LP_HIP_CHECK(hipGetLastError());
+        const dim3 grid((unsigned)ceil_div(n_entries, LP_WATCH_BLOCK_ENTRIES));
+        if (indel) {
+            const unsigned limits = 15u | ((unsigned)max_mismatch << X_MISM_SHIFT) | ((unsigned)max_cost << X_COST_SHIFT) | X_GUARD;
+            const unsigned gapw = ((unsigned)gap_cost << X_COST_SHIFT) | (1u << X_MISM_SHIFT);
+            hipLaunchKernelGGL(watch_scan_indel_kernel, grid, dim3(W_T), 0, st, (const uint2*)entries, n_entries, confuse, ended_i, ended_f, limits,
+                               gapw, ws);
+        } else {                                                       // only code 0 exists: the positional scan
+            const unsigned limits = ((unsigned)max_mismatch | ((unsigned)max_cost << W_COST_SHIFT)) | W_GUARD;
+            hipLaunchKernelGGL(watch_scan_kernel, grid, dim3(W_T), 0, st, (const uint2*)entries, n_entries, confuse, ended_i, ended_f, limits, ws);
+        }
+        LP_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(watch_tail_indel_kernel, dim3((unsigned)ceil_div(L, 256)), dim3(256), 0, st, ended_count, n_streams, max_ended, scan ? 1 : 0,
+                       indel, ws, match_i, match_align);
     LP_HIP_CHECK(hipGetLastError());
     return LP_OK;
 }

@@ -17,6 +17,8 @@
 // lp_watch_match on (q_i, q_f, q_count) with max_ended = max_tracks; its match_i lies in the workspace.
 // live_scatter_kernel, steps 6 and 7: thread t memoises the answer of a fresh slot (key repacked from its query line) and writes the
 //   slot's row of live_i from the memo.
+// lp_watch_live_indel is the same three steps with lp_watch_match_indel in the middle: its match_align lies in the workspace too, and
+//   the scatter also writes the slot's word of live_align (step 8: the code of a fresh lookup, the standing one kept, else 0).
 #include "lp_internal.h"
 #include "lp_streams.h"
 #include "lp_track_read.inc"
@@ -40,6 +42,8 @@ struct LiveWs {                                 // carve-up of the caller's work
     int32_t* match_i;                           // [L, 4] of lp_watch_match
     void* watch;                                // the workspace of lp_watch_match
     size_t watch_bytes, bytes;
+    int32_t* match_align;                       // [L] of lp_watch_match_indel: behind `bytes`, lp_watch_live_indel only
+    size_t indel_bytes;
 };
 LiveWs live_carve(void* base, size_t S, size_t T) {
     const size_t L = S * T, pos_bytes = (4 * L + 15) & ~(size_t)15;
@@ -49,7 +53,9 @@ LiveWs live_carve(void* base, size_t S, size_t T) {
     w.match_i = (int32_t*)(p + pos_bytes);
     w.watch = p + pos_bytes + 16 * L;
     w.watch_bytes = lp_watch_workspace_bytes((int)S, (int)T);
-    w.bytes = pos_bytes + 16 * L + w.watch_bytes;
+    w.bytes = pos_bytes + 16 * L + w.watch_bytes;                      // (every part is a multiple of 16 bytes)
+    w.match_align = (int32_t*)(p + w.bytes);
+    w.indel_bytes = w.bytes + pos_bytes;
     return w;
 }
 
@@ -142,10 +148,12 @@ __global__ __launch_bounds__(WL_T) void live_gather_kernel(const int* __restrict
 __global__ __launch_bounds__(WL_SLOTS) void live_scatter_kernel(const int* __restrict__ state, int T, long long sstride,
                                                                const int32_t* __restrict__ q_i, const int32_t* __restrict__ pos,
                                                                const int32_t* __restrict__ match_i, int32_t* __restrict__ memo,
-                                                               int32_t* __restrict__ live_i) {
+                                                               int32_t* __restrict__ live_i, const int32_t* __restrict__ match_align,
+                                                               int32_t* __restrict__ live_align) {
     const int s = blockIdx.x, t = threadIdx.x;
     if (t >= T) return;
     const long long line = (long long)s * T + t;
+    int align = 0;                                                     // step 8 (live_align != nullptr: lp_watch_live_indel)
     const int4 h = *(const int4*)(state + (long long)s * sstride + WL_HDR_WORDS + (long long)t * WL_SLOT_WORDS);   // id, first, last, hits
     int4* mline = (int4*)(memo + line * WL_MEMO_WORDS);
     int4 out0 = make_int4(-1, -1, 0, 0), out1 = make_int4(0, 0, 0, 0);
@@ -163,14 +171,17 @@ __global__ __launch_bounds__(WL_SLOTS) void live_scatter_kernel(const int* __res
         mline[1] = make_int4(m.y, m.z, m.w, h.z);
         out0 = make_int4(h.x, m.x, m.y, m.z);
         out1 = make_int4(m.w, 1, h.w, h.z);
+        if (live_align != nullptr) align = match_align[(long long)s * T + j];
     } else if (h.w > 0) {
         const int4 m0 = mline[0];
         if (m0.x == h.x + 1) {
             const int4 m1 = mline[1];
             out0 = make_int4(h.x, m0.w, m1.x, m1.y);
             out1 = make_int4(m1.z, 0, h.w, m1.w);
+            if (live_align != nullptr) align = live_align[line];
         }
     }
+    if (live_align != nullptr) live_align[line] = align;
     int4* row = (int4*)(live_i + line * WL_LIVE_COLS);
     row[0] = out0;
     row[1] = out1;
@@ -192,11 +203,16 @@ extern "C" size_t lp_watch_live_workspace_bytes(int n_streams, int max_tracks) {
     return live_carve(nullptr, (size_t)n_streams, (size_t)max_tracks).bytes;
 }
 
-extern "C" int lp_watch_live(const void* track_state, int n_streams, int max_tracks, const int* ncls, int min_hits, int32_t* memo,
-                             const unsigned char* entries, int n_entries, const unsigned char* confuse, int max_mismatch, int max_cost,
-                             int32_t* q_i, float* q_f, int32_t* q_slot, int32_t* q_count, int32_t* live_i, void* workspace,
-                             size_t workspace_bytes, void* stream) {
-    const std::string fn = "lp_watch_live: ";
+extern "C" size_t lp_watch_live_indel_workspace_bytes(int n_streams, int max_tracks) {
+    if (!live_dims_ok(n_streams, max_tracks)) return 0;
+    return live_carve(nullptr, (size_t)n_streams, (size_t)max_tracks).indel_bytes;
+}
+
+// Both entry points.  with_indel: lp_watch_live_indel (indel, gap_cost and live_align are its own; the workspace is the larger one).
+static int watch_live_run(const std::string& fn, bool with_indel, const void* track_state, int n_streams, int max_tracks, const int* ncls,
+                          int min_hits, int32_t* memo, const unsigned char* entries, int n_entries, const unsigned char* confuse,
+                          int max_mismatch, int max_cost, int indel, int gap_cost, int32_t* q_i, float* q_f, int32_t* q_slot, int32_t* q_count,
+                          int32_t* live_i, int32_t* live_align, void* workspace, size_t workspace_bytes, void* stream) {
     if (!live_dims_ok(n_streams, max_tracks))
         return fail(LP_ERR_ARG, fn + "need n_streams >= 1, max_tracks in 1.." + std::to_string(LP_TRACK_MAX_TRACKS) +
                                     " and n_streams * max_tracks * 12 < 2^31");
@@ -212,15 +228,19 @@ extern "C" int lp_watch_live(const void* track_state, int n_streams, int max_tra
         return fail(LP_ERR_ARG, fn + "n_entries " + std::to_string(n_entries) + " (need 0.." + std::to_string(LP_WATCH_MAX_ENTRIES) + ")");
     if (max_mismatch < 0 || max_mismatch > 8 || max_cost < 0 || max_cost > LP_WATCH_MAX_COST)
         return fail(LP_ERR_ARG, fn + "need max_mismatch in 0..8 and max_cost in 0.." + std::to_string(LP_WATCH_MAX_COST));
-    if (!track_state || !memo || !q_i || !q_f || !q_slot || !q_count || !live_i || !workspace || (n_entries > 0 && !entries))
+    if (with_indel && (indel < 0 || indel > 1 || gap_cost < 0 || gap_cost > LP_WATCH_MAX_GAP_COST))
+        return fail(LP_ERR_ARG, fn + "need indel in 0..1 and gap_cost in 0.." + std::to_string(LP_WATCH_MAX_GAP_COST));
+    if (!track_state || !memo || !q_i || !q_f || !q_slot || !q_count || !live_i || !workspace || (n_entries > 0 && !entries) ||
+        (with_indel && !live_align))
         return fail(LP_ERR_ARG, fn + "null pointer");
     if (((uintptr_t)track_state & 15) != 0 || ((uintptr_t)memo & 15) != 0 || ((uintptr_t)live_i & 15) != 0 || ((uintptr_t)workspace & 15) != 0)
         return fail(LP_ERR_ARG, fn + "the tracker state, the memo, live_i and the workspace must be 16-byte aligned");
     if (n_entries > 0 && (((uintptr_t)entries & 7) != 0 || ((uintptr_t)confuse & 3) != 0))
         return fail(LP_ERR_ARG, fn + "entries must be 8-byte and confuse 4-byte aligned");
     const LiveWs ws = live_carve(workspace, (size_t)n_streams, (size_t)max_tracks);
-    if (workspace_bytes < ws.bytes)
-        return fail(LP_ERR_ARG, fn + "workspace of " + std::to_string(workspace_bytes) + " bytes, need " + std::to_string(ws.bytes));
+    const size_t ws_bytes = with_indel ? ws.indel_bytes : ws.bytes;
+    if (workspace_bytes < ws_bytes)
+        return fail(LP_ERR_ARG, fn + "workspace of " + std::to_string(workspace_bytes) + " bytes, need " + std::to_string(ws_bytes));
     const long long sstride = (long long)WL_HDR_WORDS + (long long)max_tracks * WL_SLOT_WORDS;
     {   // no buffer that is written may overlap the state, the list or another one
         const size_t L = (size_t)n_streams * max_tracks;
@@ -233,9 +253,11 @@ extern "C" int lp_watch_live(const void* track_state, int n_streams, int max_tra
                               {q_slot, L * 4, true},
                               {q_count, (size_t)n_streams * 4, true},
                               {live_i, L * WL_LIVE_COLS * 4, true},
-                              {workspace, ws.bytes, true}};
+                              {live_align, with_indel ? L * 4 : 0, true},
+                              {workspace, ws_bytes, true}};
         if (regions_clash(reg, (int)(sizeof(reg) / sizeof(reg[0]))))
-            return fail(LP_ERR_ARG, fn + "the memo, the queries, live_i and the workspace may overlap neither an input nor each other");
+            return fail(LP_ERR_ARG, fn + (with_indel ? "the memo, the queries, live_i, live_align and the workspace may overlap neither an input nor each other"
+                                                     : "the memo, the queries, live_i and the workspace may overlap neither an input nor each other"));
     }
 
     hipStream_t st = (hipStream_t)stream;
@@ -243,11 +265,29 @@ extern "C" int lp_watch_live(const void* track_state, int n_streams, int max_tra
     hipLaunchKernelGGL(live_gather_kernel, dim3((unsigned)n_streams), dim3((unsigned)threads), 0, st, (const int*)track_state, max_tracks, sstride, nc,
                        min_hits, memo, q_i, q_f, q_slot, q_count, ws.pos);
     LP_HIP_CHECK(hipGetLastError());
-    if (int rc = lp_watch_match(entries, n_entries, confuse, q_i, q_f, q_count, n_streams, max_tracks, max_mismatch, max_cost, ws.match_i, ws.watch,
-                                ws.watch_bytes, stream))
+    if (int rc = with_indel ? lp_watch_match_indel(entries, n_entries, confuse, q_i, q_f, q_count, n_streams, max_tracks, max_mismatch, max_cost,
+                                                   indel, gap_cost, ws.match_i, ws.match_align, ws.watch, ws.watch_bytes, stream)
+                            : lp_watch_match(entries, n_entries, confuse, q_i, q_f, q_count, n_streams, max_tracks, max_mismatch, max_cost,
+                                             ws.match_i, ws.watch, ws.watch_bytes, stream))
         return rc;
     hipLaunchKernelGGL(live_scatter_kernel, dim3((unsigned)n_streams), dim3(WL_SLOTS), 0, st, (const int*)track_state, max_tracks, sstride, q_i, ws.pos,
-                       ws.match_i, memo, live_i);
+                       ws.match_i, memo, live_i, with_indel ? ws.match_align : nullptr, with_indel ? live_align : nullptr);
     LP_HIP_CHECK(hipGetLastError());
     return LP_OK;
+}
+
+extern "C" int lp_watch_live(const void* track_state, int n_streams, int max_tracks, const int* ncls, int min_hits, int32_t* memo,
+                             const unsigned char* entries, int n_entries, const unsigned char* confuse, int max_mismatch, int max_cost,
+                             int32_t* q_i, float* q_f, int32_t* q_slot, int32_t* q_count, int32_t* live_i, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    return watch_live_run("lp_watch_live: ", false, track_state, n_streams, max_tracks, ncls, min_hits, memo, entries, n_entries, confuse,
+                          max_mismatch, max_cost, 0, 0, q_i, q_f, q_slot, q_count, live_i, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lp_watch_live_indel(const void* track_state, int n_streams, int max_tracks, const int* ncls, int min_hits, int32_t* memo,
+                                   const unsigned char* entries, int n_entries, const unsigned char* confuse, int max_mismatch, int max_cost,
+                                   int indel, int gap_cost, int32_t* q_i, float* q_f, int32_t* q_slot, int32_t* q_count, int32_t* live_i,
+                                   int32_t* live_align, void* workspace, size_t workspace_bytes, void* stream) {
+    return watch_live_run("lp_watch_live_indel: ", true, track_state, n_streams, max_tracks, ncls, min_hits, memo, entries, n_entries, confuse,
+                          max_mismatch, max_cost, indel, gap_cost, q_i, q_f, q_slot, q_count, live_i, live_align, workspace, workspace_bytes, stream);
 }

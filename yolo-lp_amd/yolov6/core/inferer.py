@@ -64,7 +64,8 @@ class Inferer:
                  tile_gate_min_cells=1, tile_gate_refresh=50, tile_gate_illum='none', tile_gate_max_gain=1.5, stack_shots=False,
                  stack_search=2, stack_max_frames=64, stack_min_width=0.0, sightings=None, sight_window=None, sight_min_hits=1,
                  sight_mismatch=1, sight_cost=None, save_jpeg=None, overlay=False, overlay_font=None, overlay_size=24, overlay_thickness=2,
-                 overlay_alpha=(256, 160, 256), zones=None, zones_min_hits=1, speed=None, speed_min_hits=1, speed_confirm=2, overlay_scene=False):
+                 overlay_alpha=(256, 160, 256), zones=None, zones_min_hits=1, speed=None, speed_min_hits=1, speed_confirm=2, overlay_scene=False,
+                 watch_indel=False, watch_gap_cost=1.0):
         """``batch_size > 1`` on a GPU runs consecutive frames of one letterboxed shape as one batch (``_gpu_groups``);
         ``auto=False`` letterboxes every frame to exactly ``img_size`` (the reference pads to the next stride multiple).
         ``tile`` = (h, w): tiled detection (``_gpu_groups``; ``tiled_rows_cpu`` on the CPU) with ``tile_overlap`` (pixels, or a fraction < 1 of the tile),
@@ -102,6 +103,9 @@ class Inferer:
         ``watch_live`` (with ``watchlist``): a track is also looked up while it is still live, as soon as it has
         ``watch_live_min_hits`` detections and again whenever its voted read changes (``yolov6.utils.watch_live`` states the rule;
         the limits are those of ``watchlist``); ``infer`` writes ``alerts.txt``.
+        ``watch_indel`` (with ``watchlist``): both lookups also tolerate one lost or gained character in heads 2..7, charged
+        ``watch_gap_cost`` fully confident mismatches and counted as one mismatch; ``hits.txt`` and ``alerts.txt`` then end in one
+        more column, the alignment: ``-``, ``del@k``, ``ins@k`` or ``end`` (``watch.align_text``).
         ``sightings`` = C (with ``track``; ``yolov6.utils.sight`` states the rule): a log of the last C reads of all streams; the
         read of every ended track of at least ``sight_min_hits`` detections is matched against the reads logged at most
         ``sight_window`` frames of the source earlier (None: no limit), tolerating ``sight_mismatch`` misread positions of a total
@@ -166,6 +170,11 @@ class Inferer:
             if not track:
                 raise ValueError('watchlist needs track=True')
             check_params(watch_mismatch, cost_units(watch_cost))
+        if watch_indel:
+            from yolov6.utils.watch import gap_units
+            if watchlist is None:
+                raise ValueError('watch_indel needs watchlist=FILE')
+            gap_units(watch_gap_cost)
         if sightings is not None:
             from yolov6.utils.sight import check_call, check_log
             from yolov6.utils.watch import check_params, cost_units
@@ -579,6 +588,8 @@ class Inferer:
         self._track_tids, self._track_lines, self._track_ended, self._track_shots = deque(), [], [], []
         self._track_stacks = []         # with stack_shots: (stack_i line, crop or None) of every ended record
         self._track_hits = []           # with watchlist: the match_i line of every ended record
+        self._track_hit_align = []      # with watch_indel: its alignment code
+        self._track_alert_align = []    # with watch_indel and watch_live: the alignment code of every alert
         if self.watchlist is not None:
             from yolov6.utils import watch
             with open(self.watchlist) as f:
@@ -587,9 +598,10 @@ class Inferer:
             if self.watch_confusable:
                 confuse = watch.confuse_table(watch.confusable_pairs(self.watch_confusable), 2, self.watch_confusable_weight, self.ads_names)
             wl = runtime.Watchlist(entries, confuse, self.device) if self.device.type != 'cpu' else watch.WatchlistNp(entries, confuse)
-            self._tracker.enable_watch(wl, self.watch_mismatch, self.watch_cost)
+            indel = dict(indel=1, gap_cost=self.watch_gap_cost) if self.watch_indel else {}
+            self._tracker.enable_watch(wl, self.watch_mismatch, self.watch_cost, **indel)
             if self.watch_live:
-                self._tracker.enable_live_watch(wl, self.watch_live_min_hits, self.watch_mismatch, self.watch_cost)
+                self._tracker.enable_live_watch(wl, self.watch_live_min_hits, self.watch_mismatch, self.watch_cost, **indel)
         self._track_sights = []         # with sightings: (sight_i line, now) of every ended record
         self._track_seen = 0            # frames of the source handed to the tracker so far
         if self.sightings is not None:
@@ -656,6 +668,9 @@ class Inferer:
             stack_i = stack_i.cpu().numpy()
         if torch.is_tensor(match_i):
             match_i = match_i.cpu().numpy()
+        match_align = self._tracker.last_watch_align
+        if torch.is_tensor(match_align):
+            match_align = match_align.cpu().numpy()
         sight_i = self._tracker.last_sight if self.sightings is not None else None     # of the same update too
         if torch.is_tensor(sight_i):
             sight_i = sight_i.cpu().numpy()
@@ -666,6 +681,8 @@ class Inferer:
                 self._track_ended.append((ended_i[s, k].copy(), ended_f[s, k].copy()))
                 if match_i is not None:
                     self._track_hits.append(match_i[s, k].copy())
+                if match_align is not None:
+                    self._track_hit_align.append(int(match_align[s, k]))
                 if sight_i is not None:
                     self._track_sights.append((sight_i[s, k].copy(), self._track_now))
                 if shot_i is not None:
@@ -681,9 +698,14 @@ class Inferer:
             live_i, (q_i, _, q_slot, _) = self._tracker.last_live, self._tracker.last_live_reads
             if torch.is_tensor(live_i):
                 live_i, q_i, q_slot = live_i.cpu().numpy(), q_i.cpu().numpy(), q_slot.cpu().numpy()
+            live_align = self._tracker.last_live_align
+            if torch.is_tensor(live_align):
+                live_align = live_align.cpu().numpy()
             for s, t in alerts_of(live_i):
                 row, j = live_i[s, t], int(np.nonzero(q_slot[s] == t)[0][0])
                 self._track_alerts.append((row[7], row[0], q_i[s, j, 4:12].copy()) + tuple(row[1:5]) + (row[6],))
+                if live_align is not None:
+                    self._track_alert_align.append(int(live_align[s, t]))
         if self._tracker.last_zone is not None:     # the line and zone events of the same update
             zone_ev, zone_count = self._tracker.last_zone[:2]
             if torch.is_tensor(zone_ev):
@@ -785,14 +807,15 @@ class Inferer:
                 text = plate_text(ri[4:12], self.pro_names, self.alp_names, self.ads_names)
                 f.write('%d %d %d %d %s %s\n' % (ri[0], ri[1], ri[2], ri[3], text, ' '.join('%g' % v for v in rf[:8])))
         if self.watchlist is not None:
-            from yolov6.utils.watch import entry_text
+            from yolov6.utils.watch import align_text, entry_text
             names = (self.pro_names, self.alp_names, self.ads_names)
             entries = self._tracker._watch[0].entries_np
             with open(osp.join(save_dir, 'hits.txt'), 'w') as f:
-                for (ri, _), m in zip(self._track_ended, self._track_hits):
+                for k, ((ri, _), m) in enumerate(zip(self._track_ended, self._track_hits)):
                     if m[0] >= 0:
-                        f.write('%d %d %d %s %d %s %d %d %d\n' % (ri[0], ri[1], ri[2], plate_text(ri[4:12], *names), m[0],
-                                                                  entry_text(entries[m[0]], *names), m[1], m[2], m[3]))
+                        f.write('%d %d %d %s %d %s %d %d %d%s\n' % (ri[0], ri[1], ri[2], plate_text(ri[4:12], *names), m[0],
+                                                                    entry_text(entries[m[0]], *names), m[1], m[2], m[3],
+                                                                    ' ' + align_text(self._track_hit_align[k]) if self.watch_indel else ''))
         if self.sightings is not None:
             names = (self.pro_names, self.alp_names, self.ads_names)
             with open(osp.join(save_dir, 'resightings.txt'), 'w') as f:
@@ -801,13 +824,14 @@ class Inferer:
                         f.write('%d %d %d %s %d %d %d %d %d %d %d\n' % (ri[0], ri[1], ri[2], plate_text(ri[4:12], *names), m[4], m[5], m[6], now,
                                                                         m[1], m[2], m[3]))
         if self.watch_live:
-            from yolov6.utils.watch import entry_text
+            from yolov6.utils.watch import align_text, entry_text
             names = (self.pro_names, self.alp_names, self.ads_names)
             entries = self._tracker._watch[0].entries_np
             with open(osp.join(save_dir, 'alerts.txt'), 'w') as f:
-                for frame, tid, best, e, mism, cost, n, hits in self._track_alerts:
-                    f.write('%d %d %s %d %s %d %d %d %d\n' % (frame, tid, plate_text(best, *names), e, entry_text(entries[e], *names), mism,
-                                                              cost, n, hits))
+                for k, (frame, tid, best, e, mism, cost, n, hits) in enumerate(self._track_alerts):
+                    f.write('%d %d %s %d %s %d %d %d %d%s\n' % (frame, tid, plate_text(best, *names), e, entry_text(entries[e], *names), mism,
+                                                                cost, n, hits,
+                                                                ' ' + align_text(self._track_alert_align[k]) if self.watch_indel else ''))
         if self.zones is not None:
             from yolov6.utils.zones import EVENT_NAMES, KIND_CROSS
             names = (self.pro_names, self.alp_names, self.ads_names)

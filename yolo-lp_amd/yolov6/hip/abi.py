@@ -40,6 +40,7 @@ LP_JPEG_MAX_RESTART, LP_JPEG_PER_LAUNCH = 32, 32   # lp_jpeg_encode_batch: MCUs 
 LP_LOOKBACK_MAX_DEPTH = 32   # lp_lookback_update: frames of delay
 LP_WATCH_MAX_ENTRIES, LP_WATCH_MAX_COST = 1 << 24, 32768   # lp_watch_match: entries of a watchlist, the largest cost of an entry
 LP_WATCH_BLOCK_ENTRIES, LP_WATCH_QUERY_BLOCK = 2048, 16   # ... entries per workgroup of its scan, reads per LDS table
+LP_WATCH_MAX_GAP_COST, LP_WATCH_INDEL_QUERY_BLOCK = 4096, 16   # lp_watch_match_indel: the largest gap_cost, reads per LDS table of its scan
 LP_SIGHT_MAX_CAPACITY = 1 << 24   # lp_sight_update: slots of a log of sightings
 LP_ZONE_MAX_LINES, LP_ZONE_MAX_ZONES, LP_ZONE_MAX_VERTS, LP_ZONE_MAP_WORDS = 16, 8, 16, 368   # lp_zone_update: the packed geometry of a stream
 LP_SPEED_MAP_WORDS, LP_SPEED_MEMO_WORDS, LP_SPEED_RING = 32, 48, 8   # lp_speed_update: the packed calibration of a stream, the memo of a slot
@@ -261,10 +262,15 @@ SYMBOLS = {
     'lp_watch_workspace_bytes': (c_size_t, [c_int, c_int]),
     'lp_watch_match': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
+    'lp_watch_match_indel': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
     'lp_watch_live_state_bytes': (c_size_t, [c_int, c_int]),
     'lp_watch_live_workspace_bytes': (c_size_t, [c_int, c_int]),
     'lp_watch_live': (c_int, [c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'lp_watch_live_indel_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'lp_watch_live_indel': (c_int, [c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'lp_sight_state_bytes': (c_size_t, [c_int]),
     'lp_sight_workspace_bytes': (c_size_t, [c_int, c_int]),
     'lp_sight_update': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int,

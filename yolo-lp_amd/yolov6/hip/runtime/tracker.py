@@ -102,6 +102,10 @@ class PlateTracker:
         self._watch = None
         #: match_i [S,max_ended,4] int32 of the last ``update`` after ``enable_watch``, line-parallel to its ended_i, else None
         self.last_watch = None
+        #: match_align [S,max_ended] int32 of that lookup after ``enable_watch(..., indel=1)``, else None
+        self.last_watch_align = None
+        #: live_align [S,max_tracks] int32 of the last ``update`` after ``enable_live_watch(..., indel=1)``, else None
+        self.last_live_align = None
         self._live = None
         #: live_i [S,max_tracks,8] int32 of the last ``update`` after ``enable_live_watch``, else None
         self.last_live = None
@@ -176,8 +180,9 @@ class PlateTracker:
                                                       _dptr(ended_count), max_ended, hp, _dptr(hold[0]), _dptr(hold[1]), _dptr(hold[2]),
                                                       _stream_ptr(self.device)), 'lp_track_update_hold')
         if self._watch is not None:
-            wl, mm, mc = self._watch
-            self.last_watch = wl._match(ended_i, ended_f, ended_count, mm, mc)
+            wl, mm, mc, indel, gap = self._watch
+            self.last_watch = wl._match(ended_i, ended_f, ended_count, mm, mc, indel, gap)
+            self.last_watch_align = wl.last_align
         if self._live is not None:
             self._live_watch()
         if self._sight is not None:
@@ -318,7 +323,7 @@ class PlateTracker:
         self._sight = (log, (window, min_hits) + watch.check_params(max_mismatch, watch.cost_units(max_cost)))
 
     # ---- the live tracks looked up in a watchlist (lp_watch_live; yolov6/utils/watch_live.py states the rule) -----------------
-    def enable_live_watch(self, watchlist, min_hits=3, max_mismatch=1, max_cost=None):
+    def enable_live_watch(self, watchlist, min_hits=3, max_mismatch=1, max_cost=None, indel=0, gap_cost=None):
         """From now on every ``update`` / ``update_with_shots`` / ``flush_all*`` also enqueues, at its end on the same stream
         (behind the lookup of ``enable_watch`` if that is on), the lookup of the LIVE tracks of at least ``min_hits`` hits in
         ``watchlist`` (a ``Watchlist`` on this device): once per track when it gets there, and again only when its voted read
@@ -326,10 +331,13 @@ class PlateTracker:
         row per slot: (id, entry, mismatches, cost, n_hits, fresh, hits, last_at_lookup), or (-1, -1, 0, 0, 0, 0, 0, 0) for a
         slot without a looked-up track; a row with fresh == 1 and entry >= 0 is an alert.  ``last_live_reads`` = (q_i, q_f,
         q_slot, q_count): the reads looked up in this call.  Persistent buffers, no host read, no allocation per call.  Returns,
-        state and every other buffer are what they are without it.  Calling it again zeroes the memo;
+        state and every other buffer are what they are without it.  ``indel=1`` (lp_watch_live_indel): one lost or gained
+        character in heads 2..7 is tolerated at ``gap_cost`` fully confident mismatches (None: 1), and ``last_live_align`` =
+        live_align [S,max_tracks] int32, the alignment code of every row's lookup (None without it); the tracker owns that tensor
+        beside the memo.  Calling it again zeroes the memo;
         ``enable_live_watch(None)`` turns it off.  ``PlateTrackerNp.enable_live_watch`` is the same on the CPU, on every int32."""
         from yolov6.utils import watch, watch_live
-        self.last_live = self.last_live_reads = None
+        self.last_live = self.last_live_reads = self.last_live_align = None
         if watchlist is None:
             self._live = None
             return
@@ -337,6 +345,7 @@ class PlateTracker:
             raise ValueError('enable_live_watch needs a Watchlist on the tracker\'s device %s' % self.device)
         min_hits = watch_live.check_min_hits(min_hits)
         mm, mc = watch.check_params(max_mismatch, watch.cost_units(max_cost))
+        indel, gap = watch.check_indel(indel, watch.gap_units(gap_cost))
         S, T, dev, lib = self.n_streams, self.max_tracks, self.device, abi.load()
         i32 = dict(dtype=torch.int32, device=dev)
         self._live = dict(
@@ -344,7 +353,9 @@ class PlateTracker:
             memo=torch.zeros(lib.lp_watch_live_state_bytes(S, T) // 4, **i32).view(S, T, 8),
             live_i=torch.empty(S, T, 8, **i32), q_i=torch.empty(S, T, 12, **i32),
             q_f=torch.empty(S, T, 12, dtype=torch.float32, device=dev), q_slot=torch.empty(S, T, **i32), q_count=torch.empty(S, **i32),
-            ws=torch.empty(lib.lp_watch_live_workspace_bytes(S, T) + 256, dtype=torch.uint8, device=dev))
+            ws=torch.empty((lib.lp_watch_live_indel_workspace_bytes if indel else lib.lp_watch_live_workspace_bytes)(S, T) + 256,
+                           dtype=torch.uint8, device=dev),
+            indel=(indel, gap), align=torch.zeros(S, T, **i32) if indel else None)
 
     @property
     def live_memo(self):
@@ -356,6 +367,17 @@ class PlateTracker:
         """Enqueue lp_watch_live on the state as it stands."""
         lw = self._live
         wl, ws = lw['watchlist'], lw['ws']
+        if lw['indel'][0]:
+            with torch.cuda.device(self.device):
+                abi.check(abi.load().lp_watch_live_indel(_dptr(self.state), self.n_streams, self.max_tracks, lw['ncls'], lw['min_hits'],
+                                                         _dptr(lw['memo']), _dptr(wl.entries), wl.n, _dptr(wl.confuse), lw['limits'][0],
+                                                         lw['limits'][1], lw['indel'][0], lw['indel'][1], _dptr(lw['q_i']), _dptr(lw['q_f']),
+                                                         _dptr(lw['q_slot']), _dptr(lw['q_count']), _dptr(lw['live_i']), _dptr(lw['align']),
+                                                         *_aligned_span(ws), _stream_ptr(self.device)), 'lp_watch_live_indel')
+            self.last_live = lw['live_i']
+            self.last_live_reads = (lw['q_i'], lw['q_f'], lw['q_slot'], lw['q_count'])
+            self.last_live_align = lw['align']
+            return
         with torch.cuda.device(self.device):
             abi.check(abi.load().lp_watch_live(_dptr(self.state), self.n_streams, self.max_tracks, lw['ncls'], lw['min_hits'], _dptr(lw['memo']),
                                                _dptr(wl.entries), wl.n, _dptr(wl.confuse), lw['limits'][0], lw['limits'][1], _dptr(lw['q_i']),
@@ -365,20 +387,23 @@ class PlateTracker:
         self.last_live_reads = (lw['q_i'], lw['q_f'], lw['q_slot'], lw['q_count'])
 
     # ---- the ended reads looked up in a watchlist (lp_watch_match; yolov6/utils/watch.py states the rule) ----------------------
-    def enable_watch(self, watchlist, max_mismatch=1, max_cost=None):
+    def enable_watch(self, watchlist, max_mismatch=1, max_cost=None, indel=0, gap_cost=None):
         """From now on every ``update`` / ``update_with_shots`` / ``flush_all*`` also enqueues, behind the tracker on the same
         stream, the lookup of the records it ended in ``watchlist`` (a ``Watchlist`` on this device) and leaves match_i
         [S,max_ended,4] int32 = (entry, mismatches, cost, n_hits), line-parallel to ended_i, in ``last_watch``.  ``max_cost``: a float
-        in fully confident mismatches (``watch.cost_units``; None: no limit).  Returns, state and every other buffer are what
+        in fully confident mismatches (``watch.cost_units``; None: no limit).  ``indel=1`` (lp_watch_match_indel): one lost or
+        gained character in heads 2..7 is tolerated at ``gap_cost`` fully confident mismatches (None: 1), and match_align
+        [S,max_ended] int32 is left in ``last_watch_align`` (None without it).  Returns, state and every other buffer are what
         they are without it.  ``enable_watch(None)`` turns it off."""
         from yolov6.utils import watch
-        self.last_watch = None
+        self.last_watch = self.last_watch_align = None
         if watchlist is None:
             self._watch = None
             return
         if not isinstance(watchlist, Watchlist) or watchlist.device != self.device:
             raise ValueError('enable_watch needs a Watchlist on the tracker\'s device %s' % self.device)
-        self._watch = (watchlist,) + watch.check_params(max_mismatch, watch.cost_units(max_cost))
+        self._watch = (watchlist,) + watch.check_params(max_mismatch, watch.cost_units(max_cost)) + \
+            watch.check_indel(indel, watch.gap_units(gap_cost))
 
     # ---- redaction held over missed frames (lp_track_update_hold; rule 11 of yolov6/utils/track.py) -----------------------------
     def enable_hold(self, min_hits=1, max_misses=None):

@@ -22,6 +22,14 @@ class Watchlist:
         self.entries = torch.from_numpy(self.entries_np).to(self.device)
         self.confuse = None if self.confuse_np is None else torch.from_numpy(self.confuse_np).to(self.device)
         self._out = {}
+        self._align = {}
+        #: match_align [S,max_ended] int32 of the last ``match`` with ``indel=1``, else None
+        self.last_align = None
+
+    def align_buffer(self, S, max_ended):
+        """The persistent match_align [S,max_ended] int32 of a ``match(..., indel=1)`` of that shape."""
+        key = (int(S), int(max_ended))
+        return _persistent(self._align, key, lambda: torch.empty(key[0], key[1], dtype=torch.int32, device=self.device))
 
     def buffers(self, S, max_ended):
         """The persistent (match_i [S,max_ended,4] int32, workspace) of a ``match`` of that shape."""
@@ -30,20 +38,33 @@ class Watchlist:
         return _persistent(self._out, key, lambda: (torch.empty(key[0], key[1], 4, dtype=torch.int32, device=self.device),
                                                     torch.empty(need + 256, dtype=torch.uint8, device=self.device)))
 
-    def match(self, ended_i, ended_f, ended_count, max_mismatch=1, max_cost=None):
+    def match(self, ended_i, ended_f, ended_count, max_mismatch=1, max_cost=None, indel=0, gap_cost=None):
         """match_i [S,max_ended,4] int32 = (entry, mismatches, cost, n_hits) per line of the ended records of a
         ``PlateTracker.update`` (device tensors), enqueued on the current stream with no host read: the accepted entry of the
         smallest (cost, index), -1 for none, and how many were accepted.  ``max_mismatch`` 0..8; ``max_cost``: a float in fully
         confident mismatches (``watch.cost_units`` makes it the integer of the rule; None: no limit).  Persistent buffers per
-        (S, max_ended): a later call of the same shape overwrites what the earlier one returned."""
+        (S, max_ended): a later call of the same shape overwrites what the earlier one returned.  ``indel=1``
+        (lp_watch_match_indel): one lost or gained character in heads 2..7 is tolerated at ``gap_cost`` fully confident mismatches
+        (``watch.gap_units``; None: 1); the alignment codes, match_align [S,max_ended] int32, are left in ``last_align`` (None
+        without it; ``watch.align_text`` names a code)."""
         from yolov6.utils import watch
-        return self._match(ended_i, ended_f, ended_count, *watch.check_params(max_mismatch, watch.cost_units(max_cost)))
+        return self._match(ended_i, ended_f, ended_count, *watch.check_params(max_mismatch, watch.cost_units(max_cost)),
+                           *watch.check_indel(indel, watch.gap_units(gap_cost)))
 
-    def _match(self, ended_i, ended_f, ended_count, mm, mc):
-        """``match`` with the two limits as the checked integers of the rule."""
+    def _match(self, ended_i, ended_f, ended_count, mm, mc, indel=0, gap=0):
+        """``match`` with the limits, ``indel`` and ``gap_cost`` as the checked integers of the rule."""
         _check_ended(ended_i, ended_f, ended_count, self.device, 'the ended records must be contiguous tensors on the watchlist\'s device')
         S, max_ended = ended_i.shape[:2]
         match_i, ws = self.buffers(S, max_ended)
+        self.last_align = None
+        if indel:
+            self.last_align = self.align_buffer(S, max_ended)
+            with torch.cuda.device(self.device):
+                abi.check(abi.load().lp_watch_match_indel(_dptr(self.entries), self.n, _dptr(self.confuse), _dptr(ended_i), _dptr(ended_f),
+                                                          _dptr(ended_count), S, max_ended, mm, mc, indel, gap, _dptr(match_i),
+                                                          _dptr(self.last_align), *_aligned_span(ws), _stream_ptr(self.device)),
+                          'lp_watch_match_indel')
+            return match_i
         with torch.cuda.device(self.device):
             abi.check(abi.load().lp_watch_match(_dptr(self.entries), self.n, _dptr(self.confuse), _dptr(ended_i), _dptr(ended_f),
                                                 _dptr(ended_count), S, max_ended, mm, mc, _dptr(match_i), *_aligned_span(ws),

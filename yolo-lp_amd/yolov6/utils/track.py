@@ -224,6 +224,11 @@ class PlateTrackerNp:
         self._watch = None
         #: match_i [S, max_ended, 4] int32 of the last ``update`` after ``enable_watch``, line-parallel to its ended_i, else None
         self.last_watch = None
+        self._watch_indel = (0, 0)
+        #: match_align [S, max_ended] int32 of that lookup after ``enable_watch(..., indel=1)``, else None
+        self.last_watch_align = None
+        #: live_align [S, max_tracks] int32 of the last ``update`` after ``enable_live_watch(..., indel=1)``, else None
+        self.last_live_align = None
         self._stack = None
         #: (stack_crops, stack_i) of the last ``update_stack`` after ``enable_stack``, line-parallel to the ended records, else None
         self.last_stack = None
@@ -306,24 +311,28 @@ class PlateTrackerNp:
             raise ValueError('hold needs min_hits >= 1 and max_misses >= 0')
         self._hold = dict(min_hits=min_hits, max_misses=max_misses, out={})
 
-    def enable_watch(self, watchlist, max_mismatch=1, max_cost=None):
+    def enable_watch(self, watchlist, max_mismatch=1, max_cost=None, indel=0, gap_cost=None):
         """From now on every ``update`` / ``flush_all`` also looks the records it ended up in ``watchlist`` -- anything with
         ``entries_np`` and ``confuse_np`` (``watch.WatchlistNp``, ``runtime.Watchlist``) -- and leaves match_i [S, max_ended, 4] int32
         in ``last_watch`` (``yolov6.utils.watch`` states the rule; ``max_cost``: a float in fully confident mismatches, None: no
-        limit).  Every other output stays what it is.  ``enable_watch(None)`` turns it off."""
+        limit).  ``indel=1``: one lost or gained character is tolerated at ``gap_cost`` fully confident mismatches (None: 1) and
+        match_align [S, max_ended] int32 is left in ``last_watch_align`` (None without it).  Every other output stays what it is.
+        ``enable_watch(None)`` turns it off."""
         from yolov6.utils import watch
-        self.last_watch = None
+        self.last_watch = self.last_watch_align = None
+        self._watch_indel = watch.check_indel(indel, watch.gap_units(gap_cost))
         self._watch = None if watchlist is None else (watchlist,) + watch.check_params(max_mismatch, watch.cost_units(max_cost))
 
-    def enable_live_watch(self, watchlist, min_hits=3, max_mismatch=1, max_cost=None):
+    def enable_live_watch(self, watchlist, min_hits=3, max_mismatch=1, max_cost=None, indel=0, gap_cost=None):
         """From now on every ``update`` / ``flush_all`` also looks the reads of the LIVE tracks of at least ``min_hits`` hits up in
         ``watchlist``, once per track and voted read (``yolov6.utils.watch_live`` states the rule), and leaves live_i
         [S, max_tracks, 8] int32 in ``last_live`` and the fresh reads (q_i, q_f, q_slot, q_count) in ``last_live_reads``.  Every
-        other output and the state stay what they are.  Calling it again starts from an empty memo; ``enable_live_watch(None)``
-        turns it off."""
+        other output and the state stay what they are.  ``indel`` / ``gap_cost`` as ``enable_watch``: live_align [S, max_tracks] int32
+        is left in ``last_live_align`` (None without ``indel``).  Calling it again starts from an empty memo;
+        ``enable_live_watch(None)`` turns it off."""
         from yolov6.utils.watch_live import LiveWatchNp
-        self.last_live = self.last_live_reads = None
-        self._live = None if watchlist is None else LiveWatchNp(self, watchlist, min_hits, max_mismatch, max_cost)
+        self.last_live = self.last_live_reads = self.last_live_align = None
+        self._live = None if watchlist is None else LiveWatchNp(self, watchlist, min_hits, max_mismatch, max_cost, indel, gap_cost)
 
     def enable_sightings(self, log, window=0, min_hits=1, max_mismatch=1, max_cost=None):
         """From now on every ``update`` / ``flush_all`` also matches the records it ended against the earlier reads in ``log`` (a
@@ -575,11 +584,16 @@ class PlateTrackerNp:
         if self._watch is not None:
             from yolov6.utils.watch import watch_match_np
             wl, mm, mc = self._watch
-            self.last_watch = watch_match_np(wl.entries_np, wl.confuse_np, ended_i, ended_f, ended_count, mm, mc)
+            if self._watch_indel[0]:
+                self.last_watch, self.last_watch_align = watch_match_np(wl.entries_np, wl.confuse_np, ended_i, ended_f, ended_count, mm, mc,
+                                                                        1, self._watch_indel[1], align=True)
+            else:
+                self.last_watch = watch_match_np(wl.entries_np, wl.confuse_np, ended_i, ended_f, ended_count, mm, mc)
         if self._live is not None:
             lw = self._live
             self.last_live = lw.step()
             self.last_live_reads = (lw.q_i, lw.q_f, lw.q_slot, lw.q_count)
+            self.last_live_align = lw.live_align
         if self._sight is not None:
             from yolov6.utils.sight import sight_update_np
             log, params = self._sight

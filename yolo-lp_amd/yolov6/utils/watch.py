@@ -29,9 +29,32 @@ Rules:
      index wins); (-1, 0, 0, 0) for a line without an accepted entry, for every line at or past the stream's count, and for
      every line when N = 0.
 
-What it does not do: no insertions or deletions (a read that lost or gained a character matches nothing nearby); no alert while a
-track is still live (ended records only: ``yolov6.utils.watch_live`` does that); one best entry plus a count, not a ranked list; no persistence or update in place of
-the list (a changed list is a new ``Watchlist``).
+One lost or gained character (``indel=1``; ``lp_watch_match_indel``).  When two narrow glyphs merge, a rivet is read as a
+character, or a 7-character plate is read as 8, every later head moves by one and the positional measure charges four or five
+mismatches for one error.  Heads 2..7 share one alphabet and one confusion group, so read head p may be compared with entry head
+p + 1 or p - 1 by the same rule.  Rules 1-3 above give, per read, position p and entry byte w, a pair (cost, mismatch); call it
+U[p] for w = entries[e, p], L[p] (p in 2..6) for w = entries[e, p + 1] and R[p] (p in 3..7) for w = entries[e, p - 1].  WILD, ids
+64..254 and a best[p] outside 0..63 behave in L and R as they do in U.  An entry is scored under 12 alignments, each
+U[0] + U[1] plus:
+  code 0, unshifted: sum U[2..7];
+  codes 1..5, the read lost the character at entry head k = 2..6 (code k - 1): sum U[2..k-1] + sum L[k..6]; read head 7 is not
+     compared;
+  codes 6..10, the read gained a character at read head k = 2..6 (code k + 4): sum U[2..k-1] + sum R[k+1..7]; read head k and
+     entry head 7 are not compared;
+  code 11, the error is at the end: sum U[2..6]; head 7 is compared on neither side.
+Codes 1..11 add ``gap_cost`` (cost units, 0..COST_SCALE, default COST_SCALE: one fully confident mismatch) to the cost and 1 to
+the mismatches, so a shifted alignment compares at most seven positions plus the gap and its cost stays <= MAX_COST.  The
+entry's score is the alignment with the smallest (cost, mismatches, code); the entry is accepted iff THAT alignment has
+mismatches <= max_mismatch and cost <= max_cost.  Across entries nothing changes: the smallest (cost, index) wins, n_hits counts
+the accepted entries.  match_i's mismatches count the gap; match_align int32 [S, max_ended] is the winning entry's code, 0 on a
+line without a hit.  With ``indel=0`` only code 0 exists and the result is the positional one on every int32.  With the default
+max_mismatch = 1 a shifted read must be otherwise exact.  ``align_text`` names a code: ``-``, ``del@k``, ``ins@k``, ``end``.
+
+What it does not do: at most ONE insertion or deletion, and only in heads 2..7 (heads 0 and 1 have other alphabets; a read that
+lost or gained two characters matches nothing nearby; without ``indel`` none at all); the sightings log stays positional
+(``yolov6.utils.sight``); no alert while a track is still live (ended records only: ``yolov6.utils.watch_live`` does that); one
+best entry plus a count, not a ranked list; no persistence or update in place of the list (a changed list is a new
+``Watchlist``).
 """
 import numpy as np
 
@@ -43,6 +66,7 @@ MAX_COST = 8 * 256 * 16       # 32768
 FULL = 16                     # the weight of an unlisted confusion, in sixteenths
 COST_SCALE = 256 * FULL       # cost units of one fully confident, unlisted mismatch
 GROUP_OF = (0, 1, 2, 2, 2, 2, 2, 2)
+N_ALIGN = 12                  # alignment codes of ``indel=1``: 0 unshifted, 1..5 del@2..6, 6..10 ins@2..6, 11 end
 f32 = np.float32
 
 
@@ -83,10 +107,18 @@ class WatchlistNp:
         self.entries_np = check_entries(entries)
         self.confuse_np = None if confuse is None else check_confuse(confuse)
         self.n = len(self.entries_np)
+        self.last_align = None
 
-    def match(self, ended_i, ended_f, ended_count, max_mismatch=1, max_cost=None):
-        """``watch_match_np`` on this list; ``max_cost`` a float in fully confident mismatches (``cost_units``; None: no limit)."""
-        return watch_match_np(self.entries_np, self.confuse_np, ended_i, ended_f, ended_count, max_mismatch, cost_units(max_cost))
+    def match(self, ended_i, ended_f, ended_count, max_mismatch=1, max_cost=None, indel=0, gap_cost=None):
+        """``watch_match_np`` on this list; ``max_cost`` a float in fully confident mismatches (``cost_units``; None: no limit).
+        ``indel=1`` tolerates one lost or gained character at ``gap_cost`` fully confident mismatches (``gap_units``; None: 1) and
+        leaves match_align [S, max_ended] int32 in ``last_align`` (None without it)."""
+        self.last_align = None
+        if not check_indel(indel, gap_units(gap_cost))[0]:
+            return watch_match_np(self.entries_np, self.confuse_np, ended_i, ended_f, ended_count, max_mismatch, cost_units(max_cost))
+        m, self.last_align = watch_match_np(self.entries_np, self.confuse_np, ended_i, ended_f, ended_count, max_mismatch,
+                                            cost_units(max_cost), 1, gap_units(gap_cost), align=True)
+        return m
 
 
 def cost_units(x):
@@ -108,6 +140,36 @@ def check_params(max_mismatch, max_cost):
     if mc != max_cost or not 0 <= mc <= MAX_COST:
         raise ValueError('max_cost must be an integer in 0..%d (cost_units converts a float)' % MAX_COST)
     return mm, mc
+
+
+def gap_units(x):
+    """``gap_cost`` given in fully confident mismatches (a float; None: 1) as the integer of the rule:
+    clamp(floor(x * 4096 + 0.5), 0, 4096)."""
+    if x is None:
+        return COST_SCALE
+    x = float(x)
+    if x != x:
+        raise ValueError('gap_cost is NaN')
+    return int(min(max(np.floor(x * COST_SCALE + 0.5), 0), COST_SCALE))
+
+
+def check_indel(indel, gap_cost):
+    """(indel, gap_cost) as the integers of the rule (ValueError outside 0..1 / 0..4096)."""
+    i, g = int(indel), int(gap_cost)
+    if i != indel or i not in (0, 1):
+        raise ValueError('indel must be 0 or 1')
+    if g != gap_cost or not 0 <= g <= COST_SCALE:
+        raise ValueError('gap_cost must be an integer in 0..%d (gap_units converts a float)' % COST_SCALE)
+    return i, g
+
+
+def align_text(code):
+    """An alignment code as the tools print it: ``-`` (0), ``del@k`` (1..5, k = 2..6: the entry's head k is missing from the read),
+    ``ins@k`` (6..10, k = 2..6: the read's head k is not in the entry), ``end`` (11)."""
+    code = int(code)
+    if not 0 <= code < N_ALIGN:
+        raise ValueError('alignment code %d outside 0..%d' % (code, N_ALIGN - 1))
+    return '-' if code == 0 else 'del@%d' % (code + 1) if code <= 5 else 'ins@%d' % (code - 4) if code <= 10 else 'end'
 
 
 def confuse_table(pairs, group=2, weight=4, names=None):
@@ -221,13 +283,15 @@ def position_weight(share):
         return np.where(pos, np.where(pos, t, f32(0)).astype(np.int32) + 1, 1).astype(np.int32)
 
 
-def watch_match_np(entries, confuse, ended_i, ended_f, ended_count, max_mismatch, max_cost):
-    """match_i int32 [S, max_ended, 4] of the module's rule.  Per read and position one table over the 256 byte values of an
-    entry id gives (cost, mismatch); an entry's totals are eight gathers, so N = 10^5 with a few dozen reads takes well under a
-    second.  Unlike ``check_entries`` this takes ids 64..254, as the kernel must."""
+def watch_match_np(entries, confuse, ended_i, ended_f, ended_count, max_mismatch, max_cost, indel=0, gap_cost=COST_SCALE, align=False):
+    """match_i int32 [S, max_ended, 4] of the module's rule, or (match_i, match_align int32 [S, max_ended]) with ``align=True``.
+    Per read and position one table over the 256 byte values of an entry id gives (cost, mismatch); an entry's totals are eight
+    gathers (eighteen with ``indel=1``), so N = 10^5 with a few dozen reads takes well under a second.  Unlike
+    ``check_entries`` this takes ids 64..254, as the kernel must."""
     entries = np.ascontiguousarray(entries, dtype=np.uint8).reshape(-1, HEADS)
     confuse = check_confuse(confuse)
     mm, mc = check_params(max_mismatch, max_cost)
+    indel, gap = check_indel(indel, gap_cost)
     ended_i, ended_f = np.asarray(ended_i, np.int32), np.asarray(ended_f, f32)
     ended_count = np.asarray(ended_count).astype(np.int64).reshape(-1)
     S, max_ended = ended_i.shape[:2]
@@ -235,14 +299,13 @@ def watch_match_np(entries, confuse, ended_i, ended_f, ended_count, max_mismatch
         raise ValueError('ended_i / ended_f must be [S, max_ended, %d] and ended_count [S]' % ENDED_COLS)
     out = np.zeros((S, max_ended, 4), np.int32)
     out[:, :, 0] = -1
+    out_a = np.zeros((S, max_ended), np.int32)
     N = len(entries)
-    if N == 0:
-        return out
     ids = np.arange(256)
-    for s in range(S):
+    for s in range(S if N else 0):
         for j in range(min(max(int(ended_count[s]), 0), max_ended)):
             best, q = ended_i[s, j, 4:12], position_weight(ended_f[s, j, :HEADS])
-            cost, mism = np.zeros(N, np.int32), np.zeros(N, np.int32)
+            tab = []                                                        # per position: (cost, mismatch) of every entry byte
             for p in range(HEADS):
                 b = int(best[p])
                 c = np.full(256, FULL, np.int32)
@@ -250,12 +313,31 @@ def watch_match_np(entries, confuse, ended_i, ended_f, ended_count, max_mismatch
                 if 0 <= b < MAX_CLS:
                     c[:MAX_CLS] = confuse[GROUP_OF[p], b]
                     miss &= ids != b
-                w = entries[:, p]
-                cost += np.where(miss, int(q[p]) * c, 0).astype(np.int32)[w]
-                mism += miss.astype(np.int32)[w]
+                tab.append((np.where(miss, int(q[p]) * c, 0).astype(np.int32), miss.astype(np.int32)))
+
+            def pair(p, col):                                               # read head p against entry head col, as one word
+                w = entries[:, col]
+                return (tab[p][0][w].astype(np.int64) << 8) | tab[p][1][w]
+
+            U = [pair(p, p) for p in range(HEADS)]
+            word = [sum(U)]                                                 # code 0; cost << 8 | mismatches, mismatches <= 8
+            if indel:
+                L = {p: pair(p, p + 1) for p in range(2, 7)}
+                R = {p: pair(p, p - 1) for p in range(3, 8)}
+                gapw = (gap << 8) | 1
+                for k in range(2, 7):                                       # codes 1..5
+                    word.append(U[0] + U[1] + sum(U[2:k]) + sum(L[p] for p in range(k, 7)) + gapw)
+                for k in range(2, 7):                                       # codes 6..10
+                    word.append(U[0] + U[1] + sum(U[2:k]) + sum(R[p] for p in range(k + 1, 8)) + gapw)
+                word.append(U[0] + U[1] + sum(U[2:7]) + gapw)               # code 11
+            word = np.stack(word)
+            code = np.argmin(word, axis=0)                                  # the first (lowest) code of the smallest (cost, mismatches)
+            win = word[code, np.arange(N)]
+            cost, mism = (win >> 8).astype(np.int32), (win & 255).astype(np.int32)
             ok = (mism <= mm) & (cost <= mc)
             n = int(ok.sum())
             if n:
                 e = int(np.argmin(np.where(ok, cost, MAX_COST + 1)))        # the first index of the smallest accepted cost
                 out[s, j] = (e, mism[e], cost[e], n)
-    return out
+                out_a[s, j] = code[e]
+    return (out, out_a) if align else out

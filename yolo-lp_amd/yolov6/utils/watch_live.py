@@ -27,11 +27,15 @@ or not it had a frame in the call; every slot t < T goes through the steps in or
      layout -- the record the track would leave if it ended now: q_i[s, j] = (id, first, last, hits, best_0..7),
      q_f[s, j] = (share_0..7, box x1, y1, x2, y2), q_slot[s, j] = t, q_count[s] = their number; lines past the count are zero,
      with q_slot = -1;
-  5. m = ``watch.watch_match_np(entries, confuse, q_i, q_f, q_count, max_mismatch, max_cost)``: the existing rule, unchanged;
+  5. m = ``watch.watch_match_np(entries, confuse, q_i, q_f, q_count, max_mismatch, max_cost)``: the existing rule, unchanged
+     (with ``indel=1``: ``watch_match_np(..., 1, gap_cost, align=True)``, which also gives the alignment code a of every query);
   6. for every fresh slot memo[s, t] = (id + 1, key_lo, key_hi, m.entry, m.mismatches, m.cost, m.n_hits, slot.last).  A lookup
      that found nothing is memoised too (entry = -1), so it is not repeated;
   7. live_i int32 [S, T, 8], one row per slot: for a live slot whose memo holds its id
-     (id, entry, mismatches, cost, n_hits, fresh ? 1 : 0, hits, last_at_lookup); for every other slot (-1, -1, 0, 0, 0, 0, 0, 0).
+     (id, entry, mismatches, cost, n_hits, fresh ? 1 : 0, hits, last_at_lookup); for every other slot (-1, -1, 0, 0, 0, 0, 0, 0);
+  8. (``indel=1``) live_align int32 [S, T], one code per slot, kept beside the memo (the memo's eight words are unchanged): a fresh
+     slot gets the code of its lookup, a slot whose row of live_i is a standing one keeps the code it has, every other slot gets 0.
+     So the code of a standing hit is the one of its lookup.
 
 What follows: an alert is a row with fresh == 1 and entry >= 0; a row with fresh == 0 and entry >= 0 is a standing hit.  A track is
 looked up once when it reaches ``min_hits`` and again only when its voted read changes.  A new track in a reused slot never inherits
@@ -40,8 +44,8 @@ Enabling again, for another list or other limits, zeroes the whole memo.
 
 What it does not do: the read is the one at the end of the call (a stream with several frames in one call has each of its tracks
 looked up at most once); the memoised cost is as of the lookup -- a read whose key stays put while its shares move is not scored
-again, and the ended-record match of ``enable_watch`` remains the final word; and as before no insertions or deletions, one best
-entry plus a count.
+again, and the ended-record match of ``enable_watch`` remains the final word; and as ``yolov6.utils.watch``: at most one
+insertion or deletion in heads 2..7, and only with ``indel=1``; one best entry plus a count.
 """
 import numpy as np
 
@@ -81,13 +85,17 @@ class LiveWatchNp:
     ``entries_np`` and ``confuse_np`` (``watch.WatchlistNp``, ``runtime.Watchlist``).  ``step()`` after an ``update`` returns live_i
     and leaves the queries in ``q_i``, ``q_f``, ``q_slot``, ``q_count`` and the match of step 5 in ``match_i``."""
 
-    def __init__(self, tracker, watchlist, min_hits=3, max_mismatch=1, max_cost=None):
+    def __init__(self, tracker, watchlist, min_hits=3, max_mismatch=1, max_cost=None, indel=0, gap_cost=None):
         self.tracker, self.watchlist = tracker, watchlist
         self.min_hits = check_min_hits(min_hits)
         self.max_mismatch, self.max_cost = watch.check_params(max_mismatch, watch.cost_units(max_cost))
+        self.indel, self.gap_cost = watch.check_indel(indel, watch.gap_units(gap_cost))
         S, T = tracker.n_streams, tracker.max_tracks
         self.memo = np.zeros((S, T, MEMO_COLS), np.int32)
         self.live_i = self.q_i = self.q_f = self.q_slot = self.q_count = self.match_i = None
+        #: with ``indel=1``: int32 [S, T] of rule 8 (kept between steps), and the match_align of step 5; else None
+        self.live_align = np.zeros((S, T), np.int32) if self.indel else None
+        self.match_align = None
 
     def reset(self, streams=None):
         """Zero the memo of ``streams`` (all for None)."""
@@ -115,7 +123,11 @@ class LiveWatchNp:
                 q_slot[s, j] = t
                 q_count[s] = j + 1
         wl = self.watchlist
-        m = watch.watch_match_np(wl.entries_np, wl.confuse_np, q_i, q_f, q_count, self.max_mismatch, self.max_cost)   # 5
+        if self.indel:                                                                   # 5
+            m, a = watch.watch_match_np(wl.entries_np, wl.confuse_np, q_i, q_f, q_count, self.max_mismatch, self.max_cost, 1, self.gap_cost,
+                                        align=True)
+        else:
+            m = watch.watch_match_np(wl.entries_np, wl.confuse_np, q_i, q_f, q_count, self.max_mismatch, self.max_cost)
         for s in range(S):                                                               # 6
             for j in range(int(q_count[s])):
                 t = q_slot[s, j]
@@ -124,5 +136,11 @@ class LiveWatchNp:
         live_i[:] = NO_ROW
         for s, t in np.argwhere(live & (memo[:, :, 0] == trk.id + 1)):
             live_i[s, t] = (trk.id[s, t],) + tuple(memo[s, t, 3:7]) + (int(fresh[s, t]), trk.hits[s, t], memo[s, t, 7])
+        if self.indel:                                                                   # 8
+            keep = np.where(live & (memo[:, :, 0] == trk.id + 1), self.live_align, 0).astype(np.int32)
+            for s in range(S):
+                for j in range(int(q_count[s])):
+                    keep[s, q_slot[s, j]] = a[s, j]
+            self.live_align, self.match_align = keep, a
         self.live_i, self.q_i, self.q_f, self.q_slot, self.q_count, self.match_i = live_i, q_i, q_f, q_slot, q_count, m
         return live_i
