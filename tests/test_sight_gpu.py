@@ -33,7 +33,7 @@ def _consts():
 
 E, QB = _consts()
 CAPACITIES = [1, 5, E - 1, E, E + 1, 2 * E + 3]
-READ_COUNTS = [0, 1, QB - 1, QB, QB + 1, 2 * QB + 1]
+READ_COUNTS = [0, 1, 5, QB - 1, QB, QB + 1, 2 * QB + 1]        # 5: a block of five to eight reads is an instance of its own
 LIMITS = [(0, 32768), (1, 32768), (8, 32768), (2, 2500)]       # max_mismatch 0 / 1 / 8 and a tight max_cost
 
 
@@ -140,7 +140,7 @@ def _differ(what, got, want):
 
 @pytest.mark.parametrize('cap', CAPACITIES)
 def test_sight_update_equals_numpy_spec(cap):
-    """Six calls on one log, one per read count; every call is run under each of the four limits from the same state (the log is
+    """One call per read count on one log; every call is run under each of the four limits from the same state (the log is
     put back in between), and the sequence goes on from the last."""
     from yolov6.utils.sight import sight_update_np
     rng = np.random.default_rng(cap)

@@ -29,7 +29,7 @@ def _consts():
 
 E, QB = _consts()
 LIST_LENGTHS = [0, 1, 63, 64, 65, E - 1, E, E + 1, 2 * E + 3]
-READ_COUNTS = [0, 1, QB - 1, QB, QB + 1, 2 * QB + 1]
+READ_COUNTS = [0, 1, QB - 1, QB, QB + 1, 2 * QB + 1, 5, 9]     # 5, 9: blocks of up to eight and twelve reads are instances of their own
 LIMITS = [(0, 32768), (1, 32768), (8, 32768), (2, 2500)]       # max_mismatch 0 / 1 / 8 and a tight max_cost
 
 

@@ -5,6 +5,13 @@
 // nothing here; the written-down specification is yolov6/utils/sight.py (sight_update_np), which these kernels match on every int32
 // of sight_i and of the log (tests/test_sight_gpu.py).  Everything is integer except one fp32 product per read and position; the
 // reductions are an unsigned minimum and an integer sum, so the result does not depend on the order in which workgroups arrive.
+// The record layout, the weight of a position (read_weight, also of the stored weights), where the confusion table keeps a pair's
+// cost (confuse_offset), the prefix sum and the host's limit checks are lp_read_match.inc's, shared with lp_watch.hip.  The table
+// loop (bytes, no WILD column; the default of 16, the clamp at 16 and "own id costs nothing" restated in it), the staging (qp
+// transposed, the reads' streams), the flush of a block and the scoring loop stay this file's own: sight_scan_kernel sits on a
+// register edge (35 spilled at two workgroups per CU), and with the table's cost rule, the flush and the quantiser's test taken
+// from shared functions it kept its 35 spills but reloaded three more registers in front of every table build and lp_sight_update
+// was 3 % slower (profiles/read_match_codegen.txt).  As it stands the kernel is the one it was before the sharing.
 //
 // sight_prep_kernel (one workgroup): every thread owns a run of lines, counts its reads (a line below its stream's clamped count
 //   whose hits reach min_hits), the counts are prefix-summed in LDS, read k of the call gets its line in qlist[k] and every line its
@@ -29,6 +36,7 @@
 //   thread 0 writes the new total.  It runs behind the tail in stream order: the tail has read the old rows by then.
 #include "lp_internal.h"
 #include "lp_streams.h"
+#include "lp_read_match.inc"
 
 namespace lp {
 
@@ -40,7 +48,6 @@ constexpr int G_R = G_E / G_T;                             // slots per lane
 constexpr int G_QB = LP_SIGHT_QUERY_BLOCK;
 constexpr int G_COLS = 65;                                 // 0..63 ids, 64 matches nothing
 constexpr int G_PREP_T = 1024;
-constexpr int G_ENDED_COLS = 12;                           // ended_i / ended_f: words of a record
 constexpr int G_WORDS = 8;                                 // int32 words of a row of the log and of sight_i
 constexpr unsigned G_RANK_MASK = 0xfffffffu;               // 28 bits of the key hold the age rank (< capacity <= 2^24)
 static_assert(G_R == 4 && G_QB == 16, "lp_sight.hip is written for 4 slots per lane and blocks of 16 reads");
@@ -67,8 +74,6 @@ SightWs sight_carve(void* base, size_t S, size_t max_ended) {
     return w;
 }
 
-__device__ __forceinline__ int clamp_count(int c, int max_ended) { return c < 0 ? 0 : (c > max_ended ? max_ended : c); }
-
 // grid (1), block (1024); per = ceil(L / 1024) lines per thread
 __global__ __launch_bounds__(G_PREP_T) void sight_prep_kernel(const int32_t* __restrict__ state, const int32_t* __restrict__ ended_i,
                                                               const int32_t* __restrict__ ended_count, int S, int max_ended, int min_hits,
@@ -81,16 +86,10 @@ __global__ __launch_bounds__(G_PREP_T) void sight_prep_kernel(const int32_t* __r
     int c = 0;
     for (int l = lo; l < hi; ++l) {
         const int s = l / max_ended, j = l - s * max_ended;
-        c += (j < clamp_count(ended_count[s], max_ended) && ended_i[(long long)l * G_ENDED_COLS + 3] >= min_hits) ? 1 : 0;
+        c += (j < clamp_count(ended_count[s], max_ended) && ended_i[(long long)l * RM_REC_WORDS + RM_W_HITS] >= min_hits) ? 1 : 0;
     }
     s_scan[tid] = c;
-    __syncthreads();
-    for (int d = 1; d < G_PREP_T; d <<= 1) {                           // inclusive prefix sum
-        const int v = tid >= d ? s_scan[tid - d] : 0;
-        __syncthreads();
-        s_scan[tid] += v;
-        __syncthreads();
-    }
+    block_prefix_sum<G_PREP_T>(s_scan);
     int k = s_scan[tid] - c;                                           // number of this thread's first read: k + c <= L
     if (tid == 0) {
         ws.hdr[0] = s_scan[G_PREP_T - 1];
@@ -100,7 +99,7 @@ __global__ __launch_bounds__(G_PREP_T) void sight_prep_kernel(const int32_t* __r
     }
     for (int l = lo; l < hi; ++l) {
         const int s = l / max_ended, j = l - s * max_ended;
-        const bool read = j < clamp_count(ended_count[s], max_ended) && ended_i[(long long)l * G_ENDED_COLS + 3] >= min_hits;
+        const bool read = j < clamp_count(ended_count[s], max_ended) && ended_i[(long long)l * RM_REC_WORDS + RM_W_HITS] >= min_hits;
         ws.keys[l] = ~0ull;
         ws.cnts[l] = 0;
         ws.kidx[l] = read ? k : -1;
@@ -147,8 +146,8 @@ __device__ __forceinline__ void sight_block(SightLds& lds, const unsigned char* 
             col0[0] = 0x20u | 16u;                                     // a stored id that matches nothing
             continue;
         }
-        unsigned cw = 0x10101010u;
-        if (confuse != nullptr && inr) cw = *(const unsigned*)(confuse + ((p < 2 ? p : 2) * 4096 + b * 64 + c4 * 4));
+        unsigned cw = 0x10101010u;                                     // the cost rule of the watch table (build_read_table), in bytes   
+        if (confuse != nullptr && inr) cw = *(const unsigned*)(confuse + confuse_offset(p, b, c4));
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             unsigned c = (cw >> (8 * k)) & 0xffu;
@@ -262,9 +261,9 @@ __global__ __launch_bounds__(G_T, 2) void sight_scan_kernel(const int32_t* __res
             unsigned qp = 1u;
             if (q < nq) {
                 line = ws.qlist[k0 + q];
-                b = ended_i[(long long)line * G_ENDED_COLS + 4 + p];
-                const float share = ended_f[(long long)line * G_ENDED_COLS + p];
-                if (share > 0.f) qp = (unsigned)(int)fminf(share * 255.0f, 255.0f) + 1u;
+                b = ended_i[(long long)line * RM_REC_WORDS + RM_W_IDS + p];
+                const float share = ended_f[(long long)line * RM_REC_WORDS + RM_F_SHARES + p];
+                if (share > 0.f) qp = read_weight(share);
             }
             lds.best[tid] = b;
             lds.qp[p * G_QB + q] = qp;
@@ -311,10 +310,8 @@ __global__ __launch_bounds__(256) void sight_append_kernel(int32_t* __restrict__
     unsigned idw[2] = {0u, 0u}, qw[2] = {0u, 0u};
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
-        const int b = ended_i[(long long)line * G_ENDED_COLS + 4 + p];
-        const float share = ended_f[(long long)line * G_ENDED_COLS + p];
-        unsigned qp = 1u;
-        if (share > 0.f) qp = (unsigned)(int)fminf(share * 255.0f, 255.0f) + 1u;
+        const int b = ended_i[(long long)line * RM_REC_WORDS + RM_W_IDS + p];
+        const unsigned qp = read_weight(ended_f[(long long)line * RM_REC_WORDS + RM_F_SHARES + p]);
         idw[p >> 2] |= ((unsigned)b < 64u ? (unsigned)b : 254u) << (8 * (p & 3));
         qw[p >> 2] |= (qp - 1u) << (8 * (p & 3));
     }
@@ -322,11 +319,7 @@ __global__ __launch_bounds__(256) void sight_append_kernel(int32_t* __restrict__
     const int slot = (int)(((t % C) + C) % C);                         // in 0..C-1
     int4* row = (int4*)(state + (size_t)(1 + slot) * G_WORDS);
     row[0] = make_int4((int)idw[0], (int)idw[1], (int)qw[0], (int)qw[1]);
-    row[1] = make_int4(line / max_ended, ended_i[(long long)line * G_ENDED_COLS], now[0], (int)t);
-}
-
-bool sight_dims_ok(int n_streams, int max_ended) {
-    return n_streams >= 1 && max_ended >= 0 && (long long)n_streams * max_ended * G_ENDED_COLS < 0x80000000ll;
+    row[1] = make_int4(line / max_ended, ended_i[(long long)line * RM_REC_WORDS + RM_W_TRACK], now[0], (int)t);
 }
 
 }  // namespace
@@ -341,7 +334,7 @@ extern "C" size_t lp_sight_state_bytes(int capacity) {
 }
 
 extern "C" size_t lp_sight_workspace_bytes(int n_streams, int max_ended) {
-    if (!sight_dims_ok(n_streams, max_ended)) return 0;
+    if (!ended_dims_fault(n_streams, max_ended).empty()) return 0;
     return sight_carve(nullptr, (size_t)n_streams, (size_t)max_ended).bytes;
 }
 
@@ -352,11 +345,9 @@ extern "C" int lp_sight_update(int32_t* state, int capacity, const unsigned char
     const std::string fn = "lp_sight_update: ";
     if (capacity < 1 || capacity > LP_SIGHT_MAX_CAPACITY)
         return fail(LP_ERR_ARG, fn + "capacity " + std::to_string(capacity) + " (need 1.." + std::to_string(LP_SIGHT_MAX_CAPACITY) + ")");
-    if (!sight_dims_ok(n_streams, max_ended))
-        return fail(LP_ERR_ARG, fn + "need n_streams >= 1, max_ended >= 0 and n_streams * max_ended * 12 < 2^31");
+    if (const std::string f = ended_dims_fault(n_streams, max_ended); !f.empty()) return fail(LP_ERR_ARG, fn + f);
     if (window < 0 || min_hits < 1) return fail(LP_ERR_ARG, fn + "need window >= 0 and min_hits >= 1");
-    if (max_mismatch < 0 || max_mismatch > 8 || max_cost < 0 || max_cost > LP_WATCH_MAX_COST)
-        return fail(LP_ERR_ARG, fn + "need max_mismatch in 0..8 and max_cost in 0.." + std::to_string(LP_WATCH_MAX_COST));
+    if (const std::string f = match_limits_fault(max_mismatch, max_cost); !f.empty()) return fail(LP_ERR_ARG, fn + f);
     if (max_ended == 0) return LP_OK;                                  // no line: no read, nothing to write
     if (!state || !ended_i || !ended_f || !ended_count || !now || !sight_i || !workspace) return fail(LP_ERR_ARG, fn + "null pointer");
     if (((uintptr_t)state & 15) != 0 || ((uintptr_t)sight_i & 15) != 0 || ((uintptr_t)workspace & 15) != 0 || ((uintptr_t)confuse & 3) != 0 ||
@@ -370,8 +361,8 @@ extern "C" int lp_sight_update(int32_t* state, int capacity, const unsigned char
         const Region reg[] = {{state, lp_sight_state_bytes(capacity), true},
                               {confuse, confuse ? (size_t)3 * 64 * 64 : 0, false},
                               {pair, pair ? (size_t)n_streams * n_streams : 0, false},
-                              {ended_i, L * G_ENDED_COLS * 4, false},
-                              {ended_f, L * G_ENDED_COLS * 4, false},
+                              {ended_i, L * RM_REC_WORDS * 4, false},
+                              {ended_f, L * RM_REC_WORDS * 4, false},
                               {ended_count, (size_t)n_streams * 4, false},
                               {now, 4, false},
                               {sight_i, L * G_WORDS * 4, true},

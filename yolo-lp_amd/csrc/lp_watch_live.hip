@@ -12,7 +12,7 @@
 //   (slot, head) each read one head: the argmax over ncls[p] <= 64 floats, lowest index on a tie, and the share (track_read_head of
 //   lp_track_read.inc, rule 8 of lp_track.hip's read_head to the letter; tests pin the two together).  Thread t packs the key and
 //   decides `fresh`; the fresh slots are numbered in slot order by ballot and prefix count over the two waves, as track_kernel numbers ending
-//   tracks, and their lines go out in the ended-record layout.  Lines past the count are zeroed (q_slot -1), and pos[s][t] -- the
+//   tracks, and their lines go out in the ended-record layout (lp_read_match.inc).  Lines past the count are zeroed (q_slot -1), and pos[s][t] -- the
 //   query line of slot t, -1 for none -- is left in the workspace for the scatter.
 // lp_watch_match on (q_i, q_f, q_count) with max_ended = max_tracks; its match_i lies in the workspace.
 // live_scatter_kernel, steps 6 and 7: thread t memoises the answer of a fresh slot (key repacked from its query line) and writes the
@@ -22,6 +22,7 @@
 #include "lp_internal.h"
 #include "lp_streams.h"
 #include "lp_track_read.inc"
+#include "lp_read_match.inc"
 
 namespace lp {
 
@@ -32,7 +33,6 @@ constexpr int WL_HEADS = TR_HEADS;
 constexpr int WL_T = WL_SLOTS * WL_HEADS;       // most threads of a gather workgroup: one per (slot, head)
 // the tracker state: lp_track_read.inc
 constexpr int WL_HDR_WORDS = TR_HDR_WORDS, WL_W_BOX = TR_W_BOX, WL_SLOT_WORDS = TR_SLOT_WORDS;
-constexpr int WL_Q_COLS = 12;                   // q_i / q_f: words of a line (the ended-record layout)
 constexpr int WL_MEMO_WORDS = 8, WL_LIVE_COLS = 8;
 
 struct LiveNcls { int v[WL_HEADS]; };
@@ -60,7 +60,7 @@ LiveWs live_carve(void* base, size_t S, size_t T) {
 }
 
 bool live_dims_ok(int n_streams, int max_tracks) {
-    return n_streams >= 1 && max_tracks >= 1 && max_tracks <= LP_TRACK_MAX_TRACKS && (long long)n_streams * max_tracks * WL_Q_COLS < 0x80000000ll;
+    return n_streams >= 1 && max_tracks >= 1 && max_tracks <= LP_TRACK_MAX_TRACKS && (long long)n_streams * max_tracks * RM_REC_WORDS < 0x80000000ll;
 }
 
 // grid (n_streams), block (max(128, max_tracks * 8 rounded up to 64))
@@ -132,15 +132,15 @@ __global__ __launch_bounds__(WL_T) void live_gather_kernel(const int* __restrict
     __syncthreads();
     if (hslot < T && s_pos[hslot] >= 0) {                              // the record the track would leave if it ended now
         const int* sl = sst + (long long)hslot * WL_SLOT_WORDS;
-        int32_t* ri = q_i + (line0 + s_pos[hslot]) * WL_Q_COLS;
-        float* rf = q_f + (line0 + s_pos[hslot]) * WL_Q_COLS;
-        ri[4 + head] = s_best[tid];
-        rf[head] = s_share[tid];
-        if (head < 4) { ri[head] = sl[head]; rf[8 + head] = __int_as_float(sl[WL_W_BOX + head]); }
+        int32_t* ri = q_i + (line0 + s_pos[hslot]) * RM_REC_WORDS;
+        float* rf = q_f + (line0 + s_pos[hslot]) * RM_REC_WORDS;
+        ri[RM_W_IDS + head] = s_best[tid];
+        rf[RM_F_SHARES + head] = s_share[tid];
+        if (head < 4) { ri[RM_W_TRACK + head] = sl[head]; rf[RM_F_BOX + head] = __int_as_float(sl[WL_W_BOX + head]); }
     }
-    for (int w = nfresh * WL_Q_COLS + tid; w < T * WL_Q_COLS; w += blockDim.x) {       // the lines past the count
-        q_i[line0 * WL_Q_COLS + w] = 0;
-        q_f[line0 * WL_Q_COLS + w] = 0.f;
+    for (int w = nfresh * RM_REC_WORDS + tid; w < T * RM_REC_WORDS; w += blockDim.x) {       // the lines past the count
+        q_i[line0 * RM_REC_WORDS + w] = 0;
+        q_f[line0 * RM_REC_WORDS + w] = 0.f;
     }
 }
 
@@ -159,13 +159,13 @@ __global__ __launch_bounds__(WL_SLOTS) void live_scatter_kernel(const int* __res
     int4 out0 = make_int4(-1, -1, 0, 0), out1 = make_int4(0, 0, 0, 0);
     const int j = pos[line];
     if (j >= 0) {                                                      // step 6 (a fresh slot is live)
-        const int32_t* ri = q_i + ((long long)s * T + j) * WL_Q_COLS;
+        const int32_t* ri = q_i + ((long long)s * T + j) * RM_REC_WORDS;
         const int4 m = *(const int4*)(match_i + ((long long)s * T + j) * 4);            // entry, mismatches, cost, n_hits
         unsigned lo = 0, hi = 0;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            lo |= (unsigned)ri[4 + p] << (8 * p);
-            hi |= (unsigned)ri[8 + p] << (8 * p);
+            lo |= (unsigned)ri[RM_W_IDS + p] << (8 * p);
+            hi |= (unsigned)ri[RM_W_IDS + 4 + p] << (8 * p);
         }
         mline[0] = make_int4(h.x + 1, (int)lo, (int)hi, m.x);
         mline[1] = make_int4(m.y, m.z, m.w, h.z);
@@ -215,7 +215,7 @@ static int watch_live_run(const std::string& fn, bool with_indel, const void* tr
                           int32_t* live_i, int32_t* live_align, void* workspace, size_t workspace_bytes, void* stream) {
     if (!live_dims_ok(n_streams, max_tracks))
         return fail(LP_ERR_ARG, fn + "need n_streams >= 1, max_tracks in 1.." + std::to_string(LP_TRACK_MAX_TRACKS) +
-                                    " and n_streams * max_tracks * 12 < 2^31");
+                                    " and n_streams * max_tracks * " + std::to_string(RM_REC_WORDS) + " < 2^31");
     if (!ncls) return fail(LP_ERR_ARG, fn + "null pointer (ncls)");
     LiveNcls nc;
     for (int h = 0; h < WL_HEADS; ++h) {
@@ -226,8 +226,7 @@ static int watch_live_run(const std::string& fn, bool with_indel, const void* tr
     if (min_hits < 1) return fail(LP_ERR_ARG, fn + "min_hits must be >= 1");
     if (n_entries < 0 || n_entries > LP_WATCH_MAX_ENTRIES)
         return fail(LP_ERR_ARG, fn + "n_entries " + std::to_string(n_entries) + " (need 0.." + std::to_string(LP_WATCH_MAX_ENTRIES) + ")");
-    if (max_mismatch < 0 || max_mismatch > 8 || max_cost < 0 || max_cost > LP_WATCH_MAX_COST)
-        return fail(LP_ERR_ARG, fn + "need max_mismatch in 0..8 and max_cost in 0.." + std::to_string(LP_WATCH_MAX_COST));
+    if (const std::string f = match_limits_fault(max_mismatch, max_cost); !f.empty()) return fail(LP_ERR_ARG, fn + f);
     if (with_indel && (indel < 0 || indel > 1 || gap_cost < 0 || gap_cost > LP_WATCH_MAX_GAP_COST))
         return fail(LP_ERR_ARG, fn + "need indel in 0..1 and gap_cost in 0.." + std::to_string(LP_WATCH_MAX_GAP_COST));
     if (!track_state || !memo || !q_i || !q_f || !q_slot || !q_count || !live_i || !workspace || (n_entries > 0 && !entries) ||
@@ -248,8 +247,8 @@ static int watch_live_run(const std::string& fn, bool with_indel, const void* tr
                               {entries, (size_t)n_entries * 8, false},
                               {confuse, n_entries > 0 && confuse ? (size_t)3 * 64 * 64 : 0, false},
                               {memo, L * WL_MEMO_WORDS * 4, true},
-                              {q_i, L * WL_Q_COLS * 4, true},
-                              {q_f, L * WL_Q_COLS * 4, true},
+                              {q_i, L * RM_REC_WORDS * 4, true},
+                              {q_f, L * RM_REC_WORDS * 4, true},
                               {q_slot, L * 4, true},
                               {q_count, (size_t)n_streams * 4, true},
                               {live_i, L * WL_LIVE_COLS * 4, true},
