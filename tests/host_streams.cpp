@@ -2,9 +2,12 @@
 // The planner is checked against its stated properties, written here without looking at how it computes them: each tracked frame's
 // workgroup carries the frame's stream, workgroups are numbered by first appearance, one per distinct stream of the launch, the
 // untracked frames follow the policy, the rest of the table is zero and the scratch vector comes back all -1.
+// The rules of the stages on live tracks (ncls, min_hits, max_events, the int32 limits) are checked at both ends of each range, message
+// by message, and the tracker's state layout against the numbers that the tests' own packer uses.
 #include "../yolo-lp_amd/csrc/lp_streams.h"
 
 #include <cstdio>
+#include <utility>
 
 using namespace lp;
 
@@ -100,6 +103,55 @@ static void check_rules() {
     for (const auto& d : bad) CHECK(stream_dims_fault(d[0], d[1]) == "need n_streams >= 1 and max_tracks in 1..128", "(%d, %d)", d[0], d[1]);
 }
 
+// The rules of the stages on live tracks (lp_watch_live, lp_zone_update, lp_speed_update) and the one statement of the state layout.
+static void check_live_stage_rules() {
+    CHECK(track_state_stride(1) == 16 + 544 && track_state_stride(LP_TRACK_MAX_TRACKS) == 16 + 128 * 544, "stride %lld, %lld", track_state_stride(1),
+          track_state_stride(LP_TRACK_MAX_TRACKS));
+    CHECK(TR_W_BOX == 8 && TR_W_COR == 12 && TR_W_VEL == 20 && TR_W_TOTAL == 24 && TR_W_VOTES == 32 && TR_SLOT_WORDS == 544 && TR_HDR_WORDS == 16,
+          "the layout that tests/test_streams_cpu.py::track_state_words writes");
+    CHECK(RM_REC_WORDS == 12 && RM_W_TRACK == 0 && RM_W_HITS == 3 && RM_W_IDS == 4 && RM_F_SHARES == 0 && RM_F_BOX == 8, "the ended record");
+    // ncls: every head at both ends of 1..LP_TRACK_MAX_CLS, and one step outside
+    for (int h = 0; h < TR_HEADS; ++h) {
+        for (int v : {0, 1, LP_TRACK_MAX_CLS, LP_TRACK_MAX_CLS + 1}) {
+            int ncls[TR_HEADS] = {31, 24, 37, 37, 37, 37, 37, 37};
+            ncls[h] = v;
+            TrackNcls out = {};
+            const std::string why = ncls_fault(ncls, out);
+            if (v >= 1 && v <= LP_TRACK_MAX_CLS) {
+                bool same = why.empty();
+                for (int k = 0; k < TR_HEADS; ++k) same = same && out.v[k] == ncls[k];
+                CHECK(same, "head %d = %d: %s", h, v, why.c_str());
+            } else {
+                CHECK(why == "ncls of head " + std::to_string(h) + " must be in 1..64", "head %d = %d: %s", h, v, why.c_str());
+            }
+        }
+    }
+    TrackNcls out = {};
+    CHECK(ncls_fault(nullptr, out) == "null pointer (ncls)", "%s", ncls_fault(nullptr, out).c_str());
+    const int two_bad[TR_HEADS] = {31, 0, 37, 99, 37, 37, 37, 37};
+    CHECK(ncls_fault(two_bad, out) == "ncls of head 1 must be in 1..64", "the first bad head is named: %s", ncls_fault(two_bad, out).c_str());
+    CHECK(min_hits_fault(0) == "min_hits must be >= 1" && min_hits_fault(-3) == "min_hits must be >= 1" && min_hits_fault(1).empty() &&
+          min_hits_fault(0x7fffffff).empty(), "min_hits");
+    // max_events: 178956970 * 12 = 2^31 - 8, 178956971 * 12 = 2^31 + 4
+    const std::string ev = "need max_events >= 0 and n_streams * max_events * 12 < 2^31";
+    CHECK(max_events_fault(1, -1, 12) == ev && max_events_fault(1, 0, 12).empty() && max_events_fault(1, 178956970, 12).empty() &&
+          max_events_fault(1, 178956971, 12) == ev, "max_events of one stream: %s", max_events_fault(1, 178956971, 12).c_str());
+    CHECK(max_events_fault(4, 44739242, 12).empty() && max_events_fault(4, 44739243, 12) == ev && max_events_fault(0x7fffffff, 0, 12).empty(),
+          "max_events of several streams");
+    CHECK(max_events_fault(2, -1, 8) == "need max_events >= 0 and n_streams * max_events * 8 < 2^31", "the column count is named");
+    // the words that n_streams streams may have: 30833 * 69648 < 2^31 <= 30834 * 69648
+    const std::string dims = "need n_streams >= 1, max_tracks in 1..128 and ";
+    const long long full = track_state_stride(LP_TRACK_MAX_TRACKS);
+    CHECK(stream_words_fault(30833, 128, {full}, "a state of fewer than 2^31 words").empty(), "30833 streams of 128 slots");
+    CHECK(stream_words_fault(30834, 128, {full}, "a state of fewer than 2^31 words") == dims + "a state of fewer than 2^31 words", "30834 streams of 128 slots");
+    CHECK(stream_words_fault(5, 128, {full, 0x80000000ll / 5 + 1}, "a state and a map of fewer than 2^31 words") == dims + "a state and a map of fewer than 2^31 words" &&
+          stream_words_fault(5, 128, {full, 0x80000000ll / 5}, "x").empty(), "every entry of the list is held to the limit");
+    CHECK(stream_words_fault(1398102, 128, {128 * 12}, "n_streams * max_tracks * 12 < 2^31") == dims + "n_streams * max_tracks * 12 < 2^31" &&
+          stream_words_fault(1398101, 128, {128 * 12}, "y").empty(), "the query lines of lp_watch_live");
+    for (const auto& d : {std::pair<int, int>{0, 4}, {1, 0}, {1, LP_TRACK_MAX_TRACKS + 1}, {-1, -1}})
+        CHECK(stream_words_fault(d.first, d.second, {1}, "z") == dims + "z", "(%d, %d)", d.first, d.second);
+}
+
 static void check_regions() {
     static char buf[64];
     CHECK(!overlap(buf, 16, buf + 16, 16) && !overlap(buf + 16, 16, buf, 16), "adjacent");
@@ -130,6 +182,7 @@ static void check_thresholds() {
 int main() {
     check_planner();
     check_rules();
+    check_live_stage_rules();
     check_regions();
     check_thresholds();
     if (failures) std::printf("%d checks failed\n", failures);

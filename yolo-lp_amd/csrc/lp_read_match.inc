@@ -1,6 +1,6 @@
 // What the scans that match voted plate reads against packed 8-byte entries have in common (lp_watch.hip: lp_watch_match and
-// lp_watch_match_indel; lp_sight.hip: lp_sight_update; lp_watch_live.hip writes the records they read): the layout of an ended record,
-// the weight of a position, where the confusion table keeps a pair's cost, the table of the two watchlist scans and the prefix sum.
+// lp_watch_match_indel; lp_sight.hip: lp_sight_update; lp_watch_live.hip writes the records they read): the limits of an ended-record list
+// (its layout is lp_streams.h's), the weight of a position, where the confusion table keeps a pair's cost, the table of the two watchlist scans and the prefix sum.
 // Each rule is stated here once; its written-down form is yolov6/utils/watch.py (position_weight, confuse_table, watch_match_np),
 // which the kernels match on every int32.
 #pragma once
@@ -9,12 +9,7 @@ namespace lp {
 
 namespace {
 
-// ---- an ended record: a line of ended_i / ended_f of lp_track_update, and of q_i / q_f of lp_watch_live -----------------------------
-constexpr int RM_REC_WORDS = 12;                // words of a line, int32 and float alike
-constexpr int RM_W_TRACK = 0, RM_W_HITS = 3;    // ended_i: the track's id (then first, last), its hits,
-constexpr int RM_W_IDS = 4;                     //   and the voted ids of the eight heads at words 4..11
-constexpr int RM_F_SHARES = 0, RM_F_BOX = 8;    // ended_f: their shares of the votes at floats 0..7, the last box at 8..11
-
+// ---- an ended record (RM_REC_WORDS, RM_W_*, RM_F_*): lp_streams.h, beside the tracker's state, whose kernel writes it -------------
 // n_streams x max_ended lines that an int32 index can address; else the message that the entry points return
 inline std::string ended_dims_fault(int n_streams, int max_ended) {
     if (n_streams >= 1 && max_ended >= 0 && (long long)n_streams * max_ended * RM_REC_WORDS < 0x80000000ll) return std::string();

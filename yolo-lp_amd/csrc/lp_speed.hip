@@ -5,7 +5,7 @@
 // memo (tests/test_speed_gpu.py).
 //
 // One kernel, one workgroup of 128 threads per stream, lane t = slot t; the tracker state is read as lp_track_update left it (layout:
-// lp_track_read.inc) and never written.
+// lp_streams.h) and never written; the phases c and d are the shared pieces of lp_track_read.inc.
 //   a. the stream's 32 map words are staged in LDS once;
 //   b. lane t reads slot t's first 16 bytes (id, first, last, hits) and its memo header (64 bytes), and of a line that holds samples the
 //      newest one (16 bytes: the row of step 7 and the event of step 2 carry its position).  Only an eligible slot with a new detection
@@ -37,7 +37,6 @@ constexpr int SP_MAX_CONFIRM = 65535, SP_I32_MAX = 0x7FFFFFFF;
 static_assert(SP_T == 128 && SP_MAP == 32 && SP_MEMO == 48 && SP_RING == 8 && SP_MEMO == 16 + 4 * SP_RING, "lp_speed.hip: the layouts of lp_hip.h");
 enum { SK_ALERT = 1, SK_ENDED = 3 };
 
-struct SpeedNcls { int v[TR_HEADS]; };
 struct SpeedEst { int speed, vx, vy, span_ms; };
 
 typedef unsigned long long u64;
@@ -45,8 +44,6 @@ typedef long long i64;
 
 __device__ __forceinline__ i64 sjoin(int lo, int hi) { return (i64)(((u64)(unsigned)hi << 32) | (u64)(unsigned)lo); }
 __device__ __forceinline__ i64 ssub(i64 a, i64 b) { return (i64)((u64)a - (u64)b); }                 // wraps
-__device__ __forceinline__ int sdiff(int a, int b) { return (int)((unsigned)a - (unsigned)b); }      // wraps
-__device__ __forceinline__ bool sfinite(float x, float y) { return fabsf(x) <= 3.4028234663852886e38f && fabsf(y) <= 3.4028234663852886e38f; }
 
 // floor(sqrt(d2)), exact, for d2 <= 2^63: the double root is within a few units of it, integer compares settle it
 __device__ __forceinline__ u64 sroot(u64 d2) {
@@ -76,7 +73,7 @@ __device__ __forceinline__ SpeedEst sestimate(i64 dx, i64 dy, i64 dt) {
 }
 
 // grid (n_streams), block (128)
-__global__ __launch_bounds__(SP_T) void speed_kernel(const int* __restrict__ state, int T, long long sstride, const SpeedNcls ncls,
+__global__ __launch_bounds__(SP_T) void speed_kernel(const int* __restrict__ state, int T, long long sstride, const TrackNcls ncls,
                                                      const int* __restrict__ map, const long long* __restrict__ clock, int min_hits, int confirm,
                                                      int32_t* __restrict__ memo, int32_t* __restrict__ speed_i, int32_t* __restrict__ speed_ev,
                                                      int32_t* __restrict__ speed_count, int max_events) {
@@ -110,7 +107,7 @@ __global__ __launch_bounds__(SP_T) void speed_kernel(const int* __restrict__ sta
                 int aux = 0;
                 if (dt > 0) aux = sestimate((i64)newest.z - (i64)m1.z, (i64)newest.w - (i64)m1.w, dt).speed;
                 ev_kind = SK_ENDED;
-                ev0 = make_int4(SK_ENDED, 0, sdiff(m0.x, 1), tid);
+                ev0 = make_int4(SK_ENDED, 0, wrap_diff(m0.x, 1), tid);
                 ev1 = make_int4(m0.y, m2.w, newest.z, newest.w);
                 ev2 = make_int4(0, 0, 0, aux);
             }
@@ -140,11 +137,11 @@ __global__ __launch_bounds__(SP_T) void speed_kernel(const int* __restrict__ sta
                 const double w0 = hh[6] * x, w1 = hh[7] * y, w2 = w0 + w1, w = w2 + hh[8];
                 const double X = u / w, Y = v / w;
                 const double px = X * 1000.0, py = Y * 1000.0;
-                const bool valid = sfinite(ax, ay) && w > 0.0 && fabs(px) <= 1073741824.0 && fabs(py) <= 1073741824.0;
+                const bool valid = finite_pair(ax, ay) && w > 0.0 && fabs(px) <= 1073741824.0 && fabs(py) <= 1073741824.0;
                 if (valid) {
                     const i64 period = (i64)s_map[SP_MAP_PERIOD];
                     const i64 base = clock ? (i64)clock[s] : (i64)((u64)(i64)now * (u64)period);
-                    const i64 tt = ssub(base, (i64)((u64)(i64)sdiff(now, h.z) * (u64)period));
+                    const i64 tt = ssub(base, (i64)((u64)(i64)wrap_diff(now, h.z) * (u64)period));
                     if (m0.z == 0 || ssub(tt, sjoin(newest.x, newest.y)) >= (i64)s_map[SP_MAP_GAP]) {
                         newest = make_int4((int)(unsigned)((u64)tt & 0xFFFFFFFFull), (int)(unsigned)((u64)tt >> 32), (int)rint(px), (int)rint(py));
                         if (m0.z == 0) m1 = newest;
@@ -196,37 +193,19 @@ __global__ __launch_bounds__(SP_T) void speed_kernel(const int* __restrict__ sta
     const int cnt = ev_kind != 0 ? 1 : 0;
     s_need[tid] = ev_kind == SK_ALERT ? 1 : 0;
     // ---- d. (first half) the events numbered in slot order ---------------------------------------------------------------------------
-    int incl = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
+    const int incl = wave_inclusive_sum(cnt, lane, wave, s_wsum);
     __syncthreads();
     // ---- c. rule 8 for the slots that alert --------------------------------------------------------------------------------------------
-    for (int i = tid; i < T * TR_HEADS; i += SP_T) {
-        const int slot = i >> 3, head = i & 7;
-        if (s_need[slot]) {
-            int bi;
-            float sh;
-            track_read_head(hdr + TR_HDR_WORDS + (long long)slot * TR_SLOT_WORDS, head, ncls.v[head], bi, sh);
-            s_best[i] = bi;
-        }
-    }
+    read_needed_heads<SP_T>(hdr + TR_HDR_WORDS, T, ncls, s_need, s_best);
     __syncthreads();
     // ---- d. the event lines, written by their lane -------------------------------------------------------------------------------------
     const int total = s_wsum[0] + s_wsum[1];
     int32_t* const ev = speed_ev + (long long)s * max_events * SP_EV_COLS;               // line k < max_events only
-    const int k = (wave == 1 ? s_wsum[0] : 0) + incl - cnt;
+    const int k = events_before(incl, cnt, wave, s_wsum);
     if (cnt > 0 && k < max_events) {
         if (ev_kind == SK_ALERT) {
-            unsigned klo = 0, khi = 0;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                klo |= (unsigned)s_best[tid * TR_HEADS + p] << (8 * p);
-                khi |= (unsigned)s_best[tid * TR_HEADS + 4 + p] << (8 * p);
-            }
+            unsigned klo, khi;
+            pack_key(s_best + tid * TR_HEADS, klo, khi);
             ev2.x = (int)klo;
             ev2.y = (int)khi;
         }
@@ -235,13 +214,12 @@ __global__ __launch_bounds__(SP_T) void speed_kernel(const int* __restrict__ sta
         o[1] = ev1;
         o[2] = ev2;
     }
-    for (long long w = (long long)total * SP_EV_COLS + tid; w < (long long)max_events * SP_EV_COLS; w += SP_T) ev[w] = 0;   // total >= 0
-    if (tid == 0) speed_count[s] = total;
+    close_event_list<SP_T, SP_EV_COLS>(ev, total, max_events, speed_count + s);
 }
 
-bool speed_dims_ok(int n_streams, int max_tracks) {
-    return n_streams >= 1 && max_tracks >= 1 && max_tracks <= LP_TRACK_MAX_TRACKS &&
-           (long long)n_streams * ((long long)TR_HDR_WORDS + (long long)max_tracks * TR_SLOT_WORDS) < 0x80000000ll;
+// the dimensions of a call, the state within an int32 index
+std::string speed_dims_fault(int n_streams, int max_tracks) {
+    return stream_words_fault(n_streams, max_tracks, {track_state_stride(max_tracks)}, "a state of fewer than 2^31 words");
 }
 
 }  // namespace
@@ -251,31 +229,25 @@ bool speed_dims_ok(int n_streams, int max_tracks) {
 using namespace lp;
 
 extern "C" size_t lp_speed_state_bytes(int n_streams, int max_tracks) {
-    if (!speed_dims_ok(n_streams, max_tracks)) return 0;
+    if (!speed_dims_fault(n_streams, max_tracks).empty()) return 0;
     return (size_t)n_streams * (size_t)max_tracks * SP_MEMO * 4;
 }
 
 extern "C" int lp_speed_update(const void* track_state, int n_streams, int max_tracks, const int* ncls, const void* ground_map, const void* clock_us,
                                int min_hits, int confirm, void* memo, void* speed_i, void* speed_ev, void* speed_count, int max_events, void* stream) {
     const std::string fn = "lp_speed_update: ";
-    if (!speed_dims_ok(n_streams, max_tracks))
-        return fail(LP_ERR_ARG, fn + "need n_streams >= 1, max_tracks in 1.." + std::to_string(LP_TRACK_MAX_TRACKS) + " and a state of fewer than 2^31 words");
-    if (max_events < 0 || (long long)n_streams * max_events * SP_EV_COLS >= 0x80000000ll)
-        return fail(LP_ERR_ARG, fn + "need max_events >= 0 and n_streams * max_events * 12 < 2^31");
-    if (!ncls) return fail(LP_ERR_ARG, fn + "null pointer (ncls)");
-    SpeedNcls nc;
-    for (int h = 0; h < TR_HEADS; ++h) {
-        if (ncls[h] < 1 || ncls[h] > LP_TRACK_MAX_CLS)
-            return fail(LP_ERR_ARG, fn + "ncls of head " + std::to_string(h) + " must be in 1.." + std::to_string(LP_TRACK_MAX_CLS));
-        nc.v[h] = ncls[h];
-    }
-    if (min_hits < 1) return fail(LP_ERR_ARG, fn + "min_hits must be >= 1");
+    TrackNcls nc;
+    std::string why = speed_dims_fault(n_streams, max_tracks);
+    if (why.empty()) why = max_events_fault(n_streams, max_events, SP_EV_COLS);
+    if (why.empty()) why = ncls_fault(ncls, nc);
+    if (why.empty()) why = min_hits_fault(min_hits);
+    if (!why.empty()) return fail(LP_ERR_ARG, fn + why);
     if (confirm < 1 || confirm > SP_MAX_CONFIRM) return fail(LP_ERR_ARG, fn + "confirm must be in 1.." + std::to_string(SP_MAX_CONFIRM));
     if (!track_state || !ground_map || !memo || !speed_i || (max_events > 0 && !speed_ev) || !speed_count) return fail(LP_ERR_ARG, fn + "null pointer");
     if ((((uintptr_t)track_state | (uintptr_t)ground_map | (uintptr_t)memo | (uintptr_t)speed_i | (uintptr_t)speed_ev | (uintptr_t)speed_count) & 15) != 0 ||
         ((uintptr_t)clock_us & 7) != 0)
         return fail(LP_ERR_ARG, fn + "the tracker state, the map, the memo and the three outputs must be 16-byte aligned, the clock 8-byte aligned");
-    const long long sstride = (long long)TR_HDR_WORDS + (long long)max_tracks * TR_SLOT_WORDS;
+    const long long sstride = track_state_stride(max_tracks);
     {   // no buffer that is written may overlap the state, the map, the clock or another one
         const Region reg[] = {{track_state, (size_t)n_streams * (size_t)sstride * 4, false},
                               {ground_map, (size_t)n_streams * SP_MAP * 4, false},

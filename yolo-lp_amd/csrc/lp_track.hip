@@ -21,13 +21,14 @@
 // numbers the ending tracks); step 7 reads their heads into the same two tables; step 8 also writes det_hold / count_hold /
 // tid_hold: the frame's rows, then one predicted row per held slot.  Every other caller runs <false>, whose code is the kernel
 // without all this (profiles/hold_codegen.txt).
-// State of a stream (int32 / fp32 words, all zero = empty): 16 header words (frame counter, next id, dropped), then per slot
-// 544 words: id, first, last, hits, misses, 3 unused; box[4]; corners[8]; vx, vy, 2 unused; total[8]; votes[8][64].  A slot is
-// live iff hits > 0.
+// The state of a stream (16 header words, 544 words per slot: TR_*) and the ended record (RM_*) are laid out in lp_streams.h; rule 8 and
+// the record writer are lp_track_read.inc's, shared with the stages that read the state behind this kernel.  The ballot numbering of
+// steps 5 and 5 <true> stays written out here: as a shared function it re-lays this kernel's spilled SGPRs (profiles/live_stage_codegen.txt).
 #include "lp_internal.h"
 #include "lp_streams.h"
 #include "lp_score.inc"
 #include "lp_nms_shared.inc"
+#include "lp_track_read.inc"
 #include <cstring>
 
 namespace lp {
@@ -35,15 +36,9 @@ namespace lp {
 namespace {
 
 constexpr int TK_T = SORT_T;                    // threads of the workgroup (bitonic_step strides by SORT_T)
-constexpr int TK_SLOTS = LP_TRACK_MAX_TRACKS;   // 128
 constexpr int TK_ROWS = LP_TRACK_MAX_DETS;      // 128
-constexpr int TK_HEADS = 8;
-constexpr int TK_HDR_WORDS = 16;
-constexpr int TK_W_BOX = 8, TK_W_COR = 12, TK_W_VEL = 20, TK_W_TOTAL = 24, TK_W_VOTES = 32;
-constexpr int TK_SLOT_WORDS = TK_W_VOTES + TK_HEADS * LP_TRACK_MAX_CLS;   // 544
 constexpr int TK_FRAMES = LP_FRAMES_PER_LAUNCH; // frames (and streams) per launch: the table travels as kernel arguments
-static_assert(TK_W_COR == TK_W_BOX + 4 && TK_W_VEL == TK_W_COR + 8, "box and corners are the row's columns 0..11, contiguous");
-static_assert(TK_SLOTS * TK_ROWS == SORT_LDS_KEYS && TK_T / TK_HEADS == TK_SLOTS && TK_ROWS == 128, "track kernel geometry");
+static_assert(TR_SLOTS * TK_ROWS == SORT_LDS_KEYS && TK_T / TR_HEADS == TR_SLOTS && TK_ROWS == 128, "track kernel geometry");
 
 enum { ST_EMPTY = 0, ST_LIVE = 1, ST_MATCHED = 2, ST_ENDING = 3, ST_NEW = 4, ST_MISSED = 5, ST_HELD = 6 };   // ST_HELD: missed and held
 
@@ -54,7 +49,7 @@ struct TkTable {                                // 584 bytes of kernel arguments
     unsigned char fr_skip[TK_FRAMES];           // frame j is not tracked (stream_of == -1)
     unsigned char blk_flush[TK_FRAMES];         // workgroup k ends all live tracks after its frames
 };
-struct TkParams { float thr_f, new_f, expand_f; int max_age; int ncls[TK_HEADS]; };
+struct TkParams { float thr_f, new_f, expand_f; int max_age; TrackNcls ncls; };
 struct TkHold {                                 // rule 11 (read by the <true> instantiation only)
     int min_hits, max_misses;
     float* det;                                 // [frames, max_det + T, 28], the launch's first frame (as det_out)
@@ -101,43 +96,28 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
                                                     int32_t* __restrict__ ended_i, float* __restrict__ ended_f, int32_t* __restrict__ ended_count,
                                                     int max_ended, const TkHold hold) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long skeys[];
-    __shared__ __attribute__((aligned(16))) box4 s_pbox[TK_SLOTS];     // predicted, expanded boxes of the live slots
+    __shared__ __attribute__((aligned(16))) box4 s_pbox[TR_SLOTS];     // predicted, expanded boxes of the live slots
     __shared__ __attribute__((aligned(16))) box4 s_dbox[TK_ROWS];      // expanded boxes of the rows
-    __shared__ int s_slot_row[TK_SLOTS], s_row_slot[TK_ROWS], s_status[TK_SLOTS], s_id[TK_SLOTS], s_endpos[TK_SLOTS], s_free[TK_SLOTS];
-    __shared__ float s_share[TK_SLOTS * TK_HEADS];
-    __shared__ int s_best[TK_SLOTS * TK_HEADS];
-    __shared__ int s_ncls[TK_HEADS];
+    __shared__ int s_slot_row[TR_SLOTS], s_row_slot[TK_ROWS], s_status[TR_SLOTS], s_id[TR_SLOTS], s_endpos[TR_SLOTS], s_free[TR_SLOTS];
+    __shared__ float s_share[TR_SLOTS * TR_HEADS];
+    __shared__ int s_best[TR_SLOTS * TR_HEADS];
+    __shared__ int s_ncls[TR_HEADS];
     __shared__ int s_nkeys, s_wcnt[2], s_nfree, s_made, s_drop;
-    __shared__ int s_hslot[HOLD ? TK_SLOTS : 1], s_hcnt[2];           // HOLD: the held slots in slot order, their number per wave
+    __shared__ int s_hslot[HOLD ? TR_SLOTS : 1], s_hcnt[2];           // HOLD: the held slots in slot order, their number per wave
     const int blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int strm = tab.blk_stream[blk];
     int* const sst = state + (strm >= 0 ? (long long)strm * sstride : 0);
     const int hslot = tid >> 3, head = tid & 7;                        // the (slot, head) this thread serves
-    int* const hsl = sst + TK_HDR_WORDS + hslot * TK_SLOT_WORDS;
-    if (tid < TK_HEADS) s_ncls[tid] = prm.ncls[tid];
+    int* const hsl = sst + TR_HDR_WORDS + hslot * TR_SLOT_WORDS;
+    if (tid < TR_HEADS) s_ncls[tid] = prm.ncls.v[tid];
     int ended_n = strm >= 0 ? ended_count[strm] : 0;                   // (written by thread 0 at the very end only)
     __syncthreads();
     const unsigned long long lt = (1ull << lane) - 1ull;
 
-    // rule 8: (best, share) of head `hd` of the slot at `sl`
-    auto read_head = [&](const int* sl, int hd, int* best, float* share) {
-        const float* v = (const float*)(sl + TK_W_VOTES + hd * LP_TRACK_MAX_CLS);
-        const int nc = s_ncls[hd];
-        int bi = 0;
-        float bv = v[0];
-#pragma unroll 4
-        for (int c = 1; c < nc; ++c) {
-            const float x = v[c];
-            if (x > bv) { bv = x; bi = c; }
-        }
-        const float tot = __int_as_float(sl[TK_W_TOTAL + hd]);
-        *best = bi;
-        *share = tot > 0.f ? bv / tot : 0.f;
-    };
     // the slots marked ST_ENDING (`ending` of threads 0..127, in slot order) write their records and are zeroed
     auto end_marked = [&](bool ending) {
         const unsigned long long em = __ballot(ending);
-        if (tid < TK_SLOTS && lane == 0) s_wcnt[wave] = __popcll(em);
+        if (tid < TR_SLOTS && lane == 0) s_wcnt[wave] = __popcll(em);
         __syncthreads();
         if (ending) s_endpos[tid] = ended_n + (wave == 1 ? s_wcnt[0] : 0) + __popcll(em & lt);
         __syncthreads();
@@ -147,18 +127,15 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
             if (pos < max_ended) {
                 int best;
                 float share;
-                read_head(hsl, head, &best, &share);
-                int32_t* ri = ended_i + ((long long)strm * max_ended + pos) * 12;
-                float* rf = ended_f + ((long long)strm * max_ended + pos) * 12;
-                ri[4 + head] = best;
-                rf[head] = share;
-                if (head < 4) { ri[head] = hsl[head]; rf[8 + head] = __int_as_float(hsl[TK_W_BOX + head]); }
+                track_read_head(hsl, head, s_ncls[head], best, share);
+                write_record_share(ended_i + ((long long)strm * max_ended + pos) * RM_REC_WORDS,
+                                   ended_f + ((long long)strm * max_ended + pos) * RM_REC_WORDS, hsl, head, best, share);
             }
         }
         __syncthreads();
         if (mine) {
 #pragma unroll 4
-            for (int w = head; w < TK_SLOT_WORDS; w += TK_HEADS) hsl[w] = 0;
+            for (int w = head; w < TR_SLOT_WORDS; w += TR_HEADS) hsl[w] = 0;
         }
         ended_n += s_wcnt[0] + s_wcnt[1];
         __syncthreads();
@@ -175,23 +152,23 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
             const int frame = sst[0];
             int next_id = sst[1], dropped = sst[2];
             // ---- 1. predicted / expanded boxes ----------------------------------------------------------------------------
-            if (tid < TK_SLOTS) {
+            if (tid < TR_SLOTS) {
                 int st = ST_EMPTY;
                 if (tid < T) {
-                    const int* sl = sst + TK_HDR_WORDS + tid * TK_SLOT_WORDS;
+                    const int* sl = sst + TR_HDR_WORDS + tid * TR_SLOT_WORDS;
                     if (sl[3] > 0) {
                         const float k = (float)(sl[4] + 1);
-                        const float dx = __int_as_float(sl[TK_W_VEL]) * k, dy = __int_as_float(sl[TK_W_VEL + 1]) * k;
-                        s_pbox[tid] = expand_box(__int_as_float(sl[TK_W_BOX]) + dx, __int_as_float(sl[TK_W_BOX + 1]) + dy,
-                                                 __int_as_float(sl[TK_W_BOX + 2]) + dx, __int_as_float(sl[TK_W_BOX + 3]) + dy, prm.expand_f);
+                        const float dx = __int_as_float(sl[TR_W_VEL]) * k, dy = __int_as_float(sl[TR_W_VEL + 1]) * k;
+                        s_pbox[tid] = expand_box(__int_as_float(sl[TR_W_BOX]) + dx, __int_as_float(sl[TR_W_BOX + 1]) + dy,
+                                                 __int_as_float(sl[TR_W_BOX + 2]) + dx, __int_as_float(sl[TR_W_BOX + 3]) + dy, prm.expand_f);
                         st = ST_LIVE;
                     }
                 }
                 s_status[tid] = st;
                 s_slot_row[tid] = -1;
                 s_row_slot[tid] = -1;
-            } else if (tid < TK_SLOTS + TK_ROWS) {
-                const int r = tid - TK_SLOTS;
+            } else if (tid < TR_SLOTS + TK_ROWS) {
+                const int r = tid - TR_SLOTS;
                 if (r < n) s_dbox[r] = expand_box(rows[r * LP_DET_COLS], rows[r * LP_DET_COLS + 1], rows[r * LP_DET_COLS + 2],
                                                   rows[r * LP_DET_COLS + 3], prm.expand_f);
             }
@@ -251,19 +228,19 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
             // ---- 5. matched and unmatched slots ------------------------------------------------------------------------------
             bool ending = false, held = false;
             if (tid < T && s_status[tid] == ST_LIVE) {
-                int* sl = sst + TK_HDR_WORDS + tid * TK_SLOT_WORDS;
+                int* sl = sst + TR_HDR_WORDS + tid * TR_SLOT_WORDS;
                 const int r = s_slot_row[tid];
                 if (r >= 0) {
                     const float* row = rows + r * LP_DET_COLS;
                     const float k = (float)(sl[4] + 1);
-                    const float ox1 = __int_as_float(sl[TK_W_BOX]), oy1 = __int_as_float(sl[TK_W_BOX + 1]);
-                    const float ox2 = __int_as_float(sl[TK_W_BOX + 2]), oy2 = __int_as_float(sl[TK_W_BOX + 3]);
+                    const float ox1 = __int_as_float(sl[TR_W_BOX]), oy1 = __int_as_float(sl[TR_W_BOX + 1]);
+                    const float ox2 = __int_as_float(sl[TR_W_BOX + 2]), oy2 = __int_as_float(sl[TR_W_BOX + 3]);
                     const float nx1 = row[0], ny1 = row[1], nx2 = row[2], ny2 = row[3];
                     const float vx = ((nx1 + nx2) * 0.5f - (ox1 + ox2) * 0.5f) / k;
                     const float vy = ((ny1 + ny2) * 0.5f - (oy1 + oy2) * 0.5f) / k;
-                    sl[TK_W_VEL] = __float_as_int(vx);
-                    sl[TK_W_VEL + 1] = __float_as_int(vy);
-                    for (int c = 0; c < 12; ++c) sl[TK_W_BOX + c] = __float_as_int(row[c]);
+                    sl[TR_W_VEL] = __float_as_int(vx);
+                    sl[TR_W_VEL + 1] = __float_as_int(vy);
+                    for (int c = 0; c < 12; ++c) sl[TR_W_BOX + c] = __float_as_int(row[c]);
                     sl[3] = sl[3] + 1;
                     sl[4] = 0;
                     sl[2] = frame;
@@ -280,7 +257,7 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
             unsigned long long hm = 0;
             if (HOLD) {                                                // (made visible by the barriers of end_marked)
                 hm = __ballot(held);
-                if (tid < TK_SLOTS && lane == 0) s_hcnt[wave] = __popcll(hm);
+                if (tid < TR_SLOTS && lane == 0) s_hcnt[wave] = __popcll(hm);
             }
             end_marked(ending);
             if (HOLD && held) s_hslot[(wave == 1 ? s_hcnt[0] : 0) + __popcll(hm & lt)] = tid;   // (read behind the barriers of step 6)
@@ -325,35 +302,27 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
                 const int st = hslot < T ? s_status[hslot] : ST_EMPTY;
                 if (st == ST_MATCHED || st == ST_NEW) {
                     const float* row = rows + s_slot_row[hslot] * LP_DET_COLS;
-                    float* votes = (float*)(hsl + TK_W_VOTES + head * LP_TRACK_MAX_CLS);
-                    float* total = (float*)(hsl + TK_W_TOTAL + head);
+                    float* votes = (float*)(hsl + TR_W_VOTES + head * LP_TRACK_MAX_CLS);
+                    float* total = (float*)(hsl + TR_W_TOTAL + head);
                     if (st == ST_NEW) {
 #pragma unroll 4
                         for (int c = 0; c < LP_TRACK_MAX_CLS; ++c) votes[c] = 0.f;
                         *total = 0.f;
                         if (head == 0) {
                             hsl[0] = s_id[hslot]; hsl[1] = frame; hsl[2] = frame; hsl[3] = 1; hsl[4] = 0;
-                            hsl[TK_W_VEL] = 0; hsl[TK_W_VEL + 1] = 0;
+                            hsl[TR_W_VEL] = 0; hsl[TR_W_VEL + 1] = 0;
                         }
                         if (head < 4)
-                            for (int c = head; c < 12; c += 4) hsl[TK_W_BOX + c] = __float_as_int(row[c]);
+                            for (int c = head; c < 12; c += 4) hsl[TR_W_BOX + c] = __float_as_int(row[c]);
                     }
                     const float v = row[20 + head], conf = row[12 + head];
                     if (conf > 0.f && v >= 0.f && v < (float)s_ncls[head]) {
                         votes[(int)v] = votes[(int)v] + conf;
                         *total = *total + conf;
                     }
-                    int best;
-                    float share;
-                    read_head(hsl, head, &best, &share);
-                    s_best[tid] = best;
-                    s_share[tid] = share;
+                    track_read_head(hsl, head, s_ncls[head], s_best[tid], s_share[tid]);
                 } else if (HOLD && st == ST_HELD) {                    // a held slot casts no vote: its read as it stands
-                    int best;
-                    float share;
-                    read_head(hsl, head, &best, &share);
-                    s_best[tid] = best;
-                    s_share[tid] = share;
+                    track_read_head(hsl, head, s_ncls[head], s_best[tid], s_share[tid]);
                 }
             }
             __syncthreads();
@@ -368,7 +337,7 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
                 v = rows[i];
                 if (r < n && col >= 12) {
                     const int slot = s_row_slot[r];
-                    if (slot >= 0) v = col < 20 ? s_share[slot * TK_HEADS + col - 12] : (float)s_best[slot * TK_HEADS + col - 20];
+                    if (slot >= 0) v = col < 20 ? s_share[slot * TR_HEADS + col - 12] : (float)s_best[slot * TR_HEADS + col - 20];
                 }
             }
             dout[i] = v;
@@ -392,34 +361,32 @@ __global__ __launch_bounds__(TK_T) void track_kernel(const TkTable tab, const Tk
                 float v = 0.f;
                 if (r - nc < nheld) {
                     const int slot = s_hslot[r - nc];
-                    const int* sl = sst + TK_HDR_WORDS + slot * TK_SLOT_WORDS;
+                    const int* sl = sst + TR_HDR_WORDS + slot * TR_SLOT_WORDS;
                     if (col < 12) {                                    // the products of step 1 of this frame: k = (float)misses
-                        const float d = __int_as_float(sl[TK_W_VEL + (col & 1)]) * (float)sl[4];
-                        v = __int_as_float(sl[TK_W_BOX + col]) + d;
+                        const float d = __int_as_float(sl[TR_W_VEL + (col & 1)]) * (float)sl[4];
+                        v = __int_as_float(sl[TR_W_BOX + col]) + d;
                     } else {
-                        v = col < 20 ? s_share[slot * TK_HEADS + col - 12] : (float)s_best[slot * TK_HEADS + col - 20];
+                        v = col < 20 ? s_share[slot * TR_HEADS + col - 12] : (float)s_best[slot * TR_HEADS + col - 20];
                     }
                 }
                 dh[i] = v;
             }
             for (int r = nc + tid; r < hrows; r += TK_T)
-                hold.tid[(long long)j * hrows + r] = r - nc < nheld ? sst[TK_HDR_WORDS + s_hslot[r - nc] * TK_SLOT_WORDS] : -1;
+                hold.tid[(long long)j * hrows + r] = r - nc < nheld ? sst[TR_HDR_WORDS + s_hslot[r - nc] * TR_SLOT_WORDS] : -1;
             if (tid == 0) hold.count[j] = nc + nheld;
         }
         __syncthreads();                                               // the next frame reuses the LDS tables and reads the state
     }
     if (strm >= 0 && tab.blk_flush[blk]) {                             // flush: every live track ends, in slot order
         bool ending = false;
-        if (tid < TK_SLOTS) {
-            ending = tid < T && sst[TK_HDR_WORDS + tid * TK_SLOT_WORDS + 3] > 0;
+        if (tid < TR_SLOTS) {
+            ending = tid < T && sst[TR_HDR_WORDS + tid * TR_SLOT_WORDS + 3] > 0;
             s_status[tid] = ending ? ST_ENDING : ST_EMPTY;
         }
         end_marked(ending);
     }
     if (tid == 0 && strm >= 0) ended_count[strm] = ended_n;
 }
-
-size_t stream_words(int max_tracks) { return (size_t)TK_HDR_WORDS + (size_t)max_tracks * TK_SLOT_WORDS; }
 
 }  // namespace
 
@@ -429,12 +396,12 @@ using namespace lp;
 
 extern "C" size_t lp_track_state_bytes(int n_streams, int max_tracks) {
     if (n_streams < 1 || max_tracks < 1 || max_tracks > LP_TRACK_MAX_TRACKS) return 0;
-    return (size_t)n_streams * stream_words(max_tracks) * 4;
+    return (size_t)n_streams * (size_t)track_state_stride(max_tracks) * 4;
 }
 
 extern "C" size_t lp_track_dropped_offset(int max_tracks, int stream_index) {
     if (stream_index < 0 || max_tracks < 1 || max_tracks > LP_TRACK_MAX_TRACKS) return (size_t)-1;
-    return ((size_t)stream_index * stream_words(max_tracks) + 2) * 4;
+    return ((size_t)stream_index * (size_t)track_state_stride(max_tracks) + 2) * 4;
 }
 
 extern "C" int lp_track_update(void* state, int n_streams, int max_tracks, const lp_track_params* p, const float* det, const int32_t* count,
@@ -468,9 +435,9 @@ extern "C" int lp_track_update_hold(void* state, int n_streams, int max_tracks, 
     if (!(std::fabs(p->new_thres) <= 3.0e38)) return fail(LP_ERR_ARG, fn + "new_thres must be finite (|new_thres| <= 3e38)");
     if (!(p->expand >= 0.0 && p->expand <= 1.0e6)) return fail(LP_ERR_ARG, fn + "expand must be in [0, 1e6]");
     if (p->max_age < 0) return fail(LP_ERR_ARG, fn + "max_age must be >= 0");
-    for (int h = 0; h < TK_HEADS; ++h)
-        if (p->ncls[h] < 1 || p->ncls[h] > LP_TRACK_MAX_CLS)
-            return fail(LP_ERR_ARG, fn + "ncls of head " + std::to_string(h) + " must be in 1.." + std::to_string(LP_TRACK_MAX_CLS));
+    TkParams prm;
+    why = ncls_fault(p->ncls, prm.ncls);
+    if (!why.empty()) return fail(LP_ERR_ARG, fn + why);
     if (!state || !ended_count || (max_ended > 0 && (!ended_i || !ended_f)) || (B > 0 && (!det || !count || !stream_of || !det_out || !tid)))
         return fail(LP_ERR_ARG, fn + "null pointer");
     if (((uintptr_t)state & 15) != 0) return fail(LP_ERR_ARG, fn + "state must be 16-byte aligned");
@@ -489,15 +456,13 @@ extern "C" int lp_track_update_hold(void* state, int n_streams, int max_tracks, 
     if (int rc = hp ? set_max_lds_once(track_kernel<true>, SORT_LDS_KEYS * 8, attr_hold, "track hold")
                     : set_max_lds_once(track_kernel<false>, SORT_LDS_KEYS * 8, attr, "track")) return rc;
 
-    TkParams prm;
     prm.thr_f = f32_not_above(p->match_thres);
     prm.new_f = f32_not_below(p->new_thres);
     prm.expand_f = (float)p->expand;
     prm.max_age = p->max_age;
-    for (int h = 0; h < TK_HEADS; ++h) prm.ncls[h] = p->ncls[h];
 
     hipStream_t st = (hipStream_t)stream;
-    const long long n_words = (long long)n_streams * max_ended * 12;
+    const long long n_words = (long long)n_streams * max_ended * RM_REC_WORDS;
     {
         const long long n = n_words > n_streams ? n_words : n_streams;
         hipLaunchKernelGGL(track_clear_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ended_count, n_streams, ended_i, ended_f, n_words);
@@ -507,7 +472,7 @@ extern "C" int lp_track_update_hold(void* state, int n_streams, int max_tracks, 
     int n_max = 64;
     while (n_max < max_tracks * rows_cap) n_max <<= 1;
     const size_t lds = (size_t)n_max * 8;
-    const long long sstride = (long long)stream_words(max_tracks);
+    const long long sstride = track_state_stride(max_tracks);
     auto launch = [&](const TkTable& tab, int nblk, int b0) -> int {
         TkHold hold = {};
         if (hp && B > 0) hold = TkHold{hp->min_hits, hp->max_misses, det_hold + (size_t)b0 * hrows * LP_DET_COLS, count_hold + b0,

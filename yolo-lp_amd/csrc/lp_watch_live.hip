@@ -4,13 +4,13 @@
 // yolov6/utils/watch_live.py (LiveWatchNp), which this file matches on every int32 (tests/test_watch_live_gpu.py).
 //
 // Two kernels, one in front of and one behind the unchanged scan of lp_watch.hip; both take one workgroup per stream and read the
-// tracker state as lp_track_update left it (layout: the header comment of lp_track.hip), never writing it.
+// tracker state as lp_track_update left it (layout: lp_streams.h), never writing it.
 // live_gather_kernel, steps 1 to 4 of the rule: thread t < 128 reads slot t's first words (id, first, last, hits; 16 bytes) and its
 //   memo line.  A slot that is not live gets a zero memo line.  A candidate (hits >= min_hits) whose memo holds its id and whose
 //   `last` equals the memo's last_at_lookup cannot have a new key -- votes change only on a match, and a match sets `last` -- so it
 //   is not fresh and its votes are not read; this changes no output byte.  For every other candidate the eight threads
 //   (slot, head) each read one head: the argmax over ncls[p] <= 64 floats, lowest index on a tie, and the share (track_read_head of
-//   lp_track_read.inc, rule 8 of lp_track.hip's read_head to the letter; tests pin the two together).  Thread t packs the key and
+//   lp_track_read.inc: rule 8, the function the tracker's own vote step calls).  Thread t packs the key and
 //   decides `fresh`; the fresh slots are numbered in slot order by ballot and prefix count over the two waves, as track_kernel numbers ending
 //   tracks, and their lines go out in the ended-record layout (lp_read_match.inc).  Lines past the count are zeroed (q_slot -1), and pos[s][t] -- the
 //   query line of slot t, -1 for none -- is left in the workspace for the scatter.
@@ -28,14 +28,8 @@ namespace lp {
 
 namespace {
 
-constexpr int WL_SLOTS = TR_SLOTS;              // 128
-constexpr int WL_HEADS = TR_HEADS;
-constexpr int WL_T = WL_SLOTS * WL_HEADS;       // most threads of a gather workgroup: one per (slot, head)
-// the tracker state: lp_track_read.inc
-constexpr int WL_HDR_WORDS = TR_HDR_WORDS, WL_W_BOX = TR_W_BOX, WL_SLOT_WORDS = TR_SLOT_WORDS;
+constexpr int WL_T = TR_SLOTS * TR_HEADS;       // most threads of a gather workgroup: one per (slot, head)
 constexpr int WL_MEMO_WORDS = 8, WL_LIVE_COLS = 8;
-
-struct LiveNcls { int v[WL_HEADS]; };
 
 struct LiveWs {                                 // carve-up of the caller's workspace, L = n_streams * max_tracks
     int32_t* pos;                               // [L] query line of a slot, -1: none
@@ -59,27 +53,29 @@ LiveWs live_carve(void* base, size_t S, size_t T) {
     return w;
 }
 
-bool live_dims_ok(int n_streams, int max_tracks) {
-    return n_streams >= 1 && max_tracks >= 1 && max_tracks <= LP_TRACK_MAX_TRACKS && (long long)n_streams * max_tracks * RM_REC_WORDS < 0x80000000ll;
+// the dimensions of a call, the query lines within an int32 index
+std::string live_dims_fault(int n_streams, int max_tracks) {
+    return stream_words_fault(n_streams, max_tracks, {(long long)max_tracks * RM_REC_WORDS},
+                              "n_streams * max_tracks * " + std::to_string(RM_REC_WORDS) + " < 2^31");
 }
 
 // grid (n_streams), block (max(128, max_tracks * 8 rounded up to 64))
-__global__ __launch_bounds__(WL_T) void live_gather_kernel(const int* __restrict__ state, int T, long long sstride, const LiveNcls ncls, int min_hits,
+__global__ __launch_bounds__(WL_T) void live_gather_kernel(const int* __restrict__ state, int T, long long sstride, const TrackNcls ncls, int min_hits,
                                                           int32_t* __restrict__ memo, int32_t* __restrict__ q_i, float* __restrict__ q_f,
                                                           int32_t* __restrict__ q_slot, int32_t* __restrict__ q_count, int32_t* __restrict__ pos) {
-    __shared__ int s_need[WL_SLOTS], s_pos[WL_SLOTS], s_best[WL_SLOTS * WL_HEADS];
-    __shared__ float s_share[WL_SLOTS * WL_HEADS];
+    __shared__ int s_need[TR_SLOTS], s_pos[TR_SLOTS], s_best[TR_SLOTS * TR_HEADS];
+    __shared__ float s_share[TR_SLOTS * TR_HEADS];
     __shared__ int s_wcnt[2];
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int* const sst = state + (long long)s * sstride + WL_HDR_WORDS;
+    const int* const sst = state + (long long)s * sstride + TR_HDR_WORDS;
     const long long line0 = (long long)s * T;                          // first slot / query line of the stream; line0 + T <= S * T
     const int hslot = tid >> 3, head = tid & 7;                        // the (slot, head) this thread serves
     // ---- steps 1 and 3: live, candidate, and whether the votes have to be read ------------------------------------------------------
     bool cand = false, need = false;
     int m_id = 0, m_lo = 0, m_hi = 0;
-    if (tid < WL_SLOTS) {
+    if (tid < TR_SLOTS) {
         if (tid < T) {
-            const int4 h = *(const int4*)(sst + (long long)tid * WL_SLOT_WORDS);       // id, first, last, hits
+            const int4 h = *(const int4*)(sst + (long long)tid * TR_SLOT_WORDS);       // id, first, last, hits
             int4* mline = (int4*)(memo + (line0 + tid) * WL_MEMO_WORDS);
             if (h.w > 0) {
                 const int4 m0 = mline[0];
@@ -96,30 +92,22 @@ __global__ __launch_bounds__(WL_T) void live_gather_kernel(const int* __restrict
     __syncthreads();
     // ---- step 2: rule 8, one thread per (slot, head) -------------------------------------------------------------------------------
     if (hslot < T && s_need[hslot]) {
-        int bi;
-        float sh;
-        track_read_head(sst + (long long)hslot * WL_SLOT_WORDS, head, ncls.v[head], bi, sh);
-        s_best[tid] = bi;
-        s_share[tid] = sh;
+        track_read_head(sst + (long long)hslot * TR_SLOT_WORDS, head, ncls.v[head], s_best[tid], s_share[tid]);
     }
     __syncthreads();
     // ---- steps 3 and 4: fresh slots, numbered in slot order ------------------------------------------------------------------------
     bool fresh = false;
     if (need) {
-        unsigned lo = 0, hi = 0;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            lo |= (unsigned)s_best[tid * WL_HEADS + p] << (8 * p);
-            hi |= (unsigned)s_best[tid * WL_HEADS + 4 + p] << (8 * p);
-        }
-        const int4 h = *(const int4*)(sst + (long long)tid * WL_SLOT_WORDS);
+        unsigned lo, hi;
+        pack_key(s_best + tid * TR_HEADS, lo, hi);
+        const int4 h = *(const int4*)(sst + (long long)tid * TR_SLOT_WORDS);
         fresh = m_id != h.x + 1 || m_lo != (int)lo || m_hi != (int)hi;
     }
     const unsigned long long fm = __ballot(fresh);
-    if (tid < WL_SLOTS && lane == 0) s_wcnt[wave] = __popcll(fm);
+    if (tid < TR_SLOTS && lane == 0) s_wcnt[wave] = __popcll(fm);
     __syncthreads();
     const int nfresh = s_wcnt[0] + s_wcnt[1];
-    if (tid < WL_SLOTS) {
+    if (tid < TR_SLOTS) {
         const int j = fresh ? (wave == 1 ? s_wcnt[0] : 0) + __popcll(fm & ((1ull << lane) - 1ull)) : -1;
         s_pos[tid] = j;
         if (tid < T) {
@@ -131,12 +119,8 @@ __global__ __launch_bounds__(WL_T) void live_gather_kernel(const int* __restrict
     if (tid == 0) q_count[s] = nfresh;
     __syncthreads();
     if (hslot < T && s_pos[hslot] >= 0) {                              // the record the track would leave if it ended now
-        const int* sl = sst + (long long)hslot * WL_SLOT_WORDS;
-        int32_t* ri = q_i + (line0 + s_pos[hslot]) * RM_REC_WORDS;
-        float* rf = q_f + (line0 + s_pos[hslot]) * RM_REC_WORDS;
-        ri[RM_W_IDS + head] = s_best[tid];
-        rf[RM_F_SHARES + head] = s_share[tid];
-        if (head < 4) { ri[RM_W_TRACK + head] = sl[head]; rf[RM_F_BOX + head] = __int_as_float(sl[WL_W_BOX + head]); }
+        write_record_share(q_i + (line0 + s_pos[hslot]) * RM_REC_WORDS, q_f + (line0 + s_pos[hslot]) * RM_REC_WORDS,
+                           sst + (long long)hslot * TR_SLOT_WORDS, head, s_best[tid], s_share[tid]);
     }
     for (int w = nfresh * RM_REC_WORDS + tid; w < T * RM_REC_WORDS; w += blockDim.x) {       // the lines past the count
         q_i[line0 * RM_REC_WORDS + w] = 0;
@@ -145,7 +129,7 @@ __global__ __launch_bounds__(WL_T) void live_gather_kernel(const int* __restrict
 }
 
 // grid (n_streams), block (128)
-__global__ __launch_bounds__(WL_SLOTS) void live_scatter_kernel(const int* __restrict__ state, int T, long long sstride,
+__global__ __launch_bounds__(TR_SLOTS) void live_scatter_kernel(const int* __restrict__ state, int T, long long sstride,
                                                                const int32_t* __restrict__ q_i, const int32_t* __restrict__ pos,
                                                                const int32_t* __restrict__ match_i, int32_t* __restrict__ memo,
                                                                int32_t* __restrict__ live_i, const int32_t* __restrict__ match_align,
@@ -154,13 +138,14 @@ __global__ __launch_bounds__(WL_SLOTS) void live_scatter_kernel(const int* __res
     if (t >= T) return;
     const long long line = (long long)s * T + t;
     int align = 0;                                                     // step 8 (live_align != nullptr: lp_watch_live_indel)
-    const int4 h = *(const int4*)(state + (long long)s * sstride + WL_HDR_WORDS + (long long)t * WL_SLOT_WORDS);   // id, first, last, hits
+    const int4 h = *(const int4*)(state + (long long)s * sstride + TR_HDR_WORDS + (long long)t * TR_SLOT_WORDS);   // id, first, last, hits
     int4* mline = (int4*)(memo + line * WL_MEMO_WORDS);
     int4 out0 = make_int4(-1, -1, 0, 0), out1 = make_int4(0, 0, 0, 0);
     const int j = pos[line];
     if (j >= 0) {                                                      // step 6 (a fresh slot is live)
         const int32_t* ri = q_i + ((long long)s * T + j) * RM_REC_WORDS;
         const int4 m = *(const int4*)(match_i + ((long long)s * T + j) * 4);            // entry, mismatches, cost, n_hits
+        // pack_key of lp_track_read.inc, written out: called from here it splits this kernel's load of h (profiles/live_stage_codegen.txt)
         unsigned lo = 0, hi = 0;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
@@ -194,17 +179,17 @@ __global__ __launch_bounds__(WL_SLOTS) void live_scatter_kernel(const int* __res
 using namespace lp;
 
 extern "C" size_t lp_watch_live_state_bytes(int n_streams, int max_tracks) {
-    if (!live_dims_ok(n_streams, max_tracks)) return 0;
+    if (!live_dims_fault(n_streams, max_tracks).empty()) return 0;
     return (size_t)n_streams * max_tracks * WL_MEMO_WORDS * 4;
 }
 
 extern "C" size_t lp_watch_live_workspace_bytes(int n_streams, int max_tracks) {
-    if (!live_dims_ok(n_streams, max_tracks)) return 0;
+    if (!live_dims_fault(n_streams, max_tracks).empty()) return 0;
     return live_carve(nullptr, (size_t)n_streams, (size_t)max_tracks).bytes;
 }
 
 extern "C" size_t lp_watch_live_indel_workspace_bytes(int n_streams, int max_tracks) {
-    if (!live_dims_ok(n_streams, max_tracks)) return 0;
+    if (!live_dims_fault(n_streams, max_tracks).empty()) return 0;
     return live_carve(nullptr, (size_t)n_streams, (size_t)max_tracks).indel_bytes;
 }
 
@@ -213,17 +198,11 @@ static int watch_live_run(const std::string& fn, bool with_indel, const void* tr
                           int min_hits, int32_t* memo, const unsigned char* entries, int n_entries, const unsigned char* confuse,
                           int max_mismatch, int max_cost, int indel, int gap_cost, int32_t* q_i, float* q_f, int32_t* q_slot, int32_t* q_count,
                           int32_t* live_i, int32_t* live_align, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!live_dims_ok(n_streams, max_tracks))
-        return fail(LP_ERR_ARG, fn + "need n_streams >= 1, max_tracks in 1.." + std::to_string(LP_TRACK_MAX_TRACKS) +
-                                    " and n_streams * max_tracks * " + std::to_string(RM_REC_WORDS) + " < 2^31");
-    if (!ncls) return fail(LP_ERR_ARG, fn + "null pointer (ncls)");
-    LiveNcls nc;
-    for (int h = 0; h < WL_HEADS; ++h) {
-        if (ncls[h] < 1 || ncls[h] > LP_TRACK_MAX_CLS)
-            return fail(LP_ERR_ARG, fn + "ncls of head " + std::to_string(h) + " must be in 1.." + std::to_string(LP_TRACK_MAX_CLS));
-        nc.v[h] = ncls[h];
-    }
-    if (min_hits < 1) return fail(LP_ERR_ARG, fn + "min_hits must be >= 1");
+    TrackNcls nc;
+    std::string why = live_dims_fault(n_streams, max_tracks);
+    if (why.empty()) why = ncls_fault(ncls, nc);
+    if (why.empty()) why = min_hits_fault(min_hits);
+    if (!why.empty()) return fail(LP_ERR_ARG, fn + why);
     if (n_entries < 0 || n_entries > LP_WATCH_MAX_ENTRIES)
         return fail(LP_ERR_ARG, fn + "n_entries " + std::to_string(n_entries) + " (need 0.." + std::to_string(LP_WATCH_MAX_ENTRIES) + ")");
     if (const std::string f = match_limits_fault(max_mismatch, max_cost); !f.empty()) return fail(LP_ERR_ARG, fn + f);
@@ -240,7 +219,7 @@ static int watch_live_run(const std::string& fn, bool with_indel, const void* tr
     const size_t ws_bytes = with_indel ? ws.indel_bytes : ws.bytes;
     if (workspace_bytes < ws_bytes)
         return fail(LP_ERR_ARG, fn + "workspace of " + std::to_string(workspace_bytes) + " bytes, need " + std::to_string(ws_bytes));
-    const long long sstride = (long long)WL_HDR_WORDS + (long long)max_tracks * WL_SLOT_WORDS;
+    const long long sstride = track_state_stride(max_tracks);
     {   // no buffer that is written may overlap the state, the list or another one
         const size_t L = (size_t)n_streams * max_tracks;
         const Region reg[] = {{track_state, (size_t)n_streams * (size_t)sstride * 4, false},
@@ -260,7 +239,7 @@ static int watch_live_run(const std::string& fn, bool with_indel, const void* tr
     }
 
     hipStream_t st = (hipStream_t)stream;
-    const int threads = max_tracks * WL_HEADS <= WL_SLOTS ? WL_SLOTS : round_up(max_tracks * WL_HEADS, 64);
+    const int threads = max_tracks * TR_HEADS <= TR_SLOTS ? TR_SLOTS : round_up(max_tracks * TR_HEADS, 64);
     hipLaunchKernelGGL(live_gather_kernel, dim3((unsigned)n_streams), dim3((unsigned)threads), 0, st, (const int*)track_state, max_tracks, sstride, nc,
                        min_hits, memo, q_i, q_f, q_slot, q_count, ws.pos);
     LP_HIP_CHECK(hipGetLastError());
@@ -269,7 +248,7 @@ static int watch_live_run(const std::string& fn, bool with_indel, const void* tr
                             : lp_watch_match(entries, n_entries, confuse, q_i, q_f, q_count, n_streams, max_tracks, max_mismatch, max_cost,
                                              ws.match_i, ws.watch, ws.watch_bytes, stream))
         return rc;
-    hipLaunchKernelGGL(live_scatter_kernel, dim3((unsigned)n_streams), dim3(WL_SLOTS), 0, st, (const int*)track_state, max_tracks, sstride, q_i, ws.pos,
+    hipLaunchKernelGGL(live_scatter_kernel, dim3((unsigned)n_streams), dim3(TR_SLOTS), 0, st, (const int*)track_state, max_tracks, sstride, q_i, ws.pos,
                        ws.match_i, memo, live_i, with_indel ? ws.match_align : nullptr, with_indel ? live_align : nullptr);
     LP_HIP_CHECK(hipGetLastError());
     return LP_OK;

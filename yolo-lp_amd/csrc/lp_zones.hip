@@ -4,7 +4,7 @@
 // outputs and of the memo (tests/test_zones_gpu.py).
 //
 // One kernel, one workgroup of 128 threads per stream, lane t = slot t; the tracker state is read as lp_track_update left it (layout:
-// lp_track_read.inc) and never written.
+// lp_streams.h) and never written; the phases c and d and the close of e are the shared pieces of lp_track_read.inc.
 //   a. the stream's packed geometry (LP_ZONE_MAP_WORDS words) is staged in LDS once;
 //   b. lane t reads slot t's first 16 bytes (id, first, last, hits), its memo line and, if the slot is eligible, its box.  It settles
 //      steps 2 to 5 of the rule in registers: the zones a track that is gone ended in, the two masks of crossed lines, the masks of
@@ -36,8 +36,6 @@ constexpr int ZN_MAP_WORDS = ZN_MAP_VERTS + ZN_ZONES * ZN_VERTS * 2;
 static_assert(ZN_MAP_WORDS == LP_ZONE_MAP_WORDS && ZN_T == 128 && ZN_LINES == 16 && ZN_ZONES == 8, "lp_zones.hip: the packed map of lp_hip.h");
 enum { ZK_CROSS = 1, ZK_ENTER = 2, ZK_LEFT = 3, ZK_DWELL = 4, ZK_ENDED = 5 };
 
-struct ZoneNcls { int v[TR_HEADS]; };
-
 // cross(P, Q, R) = (Qx - Px) * (Ry - Py) - (Qy - Py) * (Rx - Px), every operation rounded on its own
 __device__ __forceinline__ double zcross(double px, double py, double qx, double qy, double rx, double ry) {
     const double a = (qx - px) * (ry - py);
@@ -45,11 +43,7 @@ __device__ __forceinline__ double zcross(double px, double py, double qx, double
     return a - b;
 }
 
-__device__ __forceinline__ bool zfinite(float x, float y) { return fabsf(x) <= 3.4028234663852886e38f && fabsf(y) <= 3.4028234663852886e38f; }
-
 __device__ __forceinline__ int zclamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-__device__ __forceinline__ int zdiff(int a, int b) { return (int)((unsigned)a - (unsigned)b); }      // wraps
 
 __device__ __forceinline__ void zstore_event(int32_t* __restrict__ line, int kind, int index, int id, int slot, int frame, int value, int axb, int ayb,
                                              int klo, int khi, int hits) {
@@ -60,7 +54,7 @@ __device__ __forceinline__ void zstore_event(int32_t* __restrict__ line, int kin
 }
 
 // grid (n_streams), block (128)
-__global__ __launch_bounds__(ZN_T) void zone_kernel(const int* __restrict__ state, int T, long long sstride, const ZoneNcls ncls,
+__global__ __launch_bounds__(ZN_T) void zone_kernel(const int* __restrict__ state, int T, long long sstride, const TrackNcls ncls,
                                                     const int* __restrict__ map, int min_hits, int32_t* __restrict__ memo,
                                                     int32_t* __restrict__ zone_ev, int32_t* __restrict__ zone_count, int max_events,
                                                     int32_t* __restrict__ zone_occ, int32_t* __restrict__ zone_totals) {
@@ -108,7 +102,7 @@ __global__ __launch_bounds__(ZN_T) void zone_kernel(const int* __restrict__ stat
             const float4 box = *(const float4*)(sl + TR_W_BOX);
             const float ax = (box.x + box.z) * 0.5f, ay = (box.y + box.w) * 0.5f;
             axb = __float_as_int(ax); ayb = __float_as_int(ay);
-            const bool fin = zfinite(ax, ay);
+            const bool fin = finite_pair(ax, ay);
             const double px = (double)ax, py = (double)ay;
             unsigned old_inside = 0, alerted = 0, inside = 0;
             if (have) {
@@ -117,7 +111,7 @@ __global__ __launch_bounds__(ZN_T) void zone_kernel(const int* __restrict__ stat
 #pragma unroll
                 for (int z = 0; z < ZN_ZONES; ++z) enter[z] = m_enter[z];
                 const float ox = __int_as_float(m0.z), oy = __int_as_float(m0.w);
-                if (fin && zfinite(ox, oy)) {                                           // 4: the lines
+                if (fin && finite_pair(ox, oy)) {                                       // 4: the lines
                     const double p0x = (double)ox, p0y = (double)oy;
                     for (int l = 0; l < nl; ++l) {
                         const float* g = (const float*)(s_map + ZN_MAP_LINES + 4 * l);
@@ -160,7 +154,7 @@ __global__ __launch_bounds__(ZN_T) void zone_kernel(const int* __restrict__ stat
                         left |= bit;
                     }
                     const int dwell = s_map[ZN_MAP_ZHDR + 4 * z + 1];
-                    if ((inside & bit) && dwell > 0 && !(alerted & bit) && zdiff(now, enter[z]) >= dwell) {
+                    if ((inside & bit) && dwell > 0 && !(alerted & bit) && wrap_diff(now, enter[z]) >= dwell) {
                         alert |= bit;
                         alerted |= bit;
                     }
@@ -179,45 +173,27 @@ __global__ __launch_bounds__(ZN_T) void zone_kernel(const int* __restrict__ stat
     const bool need = (up | down | entered | left | alert) != 0;
     s_need[tid] = need ? 1 : 0;
     // ---- d. (first half) the events numbered in slot order -----------------------------------------------------------------------
-    int incl = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int u = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += u;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
+    const int incl = wave_inclusive_sum(cnt, lane, wave, s_wsum);
     __syncthreads();
     // ---- c. rule 8 for the slots that emit a kind 1 to 4 event ----------------------------------------------------------------------
-    for (int i = tid; i < T * TR_HEADS; i += ZN_T) {
-        const int slot = i >> 3, head = i & 7;
-        if (s_need[slot]) {
-            int bi;
-            float sh;
-            track_read_head(hdr + TR_HDR_WORDS + (long long)slot * TR_SLOT_WORDS, head, ncls.v[head], bi, sh);
-            s_best[i] = bi;
-        }
-    }
+    read_needed_heads<ZN_T>(hdr + TR_HDR_WORDS, T, ncls, s_need, s_best);
     __syncthreads();
     // ---- d. the event lines, written by their lane ---------------------------------------------------------------------------------
     const int total = s_wsum[0] + s_wsum[1];
     int32_t* const ev = zone_ev + (long long)s * max_events * ZN_EV_COLS;                // line k < max_events only
-    int k = (wave == 1 ? s_wsum[0] : 0) + incl - cnt;
+    int k = events_before(incl, cnt, wave, s_wsum);
     if (cnt > 0) {
         for (unsigned m = (unsigned)gone_mask; m; m &= m - 1) {
             const int z = __ffs(m) - 1;
             int ef = 0;
 #pragma unroll
             for (int q = 0; q < ZN_ZONES; ++q) ef = q == z ? gone_enter[q] : ef;
-            if (k < max_events) zstore_event(ev + (long long)k * ZN_EV_COLS, ZK_ENDED, z, gone_id, tid, gone_last, zdiff(gone_last, ef), gone_ax, gone_ay, 0, 0, 0);
+            if (k < max_events) zstore_event(ev + (long long)k * ZN_EV_COLS, ZK_ENDED, z, gone_id, tid, gone_last, wrap_diff(gone_last, ef), gone_ax, gone_ay, 0, 0, 0);
             ++k;
         }
         if (need) {
-            unsigned klo = 0, khi = 0;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                klo |= (unsigned)s_best[tid * TR_HEADS + p] << (8 * p);
-                khi |= (unsigned)s_best[tid * TR_HEADS + 4 + p] << (8 * p);
-            }
+            unsigned klo, khi;
+            pack_key(s_best + tid * TR_HEADS, klo, khi);
             for (int l = 0; l < ZN_LINES; ++l) {
                 const int dir = (int)((up >> l) & 1u) - (int)((down >> l) & 1u);
                 if (dir != 0) {
@@ -231,21 +207,20 @@ __global__ __launch_bounds__(ZN_T) void zone_kernel(const int* __restrict__ stat
                 if ((entered | left) & bit) {
                     const bool in = (entered & bit) != 0;
                     if (k < max_events)
-                        zstore_event(ev + (long long)k * ZN_EV_COLS, in ? ZK_ENTER : ZK_LEFT, z, h.x, tid, h.z, in ? 0 : zdiff(h.z, enter[z]), axb, ayb, (int)klo,
+                        zstore_event(ev + (long long)k * ZN_EV_COLS, in ? ZK_ENTER : ZK_LEFT, z, h.x, tid, h.z, in ? 0 : wrap_diff(h.z, enter[z]), axb, ayb, (int)klo,
                                      (int)khi, h.w);
                     ++k;
                 }
                 if (alert & bit) {
                     if (k < max_events)
-                        zstore_event(ev + (long long)k * ZN_EV_COLS, ZK_DWELL, z, h.x, tid, h.z, zdiff(now, enter[z]), axb, ayb, (int)klo, (int)khi, h.w);
+                        zstore_event(ev + (long long)k * ZN_EV_COLS, ZK_DWELL, z, h.x, tid, h.z, wrap_diff(now, enter[z]), axb, ayb, (int)klo, (int)khi, h.w);
                     ++k;
                 }
             }
         }
     }
-    for (long long w = (long long)total * ZN_EV_COLS + tid; w < (long long)max_events * ZN_EV_COLS; w += ZN_T) ev[w] = 0;   // total >= 0
     // ---- e. the count, the occupancy, the totals ------------------------------------------------------------------------------------
-    if (tid == 0) zone_count[s] = total;
+    close_event_list<ZN_T, ZN_EV_COLS>(ev, total, max_events, zone_count + s);
     if (tid < ZN_ZONES) zone_occ[(long long)s * ZN_ZONES + tid] = s_occ[tid];
     if (tid < 2 * ZN_LINES) {
         int32_t* const row = mbase + (long long)(T + (tid >> 4)) * ZN_MEMO_WORDS + (tid & 15);
@@ -255,10 +230,9 @@ __global__ __launch_bounds__(ZN_T) void zone_kernel(const int* __restrict__ stat
     }
 }
 
-bool zone_dims_ok(int n_streams, int max_tracks) {
-    return n_streams >= 1 && max_tracks >= 1 && max_tracks <= LP_TRACK_MAX_TRACKS &&
-           (long long)n_streams * ((long long)TR_HDR_WORDS + (long long)max_tracks * TR_SLOT_WORDS) < 0x80000000ll &&
-           (long long)n_streams * ZN_MAP_WORDS < 0x80000000ll;
+// the dimensions of a call, the state and the map within an int32 index
+std::string zone_dims_fault(int n_streams, int max_tracks) {
+    return stream_words_fault(n_streams, max_tracks, {track_state_stride(max_tracks), ZN_MAP_WORDS}, "a state and a map of fewer than 2^31 words");
 }
 
 }  // namespace
@@ -268,7 +242,7 @@ bool zone_dims_ok(int n_streams, int max_tracks) {
 using namespace lp;
 
 extern "C" size_t lp_zone_state_bytes(int n_streams, int max_tracks) {
-    if (!zone_dims_ok(n_streams, max_tracks)) return 0;
+    if (!zone_dims_fault(n_streams, max_tracks).empty()) return 0;
     return (size_t)n_streams * (size_t)(max_tracks + 2) * ZN_MEMO_WORDS * 4;
 }
 
@@ -276,25 +250,18 @@ extern "C" int lp_zone_update(const void* track_state, int n_streams, int max_tr
                               int32_t* memo, int32_t* zone_ev, int32_t* zone_count, int max_events, int32_t* zone_occ, int32_t* zone_totals,
                               void* stream) {
     const std::string fn = "lp_zone_update: ";
-    if (!zone_dims_ok(n_streams, max_tracks))
-        return fail(LP_ERR_ARG, fn + "need n_streams >= 1, max_tracks in 1.." + std::to_string(LP_TRACK_MAX_TRACKS) +
-                                    " and a state and a map of fewer than 2^31 words");
-    if (max_events < 0 || (long long)n_streams * max_events * ZN_EV_COLS >= 0x80000000ll)
-        return fail(LP_ERR_ARG, fn + "need max_events >= 0 and n_streams * max_events * 12 < 2^31");
-    if (!ncls) return fail(LP_ERR_ARG, fn + "null pointer (ncls)");
-    ZoneNcls nc;
-    for (int h = 0; h < TR_HEADS; ++h) {
-        if (ncls[h] < 1 || ncls[h] > LP_TRACK_MAX_CLS)
-            return fail(LP_ERR_ARG, fn + "ncls of head " + std::to_string(h) + " must be in 1.." + std::to_string(LP_TRACK_MAX_CLS));
-        nc.v[h] = ncls[h];
-    }
-    if (min_hits < 1) return fail(LP_ERR_ARG, fn + "min_hits must be >= 1");
+    TrackNcls nc;
+    std::string why = zone_dims_fault(n_streams, max_tracks);
+    if (why.empty()) why = max_events_fault(n_streams, max_events, ZN_EV_COLS);
+    if (why.empty()) why = ncls_fault(ncls, nc);
+    if (why.empty()) why = min_hits_fault(min_hits);
+    if (!why.empty()) return fail(LP_ERR_ARG, fn + why);
     if (!track_state || !zone_map || !memo || (max_events > 0 && !zone_ev) || !zone_count || !zone_occ || !zone_totals)
         return fail(LP_ERR_ARG, fn + "null pointer");
     if ((((uintptr_t)track_state | (uintptr_t)zone_map | (uintptr_t)memo | (uintptr_t)zone_ev | (uintptr_t)zone_count | (uintptr_t)zone_occ |
           (uintptr_t)zone_totals) & 15) != 0)
         return fail(LP_ERR_ARG, fn + "the tracker state, the map, the memo and the four outputs must be 16-byte aligned");
-    const long long sstride = (long long)TR_HDR_WORDS + (long long)max_tracks * TR_SLOT_WORDS;
+    const long long sstride = track_state_stride(max_tracks);
     {   // no buffer that is written may overlap the state, the map or another one
         const Region reg[] = {{track_state, (size_t)n_streams * (size_t)sstride * 4, false},
                               {zone_map, (size_t)n_streams * ZN_MAP_WORDS * 4, false},

@@ -31,7 +31,28 @@ def _zero_streams(state, n_streams, streams):
             st[int(s)].zero_()
 
 
-class ZoneMap:
+def _max_events(max_events, default):
+    """The checked ``max_events`` of ``enable_zones`` / ``enable_speed`` (None: ``default``)."""
+    if max_events is not None and int(max_events) < 0:
+        raise ValueError('max_events must be >= 0')
+    return default if max_events is None else int(max_events)
+
+
+class _PackedMap:
+    """What ``ZoneMap`` and ``GroundPlane`` are: ``ref``, the numpy form of a per-stream map, checked on the host (``host``: the names of
+    its copies kept here), and its packed words on the device (``kind``, ``words``: its name in the messages, its words in lp_hip.h)."""
+
+    def __init__(self, ref, host, check_packed, kind, words, device):
+        self.n_streams, self.packed_np = ref.n_streams, ref.packed
+        self.__dict__.update((name, getattr(ref, name)) for name in host)
+        if self.packed_np.shape[1] != words:
+            raise RuntimeError('the packed %s map and lp_hip.h disagree' % kind)
+        check_packed(self.packed_np)
+        self.device = _cuda_device('cuda' if device is None else device, '%s lives on a GPU (%sNp is the CPU form)' % ((type(self).__name__,) * 2))
+        self.packed = torch.from_numpy(self.packed_np).to(self.device)
+
+
+class ZoneMap(_PackedMap):
     """The lines and zones of ``n_streams`` streams on the device (lp_zone_update; ``yolov6.utils.zones`` states the rule and the
     packed layout): the constructor of ``zones.ZoneMapNp`` -- ``lines``: per stream a list of (x1, y1, x2, y2); ``zones``: per stream
     a list of (vertices [n, 2], min_dwell) -- validated on the host and uploaded once; a changed map is a new object.  ``lines_np`` /
@@ -39,16 +60,10 @@ class ZoneMap:
 
     def __init__(self, n_streams, lines=None, zones=None, device=None):
         from yolov6.utils.zones import ZoneMapNp, check_packed
-        ref = ZoneMapNp(n_streams, lines, zones)
-        self.n_streams, self.lines_np, self.zones_np, self.packed_np = ref.n_streams, ref.lines_np, ref.zones_np, ref.packed
-        if self.packed_np.shape[1] != abi.LP_ZONE_MAP_WORDS:
-            raise RuntimeError('the packed zone map and lp_hip.h disagree')
-        check_packed(self.packed_np)
-        self.device = _cuda_device('cuda' if device is None else device, 'ZoneMap lives on a GPU (ZoneMapNp is the CPU form)')
-        self.packed = torch.from_numpy(self.packed_np).to(self.device)
+        super().__init__(ZoneMapNp(n_streams, lines, zones), ('lines_np', 'zones_np'), check_packed, 'zone', abi.LP_ZONE_MAP_WORDS, device)
 
 
-class GroundPlane:
+class GroundPlane(_PackedMap):
     """The calibrated plane of each of ``n_streams`` streams on the device (lp_speed_update; ``yolov6.utils.speed`` states the rule and
     the packed layout): the constructor of ``speed.GroundPlaneNp`` -- ``planes``: per stream None or a dict with ``H`` (3 x 3, frame
     pixels -> metres on the plane the plates move in: calibrate at plate height) and optionally ``period_us``, ``limit_mm_s``,
@@ -57,13 +72,7 @@ class GroundPlane:
 
     def __init__(self, n_streams, planes=None, device=None):
         from yolov6.utils.speed import GroundPlaneNp, check_packed
-        ref = GroundPlaneNp(n_streams, planes)
-        self.n_streams, self.planes_np, self.packed_np = ref.n_streams, ref.planes_np, ref.packed
-        if self.packed_np.shape[1] != abi.LP_SPEED_MAP_WORDS:
-            raise RuntimeError('the packed ground map and lp_hip.h disagree')
-        check_packed(self.packed_np)
-        self.device = _cuda_device('cuda' if device is None else device, 'GroundPlane lives on a GPU (GroundPlaneNp is the CPU form)')
-        self.packed = torch.from_numpy(self.packed_np).to(self.device)
+        super().__init__(GroundPlaneNp(n_streams, planes), ('planes_np',), check_packed, 'ground', abi.LP_SPEED_MAP_WORDS, device)
 
 
 class PlateTracker:
@@ -82,7 +91,8 @@ class PlateTracker:
         self.n_streams, self.max_tracks, self.max_age = int(n_streams), int(max_tracks), int(max_age)
         self.ncls = track.ncls_of(ncls)
         self.device = _cuda_device('cuda' if device is None else device, 'PlateTracker runs on a GPU (PlateTrackerNp is the CPU form)')
-        self._params = abi.TrackParams(float(match_thres), float(new_thres), float(expand), self.max_age, (ctypes.c_int * 8)(*self.ncls))
+        self._ncls = (ctypes.c_int * 8)(*self.ncls)                     # what every entry point behind the tracker takes
+        self._params = abi.TrackParams(float(match_thres), float(new_thres), float(expand), self.max_age, self._ncls)
         lib = abi.load()
         self._words = lib.lp_track_state_bytes(1, self.max_tracks) // 4
         self.state = torch.zeros(self.n_streams * self._words, dtype=torch.int32, device=self.device)
@@ -195,6 +205,13 @@ class PlateTracker:
             self._speed_update()
         return out
 
+    def _live_stage_args(self, fn, packed_map, cls, min_hits):
+        """The opening of ``enable_zones`` and ``enable_speed``: the map is a ``cls`` of this device and ``n_streams``; the checked min_hits."""
+        from yolov6.utils import watch_live
+        if not isinstance(packed_map, cls) or packed_map.device != self.device or packed_map.n_streams != self.n_streams:
+            raise ValueError('%s needs a %s of %d streams on the tracker\'s device %s' % (fn, cls.__name__, self.n_streams, self.device))
+        return watch_live.check_min_hits(min_hits)
+
     # ---- the speed of the live tracks on a calibrated plane (lp_speed_update; yolov6/utils/speed.py states the rule) ---------------
     def enable_speed(self, ground, min_hits=1, confirm=2, max_events=None, clock=False):
         """From now on every ``update`` / ``update_with_shots`` / ``flush_all*`` also enqueues, at its end on the same stream (behind
@@ -209,21 +226,17 @@ class PlateTracker:
         call; else it is the frame counter times the plane's period.  Persistent buffers, no host read, no allocation per call.
         Returns, state and every other buffer are what they are without it.  Calling it again zeroes the memo;
         ``enable_speed(None)`` turns it off.  ``PlateTrackerNp.enable_speed`` is the same on the CPU, on every int32."""
-        from yolov6.utils import speed, watch_live
+        from yolov6.utils import speed
         self.last_speed = None
         if ground is None:
             self._speed = None
             return
-        if not isinstance(ground, GroundPlane) or ground.device != self.device or ground.n_streams != self.n_streams:
-            raise ValueError('enable_speed needs a GroundPlane of %d streams on the tracker\'s device %s' % (self.n_streams, self.device))
-        min_hits, confirm = watch_live.check_min_hits(min_hits), speed.check_confirm(confirm)
-        max_events = self.max_tracks if max_events is None else int(max_events)
-        if max_events < 0:
-            raise ValueError('max_events must be >= 0')
+        min_hits = self._live_stage_args('enable_speed', ground, GroundPlane, min_hits)
+        confirm, max_events = speed.check_confirm(confirm), _max_events(max_events, self.max_tracks)
         S, T, lib = self.n_streams, self.max_tracks, abi.load()
         i32 = dict(dtype=torch.int32, device=self.device)
         self._speed = dict(
-            ground=ground, clock=self.speed_clock if clock else None, min_hits=min_hits, confirm=confirm, max_events=max_events, ncls=(ctypes.c_int * 8)(*self.ncls),
+            ground=ground, clock=self.speed_clock if clock else None, min_hits=min_hits, confirm=confirm, max_events=max_events,
             memo=torch.zeros(lib.lp_speed_state_bytes(S, T) // 4, **i32).view(S, T, abi.LP_SPEED_MEMO_WORDS),
             rows=torch.empty(S, T, 8, **i32), ev=torch.empty(S, max_events, 12, **i32), count=torch.empty(S, **i32))
 
@@ -235,7 +248,7 @@ class PlateTracker:
         """Enqueue lp_speed_update on the state as it stands."""
         sp = self._speed
         with torch.cuda.device(self.device):
-            abi.check(abi.load().lp_speed_update(_dptr(self.state), self.n_streams, self.max_tracks, sp['ncls'], _dptr(sp['ground'].packed),
+            abi.check(abi.load().lp_speed_update(_dptr(self.state), self.n_streams, self.max_tracks, self._ncls, _dptr(sp['ground'].packed),
                                                  _dptr(sp['clock']), sp['min_hits'], sp['confirm'], _dptr(sp['memo']), _dptr(sp['rows']),
                                                  _dptr(sp['ev']), _dptr(sp['count']), sp['max_events'], _stream_ptr(self.device)),
                       'lp_speed_update')
@@ -253,21 +266,15 @@ class PlateTracker:
         per line since the memo was zeroed.  Persistent buffers, no host read, no allocation per call.  Returns, state and every
         other buffer are what they are without it.  Calling it again zeroes the memo and the totals; ``enable_zones(None)`` turns it
         off.  ``PlateTrackerNp.enable_zones`` is the same on the CPU, on every int32."""
-        from yolov6.utils import watch_live
         self.last_zone = None
         if zone_map is None:
             self._zones = None
             return
-        if not isinstance(zone_map, ZoneMap) or zone_map.device != self.device or zone_map.n_streams != self.n_streams:
-            raise ValueError('enable_zones needs a ZoneMap of %d streams on the tracker\'s device %s' % (self.n_streams, self.device))
-        min_hits = watch_live.check_min_hits(min_hits)
-        max_events = 2 * self.max_tracks if max_events is None else int(max_events)
-        if max_events < 0:
-            raise ValueError('max_events must be >= 0')
+        min_hits, max_events = self._live_stage_args('enable_zones', zone_map, ZoneMap, min_hits), _max_events(max_events, 2 * self.max_tracks)
         S, T, lib = self.n_streams, self.max_tracks, abi.load()
         i32 = dict(dtype=torch.int32, device=self.device)
         self._zones = dict(
-            zone_map=zone_map, min_hits=min_hits, max_events=max_events, ncls=(ctypes.c_int * 8)(*self.ncls),
+            zone_map=zone_map, min_hits=min_hits, max_events=max_events,
             memo=torch.zeros(lib.lp_zone_state_bytes(S, T) // 4, **i32).view(S, T + 2, 16),
             ev=torch.empty(S, max_events, 12, **i32), count=torch.empty(S, **i32), occ=torch.empty(S, 8, **i32),
             totals=torch.empty(S, 2, 16, **i32))
@@ -282,7 +289,7 @@ class PlateTracker:
         """Enqueue lp_zone_update on the state as it stands."""
         zn = self._zones
         with torch.cuda.device(self.device):
-            abi.check(abi.load().lp_zone_update(_dptr(self.state), self.n_streams, self.max_tracks, zn['ncls'], _dptr(zn['zone_map'].packed),
+            abi.check(abi.load().lp_zone_update(_dptr(self.state), self.n_streams, self.max_tracks, self._ncls, _dptr(zn['zone_map'].packed),
                                                 zn['min_hits'], _dptr(zn['memo']), _dptr(zn['ev']), _dptr(zn['count']), zn['max_events'],
                                                 _dptr(zn['occ']), _dptr(zn['totals']), _stream_ptr(self.device)), 'lp_zone_update')
         self.last_zone = (zn['ev'], zn['count'], zn['occ'], zn['totals'])
@@ -349,7 +356,7 @@ class PlateTracker:
         S, T, dev, lib = self.n_streams, self.max_tracks, self.device, abi.load()
         i32 = dict(dtype=torch.int32, device=dev)
         self._live = dict(
-            watchlist=watchlist, min_hits=min_hits, limits=(mm, mc), ncls=(ctypes.c_int * 8)(*self.ncls),
+            watchlist=watchlist, min_hits=min_hits, limits=(mm, mc),
             memo=torch.zeros(lib.lp_watch_live_state_bytes(S, T) // 4, **i32).view(S, T, 8),
             live_i=torch.empty(S, T, 8, **i32), q_i=torch.empty(S, T, 12, **i32),
             q_f=torch.empty(S, T, 12, dtype=torch.float32, device=dev), q_slot=torch.empty(S, T, **i32), q_count=torch.empty(S, **i32),
@@ -364,27 +371,20 @@ class PlateTracker:
         return None if self._live is None else self._live['memo']
 
     def _live_watch(self):
-        """Enqueue lp_watch_live on the state as it stands."""
-        lw = self._live
-        wl, ws = lw['watchlist'], lw['ws']
-        if lw['indel'][0]:
-            with torch.cuda.device(self.device):
-                abi.check(abi.load().lp_watch_live_indel(_dptr(self.state), self.n_streams, self.max_tracks, lw['ncls'], lw['min_hits'],
-                                                         _dptr(lw['memo']), _dptr(wl.entries), wl.n, _dptr(wl.confuse), lw['limits'][0],
-                                                         lw['limits'][1], lw['indel'][0], lw['indel'][1], _dptr(lw['q_i']), _dptr(lw['q_f']),
-                                                         _dptr(lw['q_slot']), _dptr(lw['q_count']), _dptr(lw['live_i']), _dptr(lw['align']),
-                                                         *_aligned_span(ws), _stream_ptr(self.device)), 'lp_watch_live_indel')
-            self.last_live = lw['live_i']
-            self.last_live_reads = (lw['q_i'], lw['q_f'], lw['q_slot'], lw['q_count'])
-            self.last_live_align = lw['align']
-            return
+        """Enqueue lp_watch_live (lp_watch_live_indel after ``indel=1``) on the state as it stands."""
+        lw, lib = self._live, abi.load()
+        wl, (indel, gap) = lw['watchlist'], lw['indel']
+        reads = (lw['q_i'], lw['q_f'], lw['q_slot'], lw['q_count'])
+        head = (_dptr(self.state), self.n_streams, self.max_tracks, self._ncls, lw['min_hits'], _dptr(lw['memo']), _dptr(wl.entries), wl.n,
+                _dptr(wl.confuse)) + lw['limits']
+        outs = tuple(_dptr(t) for t in reads) + (_dptr(lw['live_i']),)
+        tail = _aligned_span(lw['ws']) + (_stream_ptr(self.device),)
         with torch.cuda.device(self.device):
-            abi.check(abi.load().lp_watch_live(_dptr(self.state), self.n_streams, self.max_tracks, lw['ncls'], lw['min_hits'], _dptr(lw['memo']),
-                                               _dptr(wl.entries), wl.n, _dptr(wl.confuse), lw['limits'][0], lw['limits'][1], _dptr(lw['q_i']),
-                                               _dptr(lw['q_f']), _dptr(lw['q_slot']), _dptr(lw['q_count']), _dptr(lw['live_i']),
-                                               *_aligned_span(ws), _stream_ptr(self.device)), 'lp_watch_live')
-        self.last_live = lw['live_i']
-        self.last_live_reads = (lw['q_i'], lw['q_f'], lw['q_slot'], lw['q_count'])
+            if indel:
+                abi.check(lib.lp_watch_live_indel(*head, indel, gap, *outs, _dptr(lw['align']), *tail), 'lp_watch_live_indel')
+            else:
+                abi.check(lib.lp_watch_live(*head, *outs, *tail), 'lp_watch_live')
+        self.last_live, self.last_live_reads, self.last_live_align = lw['live_i'], reads, lw['align']      # (align: None without indel)
 
     # ---- the ended reads looked up in a watchlist (lp_watch_match; yolov6/utils/watch.py states the rule) ----------------------
     def enable_watch(self, watchlist, max_mismatch=1, max_cost=None, indel=0, gap_cost=None):
